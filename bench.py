@@ -6,6 +6,7 @@ COLLECT+CLUSTER; SV signatures/sec clustered).
     python bench.py --workload c2                                          # configs[2] stand-in: HiFi profile, full SV-type set
     python bench.py --workload c4 --partition-max-distance 20000           # configs[4] stand-in: 60x CLR profile, large partitions
     python bench.py --bam reads.bam --fasta ref.fa                         # a real coordinate-sorted BAM (configs[2]-[4] proper)
+    python bench.py --steps 20 --warmup 5 --dump-outputs DIR               # + the tables the last timed step left for its caller as DIR/<name>.npy (dump_outputs)
     python bench.py --scaling strong [--workload c3 --scale 0.2]           # ONE whole-genome batch sharded by contig ownership (configs[3]'s shape): total work fixed,
                                                                            # N=1 is the whole batch; under torchrun with --gpus N: the strong-scaling line + fabric accounting
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -139,6 +140,54 @@ def cpu_baseline(batch, g_off, genome, params, eng=None, budget_s=20.0, parity_r
 def _granted_cpus():
     from svim_amd.harness import effective_cpus
     return effective_cpus()
+
+
+# --dump-outputs: no array holds more than this many elements, which keeps the files of any workload under 64 MB in all (at most 42 arrays of at most 8 bytes per element)
+DUMP_MAX_ELEMENTS = 180_000
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, eng):
+    """--dump-outputs: what the last timed step left for its caller - the signature table and the BND-side table of svx_collect, the cluster table of svx_cluster,
+    as fetch_signatures(0), fetch_signatures(1) and fetch_clusters() return them - as <directory>/<table>_<column>.npy.  Integer columns go out as float64 (exact: they
+    hold at most 32 bits; the 64-bit signature key as its two halves), 8-bit columns as float32.  An array of more than DUMP_MAX_ELEMENTS elements is represented by that
+    many of them, at indices drawn once from a fixed seed and the array's length: the columns of one table share their rows, and two builds that compute the same
+    tables write the same files.  counts.npy holds the full lengths; a table without rows (the BND sides of a workload without split reads across contigs) and a
+    column without elements get no files.  The tables say NaN for the standard deviations of a one-member cluster: the files say -1, so that equal files compare equal."""
+    from svim_amd import _abi
+    os.makedirs(directory, exist_ok=True)
+    sig, bnd, ct = eng.fetch_signatures(0), eng.fetch_signatures(1), eng.fetch_clusters()
+    arrays = {"counts": np.array([sig.n, int(sig.seq_off[sig.n]), bnd.n, int(bnd.seq_off[bnd.n]), ct.n, ct.n_members], dtype=np.int64),
+              "clusters_type_count": np.array(ct.type_count, dtype=np.int64)}
+    for name, t in (("signatures", sig), ("bnd_sides", bnd)):
+        if t.n == 0:
+            continue
+        arrays[name + "_key_hi"] = t.key >> np.uint64(32)
+        arrays[name + "_key_lo"] = t.key & np.uint64(0xffffffff)
+        for k in _abi.SIG_DTYPES:
+            if k != "key":
+                arrays["%s_%s" % (name, k)] = getattr(t, k)
+        arrays[name + "_seq_off"] = t.seq_off
+        arrays[name + "_seq"] = t.seq[:int(t.seq_off[t.n])]
+    if ct.n:
+        for k in _abi.CLU_DTYPES:
+            arrays["clusters_" + k] = getattr(ct, k)[:ct.n]
+        arrays["clusters_member_off"] = ct.member_off
+        arrays["clusters_members"] = ct.members[:ct.n_members]
+    total = files = 0
+    for name, a in arrays.items():
+        if a.size == 0:
+            continue
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a[np.sort(np.random.default_rng([20240, a.size]).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        a = a.astype(np.float32 if a.dtype.itemsize == 1 else np.float64)
+        path = os.path.join(directory, name + ".npy")
+        np.save(path, np.where(np.isnan(a), a.dtype.type(-1), a))
+        total += os.path.getsize(path)
+        files += 1
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs wrote %d bytes to %s: more than the %d it may" % (total, directory, DUMP_MAX_BYTES))
+    return {"directory": directory, "files": files, "bytes": total}
 
 
 def load_profile_json(name):
@@ -316,6 +365,8 @@ def main():
     ap.add_argument("--fasta", default=None)
     ap.add_argument("--foreign-frac", type=float, default=0.0, help="--gpus N, c2 / c4: this fraction of the cross-contig split-read segments points at a contig of "
                     "ANOTHER rank, so that BND signatures owned by other ranks (foreign rows) cross the fabric in the timed step")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the tables the last of them left for its caller (signatures, "
+                    "BND sides, clusters) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; the synthetic workloads on one rank")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
     ap.add_argument("--end-to-end-child", action="store_true", help=argparse.SUPPRESS)
@@ -324,6 +375,11 @@ def main():
     ap.add_argument("--e2e-chunk-mb", type=int, default=2048, help="end_to_end: inflated MB per chunk of the device reader on the headline file")
     ap.add_argument("--resident", type=float, default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and (args.bam or args.scaling == "strong" or args.workload == "c3" or int(os.environ.get("WORLD_SIZE", "1")) > 1 or
+                              os.environ.get("SVX_BENCH_FORCE_DIST") == "1"):
+        ap.error("--dump-outputs: only with the weak-scaling synthetic workloads (c1, c2, c4) on one rank")
 
     # a GPU fault must end the run, not write a multi-GB GPU core dump first
     os.environ.setdefault("HSA_DISABLE_COREDUMP_ON_EXCEPTION", "1")
@@ -505,6 +561,7 @@ def main():
     else:
         strong_block = None
         tot_used, tot_sig, tot_ops = st["n_rec_used"], st["n_sig"], st["n_ops"]
+        dumped = dump_outputs(args.dump_outputs, eng) if args.dump_outputs else None         # before anything below calls the engine again
     if rank != 0:
         return
     ms_per_step = 1e3 * elapsed / args.steps
@@ -600,6 +657,8 @@ def main():
         "roofline": roofline_edit if roofline_edit is not None else roofline_scan, "roofline_scan": roofline_scan, "roofline_edit": roofline_edit,
         "kernels": kernels, "synth_seconds": t_gen,
     }
+    if args.dump_outputs:
+        out["dumped_outputs"] = dumped
     if use_dist:
         out["strong_scaling"] = strong_block
         res = last.get("res")

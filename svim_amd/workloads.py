@@ -8,7 +8,7 @@
                     (src/svim/SVIM_inter.py:58-300)
     c3  configs[3]  whole-genome ONT profile: 47 contigs with hg38's names and length ratios (header order chr1..chr22, X, Y, M, then alt / random /
                     unplaced scaffolds and HLA alleles - their str order, which the reference sorts partitions by, interleaves them), every SV type,
-                    split reads across contigs: what a contig-sharded multi-GPU run sees (tests: 8 ranks over one file, tests/mp_c3_ranks_one_gpu.py)
+                    split reads across contigs: what a contig-sharded multi-GPU run sees (tests: several ranks over one file, tests/mp_c3_ranks_one_gpu.py)
     c4  configs[4]  60x PacBio-CLR profile: shorter, noisier reads and DENSE sites, so that --partition_max_distance in
                     {1000, 5000, 20000, 100000} produces many partitions beyond 100 and beyond 1045 signatures
                     (random.sample pool / set paths, src/svim/SVIM_clustering.py:132-134)

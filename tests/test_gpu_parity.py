@@ -1329,6 +1329,33 @@ def _run_bench(args, world, backend_env):
     return json.loads(lines[0])
 
 
+def test_bench_dump_outputs_repeat_and_hold_the_last_steps_tables(tmp_path):
+    """bench.py --dump-outputs DIR: the signature, BND-side and cluster tables of the last timed step as DIR/<name>.npy - float32 / float64 only, under 64 MB, the
+    lengths the JSON line counts, sampled where a table is longer than bench.DUMP_MAX_ELEMENTS rows (the columns of a table at the same rows), and the same files
+    from a second run with the same arguments."""
+    import os
+    import numpy as np
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "400000", "--contig-len", "100000000", "--no-cpu-baseline", "--no-end-to-end"]
+    lines = [_run_bench(common + ["--dump-outputs", str(tmp_path / d)], 1, {}) for d in ("a", "b")]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and len(files) == lines[0]["dumped_outputs"]["files"] >= 29
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    for f in files:
+        x = a[f[:-4]]
+        assert x.dtype in (np.float32, np.float64) and x.size > 0 and np.isfinite(x).all() and np.array_equal(x, np.load(tmp_path / "b" / f)), f
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) == lines[0]["dumped_outputs"]["bytes"] <= 64 << 20
+    n_sig, n_seq, n_bnd, _, n_clu, n_mem = (int(x) for x in a["counts"])
+    assert (n_bnd > 0) == ("bnd_sides_start" in a)                                      # a table without rows has no files: counts.npy says so
+    assert ((a["clusters_std_pos"] == -1) == (np.diff(a["clusters_member_off"]) == 1)).all()          # the std of a one-member cluster: NaN in the table, -1 in the file
+    assert n_sig == lines[0]["counts"]["signatures"] > 180_000 and n_seq == lines[0]["counts"]["ins_bases"] and n_clu == lines[0]["counts"]["clusters"] > 1000
+    assert a["clusters_type_count"].sum() == n_clu and a["clusters_start"].shape == (n_clu,) and a["clusters_member_off"][-1] == n_mem
+    # a sampled table: 180 000 of its rows, every column at the same ones, in table order (the keys of a signature table ascend)
+    assert a["signatures_start"].shape == a["signatures_end"].shape == a["signatures_key_hi"].shape == (180_000,)
+    d_hi, d_lo = np.diff(a["signatures_key_hi"]), np.diff(a["signatures_key_lo"])
+    assert ((d_hi > 0) | ((d_hi == 0) & (d_lo > 0))).all() and (a["signatures_end"] >= a["signatures_start"]).all()
+    assert set(np.unique(a["signatures_type"])) <= {0.0, 1.0, 2.0} and a["signatures_seq"].max() <= 15
+
+
 def test_bench_strong_scaling_two_ranks_equal_one_rank_on_one_gpu():
     """bench.py --scaling strong: ONE whole-genome batch sharded by contig ownership - two ranks (both on cuda:0 over gloo here) process the
     same records, signatures and clusters as one rank; the line names the process group's world size and what crossed the fabric in the last step.  No scaling
@@ -1347,16 +1374,26 @@ def test_bench_strong_scaling_two_ranks_equal_one_rank_on_one_gpu():
 
 
 def test_bench_strong_scaling_over_rccl_when_two_gpus_are_visible():
-    """the same over RCCL, one rank per GPU - only where the box has two GPUs (the builder's and the driver's test boxes have one: skipped there)"""
+    """the same over RCCL, one rank per GPU, where the box has two GPUs.  RCCL refuses two ranks on one device, so a box with one GPU runs the RCCL path with the
+    one rank it can have (SVX_BENCH_FORCE_DIST: an RCCL process group of world size 1, window ownership and the distributed step of svim_amd/multigpu.py, which
+    has nothing to send there): the same records, signatures and clusters as the plain run either way."""
+    import socket
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("one GPU visible: RCCL refuses two ranks on one device")
+    world = 2 if torch.cuda.device_count() >= 2 else 1
     common = ["--steps", "1", "--warmup", "1", "--scaling", "strong", "--scale", "0.01"]
     one = _run_bench(["--gpus", "1"] + common, 1, {})
-    two = _run_bench(["--gpus", "2"] + common, 2, {})
+    env = {}
+    if world == 1:
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            env = {"SVX_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(sk.getsockname()[1])}
+    rccl = _run_bench(["--gpus", str(world)] + common, world, env)
     for k in ("reads_used", "signatures", "cigar_ops", "clusters_gathered"):
-        assert one["counts"][k] == two["counts"][k], (k, one["counts"], two["counts"])
-    assert two["multi_gpu"]["backend"].startswith("nccl") and two["multi_gpu"]["world_size_seen_by_the_process_group"] == 2
+        assert one["counts"][k] == rccl["counts"][k], (k, one["counts"], rccl["counts"])
+    assert one["multi_gpu"] is None and one["counts"]["clusters_gathered"] > 100
+    assert rccl["multi_gpu"]["backend"].startswith("nccl") and rccl["multi_gpu"]["world_size_seen_by_the_process_group"] == world
+    if world == 2:
+        assert rccl["multi_gpu"]["fabric_last_step_rank0"]["collectives"] >= 4 and rccl["multi_gpu"]["fabric_last_step_rank0"]["payload_bytes"] > 0
 
 
 def _read_all_batches(nb, batch_records, regions=None):

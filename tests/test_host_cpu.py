@@ -759,7 +759,7 @@ def test_gpu_suite_order_puts_hot_path_and_configs_in_front_of_the_readers():
                  "test_c1_bench_shape_sample_vs_reference_golden", "test_collect_golden_and_oracle[0]", "test_cluster_golden_and_oracle[0]", "test_edit_distance_golden"):
         assert names.index(must) < first_reader, must
     assert names.index("test_c1_full_bench_size_vs_oracle_and_properties") == tiers.index(1)          # configs[1] at the bench size opens the configs
-    for late in ("test_device_bam_decode_equals_host_reader[None]", "test_reader_life_cycle_stress_with_pageable_copies[1]", "test_c3_whole_genome_contig_sharded_ranks_on_one_gpu[8]"):
+    for late in ("test_device_bam_decode_equals_host_reader[None]", "test_reader_life_cycle_stress_with_pageable_copies[1]", "test_c3_whole_genome_contig_sharded_ranks_on_one_gpu[4]"):
         assert names.index(late) >= first_reader, late
 
 

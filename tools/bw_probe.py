@@ -1,5 +1,5 @@
-import sys, time
-sys.path.insert(0, '/root/repo')
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 n = 1528270037
 x = torch.randint(0, 2**31 - 1, (n,), dtype=torch.int32, device="cuda:0")

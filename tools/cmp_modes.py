@@ -1,6 +1,6 @@
 """Full-scale check of the banded edit-distance pipeline against the full-matrix kernel (same GPU, same batch)."""
 import os, sys, types, pickle
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from svim_amd import _abi, _lib, devsynth
 n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 1000000

@@ -1,5 +1,6 @@
-import random, sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, random, sys
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO); sys.path.insert(0, os.path.join(REPO, 'tests'))
 from svim_amd import _lib, synth
 from oracle import oracle as om
 eng = _lib.Engine(0); orc = om.Oracle()

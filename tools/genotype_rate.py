@@ -1,10 +1,11 @@
 """GENOTYPE at configs[1] scale: every DEL / INS cluster of the synthetic batch as a candidate, the batch's own records as the
 alignment index (reference_end approximated by pos + read length: timing and GPU-vs-oracle parity only, not a reference comparison)."""
+import os
 import sys
 import time
 import types
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 from svim_amd import _abi, _lib, devsynth   # noqa: E402

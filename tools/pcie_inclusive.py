@@ -1,10 +1,11 @@
 """PCIe-inclusive rate of one COLLECT+CLUSTER pass: the same synthetic batch handed over as HOST arrays (svx_collect uploads them)
 versus resident in HBM.  Usage: python tools/pcie_inclusive.py [n_reads] [contig_len]"""
+import os
 import sys
 import time
 import types
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 from svim_amd import _abi, _lib, devsynth   # noqa: E402

@@ -1,7 +1,7 @@
 """Repeat COLLECT+CLUSTER in one context and compare every pass with the first (hunts order-dependent bugs: the INS pair
 work list is built with atomics, so the grouping of pairs into waves differs from pass to pass)."""
 import os, sys, types, pickle
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from svim_amd import _abi, _lib, devsynth
 n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 1000000
