@@ -36,6 +36,8 @@ extern "C" {
 #define SVX_E_ARG          (-3)
 #define SVX_E_CAPACITY     (-4)   /* an internal fixed-capacity buffer overflowed */
 #define SVX_E_STATE        (-5)   /* call order violated (e.g. cluster before collect/set_signatures) */
+#define SVX_E_FASTA_SYMBOL (-6)   /* svx_genome_load_fasta: a requested record holds symbols outside "=ACMGRSVTWYHKDBN" (svx_fasta_stats.bad_mask says which) */
+#define SVX_E_FASTA_HOST   (-7)   /* svx_genome_load_fasta: a file the device loader leaves to the caller's host parser (svx_fasta_stats.host_reason says why) */
 
 /* signature types, in the order CLUSTER processes them (src/svim/SVIM_CLUSTER.py:19-24) */
 enum { SVX_DEL = 0, SVX_INS = 1, SVX_INV = 2, SVX_DUP_TAN = 3, SVX_BND = 4, SVX_DUP_INT = 5, SVX_NTYPES = 6 };
@@ -201,6 +203,50 @@ int  svx_collect_count(svx_ctx* ctx, int64_t* n_sig, int64_t* n_seq_bytes, int64
 /* which: 0 = sv_signatures, 1 = translocation_signatures_all_bnds (second list of the reference's tuple) */
 int  svx_collect_fetch(svx_ctx* ctx, int which, svx_sig_view* host_out);
 
+/* ---- the reference genome from a FASTA file, parsed on the device: replaces FastaFile(options.genome) (src/svim/SVIM_clustering.py:377) ----------
+ * The bytes of the file (plain text; BGZF, inflated by the device; any other gzip file, inflated by zlib on the host) go into HBM whole, through page-locked
+ * staging pieces of SVX_FASTA_PIECE bytes, and kernels working on tiles of SVX_FASTA_TILE bytes find the records, drop headers and line ends, encode the bases
+ * and place the requested records in the order of the caller's contig list (csrc/fasta.hip).  A record starts at a '>' in the first column, its name is the
+ * first whitespace-separated token behind it (looked for in the SVX_FASTA_NAME_BYTES bytes behind the '>'), the later of two records of one name wins, a contig
+ * the file lacks gets length 0.  On SVX_OK the genome is set in the context as after svx_set_genome with host arrays, and off_out holds its offsets.
+ * SVX_E_FASTA_SYMBOL: a REQUESTED record holds a byte outside the alphabet.  SVX_E_FASTA_HOST: the loader does not restate what a host parser does with this
+ * file - the caller parses it there and calls svx_set_genome.  Either way the genome of the context is what it was before the call.  SVX_E_ARG: no such file. */
+#define SVX_FASTA_TILE        4096
+#define SVX_FASTA_PIECE       (8 << 20)
+#define SVX_FASTA_NAME_BYTES  256
+enum { SVX_FASTA_PLAIN = 0, SVX_FASTA_BGZF = 1, SVX_FASTA_GZIP = 2 };
+/* svx_fasta_stats.host_reason */
+enum { SVX_FASTA_HOST_NONE = 0, SVX_FASTA_HOST_BLANKS = 1 /* space, tab, \v, \f or a '\r' not in front of '\n' on a sequence line */,
+       SVX_FASTA_HOST_BUDGET = 2 /* raw bytes + codes beyond a quarter of the free device memory (environment SVX_FASTA_BUDGET_MB: another limit) */,
+       SVX_FASTA_HOST_NAMES = 3 /* empty, non-ASCII or over-long record name; one name twice in the contig list; millions of records */,
+       SVX_FASTA_HOST_CONTAINER = 4 /* a gzip stream zlib does not take as it is */ };
+typedef struct svx_fasta_stats {
+    int32_t kind;                /* SVX_FASTA_PLAIN / _BGZF / _GZIP */
+    int32_t host_reason;
+    int64_t raw_bytes;           /* bytes of text */
+    int64_t seq_bytes;           /* bytes of sequence lines that are bases, of every record of the file */
+    int64_t dropped_bytes;       /* every other byte: seq_bytes + dropped_bytes == raw_bytes */
+    int64_t blank_bytes;
+    int64_t bases_kept;          /* == off_out[n_contig] */
+    int64_t records_in_file, records_kept;
+    int64_t blocks;              /* BGZF blocks */
+    double  t_read_stage_s;      /* file -> page-locked staging -> HBM (BGZF: with the device inflate it overlaps; gzip: without the time inside zlib) */
+    double  t_inflate_s;         /* BGZF: sum of the inflate kernels' times; gzip: time inside zlib */
+    double  t_kernels_s;         /* the passes over the raw bytes, with the header table's trip to the host */
+    double  t_total_s;
+    uint32_t bad_mask[8];        /* bit b of word b / 32: byte value b, outside the alphabet, seen in a requested record */
+} svx_fasta_stats;
+int  svx_genome_load_fasta(svx_ctx* ctx, const char* path, int32_t n_contig, const char* names_nul_separated,
+                           int64_t* off_out /* [n_contig+1], host */, svx_fasta_stats* stats /* may be NULL */);
+/* the genome resident in the context, however it was set (a borrowed device genome included), back on the host; NULL arrays: the counts only */
+int  svx_genome_fetch(svx_ctx* ctx, int32_t* n_contig, int64_t* n_codes, int64_t* off /* [n_contig+1] */, uint8_t* codes /* [n_codes] */);
+/* host-only pieces of the loader (no GPU needed; tests): the container of a file (raw_bytes: -1 when only inflating tells; n_blocks: BGZF blocks), and the step
+ * from the header table to the placement: name_blob holds SVX_FASTA_NAME_BYTES bytes behind each of the n_hdr '>' (at hdr_pos), hdr_rank[n_hdr + 1] the number of
+ * bases in front of each header (last entry: all of them); dest[h] = where record h starts in codes, or -1 */
+int  svx_fasta_probe(const char* path, int32_t* kind, int64_t* raw_bytes, int64_t* n_blocks);
+int  svx_fasta_plan(int64_t n_hdr, const uint8_t* name_blob, const int64_t* hdr_pos, const int64_t* hdr_rank, int64_t raw_bytes, int32_t n_contig,
+                    const char* names_nul_separated, int64_t* dest, int64_t* off_out, int64_t* records_kept /* may be NULL */);
+
 /* ---- CLUSTER: replaces cluster_sv_signatures (src/svim/SVIM_CLUSTER.py:7-26) -------------------- */
 int  svx_set_genome(svx_ctx* ctx, const svx_genome* g);      /* FastaFile(options.genome), SVIM_clustering.py:377 */
 /* source: 0 = signatures resident from the last svx_collect, 1 = its all_bnds side list,
@@ -282,7 +328,7 @@ int  svx_pair_distances(svx_ctx* ctx, const svx_sig_view* host_sigs, int64_t n_p
 typedef struct svx_inflater svx_inflater;
 int   svx_inflater_create(int device, svx_inflater** out);
 void  svx_inflater_destroy(svx_inflater* f);
-/* three slots (0..2), each with its own stream, device buffers and pinned staging buffer: while one sub-batch is inflated and copied back, the
+/* eight slots (0..7; the readers use three with the wave-per-block decoder), each with its own stream, device buffers and pinned staging buffer: while one sub-batch is inflated and copied back, the
  * caller packs the next.  enqueue = H2D + inflate + copy of the inflated range to `out` (host, or device when out_on_device), asynchronous;
  * wait = its completion (error if a block was not a sound DEFLATE stream of ISIZE bytes).  run = enqueue + wait on slot 0. */
 void* svx_inflater_staging(svx_inflater* f, int slot, uint64_t bytes);   /* NULL (SVX_E_STATE) while the slot is busy and the buffer would have to grow: wait first */

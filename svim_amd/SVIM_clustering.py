@@ -17,8 +17,10 @@ def _genome_for(engine, options, contigs):
     path = getattr(options, "genome", None)
     key = (id(engine), path, tuple(contigs))
     if _GENOMES.get("key") != key:
-        off, codes = convert.genome_arrays(path, contigs) if path else (np.zeros(len(contigs) + 1, np.int64), np.zeros(1, np.uint8))
-        engine.set_genome(off, codes)
+        if path:
+            convert.load_genome(engine, path, contigs)
+        else:
+            engine.set_genome(np.zeros(len(contigs) + 1, np.int64), np.zeros(1, np.uint8))
         _GENOMES["key"] = key
 
 

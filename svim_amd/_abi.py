@@ -12,7 +12,12 @@ SRC_NAMES = ("cigar", "suppl")
 SVX_FLAG_SKIP = 0x8000
 NIBBLE = "=ACMGRSVTWYHKDBN"
 
-ERRORS = {-1: "SVX_E_NODEVICE", -2: "SVX_E_HIP", -3: "SVX_E_ARG", -4: "SVX_E_CAPACITY", -5: "SVX_E_STATE"}
+ERRORS = {-1: "SVX_E_NODEVICE", -2: "SVX_E_HIP", -3: "SVX_E_ARG", -4: "SVX_E_CAPACITY", -5: "SVX_E_STATE", -6: "SVX_E_FASTA_SYMBOL", -7: "SVX_E_FASTA_HOST"}
+SVX_E_FASTA_SYMBOL, SVX_E_FASTA_HOST = -6, -7
+# the FASTA loader (include/svx.h, csrc/fasta.hip): tile of raw bytes per workgroup, page-locked staging piece, bytes fetched behind every '>'
+FASTA_TILE, FASTA_PIECE, FASTA_NAME_BYTES = 4096, 8 << 20, 256
+FASTA_KINDS = ("plain", "bgzf", "gzip")
+FASTA_HOST_REASONS = ("none", "blanks", "budget", "names", "container")
 
 # translation table: ASCII (any case) -> 4-bit code; 255 marks symbols outside the BAM alphabet
 _ENC = np.full(256, 255, dtype=np.uint8)
@@ -88,6 +93,20 @@ SIG_DTYPES = dict(key=np.uint64, type=np.uint8, src=np.uint8, aux=np.uint8, cont
 
 class Genome(C.Structure):
     _fields_ = [("on_device", C.c_int32), ("n_contig", C.c_int32), ("off", _P), ("codes", _P)]
+
+
+class FastaStats(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("host_reason", C.c_int32), ("raw_bytes", C.c_int64), ("seq_bytes", C.c_int64), ("dropped_bytes", C.c_int64),
+                ("blank_bytes", C.c_int64), ("bases_kept", C.c_int64), ("records_in_file", C.c_int64), ("records_kept", C.c_int64), ("blocks", C.c_int64),
+                ("t_read_stage_s", C.c_double), ("t_inflate_s", C.c_double), ("t_kernels_s", C.c_double), ("t_total_s", C.c_double),
+                ("bad_mask", C.c_uint32 * 8)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "bad_mask"}
+        d["kind"] = FASTA_KINDS[self.kind] if 0 <= self.kind < len(FASTA_KINDS) else self.kind
+        d["host_reason"] = FASTA_HOST_REASONS[self.host_reason] if 0 <= self.host_reason < len(FASTA_HOST_REASONS) else self.host_reason
+        d["bad_symbols"] = [chr(b) for b in range(256) if (self.bad_mask[b >> 5] >> (b & 31)) & 1]
+        return d
 
 
 class ClusterView(C.Structure):

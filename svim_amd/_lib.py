@@ -24,11 +24,56 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_cigar_indel", "svx_edit_distance", "svx_linkage_fcluster", "svx_pair_distances",
            "svx_bam_open", "svx_bam_close", "svx_bam_header", "svx_bam_read_batch", "svx_bam_read_names", "svx_bam_set_seq_filter", "svx_bam_rewind", "svx_bam_seek", "svx_bam_set_gpu_inflate", "svx_bam_gpu_inflate_stats",
            "svx_inflater_create", "svx_inflater_destroy", "svx_inflater_staging", "svx_inflater_enqueue", "svx_inflater_wait",
-           "svx_inflater_run"]
+           "svx_inflater_run",
+           "svx_genome_load_fasta", "svx_genome_fetch", "svx_fasta_probe", "svx_fasta_plan"]
 
 
 class SvxError(RuntimeError):
     pass
+
+
+class FastaHostRoute(SvxError):
+    """svx_genome_load_fasta left the file to the host parser (SVX_E_FASTA_HOST) or met symbols outside the alphabet in a requested record
+    (SVX_E_FASTA_SYMBOL): convert.load_genome then takes the genome_arrays route, which loads the file or raises the ValueError.  `stats`: what the call measured"""
+
+    def __init__(self, msg, code, stats):
+        SvxError.__init__(self, msg)
+        self.code = code
+        self.stats = stats
+
+
+def _names_blob(references):
+    names = [r.encode("utf-8") if isinstance(r, str) else bytes(r) for r in references]
+    if any(b"\0" in n for n in names):
+        raise ValueError("contig names must not contain NUL")
+    return b"".join(n + b"\0" for n in names)
+
+
+def fasta_probe(path):
+    """host-only (no GPU needed): (container kind 'plain' / 'bgzf' / 'gzip', bytes of text or -1 when only inflating tells, BGZF blocks)"""
+    kind, raw, nb = C.c_int32(), C.c_int64(), C.c_int64()
+    _check(lib().svx_fasta_probe(os.fsencode(path), C.byref(kind), C.byref(raw), C.byref(nb)), "svx_fasta_probe")
+    return _abi.FASTA_KINDS[kind.value], raw.value, nb.value
+
+
+def fasta_plan(name_blob, hdr_pos, hdr_rank, raw_bytes, references):
+    """host-only step of the FASTA loader from the header table to the placement (svx_fasta_plan, include/svx.h) -> (dest int64[n_hdr], off int64[n+1], records kept);
+    FastaHostRoute when the names are left to the host parser"""
+    hdr_pos = np.ascontiguousarray(hdr_pos, dtype=np.int64)
+    hdr_rank = np.ascontiguousarray(hdr_rank, dtype=np.int64)
+    n_hdr = int(hdr_pos.size)
+    blob = np.frombuffer(bytes(name_blob), dtype=np.uint8) if n_hdr else np.zeros(1, np.uint8)
+    if hdr_rank.size != n_hdr + 1 or (n_hdr and blob.size != n_hdr * _abi.FASTA_NAME_BYTES):
+        raise ValueError("fasta_plan: hdr_rank needs n_hdr + 1 entries, name_blob n_hdr * %d bytes" % _abi.FASTA_NAME_BYTES)
+    dest = np.zeros(max(1, n_hdr), dtype=np.int64)
+    off = np.zeros(len(references) + 1, dtype=np.int64)
+    kept = C.c_int64()
+    rc = lib().svx_fasta_plan(C.c_int64(n_hdr), ptr(blob), ptr(hdr_pos if n_hdr else np.zeros(1, np.int64)), ptr(hdr_rank), C.c_int64(int(raw_bytes)),
+                              C.c_int32(len(references)), _names_blob(references), ptr(dest), ptr(off), C.byref(kept))
+    if rc == _abi.SVX_E_FASTA_HOST:
+        raise FastaHostRoute(lib().svx_last_error().decode("utf-8", "replace"), rc, None)
+    _check(rc, "svx_fasta_plan")
+    return dest[:n_hdr], off, kept.value
 
 
 def build(force=False):
@@ -133,6 +178,29 @@ class Engine(object):
         g = _abi.Genome(1 if on_device else 0, len(off) - 1 if not on_device else int(off.shape[0]) - 1, ptr(off), ptr(codes))
         self._keep = [off, codes]
         _check(self.L.svx_set_genome(self.ctx, C.byref(g)), "svx_set_genome")
+
+    def load_genome_fasta(self, path, references):
+        """The genome of a FASTA file (plain, BGZF, gzip) parsed, compacted and encoded on the device (svx_genome_load_fasta) and set in the context, as
+        set_genome(*convert.genome_arrays(path, references)) would -> (off int64[n + 1], stats dict).  FastaHostRoute: the file is one for the host parser
+        (convert.load_genome takes that route by itself)."""
+        references = list(references)
+        off = np.zeros(len(references) + 1, dtype=np.int64)
+        st = _abi.FastaStats()
+        rc = self.L.svx_genome_load_fasta(self.ctx, os.fsencode(path), C.c_int32(len(references)), _names_blob(references), ptr(off), C.byref(st))
+        if rc in (_abi.SVX_E_FASTA_HOST, _abi.SVX_E_FASTA_SYMBOL):
+            raise FastaHostRoute("%s: %s" % (_abi.ERRORS[rc], self.L.svx_last_error().decode("utf-8", "replace")), rc, st.as_dict())
+        _check(rc, "svx_genome_load_fasta")
+        self._keep = []
+        return off, st.as_dict()
+
+    def fetch_genome(self):
+        """(off, codes) of the genome resident in the context, however it was set"""
+        n, total = C.c_int32(), C.c_int64()
+        _check(self.L.svx_genome_fetch(self.ctx, C.byref(n), C.byref(total), None, None), "svx_genome_fetch")
+        off = np.zeros(n.value + 1, dtype=np.int64)
+        codes = np.zeros(max(1, total.value), dtype=np.uint8)
+        _check(self.L.svx_genome_fetch(self.ctx, None, None, ptr(off), ptr(codes)), "svx_genome_fetch")
+        return off, codes
 
     def cluster(self, params, contig_rank, table=None, source=2, fetch=True):
         v = table.view() if (table is not None and hasattr(table, "view")) else (table if table is not None else _abi.SigView())

@@ -238,3 +238,33 @@ def genome_arrays(path_or_dict, references):
     if codes.size == 0:
         codes = np.zeros(1, dtype=np.uint8)
     return off, codes
+
+
+def load_genome(engine, path_or_dict, references):
+    """The genome into the engine's context -> (off, stats dict).  A {name: sequence} dict goes through genome_arrays + set_genome; a FASTA path is read, parsed and
+    encoded by the device loader (Engine.load_genome_fasta), unless the loader leaves the file to the host (blanks inside sequence lines, symbols outside the
+    alphabet - genome_arrays then raises the ValueError -, beyond the memory budget, a ".gz" name on a file that is not gzip or the other way round).
+    SVX_GENOME_HOST=1 (read at every call) forces the genome_arrays route.  engine None: nothing is uploaded, -> (off, codes, stats)."""
+    import os
+    import time
+    stats = {"route": "host"}
+    path = None if isinstance(path_or_dict, dict) else os.fspath(path_or_dict)
+    if engine is not None and path is not None and os.environ.get("SVX_GENOME_HOST") != "1":
+        from ._lib import FastaHostRoute
+        with open(path, "rb") as fh:
+            gz = fh.read(2) == b"\x1f\x8b"
+        if gz == path.endswith(".gz"):                  # (genome_arrays picks its opener by the name)
+            try:
+                off, st = engine.load_genome_fasta(path, references)
+                st["route"] = "device"
+                return off, st
+            except FastaHostRoute as e:
+                stats["device_loader"] = e.stats
+    t0 = time.perf_counter()
+    off, codes = genome_arrays(path_or_dict, references)
+    stats["t_parse_s"] = time.perf_counter() - t0
+    if engine is None:
+        return off, codes, stats
+    engine.set_genome(off, codes)
+    stats["t_total_s"] = time.perf_counter() - t0
+    return off, stats

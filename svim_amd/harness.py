@@ -688,11 +688,10 @@ def run_bam(bam_path, fasta_path, opts, rank=0, world=1, device=0, steps=1, warm
     if so != "coordinate":
         raise SystemExit("bench.py --bam: coordinate-sorted input expected (header says %r)" % so)
     t0 = time.perf_counter()
-    off, codes = convert.genome_arrays(fasta_path, refs)
+    _, genome_stats = convert.load_genome(eng, fasta_path, refs)
     t_genome = time.perf_counter() - t0
-    eng.set_genome(off, codes)
     if world > 1:
-        return _run_bam_sharded(bam_path, fasta_path, opts, eng, rank, world, device, steps, warmup, threads, refs, t_genome)
+        return _run_bam_sharded(bam_path, fasta_path, opts, eng, rank, world, device, steps, warmup, threads, refs, t_genome, genome_stats)
     runs = _timed_bam_passes(bam_path, opts, eng, None, passes=warmup + steps, threads=threads)
     n, wall, ps, st, counts = min(runs[warmup:], key=lambda r: r[1])
     size = os.path.getsize(bam_path)
@@ -707,10 +706,10 @@ def run_bam(bam_path, fasta_path, opts, rank=0, world=1, device=0, steps=1, warm
                        "large_partitions": st["n_large_partitions"], "edit_pairs": st["n_edit_pairs"]},
             "end_to_end": {"bam_file_reads_per_s": n / wall, "bam_MB_per_s": size / wall / 1e6, "reader_busy_s": ps["t_reader_busy"],
                            "gpu_collect_s": ps["t_gpu_collect"], "gpu_waits_for_reader_s": ps["t_gpu_waits_for_reader"], "cluster_s": ps["t_cluster_wall"],
-                           "genome_load_s": t_genome, "host_cores_visible": os.cpu_count(), "host_cpus_granted": effective_cpus()}}
+                           "genome_load_s": t_genome, "genome_load": genome_stats, "host_cores_visible": os.cpu_count(), "host_cpus_granted": effective_cpus()}}
 
 
-def _run_bam_sharded(bam_path, fasta_path, opts, eng, rank, world, device, steps, warmup, threads, refs, t_genome):
+def _run_bam_sharded(bam_path, fasta_path, opts, eng, rank, world, device, steps, warmup, threads, refs, t_genome, genome_stats=None):
     """bench.py --gpus N --bam: contig-sharded ranks over one indexed BAM (needs <bam>.bai); value = records of ALL ranks / max wall."""
     import torch
     import torch.distributed as dist
@@ -744,4 +743,4 @@ def _run_bam_sharded(bam_path, fasta_path, opts, eng, rank, world, device, steps
                 os.path.basename(bam_path), len(refs), os.path.basename(fasta_path), world), "options": "SVIM alignment-mode defaults"},
             "counts": {"records": n_all, "signatures": int(sum(res.sig_counts)), "clusters": ct.n,
                        "clusters_by_type": dict(zip(_abi.TYPE_NAMES, [int(x) for x in ct.type_count]))},
-            "end_to_end": {"bam_file_reads_per_s": n_all / wall, "genome_load_s": t_genome, "host_cores_visible": os.cpu_count(), "host_cpus_granted": effective_cpus()}}
+            "end_to_end": {"bam_file_reads_per_s": n_all / wall, "genome_load_s": t_genome, "genome_load": genome_stats, "host_cores_visible": os.cpu_count(), "host_cpus_granted": effective_cpus()}}
