@@ -38,6 +38,7 @@ extern "C" {
 #define SVX_E_STATE        (-5)   /* call order violated (e.g. cluster before collect/set_signatures) */
 #define SVX_E_FASTA_SYMBOL (-6)   /* svx_genome_load_fasta: a requested record holds symbols outside "=ACMGRSVTWYHKDBN" (svx_fasta_stats.bad_mask says which) */
 #define SVX_E_FASTA_HOST   (-7)   /* svx_genome_load_fasta: a file the device loader leaves to the caller's host parser (svx_fasta_stats.host_reason says why) */
+#define SVX_E_NO_DELETION  (-8)   /* svx_combine: insertion-from clusters but no deletion cluster (the reference raises IndexError at src/svim/SVIM_merging.py:20) */
 
 /* signature types, in the order CLUSTER processes them (src/svim/SVIM_CLUSTER.py:19-24) */
 enum { SVX_DEL = 0, SVX_INS = 1, SVX_INV = 2, SVX_DUP_TAN = 3, SVX_BND = 4, SVX_DUP_INT = 5, SVX_NTYPES = 6 };
@@ -277,6 +278,60 @@ int  svx_cluster_set_ranks(svx_ctx* ctx, int rank, int world, svx_allgather_fn f
 int  svx_cluster_abort_ranks(svx_ctx* ctx);
 /* where each type's stream started / stopped on this rank in the last svx_cluster (32-bit words after seed(1524), SVX_* type order) */
 int  svx_cluster_stream_positions(svx_ctx* ctx, int64_t* start /* [SVX_NTYPES] */, int64_t* end /* [SVX_NTYPES] */);
+
+/* ---- COMBINE: replaces combine_clusters (src/svim/SVIM_COMBINE.py:332-478, the --skip_consensus branch) with merge_translocations_at_insertions and
+ * flag_cutpaste_candidates (src/svim/SVIM_merging.py:93-159, :12-29) and partition_and_cluster_candidates (src/svim/SVIM_clustering.py:306-372) -----
+ * Signature clusters -> SV candidates on the device (csrc/combine.hip).  The cluster and signature tables are only read. */
+typedef struct svx_combine_params {
+    int64_t trans_sv_max_distance;         /* 500  */
+    double  del_ins_dup_max_distance;      /* 1.0  */
+    double  position_distance_normalizer;  /* 900  */
+    int64_t partition_max_distance;        /* 1000 */
+    double  cluster_max_distance;          /* 0.5  */
+} svx_combine_params;
+/* candidate classes in the order of combine_clusters' return tuple */
+enum { SVX_CAND_DEL = 0, SVX_CAND_INV = 1, SVX_CAND_DUP_INT = 2, SVX_CAND_DUP_TAN = 3, SVX_CAND_INS = 4, SVX_CAND_BND = 5, SVX_NCAND = 6 };
+/* Candidate table (SoA), grouped by class in SVX_CAND_* order.  DEL / INV / DUP_TAN use the source columns, INS the destination columns (its source contig
+ * is -1), DUP_INT and BND both (BND: end = start, end2 = start2).  The constructors' max(0, start) is applied.  aux: BND direction bits as in the cluster
+ * table, DUP_INT bit 0 = cutpaste, DUP_TAN bit 0 = fully_covered.  BND: std_span = std_pos1, std_pos = std_pos2.  NaN = None. */
+typedef struct svx_candidate_view {
+    int64_t n;                 /* count on output */
+    int64_t n_members;
+    int64_t class_count[SVX_NCAND];
+    uint8_t* cls;
+    int32_t* contig;  int32_t* start;  int32_t* end;
+    int32_t* contig2; int32_t* start2; int32_t* end2;
+    uint8_t* aux;
+    int32_t* copies;           /* DUP_TAN, else 0 */
+    double*  score;
+    double*  std_span;
+    double*  std_pos;
+    int64_t* member_off;       /* [n+1] */
+    int32_t* members;          /* [n_members] indices into the clustered signature table */
+} svx_candidate_view;
+typedef struct svx_combine_stats {
+    double  t_combine_ms;      /* HIP events around the whole call on the context's stream (host steps in between included) */
+    double  t_cutpaste_ms;     /* the cut&paste kernel alone */
+    int64_t n_clusters_in, n_bnd_mirrored, n_merged, n_insertion_from, n_deletions, n_cutpaste_pairs, n_cutpaste;
+    int64_t n_remove_1, n_remove_2, n_dup_partitions, n_dup_large_partitions, n_candidates, n_candidate_members;
+} svx_combine_stats;
+/* source: 0 = the clusters resident from the last svx_cluster (SVX_E_STATE if there are none; the signature table that call clustered must still exist),
+ *         2 = the cluster table in `clusters` (grouped by type in SVX_* order, type_count set) plus `sig_aux`, the aux column of the n_sig signatures its
+ *             members index - both host or both device memory (on_device).
+ * contig_rank_host[n_contig]: rank of each contig NAME in Python str order.  SVX_E_NO_DELETION: see above; stage 2's results stay fetchable. */
+int  svx_combine(svx_ctx* ctx, int source, const svx_cluster_view* clusters, const uint8_t* sig_aux, int64_t n_sig, int32_t on_device, int32_t n_contig,
+                 const int32_t* contig_rank_host, const svx_combine_params* p);
+int  svx_combine_count(svx_ctx* ctx, int64_t* n_candidates, int64_t* n_members);
+int  svx_combine_fetch(svx_ctx* ctx, svx_candidate_view* out);   /* destination arrays: host or device memory; NULL arrays are skipped */
+/* inspection hook (tests compare with the reference's intermediates): the DUP_INT clusters stage 2 merged from an insertion and two breakend clusters (as
+ * cluster rows: cls = SVX_CAND_DUP_INT, source / destination as the cluster has them, no clamp), inserted_regions_to_remove_1 and _2 (indices into the
+ * insertion cluster list, ascending) and the flagged interspersed-duplication candidates before the re-clustering.  NULL arrays: counts only. */
+int  svx_combine_stages_fetch(svx_ctx* ctx, svx_candidate_view* merged, int64_t* n_remove_1, int32_t* remove_1, int64_t* n_remove_2, int32_t* remove_2,
+                              svx_candidate_view* flagged);
+int  svx_combine_get_stats(svx_ctx* ctx, svx_combine_stats* out);
+/* host-only (no GPU needed; tests): random.seed(1524) followed by random.sample(range(sizes[k]), 100) for k = 0 .. n - 1, as partition_and_cluster_candidates
+ * consumes the stream; out[100 * n] */
+int  svx_py_sample100(int64_t n, const int64_t* sizes, int32_t* out);
 
 /* ---- GENOTYPE: replaces the per-candidate BAM re-fetch of genotype() (src/svim/SVIM_genotyping.py:34-93) --------
  * by an interval join over the alignment records, resident in HBM.  Records are in file order of a coordinate-sorted BAM

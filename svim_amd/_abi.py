@@ -12,8 +12,12 @@ SRC_NAMES = ("cigar", "suppl")
 SVX_FLAG_SKIP = 0x8000
 NIBBLE = "=ACMGRSVTWYHKDBN"
 
-ERRORS = {-1: "SVX_E_NODEVICE", -2: "SVX_E_HIP", -3: "SVX_E_ARG", -4: "SVX_E_CAPACITY", -5: "SVX_E_STATE", -6: "SVX_E_FASTA_SYMBOL", -7: "SVX_E_FASTA_HOST"}
-SVX_E_FASTA_SYMBOL, SVX_E_FASTA_HOST = -6, -7
+ERRORS = {-1: "SVX_E_NODEVICE", -2: "SVX_E_HIP", -3: "SVX_E_ARG", -4: "SVX_E_CAPACITY", -5: "SVX_E_STATE", -6: "SVX_E_FASTA_SYMBOL", -7: "SVX_E_FASTA_HOST",
+          -8: "SVX_E_NO_DELETION"}
+SVX_E_STATE, SVX_E_FASTA_SYMBOL, SVX_E_FASTA_HOST, SVX_E_NO_DELETION = -5, -6, -7, -8
+# candidate classes in the order of combine_clusters' return tuple (include/svx.h: SVX_CAND_*)
+CAND_DEL, CAND_INV, CAND_DUP_INT, CAND_DUP_TAN, CAND_INS, CAND_BND = range(6)
+CAND_NAMES = ("DEL", "INV", "DUP_INT", "DUP_TAN", "INS", "BND")
 # the FASTA loader (include/svx.h, csrc/fasta.hip): tile of raw bytes per workgroup, page-locked staging piece, bytes fetched behind every '>'
 FASTA_TILE, FASTA_PIECE, FASTA_NAME_BYTES = 4096, 8 << 20, 256
 FASTA_KINDS = ("plain", "bgzf", "gzip")
@@ -116,6 +120,32 @@ class ClusterView(C.Structure):
                 ("n_members", C.c_int64)]
 
 
+class CombineParams(C.Structure):
+    _fields_ = [("trans_sv_max_distance", C.c_int64), ("del_ins_dup_max_distance", C.c_double), ("position_distance_normalizer", C.c_double),
+                ("partition_max_distance", C.c_int64), ("cluster_max_distance", C.c_double)]
+
+    @classmethod
+    def from_options(cls, o):
+        g = lambda k, d: getattr(o, k, d)      # noqa: E731
+        return cls(int(g("trans_sv_max_distance", 500)), float(g("del_ins_dup_max_distance", 1.0)), float(g("position_distance_normalizer", 900)),
+                   int(g("partition_max_distance", 1000)), float(g("cluster_max_distance", 0.5)))
+
+
+class CandidateView(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_members", C.c_int64), ("class_count", C.c_int64 * 6), ("cls", _P), ("contig", _P), ("start", _P), ("end", _P),
+                ("contig2", _P), ("start2", _P), ("end2", _P), ("aux", _P), ("copies", _P), ("score", _P), ("std_span", _P), ("std_pos", _P),
+                ("member_off", _P), ("members", _P)]
+
+
+class CombineStats(C.Structure):
+    _fields_ = [("t_combine_ms", C.c_double), ("t_cutpaste_ms", C.c_double)] + \
+               [(n, C.c_int64) for n in ("n_clusters_in", "n_bnd_mirrored", "n_merged", "n_insertion_from", "n_deletions", "n_cutpaste_pairs", "n_cutpaste",
+                                         "n_remove_1", "n_remove_2", "n_dup_partitions", "n_dup_large_partitions", "n_candidates", "n_candidate_members")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class AlnIndex(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_contig", C.c_int32), ("reserved", C.c_int32), ("contig_first", _P), ("contig_len", _P),
                 ("pos", _P), ("end", _P), ("flag", _P), ("mapq", _P), ("name_id", _P)]
@@ -124,6 +154,10 @@ class AlnIndex(C.Structure):
 CLU_DTYPES = dict(type=np.uint8, contig=np.int32, start=np.int32, end=np.int32, contig2=np.int32, start2=np.int32,
                   end2=np.int32, aux=np.uint8, score=np.float64, std_span=np.float64, std_pos=np.float64,
                   size=np.int32)
+
+
+CAND_DTYPES = dict(cls=np.uint8, contig=np.int32, start=np.int32, end=np.int32, contig2=np.int32, start2=np.int32, end2=np.int32, aux=np.uint8,
+                   copies=np.int32, score=np.float64, std_span=np.float64, std_pos=np.float64)
 
 
 class Stats(C.Structure):
@@ -235,6 +269,62 @@ class ClusterTable(object):
         if list(self.type_count) != list(other.type_count):
             return "type_count %r != %r" % (self.type_count, other.type_count)
         for k in CLU_DTYPES:
+            a, b = getattr(self, k), getattr(other, k)
+            if a.dtype == np.float64:
+                same = (np.isnan(a) & np.isnan(b)) | (a == b) if rtol == 0.0 else \
+                    (np.isnan(a) & np.isnan(b)) | (np.abs(a - b) <= rtol * np.maximum(1.0, np.abs(b)))
+            else:
+                same = a == b
+            if not same.all():
+                i = int(np.nonzero(~same)[0][0])
+                return "%s[%d]: %r != %r" % (k, i, a[i], b[i])
+        if not np.array_equal(self.member_off, other.member_off):
+            return "member_off differs"
+        if not np.array_equal(self.members, other.members):
+            return "members differ"
+        return None
+
+
+class CandidateTable(object):
+    """Host-side candidate table (numpy SoA; include/svx.h: svx_candidate_view), grouped by class in CAND_* order."""
+    __slots__ = tuple(CAND_DTYPES) + ("member_off", "members", "n", "n_members", "class_count")
+
+    def __init__(self, n, n_members):
+        self.n, self.n_members = n, n_members
+        for k, dt in CAND_DTYPES.items():
+            setattr(self, k, np.zeros(max(1, n), dtype=dt))
+        self.member_off = np.zeros(n + 1, dtype=np.int64)
+        self.members = np.zeros(max(1, n_members), dtype=np.int32)
+        self.class_count = [0] * 6
+
+    def view(self):
+        v = CandidateView()
+        v.n, v.n_members = self.n, self.n_members
+        for k in CAND_DTYPES:
+            setattr(v, k, ptr(getattr(self, k)))
+        v.member_off = ptr(self.member_off)
+        v.members = ptr(self.members)
+        return v
+
+    def finish(self, v):
+        self.class_count = list(v.class_count)
+        for k in CAND_DTYPES:
+            setattr(self, k, getattr(self, k)[:self.n])
+        self.members = self.members[:self.n_members]
+        return self
+
+    def bounds(self):
+        b = [0]
+        for c in self.class_count:
+            b.append(b[-1] + int(c))
+        return b
+
+    def first_difference(self, other, rtol=0.0):
+        if self.n != other.n:
+            return "n: %d != %d" % (self.n, other.n)
+        if list(self.class_count) != list(other.class_count):
+            return "class_count %r != %r" % (self.class_count, other.class_count)
+        for k in CAND_DTYPES:
             a, b = getattr(self, k), getattr(other, k)
             if a.dtype == np.float64:
                 same = (np.isnan(a) & np.isnan(b)) | (a == b) if rtol == 0.0 else \

@@ -25,7 +25,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_bam_open", "svx_bam_close", "svx_bam_header", "svx_bam_read_batch", "svx_bam_read_names", "svx_bam_set_seq_filter", "svx_bam_rewind", "svx_bam_seek", "svx_bam_set_gpu_inflate", "svx_bam_gpu_inflate_stats",
            "svx_inflater_create", "svx_inflater_destroy", "svx_inflater_staging", "svx_inflater_enqueue", "svx_inflater_wait",
            "svx_inflater_run",
-           "svx_genome_load_fasta", "svx_genome_fetch", "svx_fasta_probe", "svx_fasta_plan"]
+           "svx_genome_load_fasta", "svx_genome_fetch", "svx_fasta_probe", "svx_fasta_plan",
+           "svx_combine", "svx_combine_count", "svx_combine_fetch", "svx_combine_stages_fetch", "svx_combine_get_stats", "svx_py_sample100"]
 
 
 class SvxError(RuntimeError):
@@ -74,6 +75,20 @@ def fasta_plan(name_blob, hdr_pos, hdr_rank, raw_bytes, references):
         raise FastaHostRoute(lib().svx_last_error().decode("utf-8", "replace"), rc, None)
     _check(rc, "svx_fasta_plan")
     return dest[:n_hdr], off, kept.value
+
+
+class NoDeletionClusters(SvxError):
+    """svx_combine met insertion-from clusters but no deletion cluster (SVX_E_NO_DELETION): the reference raises IndexError there
+    (src/svim/SVIM_merging.py:20), and so does svim_amd.SVIM_COMBINE.combine_clusters"""
+
+
+def py_sample100(sizes):
+    """host-only (no GPU needed): random.seed(1524) followed by random.sample(range(n), 100) for every n of `sizes`, as the library's stage 5 of COMBINE
+    draws them -> int32 array [len(sizes), 100]"""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+    out = np.zeros((max(1, sizes.size), 100), dtype=np.int32)
+    _check(lib().svx_py_sample100(C.c_int64(sizes.size), ptr(sizes if sizes.size else np.zeros(1, np.int64)), ptr(out)), "svx_py_sample100")
+    return out[:sizes.size]
 
 
 def build(force=False):
@@ -205,10 +220,12 @@ class Engine(object):
     def cluster(self, params, contig_rank, table=None, source=2, fetch=True):
         v = table.view() if (table is not None and hasattr(table, "view")) else (table if table is not None else _abi.SigView())
         rank = np.ascontiguousarray(contig_rank, dtype=np.int32)
+        self._resident_ct, self._last_contig_rank = None, rank
         _check(self.L.svx_cluster(self.ctx, source, C.byref(v), len(rank), ptr(rank), C.byref(params)), "svx_cluster")
         if not fetch:
             return None
-        return self.fetch_clusters()
+        ct = self._resident_ct = self.fetch_clusters()       # (SVIM_COMBINE: lists that are views of this very table combine without an upload)
+        return ct
 
     def partitions(self):
         """partitions of the last cluster() call (svx_cluster_partitions_fetch): list of lists of signature indices, in the order they were formed"""
@@ -228,6 +245,51 @@ class Engine(object):
         _check(self.L.svx_cluster_fetch(self.ctx, C.byref(cv)), "svx_cluster_fetch")
         ct.finish(cv)
         return ct
+
+    # ---- COMBINE ----
+    def combine(self, cparams, contig_rank, table=None, sig_aux=None, fetch=True):
+        """svx_combine: the clusters resident from the last cluster() call (table None, source 0) or the ClusterTable `table` whose members index the
+        signatures of the aux column `sig_aux` (source 2) -> CandidateTable (fetch False: it stays on the device).  NoDeletionClusters: see there."""
+        rank = np.ascontiguousarray(contig_rank, dtype=np.int32)
+        if table is None:
+            rc = self.L.svx_combine(self.ctx, 0, None, None, C.c_int64(0), C.c_int32(0), C.c_int32(len(rank)), ptr(rank if rank.size else np.zeros(1, np.int32)),
+                                    C.byref(cparams))
+        else:
+            v = table.view()
+            for k in range(6):
+                v.type_count[k] = int(table.type_count[k])
+            aux = np.ascontiguousarray(sig_aux if sig_aux is not None else np.zeros(0, np.uint8), dtype=np.uint8)
+            rc = self.L.svx_combine(self.ctx, 2, C.byref(v), ptr(aux if aux.size else np.zeros(1, np.uint8)), C.c_int64(aux.size), C.c_int32(0),
+                                    C.c_int32(len(rank)), ptr(rank if rank.size else np.zeros(1, np.int32)), C.byref(cparams))
+        if rc == _abi.SVX_E_NO_DELETION:
+            raise NoDeletionClusters(self.L.svx_last_error().decode("utf-8", "replace"))
+        _check(rc, "svx_combine")
+        return self.fetch_candidates() if fetch else None
+
+    def fetch_candidates(self):
+        n, nm = C.c_int64(), C.c_int64()
+        _check(self.L.svx_combine_count(self.ctx, C.byref(n), C.byref(nm)), "svx_combine_count")
+        t = _abi.CandidateTable(n.value, nm.value)
+        v = t.view()
+        _check(self.L.svx_combine_fetch(self.ctx, C.byref(v)), "svx_combine_fetch")
+        return t.finish(v)
+
+    def combine_stages(self):
+        """intermediates of the last combine() (svx_combine_stages_fetch) -> dict: merged (the DUP_INT clusters merged from an insertion and two breakend
+        clusters, as a CandidateTable of cluster rows), remove_1 / remove_2 (insertion list indices, int32), flagged (DUP_INT candidates before re-clustering)"""
+        mv, fv = _abi.CandidateView(), _abi.CandidateView()
+        n1, n2 = C.c_int64(), C.c_int64()
+        _check(self.L.svx_combine_stages_fetch(self.ctx, C.byref(mv), C.byref(n1), None, C.byref(n2), None, C.byref(fv)), "svx_combine_stages_fetch")
+        merged, flagged = _abi.CandidateTable(mv.n, mv.n_members), _abi.CandidateTable(fv.n, fv.n_members)
+        r1, r2 = np.zeros(max(1, n1.value), np.int32), np.zeros(max(1, n2.value), np.int32)
+        mv, fv = merged.view(), flagged.view()
+        _check(self.L.svx_combine_stages_fetch(self.ctx, C.byref(mv), C.byref(n1), ptr(r1), C.byref(n2), ptr(r2), C.byref(fv)), "svx_combine_stages_fetch")
+        return {"merged": merged.finish(mv), "remove_1": r1[:n1.value], "remove_2": r2[:n2.value], "flagged": flagged.finish(fv)}
+
+    def combine_stats(self):
+        s = _abi.CombineStats()
+        _check(self.L.svx_combine_get_stats(self.ctx, C.byref(s)), "svx_combine_get_stats")
+        return s.as_dict()
 
     def set_alignment_index(self, index):
         """index: svim_amd.SVIM_genotyping.AlignmentIndex (arrays are copied to the device)"""

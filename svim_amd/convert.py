@@ -194,6 +194,46 @@ def cluster_objects_range(ct, lo, hi, sig_objects, references):
     return out
 
 
+def candidate_objects_range(t, lo, hi, sig_objects, references):
+    """Rows [lo, hi) of a CandidateTable (_abi.CandidateTable) -> Candidate objects (svim_amd.candidates) through the reference's constructors;
+    `members` stays (signature sequence, index array) until it is read."""
+    from . import candidates as K
+    from ._abi import CAND_DEL, CAND_INV, CAND_DUP_INT, CAND_DUP_TAN, CAND_INS
+    dirs = ("fwd", "rev")
+    out = []
+    cls, aux, copies = t.cls[lo:hi].tolist(), t.aux[lo:hi].tolist(), t.copies[lo:hi].tolist()
+    c1, st, en = t.contig[lo:hi].tolist(), t.start[lo:hi].tolist(), t.end[lo:hi].tolist()
+    c2, st2, en2 = t.contig2[lo:hi].tolist(), t.start2[lo:hi].tolist(), t.end2[lo:hi].tolist()
+    score, sspan, spos = t.score[lo:hi].tolist(), t.std_span[lo:hi].tolist(), t.std_pos[lo:hi].tolist()
+    moff = t.member_off[lo:hi + 1].tolist()
+    for k in range(hi - lo):
+        code = cls[k]
+        members = (sig_objects, t.members[moff[k]:moff[k + 1]])
+        sp, po = _none_if_nan(sspan[k]), _none_if_nan(spos[k])
+        if code == CAND_DEL:
+            o = K.CandidateDeletion(references[c1[k]], st[k], en[k], members, score[k], sp, po)
+        elif code == CAND_INV:
+            o = K.CandidateInversion(references[c1[k]], st[k], en[k], members, score[k], sp, po)
+        elif code == CAND_DUP_INT:
+            o = K.CandidateDuplicationInterspersed(references[c1[k]], st[k], en[k], references[c2[k]], st2[k], en2[k], members, score[k], sp, po,
+                                                   bool(aux[k] & 1))
+        elif code == CAND_DUP_TAN:
+            o = K.CandidateDuplicationTandem(references[c1[k]], st[k], en[k], copies[k], bool(aux[k] & 1), members, score[k], sp, po)
+        elif code == CAND_INS:
+            o = K.CandidateNovelInsertion(references[c2[k]], st2[k], en2[k], "", members, score[k], sp, po)
+        else:
+            o = K.CandidateBreakend(references[c1[k]], st[k], dirs[aux[k] & 1], references[c2[k]], st2[k], dirs[(aux[k] >> 1) & 1], members, score[k], sp, po)
+        out.append(o)
+    return out
+
+
+def candidate_lists(t, sig_objects, references):
+    """CandidateTable -> the 6-tuple combine_clusters returns (DEL, INV, DUP_INT, DUP_TAN, INS, BND) of lazy CandidateLists"""
+    from .lazy import CandidateList
+    b = t.bounds()
+    return tuple(CandidateList(t, b[k], b[k + 1], sig_objects, references) for k in range(6))
+
+
 def cluster_objects(ct, sig_objects, references):
     """ClusterTable -> the 6-tuple cluster_sv_signatures returns (src/svim/SVIM_CLUSTER.py:26):
     (DEL, INS, INV, DUP_TAN, DUP_INT, BND), each a lazy ClusterList view (the table is grouped by type in SVX_* order)."""

@@ -181,7 +181,12 @@ struct svx_ctx {
     bool no_seq_gather = false;   // svx_cigar_indel hook: positions only
     svx_stats stats;
     int64_t last_cluster_source_n = 0;
+    // COMBINE (combine.hip): the aux column of the signature table the last svx_cluster clustered (DUP_TAN members' fully_covered bit), how many
+    // svx_cluster calls this context has seen (0: nothing resident for svx_combine source 0), and the stage's own buffers and results
+    const uint8_t* last_cluster_aux = nullptr; long long cluster_calls = 0;
+    struct CombineState* combine = nullptr;
 };
+void svx_combine_release(svx_ctx* c);
 
 // ---- primitives (prims.hip, scan.hpp: hand-written radix sort and scan) -------------------------------
 int svx_sort_pairs_u64(svx_ctx* c, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
@@ -220,7 +225,7 @@ inline int svx_mail_read3(svx_ctx* c, hipStream_t st, const void* a, int na, voi
     return svx_mail_gather(c, st, 3, srcs, n, dsts);
 }
 
-void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims();      // code objects loaded at context creation
+void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims(); void svx_preload_combine();      // code objects loaded at context creation
 
 // ---- stage entry points ------------------------------------------------------------------------------------
 int svx_collect_impl(svx_ctx* c, const svx_batch* b_dev, const svx_params* p);

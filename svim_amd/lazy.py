@@ -12,6 +12,8 @@ objects.  Building 7*10^5 objects costs seconds of interpreter time; the GPU nee
     (convert.sigtable_from_objects).
   * the six cluster lists are ClusterList views of the cluster table; a cluster's `members` resolve to signature objects on
     first access.
+  * `combine_clusters` returns six CandidateList views of the candidate table the device COMBINE produced, and leaves the edits the reference makes
+    to its input lists (deleted insertions, appended clusters) on the ClusterLists as deferred edits: still no object until someone looks.
 """
 from collections.abc import MutableSequence, Sequence
 
@@ -89,13 +91,39 @@ class ClusterList(MutableSequence):
     def __init__(self, ct, lo, hi, signatures, references):
         self.ct, self.lo, self.hi, self.signatures, self.references = ct, lo, hi, signatures, references
         self._objs = None
+        self._deferred = None               # (row indices to delete, number of objects to append, callable(objects so far) -> those objects)
 
     def __len__(self):
-        return self.hi - self.lo if self._objs is None else len(self._objs)
+        if self._objs is not None:
+            return len(self._objs)
+        d = self._deferred
+        return self.hi - self.lo if d is None else self.hi - self.lo - len(d[0]) + d[1]
+
+    def untouched(self):
+        """still the plain view of its rows: no object built, no edit pending"""
+        return self._objs is None and self._deferred is None
+
+    def defer(self, deleted=(), n_appended=0, appended=None):
+        """What COMBINE does to its input lists (`del lst[i]`, `lst.extend(new)`), recorded instead of done: applied when the objects are built."""
+        if self._objs is not None or self._deferred is not None:
+            objs = self.materialise()
+            tail = list(appended(objs)) if n_appended else []
+            for i in sorted(deleted, reverse=True):
+                del objs[i]
+            objs.extend(tail)
+        elif len(deleted) or n_appended:
+            self._deferred = (list(deleted), int(n_appended), appended)
 
     def materialise(self):
         if self._objs is None:
-            self._objs = convert.cluster_objects_range(self.ct, self.lo, self.hi, self.signatures, self.references)
+            objs = convert.cluster_objects_range(self.ct, self.lo, self.hi, self.signatures, self.references)
+            d, self._deferred = self._deferred, None
+            if d is not None:
+                tail = list(d[2](objs)) if d[1] else []
+                for i in sorted(d[0], reverse=True):
+                    del objs[i]
+                objs.extend(tail)
+            self._objs = objs
         return self._objs
 
     def __copy__(self):                             # copy.copy(list) is a new list of the same objects: mutating the copy leaves the original alone
@@ -141,3 +169,64 @@ class ClusterList(MutableSequence):
 
     def __repr__(self):
         return "<ClusterList of %d clusters>" % len(self)
+
+
+class CandidateList(MutableSequence):
+    """The candidates of ONE class (one slot of combine_clusters' 6-tuple) as a view of rows [lo, hi) of the candidate table: list semantics as for
+    ClusterList, objects (svim_amd.candidates) only when touched, `members` as index slices until read."""
+
+    def __init__(self, table, lo, hi, signatures, references):
+        self.table, self.lo, self.hi, self.signatures, self.references = table, lo, hi, signatures, references
+        self._objs = None
+
+    def __len__(self):
+        return self.hi - self.lo if self._objs is None else len(self._objs)
+
+    def materialise(self):
+        if self._objs is None:
+            self._objs = convert.candidate_objects_range(self.table, self.lo, self.hi, self.signatures, self.references)
+        return self._objs
+
+    def __copy__(self):
+        c = CandidateList(self.table, self.lo, self.hi, self.signatures, self.references)
+        c._objs = list(self.materialise())
+        return c
+
+    copy = __copy__
+
+    def __iter__(self):
+        return iter(self.materialise())
+
+    def __getitem__(self, i):
+        return self.materialise()[i]
+
+    def __setitem__(self, i, value):
+        self.materialise()[i] = value
+
+    def __delitem__(self, i):
+        del self.materialise()[i]
+
+    def insert(self, i, value):
+        self.materialise().insert(i, value)
+
+    def extend(self, values):
+        self.materialise().extend(list(values))
+
+    def sort(self, key=None, reverse=False):
+        self.materialise().sort(key=key, reverse=reverse)
+
+    def __eq__(self, other):
+        if isinstance(other, (list, tuple, CandidateList)):
+            return list(self) == list(other)
+        return NotImplemented
+
+    __hash__ = None
+
+    def __add__(self, other):
+        return list(self) + list(other)
+
+    def __radd__(self, other):
+        return list(other) + list(self)
+
+    def __repr__(self):
+        return "<CandidateList of %d candidates (%s)>" % (len(self), "objects built" if self._objs is not None else "table only")
