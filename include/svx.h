@@ -260,10 +260,12 @@ int  svx_cluster_fetch(svx_ctx* ctx, svx_cluster_view* out);  /* destination arr
  * order, part_start[n_part + 1] = where each partition begins in it.  Inspection hook (tests compare it with the reference's partitions); NULL arrays: counts only */
 int  svx_cluster_partitions_fetch(svx_ctx* c, int64_t* n_sig, int64_t* n_part, uint32_t* sorted_index, int64_t* part_start);
 
-/* multi-GPU, contig-sharded ranks: each rank clusters ONLY the signatures of the contigs it owns - every partition of
+/* multi-GPU, sharded ranks: each rank clusters ONLY the signatures it owns, and the caller deals them out so that every partition of
  * src/svim/SVIM_clustering.py:17-29 is local to one rank.  What still couples the ranks is the random.sample word stream, which a signature type's
- * > 100-member partitions consume in global sorted order without re-seeding (src/svim/SVIM_clustering.py:129-134).  When ranks own consecutive ranges
- * of the name-sorted contig list that order is rank-major: rank r continues each type's stream where the partitions of ranks 0..r-1 stop.
+ * > 100-member partitions consume in global sorted order without re-seeding (src/svim/SVIM_clustering.py:129-134).  Ranks own consecutive ranges of the
+ * partition keys in (contig name, key coordinate) order - coordinate windows whose cuts may lie INSIDE a contig, in a stretch wider than
+ * partition_max_distance that no signature touches (svim_amd/multigpu.py: Windows; whole contigs are the special case of cuts at contig starts) - so that
+ * order is rank-major: rank r continues each type's stream where the partitions of ranks 0..r-1 stop, those of its own first contig included.
  * svx_cluster finds those positions itself, with ALL-GATHERS ONLY (no rank waits for another rank's sampling): (1) the sizes of everybody's large
  * partitions (4 B each); (2) every rank builds, concurrently, its transfer table "stream position before my partitions -> position after them" for a
  * 6-sigma window around the start it expects from (1) (a few thousand 8 B entries per type), the tables are all-gathered and composed.  Only when a

@@ -6,8 +6,8 @@ Ownership (round 6: coordinate WINDOWS).  The partition keys of a type are sorte
 contig is only legal where no partition can straddle it: form_partitions (src/svim/SVIM_clustering.py:17-29) cuts where the gap to the previous element
 exceeds partition_max_distance, so a cut goes into a CORRIDOR - a stretch wider than partition_max_distance that no signature's [start, end] of any type
 touches.  assign_windows proposes cuts that balance a weight (contig length, or a density histogram); Windows.refine moves every proposal into the nearest
-corridor from the signatures the ranks actually collected (one small all-gather of merged intervals per step) or, where there is none, to the contig's
-edge.  Whole-contig ownership (assign_contigs, rounds 2-5) is the special case of cuts at contig starts.  DUP_INT rows - keyed (destination contig,
+corridor from the signatures the ranks actually collected (one small all-gather of merged intervals per step) or, where there is none within the radius
+the ranks looked at, to the contig's edge (what lies beyond the radius was not gathered and is no evidence of a corridor).  Whole-contig ownership (assign_contigs, rounds 2-5) is the special case of cuts at contig starts.  DUP_INT rows - keyed (destination contig,
 SOURCE contig, destination start), i.e. not in coordinate order inside a contig - stay whole-contig: they belong to the rank that owns the destination
 contig's first base.  Every partition is local to one rank, and the global sorted order of all partitions of a type is rank-major.
 
@@ -173,10 +173,17 @@ class Windows(object):
         return np.asarray(out, dtype=np.int64)
 
     def refine_from(self, gathered, max_distance, radius, lengths=None):
-        """gathered: concatenation of every rank's local_intervals.  Every proposal inside a contig moves to the START of the nearest corridor's right edge -
-        the first covered coordinate behind a gap wider than max_distance that lies within `radius` - or, where the neighbourhood holds no such gap, down to the
-        contig's first base (the contig then belongs whole to the rank above the cut; monotonicity is restored by pushing later cuts of the same contig along).
-        Deterministic: all ranks compute the same cuts from the same gathered bytes."""
+        """gathered: concatenation of every rank's local_intervals.  Every proposal inside a contig moves to the nearest coordinate of the nearest corridor - a gap
+        wider than max_distance between the merged stretches within `radius`; a proposal inside a corridor stays - or, where the neighbourhood holds no such gap,
+        down to the contig's first base (the contig then belongs whole to the rank above the cut; monotonicity is restored by pushing later cuts of the same contig along).
+
+        The open ends of the neighbourhood are no evidence of a corridor: signatures beyond the radius were never gathered and may continue the partition of the
+        outermost stretch that was seen.  The gap in front of the first stretch therefore begins at x - radius - 1, the last coordinate an unseen signature can
+        cover, and the gap behind the last stretch ends at x + radius + 1, the first one: only the part of a gap that was looked at counts towards its width.
+        Where that leaves nothing the cut falls back to the contig's first base.  (The alternative - widen the radius and gather again until a corridor shows
+        up - costs one more collective per doubling and has no bound on a contig without corridors; the fallback costs balance, never correctness, and needs
+        nothing on the wire.)
+        Deterministic: all ranks compute the same cuts from the same gathered bytes; with radius >= max_distance, refining refined cuts again moves nothing."""
         g = np.asarray(gathered, dtype=np.int64).reshape(-1, 3)
         new_pos = self.cut_pos.copy()
         for k in range(self.world - 1):
@@ -184,28 +191,26 @@ class Windows(object):
             if x < 0:
                 continue
             iv = g[g[:, 0] == k][:, 1:]
-            if iv.shape[0] == 0:
-                continue                                                              # nobody has a signature near the proposal: it is in a corridor already
             o = np.argsort(iv[:, 0], kind="stable")
             lo, hi = iv[o, 0], np.maximum.accumulate(iv[o, 1])
-            # gaps between consecutive merged stretches (and the open ends of the neighbourhood, as far as it was looked at)
-            edges_l = np.concatenate([[x - radius - max_distance - 2], hi])             # left edge of every gap = right end of what lies before it
-            edges_r = np.concatenate([lo, [x + radius + max_distance + 2]])             # right edge = first covered coordinate behind it
+            # gaps between consecutive merged stretches, and between the rim of the neighbourhood and the outermost stretches (nobody near the proposal: one gap
+            # from rim to rim)
+            edges_l = np.concatenate([[x - radius - 1], hi]).astype(np.int64)          # left edge of every gap = right end of what lies before it
+            edges_r = np.concatenate([lo, [x + radius + 1]]).astype(np.int64)          # right edge = first covered coordinate behind it
+            # (overlapping stretches and stretches that reach beyond the rim produce negative gaps)
             ok = (edges_r - edges_l) > max_distance
-            # a gap is usable if its left neighbour really ends before its right neighbour starts (overlapping stretches produce negative gaps)
             if not ok.any():
                 new_pos[k] = -1
                 continue
             cand = np.nonzero(ok)[0]
-            # the cut goes to the right edge R of the gap (left rows end <= L < R <= right rows' start); distance of the proposal to the gap
-            dist = np.where(edges_r[cand] < x, x - edges_r[cand], np.where(edges_l[cand] > x, edges_l[cand] - x, 0))
-            j = cand[int(np.argmin(dist))]
-            r_edge = int(edges_r[j])
-            if j == edges_r.size - 1:                                                 # the open gap behind the last stretch: anywhere behind it, keep the proposal if it is inside
-                r_edge = max(x, int(edges_l[j]) + 1)
-            elif j == 0 and x <= int(edges_r[0]):
-                r_edge = min(max(x, 0), int(edges_r[0]))                              # the open gap in front of the first stretch
-            new_pos[k] = max(r_edge, 0)
+            # a cut c is legal in the gap (L, R) for L < c <= R (rows left of it end <= L < c, rows right of it start >= R >= c): the gap nearest to the
+            # proposal, and in it the coordinate nearest to the proposal - the proposal itself where it lies in a corridor
+            first, last = edges_l[cand] + 1, edges_r[cand]
+            dist = np.maximum(np.maximum(first - x, x - last), 0)
+            j = int(np.argmin(dist))
+            r_edge = min(max(x, int(first[j])), int(last[j]))
+            # (a cut at coordinate 0 is the whole contig: written as -1, so that DUP_INT rows - keyed below every coordinate - stay with the first base)
+            new_pos[k] = r_edge if r_edge > 0 else -1
         # monotone again inside every contig (a cut that fell back to -1 takes the cuts before it on the same contig with it)
         for k in range(self.world - 2, -1, -1):
             if k + 1 < self.world - 1 and self.cut_contig[k] == self.cut_contig[k + 1] and new_pos[k] > new_pos[k + 1]:

@@ -3,7 +3,9 @@ RCCL refuses several ranks on one device): BASELINE.json configs[3] as far as on
 whose name order interleaves the header order) is read contig-sharded - every rank its own contig runs through the .bai with the DEVICE-RESIDENT reader -,
 collected, clustered with svx_cluster's rank exchange over the process group, gathered on rank 0 (harness.collect_cluster_bam_sharded: foreign BND / DUP_INT rows
 travel with their read names).  Rank 0 compares the merged result with a single-rank run over the whole file and with the oracle.
-Prints one line: C3_RANKS_OK <clusters> <foreign rows> <ranks that own contigs> - or the first difference."""
+Prints one line: C3_RANKS_OK <clusters> <foreign rows> <ranks that own contigs> - or the first difference.
+With --windows (tests/test_gpu_parity.py::test_rank_exchange_three_ranks_coordinate_windows_tables_equal_one_rank_on_one_gpu, three ranks): coordinate windows
+with cuts inside a contig instead of whole contigs - tests/windows_case.py main_device, which prints C3_RANKS_WINDOWS_OK ... or the first difference."""
 import os
 import sys
 
@@ -132,4 +134,9 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--windows" in sys.argv[1:]:
+        # coordinate windows instead of whole contigs: cuts inside a contig, table-level parity (tests/windows_case.py; tests/test_gpu_parity.py drives it)
+        import windows_case
+        windows_case.main_device("C3_RANKS_WINDOWS")
+    else:
+        main()

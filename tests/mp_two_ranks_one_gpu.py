@@ -1,7 +1,9 @@
 """Worker of tests/test_gpu_parity.py::test_two_ranks_share_one_gpu_over_gloo (run under torch.distributed.run, 2 ranks, both on cuda:0, backend gloo -
 RCCL refuses two ranks on one device): the contig-sharded step of svim_amd/multigpu.py with the REAL engine and DEVICE tensors at world size 2 -
 foreign BND rows cross ranks, svx_cluster's rank exchange runs over the process group, rank 0 gathers - against the oracle on the union of both ranks'
-inputs.  Prints one line: TWO_RANKS_OK <clusters> <foreign rows> or the first difference."""
+inputs.  Prints one line: TWO_RANKS_OK <clusters> <foreign rows> or the first difference.
+With --windows (test_two_ranks_coordinate_windows_tables_equal_one_rank_on_one_gpu): coordinate windows instead of whole contigs - tests/windows_case.py
+main_device, which prints TWO_RANKS_WINDOWS_OK ... or the first difference."""
 import os
 import sys
 
@@ -132,4 +134,9 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if "--windows" in sys.argv[1:]:
+        # coordinate windows instead of whole contigs: cuts inside a contig, table-level parity (tests/windows_case.py; tests/test_gpu_parity.py drives it)
+        import windows_case
+        windows_case.main_device("TWO_RANKS_WINDOWS")
+    else:
+        main()

@@ -1281,6 +1281,44 @@ def test_two_ranks_share_one_gpu_over_gloo():
     assert int(n_clusters) > 100 and int(n_cross) > 5 and int(n_foreign) > 0
 
 
+def _rank_script_in_windows_mode(script, world, tag):
+    """tests/<script> --windows under torch.distributed.run, `world` ranks on cuda:0 over gloo -> the fields of its <tag>_OK line"""
+    import os
+    import socket
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
+                          "--master-port", str(port), os.path.join(here, script), "--windows"],
+                         capture_output=True, text=True, timeout=900, cwd=os.path.dirname(here))
+    lines = [l for l in out.stdout.splitlines() if l.startswith(tag + "_")]
+    assert out.returncode == 0 and lines, (out.stdout[-1500:], out.stderr[-3000:])
+    assert lines[-1].startswith(tag + "_OK"), lines[-1]
+    return [int(x) for x in lines[-1].split()[1:]]
+
+
+def test_two_ranks_coordinate_windows_tables_equal_one_rank_on_one_gpu():
+    """Window ownership at TABLE level on the device engine (the strong-scaling bench test below compares four counts): two ranks on cuda:0 over gloo, the
+    records of tests/windows_case.py dealt out by assign_windows with record-density weights.  The refined cut lies inside contig w1 with sampled (> 100 members)
+    DEL and INS partitions of w1 on both sides and a 1100-member partition below it - the upper rank's random.sample streams start where the lower rank's
+    partitions of the same contig stop (checked against CPython's generator) -, split reads leave BND rows on the other side of the cut.  Two steps (the second on
+    warm buffers), then one with the cut proposed by contig length, which lands in 315 kb without a corridor and has to fall back to the contig's start.  Every
+    step: merged signature table, cluster table, member lists and read names equal a single-rank run on the device engine and the oracle
+    (tests/mp_two_ranks_one_gpu.py --windows)."""
+    n_clusters, n_changed_ranks, largest, steps = _rank_script_in_windows_mode("mp_two_ranks_one_gpu.py", 2, "TWO_RANKS_WINDOWS")
+    assert n_clusters > 500 and n_changed_ranks > 100 and largest > 1045 and steps == 3
+
+
+def test_rank_exchange_three_ranks_coordinate_windows_tables_equal_one_rank_on_one_gpu():
+    """The same on three ranks (tests/mp_c3_ranks_one_gpu.py --windows): the first cut inside w1 next to the 1100-member partition, the second one in the dense
+    run of w2 falls back - the middle rank owns the rest of w1 only -, the streams pass through two cuts.  Two steps, all tables."""
+    n_clusters, n_changed_ranks, largest, steps = _rank_script_in_windows_mode("mp_c3_ranks_one_gpu.py", 3, "C3_RANKS_WINDOWS")
+    assert n_clusters > 500 and n_changed_ranks > 100 and largest > 1045 and steps == 2
+
+
 def test_bench_two_ranks_one_gpu_with_foreign_rows():
     """bench.py --gpus 2 --workload c2 --foreign-frac 0.5 as the driver launches it, but with both ranks on cuda:0 over gloo (SVX_BENCH_BACKEND): the
     timed step carries foreign rows and the rank exchange; ONE JSON line."""

@@ -231,6 +231,58 @@ def _worker_records(rank, world, port, ret, windows=False):
         dist.destroy_process_group()
 
 
+def _worker_windows_case(rank, world, port, ret, by):
+    """tests/windows_case.py through the whole step with the oracle as engine: the records dealt out by the proposed windows (by record density or by contig
+    length), every rank collects its own, cluster_step refines the cuts - one of them in a neighbourhood without a corridor - and rank 0 compares the merged
+    signature table, clusters, members and read names with the single-rank run."""
+    _setup(rank, world, port)
+    try:
+        import windows_case as WC
+        from oracle import oracle as om
+        from svim_amd import _abi, batch, convert, multigpu
+        ref, recs, header = WC.build()
+        o = WC.options()
+        p = _abi.Params.from_options(o)
+        orc = om.Oracle()
+        off, codes = convert.genome_arrays(ref, WC.REFS)
+        orc.set_genome(off, codes)
+        hb_all = batch.build_batch(header, o, mode="coordinate", records=recs)
+        sig_all, _ = orc.collect(hb_all, p)
+        full = orc.cluster(p, hb_all.contig_rank, table=sig_all)
+        owner = WC.proposals(recs, world, by)
+        mine = WC.deal(recs, owner, rank, world)
+        hb, names, names_of, ids_of = WC.local_batch(header, o, recs, mine)
+        sig, _ = orc.collect(hb, p)
+        ad = multigpu.HostAdapter(orc, sig)
+        res = multigpu.cluster_step(ad, p, rank, world, np.arange(len(WC.REFS)), hb_all.contig_rank, owner, names_of=names_of, ids_of=ids_of)
+        everyone = [None] * world
+        dist.all_gather_object(everyone, names)                      # (after the step: with the names this rank interned for the rows it received)
+        ret["chain%d" % rank] = max(ad.stream_end()) if ad.stream_end() else -1
+        if rank == 0:
+            verdict = _compare(res, full, sig_all.key[:sig_all.n].astype(np.int64))
+            order = np.argsort(res.sig_cols["key"].numpy(), kind="stable")
+            if verdict == "ok":
+                for col in ("key", "type", "src", "aux", "contig", "start", "end", "contig2", "pos2"):
+                    a = res.sig_cols[col].numpy()[order]
+                    b = getattr(sig_all, col)[:sig_all.n]
+                    if a.shape != b.shape or not np.array_equal(a, b.view(np.int64) if b.dtype == np.uint64 else b):
+                        verdict = "signature column %s differs" % col
+                        break
+            if verdict == "ok":
+                row_rank = np.repeat(np.arange(world), res.sig_counts)
+                got = [everyone[r][i] for r, i in zip(row_rank[order], res.sig_cols["read_id"].numpy()[order])]
+                if got != [hb_all.read_names[i] for i in sig_all.read_id[:sig_all.n]]:
+                    verdict = "read names of the gathered signatures differ"
+            collected_by = owner.owner_of_positions(hb_all.arrays["tid"].clip(0).astype(np.int64), hb_all.arrays["pos"].astype(np.int64))[(sig_all.key[:sig_all.n] >> np.uint64(33)).astype(np.int64)]
+            ret.update(WC.layout_report(res.windows, sig_all, orc, hb_all.contig_rank, int(p.partition_max_distance), collected_by))
+            ret["proposals"] = [(WC.REFS[int(c)], int(x)) for c, x in zip(owner.cut_contig, owner.cut_pos)]
+            ret[0] = verdict
+        else:
+            ret[rank] = "ok"
+    finally:
+        dist.destroy_process_group()
+
+
 def _runs(pid):
     """(starts, ends) of the runs of equal values in pid"""
     cut = np.nonzero(np.diff(pid))[0] + 1
@@ -274,6 +326,35 @@ def test_eight_ranks_coordinate_windows_from_records_balanced():
     assert sum(1 for c, x in cuts if x > 0) >= 6, cuts
     assert ret["straddling_partitions"] == 0
     assert min(rows) > 0 and max(rows) / (sum(rows) / 8.0) < 1.4, rows
+
+
+def test_two_ranks_windows_dense_neighbourhood_without_a_corridor():
+    """The cut proposed by contig length lands in the middle of 315 kb with a signature every <= 900 bases (tests/windows_case.py: w2:125 000): nothing within
+    the 100 kb the ranks look at is a corridor, and what lies beyond was never gathered - the cut falls back to the contig's first base instead of splitting the
+    partitions of the run, and the merged tables (signatures, clusters, members, read names) are the single-rank run's.  w1, the other contig, is all corridors."""
+    ret = _run(_worker_windows_case, world=2, extra=("length",))
+    assert [ret[r] for r in range(2)] == ["ok"] * 2, ret
+    assert ret["proposals"] == [("w2", 125000)] and ret["cuts"] == [("w2", -1)], ret
+    assert ret["straddling_partitions"] == 0 and min(ret["rows_per_rank"]) > 1000 and ret["largest_partition"] > 1045
+    assert ret["foreign_rows"] > 100                                        # everything rank 0 collected of w2 belongs to rank 1 now
+    assert 0 < ret["chain0"] < ret["chain1"]
+
+
+def test_four_ranks_windows_dense_neighbourhood_and_corridors():
+    """The same records on four ranks: the cut in w1 finds a corridor and stays inside the contig with sampled DEL and INS partitions of w1 on both of its sides,
+    the cut in the dense run of w2 falls back, the third one behind the run stays.  By length and by record density (there the run is not cut at all)."""
+    ret = _run(_worker_windows_case, world=4, extra=("length",))
+    assert [ret[r] for r in range(4)] == ["ok"] * 4, ret
+    assert ret["proposals"] == [("w1", 312500), ("w2", 125000), ("w2", 437500)], ret
+    assert [c for c, _ in ret["cuts"]] == ["w1", "w2", "w2"] and ret["cuts"][0][1] > 0 and ret["cuts"][1][1] == -1 and ret["cuts"][2][1] > 320000, ret
+    assert ret["straddling_partitions"] == 0 and min(ret["rows_per_rank"]) > 0 and ret["foreign_rows"] > 100, ret
+    w1 = [e for e in ret["inside"] if e[0] == "w1"][0]
+    assert min(w1[2]) > 100 and min(w1[3]) > 100 and max(w1[2]) > 1045, ret          # (DEL below, above), (INS below, above) the cut inside w1
+    ends = [ret["chain%d" % r] for r in range(4)]
+    assert ends == sorted(ends) and ends[0] > 0
+    ret = _run(_worker_windows_case, world=4, extra=("records",))
+    assert [ret[r] for r in range(4)] == ["ok"] * 4, ret
+    assert ret["straddling_partitions"] == 0 and sum(1 for _, x in ret["cuts"] if x > 0) == 3 and min(ret["rows_per_rank"]) > 0, ret
 
 
 def test_four_ranks_signature_lists_with_foreign_rows_and_stream_relay():
