@@ -165,6 +165,15 @@ __device__ unsigned long long g_inf_prof[16];
 #ifndef INF_WIDE_STAT
 #define INF_WIDE_STAT(taken)            // host-side: a multi-window step was tried and taken with `taken` windows / given up for an ordinary one (0)
 #endif
+#ifndef INF_SEAM
+#define INF_SEAM(which)                 // host-side: the decoder went through one of its seams (tools/inflate_host_test.cpp --corpus counts them per stream)
+#endif
+#define INF_SEAM_WALK 0                 /* a code longer than its one-lookup table: canonical walk */
+#define INF_SEAM_FAR 1                  /* a match source read back from global memory (it left the ring) */
+#define INF_SEAM_FENCE 2                /* ... that may still be in flight: the fence */
+#define INF_SEAM_REFILL 3               /* the input registers loaded again */
+#define INF_SEAM_FLUSH 4                /* the pending bytes reached the flush threshold */
+#define INF_SEAM_STEPCAP 5              /* a step cut to INF_STEP_CAP bytes of output */
 
 // ---- input ----------------------------------------------------------------------------------------------------------------------------------------
 // 1 KiB of input per refill, 16 bytes per lane, loaded when a step starts in the last words of the buffer.  No prefetch register: a register with a load
@@ -174,6 +183,7 @@ __device__ unsigned long long g_inf_prof[16];
 #define INF_IN_SLACK 16u           /* words a step may read beyond its first one */
 INF_FN void inf_load_chunks(InfState& s, uint32_t cbase) {
     s.cbase = cbase;
+    INF_SEAM(INF_SEAM_REFILL);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         W_FOR { const uint32_t k = cbase + 4u * (uint32_t)W_LANE + (uint32_t)r; V2(s.c, r) = k < s.in_words ? s.in[k] : 0u; }
@@ -241,7 +251,7 @@ INF_FN void inf_flush(InfState& s, uint32_t upto) {
     }
 }
 INF_FN void inf_maybe_flush(InfState& s) {
-    if (s.pos - s.flushed >= INF_FLUSH_AT) inf_flush(s, s.pos - ((s.pos + s.mis) & 15u));       // up to the last 16-byte boundary of the destination
+    if (s.pos - s.flushed >= INF_FLUSH_AT) { INF_SEAM(INF_SEAM_FLUSH); inf_flush(s, s.pos - ((s.pos + s.mis) & 15u)); }       // up to the last 16-byte boundary of the destination
 }
 
 // ring[op, op + len) = ring[op - dist ...] with the overlap rule of LZ77 (a distance shorter than the length repeats the pattern); dist + len <= INF_RING.
@@ -280,7 +290,8 @@ INF_FN void inf_copy_near(InfState& s, uint32_t op, uint32_t dist, uint32_t len)
 INF_FN void inf_copy_far(InfState& s, uint32_t op, uint32_t dist, uint32_t len) {
     uint8_t* ring = s.sc->ring;
     W_VEC(uint32_t, v);
-    if (op - dist + len > s.clean) { W_FENCE(); s.clean = s.flushed; }
+    INF_SEAM(INF_SEAM_FAR);
+    if (op - dist + len > s.clean) { INF_SEAM(INF_SEAM_FENCE); W_FENCE(); s.clean = s.flushed; }
     for (uint32_t done = 0; done < len; done += 64u) {
         const uint32_t n = len - done < 64u ? len - done : 64u;
         W_FOR { if ((uint32_t)W_LANE < n) V(v) = s.out[op + done + (uint32_t)W_LANE - dist]; }
@@ -301,6 +312,7 @@ INF_FN int inf_match(InfState& s, uint32_t dist, uint32_t len) {
 INF_FN int inf_decode_slow(InfState& s, const uint16_t* counts, const uint16_t* symbol) {
     uint32_t bits = inf_peek(s, s.bp);
     int code = 0, first = 0, index = 0;
+    INF_SEAM(INF_SEAM_WALK);
 #pragma unroll 1
     for (int len = 1; len <= INF_MAXBITS; len++) {
         code |= (int)(bits & 1u); bits >>= 1;
@@ -420,7 +432,10 @@ INF_FN int inf_emit_bytes(InfState& s, uint64_t MT, const VecT& T, const VecT& D
     if (bad) return INF_E_DIST;                                   // a distance reaching in front of the output
     // far sources come back from the flushed output (their distance puts them in front of everything pending): wait for those stores if they may be in flight
     W_BALLOT(wait, (uint32_t)W_LANE < acc && ((V(pk) >> 23) & 1u) && s.pos + (uint32_t)W_LANE - (V(pk) & 0xffffu) >= s.clean);
-    if (wait) { W_FENCE(); s.clean = s.flushed; }
+    if (wait) { INF_SEAM(INF_SEAM_FENCE); W_FENCE(); s.clean = s.flushed; }
+#ifdef INF_HOST
+    { uint64_t far_; W_BALLOT(far_, (uint32_t)W_LANE < acc && ((V(pk) >> 23) & 1u)); if (far_) INF_SEAM(INF_SEAM_FAR); }
+#endif
     W_FOR {
         const uint32_t dist = V(pk) & 0xffffu;
         const bool m = (uint32_t)W_LANE < acc && ((V(pk) >> 22) & 1u);
@@ -481,7 +496,10 @@ INF_FN int inf_emit_bytes_multi(InfState& s, int nw, const uint64_t* MW, VecT* T
     W_BALLOT(bad, (uint32_t)W_LANE < acc && ((V(pk) >> 22) & 1u) && (V(pk) & 0xffffu) > s.pos + ((V(pk) >> 16) & 63u));
     if (bad) return INF_E_DIST;                                   // a distance reaching in front of the output
     W_BALLOT(wait, (uint32_t)W_LANE < acc && ((V(pk) >> 23) & 1u) && s.pos + (uint32_t)W_LANE - (V(pk) & 0xffffu) >= s.clean);
-    if (wait) { W_FENCE(); s.clean = s.flushed; }
+    if (wait) { INF_SEAM(INF_SEAM_FENCE); W_FENCE(); s.clean = s.flushed; }
+#ifdef INF_HOST
+    { uint64_t far_; W_BALLOT(far_, (uint32_t)W_LANE < acc && ((V(pk) >> 23) & 1u)); if (far_) INF_SEAM(INF_SEAM_FAR); }
+#endif
     W_FOR {
         const uint32_t dist = V(pk) & 0xffffu;
         const bool m = (uint32_t)W_LANE < acc && ((V(pk) >> 22) & 1u);
@@ -678,6 +696,7 @@ INF_FN int inf_codes(InfState& s) {
                 W_EXCL_SCAN(EX, OL, acc);
                 if (acc > INF_STEP_CAP) {
                     // too much output for one step (a window of maximal matches): keep the tokens that fit - a prefix of the chain
+                    INF_SEAM(INF_SEAM_STEPCAP);
                     uint64_t keep;
                     W_BALLOT(keep, ((MT >> W_LANE) & 1ull) && V(EX) + V(OL) <= INF_STEP_CAP);
                     const uint64_t dropped = MT & ~keep;
@@ -894,10 +913,12 @@ INF_FN int inflate_raw(const uint8_t* payload, uint32_t in_bytes, uint8_t* out, 
                 const int eob_len = __builtin_amdgcn_readfirstlane((int)sc.len[256]);
 #endif
                 if (eob_len == 0) return INF_E_CODELEN;                  // no end-of-block code
+                // an incomplete set is an error, with zlib's two exceptions: ONE code of ONE bit (what is left of 2^15 is then exactly 2^14), and no distance
+                // code at all - a block of literals only, as encoders other than zlib write it (its table stays empty: a length symbol then ends in INF_E_SYMBOL)
                 err = inf_build(s, sc.len + nlen, ndist, sc.cnt_d, sc.dsym, sc.fast_d, INF_FAST_D, 0, &used);
-                if (err < 0 || (err > 0 && used != 1)) return INF_E_OVERSUB;   // incomplete only allowed for a single distance code
+                if (err < 0 || (err > 0 && used != 0 && !(used == 1 && err == (1 << (INF_MAXBITS - 1))))) return INF_E_OVERSUB;
                 err = inf_build(s, sc.len, nlen, sc.cnt_l, sc.lsym, sc.fast_l, INF_FAST_L, 256, &used);
-                if (err < 0 || (err > 0 && used != 1)) return INF_E_OVERSUB;
+                if (err < 0 || (err > 0 && !(used == 1 && err == (1 << (INF_MAXBITS - 1))))) return INF_E_OVERSUB;
             }
             inf_token_luts(s);
             INF_PROF(s, 7)

@@ -157,7 +157,7 @@ INFL_FN uint32_t infl_entry_dist(uint32_t sym, uint32_t len) { return ((sym < 30
 // code lengths [first, first + n) -> a three-level table at tab (u16): the root is indexed by R bits; a root slot shared by longer codes points to a second-level
 // table indexed by the next min(INFL_L2, longest - R) bits; a second-level slot shared by still longer codes points to a third-level table indexed by the rest
 // (flat second-level tables would need 2^(15 - R) entries under the slot of the longest codes: the budget of 64 lanes' tables in LDS does not have them).
-// Markers while building: low nibble 0, longest code length through the slot << 12.  Returns 0 = built, 1 = over-subscribed code, 2 = budget exceeded
+// Markers while building: low nibble 0, longest code length through the slot << 12.  Returns 0 = built, 1 = over-subscribed or incomplete code, 2 = budget exceeded
 #ifndef INFL_L2
 #define INFL_L2 4
 #endif
@@ -180,15 +180,18 @@ INFL_FN int infl_build(uint8_t* S, Lens lens, uint32_t n, uint16_t* tab, const u
     for (uint32_t i = 0; i < n; i++) cnt[lens.next(i)]++;
     cnt[0] = 0;
     int left = 1;
-    uint32_t code = 0, longs = 0, deep = 0;
+    uint32_t code = 0, longs = 0, deep = 0, codes = 0;
     for (uint32_t l = 1; l < 16u; l++) {
         left = 2 * left - (int)cnt[l];
         if (left < 0) return 1;
+        codes += cnt[l];
         code = (code + cnt[l - 1u]) << 1;
         nxt[l] = (uint16_t)code;
         if (l > R) longs += cnt[l];
         if (l > R + INFL_L2) deep += cnt[l];
     }
+    // an incomplete set: zlib takes no code at all (the distances of a block without matches) and one code of one bit, and refuses the rest
+    if (left > 0 && codes != 0u && !(codes == 1u && cnt[1] == 1u)) return 1;
     const uint32_t root_n = 1u << R;
     uint16_t* sub = tab + root_n;
     for (uint32_t k = 0; k < root_n; k++) tab[k] = 0;

@@ -8,7 +8,10 @@ see in the files svim_amd.records.write_bam makes.
                   blocks only when they are longer than a block: one such record spans more than two blocks); or the flat layout that cuts the
                   stream every 0xff00 bytes wherever that falls
     empty blocks  EOF markers in the middle of the stream (what concatenating BGZF pieces leaves behind)
-    DEFLATE       stored blocks (level 0), level 1, fixed Huffman codes (Z_FIXED), default dynamic codes; mixed per block
+    DEFLATE       zlib's own: stored blocks (level 0), level 1, fixed Huffman codes (Z_FIXED), default dynamic codes; mixed per block.  And what zlib's
+                  compressor never writes but libdeflate (htslib), igzip (htsjdk), zlib-ng and others do: deflate= also takes a constructor policy of
+                  tests/deflate_streams.py (payload -> raw DEFLATE: one dynamic block over the whole payload with distances up to 32 768, many short
+                  blocks with their own tables, static tables only) - stand-ins built by rule, not output of those encoders
     records       SEQ '*' (l_seq = 0), read names of 1 and 254 characters, base qualities
 
 Test infrastructure only."""
@@ -77,9 +80,14 @@ def header_bytes(references, lengths, sort_order="coordinate"):
     return out
 
 
-def bgzf_block(payload, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
-    comp = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
-    cd = comp.compress(payload) + comp.flush()
+def bgzf_block(payload, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, encoder=None):
+    """encoder: payload -> raw DEFLATE bytes (a policy of tests/deflate_streams.py) instead of zlib at level / strategy"""
+    if encoder is not None:
+        cd = encoder(payload)
+        assert zlib.decompress(cd, -15) == payload
+    else:
+        comp = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+        cd = comp.compress(payload) + comp.flush()
     bsize = len(cd) + 25
     assert bsize < 65536, bsize
     return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", bsize) + cd +
@@ -88,7 +96,7 @@ def bgzf_block(payload, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
 
 def write(path, references, lengths, rec_bytes, layout="htslib", deflate=((6, zlib.Z_DEFAULT_STRATEGY),), empty_every=0, block_payload=0xff00,
           sort_order="coordinate", tids=None, index=True):
-    """rec_bytes: list of record byte strings (record_bytes).  deflate: (level, strategy) per block, cycled.  empty_every: an EOF marker block after
+    """rec_bytes: list of record byte strings (record_bytes).  deflate: (level, strategy) or an encoder (payload -> raw DEFLATE) per block, cycled.  empty_every: an EOF marker block after
     every that many data blocks.  tids (reference id per record) + index: a .bai like records.write_bai's."""
     payloads, rec_at = [], []            # rec_at: (payload index, offset inside it) of every record start
     hdr = header_bytes(references, lengths, sort_order)
@@ -123,9 +131,9 @@ def write(path, references, lengths, rec_bytes, layout="htslib", deflate=((6, zl
     block_at = []
     with open(path, "wb") as fh:
         for k, pl in enumerate(payloads):
-            level, strategy = deflate[k % len(deflate)]
+            how = deflate[k % len(deflate)]
             block_at.append(fh.tell())
-            fh.write(bgzf_block(pl, level, strategy))
+            fh.write(bgzf_block(pl, encoder=how) if callable(how) else bgzf_block(pl, *how))
             if empty_every and (k + 1) % empty_every == 0:
                 fh.write(EOF_BLOCK)
         end_at = fh.tell()

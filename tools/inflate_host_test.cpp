@@ -1,6 +1,9 @@
 // Host build of svim_amd/csrc/inflate_core.hpp (the GPU's DEFLATE decoder with the lane operations emulated), checked against zlib:
 //   inflate_host_test <file.bam|file.gz-with-BGZF-blocks>   every BGZF block of the file: inflate_raw == zlib
 //   inflate_host_test --fuzz N                              N random buffers deflated at levels 0..9 / strategies, incl. stored and fixed blocks
+//   inflate_host_test --corpus <file>                       named streams that no zlib compressor writes (tests/deflate_streams.py: write_corpus_file), sound ones and
+//                                                           ones that break a rule, at every alignment of input and output; per stream one line
+//                                                           "<name> TAB equal | refused <code> | WRONG ... TAB <seam counters>"
 // Build: g++ -O2 -std=c++17 -DINF_HOST -I svim_amd/csrc tools/inflate_host_test.cpp -lz -o /tmp/inflate_host_test
 #include <cstdint>
 static unsigned long long g_tok[2][3], g_len[2][10], g_dist[2][17], g_bytes[2];      // [path: 0 token chain, 1 serial][...]
@@ -17,6 +20,8 @@ static unsigned long long g_wide[8];                                            
 #define INF_WIDE_STAT(taken) g_wide[taken]++;
 static unsigned long long g_steps;
 #define INF_STEP_STAT() g_steps++;
+static unsigned long long g_seam[8];                                                   // INF_SEAM_*: walk, far, fence, refill, flush, stepcap
+#define INF_SEAM(which) g_seam[which]++
 #include "inflate_core.hpp"
 #include <zlib.h>
 #include <cstdio>
@@ -96,6 +101,62 @@ int main(int argc, char** argv) {
         }
         printf("damaged: %d streams, %d wrote behind their output\n", done, bad);
         return bad ? 1 : 0;
+    }
+    if (argc >= 3 && std::string(argv[1]) == "--corpus") {
+        FILE* f = fopen(argv[2], "rb");
+        if (!f) { perror("open"); return 2; }
+        std::vector<uint8_t> file;
+        { uint8_t buf[1 << 16]; size_t k; while ((k = fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + k); }
+        fclose(f);
+        size_t at = 0;
+        auto u32 = [&]() { if (at + 4 > file.size()) { fprintf(stderr, "corpus file cut short\n"); exit(2); } uint32_t v; memcpy(&v, file.data() + at, 4); at += 4; return v; };
+        const uint32_t n = u32();
+        int wrong = 0;
+        for (uint32_t it = 0; it < n; it++) {
+            const uint32_t nl = u32(); const std::string name((const char*)file.data() + at, nl); at += nl;
+            const uint32_t clen = u32(); const uint8_t* comp = file.data() + at; at += clen;
+            const uint32_t size = u32(); const bool valid = file[at++] != 0;
+            std::vector<uint8_t> expect;
+            if (valid) {                                                    // zlib's answer is the expectation (and the file's label is held to it)
+                expect.resize(size + 1u);
+                z_stream zs; memset(&zs, 0, sizeof zs);
+                inflateInit2(&zs, -15);
+                zs.next_in = const_cast<Bytef*>(comp); zs.avail_in = clen; zs.next_out = expect.data(); zs.avail_out = size + 1u;
+                const int rc = inflate(&zs, Z_FINISH);
+                const bool ok = rc == Z_STREAM_END && zs.total_out == size;
+                inflateEnd(&zs);
+                if (!ok) { fprintf(stderr, "zlib refuses %s, labelled sound\n", name.c_str()); return 2; }
+                expect.resize(size);
+            }
+            memset(g_seam, 0, sizeof g_seam); memset(g_wide, 0, sizeof g_wide);
+            std::string verdict; int first_rc = 0;
+            for (unsigned shift = 0; shift < 8 && verdict.compare(0, 5, "WRONG") != 0; shift++) {     // input at every byte alignment, output at eight of its sixteen
+                std::vector<uint32_t> in((clen + 3) / 4 + 6, 0);
+                uint8_t* payload = reinterpret_cast<uint8_t*>(in.data()) + shift;
+                memcpy(payload, comp, clen);
+                const unsigned oshift = (5u * shift) & 15u;
+                std::vector<uint8_t> outbuf(size + 48, 0xAA);
+                uint8_t* out = outbuf.data() + 16 + oshift;                    // (guard bytes in front and behind)
+                InfScratch sc;
+                const int rc = inflate_raw(payload, clen, out, size, sc);
+                bool guard = true;
+                for (size_t i = 0; i < 16 + oshift; i++) guard = guard && outbuf[i] == 0xAA;
+                for (size_t i = 16 + oshift + size; i < outbuf.size(); i++) guard = guard && outbuf[i] == 0xAA;
+                std::string v;
+                if (!guard) v = "WRONG wrote outside the output";
+                else if (valid) v = rc == (int)size && memcmp(out, expect.data(), size) == 0 ? "equal" : "WRONG rc " + std::to_string(rc) + " for " + std::to_string(size) + " bytes";
+                else v = rc == (int)size ? "WRONG accepted" : "refused " + std::to_string(rc);
+                if (shift == 0) { verdict = v; first_rc = rc; }
+                else if (v != verdict) verdict = "WRONG differs by alignment (" + std::to_string(shift) + "): " + v + " / " + verdict;
+            }
+            (void)first_rc;
+            if (verdict.compare(0, 5, "WRONG") == 0) wrong++;
+            printf("%s\t%s\twalk %llu far %llu fence %llu refill %llu flush %llu stepcap %llu wide2 %llu wide3 %llu wide4 %llu\n", name.c_str(), verdict.c_str(),
+                   g_seam[INF_SEAM_WALK], g_seam[INF_SEAM_FAR], g_seam[INF_SEAM_FENCE], g_seam[INF_SEAM_REFILL], g_seam[INF_SEAM_FLUSH], g_seam[INF_SEAM_STEPCAP],
+                   g_wide[2], g_wide[3], g_wide[4]);
+        }
+        printf("corpus: %u streams, %d wrong\n", n, wrong);
+        return wrong ? 1 : 0;
     }
     if (argc >= 3 && std::string(argv[1]) == "--fuzz") {
         const int n = atoi(argv[2]);

@@ -2,6 +2,8 @@
 //   inflate_lanes_host_test <file.bam>     every BGZF block of the file: decoded == zlib, or given up (counted; the GPU redoes those with the wave-per-block decoder)
 //   inflate_lanes_host_test --fuzz N       N random buffers deflated at levels 0..9 / every strategy
 //   inflate_lanes_host_test --damaged N    damaged streams: an answer or a refusal, never a write outside the output and never more than a bounded number of trips
+//   inflate_lanes_host_test --corpus <file>  named streams that no zlib compressor writes (tests/deflate_streams.py: write_corpus_file), at every alignment; per stream
+//                                          one line "<name> TAB equal | given up <site> | WRONG ..." (a stream that breaks a rule must be given up)
 // Build: g++ -O2 -std=c++17 -DINFL_HOST -I svim_amd/csrc tools/inflate_lanes_host_test.cpp -lz -o /tmp/inflate_lanes_host_test
 #include <cstdint>
 static unsigned long long g_sub_hist[2][9], g_stall, g_trips, g_hdrs, g_sub_max[2];
@@ -116,6 +118,39 @@ int main(int argc, char** argv) {
         }
         printf("fuzz: %d buffers, %d mismatches, %d decoded, %d given up (stored blocks, codes beyond the table budget)\n", n, bad, ok, gave_up);
         return bad ? 1 : 0;
+    }
+    if (argc >= 3 && std::string(argv[1]) == "--corpus") {
+        FILE* f = fopen(argv[2], "rb");
+        if (!f) { perror(argv[2]); return 2; }
+        std::vector<uint8_t> file;
+        { uint8_t buf[1 << 16]; size_t k; while ((k = fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + k); }
+        fclose(f);
+        size_t at = 0;
+        auto u32 = [&]() { if (at + 4 > file.size()) { fprintf(stderr, "corpus file cut short\n"); exit(2); } uint32_t v; memcpy(&v, file.data() + at, 4); at += 4; return v; };
+        const uint32_t n = u32();
+        int wrong = 0;
+        for (uint32_t it = 0; it < n; it++) {
+            const uint32_t nl = u32(); const std::string name((const char*)file.data() + at, nl); at += nl;
+            const uint32_t clen = u32(); const std::vector<uint8_t> comp(file.data() + at, file.data() + at + clen); at += clen;
+            const uint32_t size = u32(); const bool valid = file[at++] != 0;
+            std::vector<uint8_t> expect;
+            if (valid && !zlib_ok(comp, size, expect)) { fprintf(stderr, "zlib refuses %s, labelled sound\n", name.c_str()); return 2; }
+            std::string verdict;
+            for (unsigned shift = 0; shift < 8; shift++) {
+                unsigned long long before[16]; memcpy(before, g_fail_site, sizeof before);
+                const int rc = run_lane(comp.data(), comp.size(), valid ? &expect : nullptr, size, shift);
+                std::string v;
+                if (rc < 0) v = "WRONG";
+                else if (rc == 1) v = valid ? "equal" : "WRONG accepted";
+                else { int site = 0; for (int k = 1; k < 16; k++) if (g_fail_site[k] != before[k]) site = k; v = "given up " + std::to_string(site); }
+                if (shift == 0) verdict = v;
+                else if (v != verdict && verdict.compare(0, 5, "WRONG") != 0) verdict = "WRONG differs by alignment (" + std::to_string(shift) + "): " + v + " / " + verdict;
+            }
+            if (verdict.compare(0, 5, "WRONG") == 0) wrong++;
+            printf("%s\t%s\n", name.c_str(), verdict.c_str());
+        }
+        printf("corpus: %u streams, %d wrong\n", n, wrong);
+        return wrong ? 1 : 0;
     }
     if (argc >= 3 && std::string(argv[1]) == "--damaged") {
         const int n = atoi(argv[2]);
