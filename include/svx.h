@@ -203,6 +203,11 @@ int  svx_collect_set_slot_base(svx_ctx* ctx, uint64_t slot_base);
 int  svx_collect_count(svx_ctx* ctx, int64_t* n_sig, int64_t* n_seq_bytes, int64_t* n_bnd_side);
 /* which: 0 = sv_signatures, 1 = translocation_signatures_all_bnds (second list of the reference's tuple) */
 int  svx_collect_fetch(svx_ctx* ctx, int which, svx_sig_view* host_out);
+/* geometry table of the last svx_collect: five int32 per item {reference length, query_alignment_start, query_alignment_end, infer_read_length (0: None),
+ * hard-clipped bases}, the n_rec records first, then the n_seg segment rows.  Filled in for every segment row and for the records whose split-read analysis
+ * runs (pass the filters, not supplementary, own segment rows); other entries are undefined.  Inspection hook (tests compare it with the oracle's);
+ * NULL array: counts only */
+int  svx_collect_geom_fetch(svx_ctx* ctx, int64_t* n_rec, int64_t* n_seg, int32_t* geom /* [5 * (n_rec + n_seg)], host */);
 
 /* ---- the reference genome from a FASTA file, parsed on the device: replaces FastaFile(options.genome) (src/svim/SVIM_clustering.py:377) ----------
  * The bytes of the file (plain text; BGZF, inflated by the device; any other gzip file, inflated by zlib on the host) go into HBM whole, through page-locked

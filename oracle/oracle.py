@@ -57,6 +57,13 @@ class Oracle(object):
             out.append(t)
         return out[0], out[1]
 
+    def collect_geometry(self, hb):
+        """geometry of every record and segment row of the batch, as Engine.collect_geometry lays it out: (int32[n_rec, 5], int32[n_seg, 5])"""
+        b = hb.struct() if hasattr(hb, "struct") else hb
+        g = np.zeros((max(1, b.n_rec + b.n_seg), 5), dtype=np.int32)
+        self.L.svo_collect_geom(C.byref(b), ptr(g))
+        return g[:b.n_rec], g[b.n_rec:b.n_rec + b.n_seg]
+
     def set_genome(self, off, codes):
         g = _abi.Genome(0, len(off) - 1, ptr(off), ptr(codes))
         self._keep = [off, codes]

@@ -435,6 +435,17 @@ int svo_collect(svo_ctx* ctx, const svx_batch* b, const svx_params* p) {
     ctx->stats.n_sig = t->n; ctx->stats.n_bnd_side = ctx->bnd.n; ctx->stats.n_ins_bases = tot;
     return 0;
 }
+/* the geometry of every record and, behind them, of every segment row, as svx_collect_geom_fetch lays it out (five int32 per item) */
+int svo_collect_geom(const svx_batch* b, int32_t* out) {
+    for (int64_t w = 0; w < b->n_rec + b->n_seg; w++) {
+        const int64_t s = w - b->n_rec;
+        const uint64_t o0 = w < b->n_rec ? b->cigar_off[w] : b->seg_cigar_off[s], o1 = w < b->n_rec ? b->cigar_off[w + 1] : b->seg_cigar_off[s + 1];
+        geom g = cigar_geom((w < b->n_rec ? b->cigar : b->seg_cigar) + o0, (int64_t)(o1 - o0), w < b->n_rec ? b->lseq[w] : b->seg_lseq[s]);
+        int32_t* o = out + 5 * w;
+        o[0] = (int32_t)g.ref_len; o[1] = (int32_t)g.qstart; o[2] = (int32_t)g.qend; o[3] = g.has_cigar ? (int32_t)g.read_len : 0; o[4] = (int32_t)g.hard;
+    }
+    return 0;
+}
 int svo_collect_count(svo_ctx* ctx, int64_t* n_sig, int64_t* n_seq, int64_t* n_bnd) {
     *n_sig = ctx->sig.n; *n_seq = ctx->sig_seq_off ? ctx->sig_seq_off[ctx->sig.n] : 0; *n_bnd = ctx->bnd.n; return 0;
 }

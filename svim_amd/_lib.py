@@ -18,7 +18,7 @@ _LIB = None
 _ENGINES = {}
 
 SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version", "svx_get_stats", "svx_stream", "svx_cluster_partitions_fetch", "svx_memcpy_d2h", "svx_memcpy_h2d", "svx_dev_alloc", "svx_dev_free", "svx_host_alloc", "svx_host_free", "svx_device_synchronize", "svx_selftest_prims", "svx_bam_set_device_decode",
-           "svx_collect", "svx_collect_count", "svx_collect_fetch", "svx_collect_accumulate", "svx_collect_set_slot_base", "svx_set_genome", "svx_cluster",
+           "svx_collect", "svx_collect_count", "svx_collect_fetch", "svx_collect_geom_fetch", "svx_collect_accumulate", "svx_collect_set_slot_base", "svx_set_genome", "svx_cluster",
            "svx_cluster_count", "svx_cluster_fetch", "svx_cluster_set_ranks", "svx_cluster_abort_ranks", "svx_cluster_stream_positions",
            "svx_set_alignment_index", "svx_genotype",
            "svx_cigar_indel", "svx_edit_distance", "svx_linkage_fcluster", "svx_pair_distances",
@@ -187,6 +187,14 @@ class Engine(object):
         v = t.view()
         _check(self.L.svx_collect_fetch(self.ctx, which, C.byref(v)), "svx_collect_fetch")
         return t
+
+    def collect_geometry(self):
+        """geometry table of the last collect() (svx_collect_geom_fetch): (records int32[n_rec, 5], segment rows int32[n_seg, 5]); which entries are defined: svx.h"""
+        nr, ns = C.c_int64(), C.c_int64()
+        _check(self.L.svx_collect_geom_fetch(self.ctx, C.byref(nr), C.byref(ns), None), "svx_collect_geom_fetch")
+        g = np.zeros((max(1, nr.value + ns.value), 5), dtype=np.int32)
+        _check(self.L.svx_collect_geom_fetch(self.ctx, None, None, ptr(g)), "svx_collect_geom_fetch")
+        return g[:nr.value], g[nr.value:nr.value + ns.value]
 
     # ---- CLUSTER ----
     def set_genome(self, off, codes, on_device=False):

@@ -504,6 +504,23 @@ extern "C" int svx_cluster_partitions_fetch(svx_ctx* c, int64_t* n_sig, int64_t*
     return hc.finish();
 }
 
+// The geometry table of the last svx_collect: one record of five int32 per BAM record, then one per segment-table row - {reference length,
+// query_alignment_start, query_alignment_end, infer_read_length (0: None), hard-clipped bases}.  Only the items COLLECT needs geometry for are filled in: every
+// segment row, and the records that pass the filters, are not supplementary and own segment rows; the other records' entries are undefined.
+// A test / inspection hook like svx_cluster_partitions_fetch.  NULL array: counts only.
+extern "C" int svx_collect_geom_fetch(svx_ctx* c, int64_t* n_rec, int64_t* n_seg, int32_t* geom) {
+    if (!c) return svx_fail(SVX_E_ARG, "null context", __FILE__, __LINE__, hipSuccess);
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n = c->geom_n_rec + c->geom_n_seg;
+    if (n_rec) *n_rec = c->geom_n_rec;
+    if (n_seg) *n_seg = c->geom_n_seg;
+    if (n <= 0 || !geom) return SVX_OK;
+    if (!c->rec_geom.p) return svx_fail(SVX_E_STATE, "no geometry table: run svx_collect first", __FILE__, __LINE__, hipSuccess);
+    HostCopy hc(c->stream);
+    SVXCHK(hc.d2h(geom, c->rec_geom.p, (size_t)n * 5 * 4));
+    return hc.finish();
+}
+
 // ---- single-function entry points ------------------------------------------------------------------------------
 extern "C" int svx_cigar_indel(svx_ctx* c, const uint32_t* cigar_host, int64_t n_ops, int32_t min_length, int64_t* out_pos_ref,
                                int64_t* out_pos_read, int32_t* out_len, uint8_t* out_is_del, int64_t* out_n) {

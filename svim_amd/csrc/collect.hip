@@ -14,9 +14,13 @@
 #include "common.hpp"
 #include <cstdlib>
 
-enum { CNT_SIG = 0, CNT_BND = 1, CNT_USED = 2, CNT_OPS = 3, CNT_SEGOPS = 4, CNT_INS_BASES = 5, CNT_RAW = 6, CNT_OVERFLOW = 7, CNT_SEQ_MISSING = 8 };
+enum { CNT_SIG = 0, CNT_BND = 1, CNT_USED = 2, CNT_OPS = 3, CNT_SEGOPS = 4, CNT_INS_BASES = 5, CNT_RAW = 6, CNT_OVERFLOW = 7, CNT_SEQ_MISSING = 8, CNT_SHARD_MAX = 9 };
 #define RAW_SHARDS 8192      /* one private raw-output region per persistent wave: no allocation atomics at all in the scan
                                 (a single global counter serialised the launch at ~12 ns per same-address atomic) */
+
+/* A wave whose items hold more reportable operations than its region takes makes the call run again with regions sized by the fullest wave (k_shard_prefix
+   reports it), so the regions of one call may grow to this many bytes before COLLECT gives up with SVX_E_CAPACITY ("What a dense read costs") */
+#define SCAN_RAW_MAX_BYTES (8ull << 30)
 
 #define KEY(slot, phase, ord) (((uint64_t)(slot) << 32) | ((uint64_t)(phase) << 30) | (uint64_t)(ord))
 
@@ -357,14 +361,15 @@ __global__ __launch_bounds__(1024) void k_shard_prefix(const unsigned long long*
     __shared__ long long s[1024];
     const int t = threadIdx.x;
     constexpr int PER = RAW_SHARDS / 1024;
-    long long loc[PER]; long long sum = 0; unsigned long long over = 0;
+    long long loc[PER]; long long sum = 0; unsigned long long over = 0, most = 0;
 #pragma unroll
     for (int k = 0; k < PER; k++) {
         unsigned long long c = shard_counter[t * PER + k];
-        if ((long long)c > shard_cap) { over += c - (unsigned long long)shard_cap; c = (unsigned long long)shard_cap; }
+        if ((long long)c > shard_cap) { over += c - (unsigned long long)shard_cap; most = c > most ? c : most; c = (unsigned long long)shard_cap; }
         loc[k] = sum; sum += (long long)c;
     }
-    if (over) atomicAdd(&counters[CNT_OVERFLOW], over);
+    // (rare) what did not fit, and the count of the fullest wave: the region size with which the next attempt fits whatever the batch holds
+    if (over) { atomicAdd(&counters[CNT_OVERFLOW], over); atomicMax(&counters[CNT_SHARD_MAX], most); }
     s[t] = sum;
     __syncthreads();
     for (int o = 1; o < 1024; o <<= 1) { const long long v = (t >= o) ? s[t - o] : 0; __syncthreads(); s[t] += v; __syncthreads(); }
@@ -700,6 +705,7 @@ static int order_and_store(svx_ctx* c, DevSigs& raw, DevSigs& out, int64_t n) {
 int svx_collect_impl(svx_ctx* c, const svx_batch* bd, const svx_params* p) {
     hipStream_t st = c->stream;
     const svx_batch& b = *bd;
+    c->geom_n_rec = c->geom_n_seg = 0;
     SVXCHK(c->counters.reserve(16 * 8));
     // geometry records of the records and, behind them, of the segment rows (one array: the scan addresses it by item); seg_geom holds the scan's item table
     SVXCHK(c->rec_geom.reserve((size_t)(b.n_rec + b.n_seg + 2) * 5 * 4));
@@ -720,7 +726,9 @@ int svx_collect_impl(svx_ctx* c, const svx_batch* bd, const svx_params* p) {
     if (cap_bnd < 1024) cap_bnd = 1024;
     if (p->all_bnds && cap_bnd < want_sig) cap_bnd = want_sig;
     unsigned long long h_cnt[16];
-    for (int attempt = 0; attempt < 3; attempt++) {
+    // At most two passes by construction: the first reports every count in full (a wave goes on counting what its region no longer takes, the two list
+    // counters go on counting behind their capacities), the second is sized from those counts.
+    for (int attempt = 0;; attempt++) {
         SVXCHK(c->raw_sig.reserve(cap_sig));
         SVXCHK(c->raw_bnd.reserve(cap_bnd));
         HIPCHK(hipMemsetAsync(c->counters.p, 0, 16 * 8, st));
@@ -731,18 +739,29 @@ int svx_collect_impl(svx_ctx* c, const svx_batch* bd, const svx_params* p) {
         if (items > 0) {
             long long blocks = (items + 3) / 4;
             if (items >= (1ll << 31)) return svx_fail(SVX_E_ARG, "more than 2^31 records + segment rows in one batch", __FILE__, __LINE__, hipSuccess);
-            static int per_cu = 0;                                         // resident 256-thread blocks per CU for this kernel
-            { const char* f = getenv("SVX_SCAN_BLOCKS"); if (f) per_cu = atoi(f); }
-            if (!per_cu) {
+            static int occ_per_cu = 0;                                     // resident 256-thread blocks per CU for this kernel (the query is made once per process)
+            if (!occ_per_cu) {
                 int occ = 0;
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_cigar_scan, 256, 0) != hipSuccess || occ < 1) occ = 4;
-                per_cu = occ > 8 ? 8 : occ;                                // 8 blocks = 8 waves per SIMD: the kernel is built for <= 64 VGPRs / <= 80 SGPRs (Makefile check)
+                occ_per_cu = occ > 8 ? 8 : occ;                            // 8 blocks = 8 waves per SIMD: the kernel is built for <= 64 VGPRs / <= 80 SGPRs
             }
+            int per_cu = occ_per_cu;
+            { const char* f = getenv("SVX_SCAN_BLOCKS"); const int v = f ? atoi(f) : 0; if (v > 0) per_cu = v; }      // read on every call: it holds while it is set, no longer
             long long max_blocks = (long long)c->n_cu * per_cu;
             if (max_blocks > RAW_SHARDS / 4) max_blocks = RAW_SHARDS / 4;
             if (blocks > max_blocks) blocks = max_blocks;
-            const long long shard_cap = (c->raw_sig.cap + RAW_SHARDS - 1) / RAW_SHARDS;
-            SVXCHK(c->raw_indel.reserve((size_t)shard_cap * RAW_SHARDS * sizeof(RawIndel)));
+            // region w belongs to wave w of the grid: only the regions of the waves that exist need memory
+            long long shard_cap = (c->raw_sig.cap + RAW_SHARDS - 1) / RAW_SHARDS;
+            if (shard_cap < c->scan_shard_cap) shard_cap = c->scan_shard_cap;
+            const unsigned long long raw_bytes = (unsigned long long)shard_cap * (unsigned long long)(blocks * 4) * sizeof(RawIndel);
+            if (raw_bytes > SCAN_RAW_MAX_BYTES) {
+                char msg[256];
+                snprintf(msg, sizeof msg, "CIGAR scan: the items of one wave hold %lld reportable I/D operations, and %lld regions of that size exceed %llu GiB (DESIGN.md, "
+                         "\"What a dense read costs\")", shard_cap, blocks * 4, SCAN_RAW_MAX_BYTES >> 30);
+                c->scan_shard_cap = 0;
+                return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
+            }
+            SVXCHK(c->raw_indel.reserve((size_t)raw_bytes));
             SVXCHK(c->shard_cnt.reserve((size_t)RAW_SHARDS * 8 + (size_t)(RAW_SHARDS + 1) * 8));
             unsigned long long* shard_counter = c->shard_cnt.as<unsigned long long>();
             long long* shard_prefix = reinterpret_cast<long long*>(shard_counter + RAW_SHARDS);
@@ -777,9 +796,11 @@ int svx_collect_impl(svx_ctx* c, const svx_batch* bd, const svx_params* p) {
         if (b.n_rec > 0) k_count_used<<<(unsigned)std::min<long long>((b.n_rec + 255) / 256, 1024), 256, 0, st>>>(b, *p, c->counters.as<unsigned long long>());
         SVXCHK(svx_mail_read(c, st, c->counters.p, 16, h_cnt));
         if ((int64_t)h_cnt[CNT_SIG] <= c->raw_sig.cap && (int64_t)h_cnt[CNT_BND] <= c->raw_bnd.cap && h_cnt[CNT_OVERFLOW] == 0) break;
-        if (attempt == 2) return svx_fail(SVX_E_CAPACITY, "signature buffers", __FILE__, __LINE__, hipSuccess);
-        cap_sig = 2 * ((int64_t)h_cnt[CNT_SIG] + (int64_t)h_cnt[CNT_OVERFLOW]) + 64 * (int64_t)RAW_SHARDS; cap_bnd = (int64_t)h_cnt[CNT_BND] + 1024;
-        if (cap_sig < 4 * c->raw_sig.cap && h_cnt[CNT_OVERFLOW]) cap_sig = 4 * c->raw_sig.cap;     // shard imbalance: grow generously
+        if (attempt == 2) return svx_fail(SVX_E_STATE, "signature buffers sized from the counts of the pass before do not hold this pass (internal error)", __FILE__, __LINE__, hipSuccess);
+        // the main list: what was stored or counted, plus what the waves dropped; the side list: every dropped record may be a deletion that goes there too
+        cap_sig = 2 * ((int64_t)h_cnt[CNT_SIG] + (int64_t)h_cnt[CNT_OVERFLOW]) + 64 * (int64_t)RAW_SHARDS;
+        cap_bnd = (int64_t)h_cnt[CNT_BND] + (p->all_bnds ? (int64_t)h_cnt[CNT_OVERFLOW] : 0) + 1024;
+        if (h_cnt[CNT_OVERFLOW]) c->scan_shard_cap = (long long)h_cnt[CNT_SHARD_MAX];      // the same items go to the same waves again: every region fits (kept for later calls)
     }
     const int64_t n_sig = (int64_t)h_cnt[CNT_SIG], n_bnd = (int64_t)h_cnt[CNT_BND];
     SVXCHK(order_and_store(c, c->raw_sig, c->sig, n_sig));
@@ -823,6 +844,7 @@ int svx_collect_impl(svx_ctx* c, const svx_batch* bd, const svx_params* p) {
     HIPCHK(hipEventElapsedTime(&ms, c->ev[0], c->ev[4])); s.t_collect_ms = ms;
     s.n_rec_used = (int64_t)h_cnt[CNT_USED]; s.n_ops = (int64_t)h_cnt[CNT_OPS]; s.n_seg = b.n_seg; s.n_seg_ops = (int64_t)tot_seg_ops;
     s.n_sig = n_sig; s.n_bnd_side = n_bnd; s.n_ins_bases = n_seq;
+    c->geom_n_rec = b.n_rec; c->geom_n_seg = b.n_seg;
     return SVX_OK;
 }
 

@@ -146,6 +146,8 @@ struct svx_ctx {
     DevBuf shard_cnt;               // per-shard allocation counters + prefix of the raw indel buffer
     DevBuf raw_indel;               // RawIndel records written by the scan kernel
     DevBuf rec_geom, seg_geom;      // int32 x 5 per record / per segment row
+    long long scan_shard_cap = 0;   // raw records per wave-private region of the scan that a batch of this context has needed (0: the default sizing was enough so far)
+    int64_t geom_n_rec = 0, geom_n_seg = 0;      // items of the geometry table the last COLLECT call left in rec_geom (svx_collect_geom_fetch)
     DevBuf seg_ws;                  // segment analysis workspace
     DevBuf tmp0, tmp1, tmp2, tmp3, tmp4, tmp5, sort_tmp, scan_tmp;
     // genome
