@@ -2,7 +2,10 @@
 """bench.py - COLLECT+CLUSTER throughput on MI355X (BASELINE.json metric: aligned reads/sec through
 COLLECT+CLUSTER; SV signatures/sec clustered).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1                          # configs[1], the configuration the metric is quoted on
+    python bench.py --gpus 1 --steps 3 --warmup 1                          # configs[1], the configuration the metric is quoted on: set-up, warm-up, the timed steps, one line
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full                   # + what takes runs of its own: end_to_end (a BAM file through the device reader), cpu_baseline (the
+                                                                           # oracle on one host core, parity on 100 000 records), the speed-ups over it, clusters_by_type;
+                                                                           # with --gpus N > 1 the strong_scaling block (--no-end-to-end / --no-cpu-baseline leave one out)
     python bench.py --workload c2                                          # configs[2] stand-in: HiFi profile, full SV-type set
     python bench.py --workload c4 --partition-max-distance 20000           # configs[4] stand-in: 60x CLR profile, large partitions
     python bench.py --bam reads.bam --fasta ref.fa                         # a real coordinate-sorted BAM (configs[2]-[4] proper)
@@ -367,8 +370,12 @@ def main():
                     "ANOTHER rank, so that BND signatures owned by other ranks (foreign rows) cross the fabric in the timed step")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the tables the last of them left for its caller (signatures, "
                     "BND sides, clusters) as DIR/<name>.npy, float32 / float64, at most 64 MB in all; the synthetic workloads on one rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true")
+    ap.add_argument("--full", action="store_true", help="beside the headline figure: the end_to_end block (a BAM file through the device reader, in a child process), "
+                    "the cpu_baseline block (the oracle on a slice of the batch, on one host core, and its parity with the device path on 100 000 records), the "
+                    "speed-ups that divide by it, counts.clusters_by_type and, with --gpus N > 1, the strong_scaling block.  Off by default: a plain run sets up, warms "
+                    "up, times its steps, writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its cpu_baseline block")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without its end_to_end block")
     ap.add_argument("--end-to-end-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--e2e-records-qual", type=int, default=300_000, help="end_to_end: records of the sample BAM with base qualities (the headline file)")
     ap.add_argument("--e2e-records", type=int, default=180_000, help="end_to_end: records of the sample BAM without qualities (side figure)")
@@ -548,14 +555,16 @@ def main():
         tot_used, tot_sig, tot_ops = (int(x) for x in cnt.tolist())
         # With more than one rank the weak-scaling value is linear by construction; the line therefore also carries a STRONG-scaling measurement (one whole-genome
         # batch, configs[3]'s shape at a tenth of its size, sharded by coordinate windows) - measure_strong at N ranks; the same block at N=1 is the reference point
+        # (a measurement of its own, on another batch: --full)
         strong_block = None
-        try:
-            sb = measure_strong(args, rank, world, local_rank, dev, True, dist, opts, p, max(2, min(args.steps, 3)), 1, scale_default=0.1)
-            if rank == 0:
-                strong_block = {k: sb[k] for k in ("value", "unit", "n_gpus", "ms_per_step", "scaling", "config", "counts", "ownership", "multi_gpu")}
-                strong_block["how_to_read"] = "value(N) / value(1) of THIS block is the strong-scaling speedup (same total work at every N); python bench.py --scaling strong --scale 0.1 gives value(1)"
-        except Exception as e:                                        # the headline line stands whatever happens here
-            strong_block = {"error": repr(e)}
+        if args.full:
+            try:
+                sb = measure_strong(args, rank, world, local_rank, dev, True, dist, opts, p, max(2, min(args.steps, 3)), 1, scale_default=0.1)
+                if rank == 0:
+                    strong_block = {k: sb[k] for k in ("value", "unit", "n_gpus", "ms_per_step", "scaling", "config", "counts", "ownership", "multi_gpu")}
+                    strong_block["how_to_read"] = "value(N) / value(1) of THIS block is the strong-scaling speedup (same total work at every N); python bench.py --scaling strong --scale 0.1 gives value(1)"
+            except Exception as e:                                    # the headline line stands whatever happens here
+                strong_block = {"error": repr(e)}
         MG.barrier()
         dist.destroy_process_group()                                  # all ranks together, before rank 0 goes on alone
     else:
@@ -660,17 +669,18 @@ def main():
     if args.dump_outputs:
         out["dumped_outputs"] = dumped
     if use_dist:
-        out["strong_scaling"] = strong_block
+        if args.full:
+            out["strong_scaling"] = strong_block
         res = last.get("res")
         out["multi_gpu"] = {"foreign_segments_planted_rank0": n_foreign_planted, "signatures_per_rank": list(res.sig_counts) if res is not None else None,
                             "clusters_gathered": res.n if res is not None else None, "stream_end_rank0": res.chain_end if res is not None else None,
                             "rank_exchange_allgathers_last_step": getattr(getattr(adapter, "transport", None), "calls", 0)}
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         fetch = getattr(eng, "fetch_clusters", None)
         if fetch is not None:
             ct = eng.fetch_clusters()
             out["counts"]["clusters_by_type"] = dict(zip(_abi.TYPE_NAMES, [int(x) for x in ct.type_count]))
-    if not args.no_end_to_end and world == 1 and not use_dist and args.workload == "c1":
+    if args.full and not args.no_end_to_end and world == 1 and not use_dist and args.workload == "c1":
         # The end-to-end sample (BAM file -> reader with GPU-assisted inflate -> pipeline) runs in a process of its own: whatever happens there,
         # the headline number above stands.  The child regenerates the same batch from its seed.
         import subprocess
@@ -683,7 +693,7 @@ def main():
             out["end_to_end"] = json.loads(lines[-1]) if child.returncode == 0 and lines else {"error": "exit %d: %s" % (child.returncode, child.stderr[-400:])}
         except Exception as e:
             out["end_to_end"] = {"error": repr(e)}
-    if not args.no_cpu_baseline and world == 1 and not use_dist:           # the CPU baseline is a rank-0, N=1 measurement
+    if args.full and not args.no_cpu_baseline and world == 1 and not use_dist:           # the CPU baseline is a rank-0, N=1 measurement
         out["cpu_baseline"] = cpu_baseline(batch, g_off, genome, p, eng)
         out["speedup_vs_cpu_port"] = reads_per_s / world / out["cpu_baseline"]["value"]
         e2e = (out.get("end_to_end") or {}).get("bam_file_reads_per_s")

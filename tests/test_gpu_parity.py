@@ -1394,6 +1394,45 @@ def test_bench_dump_outputs_repeat_and_hold_the_last_steps_tables(tmp_path):
     assert set(np.unique(a["signatures_type"])) <= {0.0, 1.0, 2.0} and a["signatures_seq"].max() <= 15
 
 
+def test_bench_plain_line_is_lean_and_full_adds_the_bam_file_and_cpu_baseline_blocks():
+    """bench.py without --full: set-up, warm-up, the timed steps and the line - no end_to_end, no cpu_baseline, no speed-up over it, no clusters_by_type (and
+    --no-cpu-baseline / --no-end-to-end change nothing there).  With --full the same headline fields and counts, and beside them the end_to_end block (a BAM file
+    through the device reader, from a child process), the cpu_baseline block with its parity sample (device path == oracle), the speed-ups, clusters_by_type."""
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--reads", "100000", "--contig-len", "25000000"]
+    plain = _run_bench(common, 1, {})
+    also_plain = _run_bench(common + ["--no-cpu-baseline", "--no-end-to-end"], 1, {})
+    full = _run_bench(common + ["--full", "--e2e-records", "20000", "--e2e-records-qual", "30000"], 1, {})
+    moved = {"end_to_end", "cpu_baseline", "speedup_vs_cpu_port", "speedup_vs_cpu_port_from_bam_file", "speedup_note", "strong_scaling"}
+    assert not moved & set(plain) and "clusters_by_type" not in plain["counts"]
+    assert set(plain) == set(also_plain) and set(full) - set(plain) == moved - {"strong_scaling"}
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "config"):
+        assert plain[k] == also_plain[k] == full[k], k
+    assert plain["value"] > 0 and abs(plain["value"] * plain["ms_per_step"] * 1e-3 - plain["counts"]["reads_used"]) < 1e-6 * plain["counts"]["reads_used"]
+    by_type = full["counts"].pop("clusters_by_type")
+    assert plain["counts"] == also_plain["counts"] == full["counts"] and sum(by_type.values()) == full["counts"]["clusters"] > 1000
+    e2e, cpu = full["end_to_end"], full["cpu_baseline"]
+    assert "error" not in e2e and e2e["bam_file_reads_per_s"] > 0 and e2e["bam_file"]["records"] == 30000 and e2e["resident_reads_per_s"] == full["value"]
+    par = cpu["parity_vs_gpu_on_sample"]
+    assert par["signatures_identical"] and par["clusters_identical"] and par["records"] >= 100000 and par["clusters"] > 1000
+    assert cpu["cores"] == 1 and cpu["value"] > 0 and abs(full["speedup_vs_cpu_port"] * cpu["value"] - full["value"]) < 1e-6 * full["value"]
+    assert abs(full["speedup_vs_cpu_port_from_bam_file"] * cpu["value"] - e2e["bam_file_reads_per_s"]) < 1e-6 * e2e["bam_file_reads_per_s"]
+
+
+def test_bench_two_ranks_one_gpu_full_adds_the_strong_scaling_block():
+    """the weak-scaling line of two ranks (both on cuda:0 over gloo) carries its strong-scaling measurement - one batch of the same profile, the same on both ranks,
+    sharded by coordinate windows - with --full only; the headline fields of the line do not depend on it."""
+    args = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "c2", "--scale", "0.02", "--partition-max-distance", "5000"]
+    env = {"SVX_BENCH_BACKEND": "gloo", "SVX_BENCH_ONE_GPU": "1"}
+    plain, full = _run_bench(args, 2, env), _run_bench(args + ["--full"], 2, env)
+    assert "strong_scaling" not in plain and set(full) - set(plain) == {"strong_scaling"}
+    sb = full["strong_scaling"]
+    assert "error" not in sb and sb["scaling"] == "strong" and sb["n_gpus"] == 2 and sb["value"] > 0 and sb["counts"]["clusters_gathered"] > 100
+    assert len(sb["ownership"]["signatures_collected_per_rank"]) == 2 and sb["multi_gpu"]["world_size_seen_by_the_process_group"] == 2
+    for k in ("metric", "unit", "higher_is_better", "dtype", "n_gpus", "steps", "warmup", "scaling", "counts", "config"):
+        assert plain[k] == full[k], k
+    assert plain["multi_gpu"]["clusters_gathered"] == full["multi_gpu"]["clusters_gathered"] > 100
+
+
 def test_bench_strong_scaling_two_ranks_equal_one_rank_on_one_gpu():
     """bench.py --scaling strong: ONE whole-genome batch sharded by contig ownership - two ranks (both on cuda:0 over gloo here) process the
     same records, signatures and clusters as one rank; the line names the process group's world size and what crossed the fabric in the last step.  No scaling

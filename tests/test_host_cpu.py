@@ -785,3 +785,17 @@ def test_bounce_buffer_copy_layer_over_an_asynchronous_model(tmp_path):
         assert build.returncode == 0, build.stderr[-2000:]
         run = subprocess.run([exe] + args, capture_output=True, text=True, timeout=900, env=dict(os.environ, **env))
         assert run.returncode == 0 and "every byte arrived" in run.stdout and "runtime error" not in run.stderr and "WARNING: ThreadSanitizer" not in run.stderr, (san, run.stdout[-500:], run.stderr[-3000:])
+
+
+def test_bench_has_the_full_option_off_by_default():
+    """bench.py --full (what a plain run leaves out: end_to_end, cpu_baseline, the strong-scaling block of a multi-rank line) is an option of the command line,
+    a switch that is off unless given; --no-cpu-baseline and --no-end-to-end stay as the two ways to narrow it.  The parser needs no GPU."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--help"], capture_output=True, text=True, cwd=repo)
+    assert out.returncode == 0, out.stderr[-2000:]
+    usage = " ".join(out.stdout.split())
+    assert "[--full]" in usage and "[--no-cpu-baseline]" in usage and "[--no-end-to-end]" in usage and "[--dump-outputs DIR]" in usage
+    bad = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "yes", "--steps", "0"], capture_output=True, text=True, cwd=repo)
+    assert bad.returncode == 2 and "unrecognized arguments: yes" in bad.stderr              # a switch: it takes no value

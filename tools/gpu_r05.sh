@@ -117,7 +117,7 @@ tailrepro)
 evidence)
   export HSA_DISABLE_COREDUMP_ON_EXCEPTION=1; ulimit -c 0
   R=$PWD
-  python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_c1.json 2> $out/${tag}_bench_c1.err; echo "bench c1 rc=$?"
+  python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench_c1.json 2> $out/${tag}_bench_c1.err; echo "bench c1 rc=$?"
   B="--steps 4 --warmup 2 --no-cpu-baseline --no-end-to-end"
   rm -rf /tmp/kt && (cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/kt -o p -- python $R/bench.py $B > /dev/null 2> /tmp/kt.err)
   db=$(find /tmp/kt -name "*.db" | head -1)
@@ -130,8 +130,8 @@ evidence)
     db=$(find /tmp/pmc_$t -name "*.db" | head -1)
     [ -n "$db" ] && python tools/pmc_summary.py $db $out/${tag}_pmc_$t.csv > /dev/null
   done
-  python bench.py --steps 10 --warmup 3 --workload c2 --no-cpu-baseline > $out/${tag}_bench_c2.json 2>/dev/null
-  for pmd in 1000 100000; do python bench.py --steps 5 --warmup 2 --workload c4 --partition-max-distance $pmd --no-cpu-baseline > $out/${tag}_bench_c4_pmd$pmd.json 2>/dev/null; done
+  python bench.py --full --steps 10 --warmup 3 --workload c2 --no-cpu-baseline > $out/${tag}_bench_c2.json 2>/dev/null
+  for pmd in 1000 100000; do python bench.py --full --steps 5 --warmup 2 --workload c4 --partition-max-distance $pmd --no-cpu-baseline > $out/${tag}_bench_c4_pmd$pmd.json 2>/dev/null; done
   python bench.py --scaling strong --steps 5 --warmup 2 > $out/${tag}_bench_strong_1rank.json 2> $out/${tag}_bench_strong_1rank.err
   SVX_BENCH_BACKEND=gloo SVX_BENCH_ONE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29577 bench.py --gpus 2 --scaling strong --steps 5 --warmup 2 > $out/${tag}_bench_strong_2ranks_one_gpu.json 2> $out/${tag}_bench_strong_2ranks_one_gpu.err
   python tools/device_reader_rate.py 180000 8192 2>&1 | grep -v "amdgpu.ids\|bamio pass\|   pass\|bamio 64" > $out/${tag}_device_reader_rate.txt
@@ -142,7 +142,7 @@ evidence)
   ls -la $out/${tag}_* | head -40
   ;;
 bench)
-  python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?"; cut -c1-1500 $out/${tag}_bench.json
+  python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?"; cut -c1-1500 $out/${tag}_bench.json
   ;;
 *) echo "unknown step $step"; exit 2;;
 esac

@@ -23,7 +23,7 @@ suite)
   echo "suite: rc=$? $(tail -1 $out/${tag}_pytest.txt)"
   ;;
 bench)
-  python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?"; cut -c1-3000 $out/${tag}_bench.json
+  python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; echo "bench rc=$?"; cut -c1-3000 $out/${tag}_bench.json
   ;;
 ab)
   # interleaved A/B of library variants (tools/build_variants.sh):  VARIANTS="tree a b" WL="c1"
@@ -48,7 +48,7 @@ strong)
   for n in ${RANKS:-2 4}; do
     SVX_BENCH_BACKEND=gloo SVX_BENCH_ONE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2957$n bench.py --gpus $n --scaling strong --steps 5 --warmup 2 > $out/${tag}_bench_strong_${n}ranks_one_gpu.json 2> $out/${tag}_bench_strong_${n}ranks_one_gpu.err; echo "strong $n ranks rc=$?"
   done
-  SVX_BENCH_BACKEND=gloo SVX_BENCH_ONE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29588 bench.py --gpus 2 --steps 3 --warmup 1 --reads 200000 --contig-len 50000000 > $out/${tag}_bench_default_2ranks_one_gpu.json 2> $out/${tag}_bench_default_2ranks_one_gpu.err; echo "default line, 2 ranks rc=$?"
+  SVX_BENCH_BACKEND=gloo SVX_BENCH_ONE_GPU=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29588 bench.py --gpus 2 --full --steps 3 --warmup 1 --reads 200000 --contig-len 50000000 > $out/${tag}_bench_default_2ranks_one_gpu.json 2> $out/${tag}_bench_default_2ranks_one_gpu.err; echo "default line, 2 ranks rc=$?"
   python - <<'PY'
 import json, glob
 for f in sorted(glob.glob("gpurun_out/%s_bench_strong_*.json" % "'$tag'".strip("'"))) + sorted(glob.glob("gpurun_out/%s_bench_default_2ranks*.json" % "'$tag'".strip("'"))):
@@ -90,7 +90,7 @@ PY
 evidence)
   # what profiles/ holds at the end of the round, all at the SAME code: the default bench line, kernel stats + step timelines (rocprofv3 --kernel-trace --stats),
   # the four PMC passes (separate runs, no trace domains beside --kernel-trace), the stand-in workloads, small-batch latency, strong-scaling lines (one GPU, gloo)
-  python bench.py --steps 20 --warmup 5 > $out/${tag}_bench_c1.json 2> $out/${tag}_bench_c1.err; echo "bench c1 rc=$?"
+  python bench.py --full --steps 20 --warmup 5 > $out/${tag}_bench_c1.json 2> $out/${tag}_bench_c1.err; echo "bench c1 rc=$?"
   B="--steps 4 --warmup 2 --no-cpu-baseline --no-end-to-end"
   KT=/tmp/kt_$$; rm -rf $KT; (cd /tmp && rocprofv3 --kernel-trace --stats -d $KT -o p -- python $R/bench.py $B > /dev/null 2> $KT.err)
   db=$(find $KT -name "*.db" | head -1)
@@ -104,8 +104,8 @@ evidence)
     db=$(find $P -name "*.db" | head -1)
     [ -n "$db" ] && python tools/pmc_summary.py $db $out/${tag}_pmc_$t.csv > /dev/null
   done
-  python bench.py --steps 10 --warmup 3 --workload c2 --no-cpu-baseline > $out/${tag}_bench_c2.json 2>/dev/null
-  python bench.py --steps 5 --warmup 2 --workload c4 --no-cpu-baseline > $out/${tag}_bench_c4.json 2>/dev/null
+  python bench.py --full --steps 10 --warmup 3 --workload c2 --no-cpu-baseline > $out/${tag}_bench_c2.json 2>/dev/null
+  python bench.py --full --steps 5 --warmup 2 --workload c4 --no-cpu-baseline > $out/${tag}_bench_c4.json 2>/dev/null
   python tools/small_batch_latency.py 2>&1 | grep -v amdgpu.ids > $out/${tag}_small_batch_latency.txt
   git rev-parse HEAD > $out/${tag}_evidence_commit.txt 2>/dev/null || true
   ls -la $out/${tag}_* | head -40
