@@ -340,6 +340,59 @@ int  svx_combine_get_stats(svx_ctx* ctx, svx_combine_stats* out);
  * consumes the stream; out[100 * n] */
 int  svx_py_sample100(int64_t n, const int64_t* sizes, int32_t* out);
 
+/* ---- VCF text: replaces the body of write_final_vcf (src/svim/SVIM_COMBINE.py:139-184: entries, sorted_nicely :61-68, the svim.<label>.<k> ids) and the nine
+ * get_vcf_entry* methods of src/svim/SVCandidate.py (:79, :149, :222, :323, :376, :476, :528, :640, :690) ---------------------------------------------------
+ * Candidate table -> the lines of variants.vcf behind the header, byte for byte, in device memory (csrc/vcf.hip).  The header block (SVIM_COMBINE.py:86-137)
+ * carries a time stamp and stays with the caller.  The candidate and signature tables are only read. */
+enum { SVX_VCF_DEL = 0, SVX_VCF_INV = 1, SVX_VCF_INS = 2, SVX_VCF_DUP_TANDEM = 3, SVX_VCF_DUP_INT = 4, SVX_VCF_BND = 5, SVX_VCF_NLABEL = 6 };   /* ID labels, bits of types_mask */
+typedef struct svx_vcf_params {
+    uint32_t types_mask;          /* bit per label (options.types, SVIM_COMBINE.py:145-173); a duplication written as an insertion is governed by the INS bit */
+    int32_t  sequence_alleles;    /* not options.symbolic_alleles: needs a genome in the context, else SVX_E_STATE */
+    int32_t  insertion_sequences; /* ;SEQS=  (novel insertions only) */
+    int32_t  read_names;          /* ;READS= */
+    int32_t  zmws;                /* ;ZMWS=  */
+    int32_t  tandem_duplications_as_insertions;
+    int32_t  interspersed_duplications_as_insertions;
+} svx_vcf_params;
+typedef struct svx_vcf_inputs {   /* everything optional unless a switch needs it; all HOST memory */
+    const uint8_t* gt;            /* [n_cand] 0 "./." 1 "0/0" 2 "0/1" 3 "1/1"; NULL: all "./." */
+    const int32_t* ref_reads;     /* [n_cand] -1 = None; NULL: all None */
+    const int32_t* alt_reads;
+    const char*    contig_names_nul_separated;      /* names of the contig ids of the candidate table, each followed by a NUL */
+    int32_t        n_contig;
+    const int32_t* contig_natural_rank;             /* [n_contig] rank under sorted_nicely's key; EQUAL for names with equal keys ("chr1" / "chr01") */
+    const char*    read_names_blob;                 /* read_names: name of read_id r = bytes read_name_off[r] .. read_name_off[r + 1] */
+    const int64_t* read_name_off;                   /* [n_reads + 1] */
+    int64_t        n_reads;
+    const int32_t* zmw_id;        /* [n_reads] zmws: id of "/".join(fields[0:2]) when the name has exactly three '/'-fields, else -1 */
+} svx_vcf_inputs;
+typedef struct svx_vcf_stats {
+    double  t_total_ms;           /* HIP events on the context's stream around the whole call (host steps in between included) */
+    double  t_upload_ms;          /* source 2 tables, genotype columns, names */
+    double  t_entries_ms;         /* entries, keys, the stable sorts, ids */
+    double  t_distinct_ms;        /* distinct reads / ZMWs per candidate */
+    double  t_lengths_ms;         /* member piece offsets, line lengths, the two scans and the mailbox read */
+    double  t_skeleton_ms;        /* the skeleton kernel alone */
+    double  t_payload_ms;         /* the payload kernel alone */
+    int64_t n_candidates, n_lines, n_bytes, n_tiles;
+    int64_t lines_per_label[SVX_VCF_NLABEL];
+    int64_t bytes_ref_forward, bytes_ref_revcomp, bytes_ref_repeat, bytes_seqs, bytes_reads;     /* payload bytes by kind */
+} svx_vcf_stats;
+/* source: 0 = the candidate table resident from the last svx_combine, which must have taken the resident clusters (its source 0), and the signature table
+ *             its members index - SVX_E_STATE if either is gone (no svx_combine yet, a svx_cluster call since);
+ *         2 = `cand` (grouped by class in SVX_CAND_* order, class_count set) plus, in `sigs`, the columns of the signatures its members index that the text
+ *             needs: n, read_id, and - with insertion_sequences - seq_off and seq.  Host memory.
+ * STD_* values must be NaN or below 1e10 in magnitude (they are standard deviations of int32 coordinates): SVX_E_ARG otherwise.  SVX_E_CAPACITY: the text does
+ * not fit into device memory (svx_last_error names the byte count).  SVX_E_ARG also for a contig, member or read id outside its table. */
+int  svx_vcf(svx_ctx* ctx, int source, const svx_candidate_view* cand, const svx_sig_view* sigs, const svx_vcf_params* p, const svx_vcf_inputs* in);
+int  svx_vcf_count(svx_ctx* ctx, int64_t* n_lines, int64_t* n_bytes);
+/* bytes [byte_offset, byte_offset + bytes) of the text into host_dst (NULL or bytes 0: none); line_off: [n_lines + 1] offsets of the lines (NULL: not fetched) */
+int  svx_vcf_fetch(svx_ctx* ctx, int64_t byte_offset, int64_t bytes, uint8_t* host_dst, int64_t* line_off);
+int  svx_vcf_get_stats(svx_ctx* ctx, svx_vcf_stats* out);
+/* host-only (no GPU needed; tests): the text get_std_span() / get_std_pos() put into a line (SVCandidate.py:39-50: "." for None - NaN here - and for 0.0,
+ * else str(round(x, 2))), by the integer arithmetic the kernels use.  SVX_E_ARG: |x| >= 1e10 or infinite. */
+int  svx_vcf_format_std(double x, char out[32]);
+
 /* ---- GENOTYPE: replaces the per-candidate BAM re-fetch of genotype() (src/svim/SVIM_genotyping.py:34-93) --------
  * by an interval join over the alignment records, resident in HBM.  Records are in file order of a coordinate-sorted BAM
  * (tid, pos non-decreasing); AlignmentFile.fetch(contig, start, stop) of the reference (:48) becomes "records of that contig with

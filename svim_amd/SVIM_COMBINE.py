@@ -8,10 +8,16 @@ coincide with a duplication deleted, the breakend list extended by the mirrored 
     Python object is made - neither for the clusters nor for the candidates (CandidateList) nor for the edits of the input lists (ClusterList.defer);
   * anything else (plain lists, lists somebody changed, clusters of another call) is turned into a cluster table and goes source 2.
 
+`write_final_vcf(...)` (the reference's argument order) writes variants.vcf: the header here, the lines behind it by the device writer (svx_vcf, csrc/vcf.hip);
+`sorted_nicely` is the reference's natural sort of the entries.
+
 The insertion consensus (spoa) is not part of the device path: it implements the reference's skip_consensus branch; with options.skip_consensus false
 this is logged once and the same candidates are returned ("COMBINE on the device").
 """
 import logging
+import os
+import time
+from collections import defaultdict
 
 import numpy as np
 
@@ -190,3 +196,228 @@ def combine_tables(engine, options, references=None, contig_rank=None):
     if contig_rank is None:
         raise ValueError("combine_tables: no contig ranks (pass references or contig_rank)")
     return engine.combine(_abi.CombineParams.from_options(options), contig_rank)
+
+
+# ---- variants.vcf (src/svim/SVIM_COMBINE.py:61-186) ------------------------------------------------------------------------------------------------------
+def sorted_nicely(vcf_entries):
+    """entries ((contig, start, end), vcf_string, sv_type) sorted by (natural contig key, start, end), stably (src/svim/SVIM_COMBINE.py:61-68)"""
+    return sorted(vcf_entries, key=lambda entry: (convert.natural_key(entry[0][0]), entry[0][1], entry[0][2]))
+
+
+def vcf_header(version, contig_names, contig_lengths, types_to_output, options, file_date=None):
+    """the header block of variants.vcf (src/svim/SVIM_COMBINE.py:86-137) as a list of lines"""
+    tan_dup = not options.tandem_duplications_as_insertions and "DUP:TANDEM" in types_to_output
+    int_dup = not options.interspersed_duplications_as_insertions and "DUP:INT" in types_to_output
+    info = lambda i, n, t, d: '##INFO=<ID=%s,Number=%s,Type=%s,Description="%s">' % (i, n, t, d)      # noqa: E731
+    alt = lambda i, d: '##ALT=<ID=%s,Description="%s">' % (i, d)                                      # noqa: E731
+    fmt = lambda i, n, t, d: '##FORMAT=<ID=%s,Number=%s,Type=%s,Description="%s">' % (i, n, t, d)     # noqa: E731
+    lines = ["##fileformat=VCFv4.2", "##fileDate=%s" % (file_date if file_date is not None else time.strftime("%Y-%m-%d|%I:%M:%S%p|%Z|%z")),
+             "##source=SVIM-v%s" % version]
+    lines += ["##contig=<ID=%s,length=%s>" % (n, l) for n, l in zip(contig_names, contig_lengths)]
+    lines += [alt(i, d) for on, i, d in (("DEL" in types_to_output, "DEL", "Deletion"), ("INV" in types_to_output, "INV", "Inversion"),
+                                         (tan_dup or int_dup, "DUP", "Duplication"), (tan_dup, "DUP:TANDEM", "Tandem Duplication"),
+                                         (int_dup, "DUP:INT", "Interspersed Duplication"), ("INS" in types_to_output, "INS", "Insertion"),
+                                         ("BND" in types_to_output, "BND", "Breakend")) if on]
+    lines += [info("SVTYPE", 1, "String", "Type of structural variant"),
+              info("CUTPASTE", 0, "Flag", "Genomic origin of interspersed duplication seems to be deleted"),
+              info("END", 1, "Integer", "End position of the variant described in this record"),
+              info("SVLEN", 1, "Integer", "Difference in length between REF and ALT alleles"),
+              info("SUPPORT", 1, "Integer", "Number of reads supporting this variant"),
+              info("STD_SPAN", 1, "Float", "Standard deviation in span of merged SV signatures"),
+              info("STD_POS", 1, "Float", "Standard deviation in position of merged SV signatures"),
+              info("STD_POS1", 1, "Float", "Standard deviation of breakend 1 position"),
+              info("STD_POS2", 1, "Float", "Standard deviation of breakend 2 position")]
+    if options.insertion_sequences:
+        lines.append(info("SEQS", ".", "String", "Insertion sequences from all supporting reads"))
+    if options.read_names:
+        lines.append(info("READS", ".", "String", "Names of all supporting reads"))
+    if options.zmws:
+        lines.append(info("ZMWS", 1, "Integer", "Number of supporting ZMWs (PacBio only)"))
+    lines += ['##FILTER=<ID=hom_ref,Description="Genotype is homozygous reference">',
+              '##FILTER=<ID=not_fully_covered,Description="Tandem duplication is not fully covered by a single read">',
+              fmt("GT", 1, "String", "Genotype"), fmt("DP", 1, "Integer", "Read depth"), fmt("AD", "R", "Integer", "Read depth for each allele")]
+    if tan_dup:
+        lines.append(fmt("CN", 1, "Integer", "Copy number of tandem duplication (e.g. 2 for one additional copy)"))
+    lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + options.sample)
+    return lines
+
+
+def vcf_body_python(int_dup, inv, tan_dup, dele, ins, bnd, types_to_output, options, sequence_alleles=False, reference=None):
+    """The lines of variants.vcf behind the header from candidate OBJECTS, as the reference makes them (src/svim/SVIM_COMBINE.py:139-184): the entries in append
+    order, sorted_nicely, the svim.<label>.<k> ids.  The definition the device writer is held against; -> list of lines without the newline."""
+    o, entries = options, []
+    if "DEL" in types_to_output:
+        entries += [(c.get_source(), c.get_vcf_entry(sequence_alleles, reference, o.read_names, o.zmws), "DEL") for c in dele]
+    if "INV" in types_to_output:
+        entries += [(c.get_source(), c.get_vcf_entry(sequence_alleles, reference, o.read_names, o.zmws), "INV") for c in inv]
+    if "INS" in types_to_output:
+        entries += [(c.get_destination(), c.get_vcf_entry(sequence_alleles, reference, o.insertion_sequences, o.read_names, o.zmws), "INS") for c in ins]
+    for cands, as_ins, label, name in ((tan_dup, o.tandem_duplications_as_insertions, "DUP:TANDEM", "DUP_TANDEM"),
+                                       (int_dup, o.interspersed_duplications_as_insertions, "DUP:INT", "DUP_INT")):
+        if as_ins:
+            if "INS" in types_to_output:
+                entries += [(c.get_destination(), c.get_vcf_entry_as_ins(sequence_alleles, reference, o.read_names, o.zmws), "INS") for c in cands]
+        elif label in types_to_output:
+            entries += [(c.get_source(), c.get_vcf_entry_as_dup(o.read_names, o.zmws), name) for c in cands]
+    if "BND" in types_to_output:
+        for c in bnd:
+            (sc, sp), (dc, dp) = c.get_source(), c.get_destination()
+            entries.append(((sc, sp, sp + 1), c.get_vcf_entry(o.read_names, o.zmws), "BND"))
+            entries.append(((dc, dp, dp + 1), c.get_vcf_entry_reverse(o.read_names, o.zmws), "BND"))
+    counter, lines = defaultdict(int), []
+    for _, entry, svtype in sorted_nicely(entries):
+        counter[svtype] += 1
+        lines.append(entry.replace("PLACEHOLDERFORID", "svim.%s.%d" % (svtype, counter[svtype]), 1))
+    return lines
+
+
+class GenomeText(object):
+    """reference.fetch(contig, start, end) over {name: sequence} or a FASTA path, clipped to the contig; a contig the genome lacks reads as empty"""
+
+    def __init__(self, path_or_dict, references=None):
+        if isinstance(path_or_dict, dict):
+            self.seqs = {k: (v.decode("ascii") if isinstance(v, bytes) else v) for k, v in path_or_dict.items()}
+        else:
+            references = list(references or [])
+            off, codes = convert.genome_arrays(path_or_dict, references)
+            self.seqs = {r: _abi.decode_bases(codes[off[i]:off[i + 1]]) for i, r in enumerate(references)}
+
+    def fetch(self, contig, start, end):
+        s = self.seqs.get(contig, "")
+        start = max(0, start)
+        return s[start:max(start, end)]
+
+    def close(self):
+        pass
+
+
+_CAND_SLOTS = (_abi.CAND_DUP_INT, _abi.CAND_INV, _abi.CAND_DUP_TAN, _abi.CAND_DEL, _abi.CAND_INS, _abi.CAND_BND)      # write_final_vcf's argument order
+
+
+def _resident_candidates(lists6, eng):
+    """the six lists are the untouched views of the candidate table `eng` holds from its last combine() of resident clusters"""
+    from .lazy import CandidateList, SignatureList
+    t = getattr(eng, "_resident_cand", None)
+    if t is None or getattr(eng, "_resident_cand_generation", None) != eng.collect_generation:
+        return False
+    if not all(isinstance(x, CandidateList) and x._objs is None and x.table is t for x in lists6):
+        return False
+    b = t.bounds()
+    first = lists6[0]
+    return all((x.lo, x.hi) == (b[k], b[k + 1]) for x, k in zip(lists6, _CAND_SLOTS)) and isinstance(first.signatures, SignatureList) and \
+        all(x.signatures is first.signatures and x.references is first.references for x in lists6)
+
+
+def candidate_table_from_lists(lists6, references=()):
+    """six sequences of candidate objects (write_final_vcf's argument order) -> (CandidateTable, contig names, gt / ref_reads / alt_reads columns, read names,
+    read_id / seq_off / seq columns of the member signatures); None when an object's text is outside what the table can say (a genotype string other than
+    ./. 0/0 0/1 1/1, a novel insertion with a consensus sequence)"""
+    contigs, reads = convert.Interner(references), convert.Interner()
+    by_cls = dict(zip(_CAND_SLOTS, lists6))
+    rows, gts, rrs, ars, moff, members = [], [], [], [], [0], []
+    sig_index, sig_rid, sig_seq = {}, [], []
+    none = lambda v: -1 if v is None else int(v)      # noqa: E731
+    for cls in range(6):
+        for c in by_cls[cls]:
+            gt = _abi.VCF_GT.get(c.genotype)
+            if gt is None or (cls == _abi.CAND_INS and c.sequence != "") or none(c.ref_reads) < -1 or none(c.alt_reads) < -1:
+                return None
+            if cls == _abi.CAND_INS:
+                row = (-1, 0, 0, contigs(c.dest_contig), c.dest_start, c.dest_end, 0, 0, _nan(c.std_span), _nan(c.std_pos))
+            elif cls == _abi.CAND_DUP_INT:
+                row = (contigs(c.source_contig), c.source_start, c.source_end, contigs(c.dest_contig), c.dest_start, c.dest_end, 1 if c.cutpaste else 0, 0,
+                       _nan(c.std_span), _nan(c.std_pos))
+            elif cls == _abi.CAND_BND:
+                row = (contigs(c.source_contig), c.source_start, c.source_start, contigs(c.dest_contig), c.dest_start, c.dest_start,
+                       (1 if c.source_direction == "rev" else 0) | (2 if c.dest_direction == "rev" else 0), 0, _nan(c.std_pos1), _nan(c.std_pos2))
+            else:
+                tan = cls == _abi.CAND_DUP_TAN
+                row = (contigs(c.source_contig), c.source_start, c.source_end, -1, 0, 0, (1 if c.fully_covered else 0) if tan else 0, c.copies if tan else 0,
+                       _nan(c.std_span), _nan(c.std_pos))
+            for m in c.members:
+                k = sig_index.get(id(m))
+                if k is None:
+                    k = sig_index[id(m)] = len(sig_rid)
+                    sig_rid.append(reads(m.read))
+                    sig_seq.append(getattr(m, "sequence", None) or "")      # (a signature can be a member of candidates of several classes)
+                members.append(k)
+            moff.append(len(members))
+            rows.append((cls,) + row + (float(c.score),))
+            gts.append(gt), rrs.append(none(c.ref_reads)), ars.append(none(c.alt_reads))
+    t = _abi.CandidateTable(len(rows), len(members))
+    if rows:
+        cols = list(zip(*rows))
+        for k, name in enumerate(("cls", "contig", "start", "end", "contig2", "start2", "end2", "aux", "copies", "std_span", "std_pos", "score")):
+            getattr(t, name)[:] = np.asarray(cols[k], dtype=_abi.CAND_DTYPES[name])
+    t.member_off[:] = np.asarray(moff, dtype=np.int64)
+    t.members[:len(members)] = np.asarray(members, dtype=np.int32)
+    v = t.view()
+    for cls in range(6):
+        v.class_count[cls] = len(by_cls[cls])
+    t.finish(v)
+    seq_off = np.zeros(len(sig_seq) + 1, dtype=np.int64)
+    if sig_seq:
+        np.cumsum(np.fromiter((len(x) for x in sig_seq), dtype=np.int64, count=len(sig_seq)), out=seq_off[1:])
+    seq = _abi.encode_bases("".join(sig_seq)) if seq_off[-1] else np.zeros(1, dtype=np.uint8)
+    return (t, contigs.names, np.asarray(gts, dtype=np.uint8), np.asarray(rrs, dtype=np.int32), np.asarray(ars, dtype=np.int32), reads.names,
+            np.asarray(sig_rid, dtype=np.int32), seq_off, seq)
+
+
+_VCF_PIECE = 64 << 20
+
+
+def vcf_body_device(int_dup, inv, tan_dup, dele, ins, bnd, contig_names, types_to_output, options, sequence_alleles, engine=None):
+    """svx_vcf on one of the two routes (see write_final_vcf) -> (engine, number of lines, number of bytes), the text resident in the engine;
+    None: the candidates need the Python definition (candidate_table_from_lists says when)."""
+    eng = engine if engine is not None else _lib.engine()
+    lists6 = (int_dup, inv, tan_dup, dele, ins, bnd)
+    vp = _abi.VcfParams.from_options(options, types_to_output, sequence_alleles)
+    need_names = bool(vp.read_names or vp.zmws)
+    if _resident_candidates(lists6, eng):
+        first = lists6[0]
+        references, names = first.references, (first.signatures.read_names if need_names else None)
+        run = lambda: eng.vcf(vp, references, read_names=names)      # noqa: E731
+    else:
+        built = candidate_table_from_lists(lists6, contig_names)
+        if built is None:
+            return None
+        t, references, gt, rr, ar, names, rid, seq_off, seq = built
+        run = lambda: eng.vcf(vp, references, table=t, sig_read_id=rid, sig_seq_off=seq_off if vp.insertion_sequences else None, sig_seq=seq, gt=gt,      # noqa: E731
+                              ref_reads=rr, alt_reads=ar, read_names=names if need_names else None)
+    if sequence_alleles and getattr(options, "genome", None):
+        from .SVIM_clustering import _genome_for
+        _genome_for(eng, options, references)      # (loads options.genome only if this engine does not hold it in this contig order yet)
+    n_lines, n_bytes = run()
+    return eng, n_lines, n_bytes
+
+
+def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_duplication_candidates, deletion_candidates, novel_insertion_candidates,
+                    breakend_candidates, version, contig_names, contig_lengths, types_to_output, options, engine=None):
+    """src/svim/SVIM_COMBINE.py:71-186: <working_dir>/variants.vcf.  The header is written here; the lines behind it are made on the device (svx_vcf) and
+    fetched in pieces.  Routes, as combine_clusters has them:
+      * the six lists are the untouched CandidateList views of the table the engine holds from its last combine_clusters of resident clusters: source 0 with
+        the default genotype columns - nothing is uploaded but names, no object is made;
+      * anything else (plain lists, lists genotype() wrote to, breakend_candidates + breakend_candidates_all_bnds of --all_bnds): one pass over the objects
+        builds the candidate table, the genotype columns and the member signature columns: source 2.
+    A novel insertion candidate with a non-empty `sequence` (only hand-made objects have one: the device COMBINE implements the skip_consensus branch) or a
+    genotype string outside ./. 0/0 0/1 1/1 takes the Python definition (vcf_body_python) for that call.  options.genome is loaded only when the engine does
+    not hold it yet; a missing genome file gives symbolic alleles with the reference's warning."""
+    sequence_alleles = not options.symbolic_alleles
+    if sequence_alleles and not (getattr(options, "genome", None) and os.path.exists(options.genome)):
+        logging.warning("The given reference genome is missing ({path}). Sequence alleles cannot be retrieved.".format(path=getattr(options, "genome", None)))
+        sequence_alleles = False
+    lists6 = (int_duplication_candidates, inversion_candidates, tandem_duplication_candidates, deletion_candidates, novel_insertion_candidates,
+              breakend_candidates)
+    with open(options.working_dir + "/variants.vcf", "wb") as out:
+        out.write(("\n".join(vcf_header(version, contig_names, contig_lengths, types_to_output, options)) + "\n").encode("utf-8"))
+        done = vcf_body_device(*lists6, contig_names, types_to_output, options, sequence_alleles, engine=engine)
+        if done is None:
+            names = list(convert.Interner(contig_names).names)
+            used = {getattr(c, k) for lst in lists6 for c in lst for k in ("source_contig", "dest_contig") if hasattr(c, k)}
+            reference = GenomeText(options.genome, names + sorted(used - set(names))) if sequence_alleles else None
+            lines = vcf_body_python(*lists6, types_to_output, options, sequence_alleles, reference)
+            out.write("".join(line + "\n" for line in lines).encode("utf-8"))
+            return
+        eng, _, n_bytes = done
+        for at in range(0, n_bytes, _VCF_PIECE):
+            out.write(eng.vcf_fetch(at, min(_VCF_PIECE, n_bytes - at)))

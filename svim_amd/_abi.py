@@ -146,6 +146,41 @@ class CombineStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# ID labels of VCF lines = bits of VcfParams.types_mask (include/svx.h: SVX_VCF_*), under the names options.types uses
+VCF_LABELS = ("DEL", "INV", "INS", "DUP:TANDEM", "DUP:INT", "BND")
+VCF_GT = {"./.": 0, "0/0": 1, "0/1": 2, "1/1": 3}
+
+
+class VcfParams(C.Structure):
+    _fields_ = [("types_mask", C.c_uint32), ("sequence_alleles", C.c_int32), ("insertion_sequences", C.c_int32), ("read_names", C.c_int32), ("zmws", C.c_int32),
+                ("tandem_duplications_as_insertions", C.c_int32), ("interspersed_duplications_as_insertions", C.c_int32)]
+
+    @classmethod
+    def from_options(cls, o, types_to_output=None, sequence_alleles=None):
+        g = lambda k: 1 if getattr(o, k, False) else 0      # noqa: E731
+        types = VCF_LABELS if types_to_output is None else types_to_output
+        mask = sum(1 << k for k, name in enumerate(VCF_LABELS) if name in types)
+        seq = (not getattr(o, "symbolic_alleles", False)) if sequence_alleles is None else sequence_alleles
+        return cls(mask, 1 if seq else 0, g("insertion_sequences"), g("read_names"), g("zmws"), g("tandem_duplications_as_insertions"),
+                   g("interspersed_duplications_as_insertions"))
+
+
+class VcfInputs(C.Structure):
+    _fields_ = [("gt", _P), ("ref_reads", _P), ("alt_reads", _P), ("contig_names_nul_separated", _P), ("n_contig", C.c_int32), ("contig_natural_rank", _P),
+                ("read_names_blob", _P), ("read_name_off", _P), ("n_reads", C.c_int64), ("zmw_id", _P)]
+
+
+class VcfStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_total_ms", "t_upload_ms", "t_entries_ms", "t_distinct_ms", "t_lengths_ms", "t_skeleton_ms", "t_payload_ms")] + \
+               [(n, C.c_int64) for n in ("n_candidates", "n_lines", "n_bytes", "n_tiles")] + [("lines_per_label", C.c_int64 * 6)] + \
+               [(n, C.c_int64) for n in ("bytes_ref_forward", "bytes_ref_revcomp", "bytes_ref_repeat", "bytes_seqs", "bytes_reads")]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "lines_per_label"}
+        d["lines_per_label"] = dict(zip(VCF_LABELS, list(self.lines_per_label)))
+        return d
+
+
 class AlnIndex(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_contig", C.c_int32), ("reserved", C.c_int32), ("contig_first", _P), ("contig_len", _P),
                 ("pos", _P), ("end", _P), ("flag", _P), ("mapq", _P), ("name_id", _P)]

@@ -26,7 +26,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_inflater_create", "svx_inflater_destroy", "svx_inflater_staging", "svx_inflater_enqueue", "svx_inflater_wait",
            "svx_inflater_run",
            "svx_genome_load_fasta", "svx_genome_fetch", "svx_fasta_probe", "svx_fasta_plan",
-           "svx_combine", "svx_combine_count", "svx_combine_fetch", "svx_combine_stages_fetch", "svx_combine_get_stats", "svx_py_sample100"]
+           "svx_combine", "svx_combine_count", "svx_combine_fetch", "svx_combine_stages_fetch", "svx_combine_get_stats", "svx_py_sample100",
+           "svx_vcf", "svx_vcf_count", "svx_vcf_fetch", "svx_vcf_get_stats", "svx_vcf_format_std"]
 
 
 class SvxError(RuntimeError):
@@ -89,6 +90,14 @@ def py_sample100(sizes):
     out = np.zeros((max(1, sizes.size), 100), dtype=np.int32)
     _check(lib().svx_py_sample100(C.c_int64(sizes.size), ptr(sizes if sizes.size else np.zeros(1, np.int64)), ptr(out)), "svx_py_sample100")
     return out[:sizes.size]
+
+
+def vcf_format_std(x):
+    """svx_vcf_format_std (host-only): the text get_std_span() / get_std_pos() contribute to a VCF line for x - "." for NaN and 0.0, else str(round(x, 2)) -
+    by the integer arithmetic of the kernels.  SvxError (SVX_E_ARG) for |x| >= 1e10."""
+    out = C.create_string_buffer(32)
+    _check(lib().svx_vcf_format_std(C.c_double(float(x)), out), "svx_vcf_format_std")
+    return out.value.decode("ascii")
 
 
 def build(force=False):
@@ -229,6 +238,7 @@ class Engine(object):
         v = table.view() if (table is not None and hasattr(table, "view")) else (table if table is not None else _abi.SigView())
         rank = np.ascontiguousarray(contig_rank, dtype=np.int32)
         self._resident_ct, self._last_contig_rank = None, rank
+        self._resident_cand = None
         _check(self.L.svx_cluster(self.ctx, source, C.byref(v), len(rank), ptr(rank), C.byref(params)), "svx_cluster")
         if not fetch:
             return None
@@ -272,7 +282,13 @@ class Engine(object):
         if rc == _abi.SVX_E_NO_DELETION:
             raise NoDeletionClusters(self.L.svx_last_error().decode("utf-8", "replace"))
         _check(rc, "svx_combine")
-        return self.fetch_candidates() if fetch else None
+        self._resident_cand = None
+        if not fetch:
+            return None
+        t = self.fetch_candidates()
+        if table is None:      # (SVIM_COMBINE.write_final_vcf: lists that are views of this very table are written without an upload)
+            self._resident_cand, self._resident_cand_generation = t, self.collect_generation
+        return t
 
     def fetch_candidates(self):
         n, nm = C.c_int64(), C.c_int64()
@@ -297,6 +313,87 @@ class Engine(object):
     def combine_stats(self):
         s = _abi.CombineStats()
         _check(self.L.svx_combine_get_stats(self.ctx, C.byref(s)), "svx_combine_get_stats")
+        return s.as_dict()
+
+    # ---- VCF text ----
+    def vcf(self, vparams, references, table=None, sig_read_id=None, sig_seq_off=None, sig_seq=None, gt=None, ref_reads=None, alt_reads=None, read_names=None,
+            zmw_id=None):
+        """svx_vcf: the body of variants.vcf (every line behind the header) of the candidates resident from the last combine() of the resident clusters
+        (table None, source 0) or of the CandidateTable `table` whose members index signatures with the columns sig_read_id / sig_seq_off / sig_seq (source 2).
+        references: names of the table's contig ids.  gt (codes of _abi.VCF_GT) / ref_reads / alt_reads (-1 = None): genotype columns, default "./." / None.
+        read_names: names by read id (vparams.read_names); zmw_id: convert.zmw_ids of them (vparams.zmws).  The text stays on the device:
+        -> (number of lines, number of bytes); vcf_fetch() / vcf_line_offsets() bring it over."""
+        from . import convert
+        references = list(references)
+        keep = []
+
+        def arr(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            keep.append(a)
+            return ptr(a if a.size else np.zeros(1, dt))
+        blob = b"".join(os.fsencode(r) + b"\0" for r in references) or b"\0"
+        rank = convert.natural_ranks(references)
+        inp = _abi.VcfInputs()
+        inp.gt, inp.ref_reads, inp.alt_reads = arr(gt, np.uint8), arr(ref_reads, np.int32), arr(alt_reads, np.int32)
+        cbuf = C.create_string_buffer(blob, len(blob))
+        inp.contig_names_nul_separated, inp.n_contig, inp.contig_natural_rank = C.cast(cbuf, C.c_void_p), len(references), arr(rank, np.int32)
+        rbuf = None
+        if vparams.read_names or vparams.zmws:
+            if read_names is None:
+                raise ValueError("Engine.vcf: read_names / zmws need the read names")
+            inp.n_reads = len(read_names)
+        if vparams.read_names:
+            enc = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in read_names]
+            off = np.zeros(len(enc) + 1, dtype=np.int64)
+            if enc:
+                np.cumsum(np.fromiter((len(e) for e in enc), dtype=np.int64, count=len(enc)), out=off[1:])
+            data = b"".join(enc) or b"\0"
+            rbuf = C.create_string_buffer(data, len(data))
+            inp.read_names_blob, inp.read_name_off = C.cast(rbuf, C.c_void_p), arr(off, np.int64)
+        if vparams.zmws:
+            inp.zmw_id = arr(convert.zmw_ids(read_names) if zmw_id is None else zmw_id, np.int32)
+        if table is None:
+            rc = self.L.svx_vcf(self.ctx, 0, None, None, C.byref(vparams), C.byref(inp))
+        else:
+            v = table.view()
+            for k in range(6):
+                v.class_count[k] = int(table.class_count[k])
+            sv = _abi.SigView()
+            rid = np.ascontiguousarray(sig_read_id if sig_read_id is not None else np.zeros(0, np.int32), dtype=np.int32)
+            sv.on_device, sv.n, sv.read_id = 0, rid.size, ptr(rid if rid.size else np.zeros(1, np.int32))
+            keep.append(rid)
+            if sig_seq_off is not None:
+                sv.seq_off, sv.seq = arr(sig_seq_off, np.int64), arr(sig_seq if sig_seq is not None else np.zeros(1, np.uint8), np.uint8)
+            rc = self.L.svx_vcf(self.ctx, 2, C.byref(v), C.byref(sv), C.byref(vparams), C.byref(inp))
+        _check(rc, "svx_vcf")
+        del keep, cbuf, rbuf
+        return self.vcf_count()
+
+    def vcf_count(self):
+        n, nb = C.c_int64(), C.c_int64()
+        _check(self.L.svx_vcf_count(self.ctx, C.byref(n), C.byref(nb)), "svx_vcf_count")
+        return n.value, nb.value
+
+    def vcf_fetch(self, offset=0, nbytes=None):
+        """bytes [offset, offset + nbytes) of the text of the last vcf() call (svx_vcf_fetch; nbytes None: to the end) -> bytes"""
+        _, total = self.vcf_count()
+        nbytes = total - offset if nbytes is None else nbytes
+        buf = np.zeros(max(1, nbytes), dtype=np.uint8)
+        _check(self.L.svx_vcf_fetch(self.ctx, C.c_int64(offset), C.c_int64(nbytes), ptr(buf), None), "svx_vcf_fetch")
+        return buf[:nbytes].tobytes()
+
+    def vcf_line_offsets(self):
+        """int64[n_lines + 1]: where every line of the last vcf() call starts in its text"""
+        n, _ = self.vcf_count()
+        off = np.zeros(n + 1, dtype=np.int64)
+        _check(self.L.svx_vcf_fetch(self.ctx, C.c_int64(0), C.c_int64(0), None, ptr(off)), "svx_vcf_fetch")
+        return off
+
+    def vcf_stats(self):
+        s = _abi.VcfStats()
+        _check(self.L.svx_vcf_get_stats(self.ctx, C.byref(s)), "svx_vcf_get_stats")
         return s.as_dict()
 
     def set_alignment_index(self, index):

@@ -2,7 +2,8 @@
 
 Same constructor argument order, attributes, `get_source` / `get_destination` / `get_key` / `downstream_distance_to` and the genotype fields with the
 reference's defaults (`support_fraction "."`, `genotype "./."`, `ref_reads` / `alt_reads None`), table-driven like signatures.py: one row of _SPEC per
-class instead of one hand-written constructor each.  The VCF / BED text of candidates is not part of this surface ("COMBINE on the device").
+class instead of one hand-written constructor each.  The nine `get_vcf_entry*` methods are one row of _VCF each over one formatter (`vcf_entry`): the readable
+definition of a VCF line that the device writer (csrc/vcf.hip) is held against.  The BED text of candidates is not part of this surface.
 `members` may be handed over as (signature sequence, index array) and resolves to signature objects on first read, as for clusters.
 """
 from .signatures import _LazyMembers
@@ -120,4 +121,129 @@ class CandidateBreakend(Candidate):
         return round(self.std_pos2, ndigits) if self.std_pos2 else "."
 
 
+# ---- VCF text (src/svim/SVCandidate.py: get_vcf_entry / get_vcf_entry_as_ins / get_vcf_entry_as_dup / get_vcf_entry_reverse) ---------------------------------
+def _fetch(reference, contig, start, end):
+    return reference.fetch(contig, start, end).upper()
+
+
+def _bnd_alt(n_first, opening, contig, start):
+    b = "[" if opening else "]"
+    return ("N" if n_first else "") + "%s%s:%d%s" % (b, contig, start + 1, b) + ("" if n_first else "N")
+
+
+class _VcfRow(object):
+    """One get_vcf_entry* method: where the line sits, what its INFO holds between SVTYPE and SUPPORT, its alleles.
+    args: the method's parameters in the reference's order; place(c) -> (CHROM, POS); mid(c) -> text behind "SVTYPE=<svtype>;" and in front of
+    "SUPPORT="; alleles(c, reference) -> (REF, ALT) with sequence alleles, None: the method has symbolic alleles only; symbolic(c) -> ALT otherwise."""
+
+    def __init__(self, args, svtype, place, mid, symbolic, alleles=None, std=(("STD_SPAN", "get_std_span"), ("STD_POS", "get_std_pos")), tandem=False, cn=False,
+                 seqs=False):
+        self.args, self.svtype, self.place, self.mid, self.symbolic, self.alleles, self.std = args, svtype, place, mid, symbolic, alleles, std
+        self.tandem, self.cn, self.seqs = tandem, cn, seqs
+
+
+_SEQ_ARGS = ("sequence_alleles", "reference", "read_names", "zmws")
+_complement = {"A": "T", "C": "G", "G": "C", "T": "A"}
+
+
+def _inv_alleles(c, reference):
+    ref = _fetch(reference, c.source_contig, c.source_start, c.source_end)
+    return ref, "".join(_complement.get(b, b) for b in reversed(ref))
+
+
+def _del_alleles(c, reference):
+    p = max(0, c.source_start - 1)
+    return _fetch(reference, c.source_contig, p, c.source_end), _fetch(reference, c.source_contig, p, c.source_start)
+
+
+def _ins_alleles(c, reference):
+    if c.sequence == "":
+        return None
+    p = max(0, c.dest_start - 1)
+    ref = _fetch(reference, c.dest_contig, p, p + 1)
+    return ref, ref + c.sequence
+
+
+def _tan_alleles(c, reference):
+    ref = _fetch(reference, c.source_contig, c.source_start, c.source_end)
+    return ref, ref * (c.copies + 1)
+
+
+def _int_alleles(c, reference):
+    p = max(0, c.dest_start - 1)
+    ref = _fetch(reference, c.dest_contig, p, p + 1)
+    return ref, ref + _fetch(reference, c.source_contig, c.source_start, c.source_end)
+
+
+_cut = lambda c: "CUTPASTE;" if c.cutpaste else ""      # noqa: E731
+_VCF = {
+    ("DEL", "get_vcf_entry"): _VcfRow(_SEQ_ARGS, "DEL", lambda c: (c.source_contig, max(1, c.source_start)),
+                                      lambda c: "END=%d;SVLEN=%d;" % (c.source_end, c.source_start - c.source_end), lambda c: "<DEL>", _del_alleles),
+    ("INV", "get_vcf_entry"): _VcfRow(_SEQ_ARGS, "INV", lambda c: (c.source_contig, c.source_start + 1), lambda c: "END=%d;" % c.source_end, lambda c: "<INV>",
+                                      _inv_alleles),
+    ("INS", "get_vcf_entry"): _VcfRow(("sequence_alleles", "reference", "insertion_sequences", "read_names", "zmws"), "INS",
+                                      lambda c: (c.dest_contig, max(1, c.dest_start)), lambda c: "END=%d;SVLEN=%d;" % (c.dest_start, c.dest_end - c.dest_start),
+                                      lambda c: "<INS>", _ins_alleles, seqs=True),
+    ("DUP_TAN", "get_vcf_entry_as_ins"): _VcfRow(_SEQ_ARGS, "INS", lambda c: (c.source_contig, c.source_start + 1),
+                                                 lambda c: "END=%d;SVLEN=%d;" % (c.source_end, c.get_destination()[2] - c.get_destination()[1]),
+                                                 lambda c: "<DUP_TAN>", _tan_alleles, tandem=True),
+    ("DUP_TAN", "get_vcf_entry_as_dup"): _VcfRow(("read_names", "zmws"), "DUP:TANDEM", lambda c: (c.source_contig, c.source_start + 1),
+                                                 lambda c: "END=%d;SVLEN=%d;" % (c.source_end, c.source_end - c.source_start), lambda c: "<DUP:TANDEM>",
+                                                 tandem=True, cn=True),
+    ("DUP_INT", "get_vcf_entry_as_ins"): _VcfRow(_SEQ_ARGS, "INS", lambda c: (c.dest_contig, max(1, c.dest_start)),
+                                                 lambda c: "%sEND=%d;SVLEN=%d;" % (_cut(c), c.dest_start, c.dest_end - c.dest_start), lambda c: "<DUP_INT>",
+                                                 _int_alleles),
+    ("DUP_INT", "get_vcf_entry_as_dup"): _VcfRow(("read_names", "zmws"), "DUP:INT", lambda c: (c.source_contig, c.source_start + 1),
+                                                 lambda c: "%sEND=%d;SVLEN=%d;" % (_cut(c), c.source_end, c.source_end - c.source_start), lambda c: "<DUP:INT>"),
+    ("BND", "get_vcf_entry"): _VcfRow(("read_names", "zmws"), "BND", lambda c: (c.source_contig, c.source_start + 1), lambda c: "",
+                                      lambda c: _bnd_alt(c.source_direction == "fwd", c.dest_direction == "fwd", c.dest_contig, c.dest_start),
+                                      std=(("STD_POS1", "get_std_pos1"), ("STD_POS2", "get_std_pos2"))),
+    ("BND", "get_vcf_entry_reverse"): _VcfRow(("read_names", "zmws"), "BND", lambda c: (c.dest_contig, c.dest_start + 1), lambda c: "",
+                                              lambda c: _bnd_alt(c.dest_direction == "rev", c.source_direction == "rev", c.source_contig, c.source_start),
+                                              std=(("STD_POS1", "get_std_pos2"), ("STD_POS2", "get_std_pos1"))),
+}
+
+
+def vcf_entry(c, row, sequence_alleles=False, reference=None, insertion_sequences=False, read_names=False, zmws=False):
+    """The VCF line of candidate `c` under row `row` of _VCF, with PLACEHOLDERFORID where write_final_vcf puts the id."""
+    chrom, pos = row.place(c)
+    alleles = row.alleles(c, reference) if (sequence_alleles and row.alleles is not None) else None
+    ref, alt = alleles if alleles is not None else ("N", row.symbolic(c))
+    filters = (["hom_ref"] if c.genotype == "0/0" else []) + (["not_fully_covered"] if row.tandem and not c.fully_covered else [])
+    reads = [m.read for m in c.members]
+    info = "SVTYPE=%s;%sSUPPORT=%d;%s" % (row.svtype, row.mid(c), len(set(reads)), ";".join("%s=%s" % (k, getattr(c, g)()) for k, g in row.std))
+    if row.seqs and insertion_sequences:
+        info += ";SEQS=" + ",".join(m.sequence for m in c.members)
+    if read_names:
+        info += ";READS=" + ",".join(reads)
+    if zmws:
+        fields = [r.split("/") for r in reads]
+        if all(len(f) == 3 for f in fields):
+            info += ";ZMWS=%d" % len(set("/".join(f[0:2]) for f in fields))
+    none = lambda v: "." if v is None else v      # noqa: E731
+    dp = str(c.ref_reads + c.alt_reads) if c.ref_reads is not None and c.alt_reads is not None else "."
+    sample = [c.genotype] + ([str(c.copies + 1)] if row.cn else []) + [dp, "%s,%s" % (none(c.ref_reads), none(c.alt_reads))]
+    return "\t".join([chrom, str(pos), "PLACEHOLDERFORID", ref, alt, str(int(c.score)), ";".join(filters) or "PASS", info, "GT:CN:DP:AD" if row.cn else "GT:DP:AD",
+                      ":".join(sample)])
+
+
+def _vcf_method(row, name):
+    defaults = dict(sequence_alleles=False, reference=None, insertion_sequences=False, read_names=False, zmws=False)
+
+    def method(self, *args, **kwargs):
+        if len(args) > len(row.args):
+            raise TypeError("%s() takes at most %d arguments (%d given)" % (name, len(row.args), len(args)))
+        o = dict(defaults)
+        o.update(zip(row.args, args))
+        for k, v in kwargs.items():
+            if k not in row.args or k in row.args[:len(args)]:
+                raise TypeError("%s() got an unexpected or repeated argument %r" % (name, k))
+            o[k] = v
+        return vcf_entry(self, row, **o)
+    method.__name__ = name
+    return method
+
+
 CLASSES = (CandidateDeletion, CandidateInversion, CandidateDuplicationInterspersed, CandidateDuplicationTandem, CandidateNovelInsertion, CandidateBreakend)
+for (_type, _name), _row in _VCF.items():
+    setattr({c.type: c for c in CLASSES}[_type], _name, _vcf_method(_row, _name))

@@ -227,6 +227,33 @@ def candidate_objects_range(t, lo, hi, sig_objects, references):
     return out
 
 
+def natural_key(name):
+    """sorted_nicely's key of a contig name (src/svim/SVIM_COMBINE.py:65-66): the digit runs as integers, what lies between as text"""
+    import re
+    return [int(c) if c.isdigit() else c for c in re.split("([0-9]+)", str(name))]
+
+
+def natural_ranks(names):
+    """rank of every name under natural_key, EQUAL for names with equal keys ("chr1" / "chr01": the writer's sort is stable over them) -> int32 array"""
+    keys = [natural_key(n) for n in names]
+    order = {}
+    for k in sorted(keys):
+        order.setdefault(tuple(k), len(order))
+    return np.fromiter((order[tuple(k)] for k in keys), dtype=np.int32, count=len(keys))
+
+
+def zmw_ids(read_names):
+    """per read name the dense id of "/".join(fields[0:2]) when the name has exactly three '/'-separated fields, else -1 (the ZMWS count of the VCF
+    writer, e.g. src/svim/SVCandidate.py:106-116) -> int32 array"""
+    ids = {}
+    out = np.full(len(read_names), -1, dtype=np.int32)
+    for i, n in enumerate(read_names):
+        f = n.split("/")
+        if len(f) == 3:
+            out[i] = ids.setdefault("/".join(f[0:2]), len(ids))
+    return out
+
+
 def candidate_lists(t, sig_objects, references):
     """CandidateTable -> the 6-tuple combine_clusters returns (DEL, INV, DUP_INT, DUP_TAN, INS, BND) of lazy CandidateLists"""
     from .lazy import CandidateList

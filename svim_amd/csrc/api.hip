@@ -99,7 +99,7 @@ extern "C" int svx_ctx_create(int device_ordinal, svx_ctx** out) {
         c->mail_mode = e && e[0] == '0' ? 0 : 1;
     }
     memset(&c->stats, 0, sizeof c->stats);
-    svx_preload_collect(); svx_preload_cluster(); svx_preload_edit(); svx_preload_prims(); svx_preload_combine();       // code objects now, not inside the first call
+    svx_preload_collect(); svx_preload_cluster(); svx_preload_edit(); svx_preload_prims(); svx_preload_combine(); svx_preload_vcf();       // code objects now, not inside the first call
     { const char* e = getenv("SVX_EDIT_FORCE_FULL"); c->edit_force_full = e && e[0] == '1'; }
     { const char* e = getenv("SVX_EDIT_GUESS"); if (e && atof(e) > 0) { c->edit_guess = (float)atof(e); c->edit_guess_pinned = true; } }
     *out = c;
@@ -122,6 +122,7 @@ extern "C" void svx_ctx_destroy(svx_ctx* c) {
     for (auto& b : c->user_sig) b.release();
     for (auto& b : c->geno) b.release();
     svx_combine_release(c);
+    svx_vcf_release(c);
     for (auto& ev : c->ev) (void)hipEventDestroy(ev);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->mail) (void)hipHostFree(c->mail);

@@ -64,6 +64,7 @@ struct CombineState {
     DevBuf pool[NPOOL]; int used = 0;
     DevBuf rm1_list, rm2_list; int64_t n_rm1 = 0, n_rm2 = 0;
     bool have_stage2 = false, have_result = false;
+    bool from_resident = false; long long cluster_call = 0;      // the call took the resident clusters (source 0) of svx_cluster call number cluster_call
     svx_combine_stats stats;
     template <class Tp> int get(Tp** out, size_t count) {
         if (used >= NPOOL) return svx_fail(SVX_E_CAPACITY, "combine: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
@@ -815,6 +816,7 @@ extern "C" int svx_combine(svx_ctx* c, int source, const svx_cluster_view* cv, c
     if (!c->combine) c->combine = new CombineState();
     CombineState* S = c->combine;
     S->used = 0; S->have_stage2 = false; S->have_result = false; S->n_rm1 = S->n_rm2 = 0;
+    S->from_resident = source == 0; S->cluster_call = c->cluster_calls;
     memset(&S->stats, 0, sizeof S->stats);
     for (CandTab* t : {&S->merged, &S->flagged, &S->fdup, &S->result}) { t->n = t->n_members = 0; for (auto& x : t->class_count) x = 0; }
     hipStream_t st = c->stream;
@@ -868,6 +870,19 @@ extern "C" int svx_combine(svx_ctx* c, int source, const svx_cluster_view* cv, c
         float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[20], c->ev[21])); S->stats.t_combine_ms = ms;
     }
     return rc;
+}
+
+bool svx_combine_resident(svx_ctx* c, CandDev* o) {
+    if (!c->combine || !c->combine->have_result) return false;
+    const CombineState* S = c->combine;
+    const CandTab& t = S->result;
+    const CandPtrs p = t.ptrs();
+    o->n = t.n; o->n_members = t.n_members;
+    for (int k = 0; k < SVX_NCAND; k++) o->class_count[k] = t.class_count[k];
+    o->cls = p.cls; o->contig = p.contig; o->start = p.start; o->end = p.end; o->contig2 = p.contig2; o->start2 = p.start2; o->end2 = p.end2; o->aux = p.aux;
+    o->copies = p.copies; o->score = p.score; o->std_span = p.std_span; o->std_pos = p.std_pos; o->member_off = p.member_off; o->members = p.members;
+    o->from_resident = S->from_resident; o->cluster_call = S->cluster_call;
+    return true;
 }
 
 extern "C" int svx_combine_count(svx_ctx* c, int64_t* n_candidates, int64_t* n_members) {

@@ -187,8 +187,22 @@ struct svx_ctx {
     // svx_cluster calls this context has seen (0: nothing resident for svx_combine source 0), and the stage's own buffers and results
     const uint8_t* last_cluster_aux = nullptr; long long cluster_calls = 0;
     struct CombineState* combine = nullptr;
+    // VCF text (vcf.hip): the columns of that same signature table the lines are made of (read ids for SUPPORT / READS / ZMWS, inserted bases for SEQS),
+    // and the stage's own buffers and results
+    const int32_t* last_cluster_read_id = nullptr; const int64_t* last_cluster_seq_off = nullptr; const uint8_t* last_cluster_seq = nullptr;
+    struct VcfState* vcf = nullptr;
 };
 void svx_combine_release(svx_ctx* c);
+void svx_vcf_release(svx_ctx* c);
+// the candidate table the last svx_combine left in the context, as device pointers (combine.hip; vcf.hip reads it for source 0).  from_resident: that call took
+// the resident clusters (source 0), at svx_cluster call number cluster_call - only then do the members index the signature table the context still describes
+struct CandDev {
+    int64_t n, n_members; int64_t class_count[SVX_NCAND];
+    const uint8_t* cls; const int32_t *contig, *start, *end, *contig2, *start2, *end2; const uint8_t* aux; const int32_t* copies;
+    const double *score, *std_span, *std_pos; const int64_t* member_off; const int32_t* members;
+    bool from_resident; long long cluster_call;
+};
+bool svx_combine_resident(svx_ctx* c, CandDev* out);
 
 // ---- primitives (prims.hip, scan.hpp: hand-written radix sort and scan) -------------------------------
 int svx_sort_pairs_u64(svx_ctx* c, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
@@ -227,7 +241,7 @@ inline int svx_mail_read3(svx_ctx* c, hipStream_t st, const void* a, int na, voi
     return svx_mail_gather(c, st, 3, srcs, n, dsts);
 }
 
-void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims(); void svx_preload_combine();      // code objects loaded at context creation
+void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims(); void svx_preload_combine(); void svx_preload_vcf();      // code objects loaded at context creation
 
 // ---- stage entry points ------------------------------------------------------------------------------------
 int svx_collect_impl(svx_ctx* c, const svx_batch* b_dev, const svx_params* p);
