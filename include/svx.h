@@ -417,6 +417,58 @@ int  svx_set_alignment_index(svx_ctx* ctx, const svx_aln_index* host_index);
 int  svx_genotype(svx_ctx* ctx, int32_t mode, int64_t n_cand, const int32_t* cand_tid, const int32_t* cand_start, const int32_t* cand_end,
                   const int64_t* member_off /* [n_cand+1] */, const int32_t* member_names, int32_t min_mapq, int32_t* out_ref_reads);
 
+/* ---- GENOTYPE from resident tables: the candidate table against an alignment table filled while COLLECT runs ----------------------------------------------
+ * svx_collect_keep_alignments(ctx, 1): while it and svx_collect_accumulate are on, every svx_collect appends ALL records of its batch, in file order, to a table
+ * resident in the context: tid, pos, end, flag, mapq, read_id.  end = reference_end (pos + the lengths of the M D N = X operations, by a kernel of its own:
+ * csrc/alnindex.hip) for records that are placed (tid >= 0), mapped, not secondary and not marked SVX_FLAG_SKIP; every other record is kept with end = pos and
+ * its CIGAR is not read (genotype() skips such a record before it counts, src/svim/SVIM_genotyping.py:64-65).  A record marked SVX_FLAG_SKIP is stored with the
+ * unmapped bit (4) set.  Nothing is filtered by mapping quality, so a later svx_genotype_resident may ask for any min_mapq.  svx_collect_accumulate(ctx, 1)
+ * empties the table as it empties the lists.  Off (the default): svx_collect does what it did, no kernel, no allocation.
+ * Records of one read must share their read_id across the batches of the file (the readers of svx_bam_* intern names per handle). */
+int  svx_collect_keep_alignments(svx_ctx* ctx, int on);
+int  svx_alignments_count(svx_ctx* ctx, int64_t* n);
+int  svx_alignments_fetch(svx_ctx* ctx, int32_t* tid, int32_t* pos, int32_t* end, uint16_t* flag, uint8_t* mapq, int32_t* read_id);   /* host, [n]; NULL skipped */
+typedef struct svx_alignments_stats {
+    double  t_append_ms;       /* HIP events around the appends since the table was emptied (growth copies included), summed */
+    double  t_span_ms;         /* the append and long-record kernels alone, summed */
+    double  t_finalise_ms;     /* order check + running end maximum of the last finalisation */
+    int64_t n_records, n_ops_read, n_long_records;
+} svx_alignments_stats;
+int  svx_alignments_get_stats(svx_ctx* ctx, svx_alignments_stats* out);
+typedef struct svx_genotype_params {
+    double  minimum_score;          /* 3   : candidates with score < minimum_score are not genotyped (:38-39) */
+    int32_t min_mapq;               /* 20  */
+    int32_t minimum_depth;          /* 4   */
+    double  homozygous_threshold;   /* 0.8 */
+    double  heterozygous_threshold; /* 0.2 */
+} svx_genotype_params;
+typedef struct svx_genotype_stats {
+    double  t_total_ms;        /* HIP events on the context's stream around the whole call */
+    double  t_tables_ms;       /* source 2 upload + finalisation of the alignment table (order check, contig_first, running end maximum: once per append) */
+    double  t_distinct_ms;     /* loci, distinct member reads, compaction */
+    double  t_walk_ms;         /* k_genotype */
+    double  t_call_ms;
+    int64_t n_candidates, n_members, n_alignments;
+} svx_genotype_stats;
+/* genotype() (src/svim/SVIM_genotyping.py:34-93) for the DEL, INV, INS and DUP_INT rows of a candidate table in one call, against the resident alignment table
+ * (SVX_E_STATE when there is none, or when its records are not in coordinate order: "genotyping needs a coordinate-sorted alignment file").
+ * source: 0 = the candidate table resident from the last svx_combine, which must have taken the resident clusters, and the signature table its members index;
+ *         2 = `cand` (host memory, grouped by class in SVX_CAND_* order, class_count set; the columns cls, contig, start, end, contig2, start2, score,
+ *             member_off and members are read) plus sig_read_id[n_sig], the read_id of the signatures its members index.
+ * Read identity is the read_id: the ids of the signatures and of the alignment table must come from one interning.  contig_len[n_contig]: reference lengths.
+ * Rows of other classes and rows with score < minimum_score get gt 0 ("./."), reads -1 (None) and support fraction NaN (".").  The columns stay resident
+ * until the next svx_genotype_resident; a later svx_combine or svx_cluster voids them (SVX_E_STATE from svx_genotype_fetch and from a svx_vcf that asks
+ * for them). */
+int  svx_genotype_resident(svx_ctx* ctx, int source, const svx_candidate_view* cand, const int32_t* sig_read_id, int64_t n_sig, int32_t n_contig,
+                           const int64_t* contig_len, const svx_genotype_params* p);
+int  svx_genotype_count(svx_ctx* ctx, int64_t* n_cand);
+/* gt: codes of svx_vcf_inputs.gt; ref_reads / alt_reads: -1 = None; support_fraction: NaN = ".".  Host arrays [n_cand]; NULL skipped */
+int  svx_genotype_fetch(svx_ctx* ctx, uint8_t* gt, int32_t* ref_reads, int32_t* alt_reads, double* support_fraction);
+int  svx_genotype_get_stats(svx_ctx* ctx, svx_genotype_stats* out);
+/* on: a svx_vcf with source 0 and no genotype column handed in (gt, ref_reads and alt_reads all NULL) prints the columns svx_genotype_resident (source 0) left
+ * for that table, read in place; SVX_E_STATE if there are none for it.  Off (the default): such a call prints "./." as before. */
+int  svx_vcf_use_resident_genotypes(svx_ctx* ctx, int on);
+
 /* ---- single-function entry points kept importable by the reference's API ------------------------ */
 /* analyze_cigar_indel (src/svim/SVIM_intra.py:8-30) on one packed CIGAR; out arrays sized n_ops */
 int  svx_cigar_indel(svx_ctx* ctx, const uint32_t* cigar_host, int64_t n_ops, int32_t min_length,

@@ -376,7 +376,8 @@ def vcf_body_device(int_dup, inv, tan_dup, dele, ins, bnd, contig_names, types_t
     if _resident_candidates(lists6, eng):
         first = lists6[0]
         references, names = first.references, (first.signatures.read_names if need_names else None)
-        run = lambda: eng.vcf(vp, references, read_names=names)      # noqa: E731
+        resident_gt = getattr(eng, "_resident_gt_table", None) is first.table      # genotype_resident ran on this very table: its columns, read in place
+        run = lambda: eng.vcf(vp, references, read_names=names, resident_genotypes=resident_gt)      # noqa: E731
     else:
         built = candidate_table_from_lists(lists6, contig_names)
         if built is None:
@@ -396,7 +397,8 @@ def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_dup
     """src/svim/SVIM_COMBINE.py:71-186: <working_dir>/variants.vcf.  The header is written here; the lines behind it are made on the device (svx_vcf) and
     fetched in pieces.  Routes, as combine_clusters has them:
       * the six lists are the untouched CandidateList views of the table the engine holds from its last combine_clusters of resident clusters: source 0 with
-        the default genotype columns - nothing is uploaded but names, no object is made;
+        the default genotype columns, or - after SVIM_genotyping.genotype_resident - the columns that call left on the device: nothing is uploaded but names, no
+        object is made;
       * anything else (plain lists, lists genotype() wrote to, breakend_candidates + breakend_candidates_all_bnds of --all_bnds): one pass over the objects
         builds the candidate table, the genotype columns and the member signature columns: source 2.
     A novel insertion candidate with a non-empty `sequence` (only hand-made objects have one: the device COMBINE implements the skip_consensus branch) or a

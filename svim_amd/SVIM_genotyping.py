@@ -1,6 +1,7 @@
 """GENOTYPE on the GPU: drop-in for svim.SVIM_genotyping (src/svim/SVIM_genotyping.py) - same entry points, same results.
 
     genotype(candidates, bam, type, options)          mutates the candidates like the reference (:79-93)
+    genotype_resident(engine, options, lengths)       the same for all four types at once, from the tables resident in the engine: no object is made
     span_position_distance(candidate, signature, n)   (:9-31)
 
 The reference re-fetches the BAM around every candidate (:48).  Here the alignment records are indexed once per file
@@ -137,3 +138,40 @@ def genotype(candidates, bam, type, options, engine=None):
             c.genotype = "./."
         c.ref_reads = n_ref
         c.alt_reads = n_alt
+
+
+def genotype_calls(alt_reads, ref_reads, options):
+    """The call of :77-93 from the two counts, as the table route states it: -> (genotype code of _abi.GT_NAMES, support_fraction or ".")."""
+    total = alt_reads + ref_reads
+    if total >= options.minimum_depth and total > 0:
+        f = alt_reads / total
+        return (3 if f >= options.homozygous_threshold else 2 if f >= options.heterozygous_threshold else 1 if f < options.heterozygous_threshold else 0), f
+    if total > 0:
+        return 0, alt_reads / total
+    return 0, "."
+
+
+def candidate_loci(table, minimum_score):
+    """Class and score select of the table route (:38-46): -> (selected bool[n], mode int8[n] (0 = DEL / INV, 1 = INS / DUP_INT), tid, start, end int32[n]);
+    rows that are not selected have tid -1."""
+    from ._abi import CAND_DEL, CAND_INV, CAND_DUP_INT, CAND_INS
+    cls = np.asarray(table.cls[:table.n])
+    point = (cls == CAND_INS) | (cls == CAND_DUP_INT)
+    sel = (point | (cls == CAND_DEL) | (cls == CAND_INV)) & ~(np.asarray(table.score[:table.n]) < minimum_score)
+    tid = np.where(sel, np.where(point, table.contig2[:table.n], table.contig[:table.n]), -1).astype(np.int32)
+    start = np.where(sel, np.where(point, table.start2[:table.n], table.start[:table.n]), 0).astype(np.int32)
+    end = np.where(sel, np.where(point, start, table.end[:table.n]), 0).astype(np.int32)
+    return sel, point.astype(np.int8), tid, start, end
+
+
+def genotype_resident(engine, options, lengths):
+    """genotype() for the deletion, inversion, novel insertion and interspersed duplication candidates resident in `engine` (its last combine() of resident
+    clusters) against the alignment table it kept while the file was collected (Engine.keep_alignments / harness.BamPipeline(keep_alignments=True)).
+    Nothing leaves the device but the four columns, which are returned (Engine.fetch_genotypes) and attached to the CandidateTable the engine handed out for
+    that combine(): CandidateList objects built afterwards carry them, and write_final_vcf prints them from the device."""
+    engine.genotype_resident(options, lengths)
+    g = engine.fetch_genotypes()
+    t = getattr(engine, "_resident_cand", None)
+    if t is not None:
+        t.genotypes = g
+    return g

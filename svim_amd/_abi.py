@@ -181,6 +181,33 @@ class VcfStats(C.Structure):
         return d
 
 
+class GenotypeParams(C.Structure):
+    _fields_ = [("minimum_score", C.c_double), ("min_mapq", C.c_int32), ("minimum_depth", C.c_int32), ("homozygous_threshold", C.c_double),
+                ("heterozygous_threshold", C.c_double)]
+
+    @classmethod
+    def from_options(cls, o):
+        return cls(float(o.minimum_score), int(o.min_mapq), int(o.minimum_depth), float(o.homozygous_threshold), float(o.heterozygous_threshold))
+
+
+class GenotypeStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_total_ms", "t_tables_ms", "t_distinct_ms", "t_walk_ms", "t_call_ms")] + \
+               [(n, C.c_int64) for n in ("n_candidates", "n_members", "n_alignments")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class AlignmentsStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_append_ms", "t_span_ms", "t_finalise_ms")] + [(n, C.c_int64) for n in ("n_records", "n_ops_read", "n_long_records")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+GT_NAMES = ("./.", "0/0", "0/1", "1/1")      # codes of svx_vcf_inputs.gt / svx_genotype_fetch
+
+
 class AlnIndex(C.Structure):
     _fields_ = [("n", C.c_int64), ("n_contig", C.c_int32), ("reserved", C.c_int32), ("contig_first", _P), ("contig_len", _P),
                 ("pos", _P), ("end", _P), ("flag", _P), ("mapq", _P), ("name_id", _P)]
@@ -322,10 +349,11 @@ class ClusterTable(object):
 
 class CandidateTable(object):
     """Host-side candidate table (numpy SoA; include/svx.h: svx_candidate_view), grouped by class in CAND_* order."""
-    __slots__ = tuple(CAND_DTYPES) + ("member_off", "members", "n", "n_members", "class_count")
+    __slots__ = tuple(CAND_DTYPES) + ("member_off", "members", "n", "n_members", "class_count", "genotypes")
 
     def __init__(self, n, n_members):
         self.n, self.n_members = n, n_members
+        self.genotypes = None             # SVIM_genotyping.genotype_resident: the columns of Engine.fetch_genotypes() for this table
         for k, dt in CAND_DTYPES.items():
             setattr(self, k, np.zeros(max(1, n), dtype=dt))
         self.member_off = np.zeros(n + 1, dtype=np.int64)

@@ -21,6 +21,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_collect", "svx_collect_count", "svx_collect_fetch", "svx_collect_geom_fetch", "svx_collect_accumulate", "svx_collect_set_slot_base", "svx_set_genome", "svx_cluster",
            "svx_cluster_count", "svx_cluster_fetch", "svx_cluster_set_ranks", "svx_cluster_abort_ranks", "svx_cluster_stream_positions",
            "svx_set_alignment_index", "svx_genotype",
+           "svx_collect_keep_alignments", "svx_alignments_count", "svx_alignments_fetch", "svx_alignments_get_stats",
+           "svx_genotype_resident", "svx_genotype_count", "svx_genotype_fetch", "svx_genotype_get_stats", "svx_vcf_use_resident_genotypes",
            "svx_cigar_indel", "svx_edit_distance", "svx_linkage_fcluster", "svx_pair_distances",
            "svx_bam_open", "svx_bam_close", "svx_bam_header", "svx_bam_read_batch", "svx_bam_read_names", "svx_bam_set_seq_filter", "svx_bam_rewind", "svx_bam_seek", "svx_bam_set_gpu_inflate", "svx_bam_gpu_inflate_stats",
            "svx_inflater_create", "svx_inflater_destroy", "svx_inflater_staging", "svx_inflater_enqueue", "svx_inflater_wait",
@@ -282,7 +284,7 @@ class Engine(object):
         if rc == _abi.SVX_E_NO_DELETION:
             raise NoDeletionClusters(self.L.svx_last_error().decode("utf-8", "replace"))
         _check(rc, "svx_combine")
-        self._resident_cand = None
+        self._resident_cand = self._resident_gt_table = None
         if not fetch:
             return None
         t = self.fetch_candidates()
@@ -317,10 +319,11 @@ class Engine(object):
 
     # ---- VCF text ----
     def vcf(self, vparams, references, table=None, sig_read_id=None, sig_seq_off=None, sig_seq=None, gt=None, ref_reads=None, alt_reads=None, read_names=None,
-            zmw_id=None):
+            zmw_id=None, resident_genotypes=False):
         """svx_vcf: the body of variants.vcf (every line behind the header) of the candidates resident from the last combine() of the resident clusters
         (table None, source 0) or of the CandidateTable `table` whose members index signatures with the columns sig_read_id / sig_seq_off / sig_seq (source 2).
         references: names of the table's contig ids.  gt (codes of _abi.VCF_GT) / ref_reads / alt_reads (-1 = None): genotype columns, default "./." / None.
+        resident_genotypes (table None, no column given): the columns the last genotype_resident() left for the resident candidates, read in place.
         read_names: names by read id (vparams.read_names); zmw_id: convert.zmw_ids of them (vparams.zmws).  The text stays on the device:
         -> (number of lines, number of bytes); vcf_fetch() / vcf_line_offsets() bring it over."""
         from . import convert
@@ -355,7 +358,11 @@ class Engine(object):
         if vparams.zmws:
             inp.zmw_id = arr(convert.zmw_ids(read_names) if zmw_id is None else zmw_id, np.int32)
         if table is None:
-            rc = self.L.svx_vcf(self.ctx, 0, None, None, C.byref(vparams), C.byref(inp))
+            _check(self.L.svx_vcf_use_resident_genotypes(self.ctx, C.c_int(1 if resident_genotypes else 0)), "svx_vcf_use_resident_genotypes")
+            try:
+                rc = self.L.svx_vcf(self.ctx, 0, None, None, C.byref(vparams), C.byref(inp))
+            finally:
+                self.L.svx_vcf_use_resident_genotypes(self.ctx, C.c_int(0))
         else:
             v = table.view()
             for k in range(6):
@@ -410,6 +417,63 @@ class Engine(object):
         _check(self.L.svx_genotype(self.ctx, C.c_int32(mode), C.c_int64(n), ptr(tid), ptr(start), ptr(end), ptr(member_off),
                                    ptr(member_names if member_names.size else np.zeros(1, np.int32)), C.c_int32(min_mapq), ptr(out)), "svx_genotype")
         return out[:n]
+
+    # ---- GENOTYPE from resident tables ----
+    def keep_alignments(self, on):
+        """on: while accumulate() is on too, every collect() appends its batch's records to the alignment table resident in the context
+        (svx_collect_keep_alignments) - what genotype_resident() joins the candidates with"""
+        _check(self.L.svx_collect_keep_alignments(self.ctx, C.c_int(1 if on else 0)), "svx_collect_keep_alignments")
+
+    def alignments(self):
+        """the resident alignment table (svx_alignments_fetch) -> dict of numpy columns tid, pos, end, flag, mapq, read_id, in file order"""
+        n = C.c_int64()
+        _check(self.L.svx_alignments_count(self.ctx, C.byref(n)), "svx_alignments_count")
+        cols = dict(tid=np.int32, pos=np.int32, end=np.int32, flag=np.uint16, mapq=np.uint8, read_id=np.int32)
+        out = {k: np.zeros(max(1, n.value), dtype=dt) for k, dt in cols.items()}
+        _check(self.L.svx_alignments_fetch(self.ctx, *[ptr(out[k]) for k in cols]), "svx_alignments_fetch")
+        return {k: a[:n.value] for k, a in out.items()}
+
+    def alignments_stats(self):
+        s = _abi.AlignmentsStats()
+        _check(self.L.svx_alignments_get_stats(self.ctx, C.byref(s)), "svx_alignments_get_stats")
+        return s.as_dict()
+
+    def genotype_resident(self, options, lengths, table=None, sig_read_id=None):
+        """svx_genotype_resident: genotype() of the reference for the DEL, INV, INS and DUP_INT rows of the candidates resident from the last combine() of
+        resident clusters (table None, source 0) or of the CandidateTable `table` whose members index signatures with the read ids `sig_read_id` (source 2),
+        against the resident alignment table.  options: minimum_score, min_mapq, minimum_depth, homozygous_threshold, heterozygous_threshold (or a
+        _abi.GenotypeParams); lengths: reference lengths by contig id.  The columns stay on the device: fetch_genotypes() brings them over."""
+        gp = options if isinstance(options, _abi.GenotypeParams) else _abi.GenotypeParams.from_options(options)
+        clen = np.ascontiguousarray(lengths, dtype=np.int64)
+        self._resident_gt_table = None
+        if table is None:
+            rc = self.L.svx_genotype_resident(self.ctx, 0, None, None, C.c_int64(0), C.c_int32(clen.size), ptr(clen if clen.size else np.zeros(1, np.int64)),
+                                              C.byref(gp))
+        else:
+            v = table.view()
+            for k in range(6):
+                v.class_count[k] = int(table.class_count[k])
+            rid = np.ascontiguousarray(sig_read_id if sig_read_id is not None else np.zeros(0, np.int32), dtype=np.int32)
+            rc = self.L.svx_genotype_resident(self.ctx, 2, C.byref(v), ptr(rid if rid.size else np.zeros(1, np.int32)), C.c_int64(rid.size), C.c_int32(clen.size),
+                                              ptr(clen if clen.size else np.zeros(1, np.int64)), C.byref(gp))
+        _check(rc, "svx_genotype_resident")
+        if table is None:      # (SVIM_COMBINE.vcf_body_device: views of this very table are written with these columns, read in place)
+            self._resident_gt_table = getattr(self, "_resident_cand", None)
+
+    def fetch_genotypes(self):
+        """columns of the last genotype_resident() (svx_genotype_fetch) -> dict: gt (uint8 codes of _abi.GT_NAMES), ref_reads / alt_reads (int32, -1 = None),
+        support_fraction (float64, NaN = ".")"""
+        n = C.c_int64()
+        _check(self.L.svx_genotype_count(self.ctx, C.byref(n)), "svx_genotype_count")
+        out = dict(gt=np.zeros(max(1, n.value), np.uint8), ref_reads=np.zeros(max(1, n.value), np.int32), alt_reads=np.zeros(max(1, n.value), np.int32),
+                   support_fraction=np.zeros(max(1, n.value), np.float64))
+        _check(self.L.svx_genotype_fetch(self.ctx, ptr(out["gt"]), ptr(out["ref_reads"]), ptr(out["alt_reads"]), ptr(out["support_fraction"])), "svx_genotype_fetch")
+        return {k: a[:n.value] for k, a in out.items()}
+
+    def genotype_stats(self):
+        s = _abi.GenotypeStats()
+        _check(self.L.svx_genotype_get_stats(self.ctx, C.byref(s)), "svx_genotype_get_stats")
+        return s.as_dict()
 
     def set_ranks(self, rank, world, allgather=None):
         """Contig-sharded ranks (svx_cluster_set_ranks): this engine is rank `rank` of `world`; allgather(send: bytes) -> bytes of all ranks, rank-major

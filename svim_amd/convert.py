@@ -227,6 +227,19 @@ def candidate_objects_range(t, lo, hi, sig_objects, references):
     return out
 
 
+def apply_genotype_columns(objs, g, lo):
+    """the genotype columns of Engine.fetch_genotypes() onto the candidate objects of rows lo .. lo + len(objs) - 1, as genotype() (src/svim/SVIM_genotyping.py:79-93)
+    leaves them; a row that was not genotyped (ref_reads -1) keeps the constructor's defaults"""
+    from ._abi import GT_NAMES
+    hi = lo + len(objs)
+    gt, rr, ar, sf = g["gt"][lo:hi].tolist(), g["ref_reads"][lo:hi].tolist(), g["alt_reads"][lo:hi].tolist(), g["support_fraction"][lo:hi].tolist()
+    for k, o in enumerate(objs):
+        if rr[k] < 0:
+            continue
+        o.support_fraction = "." if sf[k] != sf[k] else sf[k]
+        o.genotype, o.ref_reads, o.alt_reads = GT_NAMES[gt[k]], rr[k], ar[k]
+
+
 def natural_key(name):
     """sorted_nicely's key of a contig name (src/svim/SVIM_COMBINE.py:65-66): the digit runs as integers, what lies between as text"""
     import re

@@ -99,7 +99,7 @@ extern "C" int svx_ctx_create(int device_ordinal, svx_ctx** out) {
         c->mail_mode = e && e[0] == '0' ? 0 : 1;
     }
     memset(&c->stats, 0, sizeof c->stats);
-    svx_preload_collect(); svx_preload_cluster(); svx_preload_edit(); svx_preload_prims(); svx_preload_combine(); svx_preload_vcf();       // code objects now, not inside the first call
+    svx_preload_collect(); svx_preload_cluster(); svx_preload_edit(); svx_preload_prims(); svx_preload_combine(); svx_preload_vcf(); svx_preload_alnindex();       // code objects now, not inside the first call
     { const char* e = getenv("SVX_EDIT_FORCE_FULL"); c->edit_force_full = e && e[0] == '1'; }
     { const char* e = getenv("SVX_EDIT_GUESS"); if (e && atof(e) > 0) { c->edit_guess = (float)atof(e); c->edit_guess_pinned = true; } }
     *out = c;
@@ -123,6 +123,8 @@ extern "C" void svx_ctx_destroy(svx_ctx* c) {
     for (auto& b : c->geno) b.release();
     svx_combine_release(c);
     svx_vcf_release(c);
+    svx_aln_release(c);
+    svx_genotype_release(c);
     for (auto& ev : c->ev) (void)hipEventDestroy(ev);
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->mail) (void)hipHostFree(c->mail);
@@ -291,6 +293,7 @@ extern "C" int svx_collect(svx_ctx* c, const svx_batch* b, const svx_params* p) 
     if (c->accumulate) {
         SVXCHK(append_sigs(c, c->acc_sig, c->sig));
         SVXCHK(append_sigs(c, c->acc_bnd, c->bnd));
+        if (c->keep_alignments) SVXCHK(svx_aln_append(c, &d));
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return SVX_OK;
@@ -316,6 +319,7 @@ extern "C" int svx_collect_accumulate(svx_ctx* c, int mode) {
     }
     c->accumulate = mode != 0;
     c->acc_sig.n = c->acc_sig.n_seq = 0; c->acc_bnd.n = c->acc_bnd.n_seq = 0;
+    if (mode != 0) svx_aln_clear(c);
     c->slot_base = 0;
     return SVX_OK;
 }

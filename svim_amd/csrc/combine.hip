@@ -817,6 +817,7 @@ extern "C" int svx_combine(svx_ctx* c, int source, const svx_cluster_view* cv, c
     CombineState* S = c->combine;
     S->used = 0; S->have_stage2 = false; S->have_result = false; S->n_rm1 = S->n_rm2 = 0;
     S->from_resident = source == 0; S->cluster_call = c->cluster_calls;
+    c->combine_calls++;                                             // (genotype columns of an earlier candidate table are void from here on: genotype.hip)
     memset(&S->stats, 0, sizeof S->stats);
     for (CandTab* t : {&S->merged, &S->flagged, &S->fdup, &S->result}) { t->n = t->n_members = 0; for (auto& x : t->class_count) x = 0; }
     hipStream_t st = c->stream;

@@ -157,6 +157,11 @@ struct svx_ctx {
     DevBuf k_hi, k_lo, k_idx, k_hi2, k_lo2, k_idx2, part_flag, part_id, part_start, part_meta, samp_idx, large_list, samp_stream;
     DevBuf cell_shards;
     DevBuf geno[11]; int64_t geno_n = 0; int32_t geno_contigs = -1;      // GENOTYPE: resident alignment index + per-call candidate buffers
+    // GENOTYPE from resident tables: the alignment table svx_collect appends to while svx_collect_keep_alignments is on (alnindex.hip), the genotype columns
+    // of the last svx_genotype_resident (genotype.hip), how many svx_combine calls the context has seen (the columns belong to one of them), and whether
+    // svx_vcf source 0 reads the columns in place (svx_vcf_use_resident_genotypes)
+    struct AlnTable* aln = nullptr; bool keep_alignments = false;
+    struct GenoState* genores = nullptr; long long combine_calls = 0; bool vcf_resident_gt = false;
     DevBuf samp_meta, samp_table, samp_runs, samp_chain;    // consumption tables of the sampling walk; per-type stream positions
     int xr_rank = 0, xr_world = 1; svx_allgather_fn xr_fn = nullptr; void* xr_user = nullptr; bool xr_pending = false;   // svx_cluster_set_ranks
     long long stream_start[SVX_NTYPES] = {0, 0, 0, 0, 0, 0}, stream_end[SVX_NTYPES] = {0, 0, 0, 0, 0, 0};              // of the last svx_cluster
@@ -194,6 +199,8 @@ struct svx_ctx {
 };
 void svx_combine_release(svx_ctx* c);
 void svx_vcf_release(svx_ctx* c);
+void svx_aln_release(svx_ctx* c);
+void svx_genotype_release(svx_ctx* c);
 // the candidate table the last svx_combine left in the context, as device pointers (combine.hip; vcf.hip reads it for source 0).  from_resident: that call took
 // the resident clusters (source 0), at svx_cluster call number cluster_call - only then do the members index the signature table the context still describes
 struct CandDev {
@@ -203,6 +210,26 @@ struct CandDev {
     bool from_resident; long long cluster_call;
 };
 bool svx_combine_resident(svx_ctx* c, CandDev* out);
+
+// alignment records in file order as the genotype walk reads them (genotype.hip): svx_set_alignment_index uploads one, the resident alignment table is one
+struct AlnIndexDev {
+    int64_t n; int32_t n_contig;
+    const int64_t* contig_first; const int64_t* contig_len;
+    const int32_t* pos; const int32_t* end; const int32_t* end_prefmax; const uint16_t* flag; const uint8_t* mapq; const int32_t* name_id;
+};
+// alnindex.hip.  append: the records of a device-resident batch behind the table (svx_collect, while the switch is on); clear: an empty table (a new accumulation);
+// index: the table finalised for n_contig contigs (order check, contig_first, running end maximum: once per append) - SVX_E_STATE without a table or out of order
+int svx_aln_append(svx_ctx* c, const svx_batch* b_dev);
+void svx_aln_clear(svx_ctx* c);
+int svx_aln_table_index(svx_ctx* c, int32_t n_contig, const int64_t* contig_len_host, AlnIndexDev* out);
+// the genotype columns resident for the candidate table of the last svx_combine (genotype.hip; vcf.hip reads them for source 0): false when there are none for it
+bool svx_genotype_columns(svx_ctx* c, int64_t n_cand, const uint8_t** gt, const int32_t** ref_reads, const int32_t** alt_reads);
+// distinct ids per candidate (vcf.hip phase 3; genotype.hip: reads_supporting_variant).  (candidate << 32 | id) of every member sorted into b.k1 (b.v1: the
+// member it came from), b.flag[j] = 1 where a new pair starts, b.ex = the exclusive prefix sums of the flags, n_members + 1 entries.  mode 0: id = read id of
+// the member; 1: zmw id of that read (zbad[candidate] = 1 where a read has none).  A member index outside the signature table sets bit 1 of *err (VERR_INDEX)
+struct MemberIds { long long n_cand, n_members, n_sig, n_reads; const int64_t* member_off; const int32_t* members; const int32_t* sig_read_id; const int32_t* zmw; int* err; };
+struct DistinctBufs { uint64_t *k0, *k1; uint32_t *v0, *v1; int32_t* flag; int64_t* ex; };
+int svx_distinct_member_ids(svx_ctx* c, const MemberIds& m, int mode, const DistinctBufs& b, uint8_t* zbad);
 
 // ---- primitives (prims.hip, scan.hpp: hand-written radix sort and scan) -------------------------------
 int svx_sort_pairs_u64(svx_ctx* c, const uint64_t* keys_in, uint64_t* keys_out, const uint32_t* vals_in, uint32_t* vals_out,
@@ -241,7 +268,7 @@ inline int svx_mail_read3(svx_ctx* c, hipStream_t st, const void* a, int na, voi
     return svx_mail_gather(c, st, 3, srcs, n, dsts);
 }
 
-void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims(); void svx_preload_combine(); void svx_preload_vcf();      // code objects loaded at context creation
+void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims(); void svx_preload_combine(); void svx_preload_vcf(); void svx_preload_alnindex();      // code objects loaded at context creation
 
 // ---- stage entry points ------------------------------------------------------------------------------------
 int svx_collect_impl(svx_ctx* c, const svx_batch* b_dev, const svx_params* p);

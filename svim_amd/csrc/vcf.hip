@@ -346,7 +346,7 @@ __device__ __forceinline__ long long member_row(const int64_t* moff, long long n
     return lo;
 }
 // mode 0: id = read id of the member; mode 1: id = zmw id of that read (-1 = 0xffffffff sorts last)
-__global__ void k_vcf_member_keys(VcfIn in, int mode, uint64_t* key, uint32_t* idx) {
+__global__ void k_vcf_member_keys(MemberIds in, int mode, uint64_t* key, uint32_t* idx) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= in.n_members) return;
     const long long row = member_row(in.member_off, in.n_cand, j);
@@ -526,21 +526,26 @@ void svx_preload_vcf() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, rei
 
 static int ceil_log2(long long n) { int b = 0; while ((1ll << b) < n) b++; return b; }
 
+int svx_distinct_member_ids(svx_ctx* c, const MemberIds& m, int mode, const DistinctBufs& b, uint8_t* zbad) {
+    const long long nm = m.n_members;
+    hipStream_t st = c->stream;
+    if (nm > 0) {
+        k_vcf_member_keys<<<VGRID(nm), VT, 0, st>>>(m, mode, b.k0, b.v0);
+        SVXCHK(svx_sort_pairs_u64(c, b.k0, b.k1, b.v0, b.v1, nm, 0, std::min(64, 32 + std::max(1, ceil_log2(m.n_cand + 1)))));
+    }
+    k_vcf_distinct_flags<<<VGRID(nm + 1), VT, 0, st>>>(nm, b.k1, mode, b.flag, zbad);
+    SVXCHK(svx_exclusive_scan_i32_to_i64(c, b.flag, b.ex, nm + 1));
+    HIPCHK(hipGetLastError());
+    return SVX_OK;
+}
 // prefix sums of the 'first occurrence' flags of (candidate, id) over the member list sorted by that pair -> ex[n_members + 1]
 static int distinct_ids(svx_ctx* c, VcfState* S, const VcfIn& in, int mode, int64_t** ex_out, uint8_t* zbad) {
     const long long nm = in.n_members;
-    uint64_t *k0, *k1; uint32_t *v0, *v1; int32_t* flag; int64_t* ex;
-    SVXCHK(S->get(&k0, nm)); SVXCHK(S->get(&k1, nm)); SVXCHK(S->get(&v0, nm)); SVXCHK(S->get(&v1, nm)); SVXCHK(S->get(&flag, nm + 1)); SVXCHK(S->get(&ex, nm + 1));
-    *ex_out = ex;
-    hipStream_t st = c->stream;
-    if (nm > 0) {
-        k_vcf_member_keys<<<VGRID(nm), VT, 0, st>>>(in, mode, k0, v0);
-        SVXCHK(svx_sort_pairs_u64(c, k0, k1, v0, v1, nm, 0, std::min(64, 32 + std::max(1, ceil_log2(in.n_cand + 1)))));
-    }
-    k_vcf_distinct_flags<<<VGRID(nm + 1), VT, 0, st>>>(nm, k1, mode, flag, zbad);
-    SVXCHK(svx_exclusive_scan_i32_to_i64(c, flag, ex, nm + 1));
-    HIPCHK(hipGetLastError());
-    return SVX_OK;
+    DistinctBufs b;
+    SVXCHK(S->get(&b.k0, nm)); SVXCHK(S->get(&b.k1, nm)); SVXCHK(S->get(&b.v0, nm)); SVXCHK(S->get(&b.v1, nm)); SVXCHK(S->get(&b.flag, nm + 1)); SVXCHK(S->get(&b.ex, nm + 1));
+    *ex_out = b.ex;
+    const MemberIds m{in.n_cand, nm, in.n_sig, in.n_reads, in.member_off, in.members, in.sig_read_id, in.zmw, in.err};
+    return svx_distinct_member_ids(c, m, mode, b, zbad);
 }
 
 extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, const svx_sig_view* sv, const svx_vcf_params* pp, const svx_vcf_inputs* ip) {
@@ -602,8 +607,12 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     const long long n = in.n_cand, nm = in.n_members;
     if (n >= (1ll << 30) || nm >= (1ll << 31)) return svx_fail(SVX_E_ARG, "svx_vcf: table too large", __FILE__, __LINE__, hipSuccess);
     if (P.insertion_sequences && nm > 0 && !in.seq_off) return svx_fail(SVX_E_STATE, "svx_vcf: the resident signature table has no inserted sequences", __FILE__, __LINE__, hipSuccess);
-    // genotype columns
-    {
+    // genotype columns: the caller's, or - source 0, no column handed in, svx_vcf_use_resident_genotypes on - the ones svx_genotype_resident left for this table
+    if (source == 0 && c->vcf_resident_gt && !ip->gt && !ip->ref_reads && !ip->alt_reads) {
+        if (!svx_genotype_columns(c, n, &in.gt, &in.ref_reads, &in.alt_reads))
+            return svx_fail(SVX_E_STATE, "svx_vcf: no resident genotypes for the resident candidates (svx_genotype_resident source 0 after the last svx_combine is required)",
+                            __FILE__, __LINE__, hipSuccess);
+    } else {
         uint8_t* gt; int32_t *rr, *ar;
         SVXCHK(S->get(&gt, (size_t)n)); SVXCHK(S->get(&rr, (size_t)n)); SVXCHK(S->get(&ar, (size_t)n));
         if (n) {
@@ -763,6 +772,12 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     S->stats.bytes_ref_forward = (int64_t)words[0]; S->stats.bytes_ref_revcomp = (int64_t)words[1]; S->stats.bytes_ref_repeat = (int64_t)words[2];
     S->stats.bytes_seqs = (int64_t)words[3]; S->stats.bytes_reads = (int64_t)words[4];
     S->n_lines = n_lines; S->n_bytes = total_bytes; S->have = true;
+    return SVX_OK;
+}
+
+extern "C" int svx_vcf_use_resident_genotypes(svx_ctx* c, int on) {
+    if (!c) return svx_fail(SVX_E_ARG, "null context", __FILE__, __LINE__, hipSuccess);
+    c->vcf_resident_gt = on != 0;
     return SVX_OK;
 }
 

@@ -40,8 +40,12 @@ class BamPipeline(object):
     """reader thread || GPU thread over one BAM file; results stay resident in the engine (accumulated lists)."""
 
     def __init__(self, path, options, engine, threads=0, batch_records=200_000, mode="coordinate", sparse_seq=True, regions=None, gpu_inflate=None,
-                 device_decode=None):
+                 device_decode=None, keep_alignments=False):
         from .bamio import NativeBam
+        if keep_alignments and (regions is not None or mode != "coordinate"):
+            raise ValueError("keep_alignments needs the whole coordinate-sorted file on one rank (contig shards and query-name order genotype through "
+                             "SVIM_genotyping.genotype)")
+        self.keep_alignments = bool(keep_alignments)
         self.bam = NativeBam(path, threads=threads)
         dev = getattr(engine, "device", None)
         if device_decode is None:                                   # default on a GPU engine, either sort order (SVX_BAM_DEVICE_DECODE=0: host reader)
@@ -100,6 +104,8 @@ class BamPipeline(object):
                 box.append((None, 0, None))
                 ready.release()
 
+        if self.keep_alignments:
+            eng.keep_alignments(True)                  # (before accumulate: a fresh accumulation empties the alignment table with the lists)
         eng.accumulate(True)
         th = threading.Thread(target=reader, daemon=True)
         t_start = time.perf_counter()
@@ -151,6 +157,8 @@ class BamPipeline(object):
             free.release()
             free.release()
             th.join()
+            if self.keep_alignments:
+                eng.keep_alignments(False)
         t_collect_done = time.perf_counter()
         self.stats = dict(records=n_rec, batches=n_batches, t_collect_wall=t_collect_done - t_start, t_reader_busy=t_read[0], t_gpu_collect=t_gpu,
                           t_gpu_waits_for_reader=t_wait)
@@ -168,6 +176,41 @@ class BamPipeline(object):
         t0 = time.perf_counter()
         self.eng.cluster(self.params, contig_ranks(self.bam.references), source=0, fetch=False)
         self.stats["t_cluster_wall"] = time.perf_counter() - t0
+
+    # file -> variants.vcf without a Python object: run(), cluster(), combine(), genotype(), write_vcf(path)
+    def combine(self):
+        """COMBINE of the resident clusters; the candidate table stays on the device"""
+        from .batch import contig_ranks
+        t0 = time.perf_counter()
+        self._genotyped = False
+        self.eng.combine(_abi.CombineParams.from_options(self.options), contig_ranks(self.bam.references), fetch=False)
+        self.stats["t_combine_wall"] = time.perf_counter() - t0
+
+    def genotype(self):
+        """GENOTYPE of the resident candidates against the alignment table kept during run() (keep_alignments=True); the columns stay on the device"""
+        if not self.keep_alignments:
+            raise ValueError("BamPipeline.genotype needs keep_alignments=True")
+        t0 = time.perf_counter()
+        self.eng.genotype_resident(self.options, self.bam.lengths)
+        self._genotyped = True
+        self.stats["t_genotype_wall"] = time.perf_counter() - t0
+
+    def write_vcf(self, path, version="svim_amd", types_to_output=None):
+        """header + the lines svx_vcf makes of the resident candidates, with the resident genotype columns when genotype() ran -> bytes written"""
+        from . import SVIM_COMBINE as K
+        o = self.options
+        types = types_to_output if types_to_output is not None else [t.strip() for t in str(getattr(o, "types", "DEL,INS,INV,DUP:TANDEM,DUP:INT,BND")).split(",")]
+        sequence_alleles = not getattr(o, "symbolic_alleles", True)
+        vp = _abi.VcfParams.from_options(o, types, sequence_alleles)
+        names = self.bam.read_names() if (vp.read_names or vp.zmws) else None
+        t0 = time.perf_counter()
+        _, n_bytes = self.eng.vcf(vp, self.bam.references, read_names=names, resident_genotypes=getattr(self, "_genotyped", False))
+        with open(path, "wb") as out:
+            out.write(("\n".join(K.vcf_header(version, self.bam.references, self.bam.lengths, types, o)) + "\n").encode("utf-8"))
+            for at in range(0, n_bytes, K._VCF_PIECE):
+                out.write(self.eng.vcf_fetch(at, min(K._VCF_PIECE, n_bytes - at)))
+        self.stats["t_vcf_wall"] = time.perf_counter() - t0
+        return n_bytes
 
     def rewind(self):
         """back to the first record for another pass: buffers, worker threads and read names are kept - the state a long file is in

@@ -185,6 +185,8 @@ class CandidateList(MutableSequence):
     def materialise(self):
         if self._objs is None:
             self._objs = convert.candidate_objects_range(self.table, self.lo, self.hi, self.signatures, self.references)
+            if getattr(self.table, "genotypes", None) is not None:      # SVIM_genotyping.genotype_resident ran on this table: its columns, as genotype() writes them
+                convert.apply_genotype_columns(self._objs, self.table.genotypes, self.lo)
         return self._objs
 
     def __copy__(self):
