@@ -393,6 +393,59 @@ int  svx_vcf_get_stats(svx_ctx* ctx, svx_vcf_stats* out);
  * else str(round(x, 2))), by the integer arithmetic the kernels use.  SVX_E_ARG: |x| >= 1e10 or infinite. */
 int  svx_vcf_format_std(double x, char out[32]);
 
+/* ---- repr(float): the bare "{}" the BED and signature-VCF lines print score, std_span and std_pos with --------------------------------------------------------
+ * FP64 -> the bytes of CPython's repr(x): the shortest digit string that parses back to x (among the shortest the one closest to x), fixed notation with at
+ * least one digit behind the point while the decimal exponent is in [-4, 16), d[.ddd]e+XX / e-XX otherwise; -0.0, inf, -inf, nan.  Integer arithmetic only
+ * (csrc/fmt_repr.hpp, one source for host and device); right for every double.  out: NUL-padded to 32 bytes (the longest text has 24).
+ * svx_format_repr / _many: host-only (no GPU needed).  _device: the same header compiled for the GPU, one lane per value; host arrays in, host text out. */
+int  svx_format_repr(double x, char out[32]);
+int  svx_format_repr_many(int64_t n, const double* x, char* out /* [32 * n] */);
+int  svx_format_repr_device(svx_ctx* ctx, int64_t n, const double* host_x, char* host_out /* [32 * n] */);
+
+/* ---- BED / signature-VCF text: replaces write_signature_clusters_bed, the body of write_signature_clusters_vcf (src/svim/SVIM_CLUSTER.py:29-106) and
+ * write_candidates (src/svim/SVIM_COMBINE.py:18-58) with the get_bed_entry / get_bed_entries / get_vcf_entry methods of the cluster and candidate classes and
+ * the five as_string forms of their member signatures (csrc/bed.hip) -------------------------------------------------------------------------------------------
+ * One call makes the text of all files of one product in one device buffer, file after file; a file without lines is an empty range. */
+enum { SVX_BED_SIGNATURE_BEDS = 0,   /* 7 files: del, ins, inv, dup_tan_source, dup_tan_dest, trans, dup_int (.bed), the reference's order of opening */
+       SVX_BED_SIGNATURE_VCF  = 1,   /* 1 file: the lines of signatures/all.vcf behind its header */
+       SVX_BED_CANDIDATE_BEDS = 2 }; /* 8 files: candidates_{deletions, inversions, tan_duplications_source, tan_duplications_dest, int_duplications_source,
+                                        int_duplications_dest, novel_insertions, breakends}.bed */
+#define SVX_BED_MAX_FILES 8
+typedef struct svx_bed_inputs {      /* all HOST memory */
+    const char*    contig_names_nul_separated;      /* names of the contig ids of the tables, each followed by a NUL */
+    int32_t        n_contig;
+    const int32_t* contig_str_rank;                 /* [n_contig] rank of each NAME in Python str order: the sort of all.vcf (product 1 only; NULL otherwise) */
+    int64_t        debug_short_line;                /* tests: k > 0 counts line k - 1 one byte short, which the skeleton must refuse (SVX_E_STATE); 0 in use */
+} svx_bed_inputs;
+typedef struct svx_bed_stats {
+    double  t_total_ms;           /* HIP events on the context's stream around the whole call (host steps in between included) */
+    double  t_upload_ms;          /* source 2 tables, contig names */
+    double  t_entries_ms;         /* lines, and for product 1 the keys and the two stable sorts */
+    double  t_lengths_ms;         /* member piece lengths and their prefix, line lengths, the two scans and the mailbox read */
+    double  t_skeleton_ms;        /* the skeleton kernel alone */
+    double  t_payload_ms;         /* the payload kernel alone */
+    int64_t n_rows, n_members, n_lines, n_bytes, n_tiles, n_files;
+    int64_t bytes_members;        /* payload bytes: the member lists */
+    int64_t lines_per_file[SVX_BED_MAX_FILES];
+} svx_bed_stats;
+/* The read names every member piece ends with: uploaded once per context and kept until replaced or the context dies (name of read_id r = bytes
+ * read_name_off[r] .. read_name_off[r + 1] of the blob).  Products 0 and 2 need them (SVX_E_STATE without). */
+int  svx_bed_set_read_names(svx_ctx* ctx, const char* read_names_blob, const int64_t* read_name_off /* [n_reads + 1] */, int64_t n_reads);
+/* source: 0 = the tables resident in the context: products 0 / 1 the clusters of the last svx_cluster, product 2 the candidates of the last svx_combine (which
+ *             must have taken the resident clusters), and the signature table their members index, src column included - SVX_E_STATE if one of them is gone
+ *             (no such call yet, a svx_cluster since the svx_combine, a svx_cluster of a host table without src);
+ *         2 = `clusters` (products 0 / 1; grouped by type, type_count set) or `cand` (product 2; grouped by class, class_count set) plus, in `sigs`, the columns
+ *             of the signatures their members index: n, type, src, aux, contig, start, end, contig2, pos2, read_id.  Host memory.
+ * Candidate deviations are printed as svx_vcf prints them (NaN or below 1e10, else SVX_E_ARG), cluster deviations as repr (NaN = None).  SVX_E_ARG also for
+ * a contig, member or read id outside its table; SVX_E_CAPACITY: the text does not fit into device memory. */
+int  svx_bed(svx_ctx* ctx, int product, int source, const svx_cluster_view* clusters, const svx_candidate_view* cand, const svx_sig_view* sigs,
+             const svx_bed_inputs* in);
+int  svx_bed_count(svx_ctx* ctx, int32_t* n_files, int64_t* n_lines, int64_t* n_bytes);
+/* bytes [byte_offset, byte_offset + bytes) of the text into host_dst (NULL or bytes 0: none); file_off [n_files + 1]: byte offsets of the files; file_line_off
+ * [n_files + 1]: first line of every file; line_off [n_lines + 1]: byte offsets of the lines (each NULL: not fetched) */
+int  svx_bed_fetch(svx_ctx* ctx, int64_t byte_offset, int64_t bytes, uint8_t* host_dst, int64_t* file_off, int64_t* file_line_off, int64_t* line_off);
+int  svx_bed_get_stats(svx_ctx* ctx, svx_bed_stats* out);
+
 /* ---- GENOTYPE: replaces the per-candidate BAM re-fetch of genotype() (src/svim/SVIM_genotyping.py:34-93) --------
  * by an interval join over the alignment records, resident in HBM.  Records are in file order of a coordinate-sorted BAM
  * (tid, pos non-decreasing); AlignmentFile.fetch(contig, start, stop) of the reference (:48) becomes "records of that contig with

@@ -30,28 +30,71 @@ def _signature_dir(working_dir):
     return d
 
 
-def write_signature_clusters_bed(working_dir, clusters):
-    """<working_dir>/signatures/{del,ins,inv,dup_tan_source,dup_tan_dest,trans,dup_int}.bed (src/svim/SVIM_CLUSTER.py:29-70)."""
+def signature_bed_texts_python(clusters):
+    """The text of the seven BED files (in _BED_FILES order) from cluster OBJECTS, as the reference's writer makes it (src/svim/SVIM_CLUSTER.py:44-61): the
+    definition the device writer (svx_bed, csrc/bed.hip) is held against."""
+    texts = []
+    for name, slot, which in _BED_FILES:
+        lines = []
+        for cluster in clusters[slot]:
+            if which is None:
+                lines.append(cluster.get_bed_entry() + "\n")
+            else:
+                entries = cluster.get_bed_entries()
+                lines.extend(entries[k] + "\n" for k in which)
+        texts.append("".join(lines))
+    return texts
+
+
+def signature_vcf_body_python(clusters):
+    """The lines of signatures/all.vcf behind the header from cluster OBJECTS: the DEL / INS / INV / DUP_TAN clusters in that append order, sorted stably by
+    their source tuple - contig NAME as a string, start, end (src/svim/SVIM_CLUSTER.py:93-105)."""
+    entries = [(c.get_source(), c.get_vcf_entry()) for slot in (0, 1, 2, 3) for c in clusters[slot]]
+    return "".join("%s\n" % entry for _, entry in sorted(entries, key=lambda pair: pair[0]))
+
+
+def vcf_header_text(version):
+    return "".join(line.format(version=version) + "\n" for line in _VCF_HEADER)
+
+
+def write_signature_clusters_bed_python(working_dir, clusters):
+    """write_signature_clusters_bed over the objects (every cluster and every member signature is materialised)"""
     import os
     d = _signature_dir(working_dir)
-    for name, slot, which in _BED_FILES:
+    for (name, _, _), text in zip(_BED_FILES, signature_bed_texts_python(clusters)):
         with open(os.path.join(d, name), "w") as fh:
-            for cluster in clusters[slot]:
-                if which is None:
-                    fh.write(cluster.get_bed_entry() + "\n")
-                else:
-                    entries = cluster.get_bed_entries()
-                    for k in which:
-                        fh.write(entries[k] + "\n")
+            fh.write(text)
 
 
-def write_signature_clusters_vcf(working_dir, clusters, version):
-    """<working_dir>/signatures/all.vcf: header, then the DEL / INS / INV / DUP_TAN clusters sorted by source locus
-    (src/svim/SVIM_CLUSTER.py:73-106)."""
+def write_signature_clusters_vcf_python(working_dir, clusters, version):
+    """write_signature_clusters_vcf over the objects"""
     import os
-    entries = [(c.get_source(), c.get_vcf_entry()) for slot in (0, 1, 2, 3) for c in clusters[slot]]
     with open(os.path.join(_signature_dir(working_dir), "all.vcf"), "w") as fh:
-        for line in _VCF_HEADER:
-            fh.write(line.format(version=version) + "\n")
-        for _, entry in sorted(entries, key=lambda pair: pair[0]):
-            fh.write("%s\n" % entry)
+        fh.write(vcf_header_text(version))
+        fh.write(signature_vcf_body_python(clusters))
+
+
+def write_signature_clusters_bed(working_dir, clusters, engine=None):
+    """<working_dir>/signatures/{del,ins,inv,dup_tan_source,dup_tan_dest,trans,dup_int}.bed (src/svim/SVIM_CLUSTER.py:29-70).  The lines are made on the
+    device (svx_bed) where the clusters are, or fit, a cluster table (svim_amd.bed.signature_text says which route a call takes); the Python definition
+    (write_signature_clusters_bed_python) otherwise."""
+    from . import bed
+    done = bed.signature_text(_abi_product("SIGNATURE_BEDS"), clusters, engine=engine)
+    if done is None:
+        return write_signature_clusters_bed_python(working_dir, clusters)
+    bed.write_files(done[0], _signature_dir(working_dir), [name for name, _, _ in _BED_FILES])
+
+
+def write_signature_clusters_vcf(working_dir, clusters, version, engine=None):
+    """<working_dir>/signatures/all.vcf: header, then the DEL / INS / INV / DUP_TAN clusters sorted by source locus (src/svim/SVIM_CLUSTER.py:73-106).
+    The header is written here, the lines behind it on the device where the route allows (see write_signature_clusters_bed)."""
+    from . import bed
+    done = bed.signature_text(_abi_product("SIGNATURE_VCF"), clusters, engine=engine)
+    if done is None:
+        return write_signature_clusters_vcf_python(working_dir, clusters, version)
+    bed.write_files(done[0], _signature_dir(working_dir), ["all.vcf"], heads=[vcf_header_text(version).encode("utf-8")])
+
+
+def _abi_product(name):
+    from . import _abi
+    return getattr(_abi, "BED_" + name)

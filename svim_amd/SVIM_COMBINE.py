@@ -423,3 +423,53 @@ def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_dup
         eng, _, n_bytes = done
         for at in range(0, n_bytes, _VCF_PIECE):
             out.write(eng.vcf_fetch(at, min(_VCF_PIECE, n_bytes - at)))
+
+
+# ---- candidates/*.bed (src/svim/SVIM_COMBINE.py:18-58) -----------------------------------------------------------------------------------------------------
+# (file name, slot of write_candidates' 6-tuple, which bed line(s) of a candidate go into it), in the reference's order of opening
+_CANDIDATE_BED_FILES = (("candidates_deletions.bed", 3, None), ("candidates_inversions.bed", 1, None),
+                        ("candidates_tan_duplications_source.bed", 2, (0,)), ("candidates_tan_duplications_dest.bed", 2, (1,)),
+                        ("candidates_int_duplications_source.bed", 0, (0,)), ("candidates_int_duplications_dest.bed", 0, (1,)),
+                        ("candidates_novel_insertions.bed", 4, None), ("candidates_breakends.bed", 5, (0, 1)))
+
+
+def candidate_bed_texts_python(candidates):
+    """The text of the eight BED files (in _CANDIDATE_BED_FILES order) from candidate OBJECTS (interspersed duplication, inversion, tandem duplication,
+    deletion, novel insertion, breakend candidates: write_candidates' tuple), as the reference's writer makes it: the definition the device writer is held
+    against."""
+    texts = []
+    for name, slot, which in _CANDIDATE_BED_FILES:
+        lines = []
+        for c in candidates[slot]:
+            if which is None:
+                lines.append(c.get_bed_entry() + "\n")
+            else:
+                entries = c.get_bed_entries()
+                lines.extend(entries[k] + "\n" for k in which)
+        texts.append("".join(lines))
+    return texts
+
+
+def _candidate_dir(working_dir):
+    d = os.path.join(working_dir, "candidates")
+    os.makedirs(d, exist_ok=True)
+    return d
+
+
+def write_candidates_python(working_dir, candidates):
+    """write_candidates over the objects (every candidate and every member signature is materialised)"""
+    d = _candidate_dir(working_dir)
+    for (name, _, _), text in zip(_CANDIDATE_BED_FILES, candidate_bed_texts_python(candidates)):
+        with open(os.path.join(d, name), "w") as fh:
+            fh.write(text)
+
+
+def write_candidates(working_dir, candidates, engine=None):
+    """<working_dir>/candidates/candidates_*.bed (src/svim/SVIM_COMBINE.py:18-58; `candidates` in the reference's order: interspersed duplication, inversion,
+    tandem duplication, deletion, novel insertion, breakend candidates).  The lines are made on the device (svx_bed) where the six lists are, or fit, a
+    candidate table (svim_amd.bed.candidate_text says which route a call takes); the Python definition (write_candidates_python) otherwise."""
+    from . import bed
+    done = bed.candidate_text(tuple(candidates), engine=engine)
+    if done is None:
+        return write_candidates_python(working_dir, candidates)
+    bed.write_files(done[0], _candidate_dir(working_dir), [name for name, _, _ in _CANDIDATE_BED_FILES])

@@ -181,6 +181,26 @@ class VcfStats(C.Structure):
         return d
 
 
+# products of svx_bed (include/svx.h: SVX_BED_*) and the files of each, in the order the text holds them
+BED_SIGNATURE_BEDS, BED_SIGNATURE_VCF, BED_CANDIDATE_BEDS = 0, 1, 2
+BED_MAX_FILES = 8
+
+
+class BedInputs(C.Structure):
+    _fields_ = [("contig_names_nul_separated", _P), ("n_contig", C.c_int32), ("contig_str_rank", _P), ("debug_short_line", C.c_int64)]
+
+
+class BedStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_total_ms", "t_upload_ms", "t_entries_ms", "t_lengths_ms", "t_skeleton_ms", "t_payload_ms")] + \
+               [(n, C.c_int64) for n in ("n_rows", "n_members", "n_lines", "n_bytes", "n_tiles", "n_files", "bytes_members")] + \
+               [("lines_per_file", C.c_int64 * BED_MAX_FILES)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "lines_per_file"}
+        d["lines_per_file"] = list(self.lines_per_file)[:self.n_files]
+        return d
+
+
 class GenotypeParams(C.Structure):
     _fields_ = [("minimum_score", C.c_double), ("min_mapq", C.c_int32), ("minimum_depth", C.c_int32), ("homozygous_threshold", C.c_double),
                 ("heterozygous_threshold", C.c_double)]

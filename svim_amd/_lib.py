@@ -29,7 +29,9 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_inflater_run",
            "svx_genome_load_fasta", "svx_genome_fetch", "svx_fasta_probe", "svx_fasta_plan",
            "svx_combine", "svx_combine_count", "svx_combine_fetch", "svx_combine_stages_fetch", "svx_combine_get_stats", "svx_py_sample100",
-           "svx_vcf", "svx_vcf_count", "svx_vcf_fetch", "svx_vcf_get_stats", "svx_vcf_format_std"]
+           "svx_vcf", "svx_vcf_count", "svx_vcf_fetch", "svx_vcf_get_stats", "svx_vcf_format_std",
+           "svx_format_repr", "svx_format_repr_many", "svx_format_repr_device",
+           "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats"]
 
 
 class SvxError(RuntimeError):
@@ -100,6 +102,21 @@ def vcf_format_std(x):
     out = C.create_string_buffer(32)
     _check(lib().svx_vcf_format_std(C.c_double(float(x)), out), "svx_vcf_format_std")
     return out.value.decode("ascii")
+
+
+def format_repr(x):
+    """svx_format_repr (host-only): repr(float(x)) by the integer arithmetic of csrc/fmt_repr.hpp"""
+    out = C.create_string_buffer(32)
+    _check(lib().svx_format_repr(C.c_double(float(x)), out), "svx_format_repr")
+    return out.value.decode("ascii")
+
+
+def format_repr_many(values):
+    """svx_format_repr_many (host-only): float64 array -> list of str, one call for the whole array"""
+    x = np.ascontiguousarray(values, dtype=np.float64)
+    out = np.zeros((max(1, x.size), 32), dtype=np.uint8)
+    _check(lib().svx_format_repr_many(C.c_int64(x.size), ptr(x if x.size else np.zeros(1)), ptr(out)), "svx_format_repr_many")
+    return [b.decode("ascii") for b in out[:x.size].view("S32").ravel().tolist()]
 
 
 def build(force=False):
@@ -401,6 +418,92 @@ class Engine(object):
     def vcf_stats(self):
         s = _abi.VcfStats()
         _check(self.L.svx_vcf_get_stats(self.ctx, C.byref(s)), "svx_vcf_get_stats")
+        return s.as_dict()
+
+    # ---- BED / signature-VCF text ----
+    def format_repr(self, values):
+        """svx_format_repr_device: repr of every float64 of `values` by the device build of csrc/fmt_repr.hpp -> list of str"""
+        x = np.ascontiguousarray(values, dtype=np.float64)
+        out = np.zeros((max(1, x.size), 32), dtype=np.uint8)
+        _check(self.L.svx_format_repr_device(self.ctx, C.c_int64(x.size), ptr(x if x.size else np.zeros(1)), ptr(out)), "svx_format_repr_device")
+        return [b.decode("ascii") for b in out[:x.size].view("S32").ravel().tolist()]
+
+    def bed_set_read_names(self, read_names):
+        """svx_bed_set_read_names: the names by read id every member piece ends with, uploaded once and kept in the context until replaced.  The list handed in
+        last is remembered by identity: handing the same list again uploads nothing."""
+        if read_names is getattr(self, "_bed_names", None):
+            return
+        enc = [n.encode("utf-8") if isinstance(n, str) else bytes(n) for n in read_names]
+        off = np.zeros(len(enc) + 1, dtype=np.int64)
+        if enc:
+            np.cumsum(np.fromiter((len(e) for e in enc), dtype=np.int64, count=len(enc)), out=off[1:])
+        data = b"".join(enc) or b"\0"
+        rbuf = C.create_string_buffer(data, len(data))
+        self._bed_names = None
+        _check(self.L.svx_bed_set_read_names(self.ctx, C.cast(rbuf, C.c_void_p), ptr(off), C.c_int64(len(enc))), "svx_bed_set_read_names")
+        self._bed_names = read_names
+
+    def bed(self, product, references, table=None, sigs=None, read_names=None, debug_short_line=0):
+        """svx_bed: the text of one product (_abi.BED_SIGNATURE_BEDS: 7 files, BED_SIGNATURE_VCF: the lines of all.vcf behind the header, BED_CANDIDATE_BEDS:
+        8 files) from the tables resident in the context (table None, source 0: the clusters of the last cluster(), the candidates of the last combine()) or
+        from `table` (a ClusterTable, for BED_CANDIDATE_BEDS a CandidateTable) whose members index the SigTable `sigs` (source 2).  references: names of the
+        tables' contig ids; read_names: names by read id (uploaded only when it is another list than last time).  The text stays on the device:
+        -> (number of files, lines, bytes); bed_fetch() / bed_file_offsets() / bed_line_offsets() bring it over."""
+        from . import batch
+        references = list(references)
+        if read_names is not None:
+            self.bed_set_read_names(read_names)
+        blob = b"".join(os.fsencode(r) + b"\0" for r in references) or b"\0"
+        cbuf = C.create_string_buffer(blob, len(blob))
+        rank = np.ascontiguousarray(batch.contig_ranks(references), dtype=np.int32)
+        inp = _abi.BedInputs()
+        inp.contig_names_nul_separated, inp.n_contig = C.cast(cbuf, C.c_void_p), len(references)
+        inp.contig_str_rank = ptr(rank if rank.size else np.zeros(1, np.int32))
+        inp.debug_short_line = int(debug_short_line)
+        if table is None:
+            rc = self.L.svx_bed(self.ctx, C.c_int(product), 0, None, None, None, C.byref(inp))
+        else:
+            v = table.view()
+            counts = table.class_count if product == _abi.BED_CANDIDATE_BEDS else table.type_count
+            for k in range(6):
+                (v.class_count if product == _abi.BED_CANDIDATE_BEDS else v.type_count)[k] = int(counts[k])
+            sv = sigs.view() if sigs is not None else None
+            cl, cv = (None, C.byref(v)) if product == _abi.BED_CANDIDATE_BEDS else (C.byref(v), None)
+            rc = self.L.svx_bed(self.ctx, C.c_int(product), 2, cl, cv, C.byref(sv) if sv is not None else None, C.byref(inp))
+        _check(rc, "svx_bed")
+        del cbuf
+        return self.bed_count()
+
+    def bed_count(self):
+        nf, n, nb = C.c_int32(), C.c_int64(), C.c_int64()
+        _check(self.L.svx_bed_count(self.ctx, C.byref(nf), C.byref(n), C.byref(nb)), "svx_bed_count")
+        return nf.value, n.value, nb.value
+
+    def bed_fetch(self, offset=0, nbytes=None):
+        """bytes [offset, offset + nbytes) of the text of the last bed() call (svx_bed_fetch; nbytes None: to the end) -> bytes"""
+        _, _, total = self.bed_count()
+        nbytes = total - offset if nbytes is None else nbytes
+        buf = np.zeros(max(1, nbytes), dtype=np.uint8)
+        _check(self.L.svx_bed_fetch(self.ctx, C.c_int64(offset), C.c_int64(nbytes), ptr(buf), None, None, None), "svx_bed_fetch")
+        return buf[:nbytes].tobytes()
+
+    def bed_file_offsets(self):
+        """(int64[n_files + 1] byte offsets of the files in the text of the last bed() call, int64[n_files + 1] first line of every file)"""
+        nf, _, _ = self.bed_count()
+        off, lines = np.zeros(_abi.BED_MAX_FILES + 1, dtype=np.int64), np.zeros(_abi.BED_MAX_FILES + 1, dtype=np.int64)
+        _check(self.L.svx_bed_fetch(self.ctx, C.c_int64(0), C.c_int64(0), None, ptr(off), ptr(lines), None), "svx_bed_fetch")
+        return off[:nf + 1], lines[:nf + 1]
+
+    def bed_line_offsets(self):
+        """int64[n_lines + 1]: where every line of the last bed() call starts in its text"""
+        _, n, _ = self.bed_count()
+        off = np.zeros(n + 1, dtype=np.int64)
+        _check(self.L.svx_bed_fetch(self.ctx, C.c_int64(0), C.c_int64(0), None, None, None, ptr(off)), "svx_bed_fetch")
+        return off
+
+    def bed_stats(self):
+        s = _abi.BedStats()
+        _check(self.L.svx_bed_get_stats(self.ctx, C.byref(s)), "svx_bed_get_stats")
         return s.as_dict()
 
     def set_alignment_index(self, index):

@@ -3,7 +3,8 @@
 Same constructor argument order, attributes, `get_source` / `get_destination` / `get_key` / `downstream_distance_to` and the genotype fields with the
 reference's defaults (`support_fraction "."`, `genotype "./."`, `ref_reads` / `alt_reads None`), table-driven like signatures.py: one row of _SPEC per
 class instead of one hand-written constructor each.  The nine `get_vcf_entry*` methods are one row of _VCF each over one formatter (`vcf_entry`): the readable
-definition of a VCF line that the device writer (csrc/vcf.hip) is held against.  The BED text of candidates is not part of this surface.
+definition of a VCF line that the device writer (csrc/vcf.hip) is held against.  `get_bed_entry` / `get_bed_entries` are rows of _BED over `bed_entry` in the same
+way: the definition of a line of the candidate BED files (csrc/bed.hip).
 `members` may be handed over as (signature sequence, index array) and resolves to signature objects on first read, as for clusters.
 """
 from .signatures import _LazyMembers
@@ -247,3 +248,56 @@ def _vcf_method(row, name):
 CLASSES = (CandidateDeletion, CandidateInversion, CandidateDuplicationInterspersed, CandidateDuplicationTandem, CandidateNovelInsertion, CandidateBreakend)
 for (_type, _name), _row in _VCF.items():
     setattr({c.type: c for c in CLASSES}[_type], _name, _vcf_method(_row, _name))
+
+
+# ---- BED text (src/svim/SVCandidate.py: get_bed_entry :52, :219; get_bed_entries :302, :455, :618) -------------------------------------------------------------
+class _BedRow(object):
+    """One BED line of a candidate: locus(c) -> (contig, start, end); name(c) -> the 4th column; extra(c) -> the column between the score and the members
+    ("." or the cut&paste note), None: the line has none (breakends).  The score and the deviations go through str.format as they are: the score is printed
+    with repr's digits, the deviations as get_std_*() rounds them ("." for None and 0.0)."""
+
+    def __init__(self, locus, name, extra=lambda c: "."):
+        self.locus, self.name, self.extra = locus, name, extra
+
+
+_src = lambda c: (c.source_contig, c.source_start, c.source_end)      # noqa: E731
+_dst = lambda c: c.get_destination()                                  # noqa: E731
+_std = lambda c: "%s;%s" % (c.get_std_span(), c.get_std_pos())        # noqa: E731
+_std12 = lambda c: "%s;%s" % (c.get_std_pos1(), c.get_std_pos2())     # noqa: E731
+_note = lambda c: "origin potentially deleted" if c.cutpaste else "."      # noqa: E731
+_plain = lambda c: "%s;%s" % (c.type, _std(c))                        # noqa: E731
+# type -> (method name, rows): one row -> get_bed_entry, two -> get_bed_entries (source entry, destination entry)
+_BED = {
+    "DEL": ("get_bed_entry", (_BedRow(_src, _plain),)),
+    "INV": ("get_bed_entry", (_BedRow(_src, _plain),)),
+    "INS": ("get_bed_entry", (_BedRow(_dst, _plain),)),
+    "DUP_TAN": ("get_bed_entries", (_BedRow(_src, lambda c: "tan_dup_source;>%s:%s-%s;%s" % (_dst(c) + (_std(c),))),
+                                    _BedRow(_dst, lambda c: "tan_dup_dest;<%s:%s-%s;%s" % (_src(c) + (_std(c),))))),
+    "DUP_INT": ("get_bed_entries", (_BedRow(_src, lambda c: "int_dup_source;>%s:%s-%s;%s" % (_dst(c) + (_std(c),)), _note),
+                                    _BedRow(_dst, lambda c: "int_dup_dest;<%s:%s-%s;%s" % (_src(c) + (_std(c),)), _note))),
+    "BND": ("get_bed_entries", (_BedRow(lambda c: (c.source_contig, c.source_start, c.source_start + 1),
+                                        lambda c: "bnd;>%s:%s;%s" % (c.dest_contig, c.dest_start, _std12(c)), lambda c: None),
+                                _BedRow(lambda c: (c.dest_contig, c.dest_start, c.dest_start + 1),
+                                        lambda c: "bnd;<%s:%s;%s" % (c.source_contig, c.source_start, _std12(c)), lambda c: None))),
+}
+
+
+def bed_entry(c, row, sep="\t"):
+    """The BED line of candidate `c` under row `row` of _BED, without the newline."""
+    extra = row.extra(c)
+    members = "[" + "][".join(m.as_string("|") for m in c.members) + "]"
+    cols = row.locus(c) + (row.name(c), c.score) + (() if extra is None else (extra,)) + (members,)
+    return sep.join("{0}".format(x) for x in cols)
+
+
+def _bed_methods():
+    for cls in CLASSES:
+        name, rows = _BED[cls.type]
+        if len(rows) == 1:
+            setattr(cls, name, lambda self, _r=rows[0]: bed_entry(self, _r))
+        else:
+            setattr(cls, name, lambda self, sep="\t", _r=rows: (bed_entry(self, _r[0], sep), bed_entry(self, _r[1], sep)))
+        getattr(cls, name).__name__ = name
+
+
+_bed_methods()

@@ -99,7 +99,7 @@ extern "C" int svx_ctx_create(int device_ordinal, svx_ctx** out) {
         c->mail_mode = e && e[0] == '0' ? 0 : 1;
     }
     memset(&c->stats, 0, sizeof c->stats);
-    svx_preload_collect(); svx_preload_cluster(); svx_preload_edit(); svx_preload_prims(); svx_preload_combine(); svx_preload_vcf(); svx_preload_alnindex();       // code objects now, not inside the first call
+    svx_preload_collect(); svx_preload_cluster(); svx_preload_edit(); svx_preload_prims(); svx_preload_combine(); svx_preload_vcf(); svx_preload_alnindex(); svx_preload_bed();       // code objects now, not inside the first call
     { const char* e = getenv("SVX_EDIT_FORCE_FULL"); c->edit_force_full = e && e[0] == '1'; }
     { const char* e = getenv("SVX_EDIT_GUESS"); if (e && atof(e) > 0) { c->edit_guess = (float)atof(e); c->edit_guess_pinned = true; } }
     *out = c;
@@ -123,6 +123,8 @@ extern "C" void svx_ctx_destroy(svx_ctx* c) {
     for (auto& b : c->geno) b.release();
     svx_combine_release(c);
     svx_vcf_release(c);
+    svx_bed_release(c);
+    c->repr_tab.release();
     svx_aln_release(c);
     svx_genotype_release(c);
     for (auto& ev : c->ev) (void)hipEventDestroy(ev);
@@ -386,14 +388,14 @@ extern "C" int svx_cluster(svx_ctx* c, int source, const svx_sig_view* sigs, int
         DevSigs& s = c->accumulate ? (source ? c->acc_bnd : c->acc_sig) : (source ? c->bnd : c->sig);
         in.n = s.n; in.type = s.type.as<uint8_t>(); in.aux = s.aux.as<uint8_t>(); in.contig = s.contig.as<int32_t>(); in.start = s.start.as<int32_t>();
         in.end = s.end.as<int32_t>(); in.contig2 = s.contig2.as<int32_t>(); in.pos2 = s.pos2.as<int32_t>(); in.read_id = s.read_id.as<int32_t>();
-        in.seq_off = s.seq_off.as<int64_t>(); in.seq = s.seq.as<uint8_t>();
+        in.seq_off = s.seq_off.as<int64_t>(); in.seq = s.seq.as<uint8_t>(); in.src = s.src.as<uint8_t>();
         if (s.n > 0 && !s.seq_off.p) return svx_fail(SVX_E_STATE, "no resident signatures: run svx_collect first", __FILE__, __LINE__, hipSuccess);
     } else if (source == 2) {
         if (!sigs) return svx_fail(SVX_E_ARG, "source 2 needs a signature table", __FILE__, __LINE__, hipSuccess);
         in.n = sigs->n;
         if (sigs->on_device) {
             in.type = sigs->type; in.aux = sigs->aux; in.contig = sigs->contig; in.start = sigs->start; in.end = sigs->end; in.contig2 = sigs->contig2;
-            in.pos2 = sigs->pos2; in.read_id = sigs->read_id; in.seq_off = sigs->seq_off; in.seq = sigs->seq;
+            in.pos2 = sigs->pos2; in.read_id = sigs->read_id; in.seq_off = sigs->seq_off; in.seq = sigs->seq; in.src = sigs->src;
         } else {
             const size_t n = (size_t)sigs->n;
             const size_t nseq = n ? (size_t)sigs->seq_off[n] : 0;

@@ -1202,6 +1202,7 @@ static int svx_cluster_body(svx_ctx* c, const ClusterIn& in, int32_t n_contig, c
     c->last_cluster_source_n = n;
     c->last_cluster_aux = in.aux; c->cluster_calls++;
     c->last_cluster_read_id = in.read_id; c->last_cluster_seq_off = in.seq_off; c->last_cluster_seq = in.seq;
+    c->last_cluster_in = in;
     DevClusters& out = c->clu;
     out.n = 0; out.n_members = 0;
     for (int t = 0; t < SVX_NTYPES; t++) out.type_count[t] = 0;

@@ -119,6 +119,7 @@ struct ClusterIn {
     const uint8_t* type; const uint8_t* aux;
     const int32_t *contig, *start, *end, *contig2, *pos2, *read_id;
     const int64_t* seq_off; const uint8_t* seq;
+    const uint8_t* src = nullptr;      // SVX_SRC_* column where the caller has one on the device (only the text of bed.hip reads it)
 };
 
 struct DevClusters {
@@ -196,7 +197,14 @@ struct svx_ctx {
     // and the stage's own buffers and results
     const int32_t* last_cluster_read_id = nullptr; const int64_t* last_cluster_seq_off = nullptr; const uint8_t* last_cluster_seq = nullptr;
     struct VcfState* vcf = nullptr;
+    // BED / signature-VCF text (bed.hip): every column of that signature table (a member's text depends on its own type), the read names uploaded once per
+    // context, the stage's own buffers and results; the multiplier tables of repr(float) (fmtrepr.hip), uploaded once
+    ClusterIn last_cluster_in{}; struct BedState* bed = nullptr;
+    DevBuf repr_tab; bool repr_tab_ready = false;
 };
+void svx_bed_release(svx_ctx* c);
+const uint64_t* svx_repr_host_tables();
+int svx_repr_device_tables(svx_ctx* c, const uint64_t** out);
 void svx_combine_release(svx_ctx* c);
 void svx_vcf_release(svx_ctx* c);
 void svx_aln_release(svx_ctx* c);
@@ -268,7 +276,7 @@ inline int svx_mail_read3(svx_ctx* c, hipStream_t st, const void* a, int na, voi
     return svx_mail_gather(c, st, 3, srcs, n, dsts);
 }
 
-void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims(); void svx_preload_combine(); void svx_preload_vcf(); void svx_preload_alnindex();      // code objects loaded at context creation
+void svx_preload_collect(); void svx_preload_cluster(); void svx_preload_edit(); void svx_preload_prims(); void svx_preload_combine(); void svx_preload_vcf(); void svx_preload_alnindex(); void svx_preload_bed();      // code objects loaded at context creation
 
 // ---- stage entry points ------------------------------------------------------------------------------------
 int svx_collect_impl(svx_ctx* c, const svx_batch* b_dev, const svx_params* p);

@@ -70,8 +70,9 @@ class BamPipeline(object):
 
     def run(self):
         bam, eng, p = self.bam, self.eng, self.params
+        self._bed_read_names = None                   # (write_signature_files / write_candidate_files: the names of THIS pass)
         min_mapq = int(getattr(self.options, "min_mapq", 20))
-        free = threading.Semaphore(2)                 # the reader owns two array sets: at most one batch ahead of the GPU thread
+        free = threading.Semaphore(2)                # the reader owns two array sets: at most one batch ahead of the GPU thread
         ready, box, err = threading.Semaphore(0), [], []
         t_read = [0.0]
         stop = threading.Event()                      # set when the GPU thread gives up: the reader must leave libsvx before the handle is closed
@@ -211,6 +212,31 @@ class BamPipeline(object):
                 out.write(self.eng.vcf_fetch(at, min(K._VCF_PIECE, n_bytes - at)))
         self.stats["t_vcf_wall"] = time.perf_counter() - t0
         return n_bytes
+
+    # file -> the sixteen BED / signature-VCF files of the working directory without a Python object: run(), cluster(), write_signature_files(dir, version),
+    # combine(), write_candidate_files(dir)
+    def _bed_files(self, product, directory, names, heads=None):
+        from . import bed
+        if getattr(self, "_bed_read_names", None) is None:
+            self._bed_read_names = self.bam.read_names()             # uploaded once: the engine knows the list by identity
+        os.makedirs(directory, exist_ok=True)
+        t0 = time.perf_counter()
+        _, _, n_bytes = self.eng.bed(product, self.bam.references, read_names=self._bed_read_names)
+        bed.write_files(self.eng, directory, names, heads=heads)
+        self.stats["t_bed_wall"] = self.stats.get("t_bed_wall", 0.0) + time.perf_counter() - t0
+        return n_bytes
+
+    def write_signature_files(self, working_dir, version="svim_amd"):
+        """<working_dir>/signatures/*.bed and all.vcf of the resident clusters (after cluster()), made by svx_bed -> bytes written behind the header"""
+        from . import SVIM_CLUSTER as K
+        d = os.path.join(working_dir, "signatures")
+        n = self._bed_files(_abi.BED_SIGNATURE_BEDS, d, [name for name, _, _ in K._BED_FILES])
+        return n + self._bed_files(_abi.BED_SIGNATURE_VCF, d, ["all.vcf"], heads=[K.vcf_header_text(version).encode("utf-8")])
+
+    def write_candidate_files(self, working_dir):
+        """<working_dir>/candidates/candidates_*.bed of the resident candidates (after combine()), made by svx_bed -> bytes written"""
+        from . import SVIM_COMBINE as K
+        return self._bed_files(_abi.BED_CANDIDATE_BEDS, os.path.join(working_dir, "candidates"), [name for name, _, _ in K._CANDIDATE_BED_FILES])
 
     def rewind(self):
         """back to the first record for another pass: buffers, worker threads and read names are kept - the state a long file is in
