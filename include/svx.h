@@ -446,6 +446,35 @@ int  svx_bed_count(svx_ctx* ctx, int32_t* n_files, int64_t* n_lines, int64_t* n_
 int  svx_bed_fetch(svx_ctx* ctx, int64_t byte_offset, int64_t bytes, uint8_t* host_dst, int64_t* file_off, int64_t* file_line_off, int64_t* line_off);
 int  svx_bed_get_stats(svx_ctx* ctx, svx_bed_stats* out);
 
+/* ---- BGZF output: a text resident in the context -> a BGZF stream resident in the context (csrc/deflate_core.hpp, csrc/textgz.hip) ---------------------------
+ * The reference writes plain text and leaves compression to bgzip; here the text is compressed where it lies and only the stream crosses to the host.
+ * Every file of the text becomes BGZF blocks of 65 280 text bytes (the last one shorter) followed by the 28-byte end-of-file block; a file without bytes is that
+ * block alone.  Block kinds: dynamic Huffman, or stored where coding would not make the block smaller.  The bytes are a pure function of the text: the host
+ * build of the same header (svx_text_gz_host) writes the same stream.
+ * source: 0 = the text of the last svx_vcf (one file); 1 = the text of the last svx_bed (its n_files files);
+ *         2 = host bytes, uploaded: n_files files, file k = host_text[host_file_off[k] .. host_file_off[k + 1]) (host_file_off[0] = 0).
+ * SVX_E_STATE: no such text.  SVX_E_CAPACITY: the working buffers do not fit into device memory.
+ * The stream is void after a later svx_vcf (source 0) / svx_bed (source 1): SVX_E_STATE from count and fetch. */
+typedef struct svx_text_gz_stats {
+    double  t_total_ms;           /* HIP events on the context's stream around the whole call */
+    double  t_upload_ms;          /* source 2 text, the block table */
+    double  t_crc_ms;             /* CRC32 of every block's text */
+    double  t_matches_ms;         /* LZ77 matches and the parse: tokens and histograms */
+    double  t_codes_ms;           /* Huffman codes, block headers, sizes */
+    double  t_bits_ms;            /* the blocks written into their slots */
+    double  t_compaction_ms;      /* scan of the sizes, the dense stream, the block table's way to the host */
+    int64_t n_files, n_blocks, blocks_eof, blocks_stored, blocks_dynamic, bytes_in, bytes_out;
+} svx_text_gz_stats;
+int  svx_text_gz(svx_ctx* ctx, int source, const uint8_t* host_text, const int64_t* host_file_off, int32_t n_files);
+int  svx_text_gz_count(svx_ctx* ctx, int32_t* n_files, int64_t* n_blocks /* end-of-file blocks included */, int64_t* n_bytes);
+/* bytes [byte_offset, byte_offset + bytes) of the stream into host_dst (NULL or bytes 0: none); file_off [n_files + 1]: offsets of the files in the stream;
+ * block_coff [n_blocks + 1]: offsets of the blocks in the stream; block_uoff [n_blocks + 1]: offsets of their text in the text (an end-of-file block holds
+ * none) - what a .gzi or tabix index would be built from (each NULL: not fetched) */
+int  svx_text_gz_fetch(svx_ctx* ctx, int64_t byte_offset, int64_t bytes, uint8_t* host_dst, int64_t* file_off, int64_t* block_coff, int64_t* block_uoff);
+int  svx_text_gz_get_stats(svx_ctx* ctx, svx_text_gz_stats* out);
+/* host-only, no GPU: the same encoder built for the host, one file.  SVX_E_CAPACITY: cap is too small (n + 64 * (n / 65280 + 2) always suffices). */
+int  svx_text_gz_host(const uint8_t* text, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out);
+
 /* ---- GENOTYPE: replaces the per-candidate BAM re-fetch of genotype() (src/svim/SVIM_genotyping.py:34-93) --------
  * by an interval join over the alignment records, resident in HBM.  Records are in file order of a coordinate-sorted BAM
  * (tid, pos non-decreasing); AlignmentFile.fetch(contig, start, stop) of the reference (:48) becomes "records of that contig with

@@ -410,17 +410,33 @@ def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_dup
         sequence_alleles = False
     lists6 = (int_duplication_candidates, inversion_candidates, tandem_duplication_candidates, deletion_candidates, novel_insertion_candidates,
               breakend_candidates)
-    with open(options.working_dir + "/variants.vcf", "wb") as out:
-        out.write(("\n".join(vcf_header(version, contig_names, contig_lengths, types_to_output, options)) + "\n").encode("utf-8"))
+    bgzip = bool(getattr(options, "bgzip_output", False))      # (not an option of the reference: variants.vcf.gz, BGZF made on the device)
+    with open(options.working_dir + ("/variants.vcf.gz" if bgzip else "/variants.vcf"), "wb") as out:
+        head = ("\n".join(vcf_header(version, contig_names, contig_lengths, types_to_output, options)) + "\n").encode("utf-8")
+        if bgzip:
+            from . import harness
+            out.write(harness.bgzf_blocks(head))
+        else:
+            out.write(head)
         done = vcf_body_device(*lists6, contig_names, types_to_output, options, sequence_alleles, engine=engine)
         if done is None:
             names = list(convert.Interner(contig_names).names)
             used = {getattr(c, k) for lst in lists6 for c in lst for k in ("source_contig", "dest_contig") if hasattr(c, k)}
             reference = GenomeText(options.genome, names + sorted(used - set(names))) if sequence_alleles else None
             lines = vcf_body_python(*lists6, types_to_output, options, sequence_alleles, reference)
-            out.write("".join(line + "\n" for line in lines).encode("utf-8"))
+            text = "".join(line + "\n" for line in lines).encode("utf-8")
+            if bgzip:
+                eng = engine if engine is not None else _lib.engine()
+                eng.text_gz(_abi.TEXT_GZ_HOST, text)
+                harness.write_text_gz(eng, out)
+            else:
+                out.write(text)
             return
         eng, _, n_bytes = done
+        if bgzip:
+            eng.text_gz(_abi.TEXT_GZ_VCF)
+            harness.write_text_gz(eng, out)
+            return
         for at in range(0, n_bytes, _VCF_PIECE):
             out.write(eng.vcf_fetch(at, min(_VCF_PIECE, n_bytes - at)))
 

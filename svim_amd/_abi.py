@@ -201,6 +201,20 @@ class BedStats(C.Structure):
         return d
 
 
+# BGZF output (include/svx.h: svx_text_gz*): text bytes per block, the end-of-file block every file ends with, the sources of Engine.text_gz
+TEXT_GZ_BLOCK = 65280
+TEXT_GZ_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+TEXT_GZ_VCF, TEXT_GZ_BED, TEXT_GZ_HOST = 0, 1, 2
+
+
+class TextGzStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_total_ms", "t_upload_ms", "t_crc_ms", "t_matches_ms", "t_codes_ms", "t_bits_ms", "t_compaction_ms")] + \
+               [(n, C.c_int64) for n in ("n_files", "n_blocks", "blocks_eof", "blocks_stored", "blocks_dynamic", "bytes_in", "bytes_out")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class GenotypeParams(C.Structure):
     _fields_ = [("minimum_score", C.c_double), ("min_mapq", C.c_int32), ("minimum_depth", C.c_int32), ("homozygous_threshold", C.c_double),
                 ("heterozygous_threshold", C.c_double)]

@@ -31,7 +31,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_combine", "svx_combine_count", "svx_combine_fetch", "svx_combine_stages_fetch", "svx_combine_get_stats", "svx_py_sample100",
            "svx_vcf", "svx_vcf_count", "svx_vcf_fetch", "svx_vcf_get_stats", "svx_vcf_format_std",
            "svx_format_repr", "svx_format_repr_many", "svx_format_repr_device",
-           "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats"]
+           "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats",
+           "svx_text_gz", "svx_text_gz_count", "svx_text_gz_fetch", "svx_text_gz_get_stats", "svx_text_gz_host"]
 
 
 class SvxError(RuntimeError):
@@ -117,6 +118,18 @@ def format_repr_many(values):
     out = np.zeros((max(1, x.size), 32), dtype=np.uint8)
     _check(lib().svx_format_repr_many(C.c_int64(x.size), ptr(x if x.size else np.zeros(1)), ptr(out)), "svx_format_repr_many")
     return [b.decode("ascii") for b in out[:x.size].view("S32").ravel().tolist()]
+
+
+def text_gz_host(data):
+    """svx_text_gz_host (host-only, no GPU needed): the BGZF stream of one file of bytes by the host build of csrc/deflate_core.hpp - the bytes
+    Engine.text_gz makes of the same text on the device"""
+    data = bytes(data)
+    cap = len(data) + 64 * (len(data) // _abi.TEXT_GZ_BLOCK + 2)
+    out = np.zeros(cap, dtype=np.uint8)
+    n = C.c_int64()
+    src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+    _check(lib().svx_text_gz_host(ptr(src), C.c_int64(len(data)), ptr(out), C.c_int64(cap), C.byref(n)), "svx_text_gz_host")
+    return out[:n.value].tobytes()
 
 
 def build(force=False):
@@ -504,6 +517,50 @@ class Engine(object):
     def bed_stats(self):
         s = _abi.BedStats()
         _check(self.L.svx_bed_get_stats(self.ctx, C.byref(s)), "svx_bed_get_stats")
+        return s.as_dict()
+
+    # ---- BGZF output ----
+    def text_gz(self, source, data=None, file_off=None):
+        """svx_text_gz: the BGZF stream of a text, made and kept on the device.  source _abi.TEXT_GZ_VCF: the text of the last vcf() (one file); TEXT_GZ_BED:
+        the text of the last bed() (its files); TEXT_GZ_HOST: `data` (bytes), uploaded - one file, or the files data[file_off[k]:file_off[k + 1]].
+        -> (number of files, blocks, bytes); text_gz_fetch() / text_gz_tables() bring the stream and its tables over.  A later vcf() / bed() voids the stream
+        of its text."""
+        if source == _abi.TEXT_GZ_HOST:
+            data = bytes(data if data is not None else b"")
+            off = np.ascontiguousarray(file_off if file_off is not None else [0, len(data)], dtype=np.int64)
+            if off.size < 2 or int(off[-1]) != len(data):
+                raise ValueError("text_gz: file_off must hold n_files + 1 offsets and end at len(data)")
+            src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
+            rc = self.L.svx_text_gz(self.ctx, C.c_int(2), ptr(src), ptr(off), C.c_int32(off.size - 1))
+        else:
+            rc = self.L.svx_text_gz(self.ctx, C.c_int(source), None, None, C.c_int32(0))
+        _check(rc, "svx_text_gz")
+        return self.text_gz_count()
+
+    def text_gz_count(self):
+        nf, nb, n = C.c_int32(), C.c_int64(), C.c_int64()
+        _check(self.L.svx_text_gz_count(self.ctx, C.byref(nf), C.byref(nb), C.byref(n)), "svx_text_gz_count")
+        return nf.value, nb.value, n.value
+
+    def text_gz_fetch(self, offset=0, nbytes=None):
+        """bytes [offset, offset + nbytes) of the stream of the last text_gz() call (svx_text_gz_fetch; nbytes None: to the end) -> bytes"""
+        _, _, total = self.text_gz_count()
+        nbytes = total - offset if nbytes is None else nbytes
+        buf = np.zeros(max(1, nbytes), dtype=np.uint8)
+        _check(self.L.svx_text_gz_fetch(self.ctx, C.c_int64(offset), C.c_int64(nbytes), ptr(buf), None, None, None), "svx_text_gz_fetch")
+        return buf[:nbytes].tobytes()
+
+    def text_gz_tables(self):
+        """(int64[n_files + 1] offsets of the files in the stream, int64[n_blocks + 1] offsets of the blocks in the stream, int64[n_blocks + 1] offsets of
+        their text in the text) of the last text_gz() call: what a .gzi or tabix index would be built from"""
+        nf, nb, _ = self.text_gz_count()
+        fo, co, uo = np.zeros(nf + 1, dtype=np.int64), np.zeros(nb + 1, dtype=np.int64), np.zeros(nb + 1, dtype=np.int64)
+        _check(self.L.svx_text_gz_fetch(self.ctx, C.c_int64(0), C.c_int64(0), None, ptr(fo), ptr(co), ptr(uo)), "svx_text_gz_fetch")
+        return fo, co, uo
+
+    def text_gz_stats(self):
+        s = _abi.TextGzStats()
+        _check(self.L.svx_text_gz_get_stats(self.ctx, C.byref(s)), "svx_text_gz_get_stats")
         return s.as_dict()
 
     def set_alignment_index(self, index):

@@ -266,11 +266,22 @@ def file_texts(eng, piece=_PIECE):
     return [text[int(off[k]):int(off[k + 1])] for k in range(len(off) - 1)]
 
 
-def write_files(eng, directory, names, heads=None, piece=_PIECE):
-    """the files of the engine's last bed() call into `directory` under `names` (heads: bytes written in front of each), fetched in pieces"""
+def write_files(eng, directory, names, heads=None, piece=_PIECE, compress=False):
+    """the files of the engine's last bed() call into `directory` under `names` (heads: bytes written in front of each), fetched in pieces.
+    compress: every name with .gz appended, the text compressed to BGZF on the device (svx_text_gz) and only the streams fetched; a head is compressed here"""
     off, _ = eng.bed_file_offsets()
     if len(off) - 1 != len(names):
         raise ValueError("%d files in the text, %d names" % (len(off) - 1, len(names)))
+    if compress:
+        from . import harness
+        eng.text_gz(_abi.TEXT_GZ_BED)
+        goff, _, _ = eng.text_gz_tables()
+        for k, name in enumerate(names):
+            with open(os.path.join(directory, name + ".gz"), "wb") as fh:
+                if heads is not None:
+                    fh.write(harness.bgzf_blocks(heads[k]))
+                harness.write_text_gz(eng, fh, goff[k], goff[k + 1], piece)
+        return
     for k, name in enumerate(names):
         with open(os.path.join(directory, name), "wb") as fh:
             if heads is not None:

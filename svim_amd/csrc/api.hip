@@ -124,6 +124,7 @@ extern "C" void svx_ctx_destroy(svx_ctx* c) {
     svx_combine_release(c);
     svx_vcf_release(c);
     svx_bed_release(c);
+    svx_textgz_release(c);
     c->repr_tab.release();
     svx_aln_release(c);
     svx_genotype_release(c);

@@ -10,6 +10,7 @@
 #include "hostcopy.hpp"
 #include "devdec.hpp"
 #include "scan.hpp"
+#include "crc32_wave.hpp"
 #include <zlib.h>
 #include <chrono>
 #include <mutex>
@@ -83,72 +84,15 @@ __device__ bool dd_validate(const uint8_t* st, uint64_t q, uint64_t data_end, in
 // shift by 2^j zero bytes being a fixed 32 x 32 matrix over GF(2) - and the rounds are chained the same way.  The block is right-aligned in its rounds
 // (leading zero bytes leave a zero register alone); the initial value 0xffffffff enters at the end as shift(0xffffffff, len).
 struct CrcJob { unsigned long long at; uint32_t len, crc; };
-#define CRC_POW 17                                  /* shift matrices for 2^0 .. 2^16 zero bytes */
-typedef uint32_t __attribute__((aligned(1))) crc_u32_unaligned;
-__device__ __forceinline__ uint32_t crc_apply(const uint32_t* __restrict__ m, uint32_t x) {       // m: 32 words, wave-uniform address
-    uint32_t o = 0;
-#pragma unroll
-    for (int bit = 0; bit < 32; bit++) o ^= m[bit] & (0u - ((x >> bit) & 1u));
-    return o;
-}
+// (the arithmetic lives in crc32_wave.hpp: the writer of BGZF blocks, textgz.hip, stores what this kernel compares)
 __global__ __launch_bounds__(64) void k_crc32(const uint8_t* st, const CrcJob* jobs, long long nb, const uint32_t* __restrict__ shift, int* err) {
-    __shared__ uint32_t T[256], T1[256], T2[256], T3[256];        // T: one byte; T1..T3: the same byte followed by 1..3 zero bytes (a word takes one round of look-ups)
-    const int lane = lane_id();
-    for (int e = lane; e < 256; e += 64) {
-        uint32_t c = (uint32_t)e;
-#pragma unroll
-        for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-        T[e] = c;
-    }
-    __syncthreads();
-    for (int e = lane; e < 256; e += 64) {
-        const uint32_t c1 = T[T[e] & 255u] ^ (T[e] >> 8), c2 = T[c1 & 255u] ^ (c1 >> 8), c3 = T[c2 & 255u] ^ (c2 >> 8);
-        T1[e] = c1; T2[e] = c2; T3[e] = c3;
-    }
-    __syncthreads();
+    __shared__ CrcTables S;
+    crc32_wave_tables(S);
     const long long b = blockIdx.x;
     if (b >= nb) return;
     const CrcJob job = jobs[b];
-    const uint8_t* base = st + job.at;
-    const long long len = job.len, rounds = (len + 4095) >> 12, pad = (rounds << 12) - len;
-    uint32_t acc = 0;
-    for (long long r = 0; r < rounds; r++) {
-        const long long off = (r << 12) + (long long)lane * 64 - pad;            // where my 64 bytes start in the block (negative: virtual zero bytes)
-        uint32_t reg = 0;
-        if (off >= 0) {
-            const crc_u32_unaligned* w = reinterpret_cast<const crc_u32_unaligned*>(base + off);
-            uint32_t x[16];
-#pragma unroll
-            for (int k = 0; k < 16; k++) x[k] = w[k];
-#pragma unroll
-            for (int k = 0; k < 16; k++) {
-                reg ^= x[k];
-                reg = T3[reg & 255u] ^ T2[(reg >> 8) & 255u] ^ T1[(reg >> 16) & 255u] ^ T[reg >> 24];
-            }
-        } else if (off > -64) {
-            for (long long i = 0; i < off + 64; i++) reg = T[(reg ^ base[i]) & 255u] ^ (reg >> 8);
-        }
-        // six levels: the last lane of every group of 2, 4, ... 64 holds the register of its group's bytes
-#pragma unroll
-        for (int j = 0; j < 6; j++) {
-            const uint32_t left = (uint32_t)__shfl_up((int)reg, 1 << j, 64);
-            const uint32_t joined = crc_apply(shift + 32 * (6 + j), left) ^ reg;
-            if ((lane & ((2 << j) - 1)) == (2 << j) - 1) reg = joined;
-        }
-        acc = crc_apply(shift + 32 * 12, acc) ^ (uint32_t)__builtin_amdgcn_readlane((int)reg, 63);
-    }
-    uint32_t init = 0xffffffffu;
-    for (int j = 0; j < CRC_POW; j++) if ((len >> j) & 1) init = crc_apply(shift + 32 * j, init);
-    const uint32_t crc = ~(acc ^ init);
-    if (lane == 0 && crc != job.crc) { if (atomicCAS(err, 0, 1) == 0) err[1] = (int)b; }
-}
-// the shift matrices: column `bit` of matrix j = the register that 1 << bit becomes after 2^j zero bytes
-static void crc_shift_matrices(uint32_t (*m)[32]) {
-    uint32_t T[256];
-    for (uint32_t e = 0; e < 256; e++) { uint32_t c = e; for (int k = 0; k < 8; k++) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1; T[e] = c; }
-    for (int bit = 0; bit < 32; bit++) { const uint32_t r = 1u << bit; m[0][bit] = T[r & 255u] ^ (r >> 8); }
-    for (int j = 1; j < CRC_POW; j++)
-        for (int bit = 0; bit < 32; bit++) { uint32_t o = 0; for (int k = 0; k < 32; k++) if ((m[j - 1][bit] >> k) & 1u) o ^= m[j - 1][k]; m[j][bit] = o; }
+    const uint32_t crc = crc32_wave(st + job.at, (long long)job.len, shift, S);
+    if (lane_id() == 0 && crc != job.crc) { if (atomicCAS(err, 0, 1) == 0) err[1] = (int)b; }
 }
 
 // first record start at or after the start of every BGZF block (one wavefront per block; lanes test 64 consecutive byte offsets at a time)

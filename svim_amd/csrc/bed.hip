@@ -381,6 +381,7 @@ extern "C" int svx_bed(svx_ctx* c, int product, int source, const svx_cluster_vi
     HIPCHK(hipSetDevice(c->device));
     BedState* S; SVXCHK(bed_state(c, &S));
     S->used = 0; S->have = false; S->n_lines = S->n_bytes = 0; S->n_files = 0;
+    c->bed_calls++;                    // (a BGZF stream made of the text before is void from here on)
     memset(&S->stats, 0, sizeof S->stats);
     const bool cand = product == SVX_BED_CANDIDATE_BEDS, with_members = product != SVX_BED_SIGNATURE_VCF;
     hipStream_t st = c->stream;
@@ -615,6 +616,12 @@ extern "C" int svx_bed_fetch(svx_ctx* c, int64_t byte_offset, int64_t bytes, uin
     SVXCHK(hc.finish());
     HIPCHK(hipStreamSynchronize(c->stream));
     return SVX_OK;
+}
+
+bool svx_bed_text(svx_ctx* c, const uint8_t** text, int32_t* n_files, const int64_t** file_off_host) {
+    if (!c->bed || !c->bed->have) return false;
+    *text = c->bed->out.as<uint8_t>(); *n_files = c->bed->n_files; *file_off_host = c->bed->file_off;
+    return true;
 }
 
 extern "C" int svx_bed_get_stats(svx_ctx* c, svx_bed_stats* out) {

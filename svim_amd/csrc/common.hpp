@@ -201,8 +201,14 @@ struct svx_ctx {
     // context, the stage's own buffers and results; the multiplier tables of repr(float) (fmtrepr.hip), uploaded once
     ClusterIn last_cluster_in{}; struct BedState* bed = nullptr;
     DevBuf repr_tab; bool repr_tab_ready = false;
+    // BGZF output (textgz.hip): how many svx_vcf / svx_bed calls the context has seen (a stream belongs to the text of one of them), the stage's buffers and results
+    long long vcf_calls = 0, bed_calls = 0; struct TextGzState* textgz = nullptr;
 };
 void svx_bed_release(svx_ctx* c);
+void svx_textgz_release(svx_ctx* c);
+// the text of the last svx_vcf / svx_bed as device pointers (vcf.hip, bed.hip; textgz.hip reads it): false when there is none
+bool svx_vcf_text(svx_ctx* c, const uint8_t** text, int64_t* n_bytes);
+bool svx_bed_text(svx_ctx* c, const uint8_t** text, int32_t* n_files, const int64_t** file_off_host);
 const uint64_t* svx_repr_host_tables();
 int svx_repr_device_tables(svx_ctx* c, const uint64_t** out);
 void svx_combine_release(svx_ctx* c);

@@ -510,6 +510,7 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     VcfState* S = c->vcf;
     if (!S->have_ev) { for (auto& e : S->ev) HIPCHK(hipEventCreate(&e)); S->have_ev = true; }
     S->used = 0; S->have = false; S->n_lines = S->n_bytes = 0;
+    c->vcf_calls++;                    // (a BGZF stream made of the text before is void from here on)
     memset(&S->stats, 0, sizeof S->stats);
     const svx_vcf_params P = *pp;
     if (P.sequence_alleles && !c->g_off_p) return svx_fail(SVX_E_STATE, "svx_vcf: sequence alleles need a genome in the context (svx_set_genome / svx_genome_load_fasta)", __FILE__, __LINE__, hipSuccess);
@@ -753,6 +754,12 @@ extern "C" int svx_vcf_fetch(svx_ctx* c, int64_t byte_offset, int64_t bytes, uin
     SVXCHK(hc.finish());
     HIPCHK(hipStreamSynchronize(c->stream));
     return SVX_OK;
+}
+
+bool svx_vcf_text(svx_ctx* c, const uint8_t** text, int64_t* n_bytes) {
+    if (!c->vcf || !c->vcf->have) return false;
+    *text = c->vcf->out.as<uint8_t>(); *n_bytes = c->vcf->n_bytes;
+    return true;
 }
 
 extern "C" int svx_vcf_get_stats(svx_ctx* c, svx_vcf_stats* out) {

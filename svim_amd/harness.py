@@ -206,37 +206,46 @@ class BamPipeline(object):
         names = self.bam.read_names() if (vp.read_names or vp.zmws) else None
         t0 = time.perf_counter()
         _, n_bytes = self.eng.vcf(vp, self.bam.references, read_names=names, resident_genotypes=getattr(self, "_genotyped", False))
+        head = ("\n".join(K.vcf_header(version, self.bam.references, self.bam.lengths, types, o)) + "\n").encode("utf-8")
         with open(path, "wb") as out:
-            out.write(("\n".join(K.vcf_header(version, self.bam.references, self.bam.lengths, types, o)) + "\n").encode("utf-8"))
-            for at in range(0, n_bytes, K._VCF_PIECE):
-                out.write(self.eng.vcf_fetch(at, min(K._VCF_PIECE, n_bytes - at)))
+            if str(path).endswith(".gz"):
+                # BGZF: the header compressed here, the lines compressed where they lie (svx_text_gz); only the stream crosses to the host
+                self.eng.text_gz(_abi.TEXT_GZ_VCF)
+                out.write(bgzf_blocks(head))
+                write_text_gz(self.eng, out)
+            else:
+                out.write(head)
+                for at in range(0, n_bytes, K._VCF_PIECE):
+                    out.write(self.eng.vcf_fetch(at, min(K._VCF_PIECE, n_bytes - at)))
         self.stats["t_vcf_wall"] = time.perf_counter() - t0
         return n_bytes
 
     # file -> the sixteen BED / signature-VCF files of the working directory without a Python object: run(), cluster(), write_signature_files(dir, version),
     # combine(), write_candidate_files(dir)
-    def _bed_files(self, product, directory, names, heads=None):
+    def _bed_files(self, product, directory, names, heads=None, compress=False):
         from . import bed
         if getattr(self, "_bed_read_names", None) is None:
             self._bed_read_names = self.bam.read_names()             # uploaded once: the engine knows the list by identity
         os.makedirs(directory, exist_ok=True)
         t0 = time.perf_counter()
         _, _, n_bytes = self.eng.bed(product, self.bam.references, read_names=self._bed_read_names)
-        bed.write_files(self.eng, directory, names, heads=heads)
+        bed.write_files(self.eng, directory, names, heads=heads, compress=compress)
         self.stats["t_bed_wall"] = self.stats.get("t_bed_wall", 0.0) + time.perf_counter() - t0
         return n_bytes
 
-    def write_signature_files(self, working_dir, version="svim_amd"):
-        """<working_dir>/signatures/*.bed and all.vcf of the resident clusters (after cluster()), made by svx_bed -> bytes written behind the header"""
+    def write_signature_files(self, working_dir, version="svim_amd", compress=False):
+        """<working_dir>/signatures/*.bed and all.vcf of the resident clusters (after cluster()), made by svx_bed -> bytes of text behind the header.
+        compress: the same names with .gz appended, BGZF made on the device (svx_text_gz)"""
         from . import SVIM_CLUSTER as K
         d = os.path.join(working_dir, "signatures")
-        n = self._bed_files(_abi.BED_SIGNATURE_BEDS, d, [name for name, _, _ in K._BED_FILES])
-        return n + self._bed_files(_abi.BED_SIGNATURE_VCF, d, ["all.vcf"], heads=[K.vcf_header_text(version).encode("utf-8")])
+        n = self._bed_files(_abi.BED_SIGNATURE_BEDS, d, [name for name, _, _ in K._BED_FILES], compress=compress)
+        return n + self._bed_files(_abi.BED_SIGNATURE_VCF, d, ["all.vcf"], heads=[K.vcf_header_text(version).encode("utf-8")], compress=compress)
 
-    def write_candidate_files(self, working_dir):
-        """<working_dir>/candidates/candidates_*.bed of the resident candidates (after combine()), made by svx_bed -> bytes written"""
+    def write_candidate_files(self, working_dir, compress=False):
+        """<working_dir>/candidates/candidates_*.bed of the resident candidates (after combine()), made by svx_bed -> bytes of text.
+        compress: the same names with .gz appended, BGZF made on the device (svx_text_gz)"""
         from . import SVIM_COMBINE as K
-        return self._bed_files(_abi.BED_CANDIDATE_BEDS, os.path.join(working_dir, "candidates"), [name for name, _, _ in K._CANDIDATE_BED_FILES])
+        return self._bed_files(_abi.BED_CANDIDATE_BEDS, os.path.join(working_dir, "candidates"), [name for name, _, _ in K._CANDIDATE_BED_FILES], compress=compress)
 
     def rewind(self):
         """back to the first record for another pass: buffers, worker threads and read names are kept - the state a long file is in
@@ -259,6 +268,20 @@ def _bgzf_block(payload, level=1):
     comp = co.compress(payload) + co.flush()
     head = b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00" + (len(comp) + 25).to_bytes(2, "little")
     return head + comp + (zlib.crc32(payload) & 0xffffffff).to_bytes(4, "little") + len(payload).to_bytes(4, "little")
+
+
+def bgzf_blocks(data):
+    """bytes -> BGZF blocks of at most 65 280 bytes each WITHOUT the end-of-file block (zlib on the host): a header in front of a stream the device made -
+    concatenated BGZF is BGZF"""
+    return b"".join(_bgzf_block(data[at:at + _abi.TEXT_GZ_BLOCK]) for at in range(0, len(data), _abi.TEXT_GZ_BLOCK))
+
+
+def write_text_gz(eng, fh, lo=0, hi=None, piece=64 << 20):
+    """bytes [lo, hi) of the stream of the engine's last text_gz() call into the open file, fetched in pieces (hi None: to the end)"""
+    if hi is None:
+        hi = eng.text_gz_count()[2]
+    for at in range(int(lo), int(hi), piece):
+        fh.write(eng.text_gz_fetch(at, min(piece, int(hi) - at)))
 
 
 def write_bam_from_batch(path, hb, references, lengths, name_fmt="r%08d", threads=None, qual_seed=None):
