@@ -38,6 +38,8 @@ extern "C" {
 #define SVX_E_STATE        (-5)   /* call order violated (e.g. cluster before collect/set_signatures) */
 #define SVX_E_FASTA_SYMBOL (-6)   /* svx_genome_load_fasta: a requested record holds symbols outside "=ACMGRSVTWYHKDBN" (svx_fasta_stats.bad_mask says which) */
 #define SVX_E_FASTA_HOST   (-7)   /* svx_genome_load_fasta: a file the device loader leaves to the caller's host parser (svx_fasta_stats.host_reason says why) */
+#define SVX_E_ORDER        (-9)   /* svx_text_index: records of a contig not contiguous, or positions decreasing inside one */
+#define SVX_E_RANGE        (-10)  /* svx_text_index: a record ends beyond 2^29: outside what a .tbi can hold */
 #define SVX_E_NO_DELETION  (-8)   /* svx_combine: insertion-from clusters but no deletion cluster (the reference raises IndexError at src/svim/SVIM_merging.py:20) */
 
 /* signature types, in the order CLUSTER processes them (src/svim/SVIM_CLUSTER.py:19-24) */
@@ -475,6 +477,26 @@ int  svx_text_gz_get_stats(svx_ctx* ctx, svx_text_gz_stats* out);
 /* host-only, no GPU: the same encoder built for the host, one file.  SVX_E_CAPACITY: cap is too small (n + 64 * (n / 65280 + 2) always suffices). */
 int  svx_text_gz_host(const uint8_t* text, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out);
 
+/* ---- tabix index of the BGZF stream (textindex.hip, textindex_core.hpp; the definition in words: svim_amd/tabix.py) ----
+ * svx_text_index builds, for every file of the last svx_text_gz, the uncompressed bytes of its .tbi from the text AND the block table of that call, both where
+ * they lie on the device (SVX_E_STATE without a valid stream; the index is void whenever its stream is).  preset: how a line gives its interval
+ * (SVX_INDEX_VCF: POS, len(REF), END=; SVX_INDEX_BED: columns 2 and 3).  stream_base[k]: bytes written in front of file k's stream in its file (a header
+ * compressed on the host), NULL = 0.  The call returns SVX_OK even when single files cannot be indexed: file_status says so (SVX_E_ORDER, SVX_E_RANGE) and
+ * their bytes are empty.  Chunks are the maximal runs of records of one (contig, bin) in file order; htslib's merging of bins and chunks is not reproduced. */
+enum { SVX_INDEX_VCF = 0, SVX_INDEX_BED = 1 };
+typedef struct svx_text_index_stats {
+    double  t_total_ms, t_lines_ms, t_records_ms, t_contigs_ms, t_chunks_ms, t_linear_ms, t_serialise_ms;
+    int64_t n_files, n_files_indexed, n_lines, n_records, n_contigs, n_chunks, n_bins, n_slots, bytes_text, bytes_out;
+} svx_text_index_stats;
+int  svx_text_index(svx_ctx* ctx, int preset, const int64_t* stream_base);
+int  svx_text_index_count(svx_ctx* ctx, int32_t* n_files, int64_t* n_bytes);
+int  svx_text_index_fetch(svx_ctx* ctx, uint8_t* host_dst, int64_t* file_off /* [n_files + 1] */, int32_t* file_status /* [n_files] */);
+int  svx_text_index_get_stats(svx_ctx* ctx, svx_text_index_stats* out);
+/* host-only, no GPU: one file.  block_coff / block_uoff: n_blocks + 1 entries as svx_text_gz_fetch returns them, the last block the end-of-file block.
+ * *n_out is the size also when cap is too small (SVX_E_CAPACITY).  SVX_E_ORDER / SVX_E_RANGE: the file has no index. */
+int  svx_text_index_host(const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
+                         uint8_t* out, int64_t cap, int64_t* n_out);
+
 /* ---- GENOTYPE: replaces the per-candidate BAM re-fetch of genotype() (src/svim/SVIM_genotyping.py:34-93) --------
  * by an interval join over the alignment records, resident in HBM.  Records are in file order of a coordinate-sorted BAM
  * (tid, pos non-decreasing); AlignmentFile.fetch(contig, start, stop) of the reference (:48) becomes "records of that contig with
@@ -550,6 +572,10 @@ int  svx_genotype_get_stats(svx_ctx* ctx, svx_genotype_stats* out);
 /* on: a svx_vcf with source 0 and no genotype column handed in (gt, ref_reads and alt_reads all NULL) prints the columns svx_genotype_resident (source 0) left
  * for that table, read in place; SVX_E_STATE if there are none for it.  Off (the default): such a call prints "./." as before. */
 int  svx_vcf_use_resident_genotypes(svx_ctx* ctx, int on);
+/* On: the lines of later svx_vcf calls leave in position order - after the ids are given in the reference's order, one more stable pass sorts the lines by
+ * (contig, POS as printed); contigs in natural order, those that share a natural rank by their index.  The same lines with the same ids, every contig
+ * contiguous and POS non-decreasing inside it: what tabix asks for.  Off (the default): the reference's order, byte for byte. */
+int  svx_vcf_position_order(svx_ctx* ctx, int on);
 
 /* ---- single-function entry points kept importable by the reference's API ------------------------ */
 /* analyze_cigar_indel (src/svim/SVIM_intra.py:8-30) on one packed CIGAR; out arrays sized n_ops */

@@ -242,9 +242,23 @@ def vcf_header(version, contig_names, contig_lengths, types_to_output, options, 
     return lines
 
 
-def vcf_body_python(int_dup, inv, tan_dup, dele, ins, bnd, types_to_output, options, sequence_alleles=False, reference=None):
+def position_ordered(lines, contig_names=None):
+    """VCF lines (with their ids) sorted stably by (contig, POS as printed): contigs by their natural key, those that share a key by their index in
+    contig_names (a name the table lacks: behind it, in order of first appearance).  Every contig contiguous, POS non-decreasing inside it, ties in the order
+    they came: what tabix asks of a file, and what svx_vcf_position_order makes on the device."""
+    index = {n: k for k, n in enumerate(convert.Interner(contig_names or ()).names)}
+    keyed = []
+    for line in lines:
+        contig, pos = line.split("\t", 2)[:2]
+        keyed.append(((convert.natural_key(contig), index.setdefault(contig, len(index)), int(pos)), line))
+    return [line for _, line in sorted(keyed, key=lambda e: e[0])]
+
+
+def vcf_body_python(int_dup, inv, tan_dup, dele, ins, bnd, types_to_output, options, sequence_alleles=False, reference=None, position_order=False, contig_names=None):
     """The lines of variants.vcf behind the header from candidate OBJECTS, as the reference makes them (src/svim/SVIM_COMBINE.py:139-184): the entries in append
-    order, sorted_nicely, the svim.<label>.<k> ids.  The definition the device writer is held against; -> list of lines without the newline."""
+    order, sorted_nicely, the svim.<label>.<k> ids.  The definition the device writer is held against; -> list of lines without the newline.
+    position_order (not the reference's: its file is sorted by the candidates' (contig, start, end), and POS is max(1, start) or start + 1 by class, so POS
+    drops inside a contig, and contigs with one natural key interleave): the same lines with the same ids through position_ordered(lines, contig_names)."""
     o, entries = options, []
     if "DEL" in types_to_output:
         entries += [(c.get_source(), c.get_vcf_entry(sequence_alleles, reference, o.read_names, o.zmws), "DEL") for c in dele]
@@ -268,7 +282,7 @@ def vcf_body_python(int_dup, inv, tan_dup, dele, ins, bnd, types_to_output, opti
     for _, entry, svtype in sorted_nicely(entries):
         counter[svtype] += 1
         lines.append(entry.replace("PLACEHOLDERFORID", "svim.%s.%d" % (svtype, counter[svtype]), 1))
-    return lines
+    return position_ordered(lines, contig_names) if position_order else lines
 
 
 class GenomeText(object):
@@ -366,12 +380,24 @@ def candidate_table_from_lists(lists6, references=()):
 _VCF_PIECE = 64 << 20
 
 
+def _position_order(options):
+    """options.position_order, or an index asked for (options.bgzip_output and options.tabix_index): tabix needs the order"""
+    return bool(getattr(options, "position_order", False)) or (bool(getattr(options, "bgzip_output", False)) and bool(getattr(options, "tabix_index", False)))
+
+
+def _write_tbi(path, index_bytes):
+    from . import harness
+    with open(path, "wb") as fh:
+        fh.write(harness.bgzf_blocks(index_bytes) + _abi.TEXT_GZ_EOF)
+
+
 def vcf_body_device(int_dup, inv, tan_dup, dele, ins, bnd, contig_names, types_to_output, options, sequence_alleles, engine=None):
     """svx_vcf on one of the two routes (see write_final_vcf) -> (engine, number of lines, number of bytes), the text resident in the engine;
     None: the candidates need the Python definition (candidate_table_from_lists says when)."""
     eng = engine if engine is not None else _lib.engine()
     lists6 = (int_dup, inv, tan_dup, dele, ins, bnd)
     vp = _abi.VcfParams.from_options(options, types_to_output, sequence_alleles)
+    vp.position_order = _position_order(options)
     need_names = bool(vp.read_names or vp.zmws)
     if _resident_candidates(lists6, eng):
         first = lists6[0]
@@ -401,6 +427,8 @@ def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_dup
         object is made;
       * anything else (plain lists, lists genotype() wrote to, breakend_candidates + breakend_candidates_all_bnds of --all_bnds): one pass over the objects
         builds the candidate table, the genotype columns and the member signature columns: source 2.
+    options.position_order (not an option of the reference): the lines in position order on all three routes.  options.bgzip_output with options.tabix_index:
+    position order, and variants.vcf.gz.tbi beside the file, built on the device from the text and the block table of the stream (svx_text_index).
     A novel insertion candidate with a non-empty `sequence` (only hand-made objects have one: the device COMBINE implements the skip_consensus branch) or a
     genotype string outside ./. 0/0 0/1 1/1 takes the Python definition (vcf_body_python) for that call.  options.genome is loaded only when the engine does
     not hold it yet; a missing genome file gives symbolic alleles with the reference's warning."""
@@ -411,24 +439,34 @@ def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_dup
     lists6 = (int_duplication_candidates, inversion_candidates, tandem_duplication_candidates, deletion_candidates, novel_insertion_candidates,
               breakend_candidates)
     bgzip = bool(getattr(options, "bgzip_output", False))      # (not an option of the reference: variants.vcf.gz, BGZF made on the device)
-    with open(options.working_dir + ("/variants.vcf.gz" if bgzip else "/variants.vcf"), "wb") as out:
+    tbi = bgzip and bool(getattr(options, "tabix_index", False))
+    path = options.working_dir + ("/variants.vcf.gz" if bgzip else "/variants.vcf")
+
+    def index(eng, base):
+        if tbi:
+            eng.text_index(_abi.INDEX_VCF, base)
+            blobs, status = eng.text_index_fetch()
+            if status[0] != 0:
+                raise _lib.SvxError("variants.vcf.gz cannot be indexed: %s" % _abi.ERRORS.get(int(status[0]), int(status[0])))
+            _write_tbi(path + ".tbi", blobs[0])
+    with open(path, "wb") as out:
         head = ("\n".join(vcf_header(version, contig_names, contig_lengths, types_to_output, options)) + "\n").encode("utf-8")
         if bgzip:
             from . import harness
-            out.write(harness.bgzf_blocks(head))
-        else:
-            out.write(head)
+            head = harness.bgzf_blocks(head)
+        out.write(head)
         done = vcf_body_device(*lists6, contig_names, types_to_output, options, sequence_alleles, engine=engine)
         if done is None:
             names = list(convert.Interner(contig_names).names)
             used = {getattr(c, k) for lst in lists6 for c in lst for k in ("source_contig", "dest_contig") if hasattr(c, k)}
             reference = GenomeText(options.genome, names + sorted(used - set(names))) if sequence_alleles else None
-            lines = vcf_body_python(*lists6, types_to_output, options, sequence_alleles, reference)
+            lines = vcf_body_python(*lists6, types_to_output, options, sequence_alleles, reference, position_order=_position_order(options), contig_names=contig_names)
             text = "".join(line + "\n" for line in lines).encode("utf-8")
             if bgzip:
                 eng = engine if engine is not None else _lib.engine()
                 eng.text_gz(_abi.TEXT_GZ_HOST, text)
                 harness.write_text_gz(eng, out)
+                index(eng, len(head))
             else:
                 out.write(text)
             return
@@ -436,6 +474,7 @@ def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_dup
         if bgzip:
             eng.text_gz(_abi.TEXT_GZ_VCF)
             harness.write_text_gz(eng, out)
+            index(eng, len(head))
             return
         for at in range(0, n_bytes, _VCF_PIECE):
             out.write(eng.vcf_fetch(at, min(_VCF_PIECE, n_bytes - at)))

@@ -13,8 +13,9 @@ SVX_FLAG_SKIP = 0x8000
 NIBBLE = "=ACMGRSVTWYHKDBN"
 
 ERRORS = {-1: "SVX_E_NODEVICE", -2: "SVX_E_HIP", -3: "SVX_E_ARG", -4: "SVX_E_CAPACITY", -5: "SVX_E_STATE", -6: "SVX_E_FASTA_SYMBOL", -7: "SVX_E_FASTA_HOST",
-          -8: "SVX_E_NO_DELETION"}
+          -8: "SVX_E_NO_DELETION", -9: "SVX_E_ORDER", -10: "SVX_E_RANGE"}
 SVX_E_STATE, SVX_E_FASTA_SYMBOL, SVX_E_FASTA_HOST, SVX_E_NO_DELETION = -5, -6, -7, -8
+SVX_E_CAPACITY, SVX_E_ORDER, SVX_E_RANGE = -4, -9, -10
 # candidate classes in the order of combine_clusters' return tuple (include/svx.h: SVX_CAND_*)
 CAND_DEL, CAND_INV, CAND_DUP_INT, CAND_DUP_TAN, CAND_INS, CAND_BND = range(6)
 CAND_NAMES = ("DEL", "INV", "DUP_INT", "DUP_TAN", "INS", "BND")
@@ -161,8 +162,10 @@ class VcfParams(C.Structure):
         types = VCF_LABELS if types_to_output is None else types_to_output
         mask = sum(1 << k for k, name in enumerate(VCF_LABELS) if name in types)
         seq = (not getattr(o, "symbolic_alleles", False)) if sequence_alleles is None else sequence_alleles
-        return cls(mask, 1 if seq else 0, g("insertion_sequences"), g("read_names"), g("zmws"), g("tandem_duplications_as_insertions"),
-                   g("interspersed_duplications_as_insertions"))
+        p = cls(mask, 1 if seq else 0, g("insertion_sequences"), g("read_names"), g("zmws"), g("tandem_duplications_as_insertions"),
+                g("interspersed_duplications_as_insertions"))
+        p.position_order = bool(g("position_order"))      # (not a field of svx_vcf_params: Engine.vcf passes it through svx_vcf_position_order)
+        return p
 
 
 class VcfInputs(C.Structure):
@@ -210,6 +213,18 @@ TEXT_GZ_VCF, TEXT_GZ_BED, TEXT_GZ_HOST = 0, 1, 2
 class TextGzStats(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("t_total_ms", "t_upload_ms", "t_crc_ms", "t_matches_ms", "t_codes_ms", "t_bits_ms", "t_compaction_ms")] + \
                [(n, C.c_int64) for n in ("n_files", "n_blocks", "blocks_eof", "blocks_stored", "blocks_dynamic", "bytes_in", "bytes_out")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+# tabix index (include/svx.h: svx_text_index*): presets, and the status of a file that has none
+INDEX_VCF, INDEX_BED = 0, 1
+
+
+class TextIndexStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_total_ms", "t_lines_ms", "t_records_ms", "t_contigs_ms", "t_chunks_ms", "t_linear_ms", "t_serialise_ms")] + \
+               [(n, C.c_int64) for n in ("n_files", "n_files_indexed", "n_lines", "n_records", "n_contigs", "n_chunks", "n_bins", "n_slots", "bytes_text", "bytes_out")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

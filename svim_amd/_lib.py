@@ -32,7 +32,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_vcf", "svx_vcf_count", "svx_vcf_fetch", "svx_vcf_get_stats", "svx_vcf_format_std",
            "svx_format_repr", "svx_format_repr_many", "svx_format_repr_device",
            "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats",
-           "svx_text_gz", "svx_text_gz_count", "svx_text_gz_fetch", "svx_text_gz_get_stats", "svx_text_gz_host"]
+           "svx_text_gz", "svx_text_gz_count", "svx_text_gz_fetch", "svx_text_gz_get_stats", "svx_text_gz_host",
+           "svx_vcf_position_order", "svx_text_index", "svx_text_index_count", "svx_text_index_fetch", "svx_text_index_get_stats", "svx_text_index_host"]
 
 
 class SvxError(RuntimeError):
@@ -129,6 +130,31 @@ def text_gz_host(data):
     n = C.c_int64()
     src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
     _check(lib().svx_text_gz_host(ptr(src), C.c_int64(len(data)), ptr(out), C.c_int64(cap), C.byref(n)), "svx_text_gz_host")
+    return out[:n.value].tobytes()
+
+
+def text_index_host(text, block_coff, block_uoff, preset, stream_base=0):
+    """svx_text_index_host (host-only, no GPU needed): the uncompressed .tbi bytes of one file by the host build of csrc/textindex_core.hpp - the bytes
+    Engine.text_index makes of the same text and block table on the device, and svim_amd.tabix.build_index by the definition.  block_coff / block_uoff:
+    n_blocks + 1 entries each, the last block the end-of-file block.  svim_amd.tabix.TabixError (code E_ORDER / E_RANGE) for a text that has no index."""
+    from . import tabix
+    text = bytes(text)
+    co, uo = np.ascontiguousarray(block_coff, dtype=np.int64), np.ascontiguousarray(block_uoff, dtype=np.int64)
+    if co.size != uo.size or co.size < 2:
+        raise ValueError("text_index_host: the block table needs n_blocks + 1 entries")
+    src = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, np.uint8)
+    n, cap = C.c_int64(), 0
+    for _ in range(2):
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        rc = lib().svx_text_index_host(ptr(src), C.c_int64(len(text)), ptr(co), ptr(uo), C.c_int64(co.size - 1), C.c_int(preset), C.c_int64(stream_base), ptr(out),
+                                       C.c_int64(cap), C.byref(n))
+        if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE):
+            raise tabix.TabixError(rc, "text_index_host: " + _abi.ERRORS[rc])
+        if rc != _abi.SVX_E_CAPACITY:
+            break
+        cap = n.value
+    if rc != 0:
+        raise SvxError("svx_text_index_host failed: %s" % _abi.ERRORS.get(rc, rc))
     return out[:n.value].tobytes()
 
 
@@ -349,12 +375,13 @@ class Engine(object):
 
     # ---- VCF text ----
     def vcf(self, vparams, references, table=None, sig_read_id=None, sig_seq_off=None, sig_seq=None, gt=None, ref_reads=None, alt_reads=None, read_names=None,
-            zmw_id=None, resident_genotypes=False):
+            zmw_id=None, resident_genotypes=False, position_order=None):
         """svx_vcf: the body of variants.vcf (every line behind the header) of the candidates resident from the last combine() of the resident clusters
         (table None, source 0) or of the CandidateTable `table` whose members index signatures with the columns sig_read_id / sig_seq_off / sig_seq (source 2).
         references: names of the table's contig ids.  gt (codes of _abi.VCF_GT) / ref_reads / alt_reads (-1 = None): genotype columns, default "./." / None.
         resident_genotypes (table None, no column given): the columns the last genotype_resident() left for the resident candidates, read in place.
-        read_names: names by read id (vparams.read_names); zmw_id: convert.zmw_ids of them (vparams.zmws).  The text stays on the device:
+        read_names: names by read id (vparams.read_names); zmw_id: convert.zmw_ids of them (vparams.zmws).  position_order (None: vparams.position_order,
+        off by default): the same lines with the same ids sorted by (contig, POS) - what tabix asks for (svx_vcf_position_order).  The text stays on the device:
         -> (number of lines, number of bytes); vcf_fetch() / vcf_line_offsets() bring it over."""
         from . import convert
         references = list(references)
@@ -387,6 +414,18 @@ class Engine(object):
             inp.read_names_blob, inp.read_name_off = C.cast(rbuf, C.c_void_p), arr(off, np.int64)
         if vparams.zmws:
             inp.zmw_id = arr(convert.zmw_ids(read_names) if zmw_id is None else zmw_id, np.int32)
+        if position_order is None:
+            position_order = bool(getattr(vparams, "position_order", False))
+        _check(self.L.svx_vcf_position_order(self.ctx, C.c_int(1 if position_order else 0)), "svx_vcf_position_order")
+        try:
+            rc = self._vcf_call(vparams, inp, table, sig_read_id, sig_seq_off, sig_seq, resident_genotypes, arr, keep)
+        finally:
+            self.L.svx_vcf_position_order(self.ctx, C.c_int(0))
+        _check(rc, "svx_vcf")
+        del keep, cbuf, rbuf
+        return self.vcf_count()
+
+    def _vcf_call(self, vparams, inp, table, sig_read_id, sig_seq_off, sig_seq, resident_genotypes, arr, keep):
         if table is None:
             _check(self.L.svx_vcf_use_resident_genotypes(self.ctx, C.c_int(1 if resident_genotypes else 0)), "svx_vcf_use_resident_genotypes")
             try:
@@ -404,9 +443,7 @@ class Engine(object):
             if sig_seq_off is not None:
                 sv.seq_off, sv.seq = arr(sig_seq_off, np.int64), arr(sig_seq if sig_seq is not None else np.zeros(1, np.uint8), np.uint8)
             rc = self.L.svx_vcf(self.ctx, 2, C.byref(v), C.byref(sv), C.byref(vparams), C.byref(inp))
-        _check(rc, "svx_vcf")
-        del keep, cbuf, rbuf
-        return self.vcf_count()
+        return rc
 
     def vcf_count(self):
         n, nb = C.c_int64(), C.c_int64()
@@ -561,6 +598,37 @@ class Engine(object):
     def text_gz_stats(self):
         s = _abi.TextGzStats()
         _check(self.L.svx_text_gz_get_stats(self.ctx, C.byref(s)), "svx_text_gz_get_stats")
+        return s.as_dict()
+
+    # ---- tabix index of the BGZF stream ----
+    def text_index(self, preset, stream_base=None):
+        """svx_text_index: the uncompressed .tbi bytes of every file of the last text_gz() call, built on the device from its text and block table.
+        preset: _abi.INDEX_VCF / INDEX_BED; stream_base: per file, the bytes written in front of its stream in its .gz file (a header compressed on the host;
+        None: 0; a number: one file).  -> (number of files, bytes); text_index_fetch() brings them over.  Void whenever the stream is."""
+        nf = self.text_gz_count()[0]
+        sb = None
+        if stream_base is not None:
+            sb = np.ascontiguousarray(np.atleast_1d(stream_base), dtype=np.int64)
+            if sb.size != nf:
+                raise ValueError("text_index: stream_base needs one entry per file (%d)" % nf)
+        _check(self.L.svx_text_index(self.ctx, C.c_int(preset), ptr(sb) if sb is not None else None), "svx_text_index")
+        return self.text_index_count()
+
+    def text_index_count(self):
+        nf, n = C.c_int32(), C.c_int64()
+        _check(self.L.svx_text_index_count(self.ctx, C.byref(nf), C.byref(n)), "svx_text_index_count")
+        return nf.value, n.value
+
+    def text_index_fetch(self):
+        """-> (list of bytes, one uncompressed .tbi per file, b"" for a file without one; int32[n_files] status: 0, _abi.SVX_E_ORDER, _abi.SVX_E_RANGE)"""
+        nf, n = self.text_index_count()
+        buf, off, status = np.zeros(max(1, n), dtype=np.uint8), np.zeros(nf + 1, dtype=np.int64), np.zeros(max(1, nf), dtype=np.int32)
+        _check(self.L.svx_text_index_fetch(self.ctx, ptr(buf), ptr(off), ptr(status)), "svx_text_index_fetch")
+        return [buf[int(off[k]):int(off[k + 1])].tobytes() for k in range(nf)], status[:nf]
+
+    def text_index_stats(self):
+        s = _abi.TextIndexStats()
+        _check(self.L.svx_text_index_get_stats(self.ctx, C.byref(s)), "svx_text_index_get_stats")
         return s.as_dict()
 
     def set_alignment_index(self, index):

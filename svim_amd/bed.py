@@ -13,6 +13,7 @@ resident in the engine and return (engine, route), or None when the Python defin
   * None: something a table cannot say - a score or deviation that is not a float (`"{}".format(5)` is `5`, not `5.0`) or is NaN, a `signature` string other
     than cigar / suppl, a coordinate outside int32, an object without the attributes of its slot.
 """
+import logging
 import os
 
 import numpy as np
@@ -266,25 +267,41 @@ def file_texts(eng, piece=_PIECE):
     return [text[int(off[k]):int(off[k + 1])] for k in range(len(off) - 1)]
 
 
-def write_files(eng, directory, names, heads=None, piece=_PIECE, compress=False):
+def write_files(eng, directory, names, heads=None, piece=_PIECE, compress=False, index=None):
     """the files of the engine's last bed() call into `directory` under `names` (heads: bytes written in front of each), fetched in pieces.
-    compress: every name with .gz appended, the text compressed to BGZF on the device (svx_text_gz) and only the streams fetched; a head is compressed here"""
+    compress: every name with .gz appended, the text compressed to BGZF on the device (svx_text_gz) and only the streams fetched; a head is compressed here.
+    index (_abi.INDEX_BED / INDEX_VCF, with compress): name + ".gz.tbi" for every file whose lines tabix takes as they are (svx_text_index; nothing is
+    re-sorted) -> the names of the files that got none (logged once each); [] without index"""
     off, _ = eng.bed_file_offsets()
     if len(off) - 1 != len(names):
         raise ValueError("%d files in the text, %d names" % (len(off) - 1, len(names)))
+    if index is not None and not compress:
+        raise ValueError("write_files: an index needs compress=True")
     if compress:
         from . import harness
         eng.text_gz(_abi.TEXT_GZ_BED)
         goff, _, _ = eng.text_gz_tables()
+        zheads = [harness.bgzf_blocks(h) for h in heads] if heads is not None else [b""] * len(names)
         for k, name in enumerate(names):
             with open(os.path.join(directory, name + ".gz"), "wb") as fh:
-                if heads is not None:
-                    fh.write(harness.bgzf_blocks(heads[k]))
+                fh.write(zheads[k])
                 harness.write_text_gz(eng, fh, goff[k], goff[k + 1], piece)
-        return
+        missing = []
+        if index is not None:
+            from .SVIM_COMBINE import _write_tbi
+            eng.text_index(index, [len(h) for h in zheads])
+            blobs, status = eng.text_index_fetch()
+            for k, name in enumerate(names):
+                if status[k] == 0:
+                    _write_tbi(os.path.join(directory, name + ".gz.tbi"), blobs[k])
+                else:
+                    logging.warning("%s.gz gets no tabix index: %s" % (name, _abi.ERRORS.get(int(status[k]), int(status[k]))))
+                    missing.append(name)
+        return missing
     for k, name in enumerate(names):
         with open(os.path.join(directory, name), "wb") as fh:
             if heads is not None:
                 fh.write(heads[k])
             for at in range(int(off[k]), int(off[k + 1]), piece):
                 fh.write(eng.bed_fetch(at, min(piece, int(off[k + 1]) - at)))
+    return []

@@ -125,6 +125,7 @@ extern "C" void svx_ctx_destroy(svx_ctx* c) {
     svx_vcf_release(c);
     svx_bed_release(c);
     svx_textgz_release(c);
+    svx_textindex_release(c);
     c->repr_tab.release();
     svx_aln_release(c);
     svx_genotype_release(c);

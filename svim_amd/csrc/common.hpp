@@ -203,9 +203,20 @@ struct svx_ctx {
     DevBuf repr_tab; bool repr_tab_ready = false;
     // BGZF output (textgz.hip): how many svx_vcf / svx_bed calls the context has seen (a stream belongs to the text of one of them), the stage's buffers and results
     long long vcf_calls = 0, bed_calls = 0; struct TextGzState* textgz = nullptr;
+    // tabix index of that stream (textindex.hip); whether svx_vcf leaves its lines in position order (svx_vcf_position_order)
+    struct TextIndexState* textindex = nullptr; bool vcf_position_order = false;
 };
 void svx_bed_release(svx_ctx* c);
 void svx_textgz_release(svx_ctx* c);
+void svx_textindex_release(svx_ctx* c);
+// the text and the stream of the last svx_text_gz as textindex.hip reads them: false when the stream is void.  gen: which svx_text_gz call made it
+struct TextGzView {
+    const uint8_t* text; int32_t n_files; int64_t n_blocks; long long gen;
+    const int64_t* file_off_text; const int64_t* file_first_block;      // host, n_files + 1 entries each
+    const int64_t* h_coff; const int64_t* h_uoff;                       // host, n_blocks + 1 entries each
+    const int64_t* d_coff;                                              // device, n_blocks + 1 entries
+};
+bool svx_textgz_view(svx_ctx* c, TextGzView* out);
 // the text of the last svx_vcf / svx_bed as device pointers (vcf.hip, bed.hip; textgz.hip reads it): false when there is none
 bool svx_vcf_text(svx_ctx* c, const uint8_t** text, int64_t* n_bytes);
 bool svx_bed_text(svx_ctx* c, const uint8_t** text, int32_t* n_files, const int64_t** file_off_host);

@@ -66,7 +66,7 @@ struct TextGzState {
     DevBuf text, blocks, crc, crc_shift, tok, hist, nt, codes, bsize, coff, kinds, slots, out;
     std::vector<int64_t> file_off_text, file_first_block, h_coff, h_uoff;
     int32_t n_files = 0; int64_t n_blocks = 0, n_bytes = 0;
-    int source = -1; long long of_call = 0;
+    int source = -1; long long of_call = 0, gen = 0;
     bool have = false;
     hipEvent_t ev[10]; bool have_ev = false;
     svx_text_gz_stats stats;
@@ -92,7 +92,7 @@ extern "C" int svx_text_gz(svx_ctx* c, int source, const uint8_t* host_text, con
     if (!c->textgz) { c->textgz = new TextGzState(); memset(&c->textgz->stats, 0, sizeof c->textgz->stats); }
     TextGzState* S = c->textgz;
     if (!S->have_ev) { for (auto& e : S->ev) HIPCHK(hipEventCreate(&e)); S->have_ev = true; }
-    S->have = false; S->n_bytes = 0; S->n_blocks = 0;
+    S->have = false; S->n_bytes = 0; S->n_blocks = 0; S->gen++;
     memset(&S->stats, 0, sizeof S->stats);
     hipStream_t st = c->stream;
     const uint8_t* text = nullptr;
@@ -231,6 +231,19 @@ extern "C" int svx_text_gz_fetch(svx_ctx* c, int64_t byte_offset, int64_t bytes,
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     return SVX_OK;
+}
+
+bool svx_textgz_view(svx_ctx* c, TextGzView* v) {
+    if (!tgz_valid(c)) return false;
+    TextGzState* S = c->textgz;
+    int64_t n = 0; int32_t nf = 0; const int64_t* off = nullptr;
+    if (S->source == 0) { if (!svx_vcf_text(c, &v->text, &n)) return false; }
+    else if (S->source == 1) { if (!svx_bed_text(c, &v->text, &nf, &off)) return false; }
+    else v->text = S->text.as<uint8_t>();
+    v->n_files = S->n_files; v->n_blocks = S->n_blocks; v->gen = S->gen;
+    v->file_off_text = S->file_off_text.data(); v->file_first_block = S->file_first_block.data();
+    v->h_coff = S->h_coff.data(); v->h_uoff = S->h_uoff.data(); v->d_coff = S->coff.as<int64_t>();
+    return true;
 }
 
 extern "C" int svx_text_gz_get_stats(svx_ctx* c, svx_text_gz_stats* out) {

@@ -1,0 +1,505 @@
+// textindex.hip - the tabix index (.tbi, uncompressed bytes) of every file of the BGZF stream the last svx_text_gz left in the context, built where the text
+// and the block table lie (svx_text_index*, include/svx.h; gfx950).  What an index says: svim_amd/tabix.py; the line parser, the binning and the layout:
+// textindex_core.hpp, the source svx_text_index_host is built from as well.
+// Replaces: tabix / bcftools index after the fact (the reference writes plain text; its users compress and index it).
+// Phases, all on the context's stream; counts cross to the host between them:
+//   lines      line starts counted per 64-byte piece of the text, scanned, written (one table for the three sources; the files' first bytes start lines too)
+//   records    one lane per line: tabs, integers, END=, the virtual offset by a binary search in block_uoff; only the head of a long line is read.
+//              Lines that are skipped ('#', empty) are compacted away by a scan
+//   contigs    run heads where column 1 differs from the record before (or the file does); chunk heads where the bin does too; the order and range checks
+//              raise per-file flags; the run-head names go to the host, which looks for a name with two runs and settles every file's status
+//   chunks     (contig << 32 | bin, chunk) sorted stably (svx_sort_pairs_u64), bin heads and contig heads of the sorted list compacted
+//   linear     a record's windows get atomicMin(vbeg): its own lane for one window, the whole wave for a record of many (an inversion over a contig has 32 768)
+//   serialise  sizes per contig, a scan, the headers and names written by the host, then one lane per chunk and one wave per contig store every field at its
+//              offset; the wave's backward fill of the empty slots is a reverse scan in tiles of 64.
+// A file whose status is not 0 gets no bytes; its records still pass through the kernels (their sizes count as 0).  Every store into the index is checked
+// against the index's size: a layout that disagrees with its sizes is SVX_E_STATE, not a write somewhere else.
+#include "common.hpp"
+#include "hostcopy.hpp"
+#include "textindex_core.hpp"
+#include <algorithm>
+#include <string>
+#include <unordered_set>
+
+#define XT 256
+#define XGRID(n) (unsigned)(((long long)(n) + XT - 1) / XT)
+#define TIX_PIECE 64
+#define TIX_NPOOL 64
+enum { TIXF_ORDER = 1, TIXF_RANGE = 2 };
+
+struct TixIn {
+    const uint8_t* text; long long n_text; int n_files; long long n_blocks; int preset;
+    const int64_t *fo, *ffb, *coff, *uoff, *sbase; const uint64_t* eofv;      // per file: text offsets, first block, stream base, where the last line ends
+    int* fflag;
+};
+
+// is i the first byte of a line?  kk: a cursor into fo that only moves forward (fo[kk] >= every i asked before)
+__device__ __forceinline__ bool tix_line_start(const TixIn& in, long long i, int& kk) {
+    if (i == 0 || in.text[i - 1] == '\n') return true;
+    while (kk < in.n_files && in.fo[kk] < i) kk++;
+    return in.fo[kk] == i;
+}
+__device__ __forceinline__ int tix_first_file_at(const TixIn& in, long long i) {      // first k with fo[k] >= i
+    int lo = 0, hi = in.n_files;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (in.fo[mid] >= i) hi = mid; else lo = mid + 1; }
+    return lo;
+}
+__global__ void k_tix_line_count(TixIn in, long long n_pieces, int32_t* cnt) {
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > n_pieces) return;
+    if (c == n_pieces) { cnt[c] = 0; return; }
+    const long long lo = c * TIX_PIECE, hi = lo + TIX_PIECE < in.n_text ? lo + TIX_PIECE : in.n_text;
+    int kk = tix_first_file_at(in, lo), n = 0;
+    for (long long i = lo; i < hi; i++) n += tix_line_start(in, i, kk) ? 1 : 0;
+    cnt[c] = n;
+}
+__global__ void k_tix_line_write(TixIn in, long long n_pieces, const int64_t* lpos, long long n_lines, int64_t* line) {
+    const long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_pieces) return;
+    const long long lo = c * TIX_PIECE, hi = lo + TIX_PIECE < in.n_text ? lo + TIX_PIECE : in.n_text;
+    int kk = tix_first_file_at(in, lo);
+    long long at = lpos[c];
+    for (long long i = lo; i < hi; i++) if (tix_line_start(in, i, kk)) { if (at < n_lines) line[at] = i; at++; }
+}
+struct TixLines { int64_t *beg, *end; uint64_t* vbeg; int32_t *name_len, *file, *isrec; };
+__global__ void k_tix_parse(TixIn in, long long n_lines, const int64_t* line, TixLines o) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n_lines) return;
+    if (i == n_lines) { o.isrec[i] = 0; return; }
+    const long long s = line[i];
+    int lo = 0, hi = in.n_files - 1;                     // the file: first k with fo[k + 1] > s
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (in.fo[mid + 1] > s) hi = mid; else lo = mid + 1; }
+    const int k = lo;
+    long long e = i + 1 < n_lines ? line[i + 1] : in.n_text;
+    if (e > in.fo[k + 1]) e = in.fo[k + 1];
+    const TixLine L = tix_parse_line(in.text, s, e, in.preset);
+    o.beg[i] = L.beg; o.end[i] = L.end; o.name_len[i] = L.name_len; o.file[i] = k; o.isrec[i] = L.skip ? 0 : 1;
+    o.vbeg[i] = tix_voff(s, in.coff, in.uoff, in.ffb[k], in.ffb[k + 1], in.coff[in.ffb[k]], in.sbase[k]);
+    if (!L.skip && L.end > TIX_MAX_END) atomicOr(in.fflag + k, TIXF_RANGE);
+}
+__global__ void k_tix_compact_records(long long n_lines, const int32_t* isrec, const int64_t* rpos, long long n_rec, uint32_t* r_line) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_lines && isrec[i] && rpos[i] < n_rec) r_line[rpos[i]] = (uint32_t)i;
+}
+__device__ __forceinline__ uint32_t tix_bin_of(const TixLines& L, long long i) { return L.end[i] <= TIX_MAX_END ? tix_reg2bin(L.beg[i], L.end[i]) : 0u; }
+// contig run heads, chunk heads, the order check
+__global__ void k_tix_heads(TixIn in, long long n_rec, const uint32_t* r_line, const int64_t* line, TixLines L, int32_t* chead, int32_t* bhead) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n_rec) return;
+    if (j == n_rec) { chead[j] = 0; bhead[j] = 0; return; }
+    const long long i = r_line[j];
+    bool ch = j == 0;
+    long long ip = 0;
+    if (!ch) {
+        ip = r_line[j - 1];
+        ch = L.file[ip] != L.file[i] || L.name_len[ip] != L.name_len[i];
+        if (!ch) {
+            const uint8_t *a = in.text + line[i], *b = in.text + line[ip];
+            for (int k = 0, n = L.name_len[i]; k < n; k++) if (a[k] != b[k]) { ch = true; break; }
+        }
+        if (!ch && L.beg[i] < L.beg[ip]) atomicOr(in.fflag + L.file[i], TIXF_ORDER);
+    }
+    chead[j] = ch ? 1 : 0;
+    bhead[j] = (ch || tix_bin_of(L, i) != tix_bin_of(L, ip)) ? 1 : 0;
+}
+struct TixRuns { uint32_t* run_rec; int32_t *run_file, *run_nlen; uint32_t* chunk_rec; uint64_t* chunk_key; uint32_t* chunk_val; };
+__global__ void k_tix_runs(long long n_rec, long long n_runs, long long n_chunks, const uint32_t* r_line, TixLines L, const int32_t* chead, const int32_t* bhead, const int64_t* cpos,
+                           const int64_t* bpos, TixRuns o) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n_rec) return;
+    if (j == n_rec) { o.run_rec[n_runs] = (uint32_t)n_rec; o.run_nlen[n_runs] = 0; o.run_file[n_runs] = 0; o.chunk_rec[n_chunks] = (uint32_t)n_rec; return; }
+    const long long i = r_line[j];
+    const long long t = cpos[j] + chead[j] - 1;                 // the run j lies in
+    if (chead[j] && t < n_runs) { o.run_rec[t] = (uint32_t)j; o.run_file[t] = L.file[i]; o.run_nlen[t] = L.name_len[i] + 1; }
+    const long long q = bpos[j];
+    if (bhead[j] && q < n_chunks) { o.chunk_rec[q] = (uint32_t)j; o.chunk_key[q] = ((uint64_t)t << 32) | tix_bin_of(L, i); o.chunk_val[q] = (uint32_t)q; }
+}
+__global__ void k_tix_names(long long n_runs, const uint8_t* text, const int64_t* line, const uint32_t* r_line, const uint32_t* run_rec, const int32_t* run_nlen, const int64_t* nm_off,
+                            long long n_names, uint8_t* names) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_runs) return;
+    const uint8_t* src = text + line[r_line[run_rec[t]]];
+    const long long at = nm_off[t]; const int n = run_nlen[t] - 1;
+    if (at < 0 || at + n + 1 > n_names) return;
+    for (int k = 0; k < n; k++) names[at + k] = src[k];
+    names[at + n] = 0;
+}
+// the sorted chunk list: bin heads, and per contig its first bin
+__global__ void k_tix_bin_heads(long long n_chunks, const uint64_t* key, int32_t* bh) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > n_chunks) return;
+    bh[p] = p < n_chunks && (p == 0 || key[p] != key[p - 1]) ? 1 : 0;
+}
+__global__ void k_tix_bins(long long n_chunks, long long n_bins, long long n_runs, const uint64_t* key, const int32_t* bh, const int64_t* binpos, uint32_t* bin_first, uint32_t* tid_first_bin) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > n_chunks) return;
+    if (p == n_chunks) { bin_first[n_bins] = (uint32_t)n_chunks; tid_first_bin[n_runs] = (uint32_t)n_bins; return; }
+    if (!bh[p]) return;
+    const long long q = binpos[p];
+    if (q < n_bins) bin_first[q] = (uint32_t)p;
+    const long long t = (long long)(key[p] >> 32);
+    if ((p == 0 || (key[p - 1] >> 32) != (key[p] >> 32)) && t < n_runs) tid_first_bin[t] = (uint32_t)q;
+}
+__global__ void k_tix_max_end(long long n_rec, const uint32_t* r_line, TixLines L, const int32_t* chead, const int64_t* cpos, const int32_t* fstat, int32_t* tmax) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_rec) return;
+    const long long i = r_line[j];
+    if (fstat[L.file[i]] != 0) return;
+    atomicMax(tmax + (cpos[j] + chead[j] - 1), (int32_t)L.end[i]);          // (end <= 2^29 in a file whose status is 0)
+}
+__global__ void k_tix_sizes(long long n_runs, const int32_t* run_file, const int32_t* fstat, const int32_t* tmax, const uint32_t* tid_first_bin, const uint32_t* bin_first,
+                            int64_t* tsz, int64_t* nintv) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t > n_runs) return;
+    if (t == n_runs || fstat[run_file[t]] != 0) { tsz[t] = 0; nintv[t] = 0; return; }
+    const long long ni = 1 + (((long long)tmax[t] - 1) >> 14);
+    const uint32_t b0 = tid_first_bin[t], b1 = tid_first_bin[t + 1];
+    tsz[t] = tix_contig_bytes((long long)b1 - b0, (long long)bin_first[b1] - bin_first[b0], ni);
+    nintv[t] = ni;
+}
+__global__ __launch_bounds__(XT) void k_tix_linear(long long n_rec, const uint32_t* r_line, TixLines L, const int32_t* chead, const int64_t* cpos, const int32_t* fstat,
+                                                   const int64_t* loff, long long n_slots, unsigned long long* lin) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    long long w0 = 0, w1 = -1, base = 0; unsigned long long v = 0;
+    if (j < n_rec) {
+        const long long i = r_line[j];
+        if (fstat[L.file[i]] == 0) {
+            const long long t = cpos[j] + chead[j] - 1;
+            base = loff[t]; w0 = L.beg[i] >> 14; w1 = (L.end[i] - 1) >> 14; v = L.vbeg[i];
+            if (base + w1 >= n_slots || base + w1 >= loff[t + 1]) w1 = w0 - 1;       // (cannot happen: the slots were sized by the largest end)
+        }
+    }
+    if (w1 == w0) atomicMin(lin + base + w0, v);
+    unsigned long long many = __ballot(w1 > w0);
+    while (many) {                                           // a record of many windows: the wave writes them, 64 at a time
+        const int src = __ffsll((long long)many) - 1;
+        many &= many - 1;
+        const long long b = __shfl(base, src, 64), lo = __shfl(w0, src, 64), hi = __shfl(w1, src, 64);
+        const unsigned long long vv = __shfl(v, src, 64);
+        for (long long w = lo + lane_id(); w <= hi; w += 64) atomicMin(lin + b + w, vv);
+    }
+}
+struct TixOut { uint8_t* blob; long long n_blob; int* err; const int64_t *toff, *shift; const int32_t *run_file, *fstat; };
+__device__ __forceinline__ uint8_t* tix_at(const TixOut& o, long long off, long long len) {
+    if (off < 0 || off + len > o.n_blob) { atomicOr(o.err, 1); return nullptr; }
+    return o.blob + off;
+}
+__global__ void k_tix_ser_chunks(long long n_chunks, const uint64_t* key, const uint32_t* val, const int32_t* bh, const int64_t* binpos, const uint32_t* bin_first,
+                                 const uint32_t* tid_first_bin, const uint32_t* chunk_rec, const uint32_t* r_line, TixLines L, long long n_lines, const uint64_t* eofv, TixOut o) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_chunks) return;
+    const long long t = (long long)(key[p] >> 32);
+    const int f = o.run_file[t];
+    if (o.fstat[f] != 0) return;
+    const long long base = o.toff[t] + o.shift[f];
+    const long long q = binpos[p] + bh[p] - 1, fb = tid_first_bin[t];
+    const long long at = base + 4 + 8 * (q - fb) + 16 * ((long long)bin_first[q] - bin_first[fb]);
+    if (bh[p]) {
+        uint8_t* d = tix_at(o, at, 8);
+        if (d) { tix_put32(d, (uint32_t)key[p]); tix_put32(d + 4, bin_first[q + 1] - bin_first[q]); }
+    }
+    const uint32_t cq = val[p];
+    const long long i0 = r_line[chunk_rec[cq]], i1 = r_line[chunk_rec[cq + 1] - 1];
+    const uint64_t vend = (i1 + 1 < n_lines && L.file[i1 + 1] == f) ? L.vbeg[i1 + 1] : eofv[f];
+    uint8_t* d = tix_at(o, at + 8 + 16 * (p - (long long)bin_first[q]), 16);
+    if (d) { tix_put64(d, L.vbeg[i0]); tix_put64(d + 8, vend); }
+}
+// one wave per contig: n_bin, the pseudo-bin, n_intv, the linear index with its empty slots filled from behind
+__global__ __launch_bounds__(64) void k_tix_ser_contig(long long n_runs, const uint32_t* run_rec, const uint32_t* tid_first_bin, const uint32_t* bin_first, const uint32_t* r_line,
+                                                       TixLines L, long long n_lines, const uint64_t* eofv, const int64_t* loff, const unsigned long long* lin, TixOut o) {
+    const long long t = blockIdx.x;
+    if (t >= n_runs) return;
+    const int f = o.run_file[t];
+    if (o.fstat[f] != 0) return;
+    const long long base = o.toff[t] + o.shift[f];
+    const long long nb = (long long)tid_first_bin[t + 1] - tid_first_bin[t], nc = (long long)bin_first[tid_first_bin[t + 1]] - bin_first[tid_first_bin[t]];
+    const long long ni = loff[t + 1] - loff[t];
+    const long long ps = base + 4 + 8 * nb + 16 * nc;
+    if (lane_id() == 0) {
+        const long long j0 = run_rec[t], j1 = (long long)run_rec[t + 1] - 1;
+        const long long i0 = r_line[j0], i1 = r_line[j1];
+        const uint64_t vend = (i1 + 1 < n_lines && L.file[i1 + 1] == f) ? L.vbeg[i1 + 1] : eofv[f];
+        uint8_t* d = tix_at(o, base, 4);
+        if (d) tix_put32(d, (uint32_t)(nb + 1));
+        d = tix_at(o, ps, 44);
+        if (d) {
+            tix_put32(d, TIX_PSEUDO_BIN); tix_put32(d + 4, 2u); tix_put64(d + 8, L.vbeg[i0]); tix_put64(d + 16, vend);
+            tix_put64(d + 24, (uint64_t)(j1 - j0 + 1)); tix_put64(d + 32, 0ull); tix_put32(d + 40, (uint32_t)ni);
+        }
+    }
+    unsigned long long carry = TIX_NO_SLOT;
+    for (long long top = ni - 1; top >= 0; top -= 64) {                 // lane l holds window top - l: a prefix minimum over the lanes is a suffix minimum over the windows
+        const long long w = top - lane_id();
+        unsigned long long v = w >= 0 ? lin[loff[t] + w] : TIX_NO_SLOT;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) { const unsigned long long u = __shfl_up(v, s, 64); if (lane_id() >= s && u < v) v = u; }
+        if (carry < v) v = carry;
+        if (w >= 0) { uint8_t* d = tix_at(o, ps + 44 + 8 * w, 8); if (d) tix_put64(d, v); }
+        carry = __shfl(v, 63, 64);
+    }
+}
+
+struct TextIndexState {
+    DevBuf pool[TIX_NPOOL]; int used = 0;
+    DevBuf blob;
+    std::vector<int64_t> file_off; std::vector<int32_t> status;
+    long long gz_gen = -1; bool have = false;
+    hipEvent_t ev[8]; bool have_ev = false;
+    svx_text_index_stats stats;
+    template <class Tp> int get(Tp** o, size_t count) {
+        if (used >= TIX_NPOOL) return svx_fail(SVX_E_CAPACITY, "text index: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
+        SVXCHK(pool[used].reserve((count ? count : 1) * sizeof(Tp) + 64));
+        *o = pool[used++].as<Tp>();
+        return SVX_OK;
+    }
+};
+void svx_textindex_release(svx_ctx* c) {
+    TextIndexState* s = c->textindex;
+    if (!s) return;
+    for (auto& b : s->pool) b.release();
+    s->blob.release();
+    if (s->have_ev) for (auto& e : s->ev) (void)hipEventDestroy(e);
+    delete s;
+    c->textindex = nullptr;
+}
+static int tix_ceil_log2(long long n) { int b = 0; while ((1ll << b) < n) b++; return b; }
+static bool tix_valid(svx_ctx* c, TextGzView* v) {
+    return c && c->textindex && c->textindex->have && svx_textgz_view(c, v) && v->gen == c->textindex->gz_gen;
+}
+
+extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base) {
+    if (!c || (preset != SVX_INDEX_VCF && preset != SVX_INDEX_BED)) return svx_fail(SVX_E_ARG, "svx_text_index: bad argument (preset SVX_INDEX_VCF or SVX_INDEX_BED)", __FILE__, __LINE__, hipSuccess);
+    HIPCHK(hipSetDevice(c->device));
+    TextGzView V;
+    if (!svx_textgz_view(c, &V)) return svx_fail(SVX_E_STATE, "svx_text_index: no BGZF stream: run svx_text_gz first (a later svx_vcf / svx_bed voids the stream of its text)", __FILE__, __LINE__, hipSuccess);
+    if (!c->textindex) { c->textindex = new TextIndexState(); }
+    TextIndexState* S = c->textindex;
+    if (!S->have_ev) { for (auto& e : S->ev) HIPCHK(hipEventCreate(&e)); S->have_ev = true; }
+    S->used = 0; S->have = false;
+    memset(&S->stats, 0, sizeof S->stats);
+    hipStream_t st = c->stream;
+    const int nf = V.n_files; const long long nb = V.n_blocks, n_text = V.file_off_text[nf];
+    for (int k = 0; k < nf; k++) if (stream_base && stream_base[k] < 0) return svx_fail(SVX_E_ARG, "svx_text_index: negative stream_base", __FILE__, __LINE__, hipSuccess);
+    if (n_text >= (1ll << 40)) return svx_fail(SVX_E_CAPACITY, "svx_text_index: text too large", __FILE__, __LINE__, hipSuccess);
+    HIPCHK(hipEventRecord(S->ev[0], st));
+    // ---- what the kernels know about the files ----
+    std::vector<int64_t> sbase((size_t)nf, 0); std::vector<uint64_t> eofv((size_t)nf, 0);
+    for (int k = 0; k < nf; k++) {
+        if (stream_base) sbase[k] = stream_base[k];
+        eofv[k] = (uint64_t)(sbase[k] + V.h_coff[V.file_first_block[k + 1] - 1] - V.h_coff[V.file_first_block[k]]) << 16;
+    }
+    TixIn in; memset(&in, 0, sizeof in);
+    in.text = V.text; in.n_text = n_text; in.n_files = nf; in.n_blocks = nb; in.preset = preset; in.coff = V.d_coff;
+    int32_t* fstat_d; int* err_d;
+    {
+        int64_t *fo, *ffb, *uoff, *sb; uint64_t* ev;
+        SVXCHK(S->get(&fo, (size_t)nf + 1)); SVXCHK(S->get(&ffb, (size_t)nf + 1)); SVXCHK(S->get(&uoff, (size_t)nb + 1)); SVXCHK(S->get(&sb, (size_t)nf)); SVXCHK(S->get(&ev, (size_t)nf));
+        SVXCHK(S->get(&in.fflag, (size_t)nf)); SVXCHK(S->get(&fstat_d, (size_t)nf)); SVXCHK(S->get(&err_d, 2));
+        HostCopy hc(st);
+        SVXCHK(hc.h2d(fo, V.file_off_text, ((size_t)nf + 1) * 8)); SVXCHK(hc.h2d(ffb, V.file_first_block, ((size_t)nf + 1) * 8)); SVXCHK(hc.h2d(uoff, V.h_uoff, ((size_t)nb + 1) * 8));
+        SVXCHK(hc.h2d(sb, sbase.data(), (size_t)nf * 8)); SVXCHK(hc.h2d(ev, eofv.data(), (size_t)nf * 8));
+        SVXCHK(hc.finish());
+        in.fo = fo; in.ffb = ffb; in.uoff = uoff; in.sbase = sb; in.eofv = ev;
+        HIPCHK(hipMemsetAsync(in.fflag, 0, (size_t)nf * 4, st)); HIPCHK(hipMemsetAsync(err_d, 0, 8, st));
+    }
+    // ---- lines ----
+    const long long n_pieces = (n_text + TIX_PIECE - 1) / TIX_PIECE;
+    int64_t n_lines = 0;
+    int64_t* line = nullptr;
+    if (n_pieces > 0) {
+        int32_t* cnt; int64_t* lpos;
+        SVXCHK(S->get(&cnt, (size_t)n_pieces + 1)); SVXCHK(S->get(&lpos, (size_t)n_pieces + 1));
+        k_tix_line_count<<<XGRID(n_pieces + 1), XT, 0, st>>>(in, n_pieces, cnt);
+        SVXCHK(svx_exclusive_scan_i32_to_i64(c, cnt, lpos, n_pieces + 1));
+        SVXCHK(svx_d2h(&n_lines, lpos + n_pieces, 8, st));
+        if (n_lines < 0 || n_lines > n_text || n_lines >= (1ll << 31)) return svx_fail(SVX_E_CAPACITY, "svx_text_index: too many lines", __FILE__, __LINE__, hipSuccess);
+        SVXCHK(S->get(&line, (size_t)n_lines + 1));
+        if (n_lines) k_tix_line_write<<<XGRID(n_pieces), XT, 0, st>>>(in, n_pieces, lpos, n_lines, line);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(S->ev[1], st));
+    // ---- records ----
+    TixLines L; memset(&L, 0, sizeof L);
+    int64_t n_rec = 0; uint32_t* r_line = nullptr;
+    if (n_lines > 0) {
+        int64_t* rpos;
+        SVXCHK(S->get(&L.beg, (size_t)n_lines)); SVXCHK(S->get(&L.end, (size_t)n_lines)); SVXCHK(S->get(&L.vbeg, (size_t)n_lines)); SVXCHK(S->get(&L.name_len, (size_t)n_lines));
+        SVXCHK(S->get(&L.file, (size_t)n_lines)); SVXCHK(S->get(&L.isrec, (size_t)n_lines + 1)); SVXCHK(S->get(&rpos, (size_t)n_lines + 1));
+        k_tix_parse<<<XGRID(n_lines + 1), XT, 0, st>>>(in, n_lines, line, L);
+        SVXCHK(svx_exclusive_scan_i32_to_i64(c, L.isrec, rpos, n_lines + 1));
+        SVXCHK(svx_d2h(&n_rec, rpos + n_lines, 8, st));
+        if (n_rec < 0 || n_rec > n_lines) return svx_fail(SVX_E_STATE, "svx_text_index: the record count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+        SVXCHK(S->get(&r_line, (size_t)n_rec + 1));
+        if (n_rec) k_tix_compact_records<<<XGRID(n_lines), XT, 0, st>>>(n_lines, L.isrec, rpos, n_rec, r_line);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(S->ev[2], st));
+    // ---- contig runs and chunks; the status of every file ----
+    int64_t n_runs = 0, n_chunks = 0, n_names = 0;
+    std::vector<int32_t> fflag((size_t)nf, 0), run_file_h;
+    std::vector<int64_t> nm_off_h; std::vector<uint8_t> names_h;
+    int32_t *chead = nullptr, *bhead = nullptr; int64_t *cpos = nullptr, *bpos = nullptr, *nm_off = nullptr; uint8_t* names = nullptr;
+    TixRuns R; memset(&R, 0, sizeof R);
+    if (n_rec > 0) {
+        SVXCHK(S->get(&chead, (size_t)n_rec + 1)); SVXCHK(S->get(&bhead, (size_t)n_rec + 1)); SVXCHK(S->get(&cpos, (size_t)n_rec + 1)); SVXCHK(S->get(&bpos, (size_t)n_rec + 1));
+        k_tix_heads<<<XGRID(n_rec + 1), XT, 0, st>>>(in, n_rec, r_line, line, L, chead, bhead);
+        SVXCHK(svx_exclusive_scan_i32_to_i64(c, chead, cpos, n_rec + 1));
+        SVXCHK(svx_exclusive_scan_i32_to_i64(c, bhead, bpos, n_rec + 1));
+        {
+            HostCopy hc(st);
+            SVXCHK(hc.d2h(&n_runs, cpos + n_rec, 8)); SVXCHK(hc.d2h(&n_chunks, bpos + n_rec, 8)); SVXCHK(hc.d2h(fflag.data(), in.fflag, (size_t)nf * 4));
+            SVXCHK(hc.finish());
+        }
+        if (n_runs < 1 || n_runs > n_rec || n_chunks < n_runs || n_chunks > n_rec) return svx_fail(SVX_E_STATE, "svx_text_index: the run counts are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+        SVXCHK(S->get(&R.run_rec, (size_t)n_runs + 1)); SVXCHK(S->get(&R.run_file, (size_t)n_runs + 1)); SVXCHK(S->get(&R.run_nlen, (size_t)n_runs + 1));
+        SVXCHK(S->get(&R.chunk_rec, (size_t)n_chunks + 1)); SVXCHK(S->get(&R.chunk_key, (size_t)n_chunks)); SVXCHK(S->get(&R.chunk_val, (size_t)n_chunks));
+        SVXCHK(S->get(&nm_off, (size_t)n_runs + 1));
+        k_tix_runs<<<XGRID(n_rec + 1), XT, 0, st>>>(n_rec, n_runs, n_chunks, r_line, L, chead, bhead, cpos, bpos, R);
+        SVXCHK(svx_exclusive_scan_i32_to_i64(c, R.run_nlen, nm_off, n_runs + 1));
+        run_file_h.assign((size_t)n_runs + 1, 0); nm_off_h.assign((size_t)n_runs + 1, 0);
+        {
+            HostCopy hc(st);
+            SVXCHK(hc.d2h(nm_off_h.data(), nm_off, ((size_t)n_runs + 1) * 8)); SVXCHK(hc.d2h(run_file_h.data(), R.run_file, ((size_t)n_runs + 1) * 4));
+            SVXCHK(hc.finish());
+        }
+        n_names = nm_off_h[(size_t)n_runs];
+        if (n_names < n_runs || n_names > n_text + n_runs) return svx_fail(SVX_E_STATE, "svx_text_index: the name lengths are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+        SVXCHK(S->get(&names, (size_t)n_names));
+        k_tix_names<<<XGRID(n_runs), XT, 0, st>>>(n_runs, in.text, line, r_line, R.run_rec, R.run_nlen, nm_off, n_names, names);
+        HIPCHK(hipGetLastError());
+        names_h.assign((size_t)n_names, 0);
+        SVXCHK(svx_d2h(names_h.data(), names, (size_t)n_names, st));
+    }
+    std::vector<int32_t>& status = S->status;
+    status.assign((size_t)nf, 0);
+    std::vector<int64_t> first_run((size_t)nf + 1, n_runs);       // the runs of file k: [first_run[k], first_run[k + 1])
+    {
+        std::unordered_set<std::string> seen; int cur = -1;
+        for (int64_t t = 0; t < n_runs; t++) {
+            const int f = run_file_h[(size_t)t];
+            if (f < cur || f >= nf) return svx_fail(SVX_E_STATE, "svx_text_index: the runs are not in file order (internal error)", __FILE__, __LINE__, hipSuccess);
+            if (f != cur) { for (int k = cur + 1; k <= f; k++) first_run[(size_t)k] = t; cur = f; seen.clear(); }
+            if (!seen.insert(std::string((const char*)names_h.data() + nm_off_h[(size_t)t], (size_t)(nm_off_h[(size_t)t + 1] - nm_off_h[(size_t)t] - 1))).second) fflag[(size_t)f] |= TIXF_ORDER;
+        }
+        for (int k = 0; k < nf; k++) status[(size_t)k] = (fflag[(size_t)k] & TIXF_ORDER) ? SVX_E_ORDER : (fflag[(size_t)k] & TIXF_RANGE) ? SVX_E_RANGE : 0;
+    }
+    SVXCHK(svx_h2d(fstat_d, status.data(), (size_t)nf * 4, st));
+    HIPCHK(hipEventRecord(S->ev[3], st));
+    // ---- chunks sorted by (contig, bin); bins ----
+    int64_t n_bins = 0, n_slots = 0;
+    uint64_t* key2 = nullptr; uint32_t *val2 = nullptr, *bin_first = nullptr, *tid_first_bin = nullptr; int32_t *bh = nullptr, *tmax = nullptr; int64_t *binpos = nullptr, *tsz = nullptr, *nintv = nullptr,
+              *toff = nullptr, *loff = nullptr;
+    std::vector<int64_t> toff_h((size_t)n_runs + 1, 0);
+    if (n_rec > 0) {
+        SVXCHK(S->get(&key2, (size_t)n_chunks)); SVXCHK(S->get(&val2, (size_t)n_chunks)); SVXCHK(S->get(&bh, (size_t)n_chunks + 1)); SVXCHK(S->get(&binpos, (size_t)n_chunks + 1));
+        SVXCHK(svx_sort_pairs_u64(c, R.chunk_key, key2, R.chunk_val, val2, n_chunks, 0, std::min(64, 32 + std::max(1, tix_ceil_log2(n_runs + 1)))));
+        k_tix_bin_heads<<<XGRID(n_chunks + 1), XT, 0, st>>>(n_chunks, key2, bh);
+        SVXCHK(svx_exclusive_scan_i32_to_i64(c, bh, binpos, n_chunks + 1));
+        SVXCHK(svx_d2h(&n_bins, binpos + n_chunks, 8, st));
+        if (n_bins < n_runs || n_bins > n_chunks) return svx_fail(SVX_E_STATE, "svx_text_index: the bin count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+        SVXCHK(S->get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->get(&tid_first_bin, (size_t)n_runs + 1)); SVXCHK(S->get(&tmax, (size_t)n_runs + 1));
+        SVXCHK(S->get(&tsz, (size_t)n_runs + 1)); SVXCHK(S->get(&nintv, (size_t)n_runs + 1)); SVXCHK(S->get(&toff, (size_t)n_runs + 2)); SVXCHK(S->get(&loff, (size_t)n_runs + 2));
+        k_tix_bins<<<XGRID(n_chunks + 1), XT, 0, st>>>(n_chunks, n_bins, n_runs, key2, bh, binpos, bin_first, tid_first_bin);
+        HIPCHK(hipMemsetAsync(tmax, 0, ((size_t)n_runs + 1) * 4, st));
+        k_tix_max_end<<<XGRID(n_rec), XT, 0, st>>>(n_rec, r_line, L, chead, cpos, fstat_d, tmax);
+        k_tix_sizes<<<XGRID(n_runs + 1), XT, 0, st>>>(n_runs, R.run_file, fstat_d, tmax, tid_first_bin, bin_first, tsz, nintv);
+        SVXCHK(svx_exclusive_scan_i64(c, tsz, toff, n_runs + 1));
+        SVXCHK(svx_exclusive_scan_i64(c, nintv, loff, n_runs + 1));
+        HIPCHK(hipGetLastError());
+        {
+            HostCopy hc(st);
+            SVXCHK(hc.d2h(toff_h.data(), toff, ((size_t)n_runs + 1) * 8)); SVXCHK(hc.d2h(&n_slots, loff + n_runs, 8));
+            SVXCHK(hc.finish());
+        }
+        if (n_slots < 0 || n_slots > (int64_t)n_runs * 32768) return svx_fail(SVX_E_STATE, "svx_text_index: the window count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+    }
+    HIPCHK(hipEventRecord(S->ev[4], st));
+    // ---- linear index: the smallest vbeg per window ----
+    unsigned long long* lin = nullptr;
+    if (n_rec > 0) {
+        SVXCHK(S->get(&lin, (size_t)n_slots));
+        if (n_slots) HIPCHK(hipMemsetAsync(lin, 0xff, (size_t)n_slots * 8, st));
+        k_tix_linear<<<XGRID(n_rec), XT, 0, st>>>(n_rec, r_line, L, chead, cpos, fstat_d, loff, n_slots, lin);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(S->ev[5], st));
+    // ---- layout: header, names, the contigs' parts, trailer per file; then every field at its offset ----
+    std::vector<int64_t>& foff = S->file_off;
+    foff.assign((size_t)nf + 1, 0);
+    std::vector<int64_t> shift((size_t)nf, 0);
+    std::vector<std::vector<uint8_t>> heads((size_t)nf);
+    int n_ok = 0;
+    for (int k = 0; k < nf; k++) {
+        foff[(size_t)k + 1] = foff[(size_t)k];
+        if (status[(size_t)k] != 0) continue;
+        n_ok++;
+        const int64_t t0 = first_run[(size_t)k], t1 = first_run[(size_t)k + 1];
+        const int64_t l_nm = n_runs ? nm_off_h[(size_t)t1] - nm_off_h[(size_t)t0] : 0, body = n_runs ? toff_h[(size_t)t1] - toff_h[(size_t)t0] : 0;
+        std::vector<uint8_t>& h = heads[(size_t)k];
+        h.assign((size_t)(TIX_HEADER_BYTES + l_nm), 0);
+        memcpy(h.data(), "TBI\1", 4);
+        const uint32_t w[8] = {(uint32_t)(t1 - t0), preset == SVX_INDEX_BED ? 0x10000u : 2u, 1u, 2u, preset == SVX_INDEX_BED ? 3u : 0u, (uint32_t)'#', 0u, (uint32_t)l_nm};
+        for (int q = 0; q < 8; q++) tix_put32(h.data() + 4 + 4 * q, w[q]);
+        if (l_nm) memcpy(h.data() + TIX_HEADER_BYTES, names_h.data() + nm_off_h[(size_t)t0], (size_t)l_nm);
+        shift[(size_t)k] = foff[(size_t)k] + TIX_HEADER_BYTES + l_nm - (n_runs ? toff_h[(size_t)t0] : 0);
+        foff[(size_t)k + 1] = foff[(size_t)k] + TIX_HEADER_BYTES + l_nm + body + 8;
+    }
+    const int64_t n_blob = foff[(size_t)nf];
+    SVXCHK(S->blob.reserve((size_t)n_blob + 64));
+    uint8_t* blob = S->blob.as<uint8_t>();
+    HIPCHK(hipMemsetAsync(blob, 0, (size_t)n_blob + 64, st));
+    {
+        int64_t* shift_d; SVXCHK(S->get(&shift_d, (size_t)nf));
+        HostCopy hc(st);
+        SVXCHK(hc.h2d(shift_d, shift.data(), (size_t)nf * 8));
+        for (int k = 0; k < nf; k++) if (!heads[(size_t)k].empty()) SVXCHK(hc.h2d(blob + foff[(size_t)k], heads[(size_t)k].data(), heads[(size_t)k].size()));
+        SVXCHK(hc.finish());
+        if (n_rec > 0) {
+            TixOut o; o.blob = blob; o.n_blob = n_blob; o.err = err_d; o.toff = toff; o.shift = shift_d; o.run_file = R.run_file; o.fstat = fstat_d;
+            k_tix_ser_chunks<<<XGRID(n_chunks), XT, 0, st>>>(n_chunks, key2, val2, bh, binpos, bin_first, tid_first_bin, R.chunk_rec, r_line, L, n_lines, in.eofv, o);
+            k_tix_ser_contig<<<(unsigned)n_runs, 64, 0, st>>>(n_runs, R.run_rec, tid_first_bin, bin_first, r_line, L, n_lines, in.eofv, loff, lin, o);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    HIPCHK(hipEventRecord(S->ev[6], st));
+    int errw[2] = {0, 0};
+    SVXCHK(svx_d2h(errw, err_d, 8, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (errw[0]) return svx_fail(SVX_E_STATE, "svx_text_index: a field lay outside the index it was sized for (internal error)", __FILE__, __LINE__, hipSuccess);
+    float ms = 0;
+    double* tp[6] = {&S->stats.t_lines_ms, &S->stats.t_records_ms, &S->stats.t_contigs_ms, &S->stats.t_chunks_ms, &S->stats.t_linear_ms, &S->stats.t_serialise_ms};
+    for (int k = 0; k < 6; k++) { (void)hipEventElapsedTime(&ms, S->ev[k], S->ev[k + 1]); *tp[k] = ms; }
+    (void)hipEventElapsedTime(&ms, S->ev[0], S->ev[6]); S->stats.t_total_ms = ms;
+    S->stats.n_files = nf; S->stats.n_files_indexed = n_ok; S->stats.n_lines = n_lines; S->stats.n_records = n_rec; S->stats.n_contigs = n_runs; S->stats.n_chunks = n_chunks;
+    S->stats.n_bins = n_bins; S->stats.n_slots = n_slots; S->stats.bytes_text = n_text; S->stats.bytes_out = n_blob;
+    S->gz_gen = V.gen; S->have = true;
+    return SVX_OK;
+}
+
+extern "C" int svx_text_index_count(svx_ctx* c, int32_t* n_files, int64_t* n_bytes) {
+    TextGzView V;
+    if (!tix_valid(c, &V)) return svx_fail(SVX_E_STATE, "no index: run svx_text_index after svx_text_gz (the index is void whenever its stream is)", __FILE__, __LINE__, hipSuccess);
+    if (n_files) *n_files = (int32_t)c->textindex->status.size();
+    if (n_bytes) *n_bytes = c->textindex->file_off.back();
+    return SVX_OK;
+}
+
+extern "C" int svx_text_index_fetch(svx_ctx* c, uint8_t* host_dst, int64_t* file_off, int32_t* file_status) {
+    TextGzView V;
+    if (!tix_valid(c, &V)) return svx_fail(SVX_E_STATE, "no index: run svx_text_index after svx_text_gz (the index is void whenever its stream is)", __FILE__, __LINE__, hipSuccess);
+    TextIndexState* S = c->textindex;
+    HIPCHK(hipSetDevice(c->device));
+    if (file_off) memcpy(file_off, S->file_off.data(), S->file_off.size() * 8);
+    if (file_status) memcpy(file_status, S->status.data(), S->status.size() * 4);
+    if (host_dst && S->file_off.back() > 0) {
+        SVXCHK(svx_d2h(host_dst, S->blob.p, (size_t)S->file_off.back(), c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return SVX_OK;
+}
+
+extern "C" int svx_text_index_get_stats(svx_ctx* c, svx_text_index_stats* out) {
+    if (!c || !out) return svx_fail(SVX_E_ARG, "null argument", __FILE__, __LINE__, hipSuccess);
+    if (c->textindex) *out = c->textindex->stats; else memset(out, 0, sizeof *out);
+    return SVX_OK;
+}

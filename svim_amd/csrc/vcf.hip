@@ -45,6 +45,7 @@ struct VcfIn {
     const int32_t* sig_read_id; const int64_t* seq_off; const uint8_t* seq;
     const uint8_t* gt; const int32_t *ref_reads, *alt_reads;
     const char* cname; const int32_t* cname_off; const int32_t* cname_len; const int32_t* crank; int n_contig;
+    const int32_t* cporder;                                   // position order only: a contig's place among the contigs sorted by (natural rank, index)
     const char* rname; const int64_t* rname_off; const int32_t* zmw;
     const int64_t* g_off; const uint8_t* g_codes; int g_n;
     const int64_t *sup_ex, *zmw_ex; const uint8_t* zbad;      // prefix sums of the 'new id' flags over the sorted member list; candidates with an invalid name
@@ -132,6 +133,17 @@ template <class S> __device__ __forceinline__ void put_contig(S& s, const VcfIn&
     for (int k = 0; k < n; k++) s.ch(t[k]);
 }
 
+// CHROM and POS as the line of method `form` for candidate row i prints them
+__device__ __forceinline__ int line_contig(const VcfIn& in, int form, long long i) {
+    return (form == F_INS || form == F_INT_INS || form == F_BND_REV) ? in.contig2[i] : in.contig[i];
+}
+__device__ __forceinline__ long long line_pos(const VcfIn& in, int form, long long i) {
+    const long long s1 = in.start[i], s2 = in.start2[i];
+    if (form == F_DEL) return s1 > 1 ? s1 : 1;
+    if (form == F_INS || form == F_INT_INS) return s2 > 1 ? s2 : 1;
+    if (form == F_BND_REV) return s2 + 1;
+    return s1 + 1;
+}
 // one line.  form: the method (F_*), i: candidate row, k: the line's number among the lines of its label
 template <class S> __device__ __forceinline__ void emit_line(S& s, const VcfIn& in, int form, long long i, long long k) {
     const int c1 = in.contig[i], c2 = in.contig2[i];
@@ -139,15 +151,9 @@ template <class S> __device__ __forceinline__ void emit_line(S& s, const VcfIn& 
     const unsigned aux = in.aux[i];
     const bool seq = in.P.sequence_alleles != 0;
     const long long m_lo = in.member_off[i], m_hi = in.member_off[i + 1];
-    const bool dest = form == F_INS || form == F_INT_INS || form == F_BND_REV;
     // CHROM, POS
-    put_contig(s, in, dest ? c2 : c1); s.ch('\t');
-    long long pos;
-    if (form == F_DEL) pos = s1 > 1 ? s1 : 1;
-    else if (form == F_INS || form == F_INT_INS) pos = s2 > 1 ? s2 : 1;
-    else if (form == F_BND_REV) pos = s2 + 1;
-    else pos = s1 + 1;
-    put_i64(s, pos); s.ch('\t');
+    put_contig(s, in, line_contig(in, form, i)); s.ch('\t');
+    put_i64(s, line_pos(in, form, i)); s.ch('\t');
     // ID
     put_str(s, "svim.");
     put_str(s, form == F_DEL ? "DEL" : form == F_INV ? "INV" : (form == F_INS || form == F_TAN_INS || form == F_INT_INS) ? "INS" : form == F_TAN_DUP ? "DUP_TANDEM"
@@ -281,6 +287,21 @@ __global__ void k_vcf_gather_u64(const uint64_t* src, const uint32_t* perm, uint
 __global__ void k_vcf_label_keys(long long n, const uint32_t* order, const uint8_t* ent_form, uint64_t* key, uint32_t* idx) {
     const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (s < n) { key[s] = (uint64_t)form_label(ent_form[order[s]]); idx[s] = (uint32_t)s; }
+}
+// position order (svx_vcf_position_order): (contig's place << 32 | POS) of the line at sorted position s, and the permutation applied to order and kidx
+__global__ void k_vcf_pos_keys(long long n, const uint32_t* order, const uint32_t* ent_cand, const uint8_t* ent_form, VcfIn in, uint64_t* key, uint32_t* idx) {
+    const long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    const uint32_t e = order[s];
+    const int form = ent_form[e]; const long long i = ent_cand[e];
+    const int c = line_contig(in, form, i);
+    const unsigned place = (c < 0 || c >= in.n_contig) ? 0u : (unsigned)in.cporder[c];       // (k_vcf_entries has raised VERR_INDEX for such a contig)
+    key[s] = ((uint64_t)place << 32) | (uint64_t)((uint32_t)(int32_t)line_pos(in, form, i) ^ 0x80000000u);
+    idx[s] = (uint32_t)s;
+}
+__global__ void k_vcf_permute_lines(long long n, const uint32_t* perm, const uint32_t* order, const int64_t* kidx, uint32_t* order2, int64_t* kidx2) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < n) { order2[p] = order[perm[p]]; kidx2[p] = kidx[perm[p]]; }
 }
 struct LabelBase { long long b[SVX_VCF_NLABEL]; };
 __global__ void k_vcf_label_index(long long n, const uint64_t* key_sorted, const uint32_t* line_of, LabelBase lb, int64_t* kidx) {
@@ -589,6 +610,11 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
         }
         UP(cname, char, ip->contig_names_nul_separated, at); UP(cname_off, int32_t, off.data(), (size_t)nc + 1); UP(cname_len, int32_t, len.data(), (size_t)nc + 1);
         UP(crank, int32_t, ip->contig_natural_rank, (size_t)nc);
+        std::vector<int32_t> by_rank((size_t)nc), place((size_t)nc + 1, 0);
+        for (int k = 0; k < nc; k++) by_rank[k] = k;
+        std::stable_sort(by_rank.begin(), by_rank.end(), [&](int32_t a, int32_t b) { return ip->contig_natural_rank[a] < ip->contig_natural_rank[b]; });
+        for (int k = 0; k < nc; k++) place[by_rank[k]] = k;
+        UP(cporder, int32_t, place.data(), (size_t)nc);
         in.n_contig = nc;
         SVXCHK(hc.finish());               // (the vectors leave scope)
     }
@@ -651,6 +677,15 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     SVXCHK(svx_sort_pairs_u64(c, lab, lab2, idx, v3, ne, 0, 3));
     LabelBase lb; { long long b = 0; for (int k = 0; k < SVX_VCF_NLABEL; k++) { lb.b[k] = b; b += per_label[k]; } }
     k_vcf_label_index<<<VGRID(ne), VT, 0, st>>>(ne, lab2, v3, lb, kidx);
+    if (c->vcf_position_order) {
+        // the ids are given; one more stable pass by (contig, POS) - lines that tie keep the reference's order
+        uint64_t *pk, *pk2; uint32_t *pv, *perm, *order2; int64_t* kidx2;
+        SVXCHK(S->get(&pk, ne)); SVXCHK(S->get(&pk2, ne)); SVXCHK(S->get(&pv, ne)); SVXCHK(S->get(&perm, ne)); SVXCHK(S->get(&order2, ne)); SVXCHK(S->get(&kidx2, ne));
+        k_vcf_pos_keys<<<VGRID(ne), VT, 0, st>>>(ne, order, ent_cand, ent_form, in, pk, pv);
+        SVXCHK(svx_sort_pairs_u64(c, pk, pk2, pv, perm, ne, 0, std::min(64, 32 + std::max(1, ceil_log2((long long)ip->n_contig + 1)))));
+        k_vcf_permute_lines<<<VGRID(ne), VT, 0, st>>>(ne, perm, order, kidx, order2, kidx2);
+        order = order2; kidx = kidx2;
+    }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(S->ev[2], st));
     // ---- 3: distinct reads / zmws per candidate ----
@@ -733,6 +768,12 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
 extern "C" int svx_vcf_use_resident_genotypes(svx_ctx* c, int on) {
     if (!c) return svx_fail(SVX_E_ARG, "null context", __FILE__, __LINE__, hipSuccess);
     c->vcf_resident_gt = on != 0;
+    return SVX_OK;
+}
+
+extern "C" int svx_vcf_position_order(svx_ctx* c, int on) {
+    if (!c) return svx_fail(SVX_E_ARG, "null context", __FILE__, __LINE__, hipSuccess);
+    c->vcf_position_order = on != 0;
     return SVX_OK;
 }
 

@@ -196,13 +196,18 @@ class BamPipeline(object):
         self._genotyped = True
         self.stats["t_genotype_wall"] = time.perf_counter() - t0
 
-    def write_vcf(self, path, version="svim_amd", types_to_output=None):
-        """header + the lines svx_vcf makes of the resident candidates, with the resident genotype columns when genotype() ran -> bytes written"""
+    def write_vcf(self, path, version="svim_amd", types_to_output=None, index=False):
+        """header + the lines svx_vcf makes of the resident candidates, with the resident genotype columns when genotype() ran -> bytes written.
+        index (the path must end in .gz): the lines in position order (svx_vcf_position_order) and path + ".tbi" beside the file, built on the device from
+        the text and the block table of the stream (svx_text_index); SvxError when the text cannot be indexed (a record beyond 2^29)"""
         from . import SVIM_COMBINE as K
         o = self.options
         types = types_to_output if types_to_output is not None else [t.strip() for t in str(getattr(o, "types", "DEL,INS,INV,DUP:TANDEM,DUP:INT,BND")).split(",")]
         sequence_alleles = not getattr(o, "symbolic_alleles", True)
+        if index and not str(path).endswith(".gz"):
+            raise ValueError("write_vcf: index=True needs a path that ends in .gz (a tabix index belongs to a BGZF file)")
         vp = _abi.VcfParams.from_options(o, types, sequence_alleles)
+        vp.position_order = bool(vp.position_order or index)
         names = self.bam.read_names() if (vp.read_names or vp.zmws) else None
         t0 = time.perf_counter()
         _, n_bytes = self.eng.vcf(vp, self.bam.references, read_names=names, resident_genotypes=getattr(self, "_genotyped", False))
@@ -211,8 +216,16 @@ class BamPipeline(object):
             if str(path).endswith(".gz"):
                 # BGZF: the header compressed here, the lines compressed where they lie (svx_text_gz); only the stream crosses to the host
                 self.eng.text_gz(_abi.TEXT_GZ_VCF)
-                out.write(bgzf_blocks(head))
+                head = bgzf_blocks(head)
+                out.write(head)
                 write_text_gz(self.eng, out)
+                if index:
+                    self.eng.text_index(_abi.INDEX_VCF, len(head))
+                    blobs, status = self.eng.text_index_fetch()
+                    if status[0] != 0:
+                        from ._lib import SvxError
+                        raise SvxError("%s cannot be indexed: %s" % (path, _abi.ERRORS.get(int(status[0]), int(status[0]))))
+                    K._write_tbi(str(path) + ".tbi", blobs[0])
             else:
                 out.write(head)
                 for at in range(0, n_bytes, K._VCF_PIECE):
@@ -222,30 +235,41 @@ class BamPipeline(object):
 
     # file -> the sixteen BED / signature-VCF files of the working directory without a Python object: run(), cluster(), write_signature_files(dir, version),
     # combine(), write_candidate_files(dir)
-    def _bed_files(self, product, directory, names, heads=None, compress=False):
+    def _bed_files(self, product, directory, names, heads=None, compress=False, index=None):
         from . import bed
         if getattr(self, "_bed_read_names", None) is None:
             self._bed_read_names = self.bam.read_names()             # uploaded once: the engine knows the list by identity
         os.makedirs(directory, exist_ok=True)
         t0 = time.perf_counter()
         _, _, n_bytes = self.eng.bed(product, self.bam.references, read_names=self._bed_read_names)
-        bed.write_files(self.eng, directory, names, heads=heads, compress=compress)
+        self._not_indexed += bed.write_files(self.eng, directory, names, heads=heads, compress=compress, index=index)
         self.stats["t_bed_wall"] = self.stats.get("t_bed_wall", 0.0) + time.perf_counter() - t0
         return n_bytes
 
-    def write_signature_files(self, working_dir, version="svim_amd", compress=False):
+    def write_signature_files(self, working_dir, version="svim_amd", compress=False, index=False):
         """<working_dir>/signatures/*.bed and all.vcf of the resident clusters (after cluster()), made by svx_bed -> bytes of text behind the header.
-        compress: the same names with .gz appended, BGZF made on the device (svx_text_gz)"""
+        compress: the same names with .gz appended, BGZF made on the device (svx_text_gz).  index (with compress): a .tbi beside every file whose lines are
+        in an order tabix takes (svx_text_index; the reference's order is not changed) -> (bytes, names of the files that got none, each logged once)"""
         from . import SVIM_CLUSTER as K
+        if index and not compress:
+            raise ValueError("index=True needs compress=True (a tabix index belongs to a BGZF file)")
         d = os.path.join(working_dir, "signatures")
-        n = self._bed_files(_abi.BED_SIGNATURE_BEDS, d, [name for name, _, _ in K._BED_FILES], compress=compress)
-        return n + self._bed_files(_abi.BED_SIGNATURE_VCF, d, ["all.vcf"], heads=[K.vcf_header_text(version).encode("utf-8")], compress=compress)
+        self._not_indexed = []
+        n = self._bed_files(_abi.BED_SIGNATURE_BEDS, d, [name for name, _, _ in K._BED_FILES], compress=compress, index=_abi.INDEX_BED if index else None)
+        n += self._bed_files(_abi.BED_SIGNATURE_VCF, d, ["all.vcf"], heads=[K.vcf_header_text(version).encode("utf-8")], compress=compress, index=_abi.INDEX_VCF if index else None)
+        return (n, list(self._not_indexed)) if index else n
 
-    def write_candidate_files(self, working_dir, compress=False):
+    def write_candidate_files(self, working_dir, compress=False, index=False):
         """<working_dir>/candidates/candidates_*.bed of the resident candidates (after combine()), made by svx_bed -> bytes of text.
-        compress: the same names with .gz appended, BGZF made on the device (svx_text_gz)"""
+        compress: the same names with .gz appended, BGZF made on the device (svx_text_gz).  index (with compress): as write_signature_files has it
+        -> (bytes, names of the files that got no .tbi)"""
         from . import SVIM_COMBINE as K
-        return self._bed_files(_abi.BED_CANDIDATE_BEDS, os.path.join(working_dir, "candidates"), [name for name, _, _ in K._CANDIDATE_BED_FILES], compress=compress)
+        if index and not compress:
+            raise ValueError("index=True needs compress=True (a tabix index belongs to a BGZF file)")
+        self._not_indexed = []
+        n = self._bed_files(_abi.BED_CANDIDATE_BEDS, os.path.join(working_dir, "candidates"), [name for name, _, _ in K._CANDIDATE_BED_FILES], compress=compress,
+                            index=_abi.INDEX_BED if index else None)
+        return (n, list(self._not_indexed)) if index else n
 
     def rewind(self):
         """back to the first record for another pass: buffers, worker threads and read names are kept - the state a long file is in
