@@ -22,8 +22,12 @@ def build():
 def lib():
     global _LIB
     if _LIB is None:
-        path = os.path.join(_HERE, "libsvx_oracle.so")
+        # SVX_ORACLE_LIB: another build of svx_oracle.c to load in place of the one beside this file (tests/test_segments.py checks that the goldens
+        # notice a mutated decision tree); read when the library is opened
+        path = os.environ.get("SVX_ORACLE_LIB") or os.path.join(_HERE, "libsvx_oracle.so")
         if not os.path.exists(path):
+            if os.environ.get("SVX_ORACLE_LIB"):
+                raise OSError("SVX_ORACLE_LIB: no such file: %s" % path)
             build()
         _LIB = C.CDLL(path)
         _LIB.svo_edit_distance.restype = C.c_int32

@@ -135,7 +135,7 @@ def objects_from_sigtable(t, references, read_names):
             objs = map(SignatureInsertionFrom, c1, st, en, refs[t.contig2[idx]].tolist(), t.pos2[idx].tolist(), src, rd)
         else:
             aux = t.aux[idx]
-            objs = map(SignatureTranslocation, c1, st, dirs[aux & 1].tolist(), refs[t.contig2[idx]].tolist(), t.pos2[idx].tolist(),
+            objs = map(SignatureTranslocation.from_canonical, c1, st, dirs[aux & 1].tolist(), refs[t.contig2[idx]].tolist(), t.pos2[idx].tolist(),
                        dirs[(aux >> 1) & 1].tolist(), src, rd)
         for i, o in zip(idx.tolist(), objs):
             out[i] = o
@@ -160,7 +160,7 @@ def object_from_row(t, i, references, read_names):
         return SignatureDuplicationTandem(c, st, en, int(t.pos2[i]), bool(aux & 1), src, read)
     if code == SVX_DUP_INT:
         return SignatureInsertionFrom(c, st, en, references[int(t.contig2[i])], int(t.pos2[i]), src, read)
-    return SignatureTranslocation(c, st, dirs[aux & 1], references[int(t.contig2[i])], int(t.pos2[i]), dirs[(aux >> 1) & 1], src, read)
+    return SignatureTranslocation.from_canonical(c, st, dirs[aux & 1], references[int(t.contig2[i])], int(t.pos2[i]), dirs[(aux >> 1) & 1], src, read)
 
 
 def _none_if_nan(x):

@@ -168,6 +168,17 @@ class SignatureTranslocation(Signature):
         self.signature, self.read = signature, read
         self.type = "BND"
 
+    @classmethod
+    def from_canonical(cls, contig1, pos1, direction1, contig2, pos2, direction2, signature, read):
+        """a breakend whose ends are in canonical order already (a signature table row): stored as given.  The constructor would swap a row whose two ends
+        are the same (contig, position) a second time - the reference swaps such a breakend once (src/svim/SVSignature.py:194-211, strict <)."""
+        self = cls.__new__(cls)
+        self.contig1, self.pos1, self.direction1 = contig1, pos1, direction1
+        self.contig2, self.pos2, self.direction2 = contig2, pos2, direction2
+        self.signature, self.read = signature, read
+        self.type = "BND"
+        return self
+
     def get_source(self):
         return (self.contig1, self.pos1, self.pos1 + 1)
 

@@ -158,7 +158,7 @@ class Case(object):
         A["contig_rank"] = np.array([0, 1], dtype=np.int32)
         return hb
 
-    # the tables of the definition: CIGAR-sourced rows only (what the split-read analysis adds is the oracle's to say)
+    # the tables of the definition: CIGAR-sourced rows only (what the split-read analysis adds is held to the reference by tests/segment_cases.py and its golden)
     def expect_rows(self, min_sv_size=None, all_bnds=False):
         """(main list, side list) as rows (key, type, contig, start, end, contig2, pos2, read_id, inserted bases), in key order"""
         m = self.min_sv_size if min_sv_size is None else min_sv_size
@@ -426,7 +426,8 @@ def insertion_case():
 def segment_cases():
     """rows of 1 .. 514 operations at every residue, every combination of leading / trailing H and S, N inside, stored length 0 and not; primaries that own
     rows (their geometry comes from the scan) next to primaries that do not.  min_sv_size is large: the tables hold what the split-read analysis decides
-    from the geometry, which is the oracle's to say, and the CIGAR-sourced rows of the definition."""
+    from the geometry - compared with the oracle here; the decision tree itself is held to the reference's outputs by tests/segment_cases.py - and the CIGAR-sourced
+    rows of the definition."""
     clips = [[], [w(H, 3)], [w(S, 4)], [w(H, 3), w(S, 4)], [w(S, 4), w(H, 3)], [w(H, 0), w(S, 0)], [w(H, 2), w(H, 1), w(S, 2), w(S, 5)]]
     sizes = (1, 2, 31, 32, 33, 34, 255, 256, 257, 258, 511, 512, 513, 514)
 

@@ -165,6 +165,8 @@ def row_sig(r):
     if t == "DUP_INT":
         return S.SignatureInsertionFrom(r[1], r[2], r[3], r[6], r[7], r[4], r[5])
     if t == "BND":
+        # NOTE: the reference's constructor puts the ends into canonical order; a row whose two ends are the same (contig, position) is swapped AGAIN here
+        # (both directions flip).  No row of the generators has such ends; one that does has to set the attributes after construction.
         return S.SignatureTranslocation(r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8])
     raise ValueError(t)
 

@@ -40,6 +40,9 @@ def row_sig(r):
     if t == "DUP_INT":
         return SignatureInsertionFrom(r[1], r[2], r[3], r[6], r[7], r[4], r[5])
     if t == "BND":
+        # through the constructor, as make_golden.py's row_sig does with the reference's class: some goldens (g_combine) hold rows as they were GIVEN to it, not in
+        # canonical order.  A row that is canonical and has both ends at one (contig, position) would be swapped a second time here (both directions flip): no
+        # golden row that goes this way has such ends; the rows of g_segments_cases that do are compared as rows, never rebuilt
         return SignatureTranslocation(r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8])
     raise ValueError(t)
 
