@@ -677,6 +677,47 @@ int  svx_bam_index_get_stats(svx_bam* h, svx_bam_index_stats* out);
 int  svx_bam_index_host(int32_t n_ref, int64_t n_rows, const int32_t* tid, const int32_t* pos, const int64_t* end, const uint16_t* flag, const uint64_t* vbeg,
                         uint64_t v_end, uint8_t* out, int64_t cap, int64_t* n_out);
 
+/* ---- coordinate sort of the file the device reader is reading (bamsort.hip, bamsort_core.hpp; the definition in words: svim_amd/bamsort.py) ----
+ * The sorted file: the header with SO:coordinate, every record verbatim in the order of (uint32(refID), uint32(pos + 1), flag & 16), equal keys in file order,
+ * cut into BGZF blocks of exactly 65 280 stream bytes plus the end-of-file block, compressed by the encoder of svx_text_gz.
+ * svx_bam_sort_begin switches sorting on for the pass that follows: device decode must be on, the handle at its first record and no index pass on, else
+ * SVX_E_STATE (svx_bam_index_begin during a sort pass is SVX_E_STATE as well).  While it is on, every chunk the reader loads leaves its records' bytes in an
+ * arena on the device (a slab per chunk, never moved) and one row per record - before any filter, whatever max_records, min_mapq and mode the reads use - and
+ * svx_bam_seek / svx_bam_rewind return SVX_E_STATE.  max_bytes: the most the arena may hold (0: whatever the device has free); the svx_bam_read_batch whose
+ * chunk would pass it returns SVX_E_CAPACITY, the sort is dropped and the handle is usable again after svx_bam_rewind.
+ * svx_bam_sort_finish, once svx_bam_read_batch has returned 0 records at the end of the file (SVX_E_STATE before): a stable radix sort of the keys, the offsets
+ * of the records in the output stream.  SVX_E_ARG: a record with refID < -1 or >= n_ref or block_size < 32; SVX_E_RANGE: pos < -1; SVX_E_CAPACITY: more than
+ * 2^32 - 1 records; the sort is dropped then.  The reading pass is over after finish: svx_bam_rewind and svx_bam_seek work again, the sorted records stay.
+ * svx_bam_sort_count: records, bytes of the output stream, BGZF blocks (the end-of-file block included).
+ * svx_bam_sort_encode(first_block, n_blocks): stream bytes [first_block * 65280, ..) gathered into a piece buffer and encoded; *n_bytes = the compressed size.
+ * svx_bam_sort_fetch: the compressed bytes of the last encode, and its uncompressed bytes when stream_dst is not NULL.  Resident are the arena, about 46
+ * bytes per record and one piece; the file is never held twice.
+ * svx_bam_sort_index: the .bai of the sorted file from the sorted rows and the block sizes, read through svx_bam_index_count / svx_bam_index_fetch.
+ * SVX_E_STATE unless every block has been encoded in ascending, gap-free ranges since finish; SVX_E_RANGE: a record ends beyond 2^29.
+ * svx_bam_sort_permutation: perm[i] = the file index of the i-th record of the sorted order (n_records entries).
+ * svx_bam_sort_abort at any point: sorting off, everything dropped; SVX_E_STATE when no sort is on or finished.
+ * With sorting never begun the reader does what it did before these functions existed. */
+typedef struct svx_bam_sort_stats {
+    double  t_append_ms /* slab copies and row kernels, over all chunks */, t_finish_ms, t_sort_ms, t_layout_ms,
+            t_encode_ms /* over all pieces: host clock, the stream drained at each phase */, t_gather_ms, t_crc_ms, t_matches_ms, t_codes_ms, t_bits_ms, t_compaction_ms, t_index_ms;
+    int64_t n_records, n_slabs, arena_bytes, stream_bytes, n_blocks, key_bits, n_pieces, gather_bytes, piece_bytes_max, blocks_stored, blocks_dynamic, blocks_eof, bytes_out;
+} svx_bam_sort_stats;
+int  svx_bam_sort_begin(svx_bam* h, int64_t max_bytes);
+int  svx_bam_sort_finish(svx_bam* h);
+int  svx_bam_sort_abort(svx_bam* h);
+int  svx_bam_sort_count(svx_bam* h, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
+int  svx_bam_sort_encode(svx_bam* h, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
+int  svx_bam_sort_fetch(svx_bam* h, uint8_t* compressed_dst, uint8_t* stream_dst_or_null);
+int  svx_bam_sort_index(svx_bam* h);
+int  svx_bam_sort_permutation(svx_bam* h, uint32_t* perm);
+int  svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out);
+/* host-only, no GPU: records in file order (n_bytes of block_size + body each) -> the sorted record stream (out: n_bytes, may be NULL) and the permutation
+ * (perm: perm_cap entries, may be NULL; n_bytes / 36 + 1 always suffice).  *n_records is set also when perm_cap is too small (SVX_E_CAPACITY).
+ * SVX_E_ARG / SVX_E_RANGE: what the definition refuses (a stream that ends inside a record is SVX_E_ARG). */
+int  svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_t n_ref, uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records);
+/* host-only: the header of the sorted file from a file's header (magic .. reference dictionary).  *n_out is the size also when cap is too small (SVX_E_CAPACITY) */
+int  svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

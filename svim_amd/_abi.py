@@ -16,6 +16,7 @@ ERRORS = {-1: "SVX_E_NODEVICE", -2: "SVX_E_HIP", -3: "SVX_E_ARG", -4: "SVX_E_CAP
           -8: "SVX_E_NO_DELETION", -9: "SVX_E_ORDER", -10: "SVX_E_RANGE"}
 SVX_E_STATE, SVX_E_FASTA_SYMBOL, SVX_E_FASTA_HOST, SVX_E_NO_DELETION = -5, -6, -7, -8
 SVX_E_CAPACITY, SVX_E_ORDER, SVX_E_RANGE = -4, -9, -10
+SVX_E_ARG = -3
 # candidate classes in the order of combine_clusters' return tuple (include/svx.h: SVX_CAND_*)
 CAND_DEL, CAND_INV, CAND_DUP_INT, CAND_DUP_TAN, CAND_INS, CAND_BND = range(6)
 CAND_NAMES = ("DEL", "INV", "DUP_INT", "DUP_TAN", "INS", "BND")
@@ -246,6 +247,16 @@ class GenotypeParams(C.Structure):
     @classmethod
     def from_options(cls, o):
         return cls(float(o.minimum_score), int(o.min_mapq), int(o.minimum_depth), float(o.homozygous_threshold), float(o.heterozygous_threshold))
+
+
+class BamSortStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_append_ms", "t_finish_ms", "t_sort_ms", "t_layout_ms", "t_encode_ms", "t_gather_ms", "t_crc_ms", "t_matches_ms", "t_codes_ms",
+                                          "t_bits_ms", "t_compaction_ms", "t_index_ms")] + \
+               [(n, C.c_int64) for n in ("n_records", "n_slabs", "arena_bytes", "stream_bytes", "n_blocks", "key_bits", "n_pieces", "gather_bytes", "piece_bytes_max",
+                                         "blocks_stored", "blocks_dynamic", "blocks_eof", "bytes_out")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class GenotypeStats(C.Structure):

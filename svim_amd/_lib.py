@@ -34,7 +34,9 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats",
            "svx_text_gz", "svx_text_gz_count", "svx_text_gz_fetch", "svx_text_gz_get_stats", "svx_text_gz_host",
            "svx_vcf_position_order", "svx_text_index", "svx_text_index_count", "svx_text_index_fetch", "svx_text_index_get_stats", "svx_text_index_host",
-           "svx_bam_index_begin", "svx_bam_index_finish", "svx_bam_index_abort", "svx_bam_index_count", "svx_bam_index_fetch", "svx_bam_index_get_stats", "svx_bam_index_host"]
+           "svx_bam_index_begin", "svx_bam_index_finish", "svx_bam_index_abort", "svx_bam_index_count", "svx_bam_index_fetch", "svx_bam_index_get_stats", "svx_bam_index_host",
+           "svx_bam_sort_begin", "svx_bam_sort_finish", "svx_bam_sort_abort", "svx_bam_sort_count", "svx_bam_sort_encode", "svx_bam_sort_fetch", "svx_bam_sort_index",
+           "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host"]
 
 
 class SvxError(RuntimeError):
@@ -183,6 +185,36 @@ def bam_index_host(n_ref, rows, v_end):
         cap = n.value
     if rc != 0:
         raise SvxError("svx_bam_index_host failed: %s" % _abi.ERRORS.get(rc, rc))
+    return out[:n.value].tobytes()
+
+
+def bam_sort_host(records, n_ref):
+    """svx_bam_sort_host (host-only, no GPU needed): records in file order (bytes: block_size + body each) -> (the sorted record stream, the permutation as a
+    uint32 array) by the host build of csrc/bamsort_core.hpp - what NativeBam.sort_finish leaves on the device, and svim_amd.bamsort.sort_records by the
+    definition.  svim_amd.bamsort.BamSortError (code E_ARG / E_RANGE) for a stream the definition refuses."""
+    from . import bamsort
+    records = bytes(records)
+    src = np.frombuffer(records, dtype=np.uint8) if records else np.zeros(1, np.uint8)
+    out = np.zeros(max(1, len(records)), dtype=np.uint8)
+    cap = len(records) // 36 + 1
+    perm, n = np.zeros(cap, dtype=np.uint32), C.c_int64()
+    rc = lib().svx_bam_sort_host(ptr(src), C.c_int64(len(records)), C.c_int32(int(n_ref)), ptr(out), ptr(perm), C.c_int64(cap), C.byref(n))
+    if rc in (_abi.SVX_E_ARG, _abi.SVX_E_RANGE):
+        raise bamsort.BamSortError(rc, "bam_sort_host: " + _abi.ERRORS[rc])
+    if rc != 0:
+        raise SvxError("svx_bam_sort_host failed: %s" % _abi.ERRORS.get(rc, rc))
+    return out[:len(records)].tobytes(), perm[:n.value].copy()
+
+
+def bam_sort_header_host(header):
+    """svx_bam_sort_header_host (host-only): the header of the sorted file, as svim_amd.bamsort.sorted_header defines it"""
+    header = bytes(header)
+    src = np.frombuffer(header, dtype=np.uint8) if header else np.zeros(1, np.uint8)
+    cap = len(header) + 64
+    out, n = np.zeros(cap, dtype=np.uint8), C.c_int64()
+    rc = lib().svx_bam_sort_header_host(ptr(src), C.c_int64(len(header)), ptr(out), C.c_int64(cap), C.byref(n))
+    if rc != 0:
+        raise SvxError("svx_bam_sort_header_host failed: %s" % _abi.ERRORS.get(rc, rc))
     return out[:n.value].tobytes()
 
 

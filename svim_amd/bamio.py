@@ -120,6 +120,79 @@ class NativeBam(object):
         self.L.svx_bam_index_get_stats(self.h, C.byref(s))
         return s.as_dict()
 
+    def sort_begin(self, max_bytes=0):
+        """the pass that follows keeps every record on the device to put the file into coordinate order (svx_bam_sort_begin; svim_amd/bamsort.py says what the
+        sorted file is): device decode must be on, nothing read yet since open / rewind and no index pass on.  max_bytes: the most the records may take on the
+        device (0: what is free); the read that would pass it raises with .code SVX_E_CAPACITY, the sort is dropped and the handle rewinds.  seek() and
+        rewind() raise until sort_finish() or sort_abort()"""
+        rc = self.L.svx_bam_sort_begin(self.h, C.c_int64(int(max_bytes)))
+        if rc != 0:
+            raise self._sort_error(rc, "svx_bam_sort_begin")
+
+    def sort_finish(self):
+        """-> (records, bytes of the sorted stream, BGZF blocks of the sorted file), once read_batch has returned 0 records at the end of the file
+        (svx_bam_sort_finish): the records are sorted and laid out; sort_encode() makes the file, piece by piece"""
+        rc = self.L.svx_bam_sort_finish(self.h)
+        if rc != 0:
+            raise self._sort_error(rc, "svx_bam_sort_finish")
+        return self.sort_count()
+
+    def sort_count(self):
+        n, nbytes, nb = C.c_int64(), C.c_int64(), C.c_int64()
+        rc = self.L.svx_bam_sort_count(self.h, C.byref(n), C.byref(nbytes), C.byref(nb))
+        if rc != 0:
+            raise self._sort_error(rc, "svx_bam_sort_count")
+        return n.value, nbytes.value, nb.value
+
+    def sort_abort(self):
+        """give the sort up at any point (svx_bam_sort_abort): the records on the device are dropped, seek() / rewind() work again"""
+        rc = self.L.svx_bam_sort_abort(self.h)
+        if rc != 0:
+            raise self._sort_error(rc, "svx_bam_sort_abort")
+
+    def sort_encode(self, first_block, n_blocks, stream=False):
+        """blocks [first_block, first_block + n_blocks) of the sorted file (svx_bam_sort_encode / svx_bam_sort_fetch) -> their compressed bytes, or
+        (compressed bytes, their stream bytes) with stream=True.  Ranges go in ascending order without gaps when sort_index() is to follow"""
+        n = C.c_int64()
+        rc = self.L.svx_bam_sort_encode(self.h, C.c_int64(int(first_block)), C.c_int64(int(n_blocks)), C.byref(n))
+        if rc != 0:
+            raise self._sort_error(rc, "svx_bam_sort_encode")
+        out = np.zeros(max(1, n.value), dtype=np.uint8)
+        if stream:
+            total = self.sort_count()[1]
+            nraw = min(total, (int(first_block) + int(n_blocks)) * _abi.TEXT_GZ_BLOCK) - min(total, int(first_block) * _abi.TEXT_GZ_BLOCK)
+            raw = np.zeros(max(1, nraw), dtype=np.uint8)
+        rc = self.L.svx_bam_sort_fetch(self.h, out.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p) if stream else None)
+        if rc != 0:
+            raise self._sort_error(rc, "svx_bam_sort_fetch")
+        return (out[:n.value].tobytes(), raw[:nraw].tobytes()) if stream else out[:n.value].tobytes()
+
+    def sort_index(self):
+        """-> the bytes of the sorted file's .bai, after every block has been encoded (svx_bam_sort_index); svim_amd.bai.BaiError (E_RANGE) when a record
+        ends beyond 2^29"""
+        rc = self.L.svx_bam_sort_index(self.h)
+        if rc != 0:
+            raise (self._index_error if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE) else self._sort_error)(rc, "svx_bam_sort_index")
+        return self.index_bytes()
+
+    def sort_permutation(self):
+        """uint32 array: the file index of every record of the sorted order (svx_bam_sort_permutation)"""
+        n = self.sort_count()[0]
+        perm = np.zeros(max(1, n), dtype=np.uint32)
+        rc = self.L.svx_bam_sort_permutation(self.h, perm.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise self._sort_error(rc, "svx_bam_sort_permutation")
+        return perm[:n]
+
+    def sort_stats(self):
+        s = _abi.BamSortStats()
+        self.L.svx_bam_sort_get_stats(self.h, C.byref(s))
+        return s.as_dict()
+
+    def _sort_error(self, rc, what):
+        from . import bamsort
+        return bamsort.BamSortError(rc, "%s failed: %s (%s)" % (what, _abi.ERRORS.get(rc, rc), self.L.svx_last_error().decode("utf-8", "replace")))
+
     def _error(self, rc, what):
         """the SvxError of a call that returned status rc, the status in its `.code`"""
         e = SvxError("%s failed: %s" % (what, self.L.svx_last_error().decode("utf-8", "replace")))

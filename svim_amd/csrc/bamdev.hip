@@ -12,6 +12,7 @@
 #include "scan.hpp"
 #include "crc32_wave.hpp"
 #include "bamindex.hpp"
+#include "bamsort.hpp"
 #include <zlib.h>
 #include <chrono>
 #include <mutex>
@@ -508,6 +509,7 @@ struct svx_devdec {
     int* h_err = nullptr;                      // pinned (DD_PINNED_BYTES: 64 bytes for h_err, then the DD_H_* values of h_cnt)
     unsigned long long* h_cnt = nullptr;       // pinned: indexed by the DD_H_* slots below, each written by one copy and read after the synchronise that follows it
     BamIndex* index = nullptr; bool index_on = false;      // svx_bam_index_begin: the row table every load appends to (bamindex.hip)
+    BamSort* sort = nullptr; bool sort_on = false;         // svx_bam_sort_begin: the arena and the rows every load appends to (bamsort.hip)
 };
 
 // slots of svx_devdec::h_cnt (pinned read-backs).  The loader thread (devdec_load / devdec_count) and the consumer (devdec_batch) use disjoint slots.
@@ -576,6 +578,7 @@ void devdec_destroy(svx_devdec* d) {
     (void)hipStreamSynchronize(d->stream);
     (void)hipStreamSynchronize(d->batch_stream);
     if (d->inf) svx_inflater_destroy(d->inf);
+    bamsort_destroy(d->sort); d->sort = nullptr;
     bamindex_destroy(d->index); d->index = nullptr;
     for (auto& c : d->chunk) c.release();
     DevBuf* all[] = {&d->ref_len, &d->contig_rank, &d->ct_key, &d->ct_tid, &d->ct_names, &d->ct_name_off, &d->err, &d->counters, &d->crc_shift, &d->batch_cnt, &d->nt_key, &d->nt_check, &d->nt_id};
@@ -943,10 +946,60 @@ int devdec_load(svx_devdec* d, int slot, const DevDecBlock* blocks, size_t nb_in
                                c.ix_start.data(), c.ix_vbase.data(), (long long)c.ix_start.size()};
         SVXCHK(bamindex_append(d->index, ic, st));
     }
+    if (d->sort_on && c.n_rec > 0) {
+        // the chunk's records lie back to back from its first byte to where its tail (a partial record, in query-name mode the last read's group) begins
+        const BamSortChunk sc{(long long)c.n_rec, sp, (uint64_t)c.data_begin, (uint64_t)c.tail_start, c.rec_off.as<uint64_t>(), c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(),
+                              c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>()};
+        const int rc = bamsort_append(d->sort, sc, st);
+        if (rc != SVX_OK) { d->sort_on = false; bamsort_drop(d->sort); return rc; }      // (SVX_E_CAPACITY: the arena is full - the sort is given up, the handle rewinds)
+    }
     d->stats.records += c.n_rec;
     c.loaded = true;
     return SVX_OK;
 }
+
+int devdec_sort_begin(svx_devdec* d, int64_t max_bytes) {
+    HIPCHK(hipSetDevice(d->device));
+    SVXCHK(bamsort_begin(&d->sort, max_bytes, d->n_ref));
+    d->sort_on = true;
+    return SVX_OK;
+}
+void devdec_sort_drop(svx_devdec* d) {
+    (void)hipSetDevice(d->device);
+    d->sort_on = false;
+    bamsort_drop(d->sort);
+}
+bool devdec_sort_on(const svx_devdec* d) { return d->sort_on; }
+bool devdec_sort_finished(const svx_devdec* d) { return bamsort_finished(d->sort); }
+int devdec_sort_finish(svx_devdec* d, const uint8_t* header, int64_t header_bytes) {
+    HIPCHK(hipSetDevice(d->device));
+    d->sort_on = false;
+    const int rc = bamsort_finish(d->sort, header, header_bytes, d->stream);
+    if (rc != SVX_OK) bamsort_drop(d->sort);
+    return rc;
+}
+void devdec_sort_count(const svx_devdec* d, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) { bamsort_count(d->sort, n_records, stream_bytes, n_blocks); }
+int devdec_sort_encode(svx_devdec* d, int64_t first_block, int64_t n_blocks, int64_t* n_bytes) {
+    HIPCHK(hipSetDevice(d->device));
+    return bamsort_encode(d->sort, first_block, n_blocks, n_bytes, d->stream);
+}
+int devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_dst) {
+    HIPCHK(hipSetDevice(d->device));
+    return bamsort_fetch(d->sort, compressed_dst, stream_dst, d->stream);
+}
+int devdec_sort_index(svx_devdec* d) {
+    HIPCHK(hipSetDevice(d->device));
+    if (d->index_on) return svx_fail(SVX_E_STATE, "svx_bam_sort_index while a BAM index pass is on", __FILE__, __LINE__, hipSuccess);
+    SVXCHK(bamindex_begin(&d->index));
+    const int rc = bamsort_index(d->sort, d->index, d->stream);
+    bamindex_drop(d->index);                                // (the table's memory goes back; the bytes of a finished index stay)
+    return rc;
+}
+int devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm) {
+    HIPCHK(hipSetDevice(d->device));
+    return bamsort_permutation(d->sort, host_perm, d->stream);
+}
+void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out) { bamsort_stats(d->sort, out); }
 
 int devdec_index_begin(svx_devdec* d) {
     HIPCHK(hipSetDevice(d->device));

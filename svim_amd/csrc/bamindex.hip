@@ -314,6 +314,40 @@ int bamindex_append(BamIndex* S, const BamIndexChunk& c, hipStream_t st) {
     return SVX_OK;
 }
 
+// row i = row perm[i] of another table, at the virtual offset of its place in a stream cut into blocks of block_bytes (the sorted file of bamsort.hip)
+__global__ void k_bix_take(long long n, BixCols src, long long n_src, BixCols dst, const uint32_t* perm, const int64_t* rec_soff, const int64_t* coff, long long n_blk,
+                           long long block_bytes, int* err) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long r = perm[i], u = rec_soff[i], b = u / block_bytes;
+    if (r >= n_src || u < 0 || b >= n_blk) { atomicOr(err, BIXF_LAYOUT); return; }
+    dst.tid[i] = src.tid[r]; dst.pos[i] = src.pos[r]; dst.flag[i] = src.flag[r]; dst.end[i] = src.end[r];
+    dst.vbeg[i] = ((uint64_t)coff[b] << 16) | (uint64_t)(u - b * block_bytes);
+}
+int bamindex_take_rows(BamIndex* S, const BamIndex* src, const uint32_t* perm, const int64_t* rec_soff, const int64_t* coff, int64_t n_blk, int64_t block_bytes, hipStream_t st) {
+    if (!S || !src || S == src || n_blk < 1 || block_bytes < 1 || block_bytes > 65536) return svx_fail(SVX_E_ARG, "BAM index: bad rows", __FILE__, __LINE__, hipSuccess);
+    const int64_t n = src->n;
+    S->n = 0; S->have = false;
+    if (n > S->cap) {
+        const int64_t ncap = std::max<int64_t>(n, 1 << 16);
+        SVXCHK(S->tid.reserve((size_t)ncap * 4)); SVXCHK(S->pos.reserve((size_t)ncap * 4)); SVXCHK(S->flag.reserve((size_t)ncap * 2));
+        SVXCHK(S->end.reserve((size_t)ncap * 8)); SVXCHK(S->vbeg.reserve((size_t)ncap * 8));
+        S->cap = ncap;
+    }
+    if (n > 0) {
+        SVXCHK(S->err.reserve(64));
+        HIPCHK(hipMemsetAsync(S->err.p, 0, 64, st));
+        k_bix_take<<<BGRID(n), BT, 0, st>>>(n, src->cols(0), src->n, S->cols(0), perm, rec_soff, coff, n_blk, block_bytes, S->err.as<int>());
+        HIPCHK(hipGetLastError());
+        int err_h = 0;
+        SVXCHK(svx_d2h(&err_h, S->err.p, 4, st));
+        if (err_h) return svx_fail(SVX_E_STATE, "BAM index: a row of the sorted file lies outside its tables (internal error)", __FILE__, __LINE__, hipSuccess);
+    }
+    S->n = n; S->n_long = src->n_long; S->t_append = src->t_append;
+    return SVX_OK;
+}
+int64_t bamindex_rows(const BamIndex* S) { return S ? S->n : 0; }
+
 int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) {
     if (!S || n_ref < 0) return svx_fail(SVX_E_ARG, "BAM index: bad argument", __FILE__, __LINE__, hipSuccess);
     S->used = 0; S->have = false;

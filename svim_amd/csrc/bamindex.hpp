@@ -13,6 +13,11 @@ int  bamindex_begin(BamIndex** ix);                        // an empty table (th
 void bamindex_drop(BamIndex* ix);                          // the table's memory goes back; the bytes of a finished index stay
 void bamindex_destroy(BamIndex* ix);
 int  bamindex_append(BamIndex* ix, const BamIndexChunk& c, hipStream_t st);
+// ready rows instead of appended ones (bamsort.hip: the index of the sorted file): row i of `ix` becomes row perm[i] of `src` - tid, pos, end, flag - with the
+// virtual offset of stream offset u = rec_soff[i] in a file of blocks of block_bytes stream bytes each, (coff[u / block_bytes] << 16) | (u % block_bytes).
+// perm, rec_soff (n entries) and coff (n_blk entries) are device arrays; whatever `ix` held is replaced
+int  bamindex_take_rows(BamIndex* ix, const BamIndex* src, const uint32_t* perm, const int64_t* rec_soff, const int64_t* coff, int64_t n_blk, int64_t block_bytes, hipStream_t st);
+int64_t bamindex_rows(const BamIndex* ix);
 // the bytes of the .bai from the table, which is dropped whatever the result: SVX_OK, SVX_E_ORDER, SVX_E_RANGE
 int  bamindex_finish(BamIndex* ix, int32_t n_ref, uint64_t v_end, hipStream_t st);
 bool bamindex_bytes(const BamIndex* ix, int64_t* n_bytes);        // false: no finished index

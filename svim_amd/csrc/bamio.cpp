@@ -596,6 +596,7 @@ extern "C" int svx_bam_set_seq_filter(svx_bam* h, int min_ins_len) {
 extern "C" int svx_bam_seek(svx_bam* h, uint64_t voff, int32_t last_tid) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
     if (h->dev && devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_seek while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
+    if (h->dev && devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_seek during a sort pass (svx_bam_sort_finish or svx_bam_sort_abort first)");
     if (h->prefetch_active) { h->prefetch.wait(); h->prefetch_active = false; }
     h->prefetch_err.clear();
     const size_t coff = (size_t)(voff >> 16), uoff = (size_t)(voff & 0xffff);
@@ -621,6 +622,7 @@ extern "C" int svx_bam_seek(svx_bam* h, uint64_t voff, int32_t last_tid) {
 extern "C" int svx_bam_rewind(svx_bam* h) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
     if (h->dev && devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_rewind while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
+    if (h->dev && devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_rewind during a sort pass (svx_bam_sort_finish or svx_bam_sort_abort first)");
     if (h->prefetch_active) { h->prefetch.wait(); h->prefetch_active = false; }
     h->prefetch_err.clear();
     if (getenv("SVX_BAM_TIMING")) {                      // per pass: the stages of the pass that just ended
@@ -1042,6 +1044,7 @@ extern "C" int svx_bam_index_begin(svx_bam* h) {
     if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_index_begin: the index is built from the device reader's record stream (svx_bam_set_device_decode first)");
     if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
         return bam_fail(SVX_E_STATE, "svx_bam_index_begin: the handle is not at its first record (begin before the first read, or rewind first)");
+    if (devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_index_begin during a sort pass (the sorted file's index comes from svx_bam_sort_index)");
     const int rc = devdec_index_begin(h->dev);
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
     h->dev_data_end = 0; h->dev_eof_seen = false;
@@ -1077,6 +1080,105 @@ extern "C" int svx_bam_index_fetch(svx_bam* h, uint8_t* host_dst) {
 extern "C" int svx_bam_index_get_stats(svx_bam* h, svx_bam_index_stats* out) {
     if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
     if (h->dev) devdec_index_stats(h->dev, out); else memset(out, 0, sizeof *out);
+    return SVX_OK;
+}
+
+// ---- coordinate sort from the device reader's record stream (include/svx.h; bamdev.hip appends bytes and rows, bamsort.hip sorts, lays out and encodes) -----
+// the header as the file holds it (magic .. reference dictionary), inflated from the first blocks of the mapped file
+static int raw_header(svx_bam* h, std::vector<uint8_t>& out) {
+    out.clear();
+    size_t fp = 0;
+    std::swap(fp, h->fpos);                                      // (read_block walks h->fpos; the host reader is idle in device mode)
+    std::string err;
+    z_stream zs; memset(&zs, 0, sizeof zs);
+    if (inflateInit2(&zs, -15) != Z_OK) err = "inflateInit2 failed";
+    try {
+        while (err.empty() && out.size() < h->header_bytes) {
+            RawBlock b;
+            if (!read_block(h, b)) { err = "the file ends inside its header"; break; }
+            if (!b.isize) continue;
+            const size_t at = out.size();
+            out.resize(at + b.isize);
+            if (inflateReset(&zs) != Z_OK) { err = "inflateReset failed"; break; }
+            zs.next_in = const_cast<Bytef*>(b.comp); zs.avail_in = (uInt)b.clen; zs.next_out = out.data() + at; zs.avail_out = b.isize;
+            if (inflate(&zs, Z_FINISH) != Z_STREAM_END || zs.avail_out != 0) err = "BGZF inflate of the header failed";
+        }
+    } catch (const std::string& e) { err = e; }
+    inflateEnd(&zs);
+    std::swap(fp, h->fpos);
+    if (!err.empty()) return bam_fail(SVX_E_ARG, "svx_bam_sort_finish: " + err);
+    out.resize(h->header_bytes);
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_begin(svx_bam* h, int64_t max_bytes) {
+    if (!h || max_bytes < 0) return bam_fail(SVX_E_ARG, "svx_bam_sort_begin: bad argument");
+    if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the sort is fed by the device reader's record stream (svx_bam_set_device_decode first)");
+    if (devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
+    if (devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin during a sort pass");
+    if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
+        return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the handle is not at its first record (begin before the first read, or rewind first)");
+    const int rc = devdec_sort_begin(h->dev, max_bytes);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    h->dev_eof_seen = false;
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_finish(svx_bam* h) {
+    if (!h) return bam_fail(SVX_E_ARG, "null reader");
+    if (!h->dev || !devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_finish without svx_bam_sort_begin (a read that failed with SVX_E_CAPACITY has dropped the sort)");
+    if (!h->dev_eof_seen || h->dev_prefetching) return bam_fail(SVX_E_STATE, "svx_bam_sort_finish before svx_bam_read_batch has returned 0 records at the end of the file");
+    std::vector<uint8_t> raw, made;
+    int rc = raw_header(h, raw);
+    if (rc != SVX_OK) { devdec_sort_drop(h->dev); return rc; }
+    int64_t n = 0;
+    rc = svx_bam_sort_header_host(raw.data(), (int64_t)raw.size(), nullptr, 0, &n);
+    if (rc == SVX_E_CAPACITY) { made.resize((size_t)n); rc = svx_bam_sort_header_host(raw.data(), (int64_t)raw.size(), made.data(), n, &n); }
+    if (rc != SVX_OK) { devdec_sort_drop(h->dev); return bam_fail(rc, "svx_bam_sort_finish: the file's header cannot be rewritten"); }
+    rc = devdec_sort_finish(h->dev, made.data(), (int64_t)made.size());
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_abort(svx_bam* h) {
+    if (!h) return bam_fail(SVX_E_ARG, "null reader");
+    if (!h->dev || !(devdec_sort_on(h->dev) || devdec_sort_finished(h->dev))) return bam_fail(SVX_E_STATE, "svx_bam_sort_abort without a sort");
+    if (h->dev_prefetching) h->dev_future.wait();           // the chunk being loaded appends its records: it is kept for the next read, the arena goes after it
+    devdec_sort_drop(h->dev);
+    return SVX_OK;
+}
+#define SORT_NEEDS_FINISHED(what) \
+    if (!h) return bam_fail(SVX_E_ARG, "null reader"); \
+    if (!h->dev || !devdec_sort_finished(h->dev)) return bam_fail(SVX_E_STATE, what ": no sorted records (svx_bam_sort_begin, a pass over the file, svx_bam_sort_finish)")
+extern "C" int svx_bam_sort_count(svx_bam* h, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) {
+    SORT_NEEDS_FINISHED("svx_bam_sort_count");
+    devdec_sort_count(h->dev, n_records, stream_bytes, n_blocks);
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_encode(svx_bam* h, int64_t first_block, int64_t n_blocks, int64_t* n_bytes) {
+    SORT_NEEDS_FINISHED("svx_bam_sort_encode");
+    const int rc = devdec_sort_encode(h->dev, first_block, n_blocks, n_bytes);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_fetch(svx_bam* h, uint8_t* compressed_dst, uint8_t* stream_dst) {
+    SORT_NEEDS_FINISHED("svx_bam_sort_fetch");
+    const int rc = devdec_sort_fetch(h->dev, compressed_dst, stream_dst);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_index(svx_bam* h) {
+    SORT_NEEDS_FINISHED("svx_bam_sort_index");
+    const int rc = devdec_sort_index(h->dev);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_permutation(svx_bam* h, uint32_t* perm) {
+    SORT_NEEDS_FINISHED("svx_bam_sort_permutation");
+    const int rc = devdec_sort_permutation(h->dev, perm);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out) {
+    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
+    if (h->dev) devdec_sort_stats(h->dev, out); else memset(out, 0, sizeof *out);
     return SVX_OK;
 }
 

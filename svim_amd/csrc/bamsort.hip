@@ -1,0 +1,422 @@
+// bamsort.hip - the file the device reader (bamdev.hip) is reading, put into coordinate order on the device: the sorted BGZF file piece by piece and its .bai
+// (svx_bam_sort*, include/svx.h; gfx950).  What the sorted file is: svim_amd/bamsort.py; the key and the checks: bamsort_core.hpp, the source
+// svx_bam_sort_host is built from as well.
+// Replaces: samtools view | samtools sort and samtools index in front of the pipeline (the reference's run_alignment hands the aligner's output to them,
+// src/svim/SVIM_alignment.py:48-50): single-threaded zlib both ways and a merge on the host, for records this reader has already found.
+//   append   while sorting is on, every chunk the reader loads leaves its records' bytes - they lie back to back in the inflated stream - in a slab of their own
+//            (one device-to-device copy; slabs are never moved or regrown) and one row per record: k_bs_rows the key, the length, the address in the slab, the
+//            checks; the index rows (tid, pos, end, flag) by bamindex.hip's own append
+//   finish   the keys sorted stably (svx_sort_pairs_u64_on over the key's used bits) with the record number as payload = the permutation; k_bs_layout the
+//            segments of the output stream (the header, then the records in order) with their lengths and addresses; a scan gives every segment's offset
+//   encode   a range of 65 280-byte blocks: k_bs_gather lays the stream bytes of the range out in the piece buffer, then the encoder's phases over the piece
+//            (textgz_kernels.hpp: CRC, matches, codes, bits, compaction), every block's compressed size kept on the host
+//   index    the sorted rows with the virtual offsets the block sizes give, through bamindex.hip's phases (bamindex_take_rows, bamindex_finish)
+// k_bs_gather: a workgroup owns tiles of BS_TILE bytes of the piece; work follows the bytes of the destination, not the records (a record is between 36 bytes and
+// hundreds of kilobytes long).  Wave 0 finds the tile's first and last segment in the stream offsets by a 64-ary search (one probe per lane and step), the
+// tile's segment table goes to LDS, and every lane takes aligned 16-byte words of the destination: the segment of a word's first byte by bisection in LDS, the
+// word from two aligned 16-byte loads of the source merged by a byte funnel shift (v_alignbyte_b32), one 16-byte store.  A word that holds a segment edge (at
+// most one in 36 bytes) is put together byte by byte and still stored whole; only the last, partial word of a piece is written in bytes.  No atomics, no LDS
+// traffic per byte: the kernel moves every byte once in and once out.
+#include "common.hpp"
+#include "hostcopy.hpp"
+#include "scan.hpp"
+#include "bamsort_core.hpp"
+#include "bamsort.hpp"
+#include "textgz_kernels.hpp"
+#include <algorithm>
+
+#define BS_T 256
+#define BS_GRID(n) (unsigned)(((long long)(n) + BS_T - 1) / BS_T)
+#define BS_TILE 16384                 /* bytes of the piece per workgroup and step: 4 words of 16 bytes per lane */
+#define BS_SEGS 512                   /* segments of a tile kept in LDS: a record is at least 36 bytes, so a tile touches at most 16384 / 36 + 2 = 457 */
+#define BS_MAX_GRID 2048
+#define BS_PAD 64                     /* bytes behind a slab, the header and the piece: the aligned loads around a record's last bytes stay inside the allocation */
+static_assert(BSORT_BLOCK == DEF_BLOCK, "the output's blocks are the encoder's");
+static_assert(BSORT_BLOCK % 16 == 0 && BS_TILE % 16 == 0, "a piece and its tiles start at aligned words of the destination");
+
+typedef unsigned int bs_u32x4 __attribute__((ext_vector_type(4)));
+
+// ---- append ---------------------------------------------------------------------------------------------------------------------------------------------
+__global__ void k_bs_rows(long long n, const uint8_t* st, const uint64_t* rec_off, uint64_t first_byte, uint64_t end_byte, uint64_t slab, const int32_t* tid, const int32_t* pos,
+                          const uint16_t* flag, int32_t n_ref, uint64_t* key, uint32_t* len, uint64_t* addr, int* bad) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t p = rec_off[i];
+    const uint32_t bs = (uint32_t)st[p] | ((uint32_t)st[p + 1] << 8) | ((uint32_t)st[p + 2] << 16) | ((uint32_t)st[p + 3] << 24);
+    int b = bsort_check(tid[i], pos[i], bs, n_ref);
+    if (p < first_byte || p + 4ull + bs > end_byte) b |= BSORT_BAD_SIZE;            // (cannot happen: the reader walked these records)
+    if (b) atomicOr(bad, b);
+    key[i] = bsort_key(tid[i], pos[i], flag[i], n_ref);
+    len[i] = 4u + bs;
+    addr[i] = slab + (p - first_byte);
+}
+
+// ---- finish ---------------------------------------------------------------------------------------------------------------------------------------------
+__global__ void k_bs_iota(long long n, uint32_t* v) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) v[i] = (uint32_t)i;
+}
+// segment 0 is the header, segment i + 1 the record perm[i]; slen has one entry more (0) so that its scan ends with the stream's size
+__global__ void k_bs_layout(long long n, const uint32_t* perm, const uint32_t* len, const uint64_t* addr, uint64_t hdr, long long hdr_bytes, int64_t* slen, uint64_t* saddr) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n + 1) return;
+    if (j == n + 1) { slen[j] = 0; return; }
+    if (j == 0) { slen[0] = hdr_bytes; saddr[0] = hdr; return; }
+    const uint32_t r = perm[j - 1];
+    slen[j] = (int64_t)len[r]; saddr[j] = addr[r];
+}
+
+// ---- the gather -----------------------------------------------------------------------------------------------------------------------------------------
+struct BsSegs { const int64_t* soff; const uint64_t* saddr; long long n_seg; };      // soff: n_seg + 1 entries, soff[0] = 0, soff[n_seg] = the stream's size
+
+// largest j in [0, n) with soff[j] <= x (soff[0] <= x), by the 64 lanes of one wave: a probe per lane and step
+__device__ __forceinline__ long long bs_find(const int64_t* soff, long long n, long long x) {
+    long long a = 0, b = n;
+    const int lane = lane_id();
+    while (b - a > 1) {
+        const long long step = (b - a + 63) >> 6, p = a + (long long)lane * step;
+        const unsigned long long ok = __ballot(p < b && soff[p] <= x);          // (lane 0 probes a: always set; the set lanes are a prefix)
+        const long long c = (long long)__popcll(ok) - 1;
+        a += c * step;
+        b = a + step < b ? a + step : b;
+    }
+    return a;
+}
+// 16 bytes from any address: the two aligned 16-byte words around them, shifted into place.  Reads at most 15 bytes in front of src and 15 behind src + 16
+__device__ __forceinline__ bs_u32x4 bs_load16(uint64_t src) {
+    const unsigned sh = (unsigned)(src & 15ull);
+    const bs_u32x4* q = reinterpret_cast<const bs_u32x4*>(src - sh);
+    const bs_u32x4 lo = q[0];
+    if (sh == 0u) return lo;
+    const bs_u32x4 hi = q[1];
+    const unsigned ws = sh >> 2, bsh = sh & 3u;
+    const uint32_t s0 = ws == 0u ? lo.x : ws == 1u ? lo.y : ws == 2u ? lo.z : lo.w;
+    const uint32_t s1 = ws == 0u ? lo.y : ws == 1u ? lo.z : ws == 2u ? lo.w : hi.x;
+    const uint32_t s2 = ws == 0u ? lo.z : ws == 1u ? lo.w : ws == 2u ? hi.x : hi.y;
+    const uint32_t s3 = ws == 0u ? lo.w : ws == 1u ? hi.x : ws == 2u ? hi.y : hi.z;
+    const uint32_t s4 = ws == 0u ? hi.x : ws == 1u ? hi.y : ws == 2u ? hi.z : hi.w;
+    bs_u32x4 r;
+    r.x = __builtin_amdgcn_alignbyte(s1, s0, bsh); r.y = __builtin_amdgcn_alignbyte(s2, s1, bsh);
+    r.z = __builtin_amdgcn_alignbyte(s3, s2, bsh); r.w = __builtin_amdgcn_alignbyte(s4, s3, bsh);
+    return r;
+}
+// stream bytes [lo, lo + n_bytes) -> dst[0, n_bytes); lo is a multiple of 16 and dst 16-byte aligned
+__global__ __launch_bounds__(BS_T) void k_bs_gather(BsSegs G, long long lo, long long n_bytes, uint8_t* dst) {
+    __shared__ long long s_off[BS_SEGS + 1];
+    __shared__ unsigned long long s_addr[BS_SEGS];
+    __shared__ long long s_j[2];
+    const long long tiles = (n_bytes + BS_TILE - 1) / BS_TILE, end = lo + n_bytes;
+    for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const long long t_lo = lo + t * BS_TILE, t_hi = t_lo + BS_TILE < end ? t_lo + BS_TILE : end;
+        __syncthreads();                                                       // (the tile before is done with the table)
+        if (threadIdx.x < 64) {
+            const long long j0 = bs_find(G.soff, G.n_seg, t_lo), j1 = bs_find(G.soff, G.n_seg, t_hi - 1);
+            if (threadIdx.x == 0) { s_j[0] = j0; s_j[1] = j1; }
+        }
+        __syncthreads();
+        const long long j0 = s_j[0], m = s_j[1] - j0 + 1;                      // the m segments that hold bytes of the tile
+        const bool staged = m <= BS_SEGS;                                      // (always, for records of at least 36 bytes; the table is read in place otherwise)
+        if (staged) for (long long k = threadIdx.x; k <= m; k += BS_T) { s_off[k] = G.soff[j0 + k]; if (k < m) s_addr[k] = G.saddr[j0 + k]; }
+        __syncthreads();
+        const int64_t* goff = G.soff + j0; const uint64_t* gaddr = G.saddr + j0;
+#define BS_OFF(k) (staged ? s_off[(k)] : (long long)goff[(k)])
+#define BS_ADDR(k) (staged ? (uint64_t)s_addr[(k)] : gaddr[(k)])
+        for (long long w = t_lo + 16ll * threadIdx.x; w < t_hi; w += 16ll * BS_T) {
+            long long a = 0, b = m;                                            // the segment of byte w: the largest k with off[k] <= w
+            while (b - a > 1) { const long long mid = (a + b) >> 1; if (BS_OFF(mid) <= w) a = mid; else b = mid; }
+            long long k = a;
+            uint8_t* d = dst + (w - lo);
+            if (w + 16 <= t_hi && w + 16 <= BS_OFF(k + 1)) {
+                *reinterpret_cast<bs_u32x4*>(d) = bs_load16(BS_ADDR(k) + (uint64_t)(w - BS_OFF(k)));
+                continue;
+            }
+            // a word with a segment edge inside, or the piece's last, partial word: byte by byte
+            uint32_t v[4] = {0u, 0u, 0u, 0u};
+            const int nb = (int)(t_hi - w < 16 ? t_hi - w : 16);
+            for (int i = 0; i < nb; i++) {
+                const long long p = w + i;
+                while (p >= BS_OFF(k + 1)) k++;                                // (p < t_hi <= off[m]: k stays below m)
+                const uint32_t byte = *reinterpret_cast<const uint8_t*>(BS_ADDR(k) + (uint64_t)(p - BS_OFF(k)));
+                v[i >> 2] |= byte << (8 * (i & 3));
+            }
+            if (nb == 16) { bs_u32x4 r; r.x = v[0]; r.y = v[1]; r.z = v[2]; r.w = v[3]; *reinterpret_cast<bs_u32x4*>(d) = r; }
+            else for (int i = 0; i < nb; i++) d[i] = (uint8_t)(v[i >> 2] >> (8 * (i & 3)));
+        }
+#undef BS_OFF
+#undef BS_ADDR
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------------------
+struct BamSort {
+    int32_t n_ref = 0; int64_t max_bytes = 0;
+    int64_t n = 0, cap = 0;
+    std::vector<void*> slabs; int64_t arena_bytes = 0;
+    DevBuf key, len, addr, bad;                              // rows, in file order
+    BamIndex* rows = nullptr;                                // tid, pos, end, flag of every record, in file order (bamindex.hip's table)
+    DevBuf key2, val, perm, sort_tmp, scan_tmp, slen, soff, saddr, hdr;
+    bool finished = false;
+    int64_t stream_bytes = 0, n_blocks = 0, next_block = 0; bool broken = false;
+    std::vector<int64_t> h_csize;                            // compressed size of every block encoded so far
+    // the encoder's buffers, one piece
+    DevBuf piece, blocks, crc, crc_shift, tok, hist, nt, codes, bsize, coff, kinds, slots, out, coff_all;
+    int64_t piece_bytes = 0, out_bytes = 0; bool have_piece = false;
+    double t_append = 0;
+    svx_bam_sort_stats stats;
+};
+static inline double bs_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref) {
+    if (max_bytes < 0 || n_ref < 0) return svx_fail(SVX_E_ARG, "BAM sort: bad argument", __FILE__, __LINE__, hipSuccess);
+    if (!*s) *s = new BamSort();
+    BamSort* S = *s;
+    bamsort_drop(S);
+    S->n_ref = n_ref; S->max_bytes = max_bytes;
+    memset(&S->stats, 0, sizeof S->stats);
+    SVXCHK(bamindex_begin(&S->rows));
+    SVXCHK(S->bad.reserve(64));
+    HIPCHK(hipMemset(S->bad.p, 0, 64));
+    return SVX_OK;
+}
+void bamsort_drop(BamSort* S) {
+    if (!S) return;
+    for (void* p : S->slabs) (void)hipFree(p);
+    S->slabs.clear(); S->arena_bytes = 0;
+    DevBuf* all[] = {&S->key, &S->len, &S->addr, &S->key2, &S->val, &S->perm, &S->sort_tmp, &S->scan_tmp, &S->slen, &S->soff, &S->saddr, &S->hdr, &S->piece, &S->blocks, &S->crc, &S->tok,
+                     &S->hist, &S->nt, &S->codes, &S->bsize, &S->coff, &S->kinds, &S->slots, &S->out, &S->coff_all};
+    for (auto* b : all) b->release();
+    bamindex_drop(S->rows);
+    S->n = S->cap = 0; S->finished = false; S->have_piece = false; S->stream_bytes = S->n_blocks = S->next_block = 0; S->broken = false; S->t_append = 0;
+    S->piece_bytes = S->out_bytes = 0;
+    S->h_csize.clear(); S->h_csize.shrink_to_fit();
+}
+void bamsort_destroy(BamSort* S) {
+    if (!S) return;
+    bamsort_drop(S);
+    bamindex_destroy(S->rows);
+    S->bad.release(); S->crc_shift.release();
+    delete S;
+}
+
+int bamsort_append(BamSort* S, const BamSortChunk& c, hipStream_t st) {
+    if (!S || S->finished || c.n < 0 || c.end_byte < c.first_byte) return svx_fail(SVX_E_ARG, "BAM sort: bad chunk", __FILE__, __LINE__, hipSuccess);
+    if (c.n == 0) return SVX_OK;
+    const double t0 = bs_now();
+    if (S->n + c.n > 0xffffffffll) return svx_fail(SVX_E_CAPACITY, "BAM sort: more than 2^32 - 1 records", __FILE__, __LINE__, hipSuccess);
+    const size_t need = (size_t)(c.end_byte - c.first_byte);
+    {
+        char msg[200];
+        if (S->max_bytes > 0 && S->arena_bytes + (int64_t)need > S->max_bytes) {
+            snprintf(msg, sizeof msg, "BAM sort: the records do not fit into the arena (%lld bytes held, %zu more, limit %lld)", (long long)S->arena_bytes, need, (long long)S->max_bytes);
+            return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
+        }
+        size_t free_b = 0, total_b = 0;
+        if (S->max_bytes == 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + (size_t)c.n * 64 + ((size_t)64 << 20) > free_b) {
+            snprintf(msg, sizeof msg, "BAM sort: the records do not fit into device memory (%lld bytes held, %zu more, %zu free)", (long long)S->arena_bytes, need, free_b);
+            return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
+        }
+    }
+    if (S->n + c.n > S->cap) {                               // the rows grow by doubling, kept; the slabs never move
+        const int64_t ncap = std::max<int64_t>(std::max<int64_t>(S->n + c.n, 2 * S->cap), 1 << 16);
+        SVXCHK(S->key.reserve((size_t)ncap * 8, true, st)); SVXCHK(S->len.reserve((size_t)ncap * 4, true, st)); SVXCHK(S->addr.reserve((size_t)ncap * 8, true, st));
+        S->cap = ncap;
+    }
+    void* slab = nullptr;
+    HIPCHK(hipMalloc(&slab, need + BS_PAD));
+    S->slabs.push_back(slab); S->arena_bytes += (int64_t)need;
+    HIPCHK(hipMemcpyAsync(slab, c.stream + c.first_byte, need, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemsetAsync((uint8_t*)slab + need, 0, BS_PAD, st));
+    k_bs_rows<<<BS_GRID(c.n), BS_T, 0, st>>>(c.n, c.stream, c.rec_off, c.first_byte, c.end_byte, (uint64_t)(uintptr_t)slab, c.tid, c.pos, c.flag, S->n_ref, S->key.as<uint64_t>() + S->n,
+                                             S->len.as<uint32_t>() + S->n, S->addr.as<uint64_t>() + S->n, S->bad.as<int>());
+    HIPCHK(hipGetLastError());
+    // the index rows: end from the CIGAR (CG included) by bamindex.hip's append; its virtual offsets are replaced when the sorted file's are known
+    const uint64_t blk_start = 0, blk_vbase = 0;
+    const BamIndexChunk ic{c.n, c.tid, c.pos, c.flag, c.cigar_off, c.cigar, c.rec_off, &blk_start, &blk_vbase, 1};
+    SVXCHK(bamindex_append(S->rows, ic, st));               // (drains the stream: the chunk's arrays and its stream are no longer read)
+    S->n += c.n;
+    S->t_append += bs_now() - t0;
+    return SVX_OK;
+}
+
+int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipStream_t st) {
+    if (!S || S->finished || !header || header_bytes < 12) return svx_fail(SVX_E_ARG, "BAM sort: bad argument", __FILE__, __LINE__, hipSuccess);
+    const int64_t n = S->n;
+    if (bamindex_rows(S->rows) != n) return svx_fail(SVX_E_STATE, "BAM sort: the row tables disagree (internal error)", __FILE__, __LINE__, hipSuccess);
+    HIPCHK(hipStreamSynchronize(st));
+    const double t0 = bs_now();
+    int bad = 0;
+    SVXCHK(svx_d2h(&bad, S->bad.p, 4, st));
+    if (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID)) return svx_fail(SVX_E_ARG, "BAM sort: a record names a reference the header does not have, or is shorter than its fixed fields", __FILE__, __LINE__, hipSuccess);
+    if (bad & BSORT_BAD_POS) return svx_fail(SVX_E_RANGE, "BAM sort: a record has a position below -1", __FILE__, __LINE__, hipSuccess);
+    SVXCHK(S->hdr.reserve((size_t)header_bytes + BS_PAD));
+    HIPCHK(hipMemsetAsync((uint8_t*)S->hdr.p + header_bytes, 0, BS_PAD, st));
+    SVXCHK(svx_h2d(S->hdr.p, header, (size_t)header_bytes, st));
+    SVXCHK(S->perm.reserve((size_t)(n + 1) * 4));
+    if (n > 0) {
+        SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4));
+        k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, S->val.as<uint32_t>());
+        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->key.as<uint64_t>(), S->key2.as<uint64_t>(), S->val.as<uint32_t>(), S->perm.as<uint32_t>(), n, 0, bsort_key_bits(S->n_ref)));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    const double t1 = bs_now();
+    SVXCHK(S->slen.reserve((size_t)(n + 2) * 8)); SVXCHK(S->soff.reserve((size_t)(n + 2) * 8)); SVXCHK(S->saddr.reserve((size_t)(n + 2) * 8));
+    k_bs_layout<<<BS_GRID(n + 2), BS_T, 0, st>>>(n, S->perm.as<uint32_t>(), S->len.as<uint32_t>(), S->addr.as<uint64_t>(), (uint64_t)(uintptr_t)S->hdr.p, header_bytes, S->slen.as<int64_t>(),
+                                                 S->saddr.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    SVXCHK((svx_exclusive_scan<int64_t, int64_t>(S->slen.as<int64_t>(), S->soff.as<int64_t>(), n + 2, st, S->scan_tmp)));
+    int64_t total = 0;
+    SVXCHK(svx_d2h(&total, S->soff.as<int64_t>() + n + 1, 8, st));
+    if (total != header_bytes + S->arena_bytes) return svx_fail(SVX_E_STATE, "BAM sort: the stream's size is not the header's plus the arena's (internal error)", __FILE__, __LINE__, hipSuccess);
+    // what only the sort needed goes back: resident from here on are the arena, the permutation, the segment table and the index rows
+    S->key.release(); S->key2.release(); S->val.release(); S->len.release(); S->addr.release(); S->slen.release(); S->sort_tmp.release();
+    S->cap = 0;
+    const double t2 = bs_now();
+    S->stream_bytes = total; S->n_blocks = (total + BSORT_BLOCK - 1) / BSORT_BLOCK + 1; S->next_block = 0; S->broken = false;
+    S->h_csize.assign((size_t)S->n_blocks, 0);
+    S->finished = true;
+    S->stats.t_append_ms = S->t_append * 1e3; S->stats.t_sort_ms = (t1 - t0) * 1e3; S->stats.t_layout_ms = (t2 - t1) * 1e3; S->stats.t_finish_ms = (t2 - t0) * 1e3;
+    S->stats.n_records = n; S->stats.n_slabs = (int64_t)S->slabs.size(); S->stats.arena_bytes = S->arena_bytes; S->stats.stream_bytes = total; S->stats.n_blocks = S->n_blocks;
+    S->stats.key_bits = bsort_key_bits(S->n_ref);
+    return SVX_OK;
+}
+bool bamsort_finished(const BamSort* S) { return S && S->finished; }
+void bamsort_count(const BamSort* S, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) {
+    if (n_records) *n_records = S->n;
+    if (stream_bytes) *stream_bytes = S->stream_bytes;
+    if (n_blocks) *n_blocks = S->n_blocks;
+}
+
+int bamsort_encode(BamSort* S, int64_t first, int64_t nb, int64_t* n_bytes, hipStream_t st) {
+    if (!S || !S->finished) return svx_fail(SVX_E_STATE, "svx_bam_sort_encode before svx_bam_sort_finish", __FILE__, __LINE__, hipSuccess);
+    if (first < 0 || nb < 1 || first > S->n_blocks - nb) return svx_fail(SVX_E_ARG, "svx_bam_sort_encode: block range outside the file", __FILE__, __LINE__, hipSuccess);
+    S->have_piece = false;
+    const int64_t total = S->stream_bytes;
+    const int64_t lo = std::min<int64_t>(first * BSORT_BLOCK, total), hi = std::min<int64_t>((first + nb) * BSORT_BLOCK, total), pb = hi - lo;
+    const long long chunk = std::min<long long>(nb, TGZ_CHUNK);
+    {
+        const size_t need = (size_t)pb + (size_t)nb * DEF_SLOT + (size_t)pb + (size_t)nb * 64 + (size_t)chunk * (DEF_BLOCK * 4 + sizeof(DefBlockCodes) + DEF_NHIST * 4);
+        const size_t have = S->piece.cap + S->slots.cap + S->out.cap + S->tok.cap;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + need / 8 + (1u << 20) > free_b + have) {
+            char msg[160]; snprintf(msg, sizeof msg, "svx_bam_sort_encode: the working buffers of %lld blocks (%zu bytes) do not fit into device memory", (long long)nb, need);
+            return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
+        }
+    }
+    std::vector<TgzBlock> hb((size_t)nb);
+    for (int64_t k = 0; k < nb; k++) {
+        const int64_t at = std::min<int64_t>((first + k) * BSORT_BLOCK, total);
+        hb[(size_t)k] = TgzBlock{(unsigned long long)(at - lo), (uint32_t)std::min<int64_t>(BSORT_BLOCK, total - at), 0u};
+    }
+    SVXCHK(S->piece.reserve((size_t)pb + 256)); SVXCHK(S->blocks.reserve((size_t)nb * sizeof(TgzBlock)));
+    SVXCHK(S->crc.reserve((size_t)nb * 4)); SVXCHK(S->bsize.reserve((size_t)(nb + 1) * 8)); SVXCHK(S->coff.reserve((size_t)(nb + 1) * 8)); SVXCHK(S->kinds.reserve(64));
+    SVXCHK(S->tok.reserve((size_t)chunk * DEF_BLOCK * 4)); SVXCHK(S->hist.reserve((size_t)chunk * DEF_NHIST * 4)); SVXCHK(S->nt.reserve((size_t)chunk * 4));
+    SVXCHK(S->codes.reserve((size_t)chunk * sizeof(DefBlockCodes))); SVXCHK(S->slots.reserve((size_t)nb * DEF_SLOT));
+    {
+        HostCopy hc(st);
+        SVXCHK(hc.h2d(S->blocks.p, hb.data(), (size_t)nb * sizeof(TgzBlock)));
+        if (!S->crc_shift.p) {
+            uint32_t m[CRC_POW][32];
+            crc_shift_matrices(m);
+            SVXCHK(S->crc_shift.reserve(sizeof m));
+            SVXCHK(hc.h2d(S->crc_shift.p, m, sizeof m));
+        }
+        SVXCHK(hc.finish());
+    }
+    uint8_t* piece = S->piece.as<uint8_t>();
+    const TgzBlock* blocks = S->blocks.as<TgzBlock>();
+    uint32_t *tok = S->tok.as<uint32_t>(), *hist = S->hist.as<uint32_t>(), *nt = S->nt.as<uint32_t>(), *crc = S->crc.as<uint32_t>();
+    int64_t *bsize = S->bsize.as<int64_t>(), *coff = S->coff.as<int64_t>();
+    unsigned long long* kinds = S->kinds.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(kinds, 0, 64, st));
+    HIPCHK(hipMemsetAsync(bsize + nb, 0, 8, st));
+    HIPCHK(hipMemsetAsync(piece + pb, 0, 192, st));
+    HIPCHK(hipStreamSynchronize(st));
+    double t[7]; t[0] = bs_now();
+    if (pb > 0) {
+        const BsSegs G{S->soff.as<int64_t>(), S->saddr.as<uint64_t>(), S->n + 1};
+        const long long tiles = (pb + BS_TILE - 1) / BS_TILE;
+        k_bs_gather<<<(unsigned)std::min<long long>(tiles, BS_MAX_GRID), BS_T, 0, st>>>(G, lo, pb, piece);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(st)); t[1] = bs_now();
+    k_tgz_crc<<<(unsigned)nb, 64, 0, st>>>(piece, blocks, nb, S->crc_shift.as<uint32_t>(), crc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st)); t[2] = bs_now();
+    double t_phase[3] = {0, 0, 0};
+    for (long long b0 = 0; b0 < nb; b0 += chunk) {
+        const unsigned g = (unsigned)std::min<long long>(chunk, nb - b0);
+        double u[4]; u[0] = bs_now();
+        k_tgz_match<<<g, 64, 0, st>>>(piece, blocks, b0, tok, hist, nt);
+        HIPCHK(hipStreamSynchronize(st)); u[1] = bs_now();
+        k_tgz_codes<<<g, 64, 0, st>>>(blocks, b0, hist, crc, S->codes.as<DefBlockCodes>(), bsize, kinds);
+        HIPCHK(hipStreamSynchronize(st)); u[2] = bs_now();
+        k_tgz_bits<<<g, 64, 0, st>>>(piece, blocks, b0, tok, nt, S->codes.as<DefBlockCodes>(), S->slots.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st)); u[3] = bs_now();
+        for (int k = 0; k < 3; k++) t_phase[k] += u[k + 1] - u[k];
+    }
+    t[3] = bs_now();
+    SVXCHK((svx_exclusive_scan<int64_t, int64_t>(bsize, coff, nb + 1, st, S->scan_tmp)));
+    std::vector<int64_t> h_coff((size_t)nb + 1, 0);
+    unsigned long long hk[3] = {0, 0, 0};
+    {
+        HostCopy hc(st);
+        SVXCHK(hc.d2h(h_coff.data(), coff, (size_t)(nb + 1) * 8));
+        SVXCHK(hc.d2h(hk, kinds, sizeof hk));
+        SVXCHK(hc.finish());
+    }
+    const int64_t n_out = h_coff[(size_t)nb];
+    if (n_out < 28 || n_out > nb * (int64_t)DEF_SLOT) return svx_fail(SVX_E_STATE, "svx_bam_sort_encode: the block sizes are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+    SVXCHK(S->out.reserve((size_t)n_out + 64));
+    k_tgz_compact<<<(unsigned)nb, TGZ_CT, 0, st>>>(S->slots.as<uint8_t>(), coff, nb, S->out.as<uint8_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st)); t[4] = bs_now();
+    if (first == S->next_block) {
+        for (int64_t k = 0; k < nb; k++) S->h_csize[(size_t)(first + k)] = h_coff[(size_t)k + 1] - h_coff[(size_t)k];
+        S->next_block = first + nb;
+    } else S->broken = true;
+    S->piece_bytes = pb; S->out_bytes = n_out; S->have_piece = true;
+    if (n_bytes) *n_bytes = n_out;
+    svx_bam_sort_stats& X = S->stats;
+    X.t_gather_ms += (t[1] - t[0]) * 1e3; X.t_crc_ms += (t[2] - t[1]) * 1e3; X.t_matches_ms += t_phase[0] * 1e3; X.t_codes_ms += t_phase[1] * 1e3; X.t_bits_ms += t_phase[2] * 1e3;
+    X.t_compaction_ms += (t[4] - t[3]) * 1e3; X.t_encode_ms += (t[4] - t[0]) * 1e3;
+    X.n_pieces++; X.gather_bytes += pb; X.piece_bytes_max = std::max<int64_t>(X.piece_bytes_max, pb);
+    X.blocks_stored += (int64_t)hk[DEF_KIND_STORED]; X.blocks_dynamic += (int64_t)hk[DEF_KIND_DYNAMIC]; X.blocks_eof += (int64_t)hk[DEF_KIND_EOF]; X.bytes_out += n_out;
+    return SVX_OK;
+}
+
+int bamsort_fetch(BamSort* S, uint8_t* compressed_dst, uint8_t* stream_dst, hipStream_t st) {
+    if (!S || !S->finished || !S->have_piece) return svx_fail(SVX_E_STATE, "svx_bam_sort_fetch without an encoded piece (svx_bam_sort_encode first)", __FILE__, __LINE__, hipSuccess);
+    HostCopy hc(st);
+    if (compressed_dst && S->out_bytes) SVXCHK(hc.d2h(compressed_dst, S->out.p, (size_t)S->out_bytes));
+    if (stream_dst && S->piece_bytes) SVXCHK(hc.d2h(stream_dst, S->piece.p, (size_t)S->piece_bytes));
+    SVXCHK(hc.finish());
+    HIPCHK(hipStreamSynchronize(st));
+    return SVX_OK;
+}
+
+int bamsort_index(BamSort* S, BamIndex* ix, hipStream_t st) {
+    if (!S || !S->finished || !ix) return svx_fail(SVX_E_STATE, "svx_bam_sort_index before svx_bam_sort_finish", __FILE__, __LINE__, hipSuccess);
+    if (S->broken || S->next_block != S->n_blocks)
+        return svx_fail(SVX_E_STATE, "svx_bam_sort_index: the file's blocks have not all been encoded in ascending, gap-free ranges", __FILE__, __LINE__, hipSuccess);
+    const double t0 = bs_now();
+    const int64_t nb = S->n_blocks;
+    std::vector<int64_t> h_coff((size_t)nb + 1, 0);
+    for (int64_t b = 0; b < nb; b++) h_coff[(size_t)b + 1] = h_coff[(size_t)b] + S->h_csize[(size_t)b];
+    SVXCHK(S->coff_all.reserve((size_t)(nb + 1) * 8));
+    SVXCHK(svx_h2d(S->coff_all.p, h_coff.data(), (size_t)(nb + 1) * 8, st));
+    SVXCHK(bamindex_take_rows(ix, S->rows, S->perm.as<uint32_t>(), S->soff.as<int64_t>() + 1, S->coff_all.as<int64_t>(), nb, BSORT_BLOCK, st));
+    // the data ends where the end-of-file block starts
+    SVXCHK(bamindex_finish(ix, S->n_ref, (uint64_t)h_coff[(size_t)nb - 1] << 16, st));
+    S->stats.t_index_ms = (bs_now() - t0) * 1e3;
+    return SVX_OK;
+}
+
+int bamsort_permutation(BamSort* S, uint32_t* host_perm, hipStream_t st) {
+    if (!S || !S->finished) return svx_fail(SVX_E_STATE, "svx_bam_sort_permutation before svx_bam_sort_finish", __FILE__, __LINE__, hipSuccess);
+    if (host_perm && S->n > 0) SVXCHK(svx_d2h(host_perm, S->perm.p, (size_t)S->n * 4, st));
+    return SVX_OK;
+}
+void bamsort_stats(const BamSort* S, svx_bam_sort_stats* out) {
+    if (S) *out = S->stats; else memset(out, 0, sizeof *out);
+}

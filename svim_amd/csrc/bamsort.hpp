@@ -1,0 +1,27 @@
+// bamsort.hpp - internal interface between the device reader (bamdev.hip) and the coordinate sort it can feed from its record stream (bamsort.hip).
+#pragma once
+#include "common.hpp"
+#include "bamindex.hpp"
+
+struct BamSort;
+// what one loaded chunk hands over: its n records lie back to back in stream[first_byte, end_byte), record i at rec_off[i]; the decoded columns are those the
+// index takes (device arrays)
+struct BamSortChunk {
+    long long n; const uint8_t* stream; uint64_t first_byte, end_byte; const uint64_t* rec_off;
+    const int32_t *tid, *pos; const uint16_t* flag; const uint64_t* cigar_off; const uint32_t* cigar;
+};
+int  bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref);      // an empty arena (the state is made on first use); max_bytes 0: what the device has free
+void bamsort_drop(BamSort* s);                                         // arena, rows and the encoder's buffers go back
+void bamsort_destroy(BamSort* s);
+// SVX_E_CAPACITY: the arena would pass max_bytes (nothing of the chunk is kept)
+int  bamsort_append(BamSort* s, const BamSortChunk& c, hipStream_t st);
+// header: the rewritten header (host).  SVX_E_ARG / SVX_E_RANGE: a record the definition refuses; SVX_E_CAPACITY: more than 2^32 - 1 records
+int  bamsort_finish(BamSort* s, const uint8_t* header, int64_t header_bytes, hipStream_t st);
+bool bamsort_finished(const BamSort* s);
+void bamsort_count(const BamSort* s, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
+int  bamsort_encode(BamSort* s, int64_t first_block, int64_t n_blocks, int64_t* n_bytes, hipStream_t st);
+int  bamsort_fetch(BamSort* s, uint8_t* compressed_dst, uint8_t* stream_dst, hipStream_t st);
+// the .bai of the encoded file into `ix` (SVX_E_STATE unless every block was encoded, in ascending gap-free ranges); SVX_E_RANGE as bamindex_finish
+int  bamsort_index(BamSort* s, BamIndex* ix, hipStream_t st);
+int  bamsort_permutation(BamSort* s, uint32_t* host_perm, hipStream_t st);
+void bamsort_stats(const BamSort* s, svx_bam_sort_stats* out);

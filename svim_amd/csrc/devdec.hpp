@@ -41,3 +41,18 @@ int  devdec_index_finish(svx_devdec* d, uint64_t v_end);
 bool devdec_index_bytes(const svx_devdec* d, int64_t* n_bytes);
 int  devdec_index_fetch(svx_devdec* d, uint8_t* host_dst);
 void devdec_index_stats(const svx_devdec* d, svx_bam_index_stats* out);
+// Coordinate sort from the record stream (bamsort.hip; include/svx.h: svx_bam_sort*).  begin: an empty arena, every later devdec_load appends the bytes and the
+// rows of the records it hands to devdec_count (once per chunk, on the loader's stream); a load whose records pass max_bytes fails with SVX_E_CAPACITY and drops
+// the sort.  finish (header: the rewritten header): appending is over, the sorted order and the stream layout stay until drop or the next begin.  encode / fetch /
+// index / permutation need a finished sort; index leaves its bytes where devdec_index_bytes / devdec_index_fetch read them.
+int  devdec_sort_begin(svx_devdec* d, int64_t max_bytes);
+void devdec_sort_drop(svx_devdec* d);
+bool devdec_sort_on(const svx_devdec* d);               // appending
+bool devdec_sort_finished(const svx_devdec* d);
+int  devdec_sort_finish(svx_devdec* d, const uint8_t* header, int64_t header_bytes);
+void devdec_sort_count(const svx_devdec* d, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
+int  devdec_sort_encode(svx_devdec* d, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
+int  devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_dst);
+int  devdec_sort_index(svx_devdec* d);
+int  devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm);
+void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out);

@@ -757,6 +757,49 @@ def index_bam(path, device=0, out=None, threads=0, batch_records=200_000):
     return data
 
 
+def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000):
+    """The BAM file at `path`, in any order, written to `out` in coordinate order (svim_amd/bamsort.py says what the sorted file is), and its index to
+    out + ".bai" when `index`: one pass of the device reader whose batches are read and discarded while every record stays on the device, a sort there, then
+    the file encoded and written in pieces of piece_blocks BGZF blocks - the whole file is never held in host memory (NativeBam.sort_*).  max_bytes: the most
+    the records may take on the device (0: what is free).  -> the sort's stats.  On failure the partial output is removed and the sort given up;
+    svim_amd.bamsort.BamSortError carries the library's status in .code."""
+    from .bamio import NativeBam
+    if piece_blocks < 1:
+        raise ValueError("sort_bam: piece_blocks must be at least 1")
+    bam = NativeBam(path, threads=threads)
+    written = []
+    try:
+        bam.set_device_decode(int(device))
+        bam.sort_begin(max_bytes)
+        try:
+            while bam.read_batch(batch_records, 0, "coordinate")[1]:
+                pass
+            _, _, n_blocks = bam.sort_finish()
+            written.append(out)
+            with open(out, "wb") as fh:
+                for first in range(0, n_blocks, piece_blocks):
+                    fh.write(bam.sort_encode(first, min(piece_blocks, n_blocks - first)))
+            if index:
+                data = bam.sort_index()
+                written.append(out + ".bai")
+                with open(out + ".bai", "wb") as fh:
+                    fh.write(data)
+            stats = bam.sort_stats()
+        except BaseException:
+            for f in written:
+                if os.path.exists(f):
+                    os.remove(f)
+            try:
+                bam.sort_abort()
+            except Exception:
+                pass
+            raise
+        bam.sort_abort()
+    finally:
+        bam.close()
+    return stats
+
+
 def shard_plan(references, lengths, bai, rank, world):
     """Contig ownership (multigpu.assign_contigs) and the file regions this rank reads: maximal runs of consecutive reference ids that are
     its own (contigs without records do not interrupt a run) -> (owner[n_ref], [(virtual offset of the run's first record, last reference id,

@@ -119,6 +119,19 @@ int devdec_index_finish(svx_devdec*, uint64_t) { return SVX_E_STATE; }
 bool devdec_index_bytes(const svx_devdec*, int64_t*) { return false; }
 int devdec_index_fetch(svx_devdec*, uint8_t*) { return SVX_E_STATE; }
 void devdec_index_stats(const svx_devdec*, svx_bam_index_stats* out) { memset(out, 0, sizeof *out); }
+// (so is the coordinate sort; the header rewrite it asks the host for lives in bamsort_host.cpp, which this program does not link)
+int devdec_sort_begin(svx_devdec*, int64_t) { return SVX_E_STATE; }
+void devdec_sort_drop(svx_devdec*) {}
+bool devdec_sort_on(const svx_devdec*) { return false; }
+bool devdec_sort_finished(const svx_devdec*) { return false; }
+int devdec_sort_finish(svx_devdec*, const uint8_t*, int64_t) { return SVX_E_STATE; }
+void devdec_sort_count(const svx_devdec*, int64_t*, int64_t*, int64_t*) {}
+int devdec_sort_encode(svx_devdec*, int64_t, int64_t, int64_t*) { return SVX_E_STATE; }
+int devdec_sort_fetch(svx_devdec*, uint8_t*, uint8_t*) { return SVX_E_STATE; }
+int devdec_sort_index(svx_devdec*) { return SVX_E_STATE; }
+int devdec_sort_permutation(svx_devdec*, uint32_t*) { return SVX_E_STATE; }
+void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
+extern "C" int svx_bam_sort_header_host(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
 
 static std::vector<uint8_t> read_file(const char* p) {
     std::vector<uint8_t> d; FILE* f = fopen(p, "rb"); if (!f) { perror(p); exit(2); }
