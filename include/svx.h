@@ -718,6 +718,35 @@ int  svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_t n_ref, u
 /* host-only: the header of the sorted file from a file's header (magic .. reference dictionary).  *n_out is the size also when cap is too small (SVX_E_CAPACITY) */
 int  svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out);
 
+/* ---- SAM text through the device reader (sam.hip, sam_core.hpp; the definition in words: svim_amd/sam.py) ----
+ * svx_sam_open gives the handle type of svx_bam_open for a file of uncompressed SAM text (what an aligner writes): the header is parsed on the host
+ * (svx_bam_header answers as for a BAM, sort_order from @HD), the alignment lines are turned into the BAM record stream on the device, slice by slice, and
+ * everything behind that - field, CIGAR, SA and name decode, query-name grouping, svx_bam_sort_*, svx_bam_rewind, the contig limit - is the BAM path.
+ * Device decode is the only reading route: svx_bam_read_batch before svx_bam_set_device_decode is SVX_E_STATE, and so are svx_bam_seek, svx_bam_index_begin
+ * and svx_bam_set_gpu_inflate on such a handle (text has no virtual offsets).  After a sort pass svx_bam_sort_index gives the .bai of the sorted file.
+ * A line the definition refuses fails the svx_bam_read_batch that would hand out the records of its slice: SVX_E_RANGE for a number that is missing, malformed
+ * or out of its field's range, SVX_E_ARG otherwise; svx_last_error names the line by its number in the file: the first bad line, and of several faults in it
+ * the first in the order svim_amd/sam.py states, as svx_sam_convert_host reports it.  The handle is usable again after svx_bam_rewind.
+ * An RNAME or RNEXT the @SQ lines do not hold is refused (htslib warns and writes -1): deliberate.  A file with alignment lines and no @SQ line does not open.
+ * Floats: at most 15 significant digits and a decimal exponent of at most 22 in magnitude are converted on the device (one correctly rounded operation on
+ * exact operands, then the cast to float); every other value is resolved by strtod on the host before the slice is handed out (n_patched_floats).
+ * SVX_SAM_DEV_CHUNK_BYTES (tests): the text bytes of a slice; a line longer than the slice makes it grow, and the grown slice ends behind that line. */
+typedef struct svx_sam_stats {
+    /* host clock, the stream drained at each boundary.  lines: newline marks and their scan; measure: the line ends, k_sam_measure, the scans of sizes and patch
+     * counts and their read-back; emit: k_sam_emit and the read-back of the patch list; patch: strtod, the values to the device, k_sam_patch */
+    double  t_stage_ms /* text to the device */, t_lines_ms, t_measure_ms, t_emit_ms, t_patch_ms;
+    double  t_measure_kernel_ms, t_emit_kernel_ms;      /* k_sam_measure and k_sam_emit alone, between events on the stream */
+    int64_t n_chunks, n_lines, n_records /* a read group re-read with the next slice (query-name mode) counts again */, text_bytes, stream_bytes, n_long_cigars, n_patched_floats;
+} svx_sam_stats;
+int  svx_sam_open(const char* path, int n_threads, svx_bam** out);
+int  svx_sam_get_stats(svx_bam* h, svx_sam_stats* out);          /* zeros for a BAM handle, and before device decode is on */
+/* host-only, no GPU: SAM text (header lines in front are skipped) -> the BAM records of its alignment lines.  names_blob: n_ref reference names, NUL-separated.
+ * *n_out is the size also when cap is too small (SVX_E_CAPACITY).  SVX_E_ARG / SVX_E_RANGE: *bad_line is the 1-based number of the first line refused. */
+int  svx_sam_convert_host(const uint8_t* text, int64_t n, int32_t n_ref, const char* names_blob, uint8_t* out, int64_t cap, int64_t* n_out, int64_t* n_records,
+                          int64_t* bad_line);
+/* host-only: the BAM header (magic, l_text, the text verbatim, the dictionary of its @SQ lines in order) of a SAM header text */
+int  svx_sam_header_host(const char* header_text, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

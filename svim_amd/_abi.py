@@ -259,6 +259,15 @@ class BamSortStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+# SAM text through the device reader (include/svx.h: svx_sam_*)
+class SamStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_stage_ms", "t_lines_ms", "t_measure_ms", "t_emit_ms", "t_patch_ms", "t_measure_kernel_ms", "t_emit_kernel_ms")] + \
+               [(n, C.c_int64) for n in ("n_chunks", "n_lines", "n_records", "text_bytes", "stream_bytes", "n_long_cigars", "n_patched_floats")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class GenotypeStats(C.Structure):
     _fields_ = [(n, C.c_double) for n in ("t_total_ms", "t_tables_ms", "t_distinct_ms", "t_walk_ms", "t_call_ms")] + \
                [(n, C.c_int64) for n in ("n_candidates", "n_members", "n_alignments")]

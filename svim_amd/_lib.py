@@ -36,7 +36,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_vcf_position_order", "svx_text_index", "svx_text_index_count", "svx_text_index_fetch", "svx_text_index_get_stats", "svx_text_index_host",
            "svx_bam_index_begin", "svx_bam_index_finish", "svx_bam_index_abort", "svx_bam_index_count", "svx_bam_index_fetch", "svx_bam_index_get_stats", "svx_bam_index_host",
            "svx_bam_sort_begin", "svx_bam_sort_finish", "svx_bam_sort_abort", "svx_bam_sort_count", "svx_bam_sort_encode", "svx_bam_sort_fetch", "svx_bam_sort_index",
-           "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host"]
+           "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host",
+           "svx_sam_open", "svx_sam_get_stats", "svx_sam_convert_host", "svx_sam_header_host"]
 
 
 class SvxError(RuntimeError):
@@ -215,6 +216,49 @@ def bam_sort_header_host(header):
     rc = lib().svx_bam_sort_header_host(ptr(src), C.c_int64(len(header)), ptr(out), C.c_int64(cap), C.byref(n))
     if rc != 0:
         raise SvxError("svx_bam_sort_header_host failed: %s" % _abi.ERRORS.get(rc, rc))
+    return out[:n.value].tobytes()
+
+
+def sam_convert_host(text, references, cap=None):
+    """svx_sam_convert_host (host-only, no GPU needed): SAM text (bytes; header lines in front are skipped) -> (the BAM records of its alignment lines back to
+    back, their number) by the host build of csrc/sam_core.hpp - what the device reader makes of the same text, and svim_amd.sam.record_bytes by the definition.
+    references: the names of the @SQ dictionary in order.  svim_amd.sam.SamError (code E_ARG / E_RANGE, .line) for a line the definition refuses.  cap: the
+    room to offer (tests); too little raises SvxError with .code SVX_E_CAPACITY and .needed"""
+    from . import sam
+    text = bytes(text)
+    src = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, np.uint8)
+    blob = b"".join(r.encode("latin-1") + b"\0" for r in references) + b"\0"
+    n, nrec, bad = C.c_int64(), C.c_int64(), C.c_int64()
+    want = len(text) * 2 + 64 if cap is None else int(cap)
+    while True:
+        out = np.zeros(max(1, want), dtype=np.uint8)
+        rc = lib().svx_sam_convert_host(ptr(src), C.c_int64(len(text)), C.c_int32(len(references)), C.c_char_p(blob), ptr(out), C.c_int64(want), C.byref(n), C.byref(nrec),
+                                        C.byref(bad))
+        if rc == _abi.SVX_E_CAPACITY and cap is None:
+            want = n.value
+            continue
+        break
+    if rc in (_abi.SVX_E_ARG, _abi.SVX_E_RANGE) and bad.value:
+        raise sam.SamError(rc, lib().svx_last_error().decode("utf-8", "replace"), bad.value)
+    if rc != 0:
+        e = SvxError("svx_sam_convert_host failed: %s" % _abi.ERRORS.get(rc, rc))
+        e.code, e.needed = rc, n.value
+        raise e
+    return out[:n.value].tobytes(), nrec.value
+
+
+def sam_header_host(header_text):
+    """svx_sam_header_host (host-only): the BAM header of a SAM header text, as svim_amd.sam.header_bytes defines it"""
+    header_text = bytes(header_text)
+    cap = len(header_text) * 2 + 64
+    out, n = np.zeros(cap, dtype=np.uint8), C.c_int64()
+    rc = lib().svx_sam_header_host(C.c_char_p(header_text), C.c_int64(len(header_text)), ptr(out), C.c_int64(cap), C.byref(n))
+    if rc == _abi.SVX_E_CAPACITY:
+        cap = n.value
+        out = np.zeros(cap, dtype=np.uint8)
+        rc = lib().svx_sam_header_host(C.c_char_p(header_text), C.c_int64(len(header_text)), ptr(out), C.c_int64(cap), C.byref(n))
+    if rc != 0:
+        raise SvxError("svx_sam_header_host failed: %s" % _abi.ERRORS.get(rc, rc))
     return out[:n.value].tobytes()
 
 

@@ -1,11 +1,23 @@
 """ctypes wrapper of the native BAM front-end (svim_amd/csrc/bamio.cpp): BGZF inflate + record decode into the record
-batch, on the host, without pysam.  Needs only libsvx.so - no GPU - so it is usable (and tested) on CPU."""
+batch, on the host, without pysam.  Needs only libsvx.so - no GPU - so it is usable (and tested) on CPU.
+A path that holds SAM text is opened through svx_sam_open: such a handle is read by the device reader only (svim_amd/sam.py says what its records are)."""
 import ctypes as C
 
 import numpy as np
 
 from . import _abi
 from ._lib import SvxError, lib
+
+
+def is_sam_text(path):
+    """SAM text: the first byte is '@', or the file does not start with the gzip magic (a BAM file is BGZF, which does) and its first byte may start a QNAME
+    ('!' to '~').  Everything else is left to svx_bam_open and its messages: an empty file, a file that cannot be read, bytes that are neither"""
+    try:
+        with open(path, "rb") as fh:
+            head = fh.read(2)
+    except OSError:
+        return False
+    return head[:1] == b"@" or (len(head) > 0 and head != b"\x1f\x8b" and 0x21 <= head[0] <= 0x7e)
 
 
 class NativeBam(object):
@@ -15,9 +27,13 @@ class NativeBam(object):
     def __init__(self, path, threads=0):
         self.L = lib()
         self.h = C.c_void_p()
-        rc = self.L.svx_bam_open(path.encode(), C.c_int(threads), C.byref(self.h))
+        self.is_sam = is_sam_text(path)
+        if self.is_sam:
+            rc = self.L.svx_sam_open(path.encode(), C.c_int(threads), C.byref(self.h))
+        else:
+            rc = self.L.svx_bam_open(path.encode(), C.c_int(threads), C.byref(self.h))
         if rc != 0:
-            raise SvxError("svx_bam_open(%r) failed: %s" % (path, self.L.svx_last_error().decode()))
+            raise SvxError("%s(%r) failed: %s" % ("svx_sam_open" if self.is_sam else "svx_bam_open", path, self.L.svx_last_error().decode()))
         n = C.c_int32()
         names, lens, so = C.c_char_p(), C.POINTER(C.c_int32)(), C.c_char_p()
         blob = C.c_void_p()
@@ -187,6 +203,12 @@ class NativeBam(object):
     def sort_stats(self):
         s = _abi.BamSortStats()
         self.L.svx_bam_sort_get_stats(self.h, C.byref(s))
+        return s.as_dict()
+
+    def sam_stats(self):
+        """what the SAM text front end has done for this handle (svx_sam_get_stats); zeros for a BAM file"""
+        s = _abi.SamStats()
+        self.L.svx_sam_get_stats(self.h, C.byref(s))
         return s.as_dict()
 
     def _sort_error(self, rc, what):

@@ -13,6 +13,8 @@
 #include "crc32_wave.hpp"
 #include "bamindex.hpp"
 #include "bamsort.hpp"
+#include "sam.hpp"
+#include "contig_core.hpp"
 #include <zlib.h>
 #include <chrono>
 #include <mutex>
@@ -37,13 +39,6 @@ __device__ __forceinline__ uint32_t ld32(const uint8_t* st, uint64_t p) {
     const uint32_t sh = (uint32_t)(p & 3u) * 8u;
     const uint32_t lo = w[0];
     return sh ? (lo >> sh) | (w[1] << (32u - sh)) : lo;
-}
-
-__host__ __device__ inline uint64_t dd_fnv(const uint8_t* p, uint32_t n, uint64_t seed) {
-    uint64_t h = 0xcbf29ce484222325ull ^ seed;
-    for (uint32_t i = 0; i < n; i++) { h ^= p[i]; h *= 0x100000001b3ull; }
-    h ^= h >> 29; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 32;
-    return h;
 }
 
 // could a BAM record start at byte p?  (SAM spec 4.2: block_size, refID, pos, l_read_name/mapq/bin, n_cigar_op/flag, l_seq, next_refID, next_pos, tlen)
@@ -167,8 +162,8 @@ __global__ void k_measure(const uint8_t* st, const uint64_t* rec_off, long long 
     d.cig_at = r + 32 + l_name; d.n_cig = ncf; d.seq_at = d.cig_at + 4ull * ncf; d.sa_at = 0; d.sa_len = 0; d.flags = 0;
     d.name_len = l_name ? l_name - 1u : 0u;
     if (end - r < 32 || d.seq_at + ((uint64_t)l_seq + 1) / 2 + l_seq > end) { atomicExch(err, DD_E_CORRUPT); d.n_cig = 0; d.name_len = 0; }
-    d.h1 = dd_fnv(st + r + 32, d.name_len, 0) | 1ull;                  // 0 marks an empty slot
-    d.h2 = dd_fnv(st + r + 32, d.name_len, 0x9E3779B97F4A7C15ull);
+    d.h1 = ctg_fnv(st + r + 32, d.name_len, 0) | 1ull;                  // 0 marks an empty slot
+    d.h2 = ctg_fnv(st + r + 32, d.name_len, 0x9E3779B97F4A7C15ull);
     // htslib's bam_tag2cigar (what pysam hands the reference): a mapped record (tid, pos >= 0) whose FIRST operation is a soft clip of the whole read carries
     // its real CIGAR in CG:B,I (or B,i) - whatever the rest of the placeholder looks like
     const bool want_cg = ncf >= 1u && (int32_t)ld32(st, r) >= 0 && (int32_t)ld32(st, r + 4) >= 0 && d.n_cig == ncf && (ld32(st, d.cig_at) & 15u) == 4u && (ld32(st, d.cig_at) >> 4) == l_seq;
@@ -225,8 +220,6 @@ __global__ void k_measure(const uint8_t* st, const uint64_t* rec_off, long long 
     n_cig[i] = d.n_cig; n_seg[i] = segs; n_segop[i] = ops;
 }
 
-struct ContigTable { const uint64_t* key; const int32_t* tid; uint32_t mask; const char* names; const uint32_t* name_off; };
-
 __device__ bool dd_parse_int(const uint8_t* s, uint64_t n, long long* v) {              // bamio.cpp parse_int
     if (n == 0) return false;
     uint64_t i = 0; bool neg = false;
@@ -269,19 +262,7 @@ __global__ void k_fields(const uint8_t* st, const uint64_t* rec_off, long long n
                 if (mq < 0 || mq > 255) mq = 0;
                 // reference name -> id (open addressing over the header's names; an unknown name yields -1)
                 const uint32_t ln = (uint32_t)(fs[1] - 1 - fs[0]);
-                const uint64_t hk = dd_fnv(st + fs[0], ln, 0) | 1ull;
-                int32_t t = -1;
-                for (uint32_t s = (uint32_t)hk & ct.mask;; s = (s + 1u) & ct.mask) {
-                    const uint64_t k = ct.key[s];
-                    if (!k) break;
-                    if (k == hk) {
-                        const int32_t cand = ct.tid[s];
-                        const uint32_t o0 = ct.name_off[cand], o1 = ct.name_off[cand + 1];
-                        bool same = o1 - o0 == ln;
-                        for (uint32_t c = 0; same && c < ln; c++) same = (uint8_t)ct.names[o0 + c] == st[fs[0] + c];
-                        if (same) { t = cand; break; }
-                    }
-                }
+                const int32_t t = ctg_lookup(ct, st + fs[0], ln);
                 seg_tid[row] = t; seg_pos[row] = (int32_t)(p1 - 1);
                 seg_rev[row] = (fs[3] - 1 - fs[2] == 1 && st[fs[2]] == '+') ? 0 : 1;
                 seg_mapq[row] = (uint8_t)mq; seg_lseq[row] = l_seq;
@@ -510,6 +491,7 @@ struct svx_devdec {
     unsigned long long* h_cnt = nullptr;       // pinned: indexed by the DD_H_* slots below, each written by one copy and read after the synchronise that follows it
     BamIndex* index = nullptr; bool index_on = false;      // svx_bam_index_begin: the row table every load appends to (bamindex.hip)
     BamSort* sort = nullptr; bool sort_on = false;         // svx_bam_sort_begin: the arena and the rows every load appends to (bamsort.hip)
+    SamDev* sam = nullptr;                                 // devdec_load_text: the scratch of the SAM text front end (sam.hip)
 };
 
 // slots of svx_devdec::h_cnt (pinned read-backs).  The loader thread (devdec_load / devdec_count) and the consumer (devdec_batch) use disjoint slots.
@@ -545,21 +527,10 @@ int devdec_create(int device, int n_threads, int32_t n_ref, const int32_t* ref_l
         SVXCHK(svx_h2d(d->contig_rank.p, contig_rank, nr * 4, d->stream));
     }
     // reference names: hash table name -> id for the SA tags
-    uint32_t cap = 16; while (cap < 4u * (uint32_t)nr) cap <<= 1;
-    std::vector<uint64_t> key(cap, 0); std::vector<int32_t> tid(cap, -1); std::vector<uint32_t> off(nr + 1, 0);
-    std::string blob;
-    const char* p = names_blob;
-    for (int32_t t = 0; t < n_ref; t++) {
-        const size_t ln = strlen(p);
-        off[(size_t)t] = (uint32_t)blob.size(); blob.append(p, ln);
-        const uint64_t h = dd_fnv(reinterpret_cast<const uint8_t*>(p), (uint32_t)ln, 0) | 1ull;
-        uint32_t s = (uint32_t)h & (cap - 1);
-        while (key[s]) s = (s + 1) & (cap - 1);
-        key[s] = h; tid[s] = t;
-        p += ln + 1;
-    }
-    off[nr > (size_t)n_ref ? (size_t)n_ref : nr] = (uint32_t)blob.size();
-    if (n_ref > 0) off[(size_t)n_ref] = (uint32_t)blob.size();
+    ContigTableHost ht;
+    ht.build(n_ref, names_blob);
+    const std::vector<uint64_t>& key = ht.key; const std::vector<int32_t>& tid = ht.tid; const std::vector<uint32_t>& off = ht.off; const std::string& blob = ht.blob;
+    const uint32_t cap = ht.mask + 1u;
     SVXCHK(d->ct_key.reserve((size_t)cap * 8)); SVXCHK(d->ct_tid.reserve((size_t)cap * 4)); SVXCHK(d->ct_names.reserve(blob.size() + 16)); SVXCHK(d->ct_name_off.reserve((nr + 1) * 4));
     SVXCHK(svx_h2d(d->ct_key.p, key.data(), (size_t)cap * 8, d->stream));
     SVXCHK(svx_h2d(d->ct_tid.p, tid.data(), (size_t)cap * 4, d->stream));
@@ -579,6 +550,7 @@ void devdec_destroy(svx_devdec* d) {
     (void)hipStreamSynchronize(d->batch_stream);
     if (d->inf) svx_inflater_destroy(d->inf);
     bamsort_destroy(d->sort); d->sort = nullptr;
+    samdev_destroy(d->sam); d->sam = nullptr;
     bamindex_destroy(d->index); d->index = nullptr;
     for (auto& c : d->chunk) c.release();
     DevBuf* all[] = {&d->ref_len, &d->contig_rank, &d->ct_key, &d->ct_tid, &d->ct_names, &d->ct_name_off, &d->err, &d->counters, &d->crc_shift, &d->batch_cnt, &d->nt_key, &d->nt_check, &d->nt_id};
@@ -612,6 +584,123 @@ static int dd_check(svx_devdec* d, const char* where) {
 }
 
 #define GRIDB(n, t) (unsigned)(((n) + (t) - 1) / (t))
+
+// the records of a chunk whose stream and rec_off are in place (c.data_begin, c.data_end, c.tail_start set; d->err cleared on the stream): the batch arrays, the
+// read names, the index and sort rows.  Shared by the BGZF route (devdec_load) and the SAM text route (devdec_load_text)
+static int dd_decode(svx_devdec* d, DevChunk& c, uint64_t n_rec, bool final_chunk, int min_mapq, int mode) {
+    hipStream_t st = d->stream;
+    uint8_t* sp = c.stream.as<uint8_t>();
+    double t0 = dd_now();
+    c.n_rec = (int64_t)n_rec;
+    if (n_rec == 0) { HIPCHK(hipStreamSynchronize(st)); c.loaded = true; return SVX_OK; }
+    // ---- decode ---------------------------------------------------------------------------------------------------------------------------------------
+    const long long n = (long long)n_rec;
+    const size_t N1 = (size_t)n + 1;
+    SVXCHK(c.desc.reserve((size_t)n * sizeof(RecDesc))); SVXCHK(c.n_cig.reserve(N1 * 4)); SVXCHK(c.n_seg.reserve(N1 * 4)); SVXCHK(c.n_segop.reserve(N1 * 4));
+    HIPCHK(hipMemsetAsync(c.n_cig.as<uint32_t>() + n, 0, 4, st)); HIPCHK(hipMemsetAsync(c.n_seg.as<uint32_t>() + n, 0, 4, st)); HIPCHK(hipMemsetAsync(c.n_segop.as<uint32_t>() + n, 0, 4, st));
+    k_measure<<<GRIDB(n, 128), 128, 0, st>>>(sp, c.rec_off.as<uint64_t>(), n, min_mapq, c.desc.as<RecDesc>(), c.n_cig.as<uint32_t>(), c.n_seg.as<uint32_t>(), c.n_segop.as<uint32_t>(),
+                                            d->err.as<int>());
+    HIPCHK(hipGetLastError());
+    SVXCHK(c.cigar_off.reserve(N1 * 8)); SVXCHK(c.seg_off.reserve(N1 * 4)); SVXCHK(c.segop_off.reserve(N1 * 8)); SVXCHK(c.name_at.reserve(N1 * 8));
+    // 32-bit counts -> 64-bit offsets: widen (into name_at as scratch), then scan
+    k_widen_u32<<<GRIDB(n + 1, 256), 256, 0, st>>>(n + 1, c.n_cig.as<uint32_t>(), c.name_at.as<uint64_t>());
+    SVXCHK(dd_scan<uint64_t>(d, c, c.name_at.as<uint64_t>(), c.cigar_off.as<uint64_t>(), N1));
+    SVXCHK(dd_scan<uint32_t>(d, c, c.n_seg.as<uint32_t>(), c.seg_off.as<uint32_t>(), N1));
+    k_widen_u32<<<GRIDB(n + 1, 256), 256, 0, st>>>(n + 1, c.n_segop.as<uint32_t>(), c.name_at.as<uint64_t>());
+    SVXCHK(dd_scan<uint64_t>(d, c, c.name_at.as<uint64_t>(), c.segop_off.as<uint64_t>(), N1));
+    HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_OPS], c.cigar_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_SEGOPS], c.segop_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_SEG], c.seg_off.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
+    SVXCHK(dd_check(d, "records"));
+    c.tot_ops = (int64_t)d->h_cnt[DD_H_OPS]; c.tot_segops = (int64_t)d->h_cnt[DD_H_SEGOPS]; c.tot_seg = (int64_t)(uint32_t)d->h_cnt[DD_H_SEG];
+    SVXCHK(c.flag.reserve(N1 * 2)); SVXCHK(c.tid.reserve(N1 * 4)); SVXCHK(c.pos.reserve(N1 * 4)); SVXCHK(c.mapq.reserve(N1)); SVXCHK(c.lseq.reserve(N1 * 4));
+    SVXCHK(c.read_id.reserve(N1 * 4)); SVXCHK(c.seq_off.reserve(N1 * 8)); SVXCHK(c.cigar.reserve((size_t)(c.tot_ops + 16) * 4));
+    const size_t S1 = (size_t)c.tot_seg + 1;
+    SVXCHK(c.seg_tid.reserve(S1 * 4)); SVXCHK(c.seg_pos.reserve(S1 * 4)); SVXCHK(c.seg_rev.reserve(S1)); SVXCHK(c.seg_mapq.reserve(S1)); SVXCHK(c.seg_lseq.reserve(S1 * 4));
+    SVXCHK(c.seg_cigar_off.reserve(S1 * 8)); SVXCHK(c.seg_cigar.reserve((size_t)(c.tot_segops + 16) * 4));
+    HIPCHK(hipMemsetAsync(c.seg_cigar_off.p, 0, 8, st));
+    HIPCHK(hipMemsetAsync(d->counters.p, 0, 256, st));
+    ContigTable ct{d->ct_key.as<uint64_t>(), d->ct_tid.as<int32_t>(), d->ct_mask, d->ct_names.as<char>(), d->ct_name_off.as<uint32_t>()};
+    k_fields<<<GRIDB(n, 128), 128, 0, st>>>(sp, c.rec_off.as<uint64_t>(), n, c.desc.as<RecDesc>(), c.seg_off.as<uint32_t>(), c.segop_off.as<uint64_t>(), ct, c.flag.as<uint16_t>(),
+                                           c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.mapq.as<uint8_t>(), c.lseq.as<int32_t>(), c.seq_off.as<uint64_t>(), c.seg_tid.as<int32_t>(),
+                                           c.seg_pos.as<int32_t>(), c.seg_rev.as<uint8_t>(), c.seg_mapq.as<uint8_t>(), c.seg_lseq.as<int32_t>(), c.seg_cigar_off.as<uint64_t>(),
+                                           c.seg_cigar.as<uint32_t>(), d->err.as<int>(), d->counters.as<unsigned long long>() + 4);
+    c.seq_end_host = c.data_end;
+    SVXCHK(svx_h2d(c.seq_off.as<uint64_t>() + n, &c.seq_end_host, 8, st));
+    k_cigar_copy<<<GRIDB(n, 4), 256, 0, st>>>(sp, n, c.desc.as<RecDesc>(), c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    d->stats.t_decode += dd_now() - t0; t0 = dd_now();
+    // ---- read names ---------------------------------------------------------------------------------------------------------------------------------
+    {
+        const size_t have = d->names.size();
+        if ((have + (size_t)n) * 2 > d->nt_cap) {                       // keep the load factor below one half: grow and re-insert
+            uint32_t cap = d->nt_cap; while ((have + (size_t)n) * 2 > cap) cap <<= 1;
+            DevBuf ok = d->nt_key, oc = d->nt_check, oi = d->nt_id; const uint32_t old_cap = d->nt_cap;
+            d->nt_key = DevBuf(); d->nt_check = DevBuf(); d->nt_id = DevBuf();
+            SVXCHK(dd_alloc_names(d, cap));
+            NameTable nt{d->nt_key.as<unsigned long long>(), d->nt_check.as<unsigned long long>(), d->nt_id.as<int32_t>(), cap - 1};
+            k_name_rehash<<<GRIDB(old_cap, 256), 256, 0, st>>>(old_cap, ok.as<unsigned long long>(), oc.as<unsigned long long>(), oi.as<int32_t>(), nt);
+            HIPCHK(hipStreamSynchronize(st));
+            ok.release(); oc.release(); oi.release();
+        }
+        NameTable nt{d->nt_key.as<unsigned long long>(), d->nt_check.as<unsigned long long>(), d->nt_id.as<int32_t>(), d->nt_cap - 1};
+        SVXCHK(c.slot_of.reserve((size_t)n * 4)); SVXCHK(c.new_rec.reserve((size_t)n * 4)); SVXCHK(c.name_len.reserve(N1 * 4));
+        unsigned int* n_new_dev = reinterpret_cast<unsigned int*>(d->counters.as<unsigned long long>() + 8);
+        k_name_insert<<<GRIDB(n, 256), 256, 0, st>>>(n, c.desc.as<RecDesc>(), nt, (int32_t)have, c.slot_of.as<uint32_t>(), n_new_dev, c.new_rec.as<uint32_t>());
+        k_name_ids<<<GRIDB(n, 256), 256, 0, st>>>(n, c.desc.as<RecDesc>(), nt, c.slot_of.as<uint32_t>(), c.read_id.as<int32_t>(), d->err.as<int>());
+        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_NEW], n_new_dev, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_SA_BAD], d->counters.as<unsigned long long>() + 4, 8, hipMemcpyDeviceToHost, st));
+        SVXCHK(dd_check(d, "fields / names"));
+        const long long n_new = (long long)(unsigned int)d->h_cnt[DD_H_NEW];
+        if (d->h_cnt[DD_H_SA_BAD]) fprintf(stderr, "WARNING: %llu SA tag entries do not consist of 6 fields. This could be a sign of invalid characters (e.g. commas or semicolons) in a "
+                                          "chromosome name of the reference genome.\n", (unsigned long long)d->h_cnt[DD_H_SA_BAD]);
+        if (n_new) {
+            HIPCHK(hipMemsetAsync(c.name_len.as<uint32_t>() + n_new, 0, 4, st));
+            k_name_lens<<<GRIDB(n_new, 256), 256, 0, st>>>(n_new, c.new_rec.as<uint32_t>(), c.desc.as<RecDesc>(), c.name_len.as<uint32_t>());
+            k_widen_u32<<<GRIDB(n_new + 1, 256), 256, 0, st>>>(n_new + 1, c.name_len.as<uint32_t>(), c.segop_off.as<uint64_t>());      // (segop_off is free again: scratch)
+            SVXCHK(dd_scan<uint64_t>(d, c, c.segop_off.as<uint64_t>(), c.name_at.as<uint64_t>(), (size_t)n_new + 1));
+            HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_BLOB], c.name_at.as<uint64_t>() + n_new, 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            const size_t blob_bytes = (size_t)d->h_cnt[DD_H_BLOB];
+            SVXCHK(c.name_blob.reserve(blob_bytes + 16));
+            k_name_copy<<<GRIDB(n_new, 256), 256, 0, st>>>(sp, c.rec_off.as<uint64_t>(), n_new, c.new_rec.as<uint32_t>(), c.desc.as<RecDesc>(), c.name_at.as<uint64_t>(), c.name_blob.as<char>());
+            std::vector<char> blob(blob_bytes + 1);
+            SVXCHK(svx_d2h(blob.data(), c.name_blob.p, blob_bytes, st));
+            d->names.reserve(have + (size_t)n_new);
+            const char* q = blob.data();
+            for (long long k = 0; k < n_new; k++) { const size_t ln = strlen(q); d->names.emplace_back(q, ln); q += ln + 1; }
+        }
+    }
+    d->stats.t_names += dd_now() - t0;
+    if (mode == 1 && !final_chunk) {
+        // query-name mode: the chunk may end in the middle of a read's group - the last group goes to the next chunk whole (carried over like a partial record)
+        unsigned long long* lg = d->counters.as<unsigned long long>() + 16;
+        HIPCHK(hipMemsetAsync(lg, 0, 8, st));
+        k_q_last_group<<<GRIDB(n, 256), 256, 0, st>>>(n, c.read_id.as<int32_t>(), lg);
+        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_LAST_GROUP], lg, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const long long L = (long long)d->h_cnt[DD_H_LAST_GROUP];
+        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_LAST_OFF], c.rec_off.as<uint64_t>() + L, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        c.tail_start = (size_t)d->h_cnt[DD_H_LAST_OFF];
+        c.n_rec = L;
+    }
+    if (d->index_on && c.n_rec > 0) {
+        const BamIndexChunk ic{(long long)c.n_rec, c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(), c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>(), c.rec_off.as<uint64_t>(),
+                               c.ix_start.data(), c.ix_vbase.data(), (long long)c.ix_start.size()};
+        SVXCHK(bamindex_append(d->index, ic, st));
+    }
+    if (d->sort_on && c.n_rec > 0) {
+        // the chunk's records lie back to back from its first byte to where its tail (a partial record, in query-name mode the last read's group) begins
+        const BamSortChunk sc{(long long)c.n_rec, sp, (uint64_t)c.data_begin, (uint64_t)c.tail_start, c.rec_off.as<uint64_t>(), c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(),
+                              c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>()};
+        const int rc = bamsort_append(d->sort, sc, st);
+        if (rc != SVX_OK) { d->sort_on = false; bamsort_drop(d->sort); return rc; }      // (SVX_E_CAPACITY: the arena is full - the sort is given up, the handle rewinds)
+    }
+    d->stats.records += c.n_rec;
+    c.loaded = true;
+    return SVX_OK;
+}
 
 int devdec_load(svx_devdec* d, int slot, const DevDecBlock* blocks, size_t nb_in, int carry_slot, uint64_t skip_bytes, bool final_chunk, int min_mapq, int mode) {
     if (mode == 1) min_mapq = 1000;            // query-name mode: the segment rows of a read are its supplementary RECORDS (devdec_batch), no SA tag is expanded
@@ -847,116 +936,32 @@ int devdec_load(svx_devdec* d, int slot, const DevDecBlock* blocks, size_t nb_in
     c.tail_start = (size_t)tail;
     if (final_chunk && tail != c.data_end) return svx_fail(SVX_E_ARG, "truncated BAM record at the end of the file", __FILE__, __LINE__, hipSuccess);
     c.n_rec = (int64_t)n_rec;
-    d->stats.t_discover += dd_now() - t0; t0 = dd_now();
-    if (n_rec == 0) { HIPCHK(hipStreamSynchronize(st)); c.loaded = true; return SVX_OK; }
-    // ---- decode ---------------------------------------------------------------------------------------------------------------------------------------
-    const long long n = (long long)n_rec;
-    const size_t N1 = (size_t)n + 1;
-    SVXCHK(c.desc.reserve((size_t)n * sizeof(RecDesc))); SVXCHK(c.n_cig.reserve(N1 * 4)); SVXCHK(c.n_seg.reserve(N1 * 4)); SVXCHK(c.n_segop.reserve(N1 * 4));
-    HIPCHK(hipMemsetAsync(c.n_cig.as<uint32_t>() + n, 0, 4, st)); HIPCHK(hipMemsetAsync(c.n_seg.as<uint32_t>() + n, 0, 4, st)); HIPCHK(hipMemsetAsync(c.n_segop.as<uint32_t>() + n, 0, 4, st));
-    k_measure<<<GRIDB(n, 128), 128, 0, st>>>(sp, c.rec_off.as<uint64_t>(), n, min_mapq, c.desc.as<RecDesc>(), c.n_cig.as<uint32_t>(), c.n_seg.as<uint32_t>(), c.n_segop.as<uint32_t>(),
-                                            d->err.as<int>());
-    HIPCHK(hipGetLastError());
-    SVXCHK(c.cigar_off.reserve(N1 * 8)); SVXCHK(c.seg_off.reserve(N1 * 4)); SVXCHK(c.segop_off.reserve(N1 * 8)); SVXCHK(c.name_at.reserve(N1 * 8));
-    // 32-bit counts -> 64-bit offsets: widen (into name_at as scratch), then scan
-    k_widen_u32<<<GRIDB(n + 1, 256), 256, 0, st>>>(n + 1, c.n_cig.as<uint32_t>(), c.name_at.as<uint64_t>());
-    SVXCHK(dd_scan<uint64_t>(d, c, c.name_at.as<uint64_t>(), c.cigar_off.as<uint64_t>(), N1));
-    SVXCHK(dd_scan<uint32_t>(d, c, c.n_seg.as<uint32_t>(), c.seg_off.as<uint32_t>(), N1));
-    k_widen_u32<<<GRIDB(n + 1, 256), 256, 0, st>>>(n + 1, c.n_segop.as<uint32_t>(), c.name_at.as<uint64_t>());
-    SVXCHK(dd_scan<uint64_t>(d, c, c.name_at.as<uint64_t>(), c.segop_off.as<uint64_t>(), N1));
-    HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_OPS], c.cigar_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_SEGOPS], c.segop_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_SEG], c.seg_off.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
-    SVXCHK(dd_check(d, "records"));
-    c.tot_ops = (int64_t)d->h_cnt[DD_H_OPS]; c.tot_segops = (int64_t)d->h_cnt[DD_H_SEGOPS]; c.tot_seg = (int64_t)(uint32_t)d->h_cnt[DD_H_SEG];
-    SVXCHK(c.flag.reserve(N1 * 2)); SVXCHK(c.tid.reserve(N1 * 4)); SVXCHK(c.pos.reserve(N1 * 4)); SVXCHK(c.mapq.reserve(N1)); SVXCHK(c.lseq.reserve(N1 * 4));
-    SVXCHK(c.read_id.reserve(N1 * 4)); SVXCHK(c.seq_off.reserve(N1 * 8)); SVXCHK(c.cigar.reserve((size_t)(c.tot_ops + 16) * 4));
-    const size_t S1 = (size_t)c.tot_seg + 1;
-    SVXCHK(c.seg_tid.reserve(S1 * 4)); SVXCHK(c.seg_pos.reserve(S1 * 4)); SVXCHK(c.seg_rev.reserve(S1)); SVXCHK(c.seg_mapq.reserve(S1)); SVXCHK(c.seg_lseq.reserve(S1 * 4));
-    SVXCHK(c.seg_cigar_off.reserve(S1 * 8)); SVXCHK(c.seg_cigar.reserve((size_t)(c.tot_segops + 16) * 4));
-    HIPCHK(hipMemsetAsync(c.seg_cigar_off.p, 0, 8, st));
-    HIPCHK(hipMemsetAsync(d->counters.p, 0, 256, st));
-    ContigTable ct{d->ct_key.as<uint64_t>(), d->ct_tid.as<int32_t>(), d->ct_mask, d->ct_names.as<char>(), d->ct_name_off.as<uint32_t>()};
-    k_fields<<<GRIDB(n, 128), 128, 0, st>>>(sp, c.rec_off.as<uint64_t>(), n, c.desc.as<RecDesc>(), c.seg_off.as<uint32_t>(), c.segop_off.as<uint64_t>(), ct, c.flag.as<uint16_t>(),
-                                           c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.mapq.as<uint8_t>(), c.lseq.as<int32_t>(), c.seq_off.as<uint64_t>(), c.seg_tid.as<int32_t>(),
-                                           c.seg_pos.as<int32_t>(), c.seg_rev.as<uint8_t>(), c.seg_mapq.as<uint8_t>(), c.seg_lseq.as<int32_t>(), c.seg_cigar_off.as<uint64_t>(),
-                                           c.seg_cigar.as<uint32_t>(), d->err.as<int>(), d->counters.as<unsigned long long>() + 4);
-    c.seq_end_host = c.data_end;
-    SVXCHK(svx_h2d(c.seq_off.as<uint64_t>() + n, &c.seq_end_host, 8, st));
-    k_cigar_copy<<<GRIDB(n, 4), 256, 0, st>>>(sp, n, c.desc.as<RecDesc>(), c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    d->stats.t_decode += dd_now() - t0; t0 = dd_now();
-    // ---- read names ---------------------------------------------------------------------------------------------------------------------------------
-    {
-        const size_t have = d->names.size();
-        if ((have + (size_t)n) * 2 > d->nt_cap) {                       // keep the load factor below one half: grow and re-insert
-            uint32_t cap = d->nt_cap; while ((have + (size_t)n) * 2 > cap) cap <<= 1;
-            DevBuf ok = d->nt_key, oc = d->nt_check, oi = d->nt_id; const uint32_t old_cap = d->nt_cap;
-            d->nt_key = DevBuf(); d->nt_check = DevBuf(); d->nt_id = DevBuf();
-            SVXCHK(dd_alloc_names(d, cap));
-            NameTable nt{d->nt_key.as<unsigned long long>(), d->nt_check.as<unsigned long long>(), d->nt_id.as<int32_t>(), cap - 1};
-            k_name_rehash<<<GRIDB(old_cap, 256), 256, 0, st>>>(old_cap, ok.as<unsigned long long>(), oc.as<unsigned long long>(), oi.as<int32_t>(), nt);
-            HIPCHK(hipStreamSynchronize(st));
-            ok.release(); oc.release(); oi.release();
-        }
-        NameTable nt{d->nt_key.as<unsigned long long>(), d->nt_check.as<unsigned long long>(), d->nt_id.as<int32_t>(), d->nt_cap - 1};
-        SVXCHK(c.slot_of.reserve((size_t)n * 4)); SVXCHK(c.new_rec.reserve((size_t)n * 4)); SVXCHK(c.name_len.reserve(N1 * 4));
-        unsigned int* n_new_dev = reinterpret_cast<unsigned int*>(d->counters.as<unsigned long long>() + 8);
-        k_name_insert<<<GRIDB(n, 256), 256, 0, st>>>(n, c.desc.as<RecDesc>(), nt, (int32_t)have, c.slot_of.as<uint32_t>(), n_new_dev, c.new_rec.as<uint32_t>());
-        k_name_ids<<<GRIDB(n, 256), 256, 0, st>>>(n, c.desc.as<RecDesc>(), nt, c.slot_of.as<uint32_t>(), c.read_id.as<int32_t>(), d->err.as<int>());
-        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_NEW], n_new_dev, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_SA_BAD], d->counters.as<unsigned long long>() + 4, 8, hipMemcpyDeviceToHost, st));
-        SVXCHK(dd_check(d, "fields / names"));
-        const long long n_new = (long long)(unsigned int)d->h_cnt[DD_H_NEW];
-        if (d->h_cnt[DD_H_SA_BAD]) fprintf(stderr, "WARNING: %llu SA tag entries do not consist of 6 fields. This could be a sign of invalid characters (e.g. commas or semicolons) in a "
-                                          "chromosome name of the reference genome.\n", (unsigned long long)d->h_cnt[DD_H_SA_BAD]);
-        if (n_new) {
-            HIPCHK(hipMemsetAsync(c.name_len.as<uint32_t>() + n_new, 0, 4, st));
-            k_name_lens<<<GRIDB(n_new, 256), 256, 0, st>>>(n_new, c.new_rec.as<uint32_t>(), c.desc.as<RecDesc>(), c.name_len.as<uint32_t>());
-            k_widen_u32<<<GRIDB(n_new + 1, 256), 256, 0, st>>>(n_new + 1, c.name_len.as<uint32_t>(), c.segop_off.as<uint64_t>());      // (segop_off is free again: scratch)
-            SVXCHK(dd_scan<uint64_t>(d, c, c.segop_off.as<uint64_t>(), c.name_at.as<uint64_t>(), (size_t)n_new + 1));
-            HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_BLOB], c.name_at.as<uint64_t>() + n_new, 8, hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            const size_t blob_bytes = (size_t)d->h_cnt[DD_H_BLOB];
-            SVXCHK(c.name_blob.reserve(blob_bytes + 16));
-            k_name_copy<<<GRIDB(n_new, 256), 256, 0, st>>>(sp, c.rec_off.as<uint64_t>(), n_new, c.new_rec.as<uint32_t>(), c.desc.as<RecDesc>(), c.name_at.as<uint64_t>(), c.name_blob.as<char>());
-            std::vector<char> blob(blob_bytes + 1);
-            SVXCHK(svx_d2h(blob.data(), c.name_blob.p, blob_bytes, st));
-            d->names.reserve(have + (size_t)n_new);
-            const char* q = blob.data();
-            for (long long k = 0; k < n_new; k++) { const size_t ln = strlen(q); d->names.emplace_back(q, ln); q += ln + 1; }
-        }
-    }
-    d->stats.t_names += dd_now() - t0;
-    if (mode == 1 && !final_chunk) {
-        // query-name mode: the chunk may end in the middle of a read's group - the last group goes to the next chunk whole (carried over like a partial record)
-        unsigned long long* lg = d->counters.as<unsigned long long>() + 16;
-        HIPCHK(hipMemsetAsync(lg, 0, 8, st));
-        k_q_last_group<<<GRIDB(n, 256), 256, 0, st>>>(n, c.read_id.as<int32_t>(), lg);
-        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_LAST_GROUP], lg, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const long long L = (long long)d->h_cnt[DD_H_LAST_GROUP];
-        HIPCHK(hipMemcpyAsync(&d->h_cnt[DD_H_LAST_OFF], c.rec_off.as<uint64_t>() + L, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        c.tail_start = (size_t)d->h_cnt[DD_H_LAST_OFF];
-        c.n_rec = L;
-    }
-    if (d->index_on && c.n_rec > 0) {
-        const BamIndexChunk ic{(long long)c.n_rec, c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(), c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>(), c.rec_off.as<uint64_t>(),
-                               c.ix_start.data(), c.ix_vbase.data(), (long long)c.ix_start.size()};
-        SVXCHK(bamindex_append(d->index, ic, st));
-    }
-    if (d->sort_on && c.n_rec > 0) {
-        // the chunk's records lie back to back from its first byte to where its tail (a partial record, in query-name mode the last read's group) begins
-        const BamSortChunk sc{(long long)c.n_rec, sp, (uint64_t)c.data_begin, (uint64_t)c.tail_start, c.rec_off.as<uint64_t>(), c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(),
-                              c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>()};
-        const int rc = bamsort_append(d->sort, sc, st);
-        if (rc != SVX_OK) { d->sort_on = false; bamsort_drop(d->sort); return rc; }      // (SVX_E_CAPACITY: the arena is full - the sort is given up, the handle rewinds)
-    }
-    d->stats.records += c.n_rec;
-    c.loaded = true;
-    return SVX_OK;
+    d->stats.t_discover += dd_now() - t0;
+    return dd_decode(d, c, n_rec, final_chunk, min_mapq, mode);
 }
+
+// SAM text route: a slice of whole alignment lines (host memory) -> the slot's stream and rec_off by the kernels of sam.hip, then the decode of every route.
+// Nothing is carried over between slices: *consumed = the text bytes whose records the slot holds (query-name mode leaves the last read's group to the next slice,
+// which starts at that group's first line), *n_lines = their lines.
+int devdec_load_text(svx_devdec* d, int slot, const uint8_t* text, size_t n, bool final_chunk, int min_mapq, int mode, int64_t line_base, uint64_t* consumed, int64_t* n_lines) {
+    if (mode == 1) min_mapq = 1000;
+    if (!d || slot < 0 || slot > 2) return svx_fail(SVX_E_ARG, "bad slot", __FILE__, __LINE__, hipSuccess);
+    HIPCHK(hipSetDevice(d->device));
+    hipStream_t st = d->stream;
+    DevChunk& c = d->chunk[slot];
+    c.loaded = false; c.n_rec = c.tot_seg = c.tot_ops = c.tot_segops = 0;
+    if (!d->sam) SVXCHK(samdev_create(&d->sam));
+    const ContigTable ct{d->ct_key.as<uint64_t>(), d->ct_tid.as<int32_t>(), d->ct_mask, d->ct_names.as<char>(), d->ct_name_off.as<uint32_t>()};
+    uint64_t total = 0; int64_t n_rec = 0;
+    SVXCHK(samdev_convert(d->sam, text, n, line_base, ct, c.stream, &total, c.rec_off, &n_rec, st));
+    c.data_begin = 0; c.data_end = (size_t)total; c.tail_start = (size_t)total;
+    d->stats.bytes += (int64_t)total;
+    HIPCHK(hipMemsetAsync(d->err.p, 0, 64, st));
+    SVXCHK(dd_decode(d, c, (uint64_t)n_rec, final_chunk, min_mapq, mode));
+    *n_lines = c.n_rec;
+    return samdev_line_start(d->sam, c.n_rec, consumed, st);
+}
+void devdec_sam_stats(const svx_devdec* d, svx_sam_stats* out) { samdev_stats(d->sam, out); }
 
 int devdec_sort_begin(svx_devdec* d, int64_t max_bytes) {
     HIPCHK(hipSetDevice(d->device));

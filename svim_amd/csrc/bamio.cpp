@@ -29,6 +29,7 @@
 #include <mutex>
 #include "../../include/svx.h"
 #include "devdec.hpp"
+#include "sam_host.hpp"
 
 extern thread_local std::string g_svx_err;
 static int bam_fail(int code, const std::string& what) { g_svx_err = what; return code; }
@@ -217,6 +218,10 @@ struct svx_bam {
     int dev_grow = 0;                         // a chunk without one complete record is loaded again, into the same slot, with 2^dev_grow times the budget
     size_t dev_region_bytes = 0;              // contig-range reading: budget of the next chunk (small after a seek, x4 per chunk: a range is not read 8 GB beyond its end)
     std::future<DevLoad> dev_future; bool dev_prefetching = false;
+    // svx_sam_open: the file is SAM text.  header_bytes is the length of its header lines; the device reader takes slices of whole lines (devdec_load_text) where
+    // a BAM handle takes BGZF blocks, and nothing else differs.  sam_at / sam_lines: file offsets the loader has seen and the lines in front of them (messages)
+    bool is_sam = false; int64_t sam_header_lines = 0;
+    size_t sam_at[2] = {0, 0}; int64_t sam_lines[2] = {0, 0};
 };
 
 static void dev_drop_prefetch(svx_bam* h);
@@ -461,6 +466,7 @@ static void drop_gpu(svx_bam* h) {
 
 extern "C" int svx_bam_set_gpu_inflate(svx_bam* h, int device) {
     if (!h) return bam_fail(SVX_E_ARG, "null handle");
+    if (h->is_sam) return bam_fail(SVX_E_STATE, "svx_bam_set_gpu_inflate: a SAM text handle has nothing to inflate");
     if (h->prefetch_active) h->prefetch.wait();          // the chunk being inflated stays what it is; the next one sees the new setting
     drop_gpu(h);
     if (device < 0) return SVX_OK;
@@ -554,6 +560,61 @@ extern "C" int svx_bam_open(const char* path, int n_threads, svx_bam** out) {
     return SVX_OK;
 }
 
+// rank of each contig NAME in Python str order (bytewise for ASCII names)
+static void rank_contigs(svx_bam* h) {
+    const uint32_t n_ref = (uint32_t)h->ref_names.size();
+    std::vector<int32_t> idx(n_ref);
+    for (uint32_t i = 0; i < n_ref; i++) idx[i] = (int32_t)i;
+    std::sort(idx.begin(), idx.end(), [&](int32_t a, int32_t b) { return h->ref_names[(size_t)a] < h->ref_names[(size_t)b]; });
+    h->contig_rank.assign(n_ref ? n_ref : 1, 0);
+    for (uint32_t r = 0; r < n_ref; r++) h->contig_rank[(size_t)idx[r]] = (int32_t)r;
+}
+
+// SAM text (include/svx.h): the header lines are parsed here, the alignment lines are left to the device reader
+extern "C" int svx_sam_open(const char* path, int n_threads, svx_bam** out) {
+    if (!path || !out) return bam_fail(SVX_E_ARG, "svx_sam_open: null argument");
+    svx_bam* h = new svx_bam();
+    h->path = path; h->is_sam = true;
+    h->n_threads = n_threads > 0 ? n_threads : default_threads();
+    h->fd = open(path, O_RDONLY);
+    struct stat sb;
+    if (h->fd < 0 || fstat(h->fd, &sb) != 0) { if (h->fd >= 0) close(h->fd); delete h; return bam_fail(SVX_E_ARG, std::string("cannot open ") + path); }
+    h->map_len = (size_t)sb.st_size;
+    if (h->map_len) {
+        void* m = mmap(nullptr, h->map_len, PROT_READ, MAP_PRIVATE, h->fd, 0);
+        if (m == MAP_FAILED) { close(h->fd); delete h; return bam_fail(SVX_E_ARG, std::string("cannot map ") + path); }
+        h->map = (const uint8_t*)m;
+        (void)madvise(m, h->map_len, MADV_SEQUENTIAL);
+    }
+    std::string err;
+    if (h->map_len >= 2 && h->map[0] == 31 && h->map[1] == 139) err = "compressed SAM is not read (gzip magic)";
+    size_t p = 0;
+    while (err.empty() && p < h->map_len && h->map[p] == '@') {
+        const void* nl = memchr(h->map + p, '\n', h->map_len - p);
+        p = nl ? (size_t)((const uint8_t*)nl - h->map) + 1 : h->map_len;
+        h->sam_header_lines++;
+    }
+    h->header_bytes = p;
+    if (err.empty() && sam_header_parse((const char*)h->map, p, &h->ref_names, &h->ref_len, &h->sort_order) != SVX_OK) err = "an @SQ line without SN or LN";
+    if (err.empty() && p < h->map_len && h->ref_names.empty()) err = "alignment lines but no @SQ line";
+    if (!err.empty()) {
+        if (h->map) munmap((void*)h->map, h->map_len);
+        close(h->fd); delete h;
+        return bam_fail(SVX_E_ARG, std::string("svx_sam_open(") + path + "): " + err);
+    }
+    for (size_t i = 0; i < h->ref_names.size(); i++) { h->tid_of.emplace(h->ref_names[i], (int32_t)i); h->names_blob += h->ref_names[i]; h->names_blob.push_back('\0'); }
+    rank_contigs(h);
+    h->dev_chunk_bytes = (size_t)128 << 20;
+    *out = h;
+    return SVX_OK;
+}
+extern "C" int svx_sam_get_stats(svx_bam* h, svx_sam_stats* out) {
+    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
+    memset(out, 0, sizeof *out);
+    if (h->dev && h->is_sam) devdec_sam_stats(h->dev, out);
+    return SVX_OK;
+}
+
 extern "C" void svx_bam_close(svx_bam* h) {
     if (!h) return;
     if (h->prefetch_active) { h->prefetch.wait(); h->prefetch_active = false; }
@@ -595,6 +656,7 @@ extern "C" int svx_bam_set_seq_filter(svx_bam* h, int min_ins_len) {
 // treat the first record whose reference id is above `last_tid` (or unplaced) as the end of the file.  last_tid = -2 lifts the limit.
 extern "C" int svx_bam_seek(svx_bam* h, uint64_t voff, int32_t last_tid) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
+    if (h->is_sam) return bam_fail(SVX_E_STATE, "svx_bam_seek: SAM text has no virtual offsets");
     if (h->dev && devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_seek while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
     if (h->dev && devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_seek during a sort pass (svx_bam_sort_finish or svx_bam_sort_abort first)");
     if (h->prefetch_active) { h->prefetch.wait(); h->prefetch_active = false; }
@@ -637,6 +699,7 @@ extern "C" int svx_bam_rewind(svx_bam* h) {
         h->total_records = 0; h->tid_limit = -2; h->region_done = false;
         return SVX_OK;
     }
+    if (h->is_sam) { h->total_records = 0; h->tid_limit = -2; h->region_done = false; return SVX_OK; }      // (device decode is its only reading route)
     h->fpos = 0; h->file_eof = false; h->buf.clear(); h->pos = 0; h->next_len = 0; h->next_eof = false;
     try {
         if (!ensure(h, 12)) throw std::string("not a BAM file");
@@ -940,6 +1003,31 @@ static void clear_batch(svx_bam* h) {
 static svx_bam::DevLoad dev_load_chunk(svx_bam* h, int slot, int carry_slot, uint64_t skip, int min_mapq, int mode, size_t budget_bytes, size_t budget_blocks) {
     svx_bam::DevLoad r;
     r.slot = slot; r.carry_slot = carry_slot; r.skip = skip; r.fpos_start = h->dev_fpos;
+    if (h->is_sam) {
+        // a slice of the mapped text cut behind its last newline; what is left of the budget's reach belongs to the next slice.  The file's last line need not end in one.
+        // A slice that had to grow for a line longer than the budget ends behind that line (its first newline), so that it holds no more than it grew for - except in
+        // query-name mode, where a slice also grows for a read group and must reach the first line of the next one
+        const size_t start = std::min(h->dev_fpos + (size_t)skip, h->map_len);
+        size_t end = std::min(h->map_len, start + std::min(budget_bytes, (size_t)1 << 30));
+        if (start >= h->map_len) { r.file_done = true; r.empty = true; return r; }
+        const bool first_line_only = h->dev_grow > 0 && mode != 1;          // (dev_grow is set before the loader is started and stays until its result is taken)
+        const void* nl = first_line_only ? memchr(h->map + start, '\n', end - start) : (end < h->map_len ? memrchr(h->map + start, '\n', end - start) : nullptr);
+        if (nl) end = (size_t)((const uint8_t*)nl - h->map) + 1;
+        else if (end < h->map_len) return r;                        // not one whole line: the same slot again with twice the budget (read_batch_device)
+        const bool final_chunk = end == h->map_len;
+        const int64_t line_base = start == h->sam_at[1] ? h->sam_lines[1] : start == h->sam_at[0] ? h->sam_lines[0] : h->sam_header_lines;
+        try {
+            uint64_t consumed = 0; int64_t n_lines = 0;
+            r.rc = devdec_load_text(h->dev, slot, h->map + start, end - start, final_chunk, min_mapq, mode, line_base, &consumed, &n_lines);
+            if (r.rc == SVX_OK) r.rc = devdec_count(h->dev, slot, h->tid_limit, &r.n_rec, &r.n_valid);
+            if (r.rc != SVX_OK) { r.err = svx_last_error(); return r; }
+            h->sam_at[0] = start; h->sam_lines[0] = line_base;
+            h->sam_at[1] = start + (size_t)consumed; h->sam_lines[1] = line_base + n_lines;
+            h->dev_fpos = start + (size_t)consumed;
+            r.file_done = final_chunk && start + (size_t)consumed == h->map_len;
+        } catch (const std::exception& e) { r.rc = SVX_E_ARG; r.err = e.what(); }
+        return r;
+    }
     std::vector<DevDecBlock> blocks;
     size_t total = 0;
     try {
@@ -1031,6 +1119,7 @@ extern "C" int svx_bam_set_device_decode(svx_bam* h, int device) {
     h->dev_device = device;
     { const char* e = getenv("SVX_BAM_DEV_CHUNK_MB"); if (e && atoll(e) > 0) h->dev_chunk_bytes = (size_t)atoll(e) << 20; }
     { const char* e = getenv("SVX_BAM_DEV_CHUNK_BLOCKS"); if (e && atoll(e) > 0) h->dev_chunk_blocks = (size_t)atoll(e); }
+    if (h->is_sam) { h->dev_chunk_bytes = (size_t)128 << 20; const char* e = getenv("SVX_SAM_DEV_CHUNK_BYTES"); if (e && atoll(e) > 0) h->dev_chunk_bytes = (size_t)atoll(e); }
     if (h->prefetch_active) { h->prefetch.wait(); h->prefetch_active = false; }
     h->dev_fpos = 0; h->dev_skip = h->header_bytes; h->dev_file_done = false; h->dev_region_done = false; h->dev_cur = -1; h->dev_first = h->dev_valid = 0; h->dev_have_carry = false;
     h->dev_last_slot = h->dev_handed_slot = -1; h->dev_grow = 0; h->dev_region_bytes = 0;                      // a fresh decoder: nothing handed out from its slots yet
@@ -1041,6 +1130,7 @@ extern "C" int svx_bam_set_device_decode(svx_bam* h, int device) {
 // ---- BAM index from the device reader's record stream (include/svx.h; bamdev.hip appends the rows, bamindex.hip builds the bytes) ------------------------
 extern "C" int svx_bam_index_begin(svx_bam* h) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
+    if (h->is_sam) return bam_fail(SVX_E_STATE, "svx_bam_index_begin: SAM text has no virtual offsets (sort it: svx_bam_sort_index gives the sorted file's index)");
     if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_index_begin: the index is built from the device reader's record stream (svx_bam_set_device_decode first)");
     if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
         return bam_fail(SVX_E_STATE, "svx_bam_index_begin: the handle is not at its first record (begin before the first read, or rewind first)");
@@ -1087,6 +1177,12 @@ extern "C" int svx_bam_index_get_stats(svx_bam* h, svx_bam_index_stats* out) {
 // the header as the file holds it (magic .. reference dictionary), inflated from the first blocks of the mapped file
 static int raw_header(svx_bam* h, std::vector<uint8_t>& out) {
     out.clear();
+    if (h->is_sam) {                                             // the BAM header of the text's header lines (sam_host.cpp)
+        int64_t n = 0;
+        int rc = svx_sam_header_host((const char*)h->map, (int64_t)h->header_bytes, nullptr, 0, &n);
+        if (rc == SVX_E_CAPACITY) { out.resize((size_t)n); rc = svx_sam_header_host((const char*)h->map, (int64_t)h->header_bytes, out.data(), n, &n); }
+        return rc == SVX_OK ? SVX_OK : bam_fail(rc, "svx_bam_sort_finish: the SAM header cannot be turned into a BAM header");
+    }
     size_t fp = 0;
     std::swap(fp, h->fpos);                                      // (read_block walks h->fpos; the host reader is idle in device mode)
     std::string err;
@@ -1184,6 +1280,7 @@ extern "C" int svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out) {
 
 extern "C" int svx_bam_read_batch(svx_bam* h, int64_t max_records, int mode, int min_mapq, svx_batch* out, int64_t* n_out) {
     if (h->dev) return read_batch_device(h, max_records, mode == 1 ? 1 : 0, min_mapq, out, n_out);
+    if (h->is_sam) return bam_fail(SVX_E_STATE, "svx_bam_read_batch: SAM text is read by the device reader only (svx_bam_set_device_decode first)");
     BatchArrays* const handed_out = h->b;                                                 // the set the previous call handed out: the caller may still upload from it
     try {
         h->b = &h->ba[h->b == &h->ba[0] ? 1 : 0];                                        // the previous batch stays valid during this read

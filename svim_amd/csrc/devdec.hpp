@@ -19,6 +19,11 @@ void devdec_destroy(svx_devdec* d);
 // mode 1 = query-name-sorted input (src/svim/SVIM_COLLECT.py:96-129): no SA tag is expanded, and unless final_chunk the last read's group of the chunk is left to the
 // next load (groups never straddle loads).
 int  devdec_load(svx_devdec* d, int slot, const DevDecBlock* blocks, size_t n, int carry_slot, uint64_t skip_bytes, bool final_chunk, int min_mapq, int mode);
+// The same for a slice of SAM text made of whole alignment lines (sam.hip builds the record stream from it; nothing is carried over between slices).
+// line_base: lines of the file in front of the slice.  *consumed: the text bytes whose records the slot holds - all of them, except in query-name mode, where the
+// last read's group is left to the next slice.  A refused line: SVX_E_ARG / SVX_E_RANGE, named by its number in the file.
+int  devdec_load_text(svx_devdec* d, int slot, const uint8_t* text, size_t n, bool final_chunk, int min_mapq, int mode, int64_t line_base, uint64_t* consumed, int64_t* n_lines);
+void devdec_sam_stats(const svx_devdec* d, svx_sam_stats* out);
 // records decoded in the slot; n_valid: those before the first record whose reference id is negative or above tid_limit (tid_limit -2: all)
 int  devdec_count(svx_devdec* d, int slot, int32_t tid_limit, int64_t* n_rec, int64_t* n_valid);
 // device-resident svx_batch over records [first, first + count) of the slot (arrays stay valid until the slot is loaded again)

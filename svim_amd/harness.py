@@ -53,6 +53,9 @@ class BamPipeline(object):
         if device_decode is None:                                   # default on a GPU engine, either sort order (SVX_BAM_DEVICE_DECODE=0: host reader)
             device_decode = dev is not None and mode in ("coordinate", "queryname") and gpu_inflate is not False and os.environ.get("SVX_BAM_DEVICE_DECODE", "1") != "0"
         self.device_decode = bool(device_decode)
+        if self.bam.is_sam and not self.device_decode:
+            self.bam.close()
+            raise ValueError("SAM text is read by the device reader only (device_decode)")
         if build_index and not self.device_decode:
             self.bam.close()
             raise ValueError("build_index needs device decode: the index is built from the device reader's record stream")
@@ -758,7 +761,7 @@ def index_bam(path, device=0, out=None, threads=0, batch_records=200_000):
 
 
 def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000):
-    """The BAM file at `path`, in any order, written to `out` in coordinate order (svim_amd/bamsort.py says what the sorted file is), and its index to
+    """The BAM file (or the SAM text: NativeBam tells them apart) at `path`, in any order, written to `out` in coordinate order (svim_amd/bamsort.py says what the sorted file is), and its index to
     out + ".bai" when `index`: one pass of the device reader whose batches are read and discarded while every record stays on the device, a sort there, then
     the file encoded and written in pieces of piece_blocks BGZF blocks - the whole file is never held in host memory (NativeBam.sort_*).  max_bytes: the most
     the records may take on the device (0: what is free).  -> the sort's stats.  On failure the partial output is removed and the sort given up;
@@ -785,6 +788,8 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
                 with open(out + ".bai", "wb") as fh:
                     fh.write(data)
             stats = bam.sort_stats()
+            if bam.is_sam:
+                stats["sam"] = bam.sam_stats()
         except BaseException:
             for f in written:
                 if os.path.exists(f):
@@ -798,6 +803,33 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
     finally:
         bam.close()
     return stats
+
+
+def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000):
+    """SAM text at `sam` -> a BAM file at `out_bam`: the reference's `samtools view -b | samtools sort` and `samtools index` (src/svim/SVIM_alignment.py).
+    sort=True: one pass of the device reader, coordinate order and, with `index`, out_bam + ".bai" (sort_bam does it: svim_amd/sam.py says what the records are,
+    svim_amd/bamsort.py what the sorted file is) -> the sort's stats with the front end's under "sam".
+    sort=False: the records in file order under the header the text has; no index - a file in file order has none.  This route is the HOST's: the host build
+    of the converter (svx_sam_convert_host) and of the encoder (svx_text_gz_host) write the bytes the device builds write, the file is held in host memory
+    once, and `device` and the sort's limits play no part -> {"n_records", "text_bytes", "stream_bytes"}."""
+    from .bamio import is_sam_text
+    from . import _lib, sam as samdef
+    if not is_sam_text(sam):
+        raise ValueError("sam_to_bam: %r is not SAM text" % sam)
+    if sort:
+        return sort_bam(sam, out_bam, device=device, index=index, piece_blocks=piece_blocks, max_bytes=max_bytes, threads=threads, batch_records=batch_records)
+    if index:
+        raise ValueError("sam_to_bam: index=True needs sort=True (records in file order have no index)")
+    with open(sam, "rb") as fh:
+        text = fh.read()
+    head, lines = samdef.split_text(text)
+    if lines and not samdef.dictionary(head):
+        raise samdef.SamError(samdef.E_ARG, "alignment lines but no @SQ line")
+    header = _lib.sam_header_host(head)
+    stream, n_rec = _lib.sam_convert_host(text, [n for n, _ in samdef.dictionary(head)])
+    with open(out_bam, "wb") as fh:
+        fh.write(_lib.text_gz_host(header + stream))
+    return {"n_records": n_rec, "text_bytes": len(text), "stream_bytes": len(stream)}
 
 
 def shard_plan(references, lengths, bai, rank, world):

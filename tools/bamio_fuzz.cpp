@@ -132,6 +132,11 @@ int devdec_sort_index(svx_devdec*) { return SVX_E_STATE; }
 int devdec_sort_permutation(svx_devdec*, uint32_t*) { return SVX_E_STATE; }
 void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
 extern "C" int svx_bam_sort_header_host(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
+// SAM text (svx_sam_open): the front end is the device's (sam.hip) and the header parser sam_host.cpp's; neither is part of this program
+int devdec_load_text(svx_devdec*, int, const uint8_t*, size_t, bool, int, int, int64_t, uint64_t*, int64_t*) { return SVX_E_STATE; }
+void devdec_sam_stats(const svx_devdec*, svx_sam_stats* out) { memset(out, 0, sizeof *out); }
+int sam_header_parse(const char*, size_t, std::vector<std::string>*, std::vector<int32_t>*, std::string*) { return SVX_E_STATE; }
+extern "C" int svx_sam_header_host(const char*, int64_t, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
 
 static std::vector<uint8_t> read_file(const char* p) {
     std::vector<uint8_t> d; FILE* f = fopen(p, "rb"); if (!f) { perror(p); exit(2); }
