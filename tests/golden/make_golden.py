@@ -14,6 +14,10 @@ modules of this container (CPython 3.10.12, scipy 1.15.3); their versions are re
 Outputs are DATA ONLY: inputs (SAM text, signature rows, condensed matrices) and the reference's
 outputs for them.  No reference source is copied.
 
+Goldens written by the generators beside this one (they import this module for the stubs):
+g_bed_cases (make_golden_bed.py), g_combine_cases (make_golden_combine.py), g_segments_cases
+(make_golden_segments.py), g_vcf_cases (make_golden_vcf.py), g_hap_cases (make_golden_hap.py).
+
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 """
 import gzip
