@@ -385,6 +385,11 @@ extern "C" int svx_cluster(svx_ctx* c, int source, const svx_sig_view* sigs, int
     if (!c || !p || !contig_rank_host) return svx_fail(SVX_E_ARG, "null argument", __FILE__, __LINE__, hipSuccess);
     HIPCHK(hipSetDevice(c->device));
     SVXCHK(upload(c, c->c_rank, contig_rank_host, (size_t)n_contig * 4));
+    c->c_rank_max = 0;                                      // sizes the ordering key (cluster.hip)
+    for (int32_t k = 0; k < n_contig; k++) {
+        if (contig_rank_host[k] < 0) { c->c_rank_max = -1; break; }
+        if (contig_rank_host[k] > c->c_rank_max) c->c_rank_max = contig_rank_host[k];
+    }
     ClusterIn in;
     if (source == 0 || source == 1) {
         DevSigs& s = c->accumulate ? (source ? c->acc_bnd : c->acc_sig) : (source ? c->bnd : c->sig);

@@ -29,17 +29,32 @@ struct EditWork { uint32_t a, b; long long slot; };
 // ---------------------------------------------------------------------------------------------------------
 // sort keys (get_key): hi = type | rank1 | rank2, lo = biased coordinate
 // ---------------------------------------------------------------------------------------------------------
+// the fields of get_key: type, rank of the first and of the second contig compared, coordinate
+struct KeyFields { int t; uint64_t r1, r2; int32_t coord; };
+__device__ __forceinline__ KeyFields key_fields(const ClusterIn& in, const int32_t* rank, long long i) {
+    KeyFields k; k.t = in.type[i]; k.r2 = 0;
+    if (k.t == SVX_INS) { k.r1 = (uint64_t)rank[in.contig[i]]; k.coord = in.start[i]; }
+    else if (k.t == SVX_DUP_INT) { k.r1 = (uint64_t)rank[in.contig2[i]]; k.r2 = (uint64_t)rank[in.contig[i]]; k.coord = in.pos2[i]; }
+    else if (k.t == SVX_BND) { k.r1 = (uint64_t)rank[in.contig[i]]; k.coord = in.start[i]; }
+    else { k.r1 = (uint64_t)rank[in.contig[i]]; k.coord = in.end[i]; }
+    return k;
+}
 __global__ void k_make_keys(ClusterIn in, const int32_t* rank, uint64_t* hi, uint64_t* lo, uint32_t* idx) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= in.n) return;
-    const int t = in.type[i];
-    uint64_t r1, r2 = 0; int32_t coord;
-    if (t == SVX_INS) { r1 = (uint64_t)rank[in.contig[i]]; coord = in.start[i]; }
-    else if (t == SVX_DUP_INT) { r1 = (uint64_t)rank[in.contig2[i]]; r2 = (uint64_t)rank[in.contig[i]]; coord = in.pos2[i]; }
-    else if (t == SVX_BND) { r1 = (uint64_t)rank[in.contig[i]]; coord = in.start[i]; }
-    else { r1 = (uint64_t)rank[in.contig[i]]; coord = in.end[i]; }
-    hi[i] = ((uint64_t)t << 56) | (r1 << 28) | r2;
-    lo[i] = (uint64_t)((uint32_t)coord ^ 0x80000000u);
+    const KeyFields k = key_fields(in, rank, i);
+    hi[i] = ((uint64_t)k.t << 56) | (k.r1 << 28) | k.r2;
+    lo[i] = (uint64_t)((uint32_t)k.coord ^ 0x80000000u);
+    idx[i] = (uint32_t)i;
+}
+
+// the same order in ONE key when the ranks need only b bits each:  type (3) | rank1 (b) | rank2 (b) | biased coordinate (32), 35 + 2 b <= 64.
+// Order-isomorphic to (hi, lo): the fields keep their order of significance and every field its own order; key >> 32 stands for hi.
+__global__ void k_make_key1(ClusterIn in, const int32_t* rank, int b, uint64_t* key, uint32_t* idx) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= in.n) return;
+    const KeyFields k = key_fields(in, rank, i);
+    key[i] = ((((uint64_t)k.t << b | k.r1) << b | k.r2) << 32) | (uint64_t)((uint32_t)k.coord ^ 0x80000000u);
     idx[i] = (uint32_t)i;
 }
 
@@ -54,12 +69,13 @@ __global__ void k_gather_u64(const uint64_t* src, const uint32_t* idx, uint64_t*
 }
 
 // new-partition flags in sorted order (form_partitions: gap to the PREVIOUS element only)
-__global__ void k_part_flags(ClusterIn in, const uint64_t* hi_sorted, const uint32_t* sidx, long long max_distance, int64_t* flag) {
+// hi_sorted >> hi_shift = type and contig ranks (0 for the hi words of k_make_keys, 32 for the single key of k_make_key1)
+__global__ void k_part_flags(ClusterIn in, const uint64_t* hi_sorted, int hi_shift, const uint32_t* sidx, long long max_distance, int64_t* flag) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i > in.n) return;
     if (i == in.n) { flag[i] = 0; return; }
     int f = 1;
-    if (i > 0 && hi_sorted[i] == hi_sorted[i - 1]) {          // same type and same contig(s)
+    if (i > 0 && (hi_sorted[i] >> hi_shift) == (hi_sorted[i - 1] >> hi_shift)) {          // same type and same contig(s)
         const uint32_t a = sidx[i - 1], b = sidx[i];
         const int t = in.type[b];
         long long d;
@@ -912,7 +928,7 @@ __global__ __launch_bounds__(64) void k_cluster(long long n_part, const int64_t*
 __global__ __launch_bounds__(64) void k_finalize(long long n_part, const int64_t* samp_base, const int32_t* ncl, const int64_t* clu_off,
                                                  const int64_t* mem_off, Stage st, uint8_t* o_type, uint8_t* o_aux, int32_t* o_contig, int32_t* o_start,
                                                  int32_t* o_end, int32_t* o_contig2, int32_t* o_start2, int32_t* o_end2, double* o_score, double* o_span,
-                                                 double* o_pos, int32_t* o_size, int64_t* o_moff, int64_t* o_part, uint64_t* o_key, const int32_t* rank) {
+                                                 double* o_pos, int32_t* o_size, int64_t* o_moff, int64_t* o_part, uint64_t* o_key, const int32_t* rank, int rank_bits) {
     const long long pt = blockIdx.x;
     if (pt >= n_part) return;
     const int n = ncl[pt];
@@ -924,7 +940,8 @@ __global__ __launch_bounds__(64) void k_finalize(long long n_part, const int64_t
         o_contig2[d] = st.contig2[s]; o_start2[d] = st.start2[s]; o_end2[d] = st.end2[s]; o_score[d] = st.score[s]; o_span[d] = st.std_span[s];
         o_pos[d] = st.std_pos[s]; o_size[d] = st.size[s]; o_moff[d] = mb + st.mem_local[s]; o_part[d] = pt;
         // final order: type-major; unilocal types by (contig name rank, start+end) (SVIM_clustering.py:381), bilocal types keep partition order
-        uint64_t key = (uint64_t)t << 60;
+        // rank_bits = 26: type at bit 60, the whole word; fewer: the same fields packed into 37 + rank_bits bits (the same order, fewer radix passes)
+        uint64_t key = (uint64_t)t << (34 + rank_bits);
         if (t <= SVX_INV) key |= ((uint64_t)rank[st.contig[s]] << 34) | (uint64_t)((long long)st.start[s] + st.end[s] + (1ll << 32));
         o_key[d] = key;
     }
@@ -1233,15 +1250,33 @@ static int svx_cluster_body(svx_ctx* c, const ClusterIn& in, int32_t n_contig, c
     // ---- sort by (type, contig ranks, coordinate), stable w.r.t. list order --------------------------------------
     SVXCHK(c->k_hi.reserve((size_t)n * 8)); SVXCHK(c->k_lo.reserve((size_t)n * 8)); SVXCHK(c->k_idx.reserve((size_t)n * 4));
     SVXCHK(c->k_hi2.reserve((size_t)n * 8)); SVXCHK(c->k_lo2.reserve((size_t)n * 8)); SVXCHK(c->k_idx2.reserve((size_t)n * 4));
-    k_make_keys<<<GRID(n, T), T, 0, st>>>(in, rank, c->k_hi.as<uint64_t>(), c->k_lo.as<uint64_t>(), c->k_idx.as<uint32_t>());
-    SVXCHK(svx_sort_pairs_u64(c, c->k_lo.as<uint64_t>(), c->k_lo2.as<uint64_t>(), c->k_idx.as<uint32_t>(), c->k_idx2.as<uint32_t>(), n, 0, 32));
-    k_gather_u64<<<GRID(n, T), T, 0, st>>>(c->k_hi.as<uint64_t>(), c->k_idx2.as<uint32_t>(), c->k_hi2.as<uint64_t>(), n);
-    SVXCHK(svx_sort_pairs_u64(c, c->k_hi2.as<uint64_t>(), c->k_hi.as<uint64_t>(), c->k_idx2.as<uint32_t>(), c->k_idx.as<uint32_t>(), n, 0, 64));
-    const uint64_t* hi_sorted = c->k_hi.as<uint64_t>();
-    const uint32_t* sidx = c->k_idx.as<uint32_t>();
+    // One key and one sort where the ranks leave room (b bits each, 35 + 2 b <= 64: up to 16 384 contigs), 5-8 passes; else - or with SVX_CLUSTER_ONE_SORT=0, read per
+    // call - the coordinate word first (4 passes), then type | rank1 | rank2 (8 passes) behind a gather.  Both are stable LSD sorts: the same order, ties in list order.
+    // The key of the final cluster order (k_finalize) is packed the same way, 37 + b bits instead of 64, under a switch of its own (SVX_CLUSTER_NARROW_KEY=0).
+    int rank_bits = 1;
+    while (rank_bits < 31 && ((long long)c->c_rank_max >> rank_bits) != 0) rank_bits++;
+    bool one_sort = c->c_rank_max >= 0 && 35 + 2 * rank_bits <= 64;
+    if (const char* e = getenv("SVX_CLUSTER_ONE_SORT")) if (atoi(e) == 0) one_sort = false;
+    bool narrow_key = c->c_rank_max >= 0 && rank_bits <= 26;
+    if (const char* e = getenv("SVX_CLUSTER_NARROW_KEY")) if (atoi(e) == 0) narrow_key = false;
+    const int final_rank_bits = narrow_key ? rank_bits : 26;
+    const uint64_t* hi_sorted; const uint32_t* sidx; int hi_shift;
+    if (one_sort) {
+        k_make_key1<<<GRID(n, T), T, 0, st>>>(in, rank, rank_bits, c->k_lo.as<uint64_t>(), c->k_idx2.as<uint32_t>());
+        SVXCHK(svx_sort_pairs_u64(c, c->k_lo.as<uint64_t>(), c->k_hi.as<uint64_t>(), c->k_idx2.as<uint32_t>(), c->k_idx.as<uint32_t>(), n, 0, 35 + 2 * rank_bits));
+        hi_shift = 32;
+    } else {
+        k_make_keys<<<GRID(n, T), T, 0, st>>>(in, rank, c->k_hi.as<uint64_t>(), c->k_lo.as<uint64_t>(), c->k_idx.as<uint32_t>());
+        SVXCHK(svx_sort_pairs_u64(c, c->k_lo.as<uint64_t>(), c->k_lo2.as<uint64_t>(), c->k_idx.as<uint32_t>(), c->k_idx2.as<uint32_t>(), n, 0, 32));
+        k_gather_u64<<<GRID(n, T), T, 0, st>>>(c->k_hi.as<uint64_t>(), c->k_idx2.as<uint32_t>(), c->k_hi2.as<uint64_t>(), n);
+        SVXCHK(svx_sort_pairs_u64(c, c->k_hi2.as<uint64_t>(), c->k_hi.as<uint64_t>(), c->k_idx2.as<uint32_t>(), c->k_idx.as<uint32_t>(), n, 0, 64));
+        hi_shift = 0;
+    }
+    hi_sorted = c->k_hi.as<uint64_t>();
+    sidx = c->k_idx.as<uint32_t>();
     // ---- partitions ------------------------------------------------------------------------------------------------
     SVXCHK(c->part_flag.reserve((size_t)(n + 1) * 8)); SVXCHK(c->part_id.reserve((size_t)(n + 1) * 8));
-    k_part_flags<<<GRID(n + 1, T), T, 0, st>>>(in, hi_sorted, sidx, p.partition_max_distance, c->part_flag.as<int64_t>());
+    k_part_flags<<<GRID(n + 1, T), T, 0, st>>>(in, hi_sorted, hi_shift, sidx, p.partition_max_distance, c->part_flag.as<int64_t>());
     SVXCHK(svx_exclusive_scan_i64(c, c->part_flag.as<int64_t>(), c->part_id.as<int64_t>(), n + 1));
     int64_t n_part = 0;
     SVXCHK(svx_mail_read(c, st, c->part_id.as<int64_t>() + n, 1, &n_part));
@@ -1525,7 +1560,7 @@ static int svx_cluster_body(svx_ctx* c, const ClusterIn& in, int32_t n_contig, c
     SVXCHK(c->tmp1.reserve((size_t)(nmem + 1) * 4));
     int32_t* u_members = c->tmp1.as<int32_t>();
     k_finalize<<<(unsigned)n_part, 64, 0, st>>>(n_part, samp_base, ncl_a, clu_off, mem_off, stg, u_type, u_aux, u_contig, u_start, u_end, u_contig2, u_start2,
-                                               u_end2, u_score, u_span, u_pos, u_size, u_moff, u_part, u_key, rank);
+                                               u_end2, u_score, u_span, u_pos, u_size, u_moff, u_part, u_key, rank, final_rank_bits);
     k_copy_members<<<(unsigned)n_part, 64, 0, st>>>(n_part, samp_base, nmem_a, mem_off, stg.members, u_members);
     HIPCHK(hipGetLastError());
     // final stable order
@@ -1538,7 +1573,7 @@ static int svx_cluster_body(svx_ctx* c, const ClusterIn& in, int32_t n_contig, c
         uint64_t* key2 = c->tmp2.as<uint64_t>(); uint32_t* perm0 = reinterpret_cast<uint32_t*>(key2 + CN); uint32_t* perm = perm0 + CN;
         int64_t* src_moff = reinterpret_cast<int64_t*>(perm + CN);
         k_iota_u32c<<<GRID(ncl, T), T, 0, st>>>(perm0, ncl);
-        SVXCHK(svx_sort_pairs_u64(c, u_key, key2, perm0, perm, ncl, 0, 64));
+        SVXCHK(svx_sort_pairs_u64(c, u_key, key2, perm0, perm, ncl, 0, narrow_key ? 37 + rank_bits : 64));      // type | rank | start + end: 5 passes for up to 8 contigs, 8 over the whole word
         k_permute_clusters<<<GRID(ncl + 1, T), T, 0, st>>>(ncl, perm, u_type, u_aux, u_contig, u_start, u_end, u_contig2, u_start2, u_end2, u_score, u_span,
                                                           u_pos, u_size, u_moff, u_part, out.type.as<uint8_t>(), out.aux.as<uint8_t>(),
                                                           out.contig.as<int32_t>(), out.start.as<int32_t>(), out.end.as<int32_t>(),

@@ -687,6 +687,78 @@ __global__ __launch_bounds__(256) void k_gather_seq(SigPtrs s, long long n, cons
     }
 }
 
+// The same with every loaded byte used once: 16 bases per lane and step - one 8-byte load and one 16-byte store while 16 more bases of THIS slice remain, so the
+// load stays inside the slice's own bytes; byte accesses for the last chunk.  A slice that starts on a low nibble gives its first base away (lane 0, one byte), so
+// that every chunk starts on a byte.  Two steps are loaded before either is stored: an insertion of ~370 bases is two steps of its 16 lanes, one round trip
+// instead of two.
+__device__ __forceinline__ unsigned long long spread_bytes(unsigned v) {           // byte j of v -> byte 2 j
+    unsigned long long x = v;
+    x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+    return (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+}
+__global__ __launch_bounds__(256) void k_gather_seq16(SigPtrs s, long long n, const int64_t* seq_off, uint8_t* __restrict__ seq_out,
+                                                      const uint64_t* rec_seq_off, const uint8_t* __restrict__ rec_seq, const uint32_t* rng_off, const int32_t* rng_q0,
+                                                      const int32_t* rng_len, const uint64_t* rng_byte, unsigned long long* missing) {
+    constexpr int GS = 16;
+    const int lane = lane_id() & (GS - 1);
+    const long long i = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * (64 / GS) + (lane_id() / GS);
+    if (i >= n) return;
+    int len = s.qlen[i];
+    if (len <= 0) return;
+    const uint8_t* src;
+    uint8_t* dst = seq_out + seq_off[i];
+    int q0 = s.qpos[i];
+    if (rng_off) {
+        const int rec = s.rec[i];
+        src = nullptr;
+        for (uint32_t r = rng_off[rec]; r < rng_off[rec + 1]; r++) {
+            const int a = rng_q0[r];
+            if (a <= q0 && q0 + len <= a + rng_len[r]) { src = rec_seq + rng_byte[r]; q0 -= a; break; }      // a is even: nibble parity is kept
+        }
+        if (!src) { if (lane == 0) atomicAdd(missing, 1ull); return; }
+    } else src = rec_seq + rec_seq_off[s.rec[i]];
+    const bool lead = (q0 & 1) && lane == 0;                         // the low nibble of the slice's first byte: loaded here, stored behind the chunks (no wait of its own)
+    uint8_t* const lead_dst = dst;
+    const unsigned lead_byte = lead ? src[q0 >> 1] : 0u;
+    if (q0 & 1) { q0++; dst++; len--; }
+    src += q0 >> 1;                                                  // base k of what is left: nibble k of src[], high nibble first
+    if (len < 16) {                                                  // fewer than 8 bytes: no 8-byte load fits into the slice
+        for (int t = lane; t < len; t += GS) { const uint8_t by = src[t >> 1]; dst[t] = (t & 1) ? (by & 15) : (by >> 4); }
+        if (lead) lead_dst[0] = (uint8_t)(lead_byte & 15u);
+        return;
+    }
+    // bases k .. k + 15 of a full chunk (k + 16 <= len) are the bytes k / 2 .. k / 2 + 7, all the slice's own.  The last chunk has 1..8 bytes: it loads the
+    // slice's LAST 8 bytes (the slice has that many) and shifts its own down - one load either way, and nothing but the load inside the guard
+    const int last = (len - 1) >> 1;                                 // the slice's last byte
+    auto place = [&](const int k, int& at, int& sh) {
+        const bool full = k + 16 <= len;
+        at = full ? (k >> 1) : last - 7;
+        sh = full ? 0 : 8 * (7 - (last - (k >> 1)));
+    };
+    auto store16 = [&](const int k, const unsigned long long x) {
+        const unsigned long long hi = (x >> 4) & 0x0f0f0f0f0f0f0f0full, lo = x & 0x0f0f0f0f0f0f0f0full;      // high nibble first in every byte
+        unsigned long long out[2];
+        out[0] = spread_bytes((unsigned)hi) | (spread_bytes((unsigned)lo) << 8);
+        out[1] = spread_bytes((unsigned)(hi >> 32)) | (spread_bytes((unsigned)(lo >> 32)) << 8);
+        if (k + 16 <= len) __builtin_memcpy(dst + k, out, 16);
+        else {
+#pragma unroll
+            for (int t = 0; t < 15; t++) if (k + t < len) dst[k + t] = (uint8_t)(out[t >> 3] >> (8 * (t & 7)));
+        }
+    };
+    for (int k0 = lane * 16; k0 < len; k0 += 2 * 16 * GS) {
+        const int k1 = k0 + 16 * GS;
+        int at0, sh0, at1, sh1;
+        place(k0, at0, sh0); place(k1, at1, sh1);
+        unsigned long long x0, x1 = 0;
+        __builtin_memcpy(&x0, src + at0, 8);
+        if (k1 < len) __builtin_memcpy(&x1, src + at1, 8);
+        store16(k0, x0 >> sh0);
+        if (k1 < len) store16(k1, x1 >> sh1);
+    }
+    if (lead) lead_dst[0] = (uint8_t)(lead_byte & 15u);
+}
+
 static int order_and_store(svx_ctx* c, DevSigs& raw, DevSigs& out, int64_t n) {
     hipStream_t st = c->stream;
     SVXCHK(out.reserve(n + 1));
@@ -813,7 +885,9 @@ int svx_collect_impl(svx_ctx* c, const svx_batch* bd, const svx_params* p) {
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, c->sig.qlen.as<int32_t>(), c->sig.seq_off.as<int64_t>(), n_sig + 1));
         SVXCHK(svx_mail_read(c, st, c->sig.seq_off.as<int64_t>() + n_sig, 1, &n_seq));
         SVXCHK(c->sig.seq.reserve((size_t)n_seq + 16));
-        k_gather_seq<<<(unsigned)((n_sig + 15) / 16), 256, 0, st>>>(sig_ptrs(c->sig), n_sig, c->sig.seq_off.as<int64_t>(), c->sig.seq.as<uint8_t>(),
+        bool gather16 = true;                               // SVX_GATHER_SEQ16=0 (read per call): 8 bases per load and store, as up to round 6 (A/B switch)
+        if (const char* e = getenv("SVX_GATHER_SEQ16")) gather16 = atoi(e) != 0;
+        (gather16 ? k_gather_seq16 : k_gather_seq)<<<(unsigned)((n_sig + 15) / 16), 256, 0, st>>>(sig_ptrs(c->sig), n_sig, c->sig.seq_off.as<int64_t>(), c->sig.seq.as<uint8_t>(),
                                                                  b.seq_off, b.seq, b.seq_rng_off, b.seq_rng_q0, b.seq_rng_len, b.seq_rng_byte,
                                                                  c->counters.as<unsigned long long>() + CNT_SEQ_MISSING);
         HIPCHK(hipGetLastError());

@@ -154,7 +154,7 @@ struct svx_ctx {
     // genome
     DevBuf g_off, g_codes; int32_t g_n = 0; bool g_borrowed = false; const int64_t* g_off_p = nullptr; const uint8_t* g_codes_p = nullptr;
     // CLUSTER workspace + results
-    DevBuf user_sig[12]; DevBuf c_rank;
+    DevBuf user_sig[12]; DevBuf c_rank; int32_t c_rank_max = -1;     // contig ranks of the last svx_cluster and the largest of them (-1: a negative one was passed)
     DevBuf k_hi, k_lo, k_idx, k_hi2, k_lo2, k_idx2, part_flag, part_id, part_start, part_meta, samp_idx, large_list, samp_stream;
     DevBuf cell_shards;
     DevBuf geno[11]; int64_t geno_n = 0; int32_t geno_contigs = -1;      // GENOTYPE: resident alignment index + per-call candidate buffers

@@ -351,10 +351,14 @@ __global__ __launch_bounds__(256) void k_hap_pack(long long n_rec, PairSource sr
 #ifndef PREP_LANES
 #define PREP_LANES 16
 #endif
+#ifndef PREP_DEPTH
+#define PREP_DEPTH 4
+#endif
 // ---- 2. trim + classify (PREP_LANES lanes per pair, reads only the packed store) ---------------------------------------------------
 // G lanes per pair (64 / G pairs per wave): the kernel is bound by the latency of its dependent loads, so what counts is the number of
 // pairs in flight, not the symbols compared per step
-template <int G>
+// K: chunks per lane in the later trips of a bound pass (bound_at below)
+template <int G, int K>
 __global__ __launch_bounds__(256) void k_edit_prep(long long n_work, PairSource src, const uint32_t* packed, PairDesc* desc,
                                                    uint64_t* sort_key, uint32_t* sort_val, int32_t* ed, unsigned long long* cells, int shift_bounds) {
     const int wave_lane = lane_id();
@@ -429,28 +433,54 @@ __global__ __launch_bounds__(256) void k_edit_prep(long long n_work, PairSource 
     // mismatch from the first symbols on).  A tight bound does two things: the pair starts in the narrowest band that certifies it, and the
     // staircase window narrows against the bound instead of against the window's own capacity (d_edit_stair).
     const uint32_t* wp = packed + P.word_off; const uint32_t* wt = packed + T.word_off;
-    // (Round 6, measured and dropped - none of them moves the kernel's 1.7 ms: four chunks per lane and trip with all eight loads issued up front (1.94-2.04 ms: the
-    // lanes of a last trip load for nothing); 32 symbols per lane and trip - five words of either string, four funnel shifts, ~45 instructions per 32 symbols instead
-    // of ~25 per 8 (1.76 ms); an XCD-aware block order (1.70 ms).  The bound pass is not what the kernel waits for; the chain of dependent loads in front of it -
-    // work item -> signature columns -> contig offsets -> record headers -> first words - is the suspect, not followed up.)
+    // (Round 6, measured and dropped - none of them moved the kernel's 1.7 ms: four chunks per lane and trip for EVERY pair, the first trip included, with all eight
+    // loads issued up front (1.94-2.04 ms: the 1.7 M pairs with cores <= 340 symbols load mostly for nothing); 32 symbols per lane and trip - five words of either
+    // string, four funnel shifts, ~45 instructions per 32 symbols instead of ~25 per 8 (1.76 ms); an XCD-aware block order (1.70 ms).  The form below differs from the
+    // first of them in where it is deep: the first trip and its give-up test are the ones of round 6, so a short pair costs what it did, and only what lies behind
+    // the first 128 symbols of a long overlap runs K chunks per lane.  What that measured: DESIGN section 24.)
     auto bound_at = [&](const int a, const int b) -> int {                  // every lane of the sub-group returns the same value; m + n = useless
         const int L = (pd.m - a) < (pd.n - b) ? (pd.m - a) : (pd.n - b);
         if (L <= 0) return pd.m + pd.n;
         int ham_l = 0;
         bool useless = false;
-        for (int base = 0; base < L; base += 8 * G) {
-            const int i0 = base + lane * 8;
-            if (i0 < L) {
-                const int v = L - i0 >= 8 ? 8 : L - i0;
-                const uint32_t vmask = v >= 8 ? 0xffffffffu : ((1u << (4 * v)) - 1u);
-                const uint32_t x = (fetch8(wp, p0 + a + i0) ^ fetch8(wt, t0 + b + i0)) & vmask;
-                ham_l += __popc((x | (x >> 1) | (x >> 2) | (x >> 3)) & 0x11111111u);
-            }
-            if (base == 0 && L > 8 * G) {
-                int first = ham_l;
+        auto mism = [&](const uint32_t x, const int i0) -> int {              // mismatches among the symbols i0 .. i0 + 7 that lie inside the overlap (i0 < L)
+            const int v = L - i0 >= 8 ? 8 : L - i0;
+            const uint32_t vmask = v >= 8 ? 0xffffffffu : ((1u << (4 * v)) - 1u);
+            const uint32_t y = x & vmask;
+            return __popc((y | (y >> 1) | (y >> 2) | (y >> 3)) & 0x11111111u);
+        };
+        // first trip: 8 G symbols, then the give-up test - a short overlap costs one round trip
+        if (lane * 8 < L) ham_l += mism(fetch8(wp, p0 + a + lane * 8) ^ fetch8(wt, t0 + b + lane * 8), lane * 8);
+        if (L > 8 * G) {
+            int first = ham_l;
 #pragma unroll
-                for (int o = G / 2; o >= 1; o >>= 1) first += __shfl_xor(first, o, 64);
-                if (first > 2 * G) { useless = true; break; }
+            for (int o = G / 2; o >= 1; o >>= 1) first += __shfl_xor(first, o, 64);
+            if (first > 2 * G) useless = true;
+        }
+        // the rest in deep trips: K chunks of 8 symbols per lane, all 2 K loads issued before the first compare (the addresses depend on the induction variable
+        // only; one round trip per K * 8 G symbols instead of one per 8 G).  The sub-groups of a wave run their own trip counts: the wave stays in the loop for
+        // its longest overlap (the pairs of a wave are mostly copies of one insertion, so the lengths agree) and a shorter sub-group is masked out of it.  A chunk
+        // at or beyond L reads the overlap's LAST chunk again instead (words its neighbours need anyway, never beyond what the `i0 < L` rule allows) and counts
+        // nothing: with the loads under a guard of their own the compiler puts the funnel shifts into the guard, and every chunk waits for its own words again.
+        // K = 1 is the loop of rounds 1-6.
+        if (!useless) {
+            const uint32_t* bp = wp + ((p0 + a) >> 3); const uint32_t* bt = wt + ((t0 + b) >> 3);       // the words that hold symbol 0 of the overlap
+            const int shp = ((p0 + a) & 7) << 2, sht = ((t0 + b) & 7) << 2;
+            const int last = (L - 1) >> 3;                                       // the last chunk that starts inside the overlap
+            for (int base = 8 * G; base < L; base += K * 8 * G) {
+                uint32_t xp[K], xt[K];
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const int idx = (base >> 3) + k * G + lane;                    // symbols 8 idx .. 8 idx + 7 of the overlap
+                    const int at = idx < last ? idx : last;
+                    xp[k] = __builtin_amdgcn_alignbit(bp[at + 1], bp[at], shp);
+                    xt[k] = __builtin_amdgcn_alignbit(bt[at + 1], bt[at], sht);
+                }
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const int i0 = ((base >> 3) + k * G + lane) * 8;
+                    if (i0 < L) ham_l += mism(xp[k] ^ xt[k], i0);
+                }
             }
         }
 #pragma unroll
@@ -1739,7 +1769,13 @@ static int run_edit_pipeline(svx_ctx* c, long long n_work, const PairSource& src
     int shift_bounds = 1;                                   // SVX_EDIT_SHIFT_BOUNDS=0: upper bounds from the left-justified alignment only (A/B switch)
     if (const char* e = getenv("SVX_EDIT_SHIFT_BOUNDS")) shift_bounds = atoi(e) == 0 ? 0 : 1;
     k_slots<<<(unsigned)((n_work + T - 1) / T), T, 0, st>>>(n_work, src, slot_of);
-    k_edit_prep<PREP_LANES><<<(unsigned)((n_work + 4 * (64 / PREP_LANES) - 1) / (4 * (64 / PREP_LANES))), 256, 0, st>>>(n_work, src, scratch, desc, key_a, val_a, ed_dev, cells_dev, shift_bounds);
+    int prep_depth = PREP_DEPTH;                            // SVX_EDIT_PREP_DEPTH=1|2|4|8: chunks per lane in the later trips of a bound pass (1 = rounds 1-6; A/B switch)
+    if (const char* e = getenv("SVX_EDIT_PREP_DEPTH")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) prep_depth = v; }
+    {
+        const unsigned prep_grid = (unsigned)((n_work + 4 * (64 / PREP_LANES) - 1) / (4 * (64 / PREP_LANES)));
+        auto* prep = prep_depth == 1 ? &k_edit_prep<PREP_LANES, 1> : (prep_depth == 2 ? &k_edit_prep<PREP_LANES, 2> : (prep_depth == 8 ? &k_edit_prep<PREP_LANES, 8> : &k_edit_prep<PREP_LANES, 4>));
+        prep<<<prep_grid, 256, 0, st>>>(n_work, src, scratch, desc, key_a, val_a, ed_dev, cells_dev, shift_bounds);
+    }
     HIPCHK(hipGetLastError());
     const bool profile = getenv("SVX_EDIT_PROFILE") != nullptr, serial = getenv("SVX_EDIT_SERIAL") != nullptr;
     std::vector<PairDesc> first_desc;                       // SVX_EDIT_PROFILE: the descriptors as round 0 saw them (first class of every pair)

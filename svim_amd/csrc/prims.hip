@@ -8,7 +8,8 @@
 //                      consecutive ones; in a round the lanes with the same digit find each other with 8 ballots (one per digit bit), their rank is
 //                      the population count of the peers below them, the running count per digit lives in a per-wave LDS table (one lane per digit
 //                      group updates it: no atomics); digit counts of the four waves are prefix-summed by the 256 threads = 256 digits
-//   Up to RADIX_ONE (16384) pairs everything runs in ONE launch of one workgroup of 1024 threads (all passes; small calls are latency-bound), and
+//   Up to RADIX_ONE (16384; a limit of 32768 sent the 26 k cluster keys of configs[1] through the one workgroup and lost to the tiled passes:
+//   profiles/front_radix_one_ab.txt) pairs everything runs in ONE launch of one workgroup of 1024 threads (all passes; small calls are latency-bound), and
 //   passes over a digit that is the same in every key are skipped there.  (A one-launch-per-pass form with decoupled look-back between the tiles was
 //   built and measured: 24 us per pass of 0.74 M pairs against 28 us for the three launches - not worth workgroups that spin on each other.  Taking the next pass's histogram inside the scatter with one global atomic per pair: 0.4 ms per
 //   pass - the zero bytes of narrow keys send thousands of atomics to one address.)
