@@ -477,7 +477,7 @@ int  svx_text_gz_get_stats(svx_ctx* ctx, svx_text_gz_stats* out);
 /* host-only, no GPU: the same encoder built for the host, one file.  SVX_E_CAPACITY: cap is too small (n + 64 * (n / 65280 + 2) always suffices). */
 int  svx_text_gz_host(const uint8_t* text, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out);
 
-/* ---- tabix index of the BGZF stream (textindex.hip, textindex_core.hpp; the definition in words: svim_amd/tabix.py) ----
+/* ---- tabix index of the BGZF stream (textindex.hip, textindex_core.hpp; bins and layout: binidx_core.hpp; the definition in words: svim_amd/tabix.py) ----
  * svx_text_index builds, for every file of the last svx_text_gz, the uncompressed bytes of its .tbi from the text AND the block table of that call, both where
  * they lie on the device (SVX_E_STATE without a valid stream; the index is void whenever its stream is).  preset: how a line gives its interval
  * (SVX_INDEX_VCF: POS, len(REF), END=; SVX_INDEX_BED: columns 2 and 3).  stream_base[k]: bytes written in front of file k's stream in its file (a header
@@ -650,7 +650,7 @@ int  svx_bam_read_names(svx_bam* h, int64_t* n_names, const char** nul_separated
  * a damaged block fails the svx_bam_read_batch that would have handed out its records.  device < 0: back to the host reader. */
 int  svx_bam_set_device_decode(svx_bam* h, int device);
 
-/* ---- BAM index from the device reader's record stream (bamindex.hip, bamindex_core.hpp; the definition in words: svim_amd/bai.py) ----
+/* ---- BAM index from the device reader's record stream (bamindex.hip, bamindex_core.hpp; bins and layout: binidx_core.hpp; the definition in words: svim_amd/bai.py) ----
  * svx_bam_index_begin switches indexing on for the pass that follows: device decode must be on and the handle at its first record (after open,
  * svx_bam_set_device_decode or svx_bam_rewind, before any read), else SVX_E_STATE.  While it is on, every chunk the reader loads appends one row
  * (tid, pos, end, flag, vbeg) per record it discovers to a table resident on the device - before any filter, whatever max_records, min_mapq and mode the

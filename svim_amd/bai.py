@@ -28,7 +28,7 @@ import bisect
 import struct
 import zlib
 
-from .tabix import MAX_END, PSEUDO_BIN, reg2bin, reg2bins
+from .tabix import MAX_END, PSEUDO_BIN, contig_part, parse_part, reg2bin, reg2bins      # noqa: F401 (PSEUDO_BIN and reg2bin stay names of this module)
 
 E_ORDER, E_RANGE = -9, -10
 _REF_OPS = (0, 2, 3, 7, 8)
@@ -167,29 +167,8 @@ def build_index(n_ref, rows, v_end):
         if not rs:
             out.append(struct.pack("<ii", 0, 0))
             continue
-        bins, prev_bin = {}, None
-        for (beg, end), _, vb, ve in rs:
-            b = reg2bin(beg, end)
-            if b == prev_bin:
-                bins[b][-1][1] = ve
-            else:
-                bins.setdefault(b, []).append([vb, ve])
-            prev_bin = b
-        out.append(struct.pack("<i", len(bins) + 1))
-        for b in sorted(bins):
-            out.append(struct.pack("<Ii", b, len(bins[b])) + b"".join(struct.pack("<QQ", *c) for c in bins[b]))
         n_unmapped = sum(1 for r in rs if r[1] & 4)
-        out.append(struct.pack("<IiQQQQ", PSEUDO_BIN, 2, rs[0][2], rs[-1][3], len(rs) - n_unmapped, n_unmapped))
-        n_intv = 1 + max((r[0][1] - 1) >> 14 for r in rs)
-        lin = [None] * n_intv
-        for (beg, end), _, vb, _ in rs:
-            for w in range(beg >> 14, ((end - 1) >> 14) + 1):
-                if lin[w] is None or vb < lin[w]:
-                    lin[w] = vb
-        for w in range(n_intv - 2, -1, -1):
-            if lin[w] is None:
-                lin[w] = lin[w + 1]
-        out.append(struct.pack("<i%dQ" % n_intv, n_intv, *lin))
+        out.append(contig_part([r[0] + r[2:] for r in rs], len(rs) - n_unmapped, n_unmapped))
     out.append(struct.pack("<Q", sum(1 for r in rows if r[0] < 0)))
     return b"".join(out)
 
@@ -210,26 +189,8 @@ def _parse(data):
     n_ref, = struct.unpack_from("<i", data, 4)
     at, bins, pseudo, linear = 8, [], [], []
     for _ in range(n_ref):
-        n_bin, = struct.unpack_from("<i", data, at)
-        at += 4
-        d, order, ps = {}, [], None
-        for _ in range(n_bin):
-            b, n_chunk = struct.unpack_from("<Ii", data, at)
-            at += 8
-            chunks = [struct.unpack_from("<QQ", data, at + 16 * k) for k in range(n_chunk)]
-            at += 16 * n_chunk
-            if b == PSEUDO_BIN:
-                ps = chunks
-            else:
-                d[b] = chunks
-            order.append(b)
-        if order != sorted(order) or len(set(order)) != len(order) or (ps is None) != (n_bin == 0) or (ps is not None and len(ps) != 2):
-            raise ValueError("BAM index: bins not ascending, or no pseudo-bin")
-        n_intv, = struct.unpack_from("<i", data, at)
-        at += 4
-        linear.append(list(struct.unpack_from("<%dQ" % n_intv, data, at)))
-        at += 8 * n_intv
-        bins.append(d), pseudo.append(ps)
+        d, ps, lin, at = parse_part(data, at, "BAM index", may_be_empty=True)
+        bins.append(d), pseudo.append(ps), linear.append(lin)
     n_no_coor, = struct.unpack_from("<Q", data, at)
     if at + 8 != len(data):
         raise ValueError("BAM index: %d bytes behind the trailer" % (len(data) - at - 8))

@@ -1,6 +1,8 @@
 // bamindex.hip - the BAM index (.bai) of the file the device reader (bamdev.hip) is reading, built from the reader's own record stream (svx_bam_index*,
-// include/svx.h; gfx950).  What an index says: svim_amd/bai.py; the interval rule, the binning and the layout: bamindex_core.hpp, the source
-// svx_bam_index_host is built from as well.
+// include/svx.h; gfx950).  What an index says: svim_amd/bai.py; the interval and order rules: bamindex_core.hpp, the source svx_bam_index_host is built from
+// as well.  This file makes the row table - append, the span kernels, the rows of a sorted file - and, at finish, the check, the first row of every
+// reference, the chunk heads, header and trailer; the phases behind them (bins, sizes, the linear index, a reference's part) are those a .tbi has too:
+// binidx_kernels.hpp, instantiated with BixRows.
 // Replaces: samtools index after the fact (the reference's main() asks for it: "Please generate with 'samtools index'"): one more single-threaded zlib pass
 // over a file whose every record this reader has already found.
 // While indexing is on, every chunk the reader loads appends one row per record to a table that stays on the device:
@@ -22,17 +24,17 @@
 #include "scan.hpp"
 #include "cigar_span.hpp"
 #include "bamindex_core.hpp"
+#include "binidx_kernels.hpp"
 #include "bamindex.hpp"
 #include <algorithm>
 
-#define BT 256
-#define BGRID(n) (unsigned)(((long long)(n) + BT - 1) / BT)
+#define BT BINIDX_T
+#define BGRID(n) BINIDX_GRID(n)
 #define BIX_LONG_OPS 4096
 #define BIX_GIANT_OPS 65536
 #define BIX_LONG_TILE 1024
 #define BIX_LONG_BLOCKS 256
 #define BIX_NPOOL 32
-#define BIX_KEY_TID_SHIFT 16                /* sort key of a chunk: the bin (< 37 450 < 2^16) in the low bits, the tid above: no radix pass over bits that are zero in every key */
 enum { BIXF_ORDER = 1, BIXF_RANGE = 2, BIXF_TID = 4, BIXF_LAYOUT = 8 };
 
 struct BixCols { int32_t *tid, *pos; uint16_t* flag; int64_t* end; uint64_t* vbeg; };
@@ -94,14 +96,14 @@ __global__ void k_bix_end(long long n, BixCols T, const uint32_t* span) {
 }
 
 // ---- finish ---------------------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ BixInterval bix_row(const BixCols& T, long long i) { return bix_interval(T.pos[i], T.end[i]); }
+__device__ __forceinline__ BinIdxInterval bix_row(const BixCols& T, long long i) { return bix_interval(T.pos[i], T.end[i]); }
 __global__ void k_bix_check(long long n, int32_t n_ref, BixCols T, int* err) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int32_t t = T.tid[i];
     int e = t >= n_ref ? BIXF_TID : 0;
     if (i > 0 && bix_out_of_order(T.tid[i - 1], T.pos[i - 1], t, T.pos[i])) e |= BIXF_ORDER;
-    if (t >= 0 && bix_row(T, i).end > TIX_MAX_END) e |= BIXF_RANGE;
+    if (t >= 0 && bix_row(T, i).end > BINIDX_MAX_END) e |= BIXF_RANGE;
     if (e) atomicOr(err, e);
 }
 // first row of every reference, and of the unplaced tail (t = n_ref): the table is in order, a negative tid is the largest as an unsigned number
@@ -116,7 +118,7 @@ __global__ void k_bix_heads(long long n_placed, BixCols T, int32_t* bhead, int32
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j > n_placed) return;
     if (j == n_placed) { bhead[j] = 0; umark[j] = 0; return; }
-    bhead[j] = (j == 0 || T.tid[j] != T.tid[j - 1] || bix_bin(bix_row(T, j)) != bix_bin(bix_row(T, j - 1))) ? 1 : 0;
+    bhead[j] = (j == 0 || T.tid[j] != T.tid[j - 1] || binidx_bin(bix_row(T, j)) != binidx_bin(bix_row(T, j - 1))) ? 1 : 0;
     umark[j] = (T.flag[j] & 4u) ? 1 : 0;
 }
 __global__ void k_bix_chunks(long long n_placed, long long n_chunks, BixCols T, const int32_t* bhead, const int64_t* bpos, uint32_t* chunk_rec, uint64_t* key, uint32_t* val) {
@@ -124,139 +126,37 @@ __global__ void k_bix_chunks(long long n_placed, long long n_chunks, BixCols T, 
     if (j > n_placed) return;
     if (j == n_placed) { chunk_rec[n_chunks] = (uint32_t)n_placed; return; }
     const long long q = bpos[j];
-    if (bhead[j] && q < n_chunks) { chunk_rec[q] = (uint32_t)j; key[q] = ((uint64_t)(uint32_t)T.tid[j] << BIX_KEY_TID_SHIFT) | bix_bin(bix_row(T, j)); val[q] = (uint32_t)q; }
+    if (bhead[j] && q < n_chunks) { chunk_rec[q] = (uint32_t)j; key[q] = binidx_key((uint64_t)(uint32_t)T.tid[j], binidx_bin(bix_row(T, j))); val[q] = (uint32_t)q; }
 }
-__global__ void k_bix_bin_heads(long long n_chunks, const uint64_t* key, int32_t* bh) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > n_chunks) return;
-    bh[p] = p < n_chunks && (p == 0 || key[p] != key[p - 1]) ? 1 : 0;
-}
-__global__ void k_bix_bin_first(long long n_chunks, long long n_bins, const int32_t* bh, const int64_t* binpos, uint32_t* bin_first) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > n_chunks) return;
-    if (p == n_chunks) { bin_first[n_bins] = (uint32_t)n_chunks; return; }
-    const long long q = binpos[p];
-    if (bh[p] && q < n_bins) bin_first[q] = (uint32_t)p;
-}
-// first bin of every reference in the sorted list (a reference without rows has none: its range is empty)
-__global__ void k_bix_ref_bins(int32_t n_ref, long long n_chunks, const uint64_t* key, const int64_t* binpos, uint32_t* ref_first_bin) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > n_ref) return;
-    long long lo = 0, hi = n_chunks;
-    while (lo < hi) { const long long mid = (lo + hi) >> 1; if ((long long)(key[mid] >> BIX_KEY_TID_SHIFT) >= t) hi = mid; else lo = mid + 1; }
-    ref_first_bin[t] = (uint32_t)binpos[lo];
-}
-__global__ void k_bix_max_end(long long n_placed, BixCols T, int32_t* tmax) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n_placed) atomicMax(tmax + T.tid[j], (int32_t)bix_row(T, j).end);          // (end <= 2^29: the range check has passed)
-}
-__global__ void k_bix_sizes(int32_t n_ref, const int64_t* first, const uint32_t* ref_first_bin, const uint32_t* bin_first, const int32_t* tmax, int64_t* tsz, int64_t* nintv) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > n_ref) return;
-    if (t == n_ref) { tsz[t] = 0; nintv[t] = 0; return; }
-    const long long rows = first[t + 1] - first[t];
-    const long long ni = rows > 0 ? 1 + (((long long)tmax[t] - 1) >> 14) : 0;
-    const uint32_t b0 = ref_first_bin[t], b1 = ref_first_bin[t + 1];
-    tsz[t] = bix_ref_bytes(rows, (long long)b1 - b0, (long long)bin_first[b1] - bin_first[b0], ni);
-    nintv[t] = ni;
-}
-__global__ __launch_bounds__(BT) void k_bix_linear(long long n_placed, BixCols T, const int64_t* loff, long long n_slots, unsigned long long* lin) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    long long w0 = 0, w1 = -1, base = 0; unsigned long long v = 0;
-    if (j < n_placed) {
-        const int32_t t = T.tid[j];
-        const BixInterval iv = bix_row(T, j);
-        base = loff[t]; w0 = iv.beg >> 14; w1 = (iv.end - 1) >> 14; v = T.vbeg[j];
-        if (base + w1 >= n_slots || base + w1 >= loff[t + 1]) w1 = w0 - 1;       // (cannot happen: the slots were sized by the largest end)
-    }
-    if (w1 == w0) atomicMin(lin + base + w0, v);
-    unsigned long long many = __ballot(w1 > w0);
-    while (many) {                                           // a record of many windows: the wave writes them, 64 at a time
-        const int src = __ffsll((long long)many) - 1;
-        many &= many - 1;
-        const long long b = __shfl(base, src, 64), lo = __shfl(w0, src, 64), hi = __shfl(w1, src, 64);
-        const unsigned long long vv = __shfl(v, src, 64);
-        for (long long w = lo + lane_id(); w <= hi; w += 64) atomicMin(lin + b + w, vv);
-    }
-}
-struct BixOut { uint8_t* blob; long long n_blob; int* err; const int64_t* toff; };
-__device__ __forceinline__ uint8_t* bix_at(const BixOut& o, long long off, long long len) {
-    if (off < 0 || off + len > o.n_blob) { atomicOr(o.err, BIXF_LAYOUT); return nullptr; }
-    return o.blob + off;
-}
-__global__ void k_bix_ser_chunks(long long n_chunks, const uint64_t* key, const uint32_t* val, const int32_t* bh, const int64_t* binpos, const uint32_t* bin_first,
-                                 const uint32_t* ref_first_bin, const uint32_t* chunk_rec, BixCols T, long long n_rows, uint64_t v_end, BixOut o) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_chunks) return;
-    const long long t = (long long)(key[p] >> BIX_KEY_TID_SHIFT);
-    const long long base = BIX_HEADER_BYTES + o.toff[t];
-    const long long q = binpos[p] + bh[p] - 1, fb = ref_first_bin[t];
-    const long long at = base + 4 + 8 * (q - fb) + 16 * ((long long)bin_first[q] - bin_first[fb]);
-    if (bh[p]) {
-        uint8_t* d = bix_at(o, at, 8);
-        if (d) { tix_put32(d, (uint32_t)(key[p] & ((1u << BIX_KEY_TID_SHIFT) - 1u))); tix_put32(d + 4, bin_first[q + 1] - bin_first[q]); }
-    }
-    const uint32_t cq = val[p];
-    const long long j0 = chunk_rec[cq], j1 = (long long)chunk_rec[cq + 1] - 1;
-    const uint64_t vend = j1 + 1 < n_rows ? T.vbeg[j1 + 1] : v_end;
-    uint8_t* d = bix_at(o, at + 8 + 16 * (p - (long long)bin_first[q]), 16);
-    if (d) { tix_put64(d, T.vbeg[j0]); tix_put64(d + 8, vend); }
-}
-// one wave per reference with rows: n_bin, the pseudo-bin, n_intv, the linear index with its empty slots filled from behind (a reference without rows keeps
-// the eight zero bytes the index was cleared to)
-__global__ __launch_bounds__(64) void k_bix_ser_ref(int32_t n_ref, const int64_t* first, const int64_t* upos, const uint32_t* ref_first_bin, const uint32_t* bin_first, BixCols T,
-                                                    long long n_rows, uint64_t v_end, const int64_t* loff, const unsigned long long* lin, BixOut o) {
-    const long long t = blockIdx.x;
-    if (t >= n_ref) return;
-    const long long j0 = first[t], j1 = first[t + 1];
-    if (j1 <= j0) return;
-    const long long base = BIX_HEADER_BYTES + o.toff[t];
-    const long long nb = (long long)ref_first_bin[t + 1] - ref_first_bin[t], nc = (long long)bin_first[ref_first_bin[t + 1]] - bin_first[ref_first_bin[t]];
-    const long long ni = loff[t + 1] - loff[t];
-    const long long ps = base + 4 + 8 * nb + 16 * nc;
-    if (lane_id() == 0) {
-        const uint64_t vend = j1 < n_rows ? T.vbeg[j1] : v_end;
-        const uint64_t n_unmapped = (uint64_t)(upos[j1] - upos[j0]);
-        uint8_t* d = bix_at(o, base, 4);
-        if (d) tix_put32(d, (uint32_t)(nb + 1));
-        d = bix_at(o, ps, 44);
-        if (d) {
-            tix_put32(d, TIX_PSEUDO_BIN); tix_put32(d + 4, 2u); tix_put64(d + 8, T.vbeg[j0]); tix_put64(d + 16, vend);
-            tix_put64(d + 24, (uint64_t)(j1 - j0) - n_unmapped); tix_put64(d + 32, n_unmapped); tix_put32(d + 40, (uint32_t)ni);
-        }
-    }
-    unsigned long long carry = TIX_NO_SLOT;
-    for (long long top = ni - 1; top >= 0; top -= 64) {                 // lane l holds window top - l: a prefix minimum over the lanes is a suffix minimum over the windows
-        const long long w = top - lane_id();
-        unsigned long long v = w >= 0 ? lin[loff[t] + w] : TIX_NO_SLOT;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) { const unsigned long long u = __shfl_up(v, s, 64); if (lane_id() >= s && u < v) v = u; }
-        if (carry < v) v = carry;
-        if (w >= 0) { uint8_t* d = bix_at(o, ps + 44 + 8 * w, 8); if (d) tix_put64(d, v); }
-        carry = __shfl(v, 63, 64);
-    }
-}
+// the placed rows as binidx_kernels.hpp reads them: a group is a reference, every one of them gets bytes
+struct BixRows {
+    BixCols T; long long n_rows; uint64_t v_end; const int64_t *first_row, *upos, *toff;
+    __device__ long long group(long long j) const { return T.tid[j]; }
+    __device__ bool live(long long) const { return true; }
+    __device__ BinIdxInterval interval(long long j) const { return bix_row(T, j); }
+    __device__ uint64_t vbeg(long long j) const { return T.vbeg[j]; }
+    __device__ uint64_t vend(long long j) const { return j + 1 < n_rows ? T.vbeg[j + 1] : v_end; }      // the next row's start (an unplaced one's too), or the end of the data
+    __device__ bool group_live(long long) const { return true; }
+    __device__ long long first(long long t) const { return first_row[t]; }
+    __device__ long long last(long long t) const { return first_row[t + 1]; }
+    __device__ long long part_off(long long t) const { return BIX_HEADER_BYTES + toff[t]; }
+    __device__ uint64_t n_unmapped(long long t) const { return (uint64_t)(upos[first_row[t + 1]] - upos[first_row[t]]); }
+    __device__ uint64_t n_mapped(long long t) const { return (uint64_t)(first_row[t + 1] - first_row[t]) - n_unmapped(t); }
+};
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------
 struct BamIndex {
     int64_t n = 0, cap = 0;
     DevBuf tid, pos, flag, end, vbeg;                       // the table
     DevBuf span, long_list, counters, blk_start, blk_vbase, scan_tmp, sort_tmp, err;
-    DevBuf pool[BIX_NPOOL]; int used = 0;
+    ScratchPool<BIX_NPOOL> pool{"BAM index"};
     DevBuf blob; int64_t n_blob = 0; bool have = false;
     double t_mark[6];                                       // host clock at the phase boundaries of finish (the stream is drained at each)
     double t_append = 0; int64_t n_long = 0;
     svx_bam_index_stats stats;
     BixCols cols(int64_t at) const { return BixCols{tid.as<int32_t>() + at, pos.as<int32_t>() + at, flag.as<uint16_t>() + at, end.as<int64_t>() + at, vbeg.as<uint64_t>() + at}; }
-    template <class Tp> int get(Tp** o, size_t count) {
-        if (used >= BIX_NPOOL) return svx_fail(SVX_E_CAPACITY, "BAM index: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(pool[used].reserve((count ? count : 1) * sizeof(Tp) + 64));
-        *o = pool[used++].as<Tp>();
-        return SVX_OK;
-    }
 };
 static inline double bix_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static int bix_ceil_log2(long long n) { int b = 0; while ((1ll << b) < n) b++; return b; }
 
 int bamindex_begin(BamIndex** ix) {
     if (!*ix) *ix = new BamIndex();
@@ -269,8 +169,8 @@ void bamindex_drop(BamIndex* S) {
     if (!S) return;
     DevBuf* all[] = {&S->tid, &S->pos, &S->flag, &S->end, &S->vbeg, &S->span, &S->long_list, &S->blk_start, &S->blk_vbase, &S->scan_tmp, &S->sort_tmp};
     for (auto* b : all) b->release();
-    for (auto& b : S->pool) b.release();
-    S->n = S->cap = 0; S->used = 0;
+    S->pool.release();
+    S->n = S->cap = 0;
 }
 void bamindex_destroy(BamIndex* S) {
     if (!S) return;
@@ -350,7 +250,7 @@ int64_t bamindex_rows(const BamIndex* S) { return S ? S->n : 0; }
 
 int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) {
     if (!S || n_ref < 0) return svx_fail(SVX_E_ARG, "BAM index: bad argument", __FILE__, __LINE__, hipSuccess);
-    S->used = 0; S->have = false;
+    S->pool.reset(); S->have = false;
     const int64_t n = S->n;
     const BixCols T = S->cols(0);
     SVXCHK(S->err.reserve(64));
@@ -373,7 +273,7 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
     int64_t *first = nullptr, *bpos = nullptr, *upos = nullptr; int32_t *bhead = nullptr, *umark = nullptr;
     std::vector<int64_t> first_h((size_t)n_ref + 1, 0);
     if (n > 0 && n_ref > 0) {
-        SVXCHK(S->get(&first, (size_t)n_ref + 1));
+        SVXCHK(S->pool.get(&first, (size_t)n_ref + 1));
         k_bix_ref_first<<<BGRID(n_ref + 1), BT, 0, st>>>(n, T.tid, n_ref, first);
         HIPCHK(hipGetLastError());
         SVXCHK(svx_d2h(first_h.data(), first, ((size_t)n_ref + 1) * 8, st));
@@ -383,14 +283,14 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
     }
     uint32_t* chunk_rec = nullptr; uint64_t *key = nullptr, *key2 = nullptr; uint32_t *val = nullptr, *val2 = nullptr;
     if (n_placed > 0) {
-        SVXCHK(S->get(&bhead, (size_t)n_placed + 1)); SVXCHK(S->get(&umark, (size_t)n_placed + 1)); SVXCHK(S->get(&bpos, (size_t)n_placed + 1)); SVXCHK(S->get(&upos, (size_t)n_placed + 1));
+        SVXCHK(S->pool.get(&bhead, (size_t)n_placed + 1)); SVXCHK(S->pool.get(&umark, (size_t)n_placed + 1)); SVXCHK(S->pool.get(&bpos, (size_t)n_placed + 1)); SVXCHK(S->pool.get(&upos, (size_t)n_placed + 1));
         k_bix_heads<<<BGRID(n_placed + 1), BT, 0, st>>>(n_placed, T, bhead, umark);
         SVXCHK((svx_exclusive_scan<int32_t, int64_t>(bhead, bpos, n_placed + 1, st, S->scan_tmp)));
         SVXCHK((svx_exclusive_scan<int32_t, int64_t>(umark, upos, n_placed + 1, st, S->scan_tmp)));
         SVXCHK(svx_d2h(&n_chunks, bpos + n_placed, 8, st));
         if (n_chunks < 1 || n_chunks > n_placed) return svx_fail(SVX_E_STATE, "BAM index: the chunk count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&chunk_rec, (size_t)n_chunks + 1)); SVXCHK(S->get(&key, (size_t)n_chunks)); SVXCHK(S->get(&val, (size_t)n_chunks));
-        SVXCHK(S->get(&key2, (size_t)n_chunks)); SVXCHK(S->get(&val2, (size_t)n_chunks));
+        SVXCHK(S->pool.get(&chunk_rec, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&key, (size_t)n_chunks)); SVXCHK(S->pool.get(&val, (size_t)n_chunks));
+        SVXCHK(S->pool.get(&key2, (size_t)n_chunks)); SVXCHK(S->pool.get(&val2, (size_t)n_chunks));
         k_bix_chunks<<<BGRID(n_placed + 1), BT, 0, st>>>(n_placed, n_chunks, T, bhead, bpos, chunk_rec, key, val);
         HIPCHK(hipGetLastError());
     }
@@ -398,27 +298,27 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
     // ---- chunks sorted by (tid, bin); bins ----
     int32_t *bh = nullptr, *tmax = nullptr; int64_t *binpos = nullptr, *tsz = nullptr, *nintv = nullptr, *toff = nullptr, *loff = nullptr; uint32_t *bin_first = nullptr, *ref_first_bin = nullptr;
     if (n_placed > 0) {
-        SVXCHK(S->get(&bh, (size_t)n_chunks + 1)); SVXCHK(S->get(&binpos, (size_t)n_chunks + 1));
-        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, val2, n_chunks, 0, BIX_KEY_TID_SHIFT + std::max(1, bix_ceil_log2((long long)n_ref + 1))));
-        k_bix_bin_heads<<<BGRID(n_chunks + 1), BT, 0, st>>>(n_chunks, key2, bh);
+        SVXCHK(S->pool.get(&bh, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&binpos, (size_t)n_chunks + 1));
+        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, val2, n_chunks, 0, binidx_sort_end_bit(n_ref)));
+        k_binidx_bin_heads<BixRows><<<BGRID(n_chunks + 1), BT, 0, st>>>(n_chunks, key2, bh);
         SVXCHK((svx_exclusive_scan<int32_t, int64_t>(bh, binpos, n_chunks + 1, st, S->scan_tmp)));
         SVXCHK(svx_d2h(&n_bins, binpos + n_chunks, 8, st));
         if (n_bins < 1 || n_bins > n_chunks) return svx_fail(SVX_E_STATE, "BAM index: the bin count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->get(&ref_first_bin, (size_t)n_ref + 1));
-        k_bix_bin_first<<<BGRID(n_chunks + 1), BT, 0, st>>>(n_chunks, n_bins, bh, binpos, bin_first);
-        k_bix_ref_bins<<<BGRID(n_ref + 1), BT, 0, st>>>(n_ref, n_chunks, key2, binpos, ref_first_bin);
+        SVXCHK(S->pool.get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->pool.get(&ref_first_bin, (size_t)n_ref + 1));
+        binidx_launch_bins<BixRows>(st, n_chunks, n_bins, n_ref, key2, bh, binpos, bin_first, ref_first_bin);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st)); S->t_mark[3] = bix_now();
     // ---- sizes; the linear index: the smallest vbeg per window ----
     unsigned long long* lin = nullptr;
-    int64_t body = (int64_t)BIX_EMPTY_REF_BYTES * n_ref;
+    int64_t body = (int64_t)BINIDX_EMPTY_PART_BYTES * n_ref;
+    BixRows rows{T, n, v_end, first, upos, nullptr};
     if (n_placed > 0) {
-        SVXCHK(S->get(&tmax, (size_t)n_ref + 1)); SVXCHK(S->get(&tsz, (size_t)n_ref + 1)); SVXCHK(S->get(&nintv, (size_t)n_ref + 1));
-        SVXCHK(S->get(&toff, (size_t)n_ref + 2)); SVXCHK(S->get(&loff, (size_t)n_ref + 2));
+        SVXCHK(S->pool.get(&tmax, (size_t)n_ref + 1)); SVXCHK(S->pool.get(&tsz, (size_t)n_ref + 1)); SVXCHK(S->pool.get(&nintv, (size_t)n_ref + 1));
+        SVXCHK(S->pool.get(&toff, (size_t)n_ref + 2)); SVXCHK(S->pool.get(&loff, (size_t)n_ref + 2));
         HIPCHK(hipMemsetAsync(tmax, 0, ((size_t)n_ref + 1) * 4, st));
-        k_bix_max_end<<<BGRID(n_placed), BT, 0, st>>>(n_placed, T, tmax);
-        k_bix_sizes<<<BGRID(n_ref + 1), BT, 0, st>>>(n_ref, first, ref_first_bin, bin_first, tmax, tsz, nintv);
+        k_binidx_max_end<<<BGRID(n_placed), BT, 0, st>>>(rows, n_placed, tmax);
+        k_binidx_sizes<<<BGRID(n_ref + 1), BT, 0, st>>>(rows, n_ref, tmax, ref_first_bin, bin_first, tsz, nintv);
         SVXCHK((svx_exclusive_scan<int64_t, int64_t>(tsz, toff, (long long)n_ref + 1, st, S->scan_tmp)));
         SVXCHK((svx_exclusive_scan<int64_t, int64_t>(nintv, loff, (long long)n_ref + 1, st, S->scan_tmp)));
         HIPCHK(hipGetLastError());
@@ -427,11 +327,11 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
             SVXCHK(hc.d2h(&body, toff + n_ref, 8)); SVXCHK(hc.d2h(&n_slots, loff + n_ref, 8));
             SVXCHK(hc.finish());
         }
-        if (n_slots < 1 || n_slots > (int64_t)n_ref * 32768 || body < (int64_t)BIX_EMPTY_REF_BYTES * n_ref)
+        if (n_slots < 1 || n_slots > (int64_t)n_ref * 32768 || body < (int64_t)BINIDX_EMPTY_PART_BYTES * n_ref)
             return svx_fail(SVX_E_STATE, "BAM index: the sizes are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&lin, (size_t)n_slots));
+        SVXCHK(S->pool.get(&lin, (size_t)n_slots));
         HIPCHK(hipMemsetAsync(lin, 0xff, (size_t)n_slots * 8, st));
-        k_bix_linear<<<BGRID(n_placed), BT, 0, st>>>(n_placed, T, loff, n_slots, lin);
+        k_binidx_linear<<<BGRID(n_placed), BT, 0, st>>>(rows, n_placed, loff, n_slots, lin);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st)); S->t_mark[4] = bix_now();
@@ -442,16 +342,17 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
     HIPCHK(hipMemsetAsync(blob, 0, (size_t)n_blob + 64, st));
     {
         uint8_t head[BIX_HEADER_BYTES], trail[8];
-        memcpy(head, "BAI\1", 4); tix_put32(head + 4, (uint32_t)n_ref);
-        tix_put64(trail, (uint64_t)(n - n_placed));
+        memcpy(head, "BAI\1", 4); binidx_put32(head + 4, (uint32_t)n_ref);
+        binidx_put64(trail, (uint64_t)(n - n_placed));
         HostCopy hc(st);
         SVXCHK(hc.h2d(blob, head, sizeof head)); SVXCHK(hc.h2d(blob + n_blob - 8, trail, sizeof trail));
         SVXCHK(hc.finish());
     }
     if (n_placed > 0) {
-        BixOut o; o.blob = blob; o.n_blob = n_blob - 8; o.err = err_d; o.toff = toff;
-        k_bix_ser_chunks<<<BGRID(n_chunks), BT, 0, st>>>(n_chunks, key2, val2, bh, binpos, bin_first, ref_first_bin, chunk_rec, T, n, v_end, o);
-        k_bix_ser_ref<<<(unsigned)n_ref, 64, 0, st>>>(n_ref, first, upos, ref_first_bin, bin_first, T, n, v_end, loff, lin, o);
+        rows.toff = toff;
+        const BinIdxOut o{blob, n_blob - 8, err_d, BIXF_LAYOUT};
+        k_binidx_ser_chunks<<<BGRID(n_chunks), BT, 0, st>>>(rows, n_chunks, key2, val2, bh, binpos, bin_first, ref_first_bin, chunk_rec, o);
+        k_binidx_ser_group<<<(unsigned)n_ref, 64, 0, st>>>(rows, n_ref, ref_first_bin, bin_first, loff, lin, o);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st)); S->t_mark[5] = bix_now();

@@ -1,15 +1,12 @@
-// bamindex_host.cpp - svx_bam_index_host: the .bai of one file from its row table by the interval rule, the binning and the layout of bamindex_core.hpp,
-// built for the host; no GPU involved.  The kernels of bamindex.hip write the same bytes for the same rows; here the references, chunks and windows are
-// walked one row after the other, there they come from bisections, scans and a sort.
+// bamindex_host.cpp - svx_bam_index_host: the .bai of one file from its row table by the interval and order rules of bamindex_core.hpp, built for the host; no
+// GPU involved.  The checks, the references, their empty parts and the trailer are made here; the part of a reference with rows is written by
+// binidx_host.hpp.  The kernels of bamindex.hip write the same bytes for the same rows; here the references, chunks and windows are walked one row after
+// the other, there they come from bisections, scans and a sort.
 #include "bamindex_core.hpp"
+#include "binidx_host.hpp"
 #include "../../include/svx.h"
-#include <algorithm>
 #include <cstring>
 #include <vector>
-
-namespace {
-struct Chunk { uint32_t bin; uint64_t beg, end; };
-}
 
 extern "C" int svx_bam_index_host(int32_t n_ref, int64_t n_rows, const int32_t* tid, const int32_t* pos, const int64_t* end, const uint16_t* flag, const uint64_t* vbeg,
                                   uint64_t v_end, uint8_t* out, int64_t cap, int64_t* n_out) {
@@ -21,60 +18,32 @@ extern "C" int svx_bam_index_host(int32_t n_ref, int64_t n_rows, const int32_t* 
     int64_t n_placed = n_rows;                                 // (in order: the placed rows are a prefix)
     for (int64_t k = 0; k < n_rows; k++) {
         if (k && bix_out_of_order(tid[k - 1], pos[k - 1], tid[k], pos[k])) bad_order = true;
-        if (tid[k] >= 0 && bix_interval(pos[k], end[k]).end > TIX_MAX_END) bad_range = true;
+        if (tid[k] >= 0 && bix_interval(pos[k], end[k]).end > BINIDX_MAX_END) bad_range = true;
         if (tid[k] < 0 && n_placed == n_rows) n_placed = k;
     }
     if (bad_order) return SVX_E_ORDER;
     if (bad_range) return SVX_E_RANGE;
     std::vector<uint8_t> blob((size_t)BIX_HEADER_BYTES);
     memcpy(blob.data(), "BAI\1", 4);
-    tix_put32(blob.data() + 4, (uint32_t)n_ref);
+    binidx_put32(blob.data() + 4, (uint32_t)n_ref);
     int64_t lo = 0;
     for (int32_t t = 0; t < n_ref; t++) {
         int64_t hi = lo;
         while (hi < n_placed && tid[hi] == t) hi++;
-        if (hi == lo) { blob.resize(blob.size() + BIX_EMPTY_REF_BYTES, 0); continue; }
-        std::vector<Chunk> chunks;
-        int64_t max_end = 0; uint64_t n_unmapped = 0;
-        uint32_t prev_bin = 0;
+        if (hi == lo) { blob.resize(blob.size() + BINIDX_EMPTY_PART_BYTES, 0); continue; }
+        std::vector<BinIdxRow> rows;
+        uint64_t n_unmapped = 0;
         for (int64_t j = lo; j < hi; j++) {
-            const BixInterval v = bix_interval(pos[j], end[j]);
-            const uint32_t bin = bix_bin(v);
-            const uint64_t ve = j + 1 < n_rows ? vbeg[j + 1] : v_end;
-            if (j > lo && bin == prev_bin) chunks.back().end = ve; else chunks.push_back(Chunk{bin, vbeg[j], ve});
-            prev_bin = bin;
-            max_end = std::max(max_end, v.end);
+            const BinIdxInterval v = bix_interval(pos[j], end[j]);
+            rows.push_back(BinIdxRow{v.beg, v.end, vbeg[j], j + 1 < n_rows ? vbeg[j + 1] : v_end});
             n_unmapped += (flag[j] & 4u) ? 1u : 0u;
         }
-        std::stable_sort(chunks.begin(), chunks.end(), [](const Chunk& a, const Chunk& b) { return a.bin < b.bin; });
-        int64_t n_bins = 0;
-        for (size_t k = 0; k < chunks.size(); k++) n_bins += k == 0 || chunks[k].bin != chunks[k - 1].bin;
-        const int64_t n_intv = 1 + ((max_end - 1) >> 14);
-        const size_t at = blob.size();
-        blob.resize(at + (size_t)bix_ref_bytes(hi - lo, n_bins, (int64_t)chunks.size(), n_intv));
-        uint8_t* p = blob.data() + at;
-        tix_put32(p, (uint32_t)(n_bins + 1)); p += 4;
-        for (size_t k = 0; k < chunks.size();) {
-            size_t m = k;
-            while (m < chunks.size() && chunks[m].bin == chunks[k].bin) m++;
-            tix_put32(p, chunks[k].bin); tix_put32(p + 4, (uint32_t)(m - k)); p += 8;
-            for (; k < m; k++) { tix_put64(p, chunks[k].beg); tix_put64(p + 8, chunks[k].end); p += 16; }
-        }
-        tix_put32(p, TIX_PSEUDO_BIN); tix_put32(p + 4, 2u); tix_put64(p + 8, vbeg[lo]); tix_put64(p + 16, hi < n_rows ? vbeg[hi] : v_end);
-        tix_put64(p + 24, (uint64_t)(hi - lo) - n_unmapped); tix_put64(p + 32, n_unmapped); p += 40;
-        tix_put32(p, (uint32_t)n_intv); p += 4;
-        std::vector<uint64_t> lin((size_t)n_intv, TIX_NO_SLOT);
-        for (int64_t j = lo; j < hi; j++) {
-            const BixInterval v = bix_interval(pos[j], end[j]);
-            for (int64_t w = v.beg >> 14; w <= (v.end - 1) >> 14; w++) lin[(size_t)w] = std::min(lin[(size_t)w], vbeg[j]);
-        }
-        for (int64_t w = n_intv - 2; w >= 0; w--) if (lin[(size_t)w] == TIX_NO_SLOT) lin[(size_t)w] = lin[(size_t)w + 1];
-        for (int64_t w = 0; w < n_intv; w++) tix_put64(p + 8 * w, lin[(size_t)w]);
+        binidx_append_part(blob, rows.data(), rows.size(), (uint64_t)(hi - lo) - n_unmapped, n_unmapped);
         lo = hi;
     }
     const size_t at = blob.size();
     blob.resize(at + 8);
-    tix_put64(blob.data() + at, (uint64_t)(n_rows - n_placed));
+    binidx_put64(blob.data() + at, (uint64_t)(n_rows - n_placed));
     *n_out = (int64_t)blob.size();
     if ((int64_t)blob.size() > cap) return SVX_E_CAPACITY;
     memcpy(out, blob.data(), blob.size());

@@ -322,7 +322,7 @@ __global__ __launch_bounds__(BT) void k_bed_payload(int n_tiles, const int64_t* 
 // host: state and the call
 // ---------------------------------------------------------------------------------------------------------
 struct BedState {
-    DevBuf pool[BED_NPOOL]; int used = 0;
+    ScratchPool<BED_NPOOL> pool{"bed"};
     DevBuf out, line_off, rname, rname_off;
     int64_t n_reads = 0; bool have_names = false;
     int64_t n_lines = 0, n_bytes = 0; int n_files = 0;
@@ -330,12 +330,6 @@ struct BedState {
     bool have = false;
     hipEvent_t ev[7]; bool have_ev = false;
     svx_bed_stats stats;
-    template <class Tp> int get(Tp** o, size_t count) {
-        if (used >= BED_NPOOL) return svx_fail(SVX_E_CAPACITY, "bed: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(pool[used].reserve((count ? count : 1) * sizeof(Tp) + 64));
-        *o = pool[used++].as<Tp>();
-        return SVX_OK;
-    }
 };
 static int bed_state(svx_ctx* c, BedState** out) {
     if (!c->bed) { c->bed = new BedState(); memset(&c->bed->stats, 0, sizeof c->bed->stats); }
@@ -347,15 +341,13 @@ static int bed_state(svx_ctx* c, BedState** out) {
 void svx_bed_release(svx_ctx* c) {
     BedState* s = c->bed;
     if (!s) return;
-    for (auto& b : s->pool) b.release();
+    s->pool.release();
     s->out.release(); s->line_off.release(); s->rname.release(); s->rname_off.release();
     if (s->have_ev) for (auto& e : s->ev) (void)hipEventDestroy(e);
     delete s;
     c->bed = nullptr;
 }
 void svx_preload_bed() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_bed_payload)); (void)hipGetLastError(); }
-
-static int bed_ceil_log2(long long n) { int b = 0; while ((1ll << b) < n) b++; return b; }
 
 extern "C" int svx_bed_set_read_names(svx_ctx* c, const char* blob, const int64_t* off, int64_t n_reads) {
     if (!c || !off || n_reads < 0 || off[0] != 0) return svx_fail(SVX_E_ARG, "svx_bed_set_read_names: bad argument (offsets are required and start at 0)", __FILE__, __LINE__, hipSuccess);
@@ -380,7 +372,7 @@ extern "C" int svx_bed(svx_ctx* c, int product, int source, const svx_cluster_vi
         return svx_fail(SVX_E_ARG, "svx_bed: bad argument (product 0..2; the inputs and the contig names are required, product 1 needs the contig ranks)", __FILE__, __LINE__, hipSuccess);
     HIPCHK(hipSetDevice(c->device));
     BedState* S; SVXCHK(bed_state(c, &S));
-    S->used = 0; S->have = false; S->n_lines = S->n_bytes = 0; S->n_files = 0;
+    S->pool.reset(); S->have = false; S->n_lines = S->n_bytes = 0; S->n_files = 0;
     c->bed_calls++;                    // (a BGZF stream made of the text before is void from here on)
     memset(&S->stats, 0, sizeof S->stats);
     const bool cand = product == SVX_BED_CANDIDATE_BEDS, with_members = product != SVX_BED_SIGNATURE_VCF;
@@ -389,7 +381,7 @@ extern "C" int svx_bed(svx_ctx* c, int product, int source, const svx_cluster_vi
     BedIn in; memset(&in, 0, sizeof in);
     int64_t group_count[6];
     HostCopy hc(st);
-#define UP(field, type, host, count) do { type* d_; SVXCHK(S->get(&d_, (count))); if ((count)) SVXCHK(hc.h2d(d_, (host), (size_t)(count) * sizeof(type))); in.field = d_; } while (0)
+#define UP(field, type, host, count) do { type* d_; SVXCHK(S->pool.get(&d_, (count))); if ((count)) SVXCHK(hc.h2d(d_, (host), (size_t)(count) * sizeof(type))); in.field = d_; } while (0)
     if (source == 0) {
         if (cand) {
             CandDev cd;
@@ -478,7 +470,7 @@ extern "C" int svx_bed(svx_ctx* c, int product, int source, const svx_cluster_vi
     SVXCHK(svx_repr_device_tables(c, &in.rtab));
     in.short_line = ip->debug_short_line;
     unsigned long long* tot;
-    { int* err; unsigned long long* cnt; SVXCHK(S->get(&err, 2)); SVXCHK(S->get(&cnt, 8)); SVXCHK(S->get(&tot, 16)); HIPCHK(hipMemsetAsync(err, 0, 8, st)); HIPCHK(hipMemsetAsync(cnt, 0, 64, st)); in.err = err; in.counters = cnt; }
+    { int* err; unsigned long long* cnt; SVXCHK(S->pool.get(&err, 2)); SVXCHK(S->pool.get(&cnt, 8)); SVXCHK(S->pool.get(&tot, 16)); HIPCHK(hipMemsetAsync(err, 0, 8, st)); HIPCHK(hipMemsetAsync(cnt, 0, 64, st)); in.err = err; in.counters = cnt; }
     HIPCHK(hipEventRecord(S->ev[1], st));
 
     // ---- 1: files and lines over the grouped table ----
@@ -523,15 +515,15 @@ extern "C" int svx_bed(svx_ctx* c, int product, int source, const svx_cluster_vi
     }
     const long long ne = n_lines;
     uint32_t* line_row; uint8_t* line_form;
-    SVXCHK(S->get(&line_row, ne)); SVXCHK(S->get(&line_form, ne));
+    SVXCHK(S->pool.get(&line_row, ne)); SVXCHK(S->pool.get(&line_form, ne));
     if (product == SVX_BED_SIGNATURE_VCF) {
         uint32_t *idx, *v1; uint64_t *key_end, *key_end2, *key_cs, *key_cs_g, *key_cs2;
-        SVXCHK(S->get(&idx, ne)); SVXCHK(S->get(&v1, ne));
-        SVXCHK(S->get(&key_end, ne)); SVXCHK(S->get(&key_end2, ne)); SVXCHK(S->get(&key_cs, ne)); SVXCHK(S->get(&key_cs_g, ne)); SVXCHK(S->get(&key_cs2, ne));
+        SVXCHK(S->pool.get(&idx, ne)); SVXCHK(S->pool.get(&v1, ne));
+        SVXCHK(S->pool.get(&key_end, ne)); SVXCHK(S->pool.get(&key_end2, ne)); SVXCHK(S->pool.get(&key_cs, ne)); SVXCHK(S->pool.get(&key_cs_g, ne)); SVXCHK(S->pool.get(&key_cs2, ne));
         k_bed_vcf_keys<<<BGRID(ne), BT, 0, st>>>(ne, in, key_end, key_cs, idx, line_form);
         SVXCHK(svx_sort_pairs_u64(c, key_end, key_end2, idx, v1, ne, 0, 32));
         k_bed_gather_u64<<<BGRID(ne), BT, 0, st>>>(key_cs, v1, key_cs_g, ne);
-        SVXCHK(svx_sort_pairs_u64(c, key_cs_g, key_cs2, v1, line_row, ne, 0, std::min(64, 32 + std::max(1, bed_ceil_log2((long long)ip->n_contig + 1)))));
+        SVXCHK(svx_sort_pairs_u64(c, key_cs_g, key_cs2, v1, line_row, ne, 0, std::min(64, 32 + std::max(1, svx_ceil_log2((long long)ip->n_contig + 1)))));
     } else {
         k_bed_entries<<<BGRID(ne), BT, 0, st>>>(ne, sl, line_row, line_form);
     }
@@ -540,14 +532,14 @@ extern "C" int svx_bed(svx_ctx* c, int product, int source, const svx_cluster_vi
     // ---- 2: member piece lengths and their prefix, line lengths, offsets ----
     if (with_members) {
         int32_t* len; int64_t* pre;
-        SVXCHK(S->get(&len, nm + 1)); SVXCHK(S->get(&pre, nm + 1));
+        SVXCHK(S->pool.get(&len, nm + 1)); SVXCHK(S->pool.get(&pre, nm + 1));
         BedIn mi = in; mi.n_members = nm;
         k_bed_member_len<<<BGRID(nm + 1), BT, 0, st>>>(mi, len);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, len, pre, nm + 1));
         in.P = pre;
     }
     int64_t *line_len, *tiles, *tile_start;
-    SVXCHK(S->get(&line_len, ne + 1)); SVXCHK(S->get(&tiles, ne + 1)); SVXCHK(S->get(&tile_start, ne + 1));
+    SVXCHK(S->pool.get(&line_len, ne + 1)); SVXCHK(S->pool.get(&tiles, ne + 1)); SVXCHK(S->pool.get(&tile_start, ne + 1));
     k_bed_lengths<<<BGRID(ne + 1), BT, 0, st>>>(ne, line_row, line_form, in, line_len, tiles);
     SVXCHK(svx_exclusive_scan_i64(c, line_len, line_off, ne + 1));
     SVXCHK(svx_exclusive_scan_i64(c, tiles, tile_start, ne + 1));
@@ -576,7 +568,7 @@ extern "C" int svx_bed(svx_ctx* c, int product, int source, const svx_cluster_vi
         }
     }
     uint8_t* out = S->out.as<uint8_t>();
-    BedSeg* segs; SVXCHK(S->get(&segs, (size_t)ne));
+    BedSeg* segs; SVXCHK(S->pool.get(&segs, (size_t)ne));
     // ---- 3: skeleton, payload ----
     k_bed_skeleton<<<BGRID(ne), BT, 0, st>>>(ne, line_row, line_form, in, line_off, out, segs);
     HIPCHK(hipEventRecord(S->ev[4], st));

@@ -61,17 +61,11 @@ struct CandTab {
 struct CombineState {
     CandTab merged, flagged, fdup, result, tan;      // tan: the tandem candidates stage 4 walks (scratch)
     DevBuf in[14]; DevBuf in_aux; DevBuf rank;
-    DevBuf pool[NPOOL]; int used = 0;
+    ScratchPool<NPOOL> pool{"combine", 0};      // no pad: SVX_ALLOC_GUARD=1 faults on the first byte behind what a phase asked for
     DevBuf rm1_list, rm2_list; int64_t n_rm1 = 0, n_rm2 = 0;
     bool have_stage2 = false, have_result = false;
     bool from_resident = false; long long cluster_call = 0;      // the call took the resident clusters (source 0) of svx_cluster call number cluster_call
     svx_combine_stats stats;
-    template <class Tp> int get(Tp** out, size_t count) {
-        if (used >= NPOOL) return svx_fail(SVX_E_CAPACITY, "combine: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(pool[used].reserve((count ? count : 1) * sizeof(Tp)));
-        *out = pool[used++].as<Tp>();
-        return SVX_OK;
-    }
 };
 
 void svx_combine_release(svx_ctx* c) {
@@ -80,7 +74,7 @@ void svx_combine_release(svx_ctx* c) {
     s->merged.release(); s->flagged.release(); s->fdup.release(); s->result.release(); s->tan.release();
     for (auto& b : s->in) b.release();
     s->in_aux.release(); s->rank.release(); s->rm1_list.release(); s->rm2_list.release();
-    for (auto& b : s->pool) b.release();
+    s->pool.release();
     delete s;
     c->combine = nullptr;
 }
@@ -596,8 +590,8 @@ static int finish_offsets(svx_ctx* c, CandTab& t, int64_t n) {
 static int sort_destinations(svx_ctx* c, CombineState* S, CandPtrs t, int64_t base, int64_t n, int which, const int32_t* rank, int32_t n_contig,
                              uint64_t** key_out, long long** end_out) {
     uint64_t *k_end, *k_end2, *k_cs, *k_cs_g, *k_cs2; long long *ends, *ends2; uint32_t *v0, *v1, *v2;
-    SVXCHK(S->get(&k_end, n)); SVXCHK(S->get(&k_end2, n)); SVXCHK(S->get(&k_cs, n)); SVXCHK(S->get(&k_cs_g, n)); SVXCHK(S->get(&k_cs2, n));
-    SVXCHK(S->get(&ends, n)); SVXCHK(S->get(&ends2, n)); SVXCHK(S->get(&v0, n)); SVXCHK(S->get(&v1, n)); SVXCHK(S->get(&v2, n));
+    SVXCHK(S->pool.get(&k_end, n)); SVXCHK(S->pool.get(&k_end2, n)); SVXCHK(S->pool.get(&k_cs, n)); SVXCHK(S->pool.get(&k_cs_g, n)); SVXCHK(S->pool.get(&k_cs2, n));
+    SVXCHK(S->pool.get(&ends, n)); SVXCHK(S->pool.get(&ends2, n)); SVXCHK(S->pool.get(&v0, n)); SVXCHK(S->pool.get(&v1, n)); SVXCHK(S->pool.get(&v2, n));
     *key_out = k_cs2; *end_out = ends2;
     if (n <= 0) return SVX_OK;
     hipStream_t st = c->stream;
@@ -626,10 +620,10 @@ static int combine_body(svx_ctx* c, CombineState* S, const CluPtrs& cl, const in
     int64_t *mflag = nullptr, *mexcl = nullptr; int32_t *kf = nullptr, *kr = nullptr;
     if (n_ins > 0) {
         X.n_bnd_mirrored = n_bnd;
-        SVXCHK(S->get(&mflag, n_ins + 1)); SVXCHK(S->get(&mexcl, n_ins + 1)); SVXCHK(S->get(&kf, n_ins)); SVXCHK(S->get(&kr, n_ins));
+        SVXCHK(S->pool.get(&mflag, n_ins + 1)); SVXCHK(S->pool.get(&mexcl, n_ins + 1)); SVXCHK(S->pool.get(&kf, n_ins)); SVXCHK(S->pool.get(&kr, n_ins));
         if (n_bnd > 0) {
             uint64_t *bk, *bk2; uint32_t *bv, *bv2;
-            SVXCHK(S->get(&bk, 2 * n_bnd)); SVXCHK(S->get(&bk2, 2 * n_bnd)); SVXCHK(S->get(&bv, 2 * n_bnd)); SVXCHK(S->get(&bv2, 2 * n_bnd));
+            SVXCHK(S->pool.get(&bk, 2 * n_bnd)); SVXCHK(S->pool.get(&bk2, 2 * n_bnd)); SVXCHK(S->pool.get(&bv, 2 * n_bnd)); SVXCHK(S->pool.get(&bv2, 2 * n_bnd));
             k_bnd_keys<<<CGRID(2 * n_bnd), CT, 0, st>>>(cl, base[SVX_BND], n_bnd, bk, bv);
             SVXCHK(svx_sort_pairs_u64(c, bk, bk2, bv, bv2, 2 * n_bnd, 0, 64));
             k_ins_merge<<<CGRID(n_ins), CT, 0, st>>>(cl, base[SVX_INS], n_ins, base[SVX_BND], n_bnd, bk2, bv2, (long long)P.trans_sv_max_distance, mflag, kf, kr);
@@ -643,7 +637,7 @@ static int combine_body(svx_ctx* c, CombineState* S, const CluPtrs& cl, const in
     SVXCHK(S->rm1_list.reserve((size_t)(n_new > 0 ? n_new : 1) * 4));
     if (n_new > 0) {
         double *prod, *mainsc;
-        SVXCHK(S->get(&prod, n_new)); SVXCHK(S->get(&mainsc, n_new));
+        SVXCHK(S->pool.get(&prod, n_new)); SVXCHK(S->pool.get(&mainsc, n_new));
         k_merge_rows<<<CGRID(n_ins), CT, 0, st>>>(cl, base[SVX_INS], n_ins, base[SVX_BND], n_bnd, mflag, mexcl, kf, kr, S->merged.ptrs(), prod, mainsc, S->rm1_list.as<int32_t>());
         std::vector<double> hp((size_t)n_new), hm((size_t)n_new);
         SVXCHK(svx_d2h(hp.data(), prod, (size_t)n_new * 8, st));
@@ -666,7 +660,7 @@ static int combine_body(svx_ctx* c, CombineState* S, const CluPtrs& cl, const in
     SVXCHK(S->flagged.reserve(n_from));
     if (n_from > 0) {
         int32_t *from_s, *from_e, *dmid, *dspan; double* dmin;
-        SVXCHK(S->get(&from_s, n_from)); SVXCHK(S->get(&from_e, n_from)); SVXCHK(S->get(&dmid, n_del)); SVXCHK(S->get(&dspan, n_del)); SVXCHK(S->get(&dmin, n_from));
+        SVXCHK(S->pool.get(&from_s, n_from)); SVXCHK(S->pool.get(&from_e, n_from)); SVXCHK(S->pool.get(&dmid, n_del)); SVXCHK(S->pool.get(&dspan, n_del)); SVXCHK(S->pool.get(&dmin, n_from));
         k_flag_rows<<<CGRID(n_from), CT, 0, st>>>(cl, base[SVX_DUP_INT], n_di, S->merged.ptrs(), n_new, S->flagged.ptrs(), from_s, from_e);
         k_del_prep<<<CGRID(n_del), CT, 0, st>>>(cl.start, cl.end, base[SVX_DEL], n_del, dmid, dspan);
         HIPCHK(hipEventRecord(c->ev[22], st));
@@ -682,7 +676,7 @@ static int combine_body(svx_ctx* c, CombineState* S, const CluPtrs& cl, const in
 
     // ---- deletion clusters with score > 0 (stream compaction, order kept) -------------------------------------------------------------------
     int64_t *dflag, *dexcl; int32_t* del_rows;
-    SVXCHK(S->get(&dflag, n_del + 1)); SVXCHK(S->get(&dexcl, n_del + 1)); SVXCHK(S->get(&del_rows, n_del));
+    SVXCHK(S->pool.get(&dflag, n_del + 1)); SVXCHK(S->pool.get(&dexcl, n_del + 1)); SVXCHK(S->pool.get(&del_rows, n_del));
     int64_t n_del_keep = 0;
     if (n_del > 0) {
         k_flag_positive<<<CGRID(n_del), CT, 0, st>>>(cl.score, base[SVX_DEL], n_del, dflag);
@@ -696,14 +690,14 @@ static int combine_body(svx_ctx* c, CombineState* S, const CluPtrs& cl, const in
     if (n_from > 0) {
         CandPtrs F = S->flagged.ptrs();
         uint64_t *pk, *pk2; uint32_t *pv, *pv2; int64_t *pflag, *pexcl, *pstart;
-        SVXCHK(S->get(&pk, n_from)); SVXCHK(S->get(&pk2, n_from)); SVXCHK(S->get(&pv, n_from)); SVXCHK(S->get(&pv2, n_from));
-        SVXCHK(S->get(&pflag, n_from + 1)); SVXCHK(S->get(&pexcl, n_from + 1));
+        SVXCHK(S->pool.get(&pk, n_from)); SVXCHK(S->pool.get(&pk2, n_from)); SVXCHK(S->pool.get(&pv, n_from)); SVXCHK(S->pool.get(&pv2, n_from));
+        SVXCHK(S->pool.get(&pflag, n_from + 1)); SVXCHK(S->pool.get(&pexcl, n_from + 1));
         k_dup_keys<<<CGRID(n_from), CT, 0, st>>>(F, n_from, rank, n_contig, pk, pv);
         SVXCHK(svx_sort_pairs_u64(c, pk, pk2, pv, pv2, n_from, 0, 64));
         k_dup_part_flags<<<CGRID(n_from), CT, 0, st>>>(F, n_from, pv2, (long long)P.partition_max_distance, pflag);
         SVXCHK(scan_with_total(c, pflag, pexcl, n_from));
         SVXCHK(read_word(c, pexcl + n_from, &n_part));
-        SVXCHK(S->get(&pstart, n_part + 1));
+        SVXCHK(S->pool.get(&pstart, n_part + 1));
         k_dup_part_starts<<<CGRID(n_from), CT, 0, st>>>(pflag, pexcl, n_from, pstart, n_part);
         std::vector<int64_t> hps((size_t)n_part + 1);
         SVXCHK(svx_d2h(hps.data(), pstart, (size_t)(n_part + 1) * 8, st));
@@ -727,9 +721,9 @@ static int combine_body(svx_ctx* c, CombineState* S, const CluPtrs& cl, const in
         label_off.push_back((int64_t)sel.size());
         const int64_t nq = (int64_t)ns.size(), n_sel = (int64_t)sel.size();
         int32_t *sel_d, *prob_d, *ns_d, *labels; int64_t *sel_off_d, *d_off_d, *label_off_d, *ncl, *clu_off; double* dist;
-        SVXCHK(S->get(&sel_d, n_sel)); SVXCHK(S->get(&prob_d, nq)); SVXCHK(S->get(&ns_d, nq)); SVXCHK(S->get(&labels, n_sel));
-        SVXCHK(S->get(&sel_off_d, n_part + 1)); SVXCHK(S->get(&d_off_d, nq + 1)); SVXCHK(S->get(&label_off_d, nq + 1));
-        SVXCHK(S->get(&ncl, n_part + 1)); SVXCHK(S->get(&clu_off, n_part + 1)); SVXCHK(S->get(&dist, d_off.back()));
+        SVXCHK(S->pool.get(&sel_d, n_sel)); SVXCHK(S->pool.get(&prob_d, nq)); SVXCHK(S->pool.get(&ns_d, nq)); SVXCHK(S->pool.get(&labels, n_sel));
+        SVXCHK(S->pool.get(&sel_off_d, n_part + 1)); SVXCHK(S->pool.get(&d_off_d, nq + 1)); SVXCHK(S->pool.get(&label_off_d, nq + 1));
+        SVXCHK(S->pool.get(&ncl, n_part + 1)); SVXCHK(S->pool.get(&clu_off, n_part + 1)); SVXCHK(S->pool.get(&dist, d_off.back()));
         SVXCHK(svx_h2d(sel_d, sel.data(), (size_t)n_sel * 4, st));
         SVXCHK(svx_h2d(sel_off_d, sel_off.data(), (size_t)(n_part + 1) * 8, st));
         if (nq > 0) {
@@ -756,8 +750,8 @@ static int combine_body(svx_ctx* c, CombineState* S, const CluPtrs& cl, const in
     CandTab& R = S->result;
     int64_t n_ins_keep = 0, n_rm2 = 0;
     int64_t *keep = nullptr, *kexcl = nullptr, *r2flag = nullptr, *r2excl = nullptr; int32_t* ins_rows = nullptr; uint8_t* rm2 = nullptr;
-    SVXCHK(S->get(&keep, n_ins + 1)); SVXCHK(S->get(&kexcl, n_ins + 1)); SVXCHK(S->get(&r2flag, n_ins + 1)); SVXCHK(S->get(&r2excl, n_ins + 1));
-    SVXCHK(S->get(&ins_rows, n_ins)); SVXCHK(S->get(&rm2, n_ins));
+    SVXCHK(S->pool.get(&keep, n_ins + 1)); SVXCHK(S->pool.get(&kexcl, n_ins + 1)); SVXCHK(S->pool.get(&r2flag, n_ins + 1)); SVXCHK(S->pool.get(&r2excl, n_ins + 1));
+    SVXCHK(S->pool.get(&ins_rows, n_ins)); SVXCHK(S->pool.get(&rm2, n_ins));
     CandTab& tan_tab = S->tan;
     SVXCHK(tan_tab.reserve(n_tan));
     if (n_tan > 0) k_cmb_emit<<<CGRID(n_tan), CT, 0, st>>>(cl, SVX_CAND_DUP_TAN, n_tan, nullptr, base[SVX_DUP_TAN], tan_tab.ptrs(), 0, sig_aux, n_sig);
@@ -815,7 +809,7 @@ extern "C" int svx_combine(svx_ctx* c, int source, const svx_cluster_view* cv, c
     HIPCHK(hipSetDevice(c->device));
     if (!c->combine) c->combine = new CombineState();
     CombineState* S = c->combine;
-    S->used = 0; S->have_stage2 = false; S->have_result = false; S->n_rm1 = S->n_rm2 = 0;
+    S->pool.reset(); S->have_stage2 = false; S->have_result = false; S->n_rm1 = S->n_rm2 = 0;
     S->from_resident = source == 0; S->cluster_call = c->cluster_calls;
     c->combine_calls++;                                             // (genotype columns of an earlier candidate table are void from here on: genotype.hip)
     memset(&S->stats, 0, sizeof S->stats);

@@ -64,6 +64,25 @@ struct DevBuf {
     }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+// The scratch arrays of one call of a stage: N buffers handed out in order and kept for the next call, which asks for them in the same order.  owner: the
+// stage's name in the error message; pad: bytes added behind every array
+template <int N> struct ScratchPool {
+    DevBuf buf[N]; int used = 0;
+    const char* owner; size_t pad;
+    explicit ScratchPool(const char* owner_, size_t pad_ = 64) : owner(owner_), pad(pad_) {}
+    template <class T> int get(T** out, size_t count) {
+        if (used >= N) {
+            char what[96]; snprintf(what, sizeof what, "%s: scratch pool exhausted", owner);
+            return svx_fail(SVX_E_CAPACITY, what, __FILE__, __LINE__, hipSuccess);
+        }
+        SVXCHK(buf[used].reserve((count ? count : 1) * sizeof(T) + pad));
+        *out = buf[used++].template as<T>();
+        return SVX_OK;
+    }
+    void reset() { used = 0; }
+    void release() { for (auto& b : buf) b.release(); used = 0; }
+};
+inline int svx_ceil_log2(long long n) { int b = 0; while ((1ll << b) < n) b++; return b; }
 
 // Device-resident signature table (SoA); `cap` entries allocated.
 struct DevSigs {

@@ -144,22 +144,16 @@ int svx_genotype_impl(svx_ctx* c, int32_t mode, int64_t n_cand, const int32_t* t
 //   k_geno_call      the call from the two counts (:79-93); support_fraction is ONE FP64 division
 // ---------------------------------------------------------------------------------------------------------
 struct GenoState {
-    DevBuf pool[32]; int used = 0;
+    ScratchPool<32> pool{"genotype"};
     DevBuf gt, ref_reads, alt_reads, frac;                       // the resident columns
     int64_t n = 0; bool have = false; int source = -1; long long combine_call = 0, cluster_call = 0;
     hipEvent_t ev[6]; bool have_ev = false;
     svx_genotype_stats stats;
-    template <class Tp> int get(Tp** o, size_t count) {
-        if (used >= 32) return svx_fail(SVX_E_CAPACITY, "genotype: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(pool[used].reserve((count ? count : 1) * sizeof(Tp) + 64));
-        *o = pool[used++].as<Tp>();
-        return SVX_OK;
-    }
 };
 void svx_genotype_release(svx_ctx* c) {
     GenoState* S = c->genores;
     if (!S) return;
-    for (auto& b : S->pool) b.release();
+    S->pool.release();
     S->gt.release(); S->ref_reads.release(); S->alt_reads.release(); S->frac.release();
     if (S->have_ev) for (auto& e : S->ev) (void)hipEventDestroy(e);
     delete S;
@@ -229,7 +223,7 @@ extern "C" int svx_genotype_resident(svx_ctx* c, int source, const svx_candidate
     if (!c->genores) c->genores = new GenoState();
     GenoState* S = c->genores;
     if (!S->have_ev) { for (auto& e : S->ev) HIPCHK(hipEventCreate(&e)); S->have_ev = true; }
-    S->used = 0; S->have = false; S->n = 0;
+    S->pool.reset(); S->have = false; S->n = 0;
     memset(&S->stats, 0, sizeof S->stats);
     const svx_genotype_params P = *pp;
     hipStream_t st = c->stream;
@@ -264,7 +258,7 @@ extern "C" int svx_genotype_resident(svx_ctx* c, int source, const svx_candidate
             if (cv->member_off[i + 1] < cv->member_off[i]) return svx_fail(SVX_E_ARG, "svx_genotype_resident: member_off decreases", __FILE__, __LINE__, hipSuccess);
         }
         HostCopy hc(st);
-#define UP(dst, type, host, count) do { type* d_; SVXCHK(S->get(&d_, (count))); if ((count)) SVXCHK(hc.h2d(d_, (host), (size_t)(count) * sizeof(type))); dst = d_; } while (0)
+#define UP(dst, type, host, count) do { type* d_; SVXCHK(S->pool.get(&d_, (count))); if ((count)) SVXCHK(hc.h2d(d_, (host), (size_t)(count) * sizeof(type))); dst = d_; } while (0)
         UP(t.cls, uint8_t, cv->cls, n); UP(t.contig, int32_t, cv->contig, n); UP(t.start, int32_t, cv->start, n); UP(t.end, int32_t, cv->end, n);
         UP(t.contig2, int32_t, cv->contig2, n); UP(t.start2, int32_t, cv->start2, n); UP(t.score, double, cv->score, n);
         UP(member_off, int64_t, cv->member_off, n + 1); UP(members, int32_t, cv->members, m); UP(rid, int32_t, sig_read_id, (size_t)n_sig);
@@ -282,13 +276,13 @@ extern "C" int svx_genotype_resident(svx_ctx* c, int source, const svx_candidate
     if (n > 0) {
         const unsigned grid = (unsigned)((n + 255) / 256);
         int32_t *tid, *start, *end, *ref, *ids; uint8_t *sel, *zbad; int64_t* ids_off; int* err;
-        SVXCHK(S->get(&tid, n)); SVXCHK(S->get(&start, n)); SVXCHK(S->get(&end, n)); SVXCHK(S->get(&ref, n)); SVXCHK(S->get(&sel, n)); SVXCHK(S->get(&zbad, n + 1));
-        SVXCHK(S->get(&ids, nm)); SVXCHK(S->get(&ids_off, n + 1)); SVXCHK(S->get(&err, 2));
+        SVXCHK(S->pool.get(&tid, n)); SVXCHK(S->pool.get(&start, n)); SVXCHK(S->pool.get(&end, n)); SVXCHK(S->pool.get(&ref, n)); SVXCHK(S->pool.get(&sel, n)); SVXCHK(S->pool.get(&zbad, n + 1));
+        SVXCHK(S->pool.get(&ids, nm)); SVXCHK(S->pool.get(&ids_off, n + 1)); SVXCHK(S->pool.get(&err, 2));
         HIPCHK(hipMemsetAsync(err, 0, 8, st));
         k_geno_loci<<<grid, 256, 0, st>>>(t, P.minimum_score, tid, start, end, sel);
         // ---- reads_supporting_variant ----
         DistinctBufs b;
-        SVXCHK(S->get(&b.k0, nm)); SVXCHK(S->get(&b.k1, nm)); SVXCHK(S->get(&b.v0, nm)); SVXCHK(S->get(&b.v1, nm)); SVXCHK(S->get(&b.flag, nm + 1)); SVXCHK(S->get(&b.ex, nm + 1));
+        SVXCHK(S->pool.get(&b.k0, nm)); SVXCHK(S->pool.get(&b.k1, nm)); SVXCHK(S->pool.get(&b.v0, nm)); SVXCHK(S->pool.get(&b.v1, nm)); SVXCHK(S->pool.get(&b.flag, nm + 1)); SVXCHK(S->pool.get(&b.ex, nm + 1));
         const MemberIds m{n, nm, ns, 0, member_off, members, rid, nullptr, err};
         SVXCHK(svx_distinct_member_ids(c, m, 0, b, zbad));
         if (nm > 0) k_geno_compact<<<(unsigned)((nm + 255) / 256), 256, 0, st>>>(nm, b.k1, b.flag, b.ex, ids, err);

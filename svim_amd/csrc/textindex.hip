@@ -1,6 +1,7 @@
 // textindex.hip - the tabix index (.tbi, uncompressed bytes) of every file of the BGZF stream the last svx_text_gz left in the context, built where the text
-// and the block table lie (svx_text_index*, include/svx.h; gfx950).  What an index says: svim_amd/tabix.py; the line parser, the binning and the layout:
-// textindex_core.hpp, the source svx_text_index_host is built from as well.
+// and the block table lie (svx_text_index*, include/svx.h; gfx950).  What an index says: svim_amd/tabix.py; the line parser: textindex_core.hpp, the source
+// svx_text_index_host is built from as well.  This file makes the row table - lines, records, contig runs, names, the status of every file - and the headers;
+// the phases behind it (bins, sizes, the linear index, a contig's part) are those a .bai has too: binidx_kernels.hpp, instantiated with TixRows.
 // Replaces: tabix / bcftools index after the fact (the reference writes plain text; its users compress and index it).
 // Phases, all on the context's stream; counts cross to the host between them:
 //   lines      line starts counted per 64-byte piece of the text, scanned, written (one table for the three sources; the files' first bytes start lines too)
@@ -8,7 +9,7 @@
 //              Lines that are skipped ('#', empty) are compacted away by a scan
 //   contigs    run heads where column 1 differs from the record before (or the file does); chunk heads where the bin does too; the order and range checks
 //              raise per-file flags; the run-head names go to the host, which looks for a name with two runs and settles every file's status
-//   chunks     (contig << 32 | bin, chunk) sorted stably (svx_sort_pairs_u64), bin heads and contig heads of the sorted list compacted
+//   chunks     (contig << 16 | bin, chunk) sorted stably (svx_sort_pairs_u64), bin heads of the sorted list compacted, first bin of every contig by bisection
 //   linear     a record's windows get atomicMin(vbeg): its own lane for one window, the whole wave for a record of many (an inversion over a contig has 32 768)
 //   serialise  sizes per contig, a scan, the headers and names written by the host, then one lane per chunk and one wave per contig store every field at its
 //              offset; the wave's backward fill of the empty slots is a reverse scan in tiles of 64.
@@ -17,12 +18,13 @@
 #include "common.hpp"
 #include "hostcopy.hpp"
 #include "textindex_core.hpp"
+#include "binidx_kernels.hpp"
 #include <algorithm>
 #include <string>
 #include <unordered_set>
 
-#define XT 256
-#define XGRID(n) (unsigned)(((long long)(n) + XT - 1) / XT)
+#define XT BINIDX_T
+#define XGRID(n) BINIDX_GRID(n)
 #define TIX_PIECE 64
 #define TIX_NPOOL 64
 enum { TIXF_ORDER = 1, TIXF_RANGE = 2 };
@@ -75,13 +77,13 @@ __global__ void k_tix_parse(TixIn in, long long n_lines, const int64_t* line, Ti
     const TixLine L = tix_parse_line(in.text, s, e, in.preset);
     o.beg[i] = L.beg; o.end[i] = L.end; o.name_len[i] = L.name_len; o.file[i] = k; o.isrec[i] = L.skip ? 0 : 1;
     o.vbeg[i] = tix_voff(s, in.coff, in.uoff, in.ffb[k], in.ffb[k + 1], in.coff[in.ffb[k]], in.sbase[k]);
-    if (!L.skip && L.end > TIX_MAX_END) atomicOr(in.fflag + k, TIXF_RANGE);
+    if (!L.skip && L.end > BINIDX_MAX_END) atomicOr(in.fflag + k, TIXF_RANGE);
 }
 __global__ void k_tix_compact_records(long long n_lines, const int32_t* isrec, const int64_t* rpos, long long n_rec, uint32_t* r_line) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_lines && isrec[i] && rpos[i] < n_rec) r_line[rpos[i]] = (uint32_t)i;
 }
-__device__ __forceinline__ uint32_t tix_bin_of(const TixLines& L, long long i) { return L.end[i] <= TIX_MAX_END ? tix_reg2bin(L.beg[i], L.end[i]) : 0u; }
+__device__ __forceinline__ uint32_t tix_bin_of(const TixLines& L, long long i) { return binidx_bin(BinIdxInterval{L.beg[i], L.end[i]}); }
 // contig run heads, chunk heads, the order check
 __global__ void k_tix_heads(TixIn in, long long n_rec, const uint32_t* r_line, const int64_t* line, TixLines L, int32_t* chead, int32_t* bhead) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -112,7 +114,7 @@ __global__ void k_tix_runs(long long n_rec, long long n_runs, long long n_chunks
     const long long t = cpos[j] + chead[j] - 1;                 // the run j lies in
     if (chead[j] && t < n_runs) { o.run_rec[t] = (uint32_t)j; o.run_file[t] = L.file[i]; o.run_nlen[t] = L.name_len[i] + 1; }
     const long long q = bpos[j];
-    if (bhead[j] && q < n_chunks) { o.chunk_rec[q] = (uint32_t)j; o.chunk_key[q] = ((uint64_t)t << 32) | tix_bin_of(L, i); o.chunk_val[q] = (uint32_t)q; }
+    if (bhead[j] && q < n_chunks) { o.chunk_rec[q] = (uint32_t)j; o.chunk_key[q] = binidx_key((uint64_t)t, tix_bin_of(L, i)); o.chunk_val[q] = (uint32_t)q; }
 }
 __global__ void k_tix_names(long long n_runs, const uint8_t* text, const int64_t* line, const uint32_t* r_line, const uint32_t* run_rec, const int32_t* run_nlen, const int64_t* nm_off,
                             long long n_names, uint8_t* names) {
@@ -124,145 +126,43 @@ __global__ void k_tix_names(long long n_runs, const uint8_t* text, const int64_t
     for (int k = 0; k < n; k++) names[at + k] = src[k];
     names[at + n] = 0;
 }
-// the sorted chunk list: bin heads, and per contig its first bin
-__global__ void k_tix_bin_heads(long long n_chunks, const uint64_t* key, int32_t* bh) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > n_chunks) return;
-    bh[p] = p < n_chunks && (p == 0 || key[p] != key[p - 1]) ? 1 : 0;
-}
-__global__ void k_tix_bins(long long n_chunks, long long n_bins, long long n_runs, const uint64_t* key, const int32_t* bh, const int64_t* binpos, uint32_t* bin_first, uint32_t* tid_first_bin) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > n_chunks) return;
-    if (p == n_chunks) { bin_first[n_bins] = (uint32_t)n_chunks; tid_first_bin[n_runs] = (uint32_t)n_bins; return; }
-    if (!bh[p]) return;
-    const long long q = binpos[p];
-    if (q < n_bins) bin_first[q] = (uint32_t)p;
-    const long long t = (long long)(key[p] >> 32);
-    if ((p == 0 || (key[p - 1] >> 32) != (key[p] >> 32)) && t < n_runs) tid_first_bin[t] = (uint32_t)q;
-}
-__global__ void k_tix_max_end(long long n_rec, const uint32_t* r_line, TixLines L, const int32_t* chead, const int64_t* cpos, const int32_t* fstat, int32_t* tmax) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_rec) return;
-    const long long i = r_line[j];
-    if (fstat[L.file[i]] != 0) return;
-    atomicMax(tmax + (cpos[j] + chead[j] - 1), (int32_t)L.end[i]);          // (end <= 2^29 in a file whose status is 0)
-}
-__global__ void k_tix_sizes(long long n_runs, const int32_t* run_file, const int32_t* fstat, const int32_t* tmax, const uint32_t* tid_first_bin, const uint32_t* bin_first,
-                            int64_t* tsz, int64_t* nintv) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > n_runs) return;
-    if (t == n_runs || fstat[run_file[t]] != 0) { tsz[t] = 0; nintv[t] = 0; return; }
-    const long long ni = 1 + (((long long)tmax[t] - 1) >> 14);
-    const uint32_t b0 = tid_first_bin[t], b1 = tid_first_bin[t + 1];
-    tsz[t] = tix_contig_bytes((long long)b1 - b0, (long long)bin_first[b1] - bin_first[b0], ni);
-    nintv[t] = ni;
-}
-__global__ __launch_bounds__(XT) void k_tix_linear(long long n_rec, const uint32_t* r_line, TixLines L, const int32_t* chead, const int64_t* cpos, const int32_t* fstat,
-                                                   const int64_t* loff, long long n_slots, unsigned long long* lin) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    long long w0 = 0, w1 = -1, base = 0; unsigned long long v = 0;
-    if (j < n_rec) {
-        const long long i = r_line[j];
-        if (fstat[L.file[i]] == 0) {
-            const long long t = cpos[j] + chead[j] - 1;
-            base = loff[t]; w0 = L.beg[i] >> 14; w1 = (L.end[i] - 1) >> 14; v = L.vbeg[i];
-            if (base + w1 >= n_slots || base + w1 >= loff[t + 1]) w1 = w0 - 1;       // (cannot happen: the slots were sized by the largest end)
-        }
+// the row table as binidx_kernels.hpp reads it: row j is record j of the stream, a group is a contig run
+struct TixRows {
+    const uint32_t* r_line; TixLines L; long long n_lines; const int32_t* chead; const int64_t* cpos; const int32_t* fstat; const uint64_t* eofv;
+    const uint32_t* run_rec; const int32_t* run_file; const int64_t *toff, *shift;
+    __device__ long long group(long long j) const { return cpos[j] + chead[j] - 1; }
+    __device__ bool live(long long j) const { return fstat[L.file[r_line[j]]] == 0; }
+    __device__ BinIdxInterval interval(long long j) const { const long long i = r_line[j]; return BinIdxInterval{L.beg[i], L.end[i]}; }
+    __device__ uint64_t vbeg(long long j) const { return L.vbeg[r_line[j]]; }
+    __device__ uint64_t vend(long long j) const {                 // the next line's start, or where the file's last line ends
+        const long long i = r_line[j]; const int f = L.file[i];
+        return (i + 1 < n_lines && L.file[i + 1] == f) ? L.vbeg[i + 1] : eofv[f];
     }
-    if (w1 == w0) atomicMin(lin + base + w0, v);
-    unsigned long long many = __ballot(w1 > w0);
-    while (many) {                                           // a record of many windows: the wave writes them, 64 at a time
-        const int src = __ffsll((long long)many) - 1;
-        many &= many - 1;
-        const long long b = __shfl(base, src, 64), lo = __shfl(w0, src, 64), hi = __shfl(w1, src, 64);
-        const unsigned long long vv = __shfl(v, src, 64);
-        for (long long w = lo + lane_id(); w <= hi; w += 64) atomicMin(lin + b + w, vv);
-    }
-}
-struct TixOut { uint8_t* blob; long long n_blob; int* err; const int64_t *toff, *shift; const int32_t *run_file, *fstat; };
-__device__ __forceinline__ uint8_t* tix_at(const TixOut& o, long long off, long long len) {
-    if (off < 0 || off + len > o.n_blob) { atomicOr(o.err, 1); return nullptr; }
-    return o.blob + off;
-}
-__global__ void k_tix_ser_chunks(long long n_chunks, const uint64_t* key, const uint32_t* val, const int32_t* bh, const int64_t* binpos, const uint32_t* bin_first,
-                                 const uint32_t* tid_first_bin, const uint32_t* chunk_rec, const uint32_t* r_line, TixLines L, long long n_lines, const uint64_t* eofv, TixOut o) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n_chunks) return;
-    const long long t = (long long)(key[p] >> 32);
-    const int f = o.run_file[t];
-    if (o.fstat[f] != 0) return;
-    const long long base = o.toff[t] + o.shift[f];
-    const long long q = binpos[p] + bh[p] - 1, fb = tid_first_bin[t];
-    const long long at = base + 4 + 8 * (q - fb) + 16 * ((long long)bin_first[q] - bin_first[fb]);
-    if (bh[p]) {
-        uint8_t* d = tix_at(o, at, 8);
-        if (d) { tix_put32(d, (uint32_t)key[p]); tix_put32(d + 4, bin_first[q + 1] - bin_first[q]); }
-    }
-    const uint32_t cq = val[p];
-    const long long i0 = r_line[chunk_rec[cq]], i1 = r_line[chunk_rec[cq + 1] - 1];
-    const uint64_t vend = (i1 + 1 < n_lines && L.file[i1 + 1] == f) ? L.vbeg[i1 + 1] : eofv[f];
-    uint8_t* d = tix_at(o, at + 8 + 16 * (p - (long long)bin_first[q]), 16);
-    if (d) { tix_put64(d, L.vbeg[i0]); tix_put64(d + 8, vend); }
-}
-// one wave per contig: n_bin, the pseudo-bin, n_intv, the linear index with its empty slots filled from behind
-__global__ __launch_bounds__(64) void k_tix_ser_contig(long long n_runs, const uint32_t* run_rec, const uint32_t* tid_first_bin, const uint32_t* bin_first, const uint32_t* r_line,
-                                                       TixLines L, long long n_lines, const uint64_t* eofv, const int64_t* loff, const unsigned long long* lin, TixOut o) {
-    const long long t = blockIdx.x;
-    if (t >= n_runs) return;
-    const int f = o.run_file[t];
-    if (o.fstat[f] != 0) return;
-    const long long base = o.toff[t] + o.shift[f];
-    const long long nb = (long long)tid_first_bin[t + 1] - tid_first_bin[t], nc = (long long)bin_first[tid_first_bin[t + 1]] - bin_first[tid_first_bin[t]];
-    const long long ni = loff[t + 1] - loff[t];
-    const long long ps = base + 4 + 8 * nb + 16 * nc;
-    if (lane_id() == 0) {
-        const long long j0 = run_rec[t], j1 = (long long)run_rec[t + 1] - 1;
-        const long long i0 = r_line[j0], i1 = r_line[j1];
-        const uint64_t vend = (i1 + 1 < n_lines && L.file[i1 + 1] == f) ? L.vbeg[i1 + 1] : eofv[f];
-        uint8_t* d = tix_at(o, base, 4);
-        if (d) tix_put32(d, (uint32_t)(nb + 1));
-        d = tix_at(o, ps, 44);
-        if (d) {
-            tix_put32(d, TIX_PSEUDO_BIN); tix_put32(d + 4, 2u); tix_put64(d + 8, L.vbeg[i0]); tix_put64(d + 16, vend);
-            tix_put64(d + 24, (uint64_t)(j1 - j0 + 1)); tix_put64(d + 32, 0ull); tix_put32(d + 40, (uint32_t)ni);
-        }
-    }
-    unsigned long long carry = TIX_NO_SLOT;
-    for (long long top = ni - 1; top >= 0; top -= 64) {                 // lane l holds window top - l: a prefix minimum over the lanes is a suffix minimum over the windows
-        const long long w = top - lane_id();
-        unsigned long long v = w >= 0 ? lin[loff[t] + w] : TIX_NO_SLOT;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) { const unsigned long long u = __shfl_up(v, s, 64); if (lane_id() >= s && u < v) v = u; }
-        if (carry < v) v = carry;
-        if (w >= 0) { uint8_t* d = tix_at(o, ps + 44 + 8 * w, 8); if (d) tix_put64(d, v); }
-        carry = __shfl(v, 63, 64);
-    }
-}
+    __device__ bool group_live(long long t) const { return fstat[run_file[t]] == 0; }
+    __device__ long long first(long long t) const { return run_rec[t]; }
+    __device__ long long last(long long t) const { return run_rec[t + 1]; }
+    __device__ long long part_off(long long t) const { return toff[t] + shift[run_file[t]]; }
+    __device__ uint64_t n_mapped(long long t) const { return (uint64_t)run_rec[t + 1] - run_rec[t]; }
+    __device__ uint64_t n_unmapped(long long) const { return 0; }
+};
 
 struct TextIndexState {
-    DevBuf pool[TIX_NPOOL]; int used = 0;
+    ScratchPool<TIX_NPOOL> pool{"text index"};
     DevBuf blob;
     std::vector<int64_t> file_off; std::vector<int32_t> status;
     long long gz_gen = -1; bool have = false;
     hipEvent_t ev[8]; bool have_ev = false;
     svx_text_index_stats stats;
-    template <class Tp> int get(Tp** o, size_t count) {
-        if (used >= TIX_NPOOL) return svx_fail(SVX_E_CAPACITY, "text index: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(pool[used].reserve((count ? count : 1) * sizeof(Tp) + 64));
-        *o = pool[used++].as<Tp>();
-        return SVX_OK;
-    }
 };
 void svx_textindex_release(svx_ctx* c) {
     TextIndexState* s = c->textindex;
     if (!s) return;
-    for (auto& b : s->pool) b.release();
+    s->pool.release();
     s->blob.release();
     if (s->have_ev) for (auto& e : s->ev) (void)hipEventDestroy(e);
     delete s;
     c->textindex = nullptr;
 }
-static int tix_ceil_log2(long long n) { int b = 0; while ((1ll << b) < n) b++; return b; }
 static bool tix_valid(svx_ctx* c, TextGzView* v) {
     return c && c->textindex && c->textindex->have && svx_textgz_view(c, v) && v->gen == c->textindex->gz_gen;
 }
@@ -275,7 +175,7 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     if (!c->textindex) { c->textindex = new TextIndexState(); }
     TextIndexState* S = c->textindex;
     if (!S->have_ev) { for (auto& e : S->ev) HIPCHK(hipEventCreate(&e)); S->have_ev = true; }
-    S->used = 0; S->have = false;
+    S->pool.reset(); S->have = false;
     memset(&S->stats, 0, sizeof S->stats);
     hipStream_t st = c->stream;
     const int nf = V.n_files; const long long nb = V.n_blocks, n_text = V.file_off_text[nf];
@@ -293,8 +193,8 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     int32_t* fstat_d; int* err_d;
     {
         int64_t *fo, *ffb, *uoff, *sb; uint64_t* ev;
-        SVXCHK(S->get(&fo, (size_t)nf + 1)); SVXCHK(S->get(&ffb, (size_t)nf + 1)); SVXCHK(S->get(&uoff, (size_t)nb + 1)); SVXCHK(S->get(&sb, (size_t)nf)); SVXCHK(S->get(&ev, (size_t)nf));
-        SVXCHK(S->get(&in.fflag, (size_t)nf)); SVXCHK(S->get(&fstat_d, (size_t)nf)); SVXCHK(S->get(&err_d, 2));
+        SVXCHK(S->pool.get(&fo, (size_t)nf + 1)); SVXCHK(S->pool.get(&ffb, (size_t)nf + 1)); SVXCHK(S->pool.get(&uoff, (size_t)nb + 1)); SVXCHK(S->pool.get(&sb, (size_t)nf)); SVXCHK(S->pool.get(&ev, (size_t)nf));
+        SVXCHK(S->pool.get(&in.fflag, (size_t)nf)); SVXCHK(S->pool.get(&fstat_d, (size_t)nf)); SVXCHK(S->pool.get(&err_d, 2));
         HostCopy hc(st);
         SVXCHK(hc.h2d(fo, V.file_off_text, ((size_t)nf + 1) * 8)); SVXCHK(hc.h2d(ffb, V.file_first_block, ((size_t)nf + 1) * 8)); SVXCHK(hc.h2d(uoff, V.h_uoff, ((size_t)nb + 1) * 8));
         SVXCHK(hc.h2d(sb, sbase.data(), (size_t)nf * 8)); SVXCHK(hc.h2d(ev, eofv.data(), (size_t)nf * 8));
@@ -308,12 +208,12 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     int64_t* line = nullptr;
     if (n_pieces > 0) {
         int32_t* cnt; int64_t* lpos;
-        SVXCHK(S->get(&cnt, (size_t)n_pieces + 1)); SVXCHK(S->get(&lpos, (size_t)n_pieces + 1));
+        SVXCHK(S->pool.get(&cnt, (size_t)n_pieces + 1)); SVXCHK(S->pool.get(&lpos, (size_t)n_pieces + 1));
         k_tix_line_count<<<XGRID(n_pieces + 1), XT, 0, st>>>(in, n_pieces, cnt);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, cnt, lpos, n_pieces + 1));
         SVXCHK(svx_d2h(&n_lines, lpos + n_pieces, 8, st));
         if (n_lines < 0 || n_lines > n_text || n_lines >= (1ll << 31)) return svx_fail(SVX_E_CAPACITY, "svx_text_index: too many lines", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&line, (size_t)n_lines + 1));
+        SVXCHK(S->pool.get(&line, (size_t)n_lines + 1));
         if (n_lines) k_tix_line_write<<<XGRID(n_pieces), XT, 0, st>>>(in, n_pieces, lpos, n_lines, line);
         HIPCHK(hipGetLastError());
     }
@@ -323,13 +223,13 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     int64_t n_rec = 0; uint32_t* r_line = nullptr;
     if (n_lines > 0) {
         int64_t* rpos;
-        SVXCHK(S->get(&L.beg, (size_t)n_lines)); SVXCHK(S->get(&L.end, (size_t)n_lines)); SVXCHK(S->get(&L.vbeg, (size_t)n_lines)); SVXCHK(S->get(&L.name_len, (size_t)n_lines));
-        SVXCHK(S->get(&L.file, (size_t)n_lines)); SVXCHK(S->get(&L.isrec, (size_t)n_lines + 1)); SVXCHK(S->get(&rpos, (size_t)n_lines + 1));
+        SVXCHK(S->pool.get(&L.beg, (size_t)n_lines)); SVXCHK(S->pool.get(&L.end, (size_t)n_lines)); SVXCHK(S->pool.get(&L.vbeg, (size_t)n_lines)); SVXCHK(S->pool.get(&L.name_len, (size_t)n_lines));
+        SVXCHK(S->pool.get(&L.file, (size_t)n_lines)); SVXCHK(S->pool.get(&L.isrec, (size_t)n_lines + 1)); SVXCHK(S->pool.get(&rpos, (size_t)n_lines + 1));
         k_tix_parse<<<XGRID(n_lines + 1), XT, 0, st>>>(in, n_lines, line, L);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, L.isrec, rpos, n_lines + 1));
         SVXCHK(svx_d2h(&n_rec, rpos + n_lines, 8, st));
         if (n_rec < 0 || n_rec > n_lines) return svx_fail(SVX_E_STATE, "svx_text_index: the record count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&r_line, (size_t)n_rec + 1));
+        SVXCHK(S->pool.get(&r_line, (size_t)n_rec + 1));
         if (n_rec) k_tix_compact_records<<<XGRID(n_lines), XT, 0, st>>>(n_lines, L.isrec, rpos, n_rec, r_line);
         HIPCHK(hipGetLastError());
     }
@@ -341,7 +241,7 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     int32_t *chead = nullptr, *bhead = nullptr; int64_t *cpos = nullptr, *bpos = nullptr, *nm_off = nullptr; uint8_t* names = nullptr;
     TixRuns R; memset(&R, 0, sizeof R);
     if (n_rec > 0) {
-        SVXCHK(S->get(&chead, (size_t)n_rec + 1)); SVXCHK(S->get(&bhead, (size_t)n_rec + 1)); SVXCHK(S->get(&cpos, (size_t)n_rec + 1)); SVXCHK(S->get(&bpos, (size_t)n_rec + 1));
+        SVXCHK(S->pool.get(&chead, (size_t)n_rec + 1)); SVXCHK(S->pool.get(&bhead, (size_t)n_rec + 1)); SVXCHK(S->pool.get(&cpos, (size_t)n_rec + 1)); SVXCHK(S->pool.get(&bpos, (size_t)n_rec + 1));
         k_tix_heads<<<XGRID(n_rec + 1), XT, 0, st>>>(in, n_rec, r_line, line, L, chead, bhead);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, chead, cpos, n_rec + 1));
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, bhead, bpos, n_rec + 1));
@@ -351,9 +251,9 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
             SVXCHK(hc.finish());
         }
         if (n_runs < 1 || n_runs > n_rec || n_chunks < n_runs || n_chunks > n_rec) return svx_fail(SVX_E_STATE, "svx_text_index: the run counts are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&R.run_rec, (size_t)n_runs + 1)); SVXCHK(S->get(&R.run_file, (size_t)n_runs + 1)); SVXCHK(S->get(&R.run_nlen, (size_t)n_runs + 1));
-        SVXCHK(S->get(&R.chunk_rec, (size_t)n_chunks + 1)); SVXCHK(S->get(&R.chunk_key, (size_t)n_chunks)); SVXCHK(S->get(&R.chunk_val, (size_t)n_chunks));
-        SVXCHK(S->get(&nm_off, (size_t)n_runs + 1));
+        SVXCHK(S->pool.get(&R.run_rec, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&R.run_file, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&R.run_nlen, (size_t)n_runs + 1));
+        SVXCHK(S->pool.get(&R.chunk_rec, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&R.chunk_key, (size_t)n_chunks)); SVXCHK(S->pool.get(&R.chunk_val, (size_t)n_chunks));
+        SVXCHK(S->pool.get(&nm_off, (size_t)n_runs + 1));
         k_tix_runs<<<XGRID(n_rec + 1), XT, 0, st>>>(n_rec, n_runs, n_chunks, r_line, L, chead, bhead, cpos, bpos, R);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, R.run_nlen, nm_off, n_runs + 1));
         run_file_h.assign((size_t)n_runs + 1, 0); nm_off_h.assign((size_t)n_runs + 1, 0);
@@ -364,7 +264,7 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
         }
         n_names = nm_off_h[(size_t)n_runs];
         if (n_names < n_runs || n_names > n_text + n_runs) return svx_fail(SVX_E_STATE, "svx_text_index: the name lengths are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&names, (size_t)n_names));
+        SVXCHK(S->pool.get(&names, (size_t)n_names));
         k_tix_names<<<XGRID(n_runs), XT, 0, st>>>(n_runs, in.text, line, r_line, R.run_rec, R.run_nlen, nm_off, n_names, names);
         HIPCHK(hipGetLastError());
         names_h.assign((size_t)n_names, 0);
@@ -387,22 +287,24 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     HIPCHK(hipEventRecord(S->ev[3], st));
     // ---- chunks sorted by (contig, bin); bins ----
     int64_t n_bins = 0, n_slots = 0;
+    TixRows rows; memset(&rows, 0, sizeof rows);
+    rows.r_line = r_line; rows.L = L; rows.n_lines = n_lines; rows.chead = chead; rows.cpos = cpos; rows.fstat = fstat_d; rows.eofv = in.eofv; rows.run_rec = R.run_rec; rows.run_file = R.run_file;
     uint64_t* key2 = nullptr; uint32_t *val2 = nullptr, *bin_first = nullptr, *tid_first_bin = nullptr; int32_t *bh = nullptr, *tmax = nullptr; int64_t *binpos = nullptr, *tsz = nullptr, *nintv = nullptr,
               *toff = nullptr, *loff = nullptr;
     std::vector<int64_t> toff_h((size_t)n_runs + 1, 0);
     if (n_rec > 0) {
-        SVXCHK(S->get(&key2, (size_t)n_chunks)); SVXCHK(S->get(&val2, (size_t)n_chunks)); SVXCHK(S->get(&bh, (size_t)n_chunks + 1)); SVXCHK(S->get(&binpos, (size_t)n_chunks + 1));
-        SVXCHK(svx_sort_pairs_u64(c, R.chunk_key, key2, R.chunk_val, val2, n_chunks, 0, std::min(64, 32 + std::max(1, tix_ceil_log2(n_runs + 1)))));
-        k_tix_bin_heads<<<XGRID(n_chunks + 1), XT, 0, st>>>(n_chunks, key2, bh);
+        SVXCHK(S->pool.get(&key2, (size_t)n_chunks)); SVXCHK(S->pool.get(&val2, (size_t)n_chunks)); SVXCHK(S->pool.get(&bh, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&binpos, (size_t)n_chunks + 1));
+        SVXCHK(svx_sort_pairs_u64(c, R.chunk_key, key2, R.chunk_val, val2, n_chunks, 0, binidx_sort_end_bit(n_runs)));
+        k_binidx_bin_heads<TixRows><<<XGRID(n_chunks + 1), XT, 0, st>>>(n_chunks, key2, bh);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, bh, binpos, n_chunks + 1));
         SVXCHK(svx_d2h(&n_bins, binpos + n_chunks, 8, st));
         if (n_bins < n_runs || n_bins > n_chunks) return svx_fail(SVX_E_STATE, "svx_text_index: the bin count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->get(&tid_first_bin, (size_t)n_runs + 1)); SVXCHK(S->get(&tmax, (size_t)n_runs + 1));
-        SVXCHK(S->get(&tsz, (size_t)n_runs + 1)); SVXCHK(S->get(&nintv, (size_t)n_runs + 1)); SVXCHK(S->get(&toff, (size_t)n_runs + 2)); SVXCHK(S->get(&loff, (size_t)n_runs + 2));
-        k_tix_bins<<<XGRID(n_chunks + 1), XT, 0, st>>>(n_chunks, n_bins, n_runs, key2, bh, binpos, bin_first, tid_first_bin);
+        SVXCHK(S->pool.get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->pool.get(&tid_first_bin, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&tmax, (size_t)n_runs + 1));
+        SVXCHK(S->pool.get(&tsz, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&nintv, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&toff, (size_t)n_runs + 2)); SVXCHK(S->pool.get(&loff, (size_t)n_runs + 2));
+        binidx_launch_bins<TixRows>(st, n_chunks, n_bins, n_runs, key2, bh, binpos, bin_first, tid_first_bin);
         HIPCHK(hipMemsetAsync(tmax, 0, ((size_t)n_runs + 1) * 4, st));
-        k_tix_max_end<<<XGRID(n_rec), XT, 0, st>>>(n_rec, r_line, L, chead, cpos, fstat_d, tmax);
-        k_tix_sizes<<<XGRID(n_runs + 1), XT, 0, st>>>(n_runs, R.run_file, fstat_d, tmax, tid_first_bin, bin_first, tsz, nintv);
+        k_binidx_max_end<<<XGRID(n_rec), XT, 0, st>>>(rows, n_rec, tmax);
+        k_binidx_sizes<<<XGRID(n_runs + 1), XT, 0, st>>>(rows, n_runs, tmax, tid_first_bin, bin_first, tsz, nintv);
         SVXCHK(svx_exclusive_scan_i64(c, tsz, toff, n_runs + 1));
         SVXCHK(svx_exclusive_scan_i64(c, nintv, loff, n_runs + 1));
         HIPCHK(hipGetLastError());
@@ -417,9 +319,9 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     // ---- linear index: the smallest vbeg per window ----
     unsigned long long* lin = nullptr;
     if (n_rec > 0) {
-        SVXCHK(S->get(&lin, (size_t)n_slots));
+        SVXCHK(S->pool.get(&lin, (size_t)n_slots));
         if (n_slots) HIPCHK(hipMemsetAsync(lin, 0xff, (size_t)n_slots * 8, st));
-        k_tix_linear<<<XGRID(n_rec), XT, 0, st>>>(n_rec, r_line, L, chead, cpos, fstat_d, loff, n_slots, lin);
+        k_binidx_linear<<<XGRID(n_rec), XT, 0, st>>>(rows, n_rec, loff, n_slots, lin);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(S->ev[5], st));
@@ -439,7 +341,7 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
         h.assign((size_t)(TIX_HEADER_BYTES + l_nm), 0);
         memcpy(h.data(), "TBI\1", 4);
         const uint32_t w[8] = {(uint32_t)(t1 - t0), preset == SVX_INDEX_BED ? 0x10000u : 2u, 1u, 2u, preset == SVX_INDEX_BED ? 3u : 0u, (uint32_t)'#', 0u, (uint32_t)l_nm};
-        for (int q = 0; q < 8; q++) tix_put32(h.data() + 4 + 4 * q, w[q]);
+        for (int q = 0; q < 8; q++) binidx_put32(h.data() + 4 + 4 * q, w[q]);
         if (l_nm) memcpy(h.data() + TIX_HEADER_BYTES, names_h.data() + nm_off_h[(size_t)t0], (size_t)l_nm);
         shift[(size_t)k] = foff[(size_t)k] + TIX_HEADER_BYTES + l_nm - (n_runs ? toff_h[(size_t)t0] : 0);
         foff[(size_t)k + 1] = foff[(size_t)k] + TIX_HEADER_BYTES + l_nm + body + 8;
@@ -449,15 +351,16 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     uint8_t* blob = S->blob.as<uint8_t>();
     HIPCHK(hipMemsetAsync(blob, 0, (size_t)n_blob + 64, st));
     {
-        int64_t* shift_d; SVXCHK(S->get(&shift_d, (size_t)nf));
+        int64_t* shift_d; SVXCHK(S->pool.get(&shift_d, (size_t)nf));
         HostCopy hc(st);
         SVXCHK(hc.h2d(shift_d, shift.data(), (size_t)nf * 8));
         for (int k = 0; k < nf; k++) if (!heads[(size_t)k].empty()) SVXCHK(hc.h2d(blob + foff[(size_t)k], heads[(size_t)k].data(), heads[(size_t)k].size()));
         SVXCHK(hc.finish());
         if (n_rec > 0) {
-            TixOut o; o.blob = blob; o.n_blob = n_blob; o.err = err_d; o.toff = toff; o.shift = shift_d; o.run_file = R.run_file; o.fstat = fstat_d;
-            k_tix_ser_chunks<<<XGRID(n_chunks), XT, 0, st>>>(n_chunks, key2, val2, bh, binpos, bin_first, tid_first_bin, R.chunk_rec, r_line, L, n_lines, in.eofv, o);
-            k_tix_ser_contig<<<(unsigned)n_runs, 64, 0, st>>>(n_runs, R.run_rec, tid_first_bin, bin_first, r_line, L, n_lines, in.eofv, loff, lin, o);
+            rows.toff = toff; rows.shift = shift_d;
+            const BinIdxOut o{blob, n_blob, err_d, 1};
+            k_binidx_ser_chunks<<<XGRID(n_chunks), XT, 0, st>>>(rows, n_chunks, key2, val2, bh, binpos, bin_first, tid_first_bin, R.chunk_rec, o);
+            k_binidx_ser_group<<<(unsigned)n_runs, 64, 0, st>>>(rows, n_runs, tid_first_bin, bin_first, loff, lin, o);
             HIPCHK(hipGetLastError());
         }
     }

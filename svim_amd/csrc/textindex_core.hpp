@@ -1,25 +1,17 @@
-// textindex_core.hpp - what a tabix index says about one line of a VCF or BED text, and where the fields of the .tbi lie: one source for the kernels of
-// textindex.hip and for svx_text_index_host (textindex_host.cpp), as deflate_core.hpp is for the encoder.  The definition in words: svim_amd/tabix.py.
+// textindex_core.hpp - what a tabix index says about one line of a VCF or BED text: the line parser and the virtual offset of a text offset, one source for
+// the kernels of textindex.hip and for svx_text_index_host (textindex_host.cpp), as deflate_core.hpp is for the encoder.  The bins and the layout of a
+// contig's part: binidx_core.hpp.  The definition in words: svim_amd/tabix.py.
 #pragma once
-#include <cstdint>
-
-#ifdef __HIPCC__
-#define TIX_HD __host__ __device__ __forceinline__
-#else
-#define TIX_HD inline
-#endif
+#include "binidx_core.hpp"
 
 #define TIX_HEAD 65280                       /* bytes of a line that are parsed (one BGZF block of text) */
-#define TIX_MAX_END (1ll << 29)              /* what the five-level binning holds */
 #define TIX_NUM_CAP (1ll << 40)
-#define TIX_PSEUDO_BIN 37450u
-#define TIX_NO_SLOT 0xffffffffffffffffull
 #define TIX_HEADER_BYTES 36                  /* magic + eight int32, in front of the names */
 
 struct TixLine { int32_t skip, name_len; int64_t beg, end; };
 
 // leading decimal digits at p (none: 0), capped; *used = how many
-TIX_HD int64_t tix_num(const uint8_t* p, const uint8_t* e, int* used) {
+BINIDX_HD int64_t tix_num(const uint8_t* p, const uint8_t* e, int* used) {
     int64_t v = 0; int k = 0;
     while (p + k < e && p[k] >= '0' && p[k] <= '9') { v = v * 10 + (p[k] - '0'); if (v > TIX_NUM_CAP) v = TIX_NUM_CAP; k++; }
     if (used) *used = k;
@@ -27,7 +19,7 @@ TIX_HD int64_t tix_num(const uint8_t* p, const uint8_t* e, int* used) {
 }
 // one column: x at its first byte while `more` says the line has it (an absent column is empty) -> [*b, *e); x and more move on to the next one.
 // A column ends at a tab, at the line's newline or at lim
-TIX_HD void tix_col(const uint8_t*& x, const uint8_t* lim, bool& more, const uint8_t** b, const uint8_t** e) {
+BINIDX_HD void tix_col(const uint8_t*& x, const uint8_t* lim, bool& more, const uint8_t** b, const uint8_t** e) {
     if (!more) { *b = *e = lim; return; }
     *b = x;
     while (x < lim && *x != '\t' && *x != '\n') x++;
@@ -36,7 +28,7 @@ TIX_HD void tix_col(const uint8_t*& x, const uint8_t* lim, bool& more, const uin
     if (more) x++;
 }
 // the line text[s, e) (e: the next line's start, or the text's end); only its first TIX_HEAD bytes are read
-TIX_HD TixLine tix_parse_line(const uint8_t* text, int64_t s, int64_t e, int preset) {
+BINIDX_HD TixLine tix_parse_line(const uint8_t* text, int64_t s, int64_t e, int preset) {
     TixLine r; r.skip = 1; r.name_len = 0; r.beg = 0; r.end = 0;
     if (e <= s || text[s] == '#' || text[s] == '\n') return r;
     r.skip = 0;
@@ -70,25 +62,11 @@ TIX_HD TixLine tix_parse_line(const uint8_t* text, int64_t s, int64_t e, int pre
     if (r.end <= r.beg) r.end = r.beg + 1;
     return r;
 }
-TIX_HD uint32_t tix_reg2bin(int64_t beg, int64_t end) {
-    end--;
-    if (beg >> 14 == end >> 14) return (uint32_t)(4681 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t)(585 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t)(73 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t)(9 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t)(1 + (beg >> 26));
-    return 0u;
-}
 // virtual offset of text offset u: the last block of [b_lo, b_hi) that starts at or before u (uoff[b_lo] <= u is required); coff_base: where the file's
 // stream starts in coff's numbering, stream_base: what lies in front of it in the file
-TIX_HD uint64_t tix_voff(int64_t u, const int64_t* coff, const int64_t* uoff, int64_t b_lo, int64_t b_hi, int64_t coff_base, int64_t stream_base) {
+BINIDX_HD uint64_t tix_voff(int64_t u, const int64_t* coff, const int64_t* uoff, int64_t b_lo, int64_t b_hi, int64_t coff_base, int64_t stream_base) {
     int64_t lo = b_lo, hi = b_hi;                     // first block with uoff > u
     while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (uoff[mid] > u) hi = mid; else lo = mid + 1; }
     const int64_t b = lo - 1;
     return ((uint64_t)(stream_base + coff[b] - coff_base) << 16) | (uint64_t)(u - uoff[b]);
 }
-// little-endian stores at any alignment
-TIX_HD void tix_put32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-TIX_HD void tix_put64(uint8_t* p, uint64_t v) { tix_put32(p, (uint32_t)v); tix_put32(p + 4, (uint32_t)(v >> 32)); }
-// the bytes of one contig's part: n_bin, its bins with their chunks, the pseudo-bin, n_intv, the linear index
-TIX_HD int64_t tix_contig_bytes(int64_t n_bins, int64_t n_chunks, int64_t n_intv) { return 4 + 8 * n_bins + 16 * n_chunks + 40 + 4 + 8 * n_intv; }

@@ -1,17 +1,16 @@
-// textindex_host.cpp - svx_text_index_host: the tabix index of one file by the line parser, the binning and the layout of textindex_core.hpp, built for the
-// host; no GPU involved.  The kernels of textindex.hip write the same bytes for the same text and block table; here the runs, chunks and windows are
-// walked one record after the other, there they come from scans and a sort.
+// textindex_host.cpp - svx_text_index_host: the tabix index of one file by the line parser of textindex_core.hpp, built for the host; no GPU involved.  Lines,
+// records, contig runs, names and the header are made here; a contig's part is written by binidx_host.hpp.  The kernels of textindex.hip write the same
+// bytes for the same text and block table; here the runs, chunks and windows are walked one record after the other, there they come from scans and a sort.
 #include "textindex_core.hpp"
+#include "binidx_host.hpp"
 #include "../../include/svx.h"
-#include <algorithm>
 #include <cstring>
 #include <string>
 #include <unordered_set>
 #include <vector>
 
 namespace {
-struct Rec { int64_t at, beg, end; int32_t name_len; uint32_t bin; uint64_t vbeg, vend; };
-struct Chunk { uint64_t key, beg, end; };
+struct Rec { int64_t at, beg, end; int32_t name_len; uint64_t vbeg, vend; };
 }
 
 extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
@@ -34,7 +33,7 @@ extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t
         const int64_t s = starts[k], e = k + 1 < starts.size() ? starts[k + 1] : n;
         const TixLine L = tix_parse_line(text, s, e, preset);
         if (L.skip) continue;
-        Rec r; r.at = s; r.beg = L.beg; r.end = L.end; r.name_len = L.name_len; r.bin = L.end <= TIX_MAX_END ? tix_reg2bin(L.beg, L.end) : 0u;
+        Rec r; r.at = s; r.beg = L.beg; r.end = L.end; r.name_len = L.name_len;
         r.vbeg = tix_voff(s, block_coff, block_uoff, 0, n_blocks, 0, stream_base);
         r.vend = k + 1 < starts.size() ? tix_voff(e, block_coff, block_uoff, 0, n_blocks, 0, stream_base) : v_eof;
         recs.push_back(r);
@@ -50,7 +49,7 @@ extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t
             if (!seen.insert(std::string((const char*)text + r.at, (size_t)r.name_len)).second) bad_order = true;
             run_first.push_back(j);
         } else if (r.beg < recs[j - 1].beg) bad_order = true;
-        if (r.end > TIX_MAX_END) bad_range = true;
+        if (r.end > BINIDX_MAX_END) bad_range = true;
     }
     if (bad_order) return SVX_E_ORDER;
     if (bad_range) return SVX_E_RANGE;
@@ -65,38 +64,12 @@ extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t
     }
     memcpy(blob.data(), "TBI\1", 4);
     const uint32_t head[8] = {(uint32_t)n_ref, preset == SVX_INDEX_BED ? 0x10000u : 2u, 1u, 2u, preset == SVX_INDEX_BED ? 3u : 0u, (uint32_t)'#', 0u, (uint32_t)l_nm};
-    for (int k = 0; k < 8; k++) tix_put32(blob.data() + 4 + 4 * k, head[k]);
+    for (int k = 0; k < 8; k++) binidx_put32(blob.data() + 4 + 4 * k, head[k]);
     for (size_t t = 0; t < n_ref; t++) {
         const size_t lo = run_first[t], hi = run_first[t + 1];
-        std::vector<Chunk> chunks;
-        int64_t max_end = 0;
-        for (size_t j = lo; j < hi; j++) {
-            const Rec& r = recs[j];
-            if (j > lo && r.bin == recs[j - 1].bin) chunks.back().end = r.vend; else chunks.push_back(Chunk{r.bin, r.vbeg, r.vend});
-            max_end = std::max(max_end, r.end);
-        }
-        std::stable_sort(chunks.begin(), chunks.end(), [](const Chunk& a, const Chunk& b) { return a.key < b.key; });
-        int64_t n_bins = 0;
-        for (size_t k = 0; k < chunks.size(); k++) n_bins += k == 0 || chunks[k].key != chunks[k - 1].key;
-        const int64_t n_intv = 1 + ((max_end - 1) >> 14);
-        size_t at = blob.size();
-        blob.resize(at + (size_t)tix_contig_bytes(n_bins, (int64_t)chunks.size(), n_intv));
-        uint8_t* p = blob.data() + at;
-        tix_put32(p, (uint32_t)(n_bins + 1)); p += 4;
-        for (size_t k = 0; k < chunks.size();) {
-            size_t m = k;
-            while (m < chunks.size() && chunks[m].key == chunks[k].key) m++;
-            tix_put32(p, (uint32_t)chunks[k].key); tix_put32(p + 4, (uint32_t)(m - k)); p += 8;
-            for (; k < m; k++) { tix_put64(p, chunks[k].beg); tix_put64(p + 8, chunks[k].end); p += 16; }
-        }
-        tix_put32(p, TIX_PSEUDO_BIN); tix_put32(p + 4, 2u); tix_put64(p + 8, recs[lo].vbeg); tix_put64(p + 16, recs[hi - 1].vend);
-        tix_put64(p + 24, (uint64_t)(hi - lo)); tix_put64(p + 32, 0ull); p += 40;
-        tix_put32(p, (uint32_t)n_intv); p += 4;
-        std::vector<uint64_t> lin((size_t)n_intv, TIX_NO_SLOT);
-        for (size_t j = lo; j < hi; j++)
-            for (int64_t w = recs[j].beg >> 14; w <= (recs[j].end - 1) >> 14; w++) lin[(size_t)w] = std::min(lin[(size_t)w], recs[j].vbeg);
-        for (int64_t w = n_intv - 2; w >= 0; w--) if (lin[(size_t)w] == TIX_NO_SLOT) lin[(size_t)w] = lin[(size_t)w + 1];
-        for (int64_t w = 0; w < n_intv; w++) tix_put64(p + 8 * w, lin[(size_t)w]);
+        std::vector<BinIdxRow> rows;
+        for (size_t j = lo; j < hi; j++) rows.push_back(BinIdxRow{recs[j].beg, recs[j].end, recs[j].vbeg, recs[j].vend});
+        binidx_append_part(blob, rows.data(), rows.size(), (uint64_t)(hi - lo), 0ull);
     }
     blob.resize(blob.size() + 8, 0);
     *n_out = (int64_t)blob.size();

@@ -475,23 +475,17 @@ __global__ __launch_bounds__(VT) void k_vcf_payload(int n_tiles, const int64_t* 
 // host: state and the call
 // ---------------------------------------------------------------------------------------------------------
 struct VcfState {
-    DevBuf pool[VCF_NPOOL]; int used = 0;
+    ScratchPool<VCF_NPOOL> pool{"vcf"};
     DevBuf out, line_off;
     int64_t n_lines = 0, n_bytes = 0;
     bool have = false;
     hipEvent_t ev[8]; bool have_ev = false;
     svx_vcf_stats stats;
-    template <class Tp> int get(Tp** o, size_t count) {
-        if (used >= VCF_NPOOL) return svx_fail(SVX_E_CAPACITY, "vcf: scratch pool exhausted", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(pool[used].reserve((count ? count : 1) * sizeof(Tp) + 64));
-        *o = pool[used++].as<Tp>();
-        return SVX_OK;
-    }
 };
 void svx_vcf_release(svx_ctx* c) {
     VcfState* s = c->vcf;
     if (!s) return;
-    for (auto& b : s->pool) b.release();
+    s->pool.release();
     s->out.release(); s->line_off.release();
     if (s->have_ev) for (auto& e : s->ev) (void)hipEventDestroy(e);
     delete s;
@@ -499,14 +493,12 @@ void svx_vcf_release(svx_ctx* c) {
 }
 void svx_preload_vcf() { hipFuncAttributes a; (void)hipFuncGetAttributes(&a, reinterpret_cast<const void*>(&k_vcf_payload)); (void)hipGetLastError(); }
 
-static int ceil_log2(long long n) { int b = 0; while ((1ll << b) < n) b++; return b; }
-
 int svx_distinct_member_ids(svx_ctx* c, const MemberIds& m, int mode, const DistinctBufs& b, uint8_t* zbad) {
     const long long nm = m.n_members;
     hipStream_t st = c->stream;
     if (nm > 0) {
         k_vcf_member_keys<<<VGRID(nm), VT, 0, st>>>(m, mode, b.k0, b.v0);
-        SVXCHK(svx_sort_pairs_u64(c, b.k0, b.k1, b.v0, b.v1, nm, 0, std::min(64, 32 + std::max(1, ceil_log2(m.n_cand + 1)))));
+        SVXCHK(svx_sort_pairs_u64(c, b.k0, b.k1, b.v0, b.v1, nm, 0, std::min(64, 32 + std::max(1, svx_ceil_log2(m.n_cand + 1)))));
     }
     k_vcf_distinct_flags<<<VGRID(nm + 1), VT, 0, st>>>(nm, b.k1, mode, b.flag, zbad);
     SVXCHK(svx_exclusive_scan_i32_to_i64(c, b.flag, b.ex, nm + 1));
@@ -517,7 +509,7 @@ int svx_distinct_member_ids(svx_ctx* c, const MemberIds& m, int mode, const Dist
 static int distinct_ids(svx_ctx* c, VcfState* S, const VcfIn& in, int mode, int64_t** ex_out, uint8_t* zbad) {
     const long long nm = in.n_members;
     DistinctBufs b;
-    SVXCHK(S->get(&b.k0, nm)); SVXCHK(S->get(&b.k1, nm)); SVXCHK(S->get(&b.v0, nm)); SVXCHK(S->get(&b.v1, nm)); SVXCHK(S->get(&b.flag, nm + 1)); SVXCHK(S->get(&b.ex, nm + 1));
+    SVXCHK(S->pool.get(&b.k0, nm)); SVXCHK(S->pool.get(&b.k1, nm)); SVXCHK(S->pool.get(&b.v0, nm)); SVXCHK(S->pool.get(&b.v1, nm)); SVXCHK(S->pool.get(&b.flag, nm + 1)); SVXCHK(S->pool.get(&b.ex, nm + 1));
     *ex_out = b.ex;
     const MemberIds m{in.n_cand, nm, in.n_sig, in.n_reads, in.member_off, in.members, in.sig_read_id, in.zmw, in.err};
     return svx_distinct_member_ids(c, m, mode, b, zbad);
@@ -530,7 +522,7 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     if (!c->vcf) c->vcf = new VcfState();
     VcfState* S = c->vcf;
     if (!S->have_ev) { for (auto& e : S->ev) HIPCHK(hipEventCreate(&e)); S->have_ev = true; }
-    S->used = 0; S->have = false; S->n_lines = S->n_bytes = 0;
+    S->pool.reset(); S->have = false; S->n_lines = S->n_bytes = 0;
     c->vcf_calls++;                    // (a BGZF stream made of the text before is void from here on)
     memset(&S->stats, 0, sizeof S->stats);
     const svx_vcf_params P = *pp;
@@ -543,7 +535,7 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     in.P = P;
     int64_t class_count[SVX_NCAND];
     HostCopy hc(st);
-#define UP(field, type, host, count) do { type* d_; SVXCHK(S->get(&d_, (count))); if ((count)) SVXCHK(hc.h2d(d_, (host), (size_t)(count) * sizeof(type))); in.field = d_; } while (0)
+#define UP(field, type, host, count) do { type* d_; SVXCHK(S->pool.get(&d_, (count))); if ((count)) SVXCHK(hc.h2d(d_, (host), (size_t)(count) * sizeof(type))); in.field = d_; } while (0)
     if (source == 0) {
         CandDev cd;
         if (!svx_combine_resident(c, &cd)) return svx_fail(SVX_E_STATE, "svx_vcf: no resident candidates: run svx_combine first", __FILE__, __LINE__, hipSuccess);
@@ -590,7 +582,7 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
                             __FILE__, __LINE__, hipSuccess);
     } else {
         uint8_t* gt; int32_t *rr, *ar;
-        SVXCHK(S->get(&gt, (size_t)n)); SVXCHK(S->get(&rr, (size_t)n)); SVXCHK(S->get(&ar, (size_t)n));
+        SVXCHK(S->pool.get(&gt, (size_t)n)); SVXCHK(S->pool.get(&rr, (size_t)n)); SVXCHK(S->pool.get(&ar, (size_t)n));
         if (n) {
             if (ip->gt) SVXCHK(hc.h2d(gt, ip->gt, (size_t)n)); else HIPCHK(hipMemsetAsync(gt, 0, (size_t)n, st));
             if (ip->ref_reads) SVXCHK(hc.h2d(rr, ip->ref_reads, (size_t)n * 4)); else HIPCHK(hipMemsetAsync(rr, 0xff, (size_t)n * 4, st));
@@ -629,7 +621,7 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     SVXCHK(hc.finish());
 #undef UP
     in.g_off = c->g_off_p; in.g_codes = c->g_codes_p; in.g_n = P.sequence_alleles ? c->g_n : 0;
-    { int* err; unsigned long long* cnt; SVXCHK(S->get(&err, 2)); SVXCHK(S->get(&cnt, 8)); HIPCHK(hipMemsetAsync(err, 0, 8, st)); HIPCHK(hipMemsetAsync(cnt, 0, 64, st)); in.err = err; in.counters = cnt; }
+    { int* err; unsigned long long* cnt; SVXCHK(S->pool.get(&err, 2)); SVXCHK(S->pool.get(&cnt, 8)); HIPCHK(hipMemsetAsync(err, 0, 8, st)); HIPCHK(hipMemsetAsync(cnt, 0, 64, st)); in.err = err; in.counters = cnt; }
     HIPCHK(hipEventRecord(S->ev[1], st));
 
     // ---- 1: the six append slots (SVIM_COMBINE.py:145-173) over the class-grouped table ----
@@ -665,14 +657,14 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     }
     const long long ne = n_lines;
     uint32_t *ent_cand, *idx, *v1, *order, *v3; uint8_t* ent_form; uint64_t *key_end, *key_end2, *key_cs, *key_cs_g, *key_cs2, *lab, *lab2; int64_t* kidx;
-    SVXCHK(S->get(&ent_cand, ne)); SVXCHK(S->get(&idx, ne)); SVXCHK(S->get(&v1, ne)); SVXCHK(S->get(&order, ne)); SVXCHK(S->get(&v3, ne)); SVXCHK(S->get(&ent_form, ne));
-    SVXCHK(S->get(&key_end, ne)); SVXCHK(S->get(&key_end2, ne)); SVXCHK(S->get(&key_cs, ne)); SVXCHK(S->get(&key_cs_g, ne)); SVXCHK(S->get(&key_cs2, ne));
-    SVXCHK(S->get(&lab, ne)); SVXCHK(S->get(&lab2, ne)); SVXCHK(S->get(&kidx, ne));
+    SVXCHK(S->pool.get(&ent_cand, ne)); SVXCHK(S->pool.get(&idx, ne)); SVXCHK(S->pool.get(&v1, ne)); SVXCHK(S->pool.get(&order, ne)); SVXCHK(S->pool.get(&v3, ne)); SVXCHK(S->pool.get(&ent_form, ne));
+    SVXCHK(S->pool.get(&key_end, ne)); SVXCHK(S->pool.get(&key_end2, ne)); SVXCHK(S->pool.get(&key_cs, ne)); SVXCHK(S->pool.get(&key_cs_g, ne)); SVXCHK(S->pool.get(&key_cs2, ne));
+    SVXCHK(S->pool.get(&lab, ne)); SVXCHK(S->pool.get(&lab2, ne)); SVXCHK(S->pool.get(&kidx, ne));
     k_vcf_entries<<<VGRID(ne), VT, 0, st>>>(ne, sl, in, ent_cand, ent_form, key_end, key_cs, idx);
     // ---- 2: stable sort by (rank, start, end); running index per label ----
     SVXCHK(svx_sort_pairs_u64(c, key_end, key_end2, idx, v1, ne, 0, 64));
     k_vcf_gather_u64<<<VGRID(ne), VT, 0, st>>>(key_cs, v1, key_cs_g, ne);
-    SVXCHK(svx_sort_pairs_u64(c, key_cs_g, key_cs2, v1, order, ne, 0, std::min(64, 32 + std::max(1, ceil_log2((long long)ip->n_contig + 1)))));
+    SVXCHK(svx_sort_pairs_u64(c, key_cs_g, key_cs2, v1, order, ne, 0, std::min(64, 32 + std::max(1, svx_ceil_log2((long long)ip->n_contig + 1)))));
     k_vcf_label_keys<<<VGRID(ne), VT, 0, st>>>(ne, order, ent_form, lab, idx);
     SVXCHK(svx_sort_pairs_u64(c, lab, lab2, idx, v3, ne, 0, 3));
     LabelBase lb; { long long b = 0; for (int k = 0; k < SVX_VCF_NLABEL; k++) { lb.b[k] = b; b += per_label[k]; } }
@@ -680,9 +672,9 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     if (c->vcf_position_order) {
         // the ids are given; one more stable pass by (contig, POS) - lines that tie keep the reference's order
         uint64_t *pk, *pk2; uint32_t *pv, *perm, *order2; int64_t* kidx2;
-        SVXCHK(S->get(&pk, ne)); SVXCHK(S->get(&pk2, ne)); SVXCHK(S->get(&pv, ne)); SVXCHK(S->get(&perm, ne)); SVXCHK(S->get(&order2, ne)); SVXCHK(S->get(&kidx2, ne));
+        SVXCHK(S->pool.get(&pk, ne)); SVXCHK(S->pool.get(&pk2, ne)); SVXCHK(S->pool.get(&pv, ne)); SVXCHK(S->pool.get(&perm, ne)); SVXCHK(S->pool.get(&order2, ne)); SVXCHK(S->pool.get(&kidx2, ne));
         k_vcf_pos_keys<<<VGRID(ne), VT, 0, st>>>(ne, order, ent_cand, ent_form, in, pk, pv);
-        SVXCHK(svx_sort_pairs_u64(c, pk, pk2, pv, perm, ne, 0, std::min(64, 32 + std::max(1, ceil_log2((long long)ip->n_contig + 1)))));
+        SVXCHK(svx_sort_pairs_u64(c, pk, pk2, pv, perm, ne, 0, std::min(64, 32 + std::max(1, svx_ceil_log2((long long)ip->n_contig + 1)))));
         k_vcf_permute_lines<<<VGRID(ne), VT, 0, st>>>(ne, perm, order, kidx, order2, kidx2);
         order = order2; kidx = kidx2;
     }
@@ -691,7 +683,7 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     // ---- 3: distinct reads / zmws per candidate ----
     {
         int64_t* ex; uint8_t* zbad;
-        SVXCHK(S->get(&zbad, (size_t)n + 1));
+        SVXCHK(S->pool.get(&zbad, (size_t)n + 1));
         HIPCHK(hipMemsetAsync(zbad, 0, (size_t)n + 1, st));
         SVXCHK(distinct_ids(c, S, in, 0, &ex, zbad)); in.sup_ex = ex;
         if (P.zmws) { SVXCHK(distinct_ids(c, S, in, 1, &ex, zbad)); in.zmw_ex = ex; }
@@ -702,14 +694,14 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
     for (int mode = 0; mode < 2; mode++) {
         if (!(mode == 0 ? P.insertion_sequences : P.read_names)) continue;
         int32_t* len; int64_t* pre;
-        SVXCHK(S->get(&len, nm + 1)); SVXCHK(S->get(&pre, nm + 1));
+        SVXCHK(S->pool.get(&len, nm + 1)); SVXCHK(S->pool.get(&pre, nm + 1));
         k_vcf_member_len<<<VGRID(nm + 1), VT, 0, st>>>(in, mode, len);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, len, pre, nm + 1));
         if (mode == 0) in.pseq = pre; else in.pread = pre;
     }
     const long long n_seg = ne * VCF_NSEG;
     int64_t *line_len, *tiles, *tile_start;
-    SVXCHK(S->get(&line_len, ne + 1)); SVXCHK(S->get(&tiles, n_seg + 1)); SVXCHK(S->get(&tile_start, n_seg + 1));
+    SVXCHK(S->pool.get(&line_len, ne + 1)); SVXCHK(S->pool.get(&tiles, n_seg + 1)); SVXCHK(S->pool.get(&tile_start, n_seg + 1));
     k_vcf_lengths<<<VGRID(ne + 1), VT, 0, st>>>(ne, order, ent_cand, ent_form, kidx, in, line_len, tiles);
     SVXCHK(svx_exclusive_scan_i64(c, line_len, line_off, ne + 1));
     SVXCHK(svx_exclusive_scan_i64(c, tiles, tile_start, n_seg + 1));
@@ -744,7 +736,7 @@ extern "C" int svx_vcf(svx_ctx* c, int source, const svx_candidate_view* cv, con
         }
     }
     uint8_t* out = S->out.as<uint8_t>();
-    SegDesc* segs; SVXCHK(S->get(&segs, (size_t)n_seg));
+    SegDesc* segs; SVXCHK(S->pool.get(&segs, (size_t)n_seg));
     // ---- 5: skeleton, payload ----
     k_vcf_skeleton<<<VGRID(ne), VT, 0, st>>>(ne, order, ent_cand, ent_form, kidx, in, line_off, out, segs);
     HIPCHK(hipEventRecord(S->ev[5], st));

@@ -128,6 +128,34 @@ def check_order(recs):
     return status
 
 
+def contig_part(rows, n_mapped, n_unmapped):
+    """the bytes of the part of one contig (of one reference in a .bai: bai.py) from its rows (beg, end, vbeg, vend), in file order and at least one: n_bin,
+    the bins ascending with their chunks, the pseudo-bin with the two counts, n_intv, the linear index"""
+    bins, prev_bin = {}, None
+    for beg, end, vbeg, vend in rows:
+        b = reg2bin(beg, end)
+        if b == prev_bin:
+            bins[b][-1][1] = vend
+        else:
+            bins.setdefault(b, []).append([vbeg, vend])
+        prev_bin = b
+    out = [struct.pack("<i", len(bins) + 1)]
+    for b in sorted(bins):
+        out.append(struct.pack("<Ii", b, len(bins[b])) + b"".join(struct.pack("<QQ", *c) for c in bins[b]))
+    out.append(struct.pack("<IiQQQQ", PSEUDO_BIN, 2, rows[0][2], rows[-1][3], n_mapped, n_unmapped))
+    n_intv = 1 + max((r[1] - 1) >> 14 for r in rows)
+    lin = [None] * n_intv
+    for beg, end, vbeg, _ in rows:
+        for w in range(beg >> 14, ((end - 1) >> 14) + 1):
+            if lin[w] is None or vbeg < lin[w]:
+                lin[w] = vbeg
+    for w in range(n_intv - 2, -1, -1):
+        if lin[w] is None:
+            lin[w] = lin[w + 1]
+    out.append(struct.pack("<i%dQ" % n_intv, n_intv, *lin))
+    return b"".join(out)
+
+
 def build_index(text, block_coff, block_uoff, preset, stream_base=0):
     """the uncompressed .tbi bytes of `text` (bytes) whose BGZF stream has the block table block_coff / block_uoff (n_blocks + 1 entries each, the last block
     the end-of-file block: Engine.text_gz_tables, or block_table of the stream) and lies stream_base bytes into its file.  TabixError when it has none."""
@@ -143,30 +171,34 @@ def build_index(text, block_coff, block_uoff, preset, stream_base=0):
     names = b"".join(c[0] + b"\0" for c in contigs)
     out = [b"TBI\1", struct.pack("<8i", len(contigs), *_FORMAT[preset], ord("#"), 0, len(names)), names]
     for _, rs in contigs:
-        bins, prev_bin = {}, None
-        for _, beg, end, vbeg, vend, _ in rs:
-            b = reg2bin(beg, end)
-            if b == prev_bin:
-                bins[b][-1][1] = vend
-            else:
-                bins.setdefault(b, []).append([vbeg, vend])
-            prev_bin = b
-        out.append(struct.pack("<i", len(bins) + 1))
-        for b in sorted(bins):
-            out.append(struct.pack("<Ii", b, len(bins[b])) + b"".join(struct.pack("<QQ", *c) for c in bins[b]))
-        out.append(struct.pack("<IiQQQQ", PSEUDO_BIN, 2, rs[0][3], rs[-1][4], len(rs), 0))
-        n_intv = 1 + max((r[2] - 1) >> 14 for r in rs)
-        lin = [None] * n_intv
-        for _, beg, end, vbeg, _, _ in rs:
-            for w in range(beg >> 14, ((end - 1) >> 14) + 1):
-                if lin[w] is None or vbeg < lin[w]:
-                    lin[w] = vbeg
-        for w in range(n_intv - 2, -1, -1):
-            if lin[w] is None:
-                lin[w] = lin[w + 1]
-        out.append(struct.pack("<i%dQ" % n_intv, n_intv, *lin))
+        out.append(contig_part([r[1:5] for r in rs], len(rs), 0))
     out.append(struct.pack("<Q", 0))
     return b"".join(out)
+
+
+def parse_part(data, at, what, may_be_empty=False):
+    """the part of one contig (of one reference in a .bai) at data[at:] -> ({bin: [(beg, end)]}, the pairs of bin 37450, linear list, offset behind the part).
+    may_be_empty: the .bai rule - a part without bins has no pseudo-bin (None), every other has one of two pairs.  ValueError with `what` in front"""
+    n_bin, = struct.unpack_from("<i", data, at)
+    at += 4
+    d, order, ps = {}, [], None
+    for _ in range(n_bin):
+        b, n_chunk = struct.unpack_from("<Ii", data, at)
+        at += 8
+        chunks = [struct.unpack_from("<QQ", data, at + 16 * k) for k in range(n_chunk)]
+        at += 16 * n_chunk
+        if b == PSEUDO_BIN:
+            ps = chunks
+        else:
+            d[b] = chunks
+        order.append(b)
+    bad_pseudo = ((ps is None) != (n_bin == 0) or (ps is not None and len(ps) != 2)) if may_be_empty else ps is None
+    if order != sorted(order) or len(set(order)) != len(order) or bad_pseudo:
+        raise ValueError("%s: bins not ascending, or no pseudo-bin" % what)
+    n_intv, = struct.unpack_from("<i", data, at)
+    at += 4
+    lin = list(struct.unpack_from("<%dQ" % n_intv, data, at))
+    return d, ps, lin, at + 8 * n_intv
 
 
 def parse_index(data):
@@ -183,26 +215,8 @@ def parse_index(data):
     at += l_nm
     bins, pseudo, linear = [], [], []
     for _ in range(n_ref):
-        n_bin, = struct.unpack_from("<i", data, at)
-        at += 4
-        d, order, ps = {}, [], None
-        for _ in range(n_bin):
-            b, n_chunk = struct.unpack_from("<Ii", data, at)
-            at += 8
-            chunks = [struct.unpack_from("<QQ", data, at + 16 * k) for k in range(n_chunk)]
-            at += 16 * n_chunk
-            if b == PSEUDO_BIN:
-                ps = chunks
-            else:
-                d[b] = chunks
-            order.append(b)
-        if order != sorted(order) or len(set(order)) != len(order) or ps is None:
-            raise ValueError("tabix index: bins not ascending, or no pseudo-bin")
-        n_intv, = struct.unpack_from("<i", data, at)
-        at += 4
-        linear.append(list(struct.unpack_from("<%dQ" % n_intv, data, at)))
-        at += 8 * n_intv
-        bins.append(d), pseudo.append(ps)
+        d, ps, lin, at = parse_part(data, at, "tabix index")
+        bins.append(d), pseudo.append(ps), linear.append(lin)
     n_no_coor, = struct.unpack_from("<Q", data, at)
     if at + 8 != len(data):
         raise ValueError("tabix index: %d bytes behind the trailer" % (len(data) - at - 8))

@@ -5,7 +5,7 @@ tests/test_gpu_bam_index.py the device build on the GPU.
     block layout  a record that starts exactly at a block start; records that straddle two and three blocks; empty blocks in the middle (at a record start
                   and inside a record); pieces that were concatenated (an end-of-file marker between them, another compression behind it); stored and
                   fixed-Huffman blocks; no end-of-file block
-    references    without records at the start, in the middle and at the end of the header
+    references    without records at the start, in the middle and at the end of the header; 600 of them with three records (more references than chunks)
     records       secondary, supplementary, duplicate, mapping quality 0, placed but unmapped, reference length 0; intervals that end at and cross 2^14, 2^17,
                   2^20, 2^23 and 2^26, one that covers a thousand windows; a CG-tag CIGAR of more than 65 535 operations; unplaced records at the tail
     files         unplaced records only; no record at all; one record; 150 000 short records (large_file: beyond the table's first capacity, the scans' tile
@@ -197,6 +197,14 @@ def large_file(path, n=150000, n_unplaced=500, seed=31):
             fh.write(FB.bgzf_block(raw[lo:lo + 0xff00], 1, zlib.Z_DEFAULT_STRATEGY))
         fh.write(FB.EOF_BLOCK)
     return m
+
+
+def many_references_file(dirpath, n_ref=600):
+    """three records in a header of 600 references: more references than chunks, by more than one block of lanes of the kernel that serves both -> (name, path)"""
+    path = os.path.join(dirpath, "many_references_few_records.bam")
+    recs = [seg("a", 0, 10, [(0, 50)]), seg("b", n_ref // 2, 70000, [(0, 50)]), seg("c", n_ref - 1, 5, [(0, 20000)])]
+    write_file(path, ["r%d" % k for k in range(n_ref)], [100000] * n_ref, record_bytes(recs), 0xff00)
+    return "many_references_few_records", path
 
 
 def swapped_file(path):

@@ -20,7 +20,7 @@ def corner(tmp_path_factory):
     """every corner file with its rows, the definition's bytes and the host build's, computed once"""
     d = str(tmp_path_factory.mktemp("bai_cases_gpu"))
     out = {}
-    for name, path in BC.build_all(d):
+    for name, path in BC.build_all(d) + [BC.many_references_file(d)]:
         n_ref, rows, v_end = bai.rows_of_bam(path)
         want = bai.build_index(n_ref, rows, v_end)
         assert _lib.bam_index_host(n_ref, rows, v_end) == want, name

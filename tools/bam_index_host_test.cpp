@@ -62,7 +62,7 @@ static bool walk(const std::vector<uint8_t>& b, const Table& t) {
             if ((k && bin <= prev) || n_chunk == 0) return false;
             prev = bin; at += 8 + 16 * (size_t)n_chunk;
         }
-        if ((n_bin && prev != TIX_PSEUDO_BIN) || at + 4 > b.size()) return false;
+        if ((n_bin && prev != BINIDX_PSEUDO_BIN) || at + 4 > b.size()) return false;
         const size_t n_intv = u32(at);
         if ((n_bin == 0) != (n_intv == 0)) return false;
         at += 4 + 8 * n_intv;

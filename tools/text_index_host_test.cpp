@@ -61,7 +61,7 @@ static bool walk(const std::vector<uint8_t>& b) {
             if ((k && bin <= prev) || n_chunk == 0) return false;
             prev = bin; at += 8 + 16 * (size_t)n_chunk;
         }
-        if (prev != TIX_PSEUDO_BIN || at + 4 > b.size()) return false;
+        if (prev != BINIDX_PSEUDO_BIN || at + 4 > b.size()) return false;
         at += 4 + 8 * (size_t)u32(at);
     }
     return at + 8 == b.size();
