@@ -29,8 +29,11 @@ class AlignmentIndex(object):
                 continue                                    # records without a position are never returned by a region fetch
             tid.append(a.reference_id)
             pos.append(a.reference_start)
+            # end = pos + reference span, as the resident table has it (csrc/alnindex.hip): pos itself for an unmapped-but-placed record and for a mapped record
+            # without reference span (30S), for which reference_end is bam_endpos = pos + 1; the join derives bam_endpos from the two columns where it needs it
             re = a.reference_end
-            end.append(re if re is not None else a.reference_start)
+            spans = re is not None and any(l and op in (0, 2, 3, 7, 8) for op, l in a.cigartuples)
+            end.append(re if spans else a.reference_start)
             flag.append(a.flag)
             mapq.append(a.mapping_quality)
             name.append(self.name_ids.setdefault(a.query_name, len(self.name_ids)))

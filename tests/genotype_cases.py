@@ -1,5 +1,6 @@
 """Shared by the GENOTYPE table-route tests: the golden's hand-made candidates as a candidate table (svx_candidate_view) plus the read ids of the signatures its
-members index, the table route stated in Python over an interval join (the C oracle's or the HIP one's), and the object route the results are compared with."""
+members index, the table route stated in Python over an interval join (the C oracle's or the HIP one's), the object route the results are compared with, and
+the check of the resident alignment table against AlignmentIndex."""
 import numpy as np
 
 from svim_amd import SVIM_genotyping, _abi
@@ -96,3 +97,18 @@ def columns_as_fields(g):
     for gt, rr, ar, sf in zip(g["gt"].tolist(), g["ref_reads"].tolist(), g["alt_reads"].tolist(), g["support_fraction"].tolist()):
         out.append([".", "./.", None, None] if rr < 0 else ["." if sf != sf else sf, _abi.GT_NAMES[gt], rr, ar])
     return out
+
+
+def check_table_against_index(eng, pipe, index):
+    """the resident table = AlignmentIndex of the same records, column by column; names up to the id relabelling; end only where it is defined"""
+    a, names = eng.alignments(), pipe.bam.read_names()
+    keep = np.flatnonzero(a["tid"] >= 0)                    # (AlignmentIndex leaves records without a position out; the table keeps them, behind the contigs)
+    assert keep.size == index.n and (keep == np.arange(keep.size)).all()
+    for col, exp in (("pos", index.pos), ("flag", index.flag), ("mapq", index.mapq)):
+        assert (a[col][keep] == exp).all(), col
+    assert (np.searchsorted(a["tid"][keep], np.arange(index.n_contig + 1)) == index.contig_first).all()
+    counts = (a["flag"][keep] & (4 | 256)) == 0
+    assert (a["end"][keep][counts] == index.end[counts]).all() and (a["end"][keep][~counts] == a["pos"][keep][~counts]).all()
+    by_id = {v: k for k, v in index.name_ids.items()}
+    assert [names[r] for r in a["read_id"][keep].tolist()] == [by_id[i] for i in index.name_id.tolist()]
+    return a, names

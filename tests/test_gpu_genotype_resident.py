@@ -42,21 +42,6 @@ def _collect_file(eng, path, o, batch_records, device_decode=True, keep=True):
     return pipe, n
 
 
-def _check_table_against_index(eng, pipe, index):
-    """the resident table = AlignmentIndex of the same records, column by column; names up to the id relabelling; end only where it is defined"""
-    a, names = eng.alignments(), pipe.bam.read_names()
-    keep = np.flatnonzero(a["tid"] >= 0)                    # (AlignmentIndex leaves records without a position out; the table keeps them, behind the contigs)
-    assert keep.size == index.n and (keep == np.arange(keep.size)).all()
-    for col, exp in (("pos", index.pos), ("flag", index.flag), ("mapq", index.mapq)):
-        assert (a[col][keep] == exp).all(), col
-    assert (np.searchsorted(a["tid"][keep], np.arange(index.n_contig + 1)) == index.contig_first).all()
-    counts = (a["flag"][keep] & (4 | 256)) == 0
-    assert (a["end"][keep][counts] == index.end[counts]).all() and (a["end"][keep][~counts] == a["pos"][keep][~counts]).all()
-    by_id = {v: k for k, v in index.name_ids.items()}
-    assert [names[r] for r in a["read_id"][keep].tolist()] == [by_id[i] for i in index.name_id.tolist()]
-    return a, names
-
-
 def test_golden_rows_from_a_bam_file_in_small_batches(eng, tmp_path):
     g = H.load("g_genotype.json.gz")
     recs = _rows_as_records(g["references"], g["lengths"], g["rows"])
@@ -67,7 +52,7 @@ def test_golden_rows_from_a_bam_file_in_small_batches(eng, tmp_path):
     try:
         assert n == len(recs) and pipe.stats["batches"] >= len(recs) // 150
         index = SVIM_genotyping.AlignmentIndex(records.AlignmentFile(text=synth.genotype_sam_text(g["references"], g["lengths"], g["rows"])))
-        _, names = _check_table_against_index(eng, pipe, index)
+        _, names = GC.check_table_against_index(eng, pipe, index)
         ids = {nm: k for k, nm in enumerate(names)}
         cands = GC.golden_candidates(g)
         t, rid, row_of = GC.table_from_candidates(cands, g["references"], lambda nm: ids.setdefault(nm, len(ids)))
