@@ -142,12 +142,36 @@ def _apply_edits(lists6, n_ins, stages, signatures, references, with_deletions=T
             del insr[k]
 
 
+def _tandem_without_span(tan):
+    """a tandem duplication cluster with source_end == source_start: the reference divides by its span (src/svim/SVIM_COMBINE.py:349)"""
+    if isinstance(tan, ClusterList) and tan.untouched():
+        return bool((tan.ct.start[tan.lo:tan.hi] == tan.ct.end[tan.lo:tan.hi]).any())
+    return any(c.source_end == c.source_start for c in tan)
+
+
+def _zero_spans_meet(ct, merged):
+    """a deletion cluster and an insertion-from cluster (CLUSTER's or one stage 2 merged) that both have no span: the reference divides by the larger of the
+    two spans (src/svim/SVIM_clustering.py:106); k_cutpaste_min leaves such a pair out of the minimum"""
+    bounds = np.concatenate(([0], np.cumsum(np.asarray(list(ct.type_count), dtype=np.int64))))
+
+    def spanless(t):
+        lo, hi = int(bounds[t]), int(bounds[t + 1])
+        return bool((ct.start[lo:hi] == ct.end[lo:hi]).any())
+    return spanless(SVX_DEL) and (spanless(SVX_DUP_INT) or bool((merged.start[:merged.n] == merged.end[:merged.n]).any()))
+
+
 def combine_clusters(signature_clusters, options, engine=None):
     """src/svim/SVIM_COMBINE.py:332-478 on the device -> (deletion, inversion, interspersed duplication, tandem duplication, novel insertion, breakend
-    candidates) as lazy CandidateLists.  IndexError when there are insertion-from clusters but no deletion cluster, as in the reference."""
+    candidates) as lazy CandidateLists.  IndexError when there are insertion-from clusters but no deletion cluster, as in the reference; ZeroDivisionError
+    where the reference divides by zero: a tandem duplication cluster without source span (the lists stay as they are), and a deletion cluster and an
+    insertion-from cluster that both have no span (the breakend and the insertion-from lists are extended by then, no insertion cluster is deleted).
+    OverflowError (not the reference's: Python integers have no width) where a merged cluster's destination end `ins_start + distance` lies beyond 2^31 - 1,
+    which the table's int32 columns cannot hold; the lists stay as they are."""
     lists6 = tuple(signature_clusters)
     if len(lists6) != 6:
         raise ValueError("combine_clusters expects the 6-tuple cluster_sv_signatures returns")
+    if _tandem_without_span(lists6[3]):
+        raise ZeroDivisionError("division by zero")
     if not getattr(options, "skip_consensus", True) and not _CONSENSUS_NOTE[0]:
         _CONSENSUS_NOTE[0] = True
         logging.warning("svim_amd: insertion consensus sequences are not computed on the device path; continuing as with --skip_consensus")
@@ -155,7 +179,7 @@ def combine_clusters(signature_clusters, options, engine=None):
     cp = _abi.CombineParams.from_options(options)
     n_ins = len(lists6[1])
     if _resident(lists6, eng):
-        signatures, references = lists6[0].signatures, lists6[0].references
+        signatures, references, ct = lists6[0].signatures, lists6[0].references, eng._resident_ct
         run = lambda: eng.combine(cp, batch.contig_ranks(references))                              # noqa: E731
     else:
         ct, references, signatures, aux = cluster_table_from_lists(lists6) if not _same_table(lists6) else _table_of(lists6)
@@ -166,7 +190,14 @@ def combine_clusters(signature_clusters, options, engine=None):
     except _lib.NoDeletionClusters:
         _apply_edits(lists6, n_ins, eng.combine_stages(), signatures, references, with_deletions=False)
         raise IndexError("list index out of range")
-    _apply_edits(lists6, n_ins, eng.combine_stages(), signatures, references)
+    stages = eng.combine_stages()
+    merged = stages["merged"]
+    if bool((merged.end2[:merged.n] < merged.start2[:merged.n]).any()):      # ins_start + distance >= 0 in the reference: a wrapped int32
+        raise OverflowError("a merged insertion-from cluster ends beyond 2^31 - 1: the candidate table cannot hold it")
+    if _zero_spans_meet(ct, stages["merged"]):
+        _apply_edits(lists6, n_ins, stages, signatures, references, with_deletions=False)
+        raise ZeroDivisionError("division by zero")
+    _apply_edits(lists6, n_ins, stages, signatures, references)
     logging.info("Cluster interspersed duplication candidates one more time..")
     return convert.candidate_lists(table, signatures, references)
 

@@ -22,11 +22,14 @@ def merge_translocations_at_insertions(translocation_signature_clusters, inserti
 
 
 def flag_cutpaste_candidates(insertion_from_signature_clusters, deletion_signature_clusters, options, engine=None):
-    """src/svim/SVIM_merging.py:12-29 -> CandidateDuplicationInterspersed objects, cutpaste set where a deletion cluster is close"""
+    """src/svim/SVIM_merging.py:12-29 -> CandidateDuplicationInterspersed objects, cutpaste set where a deletion cluster is close.  IndexError without a
+    deletion cluster and ZeroDivisionError where a deletion cluster and an insertion-from cluster both have no span, as in the reference."""
     if len(insertion_from_signature_clusters) == 0:
         return []
     if len(deletion_signature_clusters) == 0:
         raise IndexError("list index out of range")
+    if any(d.end == d.start for d in deletion_signature_clusters) and any(c.source_end == c.source_start for c in insertion_from_signature_clusters):
+        raise ZeroDivisionError("division by zero")
     eng = engine if engine is not None else _lib.engine()
     ct, names, sigs, aux = cluster_table_from_lists((deletion_signature_clusters, [], [], [], insertion_from_signature_clusters, []))
     eng.combine(_abi.CombineParams.from_options(options), batch.contig_ranks(names), table=ct, sig_aux=aux, fetch=False)

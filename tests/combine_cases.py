@@ -1,5 +1,5 @@
-"""Shared by tests/test_combine.py and tests/test_gpu_combine.py: the cases of tests/golden/g_combine_cases.json.gz as svim_amd cluster objects, and
-candidate objects as the rows the goldens hold."""
+"""Shared by tests/test_combine.py, tests/test_gpu_combine.py and the two modules of the threshold cases: the cases of tests/golden/g_combine_cases.json.gz and
+g_combine_threshold_cases.json.gz as svim_amd cluster objects, candidate objects as the rows the goldens hold, and the stage tables of the device against them."""
 from svim_amd.signatures import SignatureClusterBiLocal, SignatureClusterUniLocal
 
 TYPES = ("DEL", "INS", "INV", "DUP_TAN", "DUP_INT", "BND")
@@ -41,3 +41,21 @@ def cand_row(c, idx):
 def merged_rows(clusters, idx):
     return [[c.source_contig, c.source_start, c.source_end, c.dest_contig, c.dest_start, c.dest_end, c.score, c.size, [idx[id(m)] for m in c.members], c.type,
              c.std_span, c.std_pos] for c in clusters]
+
+
+def check_stages(eng, exp, sigs, references, idx, what=None):
+    """the stage tables of the engine's last combine() against the golden's intermediates, ROW FOR ROW: the merged clusters, stage 2's removal list, the flagged
+    candidates and - where the golden holds it - the walk's removal list"""
+    import helpers as H
+    from svim_amd import SVIM_COMBINE, convert
+    st = eng.combine_stages()
+    merged = merged_rows(SVIM_COMBINE.merged_cluster_objects(st["merged"], sigs, references), idx)
+    d = H.first_json_difference(merged, exp["merged_insertion_from_clusters"])
+    assert d is None, (what, d)
+    assert st["remove_1"].tolist() == exp["inserted_regions_to_remove"], what
+    flagged = [cand_row(c, idx) for c in convert.candidate_objects_range(st["flagged"], 0, st["flagged"].n, sigs, references)]
+    d = H.first_json_difference(flagged, exp["flag_cutpaste"])
+    assert d is None, (what, d)
+    if "inserted_regions_to_remove_2" in exp:
+        assert st["remove_2"].tolist() == exp["inserted_regions_to_remove_2"], what
+    return st

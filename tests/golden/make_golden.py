@@ -17,7 +17,7 @@ outputs for them.  No reference source is copied.
 Goldens written by the generators beside this one (they import this module for the stubs):
 g_bed_cases (make_golden_bed.py), g_combine_cases (make_golden_combine.py), g_segments_cases
 (make_golden_segments.py), g_vcf_cases (make_golden_vcf.py), g_hap_cases (make_golden_hap.py), g_cluster_cases (make_golden_cluster.py),
-g_genotype_cases (make_golden_genotype.py).
+g_genotype_cases (make_golden_genotype.py), g_combine_threshold_cases (make_golden_combine_thresholds.py).
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 """

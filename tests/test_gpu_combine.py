@@ -25,18 +25,6 @@ def _expected_state(lists6, exp):
     assert len(bnd) == exp.get("n_bnd_after", exp.get("n_bnd_after_merge"))
 
 
-def _check_stages(eng, exp, sigs, references, idx):
-    from svim_amd import SVIM_COMBINE, convert
-    st = eng.combine_stages()
-    merged = CC.merged_rows(SVIM_COMBINE.merged_cluster_objects(st["merged"], sigs, references), idx)
-    assert H.first_json_difference(merged, exp["merged_insertion_from_clusters"]) is None, H.first_json_difference(merged, exp["merged_insertion_from_clusters"])
-    assert st["remove_1"].tolist() == exp["inserted_regions_to_remove"]
-    flagged = [CC.cand_row(c, idx) for c in convert.candidate_objects_range(st["flagged"], 0, st["flagged"].n, sigs, references)]
-    d = H.first_json_difference(flagged, exp["flag_cutpaste"])
-    assert d is None, d
-    return st
-
-
 def test_golden_through_cluster_and_combine(eng):
     """g_combine.json.gz: signatures -> cluster_sv_signatures -> combine_clusters, both on the device, nothing materialised on the resident route"""
     import svim_amd
@@ -54,7 +42,7 @@ def test_golden_through_cluster_and_combine(eng):
     got = [[CC.cand_row(c, idx) for c in lst] for lst in out]
     d = H.first_json_difference(got, exp["combine"])
     assert d is None, d
-    st = _check_stages(eng, exp, sigs, clusters[0].references, idx)
+    st = CC.check_stages(eng, exp, sigs, clusters[0].references, idx)
     assert sorted(set(st["remove_1"].tolist()) | set(st["remove_2"].tolist())) and exp["n_ins_before"] - exp["n_ins_after"] == len(set(st["remove_1"].tolist()) | set(st["remove_2"].tolist()))
     # the resident cluster tables are only read
     assert before.first_difference(eng.fetch_clusters()) is None
