@@ -40,6 +40,7 @@ extern "C" {
 #define SVX_E_FASTA_HOST   (-7)   /* svx_genome_load_fasta: a file the device loader leaves to the caller's host parser (svx_fasta_stats.host_reason says why) */
 #define SVX_E_ORDER        (-9)   /* svx_text_index: records of a contig not contiguous, or positions decreasing inside one */
 #define SVX_E_RANGE        (-10)  /* svx_text_index: a record ends beyond 2^29: outside what a .tbi can hold */
+#define SVX_E_IO           (-11)  /* svx_bam_sort_*: a write to or a read from the spill file failed or came back short */
 #define SVX_E_NO_DELETION  (-8)   /* svx_combine: insertion-from clusters but no deletion cluster (the reference raises IndexError at src/svim/SVIM_merging.py:20) */
 
 /* signature types, in the order CLUSTER processes them (src/svim/SVIM_CLUSTER.py:19-24) */
@@ -696,13 +697,34 @@ int  svx_bam_index_host(int32_t n_ref, int64_t n_rows, const int32_t* tid, const
  * SVX_E_STATE unless every block has been encoded in ascending, gap-free ranges since finish; SVX_E_RANGE: a record ends beyond 2^29.
  * svx_bam_sort_permutation: perm[i] = the file index of the i-th record of the sorted order (n_records entries).
  * svx_bam_sort_abort at any point: sorting off, everything dropped; SVX_E_STATE when no sort is on or finished.
- * With sorting never begun the reader does what it did before these functions existed. */
+ * With sorting never begun the reader does what it did before these functions existed.
+ * Files whose records do not fit into device memory: svx_bam_sort_begin_spill(max_bytes, spill_dir) has the preconditions of svx_bam_sort_begin; spill_dir
+ * must be a directory the process can write to (SVX_E_ARG otherwise).  The chunk that would take the arena past the limit (max_bytes, or with 0 what the device
+ * has free) no longer fails the read: it CLOSES A RUN - the run's records are sorted, laid out in that order and appended to one spill file in spill_dir, the
+ * slabs are freed - and starts the next run.  Only a chunk whose own bytes pass max_bytes is SVX_E_CAPACITY.  The spill file is unlinked as soon as it is
+ * open (a killed process leaves nothing behind), holds raw stream bytes, and is closed by abort, by closing the handle and by every failure.  Resident for the
+ * whole file stay about 60 bytes per record: key, length, file index and offset of every record in run order, the index rows, and after finish the
+ * permutation and the segment table.  If no run was closed when the file ends, finish is the in-memory finish: no file is made.  Otherwise the last run is
+ * spilled too, one stable radix sort over the run-sorted keys (payload: the place in the concatenation of the runs) gives the order - equal keys tie by run,
+ * then by place in the run, which is file order: the permutation of the in-memory sort - and svx_bam_sort_encode reads, for every piece, one contiguous byte
+ * range per run back from the file into a staging buffer (SVX_E_CAPACITY with the size in svx_last_error if it does not fit) before the same gather and
+ * encoder.  count, fetch, index and permutation mean what they mean above; the bytes are the same.  SVX_E_IO: a write or read of the spill file failed or was
+ * short; the sort is dropped and the handle is usable after svx_bam_rewind.  svx_bam_sort_stats.arena_bytes counts the records' bytes wherever they lie.
+ * svx_bam_sort_get_spill_stats: valid after any finish, spilled or not (n_runs 0 without records, 1 when nothing was spilled); n_runs, spilled_bytes,
+ * max_chunk_bytes and max_run_bytes are kept up to date during the pass. */
+typedef struct svx_bam_sort_spill_stats {
+    int64_t n_runs, spilled_bytes /* written to the spill file */, max_chunk_bytes /* the largest slab */, max_run_bytes, max_stage_bytes /* the largest staging buffer of an encode, pads included */,
+            readback_bytes /* read from the spill file, over all pieces */;
+    double  t_spill_ms /* closing runs: sort, layout, gather, copy out, pwrite */, t_readback_ms /* pread and copy in, over all pieces */,
+            t_merge_ms /* the sort over the runs, its layout, and the cuts and addresses of every piece */;
+} svx_bam_sort_spill_stats;
 typedef struct svx_bam_sort_stats {
     double  t_append_ms /* slab copies and row kernels, over all chunks */, t_finish_ms, t_sort_ms, t_layout_ms,
             t_encode_ms /* over all pieces: host clock, the stream drained at each phase */, t_gather_ms, t_crc_ms, t_matches_ms, t_codes_ms, t_bits_ms, t_compaction_ms, t_index_ms;
     int64_t n_records, n_slabs, arena_bytes, stream_bytes, n_blocks, key_bits, n_pieces, gather_bytes, piece_bytes_max, blocks_stored, blocks_dynamic, blocks_eof, bytes_out;
 } svx_bam_sort_stats;
 int  svx_bam_sort_begin(svx_bam* h, int64_t max_bytes);
+int  svx_bam_sort_begin_spill(svx_bam* h, int64_t max_bytes, const char* spill_dir);
 int  svx_bam_sort_finish(svx_bam* h);
 int  svx_bam_sort_abort(svx_bam* h);
 int  svx_bam_sort_count(svx_bam* h, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
@@ -711,10 +733,21 @@ int  svx_bam_sort_fetch(svx_bam* h, uint8_t* compressed_dst, uint8_t* stream_dst
 int  svx_bam_sort_index(svx_bam* h);
 int  svx_bam_sort_permutation(svx_bam* h, uint32_t* perm);
 int  svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out);
+int  svx_bam_sort_get_spill_stats(svx_bam* h, svx_bam_sort_spill_stats* out);
 /* host-only, no GPU: records in file order (n_bytes of block_size + body each) -> the sorted record stream (out: n_bytes, may be NULL) and the permutation
  * (perm: perm_cap entries, may be NULL; n_bytes / 36 + 1 always suffice).  *n_records is set also when perm_cap is too small (SVX_E_CAPACITY).
  * SVX_E_ARG / SVX_E_RANGE: what the definition refuses (a stream that ends inside a record is SVX_E_ARG). */
 int  svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_t n_ref, uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records);
+/* host-only, no GPU: the spilled sort by the rules the kernels use (bamsort_core.hpp: bsort_piece_cut).  run_ends[n_runs]: the number of records in front of
+ * the end of every run, in file order, non-decreasing (an empty run is allowed), the last one the number of records (SVX_E_ARG otherwise; n_runs 0 only for a
+ * stream without records).  Every run is sorted stably and written in that order to a "run file"; one stable sort over the run-sorted keys gives the order;
+ * the sorted record stream is then written in pieces of piece_blocks * 65280 bytes, every piece from one contiguous byte range per run read back from the run
+ * file.  out, perm, perm_cap, *n_records and the refusals: as svx_bam_sort_host, and the same bytes and permutation.  The run file is memory of the call unless
+ * write_fn / read_fn are given (both or neither): they move n_bytes at `offset` of the caller's file and return the bytes moved; fewer than asked is SVX_E_IO. */
+typedef int64_t (*svx_spill_write_fn)(void* user, int64_t offset, const uint8_t* src, int64_t n_bytes);
+typedef int64_t (*svx_spill_read_fn)(void* user, int64_t offset, uint8_t* dst, int64_t n_bytes);
+int  svx_bam_sort_spill_host(const uint8_t* records, int64_t n_bytes, int32_t n_ref, const int64_t* run_ends, int64_t n_runs, int64_t piece_blocks, uint8_t* out,
+                             uint32_t* perm, int64_t perm_cap, int64_t* n_records, svx_spill_write_fn write_fn, svx_spill_read_fn read_fn, void* user);
 /* host-only: the header of the sorted file from a file's header (magic .. reference dictionary).  *n_out is the size also when cap is too small (SVX_E_CAPACITY) */
 int  svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out);
 

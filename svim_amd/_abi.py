@@ -13,10 +13,11 @@ SVX_FLAG_SKIP = 0x8000
 NIBBLE = "=ACMGRSVTWYHKDBN"
 
 ERRORS = {-1: "SVX_E_NODEVICE", -2: "SVX_E_HIP", -3: "SVX_E_ARG", -4: "SVX_E_CAPACITY", -5: "SVX_E_STATE", -6: "SVX_E_FASTA_SYMBOL", -7: "SVX_E_FASTA_HOST",
-          -8: "SVX_E_NO_DELETION", -9: "SVX_E_ORDER", -10: "SVX_E_RANGE"}
+          -8: "SVX_E_NO_DELETION", -9: "SVX_E_ORDER", -10: "SVX_E_RANGE", -11: "SVX_E_IO"}
 SVX_E_STATE, SVX_E_FASTA_SYMBOL, SVX_E_FASTA_HOST, SVX_E_NO_DELETION = -5, -6, -7, -8
 SVX_E_CAPACITY, SVX_E_ORDER, SVX_E_RANGE = -4, -9, -10
 SVX_E_ARG = -3
+SVX_E_IO = -11
 # candidate classes in the order of combine_clusters' return tuple (include/svx.h: SVX_CAND_*)
 CAND_DEL, CAND_INV, CAND_DUP_INT, CAND_DUP_TAN, CAND_INS, CAND_BND = range(6)
 CAND_NAMES = ("DEL", "INV", "DUP_INT", "DUP_TAN", "INS", "BND")
@@ -257,6 +258,19 @@ class BamSortStats(C.Structure):
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class BamSortSpillStats(C.Structure):
+    """svx_bam_sort_spill_stats: the spilled sort (svx_bam_sort_begin_spill); valid after any sort_finish"""
+    _fields_ = [(n, C.c_int64) for n in ("n_runs", "spilled_bytes", "max_chunk_bytes", "max_run_bytes", "max_stage_bytes", "readback_bytes")] + \
+               [(n, C.c_double) for n in ("t_spill_ms", "t_readback_ms", "t_merge_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+SPILL_WRITE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_uint8), C.c_int64)
+SPILL_READ_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_uint8), C.c_int64)
 
 
 # SAM text through the device reader (include/svx.h: svx_sam_*)

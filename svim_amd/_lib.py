@@ -36,7 +36,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_vcf_position_order", "svx_text_index", "svx_text_index_count", "svx_text_index_fetch", "svx_text_index_get_stats", "svx_text_index_host",
            "svx_bam_index_begin", "svx_bam_index_finish", "svx_bam_index_abort", "svx_bam_index_count", "svx_bam_index_fetch", "svx_bam_index_get_stats", "svx_bam_index_host",
            "svx_bam_sort_begin", "svx_bam_sort_finish", "svx_bam_sort_abort", "svx_bam_sort_count", "svx_bam_sort_encode", "svx_bam_sort_fetch", "svx_bam_sort_index",
-           "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host",
+           "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host", "svx_bam_sort_begin_spill", "svx_bam_sort_get_spill_stats",
+           "svx_bam_sort_spill_host",
            "svx_sam_open", "svx_sam_get_stats", "svx_sam_convert_host", "svx_sam_header_host"]
 
 
@@ -204,6 +205,40 @@ def bam_sort_host(records, n_ref):
         raise bamsort.BamSortError(rc, "bam_sort_host: " + _abi.ERRORS[rc])
     if rc != 0:
         raise SvxError("svx_bam_sort_host failed: %s" % _abi.ERRORS.get(rc, rc))
+    return out[:len(records)].tobytes(), perm[:n.value].copy()
+
+
+def bam_sort_spill_host(records, n_ref, run_ends, piece_blocks=4096, write=None, read=None):
+    """svx_bam_sort_spill_host (host-only): the spilled sort by the rules of the kernels - runs that end in front of the records run_ends (the last one the
+    number of records), a run file, one contiguous byte range per run and piece of piece_blocks blocks (svim_amd.bamsort.runs_of / merge_runs / piece_cuts say
+    it in Python) -> (the sorted record stream, the permutation): what bam_sort_host gives.  write(offset, data) / read(offset, n_bytes) -> bytes: the run file
+    is the caller's (both or neither; what they return may be short: SvxError with .code SVX_E_IO)."""
+    from . import bamsort
+    records = bytes(records)
+    src = np.frombuffer(records, dtype=np.uint8) if records else np.zeros(1, np.uint8)
+    out = np.zeros(max(1, len(records)), dtype=np.uint8)
+    cap = len(records) // 36 + 1
+    perm, n = np.zeros(cap, dtype=np.uint32), C.c_int64()
+    ends = np.asarray(list(run_ends), dtype=np.int64)
+    ends_p = ptr(ends) if len(ends) else None
+
+    def _write(user, offset, data, n_bytes):
+        return int(write(int(offset), C.string_at(data, n_bytes)))
+
+    def _read(user, offset, dst, n_bytes):
+        got = bytes(read(int(offset), int(n_bytes)))[:n_bytes]
+        C.memmove(dst, got, len(got))
+        return len(got)
+    wf = _abi.SPILL_WRITE_FN(_write) if write else C.cast(None, _abi.SPILL_WRITE_FN)
+    rf = _abi.SPILL_READ_FN(_read) if read else C.cast(None, _abi.SPILL_READ_FN)
+    rc = lib().svx_bam_sort_spill_host(ptr(src), C.c_int64(len(records)), C.c_int32(int(n_ref)), ends_p, C.c_int64(len(ends)), C.c_int64(int(piece_blocks)), ptr(out), ptr(perm),
+                                       C.c_int64(cap), C.byref(n), wf, rf, None)
+    if rc in (_abi.SVX_E_ARG, _abi.SVX_E_RANGE):
+        raise bamsort.BamSortError(rc, "bam_sort_spill_host: " + _abi.ERRORS[rc])
+    if rc != 0:
+        e = SvxError("svx_bam_sort_spill_host failed: %s" % _abi.ERRORS.get(rc, rc))
+        e.code = rc
+        raise e
     return out[:len(records)].tobytes(), perm[:n.value].copy()
 
 

@@ -2,6 +2,7 @@
 batch, on the host, without pysam.  Needs only libsvx.so - no GPU - so it is usable (and tested) on CPU.
 A path that holds SAM text is opened through svx_sam_open: such a handle is read by the device reader only (svim_amd/sam.py says what its records are)."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -136,14 +137,20 @@ class NativeBam(object):
         self.L.svx_bam_index_get_stats(self.h, C.byref(s))
         return s.as_dict()
 
-    def sort_begin(self, max_bytes=0):
+    def sort_begin(self, max_bytes=0, spill_dir=None):
         """the pass that follows keeps every record on the device to put the file into coordinate order (svx_bam_sort_begin; svim_amd/bamsort.py says what the
         sorted file is): device decode must be on, nothing read yet since open / rewind and no index pass on.  max_bytes: the most the records may take on the
         device (0: what is free); the read that would pass it raises with .code SVX_E_CAPACITY, the sort is dropped and the handle rewinds.  seek() and
-        rewind() raise until sort_finish() or sort_abort()"""
-        rc = self.L.svx_bam_sort_begin(self.h, C.c_int64(int(max_bytes)))
+        rewind() raise until sort_finish() or sort_abort().
+        spill_dir: a directory the process can write to (svx_bam_sort_begin_spill).  The read that would pass max_bytes (0: what is free) then closes a run -
+        sorted, written to one spill file there that is unlinked as soon as it is open - and goes on; only a chunk that alone passes the limit raises.
+        sort_finish() merges the runs; the file, its index and the permutation are those of the in-memory sort.  None: no spill file, the limit raises"""
+        if spill_dir is None:
+            rc = self.L.svx_bam_sort_begin(self.h, C.c_int64(int(max_bytes)))
+        else:
+            rc = self.L.svx_bam_sort_begin_spill(self.h, C.c_int64(int(max_bytes)), os.fsencode(spill_dir))
         if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_begin")
+            raise self._sort_error(rc, "svx_bam_sort_begin" if spill_dir is None else "svx_bam_sort_begin_spill")
 
     def sort_finish(self):
         """-> (records, bytes of the sorted stream, BGZF blocks of the sorted file), once read_batch has returned 0 records at the end of the file
@@ -203,6 +210,13 @@ class NativeBam(object):
     def sort_stats(self):
         s = _abi.BamSortStats()
         self.L.svx_bam_sort_get_stats(self.h, C.byref(s))
+        return s.as_dict()
+
+    def sort_spill_stats(self):
+        """runs, bytes written to and read from the spill file, the largest chunk, run and staging buffer, the time spent spilling, reading back and merging
+        (svx_bam_sort_get_spill_stats); after a sort that spilled nothing: n_runs 1 (0 without records), spilled_bytes 0"""
+        s = _abi.BamSortSpillStats()
+        self.L.svx_bam_sort_get_spill_stats(self.h, C.byref(s))
         return s.as_dict()
 
     def sam_stats(self):

@@ -15,7 +15,10 @@ What the sorted file is:
   file        the stream cut into BGZF blocks of exactly 65 280 stream bytes (the last one shorter) and the 28-byte end-of-file block.  Block edges ignore header
               and record edges, which the BAM specification allows; htslib's own layout is not reproduced.  The compressed bytes are what
               svx_text_gz_host makes of the stream (csrc/deflate_core.hpp).
-  index       bai.build_index(*bai.rows_of_bam(file)): a record that starts at stream offset u has vbeg = (coff[u // 65280] << 16) | (u % 65280)."""
+  index       bai.build_index(*bai.rows_of_bam(file)): a record that starts at stream offset u has vbeg = (coff[u // 65280] << 16) | (u % 65280).
+  spilled     a file whose records do not fit on the device is sorted in runs (svx_bam_sort_begin_spill): runs_of cuts the file into consecutive ranges and
+              sorts each, merge_runs merges them with ties to the lower run - the same stream and permutation, whatever the cuts - and piece_cuts says which
+              contiguous range of every run a piece of the output needs.  The device and the host build (svx_bam_sort_spill_host) are held to these."""
 import struct
 
 E_ARG, E_RANGE = -3, -10
@@ -112,6 +115,66 @@ def sort_records(stream, n_ref):
     recs = split_records(stream, n_ref)
     perm = permutation(recs)
     return b"".join(recs[k] for k in perm), perm
+
+
+def runs_of(stream, n_ref, run_ends):
+    """The spilled sort (svx_bam_sort_begin_spill) forms runs: consecutive ranges of the file, each sorted on its own.  stream: records in file order;
+    run_ends: the number of records in front of the end of every run, non-decreasing (equal neighbours: an empty run), the last one the number of records
+    -> one list per run of (sort key, file index, record bytes), in the run's stable order.  The bytes of a run, joined, are its part of the spill file."""
+    recs = list(stream) if isinstance(stream, (list, tuple)) else split_records(stream, n_ref)      # (a list: records already split and checked)
+    run_ends = [int(e) for e in run_ends]
+    if any(b < a for a, b in zip([0] + run_ends, run_ends)) or (run_ends[-1] if run_ends else 0) != len(recs):
+        raise ValueError("run_ends must be non-decreasing and end with the number of records")
+    return [[(sort_key(recs[k][4:]), k, recs[k]) for k in sorted(range(a, b), key=lambda k: sort_key(recs[k][4:]))] for a, b in zip([0] + run_ends, run_ends)]
+
+
+def merge_runs(runs):
+    """the k-way merge of sorted runs, a tie going to the lower run (within a run the order stands) -> (the sorted record stream, the permutation).  Runs are
+    consecutive ranges of the file and each is in stable order, so equal keys leave in file order: the stream and the permutation of sort_records."""
+    import heapq
+    heads = [(run[0][0], r, 0) for r, run in enumerate(runs) if run]
+    heapq.heapify(heads)
+    out, perm = [], []
+    while heads:
+        _, r, i = heapq.heappop(heads)
+        perm.append(runs[r][i][1])
+        out.append(runs[r][i][2])
+        if i + 1 < len(runs[r]):
+            heapq.heappush(heads, (runs[r][i + 1][0], r, i + 1))
+    return b"".join(out), perm
+
+
+def piece_cuts(runs, perm, first_byte, piece_bytes):
+    """What a piece of the output needs of every run.  runs: runs_of(...); perm: the permutation of the sorted order; first_byte: bytes in front of the first
+    record in the output stream (the header; 0 for the record stream alone); a piece is piece_bytes of the stream.
+    The rule: a run's records keep their in-run order in the global order, so the global positions of a run's records, gpos, increase along the run, and among
+    any CONTIGUOUS range [p0, p1) of global positions the run's records are a contiguous in-run range [a, b): a = the first i with gpos[i] >= p0, b = the
+    first i with gpos[i] >= p1 (csrc/bamsort_core.hpp: bsort_piece_cut).  A piece holds bytes of the records at positions [p0, p1) - the first and the last
+    may straddle its edges - and therefore reads one contiguous byte range per run.
+    -> per piece (p0, p1, [(a, b) per run])."""
+    import bisect
+    where = {}
+    for r, run in enumerate(runs):
+        for i, (_, k, _) in enumerate(run):
+            where[k] = (r, i)
+    n = len(perm)
+    gpos = [[0] * len(run) for run in runs]
+    ends, at = [], first_byte
+    for j, k in enumerate(perm):
+        r, i = where[k]
+        gpos[r][i] = j
+        at += len(runs[r][i][2])
+        ends.append(at)
+    out = []
+    for lo in range(0, at, piece_bytes):
+        hi = min(lo + piece_bytes, at)
+        # the records with a byte in [lo, hi): record j covers [ends[j - 1], ends[j])
+        p0 = bisect.bisect_right(ends, lo) if n else 0
+        p1 = bisect.bisect_left(ends, hi) + 1 if hi > first_byte and n else 0
+        p0, p1 = min(p0, n), min(p1, n)
+        p0 = min(p0, p1)
+        out.append((p0, p1, [(bisect.bisect_left(g, p0), bisect.bisect_left(g, p1)) for g in gpos]))
+    return out
 
 
 def inflate(path):

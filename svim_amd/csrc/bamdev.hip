@@ -963,9 +963,9 @@ int devdec_load_text(svx_devdec* d, int slot, const uint8_t* text, size_t n, boo
 }
 void devdec_sam_stats(const svx_devdec* d, svx_sam_stats* out) { samdev_stats(d->sam, out); }
 
-int devdec_sort_begin(svx_devdec* d, int64_t max_bytes) {
+int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir) {
     HIPCHK(hipSetDevice(d->device));
-    SVXCHK(bamsort_begin(&d->sort, max_bytes, d->n_ref));
+    SVXCHK(bamsort_begin(&d->sort, max_bytes, d->n_ref, spill_dir));
     d->sort_on = true;
     return SVX_OK;
 }
@@ -986,7 +986,9 @@ int devdec_sort_finish(svx_devdec* d, const uint8_t* header, int64_t header_byte
 void devdec_sort_count(const svx_devdec* d, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) { bamsort_count(d->sort, n_records, stream_bytes, n_blocks); }
 int devdec_sort_encode(svx_devdec* d, int64_t first_block, int64_t n_blocks, int64_t* n_bytes) {
     HIPCHK(hipSetDevice(d->device));
-    return bamsort_encode(d->sort, first_block, n_blocks, n_bytes, d->stream);
+    const int rc = bamsort_encode(d->sort, first_block, n_blocks, n_bytes, d->stream);
+    if (rc == SVX_E_IO) bamsort_drop(d->sort);              // (the spill file cannot be read: nothing of the sort is of use)
+    return rc;
 }
 int devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_dst) {
     HIPCHK(hipSetDevice(d->device));
@@ -1005,6 +1007,7 @@ int devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm) {
     return bamsort_permutation(d->sort, host_perm, d->stream);
 }
 void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out) { bamsort_stats(d->sort, out); }
+void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out) { bamsort_spill_stats(d->sort, out); }
 
 int devdec_index_begin(svx_devdec* d) {
     HIPCHK(hipSetDevice(d->device));

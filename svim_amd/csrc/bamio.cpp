@@ -1206,17 +1206,22 @@ static int raw_header(svx_bam* h, std::vector<uint8_t>& out) {
     out.resize(h->header_bytes);
     return SVX_OK;
 }
-extern "C" int svx_bam_sort_begin(svx_bam* h, int64_t max_bytes) {
+static int sort_begin(svx_bam* h, int64_t max_bytes, const char* spill_dir) {
     if (!h || max_bytes < 0) return bam_fail(SVX_E_ARG, "svx_bam_sort_begin: bad argument");
     if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the sort is fed by the device reader's record stream (svx_bam_set_device_decode first)");
     if (devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
     if (devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin during a sort pass");
     if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
         return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the handle is not at its first record (begin before the first read, or rewind first)");
-    const int rc = devdec_sort_begin(h->dev, max_bytes);
+    const int rc = devdec_sort_begin(h->dev, max_bytes, spill_dir);
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
     h->dev_eof_seen = false;
     return SVX_OK;
+}
+extern "C" int svx_bam_sort_begin(svx_bam* h, int64_t max_bytes) { return sort_begin(h, max_bytes, nullptr); }
+extern "C" int svx_bam_sort_begin_spill(svx_bam* h, int64_t max_bytes, const char* spill_dir) {
+    if (!spill_dir) return bam_fail(SVX_E_ARG, "svx_bam_sort_begin_spill: no spill directory");
+    return sort_begin(h, max_bytes, spill_dir);
 }
 extern "C" int svx_bam_sort_finish(svx_bam* h) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
@@ -1275,6 +1280,12 @@ extern "C" int svx_bam_sort_permutation(svx_bam* h, uint32_t* perm) {
 extern "C" int svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out) {
     if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
     if (h->dev) devdec_sort_stats(h->dev, out); else memset(out, 0, sizeof *out);
+    return SVX_OK;
+}
+
+extern "C" int svx_bam_sort_get_spill_stats(svx_bam* h, svx_bam_sort_spill_stats* out) {
+    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
+    if (h->dev) devdec_sort_spill_stats(h->dev, out); else memset(out, 0, sizeof *out);
     return SVX_OK;
 }
 

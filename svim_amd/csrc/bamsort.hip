@@ -11,6 +11,16 @@
 //   encode   a range of 65 280-byte blocks: k_bs_gather lays the stream bytes of the range out in the piece buffer, then the encoder's phases over the piece
 //            (textgz_kernels.hpp: CRC, matches, codes, bits, compaction), every block's compressed size kept on the host
 //   index    the sorted rows with the virtual offsets the block sizes give, through bamindex.hip's phases (bamindex_take_rows, bamindex_finish)
+// Files whose records do not fit (svx_bam_sort_begin_spill): only the record BYTES are spilled, the rows stay.
+//   run      the chunk that would take the arena past the limit closes a run: its (key, record number) pairs sorted stably, k_bs_run_layout the segments of the
+//            run's stream (no header) and the run-order rows that stay resident (key, length, file index, offset in the run's stream), the stream gathered
+//            piece by piece by k_bs_gather and appended to ONE spill file (created in the caller's directory, unlinked at once), the slabs freed
+//   merge    finish: one stable radix sort over the concatenation of the run-sorted keys, payload the place in the concatenation.  Equal keys tie by run, then
+//            by place in the run; runs are consecutive file ranges and each run's sort is stable: the permutation of the in-memory sort.  k_bs_spill_layout
+//            the segment table (run, offset in the run's stream, length) and gpos, the global positions of each run's records, increasing within a run
+//   encode   k_bs_piece_cuts: for every run the in-run range of the piece's records, by two bisections in the run's gpos (bamsort_core.hpp: bsort_piece_cut -
+//            a run contributes a CONTIGUOUS range to any contiguous range of the global order); the byte ranges are read back from the file into a staging
+//            buffer, back to back, k_bs_piece_addr gives the piece's segments their addresses there, and the gather and the encoder run unchanged
 // k_bs_gather: a workgroup owns tiles of BS_TILE bytes of the piece; work follows the bytes of the destination, not the records (a record is between 36 bytes and
 // hundreds of kilobytes long).  Wave 0 finds the tile's first and last segment in the stream offsets by a 64-ary search (one probe per lane and step), the
 // tile's segment table goes to LDS, and every lane takes aligned 16-byte words of the destination: the segment of a word's first byte by bisection in LDS, the
@@ -24,12 +34,17 @@
 #include "bamsort.hpp"
 #include "textgz_kernels.hpp"
 #include <algorithm>
+#include <string>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
 
 #define BS_T 256
 #define BS_GRID(n) (unsigned)(((long long)(n) + BS_T - 1) / BS_T)
 #define BS_TILE 16384                 /* bytes of the piece per workgroup and step: 4 words of 16 bytes per lane */
 #define BS_SEGS 512                   /* segments of a tile kept in LDS: a record is at least 36 bytes, so a tile touches at most 16384 / 36 + 2 = 457 */
 #define BS_MAX_GRID 2048
+#define BS_SPILL_PIECE (32ll << 20)   /* bytes of a run's stream gathered and written at a time (a multiple of 16) */
 #define BS_PAD 64                     /* bytes behind a slab, the header and the piece: the aligned loads around a record's last bytes stay inside the allocation */
 static_assert(BSORT_BLOCK == DEF_BLOCK, "the output's blocks are the encoder's");
 static_assert(BSORT_BLOCK % 16 == 0 && BS_TILE % 16 == 0, "a piece and its tiles start at aligned words of the destination");
@@ -64,6 +79,31 @@ __global__ void k_bs_layout(long long n, const uint32_t* perm, const uint32_t* l
     if (j == 0) { slen[0] = hdr_bytes; saddr[0] = hdr; return; }
     const uint32_t r = perm[j - 1];
     slen[j] = (int64_t)len[r]; saddr[j] = addr[r];
+}
+
+// a run is closed: segment j of its stream is the record first + order[j] (order: the run's stable sort, indices inside the run; len / addr: the run's rows in
+// file order); slen has one entry more (0).  What stays resident of the run, in run order: length and file index (the key comes from the sort itself)
+__global__ void k_bs_run_layout(long long m, const uint32_t* order, const uint32_t* len, const uint64_t* addr, uint32_t first, int64_t* slen, uint64_t* saddr, uint32_t* rlen,
+                                uint32_t* rfile) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > m) return;
+    if (j == m) { slen[j] = 0; return; }
+    const uint32_t r = order[j];
+    slen[j] = (int64_t)len[r]; saddr[j] = addr[r];
+    rlen[j] = len[r]; rfile[j] = first + r;
+}
+// the merge: gp[j - 1] = the place in the concatenation of the runs of the record at global position j - 1 (segment j; segment 0 is the header).  Per segment
+// its run, its offset in the run's stream and its length; per place its global position (gpos: increasing within a run); the permutation
+__global__ void k_bs_spill_layout(long long n, const uint32_t* gp, const uint32_t* rlen, const uint32_t* rfile, const int64_t* roff, const int64_t* run_base, long long n_runs,
+                                  uint64_t hdr, long long hdr_bytes, uint32_t* perm, int64_t* slen, uint32_t* srun, int64_t* sroff, uint32_t* gpos, uint64_t* saddr) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > n + 1) return;
+    if (j == n + 1) { slen[j] = 0; return; }
+    if (j == 0) { slen[0] = hdr_bytes; saddr[0] = hdr; srun[0] = 0u; sroff[0] = 0; return; }
+    const uint32_t q = gp[j - 1];
+    perm[j - 1] = rfile[q];
+    slen[j] = (int64_t)rlen[q]; srun[j] = (uint32_t)bsort_run_of(run_base, n_runs, (int64_t)q); sroff[j] = roff[q];
+    gpos[q] = (uint32_t)(j - 1);
 }
 
 // ---- the gather -----------------------------------------------------------------------------------------------------------------------------------------
@@ -147,7 +187,37 @@ __global__ __launch_bounds__(BS_T) void k_bs_gather(BsSegs G, long long lo, long
     }
 }
 
+// ---- a piece of a spilled sort ----------------------------------------------------------------------------------------------------------------------------
+// stream bytes [lo, hi) lie in segments j0 .. j1 (found as the gather finds them, by wave 0 of every workgroup); a thread per run: the in-run range [a, b) of
+// the records at global positions [max(j0, 1) - 1, j1) and its byte range in the run's stream -> cuts[2 r], cuts[2 r + 1]; j0, j1 -> cuts[2 n_runs ..]
+__global__ __launch_bounds__(BS_T) void k_bs_piece_cuts(const int64_t* soff, long long n_seg, long long lo, long long hi, const uint32_t* gpos, const int64_t* roff, const int64_t* run_base,
+                                                        const int64_t* run_bytes, long long n_runs, int64_t* cuts) {
+    __shared__ long long s_j[2];
+    if (threadIdx.x < 64) {
+        const long long j0 = bs_find(soff, n_seg, lo), j1 = bs_find(soff, n_seg, hi - 1);
+        if (threadIdx.x == 0) { s_j[0] = j0; s_j[1] = j1; }
+    }
+    __syncthreads();
+    const long long j0 = s_j[0], j1 = s_j[1];
+    const long long r = (long long)blockIdx.x * BS_T + threadIdx.x;
+    if (r == 0) { cuts[2 * n_runs] = j0; cuts[2 * n_runs + 1] = j1; }
+    if (r >= n_runs) return;
+    const int64_t base = run_base[r], cnt = run_base[r + 1] - base;
+    int64_t a, b;
+    bsort_piece_cut(gpos + base, cnt, (j0 > 0 ? j0 : 1) - 1, j1, &a, &b);
+    cuts[2 * r] = a < cnt ? roff[base + a] : run_bytes[r];
+    cuts[2 * r + 1] = b < cnt ? roff[base + b] : run_bytes[r];
+}
+// the records of the piece, segments max(j0, 1) .. j1: where they lie in the staging buffer (stage[r]: where the run's byte range starts there)
+__global__ void k_bs_piece_addr(long long j_first, long long j_last, const uint32_t* srun, const int64_t* sroff, const uint64_t* stage, const int64_t* cuts, uint64_t* saddr) {
+    const long long j = j_first + (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > j_last) return;
+    const uint32_t r = srun[j];
+    saddr[j] = stage[r] + (uint64_t)(sroff[j] - cuts[2 * r]);
+}
+
 // ---------------------------------------------------------------------------------------------------------------------------------------------------------
+struct BsRun { int64_t base, count, file_off, bytes; };     // records [base, base + count) of the file; the run's stream at file_off of the spill file
 struct BamSort {
     int32_t n_ref = 0; int64_t max_bytes = 0;
     int64_t n = 0, cap = 0;
@@ -163,16 +233,33 @@ struct BamSort {
     int64_t piece_bytes = 0, out_bytes = 0; bool have_piece = false;
     double t_append = 0;
     svx_bam_sort_stats stats;
+    // spilling (bamsort_begin with a directory): the runs closed so far lie in one unlinked file; key / len / addr hold the rows of the open run only
+    bool spill = false; std::string spill_dir; int fd = -1; int64_t spill_piece = BS_SPILL_PIECE;
+    int64_t file_bytes = 0, total_bytes = 0 /* record bytes of all runs and the arena */, run_first = 0 /* the open run's first record */, n_slabs_all = 0;
+    std::vector<BsRun> runs;
+    DevBuf rkey, rlen, rfile, roff; int64_t rcap = 0;        // every record of a closed run, in run order: key, length, file index, offset in the run's stream
+    DevBuf gp, srun, sroff, gpos, run_base, run_bytes, cuts, stage_at, stage;
+    std::vector<uint8_t> h_io;                               // the host's side of the file's traffic
+    std::vector<int64_t> h_cuts;                             // of the piece being encoded: 2 n_runs byte offsets, j0, j1
+    svx_bam_sort_spill_stats sp;
 };
 static inline double bs_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref) {
+int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir) {
     if (max_bytes < 0 || n_ref < 0) return svx_fail(SVX_E_ARG, "BAM sort: bad argument", __FILE__, __LINE__, hipSuccess);
+    if (spill_dir) {
+        struct stat sb;
+        if (!*spill_dir || stat(spill_dir, &sb) != 0 || !S_ISDIR(sb.st_mode) || access(spill_dir, W_OK | X_OK) != 0)
+            return svx_fail(SVX_E_ARG, "BAM sort: the spill directory does not exist or cannot be written to", __FILE__, __LINE__, hipSuccess);
+    }
     if (!*s) *s = new BamSort();
     BamSort* S = *s;
     bamsort_drop(S);
     S->n_ref = n_ref; S->max_bytes = max_bytes;
-    memset(&S->stats, 0, sizeof S->stats);
+    S->spill = spill_dir != nullptr; S->spill_dir = spill_dir ? spill_dir : "";
+    S->spill_piece = BS_SPILL_PIECE;                         // test hook: SVX_BAM_SORT_SPILL_PIECE_KB, so that small runs leave in several pieces
+    { const char* e = getenv("SVX_BAM_SORT_SPILL_PIECE_KB"); if (e && atoll(e) > 0 && atoll(e) <= (BS_SPILL_PIECE >> 10)) S->spill_piece = atoll(e) << 10; }
+    memset(&S->stats, 0, sizeof S->stats); memset(&S->sp, 0, sizeof S->sp);
     SVXCHK(bamindex_begin(&S->rows));
     SVXCHK(S->bad.reserve(64));
     HIPCHK(hipMemset(S->bad.p, 0, 64));
@@ -183,8 +270,12 @@ void bamsort_drop(BamSort* S) {
     for (void* p : S->slabs) (void)hipFree(p);
     S->slabs.clear(); S->arena_bytes = 0;
     DevBuf* all[] = {&S->key, &S->len, &S->addr, &S->key2, &S->val, &S->perm, &S->sort_tmp, &S->scan_tmp, &S->slen, &S->soff, &S->saddr, &S->hdr, &S->piece, &S->blocks, &S->crc, &S->tok,
-                     &S->hist, &S->nt, &S->codes, &S->bsize, &S->coff, &S->kinds, &S->slots, &S->out, &S->coff_all};
+                     &S->hist, &S->nt, &S->codes, &S->bsize, &S->coff, &S->kinds, &S->slots, &S->out, &S->coff_all,
+                     &S->rkey, &S->rlen, &S->rfile, &S->roff, &S->gp, &S->srun, &S->sroff, &S->gpos, &S->run_base, &S->run_bytes, &S->cuts, &S->stage_at, &S->stage};
     for (auto* b : all) b->release();
+    if (S->fd >= 0) { (void)close(S->fd); S->fd = -1; }      // (unlinked when it was opened: its blocks go back now)
+    S->runs.clear(); S->file_bytes = S->total_bytes = S->run_first = S->n_slabs_all = 0; S->rcap = 0;
+    S->h_io.clear(); S->h_io.shrink_to_fit(); S->h_cuts.clear();
     bamindex_drop(S->rows);
     S->n = S->cap = 0; S->finished = false; S->have_piece = false; S->stream_bytes = S->n_blocks = S->next_block = 0; S->broken = false; S->t_append = 0;
     S->piece_bytes = S->out_bytes = 0;
@@ -198,43 +289,153 @@ void bamsort_destroy(BamSort* S) {
     delete S;
 }
 
+// ---- spilling: a run is closed ----------------------------------------------------------------------------------------------------------------------------
+static int bs_io_fail(const char* what, long long at, long long n_bytes) {
+    char msg[200]; snprintf(msg, sizeof msg, "BAM sort: %s of %lld bytes at offset %lld of the spill file failed or was short (%s)", what, n_bytes, at, errno ? strerror(errno) : "no error code");
+    return svx_fail(SVX_E_IO, msg, __FILE__, __LINE__, hipSuccess);
+}
+static int bs_spill_open(BamSort* S) {
+    std::string path = S->spill_dir + "/svx_sort_spill_XXXXXX";
+    S->fd = mkostemp(&path[0], O_CLOEXEC);
+    if (S->fd < 0) return svx_fail(SVX_E_IO, "BAM sort: the spill file cannot be created", __FILE__, __LINE__, hipSuccess);
+    (void)unlink(path.c_str());                              // nothing is left behind, whatever ends the process
+    S->file_bytes = 0;
+    return SVX_OK;
+}
+// the open run - records [run_first, n), their bytes in the slabs - sorted, laid out, written behind the runs before it; the slabs go back
+static int bs_close_run(BamSort* S, hipStream_t st) {
+    const int64_t first = S->run_first, m = S->n - first;
+    if (m <= 0) return SVX_OK;
+    const double t0 = bs_now();
+    if (S->fd < 0) SVXCHK(bs_spill_open(S));
+    if (S->n + 1 > S->rcap) {                                // (roff takes one entry more: the scan ends with the run's size)
+        const int64_t ncap = std::max<int64_t>(std::max<int64_t>(S->n + 1, 2 * S->rcap), 1 << 16);
+        SVXCHK(S->rkey.reserve((size_t)ncap * 8, true, st)); SVXCHK(S->rlen.reserve((size_t)ncap * 4, true, st)); SVXCHK(S->rfile.reserve((size_t)ncap * 4, true, st));
+        SVXCHK(S->roff.reserve((size_t)ncap * 8, true, st));
+        S->rcap = ncap;
+    }
+    SVXCHK(S->val.reserve((size_t)m * 4)); SVXCHK(S->perm.reserve((size_t)(m + 1) * 4)); SVXCHK(S->slen.reserve((size_t)(m + 1) * 8)); SVXCHK(S->saddr.reserve((size_t)(m + 1) * 8));
+    k_bs_iota<<<BS_GRID(m), BS_T, 0, st>>>(m, S->val.as<uint32_t>());
+    SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->key.as<uint64_t>(), S->rkey.as<uint64_t>() + first, S->val.as<uint32_t>(), S->perm.as<uint32_t>(), m, 0, bsort_key_bits(S->n_ref)));
+    k_bs_run_layout<<<BS_GRID(m + 1), BS_T, 0, st>>>(m, S->perm.as<uint32_t>(), S->len.as<uint32_t>(), S->addr.as<uint64_t>(), (uint32_t)first, S->slen.as<int64_t>(), S->saddr.as<uint64_t>(),
+                                                     S->rlen.as<uint32_t>() + first, S->rfile.as<uint32_t>() + first);
+    HIPCHK(hipGetLastError());
+    int64_t* roff = S->roff.as<int64_t>() + first;
+    SVXCHK((svx_exclusive_scan<int64_t, int64_t>(S->slen.as<int64_t>(), roff, m + 1, st, S->scan_tmp)));
+    int64_t total = 0;
+    SVXCHK(svx_d2h(&total, roff + m, 8, st));
+    if (total != S->arena_bytes) return svx_fail(SVX_E_STATE, "BAM sort: a run's stream is not the size of its slabs (internal error)", __FILE__, __LINE__, hipSuccess);
+    const int64_t step = std::min<int64_t>(S->spill_piece, total);
+    SVXCHK(S->piece.reserve((size_t)step + 256));
+    if ((int64_t)S->h_io.size() < step) S->h_io.resize((size_t)step);
+    const BsSegs G{roff, S->saddr.as<uint64_t>(), m};
+    for (int64_t lo = 0; lo < total; lo += step) {
+        const int64_t pb = std::min<int64_t>(step, total - lo);
+        const long long tiles = (pb + BS_TILE - 1) / BS_TILE;
+        k_bs_gather<<<(unsigned)std::min<long long>(tiles, BS_MAX_GRID), BS_T, 0, st>>>(G, lo, pb, S->piece.as<uint8_t>());
+        HIPCHK(hipGetLastError());
+        SVXCHK(svx_d2h(S->h_io.data(), S->piece.p, (size_t)pb, st));
+        for (int64_t done = 0; done < pb;) {
+            errno = 0;
+            const ssize_t w = pwrite(S->fd, S->h_io.data() + done, (size_t)(pb - done), (off_t)(S->file_bytes + lo + done));
+            if (w <= 0) { if (w < 0 && errno == EINTR) continue; return bs_io_fail("a write", S->file_bytes + lo + done, pb - done); }
+            done += w;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    S->runs.push_back(BsRun{first, m, S->file_bytes, total});
+    S->file_bytes += total;
+    for (void* p : S->slabs) (void)hipFree(p);
+    S->slabs.clear(); S->arena_bytes = 0; S->run_first = S->n;
+    S->sp.n_runs = (int64_t)S->runs.size(); S->sp.spilled_bytes = S->file_bytes; S->sp.max_run_bytes = std::max<int64_t>(S->sp.max_run_bytes, total);
+    S->sp.t_spill_ms += (bs_now() - t0) * 1e3;
+    return SVX_OK;
+}
+
 int bamsort_append(BamSort* S, const BamSortChunk& c, hipStream_t st) {
     if (!S || S->finished || c.n < 0 || c.end_byte < c.first_byte) return svx_fail(SVX_E_ARG, "BAM sort: bad chunk", __FILE__, __LINE__, hipSuccess);
     if (c.n == 0) return SVX_OK;
     const double t0 = bs_now();
     if (S->n + c.n > 0xffffffffll) return svx_fail(SVX_E_CAPACITY, "BAM sort: more than 2^32 - 1 records", __FILE__, __LINE__, hipSuccess);
     const size_t need = (size_t)(c.end_byte - c.first_byte);
-    {
-        char msg[200];
-        if (S->max_bytes > 0 && S->arena_bytes + (int64_t)need > S->max_bytes) {
-            snprintf(msg, sizeof msg, "BAM sort: the records do not fit into the arena (%lld bytes held, %zu more, limit %lld)", (long long)S->arena_bytes, need, (long long)S->max_bytes);
-            return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
-        }
+    double t_closing = 0;
+    for (int attempt = 0;; attempt++) {
+        char msg[200]; msg[0] = 0;
         size_t free_b = 0, total_b = 0;
-        if (S->max_bytes == 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + (size_t)c.n * 64 + ((size_t)64 << 20) > free_b) {
+        if (S->max_bytes > 0 && S->arena_bytes + (int64_t)need > S->max_bytes)
+            snprintf(msg, sizeof msg, "BAM sort: the records do not fit into the arena (%lld bytes held, %zu more, limit %lld)", (long long)S->arena_bytes, need, (long long)S->max_bytes);
+        else if (S->max_bytes == 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + (size_t)c.n * 64 + ((size_t)64 << 20) > free_b)
             snprintf(msg, sizeof msg, "BAM sort: the records do not fit into device memory (%lld bytes held, %zu more, %zu free)", (long long)S->arena_bytes, need, free_b);
-            return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
-        }
+        if (!msg[0]) break;
+        // with a spill directory the open run is closed and the chunk starts the next one; a chunk that alone passes the limit has nowhere to go
+        if (!S->spill || attempt > 0 || S->arena_bytes == 0) return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
+        const double tc = bs_now();
+        SVXCHK(bs_close_run(S, st));
+        t_closing = bs_now() - tc;
     }
-    if (S->n + c.n > S->cap) {                               // the rows grow by doubling, kept; the slabs never move
-        const int64_t ncap = std::max<int64_t>(std::max<int64_t>(S->n + c.n, 2 * S->cap), 1 << 16);
+    const int64_t n_run = S->n - S->run_first;               // rows of the open run (all rows, when nothing spills)
+    if (n_run + c.n > S->cap) {                              // the rows grow by doubling, kept; the slabs never move
+        const int64_t ncap = std::max<int64_t>(std::max<int64_t>(n_run + c.n, 2 * S->cap), 1 << 16);
         SVXCHK(S->key.reserve((size_t)ncap * 8, true, st)); SVXCHK(S->len.reserve((size_t)ncap * 4, true, st)); SVXCHK(S->addr.reserve((size_t)ncap * 8, true, st));
         S->cap = ncap;
     }
     void* slab = nullptr;
     HIPCHK(hipMalloc(&slab, need + BS_PAD));
-    S->slabs.push_back(slab); S->arena_bytes += (int64_t)need;
+    S->slabs.push_back(slab); S->arena_bytes += (int64_t)need; S->total_bytes += (int64_t)need; S->n_slabs_all++;
+    S->sp.max_chunk_bytes = std::max<int64_t>(S->sp.max_chunk_bytes, (int64_t)need);
     HIPCHK(hipMemcpyAsync(slab, c.stream + c.first_byte, need, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemsetAsync((uint8_t*)slab + need, 0, BS_PAD, st));
-    k_bs_rows<<<BS_GRID(c.n), BS_T, 0, st>>>(c.n, c.stream, c.rec_off, c.first_byte, c.end_byte, (uint64_t)(uintptr_t)slab, c.tid, c.pos, c.flag, S->n_ref, S->key.as<uint64_t>() + S->n,
-                                             S->len.as<uint32_t>() + S->n, S->addr.as<uint64_t>() + S->n, S->bad.as<int>());
+    k_bs_rows<<<BS_GRID(c.n), BS_T, 0, st>>>(c.n, c.stream, c.rec_off, c.first_byte, c.end_byte, (uint64_t)(uintptr_t)slab, c.tid, c.pos, c.flag, S->n_ref, S->key.as<uint64_t>() + n_run,
+                                             S->len.as<uint32_t>() + n_run, S->addr.as<uint64_t>() + n_run, S->bad.as<int>());
     HIPCHK(hipGetLastError());
     // the index rows: end from the CIGAR (CG included) by bamindex.hip's append; its virtual offsets are replaced when the sorted file's are known
     const uint64_t blk_start = 0, blk_vbase = 0;
     const BamIndexChunk ic{c.n, c.tid, c.pos, c.flag, c.cigar_off, c.cigar, c.rec_off, &blk_start, &blk_vbase, 1};
     SVXCHK(bamindex_append(S->rows, ic, st));               // (drains the stream: the chunk's arrays and its stream are no longer read)
     S->n += c.n;
-    S->t_append += bs_now() - t0;
+    S->t_append += bs_now() - t0 - t_closing;
+    return SVX_OK;
+}
+
+// finish with runs in the file: the open run joins them, then the merge.  The header lies in S->hdr.
+static int bs_finish_spilled(BamSort* S, int64_t header_bytes, double t0, hipStream_t st) {
+    const int64_t n = S->n;
+    SVXCHK(bs_close_run(S, st));
+    const double t1 = bs_now();
+    const int64_t n_runs = (int64_t)S->runs.size();
+    std::vector<int64_t> h_base((size_t)n_runs + 1, n), h_bytes((size_t)n_runs, 0);
+    for (int64_t r = 0; r < n_runs; r++) { h_base[(size_t)r] = S->runs[(size_t)r].base; h_bytes[(size_t)r] = S->runs[(size_t)r].bytes; }
+    SVXCHK(S->run_base.reserve((size_t)(n_runs + 1) * 8)); SVXCHK(S->run_bytes.reserve((size_t)n_runs * 8));
+    SVXCHK(svx_h2d(S->run_base.p, h_base.data(), (size_t)(n_runs + 1) * 8, st)); SVXCHK(svx_h2d(S->run_bytes.p, h_bytes.data(), (size_t)n_runs * 8, st));
+    // the run-sorted keys lie back to back in rkey: one stable sort, the place in the concatenation as payload.  Equal keys keep the order run, place in the run
+    SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4)); SVXCHK(S->gp.reserve((size_t)n * 4));
+    k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, S->val.as<uint32_t>());
+    SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->rkey.as<uint64_t>(), S->key2.as<uint64_t>(), S->val.as<uint32_t>(), S->gp.as<uint32_t>(), n, 0, bsort_key_bits(S->n_ref)));
+    HIPCHK(hipStreamSynchronize(st));
+    const double t2 = bs_now();
+    SVXCHK(S->slen.reserve((size_t)(n + 2) * 8)); SVXCHK(S->soff.reserve((size_t)(n + 2) * 8)); SVXCHK(S->saddr.reserve((size_t)(n + 2) * 8));
+    SVXCHK(S->srun.reserve((size_t)(n + 2) * 4)); SVXCHK(S->sroff.reserve((size_t)(n + 2) * 8)); SVXCHK(S->gpos.reserve((size_t)n * 4));
+    k_bs_spill_layout<<<BS_GRID(n + 2), BS_T, 0, st>>>(n, S->gp.as<uint32_t>(), S->rlen.as<uint32_t>(), S->rfile.as<uint32_t>(), S->roff.as<int64_t>(), S->run_base.as<int64_t>(), n_runs,
+                                                       (uint64_t)(uintptr_t)S->hdr.p, header_bytes, S->perm.as<uint32_t>(), S->slen.as<int64_t>(), S->srun.as<uint32_t>(),
+                                                       S->sroff.as<int64_t>(), S->gpos.as<uint32_t>(), S->saddr.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    SVXCHK((svx_exclusive_scan<int64_t, int64_t>(S->slen.as<int64_t>(), S->soff.as<int64_t>(), n + 2, st, S->scan_tmp)));
+    int64_t total = 0;
+    SVXCHK(svx_d2h(&total, S->soff.as<int64_t>() + n + 1, 8, st));
+    if (total != header_bytes + S->total_bytes || S->file_bytes != S->total_bytes)
+        return svx_fail(SVX_E_STATE, "BAM sort: the stream's size is not the header's plus the runs' (internal error)", __FILE__, __LINE__, hipSuccess);
+    // resident from here on: the permutation, the segment table (offset, run, offset in the run), gpos, the runs' record offsets and the index rows
+    S->key.release(); S->key2.release(); S->val.release(); S->len.release(); S->addr.release(); S->slen.release(); S->sort_tmp.release();
+    S->rkey.release(); S->rlen.release(); S->rfile.release(); S->gp.release();
+    S->cap = 0;
+    const double t3 = bs_now();
+    S->stream_bytes = total; S->n_blocks = (total + BSORT_BLOCK - 1) / BSORT_BLOCK + 1; S->next_block = 0; S->broken = false;
+    S->h_csize.assign((size_t)S->n_blocks, 0);
+    S->finished = true;
+    S->stats.t_append_ms = S->t_append * 1e3; S->stats.t_sort_ms = (t2 - t1) * 1e3; S->stats.t_layout_ms = (t3 - t2) * 1e3; S->stats.t_finish_ms = (t3 - t0) * 1e3;
+    S->stats.n_records = n; S->stats.n_slabs = S->n_slabs_all; S->stats.arena_bytes = S->total_bytes; S->stats.stream_bytes = total; S->stats.n_blocks = S->n_blocks;
+    S->stats.key_bits = bsort_key_bits(S->n_ref);
+    S->sp.t_merge_ms += (t3 - t1) * 1e3;
     return SVX_OK;
 }
 
@@ -252,6 +453,7 @@ int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipS
     HIPCHK(hipMemsetAsync((uint8_t*)S->hdr.p + header_bytes, 0, BS_PAD, st));
     SVXCHK(svx_h2d(S->hdr.p, header, (size_t)header_bytes, st));
     SVXCHK(S->perm.reserve((size_t)(n + 1) * 4));
+    if (!S->runs.empty()) return bs_finish_spilled(S, header_bytes, t0, st);      // (no run was closed: exactly the in-memory path, no file)
     if (n > 0) {
         SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4));
         k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, S->val.as<uint32_t>());
@@ -277,6 +479,7 @@ int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipS
     S->stats.t_append_ms = S->t_append * 1e3; S->stats.t_sort_ms = (t1 - t0) * 1e3; S->stats.t_layout_ms = (t2 - t1) * 1e3; S->stats.t_finish_ms = (t2 - t0) * 1e3;
     S->stats.n_records = n; S->stats.n_slabs = (int64_t)S->slabs.size(); S->stats.arena_bytes = S->arena_bytes; S->stats.stream_bytes = total; S->stats.n_blocks = S->n_blocks;
     S->stats.key_bits = bsort_key_bits(S->n_ref);
+    S->sp.n_runs = n > 0 ? 1 : 0; S->sp.max_run_bytes = S->arena_bytes;      // one run, resident
     return SVX_OK;
 }
 bool bamsort_finished(const BamSort* S) { return S && S->finished; }
@@ -286,6 +489,68 @@ void bamsort_count(const BamSort* S, int64_t* n_records, int64_t* stream_bytes, 
     if (n_blocks) *n_blocks = S->n_blocks;
 }
 
+// ---- a piece of a spilled sort: cuts, read-back, addresses ---------------------------------------------------------------------------------------------------
+// stream bytes [lo, hi) -> h_cuts (per run the byte range of its stream the piece needs, then j0 and j1); *stage_bytes: the ranges back to back, each padded
+static int bs_piece_cuts(BamSort* S, int64_t lo, int64_t hi, int64_t* stage_bytes, hipStream_t st) {
+    const double t0 = bs_now();
+    const int64_t n_runs = (int64_t)S->runs.size();
+    SVXCHK(S->cuts.reserve((size_t)(2 * n_runs + 2) * 8));
+    k_bs_piece_cuts<<<BS_GRID(n_runs), BS_T, 0, st>>>(S->soff.as<int64_t>(), S->n + 1, lo, hi, S->gpos.as<uint32_t>(), S->roff.as<int64_t>(), S->run_base.as<int64_t>(), S->run_bytes.as<int64_t>(),
+                                                      n_runs, S->cuts.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    S->h_cuts.assign((size_t)(2 * n_runs + 2), 0);
+    SVXCHK(svx_d2h(S->h_cuts.data(), S->cuts.p, (size_t)(2 * n_runs + 2) * 8, st));
+    int64_t total = 0;
+    for (int64_t r = 0; r < n_runs; r++) {
+        const int64_t a = S->h_cuts[(size_t)(2 * r)], b = S->h_cuts[(size_t)(2 * r + 1)];
+        if (a < 0 || b < a || b > S->runs[(size_t)r].bytes) return svx_fail(SVX_E_STATE, "svx_bam_sort_encode: a run's byte range lies outside the run (internal error)", __FILE__, __LINE__, hipSuccess);
+        if (b > a) total += b - a + BS_PAD;
+    }
+    const int64_t j0 = S->h_cuts[(size_t)(2 * n_runs)], j1 = S->h_cuts[(size_t)(2 * n_runs + 1)];
+    if (j0 < 0 || j1 < j0 || j1 > S->n) return svx_fail(SVX_E_STATE, "svx_bam_sort_encode: the piece's segments lie outside the table (internal error)", __FILE__, __LINE__, hipSuccess);
+    *stage_bytes = total;
+    S->sp.t_merge_ms += (bs_now() - t0) * 1e3;
+    return SVX_OK;
+}
+static int bs_piece_stage(BamSort* S, int64_t stage_bytes, hipStream_t st) {
+    const double t0 = bs_now();
+    const int64_t n_runs = (int64_t)S->runs.size();
+    const int64_t j0 = S->h_cuts[(size_t)(2 * n_runs)], j1 = S->h_cuts[(size_t)(2 * n_runs + 1)];
+    if (j1 < 1) return SVX_OK;                               // (the piece lies inside the header)
+    SVXCHK(S->stage.reserve((size_t)stage_bytes + BS_PAD)); SVXCHK(S->stage_at.reserve((size_t)n_runs * 8));
+    if ((int64_t)S->h_io.size() < stage_bytes) S->h_io.resize((size_t)stage_bytes);
+    std::vector<uint64_t> h_at((size_t)n_runs, 0);
+    int64_t at = 0, n_read = 0;
+    for (int64_t r = 0; r < n_runs; r++) {
+        const int64_t a = S->h_cuts[(size_t)(2 * r)], len = S->h_cuts[(size_t)(2 * r + 1)] - a;
+        h_at[(size_t)r] = (uint64_t)(uintptr_t)S->stage.p + (uint64_t)at;
+        if (len <= 0) continue;
+        for (int64_t done = 0; done < len;) {
+            errno = 0;
+            const ssize_t g = pread(S->fd, S->h_io.data() + at + done, (size_t)(len - done), (off_t)(S->runs[(size_t)r].file_off + a + done));
+            if (g <= 0) { if (g < 0 && errno == EINTR) continue; return bs_io_fail("a read", S->runs[(size_t)r].file_off + a + done, len - done); }
+            done += g;
+        }
+        memset(S->h_io.data() + at + len, 0, BS_PAD);
+        at += len + BS_PAD; n_read += len;
+    }
+    {
+        HostCopy hc(st);
+        if (at > 0) SVXCHK(hc.h2d(S->stage.p, S->h_io.data(), (size_t)at));
+        SVXCHK(hc.h2d(S->stage_at.p, h_at.data(), (size_t)n_runs * 8));
+        SVXCHK(hc.finish());
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    const double t1 = bs_now();
+    const int64_t j_first = std::max<int64_t>(j0, 1);
+    k_bs_piece_addr<<<BS_GRID(j1 - j_first + 1), BS_T, 0, st>>>(j_first, j1, S->srun.as<uint32_t>(), S->sroff.as<int64_t>(), S->stage_at.as<uint64_t>(), S->cuts.as<int64_t>(), S->saddr.as<uint64_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    S->sp.max_stage_bytes = std::max<int64_t>(S->sp.max_stage_bytes, at); S->sp.readback_bytes += n_read;
+    S->sp.t_readback_ms += (t1 - t0) * 1e3; S->sp.t_merge_ms += (bs_now() - t1) * 1e3;
+    return SVX_OK;
+}
+
 int bamsort_encode(BamSort* S, int64_t first, int64_t nb, int64_t* n_bytes, hipStream_t st) {
     if (!S || !S->finished) return svx_fail(SVX_E_STATE, "svx_bam_sort_encode before svx_bam_sort_finish", __FILE__, __LINE__, hipSuccess);
     if (first < 0 || nb < 1 || first > S->n_blocks - nb) return svx_fail(SVX_E_ARG, "svx_bam_sort_encode: block range outside the file", __FILE__, __LINE__, hipSuccess);
@@ -293,12 +558,16 @@ int bamsort_encode(BamSort* S, int64_t first, int64_t nb, int64_t* n_bytes, hipS
     const int64_t total = S->stream_bytes;
     const int64_t lo = std::min<int64_t>(first * BSORT_BLOCK, total), hi = std::min<int64_t>((first + nb) * BSORT_BLOCK, total), pb = hi - lo;
     const long long chunk = std::min<long long>(nb, TGZ_CHUNK);
+    const bool spilled = !S->runs.empty();
+    int64_t stage_bytes = 0;
+    if (spilled && pb > 0) SVXCHK(bs_piece_cuts(S, lo, hi, &stage_bytes, st));          // what the piece needs of every run: known before anything is allocated
     {
-        const size_t need = (size_t)pb + (size_t)nb * DEF_SLOT + (size_t)pb + (size_t)nb * 64 + (size_t)chunk * (DEF_BLOCK * 4 + sizeof(DefBlockCodes) + DEF_NHIST * 4);
-        const size_t have = S->piece.cap + S->slots.cap + S->out.cap + S->tok.cap;
+        const size_t need = (size_t)pb + (size_t)nb * DEF_SLOT + (size_t)pb + (size_t)nb * 64 + (size_t)chunk * (DEF_BLOCK * 4 + sizeof(DefBlockCodes) + DEF_NHIST * 4) + (size_t)stage_bytes;
+        const size_t have = S->piece.cap + S->slots.cap + S->out.cap + S->tok.cap + S->stage.cap;
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + need / 8 + (1u << 20) > free_b + have) {
-            char msg[160]; snprintf(msg, sizeof msg, "svx_bam_sort_encode: the working buffers of %lld blocks (%zu bytes) do not fit into device memory", (long long)nb, need);
+            char msg[240]; snprintf(msg, sizeof msg, "svx_bam_sort_encode: the working buffers of %lld blocks (%zu bytes, %lld of them the staging buffer of the runs' records) do not fit into device memory",
+                                    (long long)nb, need, (long long)stage_bytes);
             return svx_fail(SVX_E_CAPACITY, msg, __FILE__, __LINE__, hipSuccess);
         }
     }
@@ -331,6 +600,7 @@ int bamsort_encode(BamSort* S, int64_t first, int64_t nb, int64_t* n_bytes, hipS
     HIPCHK(hipMemsetAsync(bsize + nb, 0, 8, st));
     HIPCHK(hipMemsetAsync(piece + pb, 0, 192, st));
     HIPCHK(hipStreamSynchronize(st));
+    if (spilled && pb > 0) SVXCHK(bs_piece_stage(S, stage_bytes, st));                  // the runs' byte ranges read back; the piece's segments point into the staging buffer
     double t[7]; t[0] = bs_now();
     if (pb > 0) {
         const BsSegs G{S->soff.as<int64_t>(), S->saddr.as<uint64_t>(), S->n + 1};
@@ -416,6 +686,9 @@ int bamsort_permutation(BamSort* S, uint32_t* host_perm, hipStream_t st) {
     if (!S || !S->finished) return svx_fail(SVX_E_STATE, "svx_bam_sort_permutation before svx_bam_sort_finish", __FILE__, __LINE__, hipSuccess);
     if (host_perm && S->n > 0) SVXCHK(svx_d2h(host_perm, S->perm.p, (size_t)S->n * 4, st));
     return SVX_OK;
+}
+void bamsort_spill_stats(const BamSort* S, svx_bam_sort_spill_stats* out) {
+    if (S) *out = S->sp; else memset(out, 0, sizeof *out);
 }
 void bamsort_stats(const BamSort* S, svx_bam_sort_stats* out) {
     if (S) *out = S->stats; else memset(out, 0, sizeof *out);

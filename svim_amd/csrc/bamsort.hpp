@@ -10,10 +10,12 @@ struct BamSortChunk {
     long long n; const uint8_t* stream; uint64_t first_byte, end_byte; const uint64_t* rec_off;
     const int32_t *tid, *pos; const uint16_t* flag; const uint64_t* cigar_off; const uint32_t* cigar;
 };
-int  bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref);      // an empty arena (the state is made on first use); max_bytes 0: what the device has free
+// an empty arena (the state is made on first use); max_bytes 0: what the device has free.  spill_dir (may be null): the directory of the spill file - a chunk
+// that would pass the limit then closes a run (sorted, laid out, written to the file, slabs freed) instead of failing; SVX_E_ARG: not a writable directory
+int  bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir = nullptr);
 void bamsort_drop(BamSort* s);                                         // arena, rows and the encoder's buffers go back
 void bamsort_destroy(BamSort* s);
-// SVX_E_CAPACITY: the arena would pass max_bytes (nothing of the chunk is kept)
+// SVX_E_CAPACITY: the arena would pass max_bytes (nothing of the chunk is kept); with a spill directory only for a chunk that alone passes it.  SVX_E_IO: the spill file
 int  bamsort_append(BamSort* s, const BamSortChunk& c, hipStream_t st);
 // header: the rewritten header (host).  SVX_E_ARG / SVX_E_RANGE: a record the definition refuses; SVX_E_CAPACITY: more than 2^32 - 1 records
 int  bamsort_finish(BamSort* s, const uint8_t* header, int64_t header_bytes, hipStream_t st);
@@ -25,3 +27,4 @@ int  bamsort_fetch(BamSort* s, uint8_t* compressed_dst, uint8_t* stream_dst, hip
 int  bamsort_index(BamSort* s, BamIndex* ix, hipStream_t st);
 int  bamsort_permutation(BamSort* s, uint32_t* host_perm, hipStream_t st);
 void bamsort_stats(const BamSort* s, svx_bam_sort_stats* out);
+void bamsort_spill_stats(const BamSort* s, svx_bam_sort_spill_stats* out);

@@ -26,5 +26,27 @@ BSORT_FN uint64_t bsort_key(int32_t tid, int32_t pos, uint32_t flag, int32_t n_r
     return (t << 33) | ((uint64_t)(uint32_t)(pos + 1) << 1) | ((flag >> 4) & 1u);
 }
 BSORT_FN int bsort_key_bits(int32_t n_ref) { return 33 + bsort_tid_bits(n_ref); }
+// ---- the spilled sort: which of a run's records a piece of the output needs ----
+// Runs are consecutive ranges of the file, each sorted stably; the global order sorts the concatenation of the run-sorted keys stably, so a run's records keep
+// their in-run order in it: gpos[i], the global position of the run's i-th record, increases with i.  Hence the records of a run among ANY contiguous range
+// [p0, p1) of global positions are a contiguous in-run range [a, b): a = the first i with gpos[i] >= p0, b = the first i with gpos[i] >= p1 (an empty range
+// has a == b).  A piece reads one contiguous byte range per run from the spill file.
+// first i in [0, n] with g[i] >= x (n when there is none)
+BSORT_FN int64_t bsort_lower_bound(const uint32_t* g, int64_t n, int64_t x) {
+    int64_t a = 0, b = n;
+    while (a < b) { const int64_t m = a + ((b - a) >> 1); if ((int64_t)g[m] < x) a = m + 1; else b = m; }
+    return a;
+}
+BSORT_FN void bsort_piece_cut(const uint32_t* gpos_of_run, int64_t n_in_run, int64_t p0, int64_t p1, int64_t* a, int64_t* b) {
+    *a = bsort_lower_bound(gpos_of_run, n_in_run, p0);
+    *b = p1 > p0 ? bsort_lower_bound(gpos_of_run, n_in_run, p1) : *a;
+}
+// the run of place q in the concatenation of the runs: run_base has n_runs + 1 entries, run_base[0] = 0, non-decreasing (an empty run has equal neighbours);
+// the largest r with run_base[r] <= q, which skips empty runs in front of q
+BSORT_FN int64_t bsort_run_of(const int64_t* run_base, int64_t n_runs, int64_t q) {
+    int64_t a = 0, b = n_runs;
+    while (b - a > 1) { const int64_t m = a + ((b - a) >> 1); if (run_base[m] <= q) a = m; else b = m; }
+    return a;
+}
 // the status of a stream whose records showed the union `bad` of bsort_check: SVX_E_ARG (-3) before SVX_E_RANGE (-10)
 BSORT_FN int bsort_status(int bad) { return (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID)) ? -3 : (bad & BSORT_BAD_POS) ? -10 : 0; }

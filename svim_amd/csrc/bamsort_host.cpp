@@ -44,6 +44,106 @@ extern "C" int svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_
     return SVX_OK;
 }
 
+// The spilled sort as bamsort.hip does it, on the host: every run sorted stably and written to a run file, one stable sort over the run-sorted keys (ties: run,
+// then place in the run), and the stream written piece by piece, every piece from one contiguous byte range per run (bamsort_core.hpp: bsort_piece_cut) read
+// back into a staging buffer.  The stream has no header here: segment j is the record at global position j.
+extern "C" int svx_bam_sort_spill_host(const uint8_t* records, int64_t n_bytes, int32_t n_ref, const int64_t* run_ends, int64_t n_runs, int64_t piece_blocks, uint8_t* out,
+                                       uint32_t* perm, int64_t perm_cap, int64_t* n_records, svx_spill_write_fn write_fn, svx_spill_read_fn read_fn, void* user) {
+    if (n_bytes < 0 || n_ref < 0 || perm_cap < 0 || (n_bytes && !records) || !n_records || n_runs < 0 || (n_runs && !run_ends) || piece_blocks < 1 || (!write_fn) != (!read_fn)) return SVX_E_ARG;
+    *n_records = 0;
+    struct Row { uint64_t key; int64_t at; uint32_t len; };
+    std::vector<Row> rows;
+    int bad = 0;
+    for (int64_t p = 0; p < n_bytes;) {
+        if (n_bytes - p < 4) return SVX_E_ARG;
+        const uint32_t bs = rd32(records + p);
+        if (bs < BSORT_MIN_BLOCK_SIZE || (int64_t)bs > n_bytes - p - 4) return SVX_E_ARG;
+        const int32_t tid = (int32_t)rd32(records + p + 4), pos = (int32_t)rd32(records + p + 8);
+        const uint32_t flag = rd32(records + p + 16) >> 16;
+        bad |= bsort_check(tid, pos, bs, n_ref);
+        rows.push_back(Row{bsort_key(tid, pos, flag, n_ref), p, 4u + bs});
+        p += 4 + (int64_t)bs;
+    }
+    if (bad) return bsort_status(bad);
+    if (rows.size() > 0xffffffffull) return SVX_E_CAPACITY;
+    const int64_t n = (int64_t)rows.size();
+    *n_records = n;
+    if (perm && n > perm_cap) return SVX_E_CAPACITY;
+    for (int64_t r = 0; r < n_runs; r++)
+        if (run_ends[r] < (r ? run_ends[r - 1] : 0) || run_ends[r] > n) return SVX_E_ARG;
+    if ((n_runs ? run_ends[n_runs - 1] : 0) != n) return SVX_E_ARG;
+    // run formation: per place q of the concatenation of the runs its key, length, file index and offset in its run's stream; the streams go to the run file
+    std::vector<uint8_t> memory_file;
+    std::vector<int64_t> run_base((size_t)n_runs + 1, n), run_bytes((size_t)n_runs, 0), run_at((size_t)n_runs, 0), roff((size_t)n + 1, 0);
+    std::vector<uint64_t> rkey((size_t)n);
+    std::vector<uint32_t> rlen((size_t)n), rfile((size_t)n), order;
+    std::vector<uint8_t> buf;
+    int64_t file_bytes = 0;
+    for (int64_t r = 0; r < n_runs; r++) {
+        const int64_t first = r ? run_ends[r - 1] : 0, m = run_ends[r] - first;
+        run_base[(size_t)r] = first; run_at[(size_t)r] = file_bytes;
+        order.resize((size_t)m);
+        for (int64_t k = 0; k < m; k++) order[(size_t)k] = (uint32_t)k;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[(size_t)(first + a)].key < rows[(size_t)(first + b)].key; });
+        int64_t total = 0;
+        for (int64_t k = 0; k < m; k++) total += rows[(size_t)(first + order[(size_t)k])].len;
+        buf.resize((size_t)total);
+        int64_t at = 0;
+        for (int64_t k = 0; k < m; k++) {
+            const Row& w = rows[(size_t)(first + order[(size_t)k])];
+            rkey[(size_t)(first + k)] = w.key; rlen[(size_t)(first + k)] = w.len; rfile[(size_t)(first + k)] = (uint32_t)(first + order[(size_t)k]); roff[(size_t)(first + k)] = at;
+            memcpy(buf.data() + at, records + w.at, w.len);
+            at += w.len;
+        }
+        run_bytes[(size_t)r] = total;
+        if (write_fn) { if (total && write_fn(user, file_bytes, buf.data(), total) != total) return SVX_E_IO; }
+        else memory_file.insert(memory_file.end(), buf.begin(), buf.end());
+        file_bytes += total;
+    }
+    // the merge: places sorted stably by key; gpos the inverse
+    std::vector<uint32_t> gp((size_t)n), gpos((size_t)n), srun((size_t)n);
+    for (int64_t q = 0; q < n; q++) gp[(size_t)q] = (uint32_t)q;
+    std::stable_sort(gp.begin(), gp.end(), [&](uint32_t a, uint32_t b) { return rkey[a] < rkey[b]; });
+    std::vector<int64_t> soff((size_t)n + 1, 0);
+    for (int64_t j = 0; j < n; j++) {
+        const uint32_t q = gp[(size_t)j];
+        gpos[q] = (uint32_t)j; srun[(size_t)j] = (uint32_t)bsort_run_of(run_base.data(), n_runs, (int64_t)q);
+        soff[(size_t)j + 1] = soff[(size_t)j] + rlen[q];
+        if (perm) perm[j] = rfile[q];
+    }
+    if (!out) return SVX_OK;
+    // the pieces
+    const int64_t total = soff[(size_t)n], step = std::min<int64_t>(piece_blocks, total / BSORT_BLOCK + 1) * BSORT_BLOCK;
+    std::vector<uint8_t> stage;
+    std::vector<int64_t> stage_at((size_t)n_runs), cut0((size_t)n_runs);
+    for (int64_t lo = 0; lo < total; lo += step) {
+        const int64_t hi = lo + step < total ? lo + step : total;
+        // the segments that hold bytes lo and hi - 1: the largest j with soff[j] <= x
+        const int64_t j0 = (std::upper_bound(soff.begin(), soff.begin() + n, lo) - soff.begin()) - 1, j1 = (std::upper_bound(soff.begin(), soff.begin() + n, hi - 1) - soff.begin()) - 1;
+        int64_t at = 0;
+        for (int64_t r = 0; r < n_runs; r++) {
+            const int64_t base = run_base[(size_t)r], cnt = run_base[(size_t)r + 1] - base;
+            int64_t a, b;
+            bsort_piece_cut(gpos.data() + base, cnt, j0, j1 + 1, &a, &b);
+            const int64_t c0 = a < cnt ? roff[(size_t)(base + a)] : run_bytes[(size_t)r], c1 = b < cnt ? roff[(size_t)(base + b)] : run_bytes[(size_t)r];
+            stage_at[(size_t)r] = at; cut0[(size_t)r] = c0;
+            if (c1 <= c0) continue;
+            stage.resize((size_t)(at + c1 - c0));
+            if (read_fn) { if (read_fn(user, run_at[(size_t)r] + c0, stage.data() + at, c1 - c0) != c1 - c0) return SVX_E_IO; }
+            else memcpy(stage.data() + at, memory_file.data() + run_at[(size_t)r] + c0, (size_t)(c1 - c0));
+            at += c1 - c0;
+        }
+        for (int64_t j = j0; j <= j1; j++) {                                  // the bytes of segment j inside [lo, hi)
+            const uint32_t q = gp[(size_t)j], r = srun[(size_t)j];
+            const int64_t s0 = std::max<int64_t>(soff[(size_t)j], lo), s1 = std::min<int64_t>(soff[(size_t)j + 1], hi);
+            const int64_t src = stage_at[r] + (roff[q] - cut0[r]) + (s0 - soff[(size_t)j]);
+            if (src < 0 || src + (s1 - s0) > at) return SVX_E_STATE;           // (a cut that does not cover its records: internal error)
+            memcpy(out + s0, stage.data() + src, (size_t)(s1 - s0));
+        }
+    }
+    return SVX_OK;
+}
+
 // header: magic, l_text, text, n_ref, the reference dictionary (the inflated file up to its first record)
 extern "C" int svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out) {
     if (!header || n_bytes < 12 || cap < 0 || (cap && !out) || !n_out || memcmp(header, "BAM\1", 4) != 0) return SVX_E_ARG;

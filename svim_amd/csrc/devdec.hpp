@@ -50,7 +50,7 @@ void devdec_index_stats(const svx_devdec* d, svx_bam_index_stats* out);
 // rows of the records it hands to devdec_count (once per chunk, on the loader's stream); a load whose records pass max_bytes fails with SVX_E_CAPACITY and drops
 // the sort.  finish (header: the rewritten header): appending is over, the sorted order and the stream layout stay until drop or the next begin.  encode / fetch /
 // index / permutation need a finished sort; index leaves its bytes where devdec_index_bytes / devdec_index_fetch read them.
-int  devdec_sort_begin(svx_devdec* d, int64_t max_bytes);
+int  devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir /* null: no spill file, SVX_E_CAPACITY at the limit */);
 void devdec_sort_drop(svx_devdec* d);
 bool devdec_sort_on(const svx_devdec* d);               // appending
 bool devdec_sort_finished(const svx_devdec* d);
@@ -61,3 +61,4 @@ int  devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_d
 int  devdec_sort_index(svx_devdec* d);
 int  devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm);
 void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out);
+void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out);

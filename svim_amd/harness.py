@@ -760,11 +760,13 @@ def index_bam(path, device=0, out=None, threads=0, batch_records=200_000):
     return data
 
 
-def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000):
+def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None):
     """The BAM file (or the SAM text: NativeBam tells them apart) at `path`, in any order, written to `out` in coordinate order (svim_amd/bamsort.py says what the sorted file is), and its index to
     out + ".bai" when `index`: one pass of the device reader whose batches are read and discarded while every record stays on the device, a sort there, then
     the file encoded and written in pieces of piece_blocks BGZF blocks - the whole file is never held in host memory (NativeBam.sort_*).  max_bytes: the most
-    the records may take on the device (0: what is free).  -> the sort's stats.  On failure the partial output is removed and the sort given up;
+    the records may take on the device (0: what is free).  spill_dir: a directory for the spill file of a file whose records pass that limit (runs are
+    written there and merged: the same bytes; the file is unlinked while it is open, nothing is left behind) - None: such a file raises with SVX_E_CAPACITY.
+    -> the sort's stats, the spill's under "spill".  On failure the partial output is removed and the sort given up;
     svim_amd.bamsort.BamSortError carries the library's status in .code."""
     from .bamio import NativeBam
     if piece_blocks < 1:
@@ -773,7 +775,7 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
     written = []
     try:
         bam.set_device_decode(int(device))
-        bam.sort_begin(max_bytes)
+        bam.sort_begin(max_bytes, spill_dir)
         try:
             while bam.read_batch(batch_records, 0, "coordinate")[1]:
                 pass
@@ -788,6 +790,7 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
                 with open(out + ".bai", "wb") as fh:
                     fh.write(data)
             stats = bam.sort_stats()
+            stats["spill"] = bam.sort_spill_stats()
             if bam.is_sam:
                 stats["sam"] = bam.sam_stats()
         except BaseException:
@@ -805,10 +808,10 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
     return stats
 
 
-def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000):
+def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None):
     """SAM text at `sam` -> a BAM file at `out_bam`: the reference's `samtools view -b | samtools sort` and `samtools index` (src/svim/SVIM_alignment.py).
     sort=True: one pass of the device reader, coordinate order and, with `index`, out_bam + ".bai" (sort_bam does it: svim_amd/sam.py says what the records are,
-    svim_amd/bamsort.py what the sorted file is) -> the sort's stats with the front end's under "sam".
+    svim_amd/bamsort.py what the sorted file is; spill_dir as there) -> the sort's stats with the front end's under "sam".
     sort=False: the records in file order under the header the text has; no index - a file in file order has none.  This route is the HOST's: the host build
     of the converter (svx_sam_convert_host) and of the encoder (svx_text_gz_host) write the bytes the device builds write, the file is held in host memory
     once, and `device` and the sort's limits play no part -> {"n_records", "text_bytes", "stream_bytes"}."""
@@ -817,7 +820,7 @@ def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096,
     if not is_sam_text(sam):
         raise ValueError("sam_to_bam: %r is not SAM text" % sam)
     if sort:
-        return sort_bam(sam, out_bam, device=device, index=index, piece_blocks=piece_blocks, max_bytes=max_bytes, threads=threads, batch_records=batch_records)
+        return sort_bam(sam, out_bam, device=device, index=index, piece_blocks=piece_blocks, max_bytes=max_bytes, threads=threads, batch_records=batch_records, spill_dir=spill_dir)
     if index:
         raise ValueError("sam_to_bam: index=True needs sort=True (records in file order have no index)")
     with open(sam, "rb") as fh:

@@ -9,7 +9,15 @@ piece.  Reported: the reader's rate with the sort off and on (median of the warm
 against twice its bytes over the rate of a plain device-to-device copy of the same size measured here, the encoder's phases and rate, the share of stored
 blocks, and the compressed size against zlib level 1 over the same 65 280-byte blocks (on the first --zlib-blocks blocks).  --qual: the file carries seeded
 base qualities (the encoder's hard case) instead of none.  --check: the stream and the file against the definition (svim_amd.bamsort, in Python: slow on a
-large file).  One JSON line is appended to --out."""
+large file).  One JSON line is appended to --out.
+
+    python tools/bam_sort_rate.py --spill-dir DIR [--spill-split 64] [--records ...] [--qual]
+
+The spilled sort (svx_bam_sort_begin_spill) instead: the same file, read in at least --spill-split chunks, sorted whole - pass, finish, every piece encoded,
+index - three ways: in memory, with max_bytes = arena / 4 and with max_bytes = arena / 16 (never below the largest chunk), runs written to a spill file in DIR.
+One warm-up of each, then the three interleaved --passes times; the median of each.  The line holds the three rates, t_spill_ms, t_readback_ms, t_merge_ms,
+the spill file's write and read bytes per second (bytes over the time spent in the phase that moves them: gather and copy out included in the write, copy in
+included in the read), max_stage_bytes, and whether the three files are the same bytes.  Disk speed belongs to the box: recorded figures, no thresholds."""
 import argparse
 import json
 import os
@@ -78,6 +86,62 @@ def copy_rate(n_bytes, reps=5):
     return n_bytes / statistics.median(times)
 
 
+def full_sort(nb, max_bytes, spill_dir, piece_blocks):
+    """rewind, pass, finish, encode every piece, index -> (seconds, sha of the file and the index, stats, spill stats)"""
+    import hashlib
+    t = time.perf_counter()
+    nb.rewind()
+    nb.sort_begin(max_bytes, spill_dir)
+    while nb.read_batch(30000, 20, "coordinate")[1]:
+        pass
+    _, _, n_blocks = nb.sort_finish()
+    h = hashlib.sha256()
+    for first in range(0, n_blocks, piece_blocks):
+        h.update(nb.sort_encode(first, min(piece_blocks, n_blocks - first)))
+    h.update(nb.sort_index())
+    dt = time.perf_counter() - t
+    st, sp = nb.sort_stats(), nb.sort_spill_stats()
+    nb.sort_abort()
+    return dt, h.hexdigest(), st, sp
+
+
+def spill_main(a, shuffled, nrec, raw):
+    n_file_blocks = -(-raw // 0xff00)
+    os.environ["SVX_BAM_DEV_CHUNK_BLOCKS"] = str(max(1, n_file_blocks // a.spill_split))
+    nb = NativeBam(shuffled)
+    nb.set_device_decode(0)
+    while nb.read_batch(30000, 20, "coordinate")[1]:
+        pass
+    _, _, st, sp = full_sort(nb, 0, None, a.piece_blocks)
+    arena, max_chunk = st["arena_bytes"], sp["max_chunk_bytes"]
+    ways = [("in_memory", 0, None), ("arena_4", max(max_chunk, arena // 4), a.spill_dir), ("arena_16", max(max_chunk, arena // 16), a.spill_dir)]
+    for _, mb, d in ways:
+        full_sort(nb, mb, d, a.piece_blocks)                                   # warm-up of each way
+    times, last, shas = {w[0]: [] for w in ways}, {}, {}
+    for _ in range(a.passes):
+        for name, mb, d in ways:
+            dt, sha, st, sp = full_sort(nb, mb, d, a.piece_blocks)
+            times[name].append(dt)
+            last[name], shas[name] = (st, sp), sha
+    nb.close()
+    line = {"tool": "bam_sort_rate", "mode": "spill", "records": nrec, "inflated_bytes": raw, "qualities": bool(a.qual), "passes": a.passes, "piece_blocks": a.piece_blocks,
+            "spill_split": a.spill_split, "arena_bytes": arena, "max_chunk_bytes": max_chunk, "same_bytes_three_ways": len(set(shas.values())) == 1}
+    for name, mb, _ in ways:
+        st, sp = last[name]
+        m = statistics.median(times[name])
+        line[name] = {"max_bytes": mb, "sort_s": times[name], "sort_s_median": m, "records_per_s": nrec / m, "stream_bytes_per_s": st["stream_bytes"] / m, "n_runs": sp["n_runs"],
+                      "t_spill_ms": sp["t_spill_ms"], "t_readback_ms": sp["t_readback_ms"], "t_merge_ms": sp["t_merge_ms"], "max_stage_bytes": sp["max_stage_bytes"],
+                      "spilled_bytes": sp["spilled_bytes"], "readback_bytes": sp["readback_bytes"],
+                      "spill_write_bytes_per_s": sp["spilled_bytes"] / (sp["t_spill_ms"] * 1e-3) if sp["t_spill_ms"] else None,
+                      "spill_read_bytes_per_s": sp["readback_bytes"] / (sp["t_readback_ms"] * 1e-3) if sp["t_readback_ms"] else None,
+                      "t_append_ms": st["t_append_ms"], "t_finish_ms": st["t_finish_ms"], "t_encode_ms": st["t_encode_ms"], "t_gather_ms": st["t_gather_ms"]}
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "a") as fh:
+        fh.write(json.dumps(line) + "\n")
+    print(json.dumps(line))
+    os.remove(shuffled)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--records", type=int, default=20000)
@@ -87,6 +151,8 @@ def main():
     ap.add_argument("--zlib-blocks", type=int, default=2000)
     ap.add_argument("--qual", action="store_true")
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--spill-dir", default=None, help="measure the spilled sort instead, its spill file in this directory")
+    ap.add_argument("--spill-split", type=int, default=64, help="with --spill-dir: the file is read in at least this many chunks")
     ap.add_argument("--path", default="/tmp/device_reader.bam")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "bam_sort_rates.jsonl"))
     a = ap.parse_args()
@@ -99,6 +165,8 @@ def main():
     shuffled = a.path + ".shuffled.bam"
     nrec, raw = shuffle_file(a.path, shuffled, 3)
     size = os.path.getsize(shuffled)
+    if a.spill_dir:
+        return spill_main(a, shuffled, nrec, raw)
     os.environ["SVX_BAM_DEV_CHUNK_MB"] = str(a.chunk_mb)
     nb = NativeBam(shuffled)
     nb.set_device_decode(0)

@@ -120,7 +120,7 @@ bool devdec_index_bytes(const svx_devdec*, int64_t*) { return false; }
 int devdec_index_fetch(svx_devdec*, uint8_t*) { return SVX_E_STATE; }
 void devdec_index_stats(const svx_devdec*, svx_bam_index_stats* out) { memset(out, 0, sizeof *out); }
 // (so is the coordinate sort; the header rewrite it asks the host for lives in bamsort_host.cpp, which this program does not link)
-int devdec_sort_begin(svx_devdec*, int64_t) { return SVX_E_STATE; }
+int devdec_sort_begin(svx_devdec*, int64_t, const char*) { return SVX_E_STATE; }
 void devdec_sort_drop(svx_devdec*) {}
 bool devdec_sort_on(const svx_devdec*) { return false; }
 bool devdec_sort_finished(const svx_devdec*) { return false; }
@@ -131,6 +131,7 @@ int devdec_sort_fetch(svx_devdec*, uint8_t*, uint8_t*) { return SVX_E_STATE; }
 int devdec_sort_index(svx_devdec*) { return SVX_E_STATE; }
 int devdec_sort_permutation(svx_devdec*, uint32_t*) { return SVX_E_STATE; }
 void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
+void devdec_sort_spill_stats(const svx_devdec*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
 extern "C" int svx_bam_sort_header_host(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
 // SAM text (svx_sam_open): the front end is the device's (sam.hip) and the header parser sam_host.cpp's; neither is part of this program
 int devdec_load_text(svx_devdec*, int, const uint8_t*, size_t, bool, int, int, int64_t, uint64_t*, int64_t*) { return SVX_E_STATE; }
