@@ -497,6 +497,15 @@ int  svx_text_index_get_stats(svx_ctx* ctx, svx_text_index_stats* out);
  * *n_out is the size also when cap is too small (SVX_E_CAPACITY).  SVX_E_ORDER / SVX_E_RANGE: the file has no index. */
 int  svx_text_index_host(const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
                          uint8_t* out, int64_t cap, int64_t* n_out);
+/* The format of an index is an argument: SVX_INDEX_CLASSIC is the five-level .tbi / .bai, which ends at 2^29; SVX_INDEX_CSI is the .csi of the same rows (the
+ * definition in words: svim_amd/csi.py): min_shift 14, a depth chosen per file from its largest end (5 .. 9), a loffset per bin in place of the linear index.
+ * svx_text_index_fmt(.., SVX_INDEX_CLASSIC) is svx_text_index; with SVX_INDEX_CSI a file's status is 0 or SVX_E_ORDER, never SVX_E_RANGE.  count / fetch /
+ * get_stats serve whichever was built last; the fetched bytes are uncompressed (a .csi on disk is BGZF-framed, as a .tbi is).  Any other fmt: SVX_E_ARG. */
+enum { SVX_INDEX_CLASSIC = 0, SVX_INDEX_CSI = 1 };
+int  svx_text_index_fmt(svx_ctx* ctx, int preset, const int64_t* stream_base, int fmt);
+/* host-only: the uncompressed .csi of one file; arguments and results of svx_text_index_host, without SVX_E_RANGE */
+int  svx_text_index_csi_host(const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
+                             uint8_t* out, int64_t cap, int64_t* n_out);
 
 /* ---- GENOTYPE: replaces the per-candidate BAM re-fetch of genotype() (src/svim/SVIM_genotyping.py:34-93) --------
  * by an interval join over the alignment records, resident in HBM.  Records are in file order of a coordinate-sorted BAM
@@ -677,6 +686,15 @@ int  svx_bam_index_get_stats(svx_bam* h, svx_bam_index_stats* out);
  * cap is too small (SVX_E_CAPACITY).  SVX_E_ORDER / SVX_E_RANGE: the file has no index; SVX_E_ARG: a tid beyond n_ref. */
 int  svx_bam_index_host(int32_t n_ref, int64_t n_rows, const int32_t* tid, const int32_t* pos, const int64_t* end, const uint16_t* flag, const uint64_t* vbeg,
                         uint64_t v_end, uint8_t* out, int64_t cap, int64_t* n_out);
+/* The same index in the format asked for (SVX_INDEX_CLASSIC / SVX_INDEX_CSI, above; any other: SVX_E_ARG, the pass stays on): svx_bam_index_finish(h) is
+ * svx_bam_index_finish_fmt(h, SVX_INDEX_CLASSIC) and svx_bam_sort_index(h) is svx_bam_sort_index_fmt(h, SVX_INDEX_CLASSIC).  A .csi has no SVX_E_RANGE: a BAM
+ * coordinate never needs more than depth 7.  count / fetch serve whichever was built last; the bytes of a .csi are uncompressed (the file on disk is these
+ * bytes BGZF-framed). */
+int  svx_bam_index_finish_fmt(svx_bam* h, int fmt);
+int  svx_bam_sort_index_fmt(svx_bam* h, int fmt);
+/* host-only: the uncompressed .csi of a row table; arguments and results of svx_bam_index_host, without SVX_E_RANGE */
+int  svx_bam_index_csi_host(int32_t n_ref, int64_t n_rows, const int32_t* tid, const int32_t* pos, const int64_t* end, const uint16_t* flag, const uint64_t* vbeg,
+                            uint64_t v_end, uint8_t* out, int64_t cap, int64_t* n_out);
 
 /* ---- coordinate sort of the file the device reader is reading (bamsort.hip, bamsort_core.hpp; the definition in words: svim_amd/bamsort.py) ----
  * The sorted file: the header with SO:coordinate, every record verbatim in the order of (uint32(refID), uint32(pos + 1), flag & 16), equal keys in file order,

@@ -413,7 +413,7 @@ _VCF_PIECE = 64 << 20
 
 def _position_order(options):
     """options.position_order, or an index asked for (options.bgzip_output and options.tabix_index): tabix needs the order"""
-    return bool(getattr(options, "position_order", False)) or (bool(getattr(options, "bgzip_output", False)) and bool(getattr(options, "tabix_index", False)))
+    return bool(getattr(options, "position_order", False)) or (bool(getattr(options, "bgzip_output", False)) and (bool(getattr(options, "tabix_index", False)) or bool(getattr(options, "csi_index", False))))
 
 
 def _write_tbi(path, index_bytes):
@@ -470,16 +470,17 @@ def write_final_vcf(int_duplication_candidates, inversion_candidates, tandem_dup
     lists6 = (int_duplication_candidates, inversion_candidates, tandem_duplication_candidates, deletion_candidates, novel_insertion_candidates,
               breakend_candidates)
     bgzip = bool(getattr(options, "bgzip_output", False))      # (not an option of the reference: variants.vcf.gz, BGZF made on the device)
+    csi = bgzip and bool(getattr(options, "csi_index", False))      # variants.vcf.gz.csi (svim_amd/csi.py): contigs beyond 2^29; beside or instead of the .tbi
     tbi = bgzip and bool(getattr(options, "tabix_index", False))
     path = options.working_dir + ("/variants.vcf.gz" if bgzip else "/variants.vcf")
 
     def index(eng, base):
-        if tbi:
-            eng.text_index(_abi.INDEX_VCF, base)
+        for fmt in [f for f, wanted in (("tbi", tbi), ("csi", csi)) if wanted]:
+            eng.text_index(_abi.INDEX_VCF, base, fmt=fmt)
             blobs, status = eng.text_index_fetch()
             if status[0] != 0:
                 raise _lib.SvxError("variants.vcf.gz cannot be indexed: %s" % _abi.ERRORS.get(int(status[0]), int(status[0])))
-            _write_tbi(path + ".tbi", blobs[0])
+            _write_tbi(path + "." + fmt, blobs[0])
     with open(path, "wb") as out:
         head = ("\n".join(vcf_header(version, contig_names, contig_lengths, types_to_output, options)) + "\n").encode("utf-8")
         if bgzip:

@@ -222,6 +222,24 @@ class TextGzStats(C.Structure):
 
 # tabix index (include/svx.h: svx_text_index*): presets, and the status of a file that has none
 INDEX_VCF, INDEX_BED = 0, 1
+# the format of an index (SVX_INDEX_CLASSIC: .bai / .tbi, SVX_INDEX_CSI: .csi, svim_amd/csi.py)
+INDEX_CLASSIC, INDEX_CSI = 0, 1
+CSI_MIN_REFERENCE = 1 << 29      # "auto": a .csi exactly when a reference of the header is longer than this, the rule samtools users know
+
+
+def index_format(fmt, classic):
+    """`classic` (the name of the five-level index of this kind of file: "bai" for a BAM, "tbi" for a text) or "csi", or a number the library is to
+    judge -> the library's constant.  The other kind's name is refused: a BAM has no .tbi, a text no .bai"""
+    if isinstance(fmt, str):
+        if fmt not in (classic, "csi"):
+            raise ValueError("unknown index format %r (%s, csi)" % (fmt, classic))
+        return INDEX_CSI if fmt == "csi" else INDEX_CLASSIC
+    return int(fmt)
+
+
+def auto_index_format(lengths, classic):
+    """"auto" resolved before the pass: "csi" when a reference length exceeds 2^29, else `classic` ("bai" / "tbi")"""
+    return "csi" if any(int(n) > CSI_MIN_REFERENCE for n in lengths) else classic
 
 
 class TextIndexStats(C.Structure):

@@ -34,6 +34,7 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats",
            "svx_text_gz", "svx_text_gz_count", "svx_text_gz_fetch", "svx_text_gz_get_stats", "svx_text_gz_host",
            "svx_vcf_position_order", "svx_text_index", "svx_text_index_count", "svx_text_index_fetch", "svx_text_index_get_stats", "svx_text_index_host",
+           "svx_text_index_fmt", "svx_text_index_csi_host", "svx_bam_index_finish_fmt", "svx_bam_sort_index_fmt", "svx_bam_index_csi_host",
            "svx_bam_index_begin", "svx_bam_index_finish", "svx_bam_index_abort", "svx_bam_index_count", "svx_bam_index_fetch", "svx_bam_index_get_stats", "svx_bam_index_host",
            "svx_bam_sort_begin", "svx_bam_sort_finish", "svx_bam_sort_abort", "svx_bam_sort_count", "svx_bam_sort_encode", "svx_bam_sort_fetch", "svx_bam_sort_index",
            "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host", "svx_bam_sort_begin_spill", "svx_bam_sort_get_spill_stats",
@@ -138,10 +139,12 @@ def text_gz_host(data):
     return out[:n.value].tobytes()
 
 
-def text_index_host(text, block_coff, block_uoff, preset, stream_base=0):
+def text_index_host(text, block_coff, block_uoff, preset, stream_base=0, fmt="tbi"):
     """svx_text_index_host (host-only, no GPU needed): the uncompressed .tbi bytes of one file by the host build of csrc/textindex_core.hpp - the bytes
     Engine.text_index makes of the same text and block table on the device, and svim_amd.tabix.build_index by the definition.  block_coff / block_uoff:
-    n_blocks + 1 entries each, the last block the end-of-file block.  svim_amd.tabix.TabixError (code E_ORDER / E_RANGE) for a text that has no index."""
+    n_blocks + 1 entries each, the last block the end-of-file block.  svim_amd.tabix.TabixError (code E_ORDER / E_RANGE) for a text that has no index.
+    fmt="csi": svx_text_index_csi_host, the uncompressed .csi bytes (svim_amd.csi.build_text_index by the definition)."""
+    fn = lib().svx_text_index_csi_host if _abi.index_format(fmt, "tbi") == _abi.INDEX_CSI else lib().svx_text_index_host
     from . import tabix
     text = bytes(text)
     co, uo = np.ascontiguousarray(block_coff, dtype=np.int64), np.ascontiguousarray(block_uoff, dtype=np.int64)
@@ -151,7 +154,7 @@ def text_index_host(text, block_coff, block_uoff, preset, stream_base=0):
     n, cap = C.c_int64(), 0
     for _ in range(2):
         out = np.zeros(max(1, cap), dtype=np.uint8)
-        rc = lib().svx_text_index_host(ptr(src), C.c_int64(len(text)), ptr(co), ptr(uo), C.c_int64(co.size - 1), C.c_int(preset), C.c_int64(stream_base), ptr(out),
+        rc = fn(ptr(src), C.c_int64(len(text)), ptr(co), ptr(uo), C.c_int64(co.size - 1), C.c_int(preset), C.c_int64(stream_base), ptr(out),
                                        C.c_int64(cap), C.byref(n))
         if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE):
             raise tabix.TabixError(rc, "text_index_host: " + _abi.ERRORS[rc])
@@ -163,10 +166,12 @@ def text_index_host(text, block_coff, block_uoff, preset, stream_base=0):
     return out[:n.value].tobytes()
 
 
-def bam_index_host(n_ref, rows, v_end):
+def bam_index_host(n_ref, rows, v_end, fmt="bai"):
     """svx_bam_index_host (host-only, no GPU needed): the .bai bytes of a row table by the host build of csrc/bamindex_core.hpp - the bytes NativeBam.index_finish
     makes of the same file on the device, and svim_amd.bai.build_index by the definition.  rows: (tid, pos, end, flag, vbeg) per record, as bai.rows_of_bam lists
-    them, or the five columns as arrays.  svim_amd.bai.BaiError (code E_ORDER / E_RANGE) for a file that has no index."""
+    them, or the five columns as arrays.  svim_amd.bai.BaiError (code E_ORDER / E_RANGE) for a file that has no index.
+    fmt="csi": svx_bam_index_csi_host, the uncompressed .csi bytes (svim_amd.csi.build_bam_index by the definition)."""
+    fn = lib().svx_bam_index_csi_host if _abi.index_format(fmt, "bai") == _abi.INDEX_CSI else lib().svx_bam_index_host
     from . import bai
     if isinstance(rows, (tuple, list)) and len(rows) == 5 and all(isinstance(c, np.ndarray) for c in rows):
         cols = rows
@@ -179,7 +184,7 @@ def bam_index_host(n_ref, rows, v_end):
     n, cap = C.c_int64(), 0
     for _ in range(2):
         out = np.zeros(max(1, cap), dtype=np.uint8)
-        rc = lib().svx_bam_index_host(C.c_int32(int(n_ref)), C.c_int64(n_rows), *[ptr(c) for c in cols], C.c_uint64(int(v_end)), ptr(out), C.c_int64(cap), C.byref(n))
+        rc = fn(C.c_int32(int(n_ref)), C.c_int64(n_rows), *[ptr(c) for c in cols], C.c_uint64(int(v_end)), ptr(out), C.c_int64(cap), C.byref(n))
         if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE):
             raise bai.BaiError(rc, "bam_index_host: " + _abi.ERRORS[rc])
         if rc != _abi.SVX_E_CAPACITY:
@@ -740,17 +745,21 @@ class Engine(object):
         return s.as_dict()
 
     # ---- tabix index of the BGZF stream ----
-    def text_index(self, preset, stream_base=None):
+    def text_index(self, preset, stream_base=None, fmt="tbi"):
         """svx_text_index: the uncompressed .tbi bytes of every file of the last text_gz() call, built on the device from its text and block table.
         preset: _abi.INDEX_VCF / INDEX_BED; stream_base: per file, the bytes written in front of its stream in its .gz file (a header compressed on the host;
-        None: 0; a number: one file).  -> (number of files, bytes); text_index_fetch() brings them over.  Void whenever the stream is."""
+        None: 0; a number: one file).  -> (number of files, bytes); text_index_fetch() brings them over.  Void whenever the stream is.
+        fmt="csi": the uncompressed .csi bytes (svx_text_index_fmt; svim_amd/csi.py): no file is out of range in that format."""
         nf = self.text_gz_count()[0]
         sb = None
         if stream_base is not None:
             sb = np.ascontiguousarray(np.atleast_1d(stream_base), dtype=np.int64)
             if sb.size != nf:
                 raise ValueError("text_index: stream_base needs one entry per file (%d)" % nf)
-        _check(self.L.svx_text_index(self.ctx, C.c_int(preset), ptr(sb) if sb is not None else None), "svx_text_index")
+        if fmt == "tbi":
+            _check(self.L.svx_text_index(self.ctx, C.c_int(preset), ptr(sb) if sb is not None else None), "svx_text_index")
+        else:
+            _check(self.L.svx_text_index_fmt(self.ctx, C.c_int(preset), ptr(sb) if sb is not None else None, C.c_int(_abi.index_format(fmt, "tbi"))), "svx_text_index_fmt")
         return self.text_index_count()
 
     def text_index_count(self):

@@ -105,10 +105,14 @@ class NativeBam(object):
         if rc != 0:
             raise self._index_error(rc, "svx_bam_index_begin")
 
-    def index_finish(self):
+    def index_finish(self, fmt="bai"):
         """-> the bytes of the .bai (svim_amd/bai.py says what they hold), once read_batch has returned 0 records at the end of the file
-        (svx_bam_index_finish).  svim_amd.bai.BaiError for a file that has no index (not in coordinate order, a record beyond 2^29): the handle stays usable"""
-        rc = self.L.svx_bam_index_finish(self.h)
+        (svx_bam_index_finish).  svim_amd.bai.BaiError for a file that has no index (not in coordinate order, a record beyond 2^29): the handle stays usable.
+        fmt="csi": the uncompressed bytes of the .csi (svim_amd/csi.py; svx_bam_index_finish_fmt), which has no limit at 2^29"""
+        if fmt == "bai":
+            rc = self.L.svx_bam_index_finish(self.h)
+        else:
+            rc = self.L.svx_bam_index_finish_fmt(self.h, C.c_int(_abi.index_format(fmt, "bai")))
         if rc != 0:
             raise self._index_error(rc, "svx_bam_index_finish")
         return self.index_bytes()
@@ -190,10 +194,13 @@ class NativeBam(object):
             raise self._sort_error(rc, "svx_bam_sort_fetch")
         return (out[:n.value].tobytes(), raw[:nraw].tobytes()) if stream else out[:n.value].tobytes()
 
-    def sort_index(self):
+    def sort_index(self, fmt="bai"):
         """-> the bytes of the sorted file's .bai, after every block has been encoded (svx_bam_sort_index); svim_amd.bai.BaiError (E_RANGE) when a record
-        ends beyond 2^29"""
-        rc = self.L.svx_bam_sort_index(self.h)
+        ends beyond 2^29.  fmt="csi": the uncompressed bytes of its .csi (svx_bam_sort_index_fmt), which has no such limit"""
+        if fmt == "bai":
+            rc = self.L.svx_bam_sort_index(self.h)
+        else:
+            rc = self.L.svx_bam_sort_index_fmt(self.h, C.c_int(_abi.index_format(fmt, "bai")))
         if rc != 0:
             raise (self._index_error if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE) else self._sort_error)(rc, "svx_bam_sort_index")
         return self.index_bytes()

@@ -267,11 +267,12 @@ def file_texts(eng, piece=_PIECE):
     return [text[int(off[k]):int(off[k + 1])] for k in range(len(off) - 1)]
 
 
-def write_files(eng, directory, names, heads=None, piece=_PIECE, compress=False, index=None):
+def write_files(eng, directory, names, heads=None, piece=_PIECE, compress=False, index=None, index_format="tbi"):
     """the files of the engine's last bed() call into `directory` under `names` (heads: bytes written in front of each), fetched in pieces.
     compress: every name with .gz appended, the text compressed to BGZF on the device (svx_text_gz) and only the streams fetched; a head is compressed here.
     index (_abi.INDEX_BED / INDEX_VCF, with compress): name + ".gz.tbi" for every file whose lines tabix takes as they are (svx_text_index; nothing is
-    re-sorted) -> the names of the files that got none (logged once each); [] without index"""
+    re-sorted) -> the names of the files that got none (logged once each); [] without index.  index_format="csi": name + ".gz.csi" instead (svim_amd/csi.py),
+    which no coordinate is too large for"""
     off, _ = eng.bed_file_offsets()
     if len(off) - 1 != len(names):
         raise ValueError("%d files in the text, %d names" % (len(off) - 1, len(names)))
@@ -289,11 +290,11 @@ def write_files(eng, directory, names, heads=None, piece=_PIECE, compress=False,
         missing = []
         if index is not None:
             from .SVIM_COMBINE import _write_tbi
-            eng.text_index(index, [len(h) for h in zheads])
+            eng.text_index(index, [len(h) for h in zheads], fmt=index_format)
             blobs, status = eng.text_index_fetch()
             for k, name in enumerate(names):
                 if status[k] == 0:
-                    _write_tbi(os.path.join(directory, name + ".gz.tbi"), blobs[k])
+                    _write_tbi(os.path.join(directory, name + ".gz." + index_format), blobs[k])
                 else:
                     logging.warning("%s.gz gets no tabix index: %s" % (name, _abi.ERRORS.get(int(status[k]), int(status[k]))))
                     missing.append(name)

@@ -994,11 +994,11 @@ int devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_ds
     HIPCHK(hipSetDevice(d->device));
     return bamsort_fetch(d->sort, compressed_dst, stream_dst, d->stream);
 }
-int devdec_sort_index(svx_devdec* d) {
+int devdec_sort_index(svx_devdec* d, int fmt) {
     HIPCHK(hipSetDevice(d->device));
     if (d->index_on) return svx_fail(SVX_E_STATE, "svx_bam_sort_index while a BAM index pass is on", __FILE__, __LINE__, hipSuccess);
     SVXCHK(bamindex_begin(&d->index));
-    const int rc = bamsort_index(d->sort, d->index, d->stream);
+    const int rc = bamsort_index(d->sort, d->index, d->stream, fmt);
     bamindex_drop(d->index);                                // (the table's memory goes back; the bytes of a finished index stay)
     return rc;
 }
@@ -1022,9 +1022,9 @@ void devdec_index_drop(svx_devdec* d) {
     bamindex_drop(d->index);
 }
 bool devdec_index_on(const svx_devdec* d) { return d->index_on; }
-int devdec_index_finish(svx_devdec* d, uint64_t v_end) {
+int devdec_index_finish(svx_devdec* d, uint64_t v_end, int fmt) {
     HIPCHK(hipSetDevice(d->device));
-    const int rc = bamindex_finish(d->index, d->n_ref, v_end, d->stream);
+    const int rc = bamindex_finish(d->index, d->n_ref, v_end, d->stream, fmt);
     devdec_index_drop(d);
     return rc;
 }

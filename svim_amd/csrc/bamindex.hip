@@ -19,6 +19,9 @@
 //   serialise  one lane per chunk and one wave per reference store every field at its offset; the wave's backward fill of the empty slots is a reverse scan
 //              in tiles of 64.  Header and trailer come from the host.
 // Every store into the index is checked against the index's size: a layout that disagrees with its sizes is SVX_E_STATE, not a write somewhere else.
+// With fmt SVX_INDEX_CSI finish builds the uncompressed .csi of the same rows (svim_amd/csi.py): no range check; behind the references a segmented running
+// maximum of the ends (binidx_launch_run_max), whose last entry per reference gives the file's depth; chunk heads, keys and the sort at that depth; in place
+// of the linear phase one bisection of the running maximum per bin (k_binidx_bin_loff); the CSI serialisers.
 #include "common.hpp"
 #include "hostcopy.hpp"
 #include "scan.hpp"
@@ -97,13 +100,13 @@ __global__ void k_bix_end(long long n, BixCols T, const uint32_t* span) {
 
 // ---- finish ---------------------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ BinIdxInterval bix_row(const BixCols& T, long long i) { return bix_interval(T.pos[i], T.end[i]); }
-__global__ void k_bix_check(long long n, int32_t n_ref, BixCols T, int* err) {
+__global__ void k_bix_check(long long n, int32_t n_ref, BixCols T, int* err, int check_range) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int32_t t = T.tid[i];
     int e = t >= n_ref ? BIXF_TID : 0;
     if (i > 0 && bix_out_of_order(T.tid[i - 1], T.pos[i - 1], t, T.pos[i])) e |= BIXF_ORDER;
-    if (t >= 0 && bix_row(T, i).end > BINIDX_MAX_END) e |= BIXF_RANGE;
+    if (check_range && t >= 0 && bix_row(T, i).end > BINIDX_MAX_END) e |= BIXF_RANGE;
     if (e) atomicOr(err, e);
 }
 // first row of every reference, and of the unplaced tail (t = n_ref): the table is in order, a negative tid is the largest as an unsigned number
@@ -114,23 +117,29 @@ __global__ void k_bix_ref_first(long long n, const int32_t* tid, int32_t n_ref, 
     while (lo < hi) { const long long mid = (lo + hi) >> 1; if ((uint32_t)tid[mid] >= (uint32_t)t) hi = mid; else lo = mid + 1; }
     first[t] = lo;
 }
-__global__ void k_bix_heads(long long n_placed, BixCols T, int32_t* bhead, int32_t* umark) {
+// depth: 0 for the five-level bins of a .bai, the depth of the file for a .csi
+__device__ __forceinline__ uint32_t bix_bin(const BixCols& T, long long j, int depth) {
+    const BinIdxInterval v = bix_row(T, j);
+    return depth ? binidx_reg2bin_csi(v.beg, v.end, depth) : binidx_bin(v);
+}
+__global__ void k_bix_heads(long long n_placed, BixCols T, int32_t* bhead, int32_t* umark, int depth) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j > n_placed) return;
     if (j == n_placed) { bhead[j] = 0; umark[j] = 0; return; }
-    bhead[j] = (j == 0 || T.tid[j] != T.tid[j - 1] || binidx_bin(bix_row(T, j)) != binidx_bin(bix_row(T, j - 1))) ? 1 : 0;
+    bhead[j] = (j == 0 || T.tid[j] != T.tid[j - 1] || bix_bin(T, j, depth) != bix_bin(T, j - 1, depth)) ? 1 : 0;
     umark[j] = (T.flag[j] & 4u) ? 1 : 0;
 }
-__global__ void k_bix_chunks(long long n_placed, long long n_chunks, BixCols T, const int32_t* bhead, const int64_t* bpos, uint32_t* chunk_rec, uint64_t* key, uint32_t* val) {
+__global__ void k_bix_chunks(long long n_placed, long long n_chunks, BixCols T, const int32_t* bhead, const int64_t* bpos, uint32_t* chunk_rec, uint64_t* key, uint32_t* val, int depth) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j > n_placed) return;
     if (j == n_placed) { chunk_rec[n_chunks] = (uint32_t)n_placed; return; }
     const long long q = bpos[j];
-    if (bhead[j] && q < n_chunks) { chunk_rec[q] = (uint32_t)j; key[q] = binidx_key((uint64_t)(uint32_t)T.tid[j], binidx_bin(bix_row(T, j))); val[q] = (uint32_t)q; }
+    if (bhead[j] && q < n_chunks) { chunk_rec[q] = (uint32_t)j; key[q] = depth ? binidx_csi_key((uint64_t)(uint32_t)T.tid[j], bix_bin(T, j, depth), depth) : binidx_key((uint64_t)(uint32_t)T.tid[j], bix_bin(T, j, 0)); val[q] = (uint32_t)q; }
 }
 // the placed rows as binidx_kernels.hpp reads them: a group is a reference, every one of them gets bytes
 struct BixRows {
-    BixCols T; long long n_rows; uint64_t v_end; const int64_t *first_row, *upos, *toff;
+    BixCols T; long long n_rows; uint64_t v_end; const int64_t *first_row, *upos, *toff; int header_bytes, csi_depth;
+    __device__ int depth(long long) const { return csi_depth; }
     __device__ long long group(long long j) const { return T.tid[j]; }
     __device__ bool live(long long) const { return true; }
     __device__ BinIdxInterval interval(long long j) const { return bix_row(T, j); }
@@ -139,7 +148,7 @@ struct BixRows {
     __device__ bool group_live(long long) const { return true; }
     __device__ long long first(long long t) const { return first_row[t]; }
     __device__ long long last(long long t) const { return first_row[t + 1]; }
-    __device__ long long part_off(long long t) const { return BIX_HEADER_BYTES + toff[t]; }
+    __device__ long long part_off(long long t) const { return header_bytes + toff[t]; }
     __device__ uint64_t n_unmapped(long long t) const { return (uint64_t)(upos[first_row[t + 1]] - upos[first_row[t]]); }
     __device__ uint64_t n_mapped(long long t) const { return (uint64_t)(first_row[t + 1] - first_row[t]) - n_unmapped(t); }
 };
@@ -248,11 +257,14 @@ int bamindex_take_rows(BamIndex* S, const BamIndex* src, const uint32_t* perm, c
 }
 int64_t bamindex_rows(const BamIndex* S) { return S ? S->n : 0; }
 
-int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) {
-    if (!S || n_ref < 0) return svx_fail(SVX_E_ARG, "BAM index: bad argument", __FILE__, __LINE__, hipSuccess);
+int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st, int fmt) {
+    if (!S || n_ref < 0 || (fmt != SVX_INDEX_CLASSIC && fmt != SVX_INDEX_CSI)) return svx_fail(SVX_E_ARG, "BAM index: bad argument", __FILE__, __LINE__, hipSuccess);
     S->pool.reset(); S->have = false;
     const int64_t n = S->n;
     const BixCols T = S->cols(0);
+    const bool csi = fmt == SVX_INDEX_CSI;
+    const int header_bytes = csi ? BIX_CSI_HEADER_BYTES : BIX_HEADER_BYTES;
+    int depth = 0, key_shift = BINIDX_KEY_SHIFT;                 // (depth 0: the five-level bins)
     SVXCHK(S->err.reserve(64));
     int* err_d = S->err.as<int>();
     HIPCHK(hipMemsetAsync(err_d, 0, 64, st));
@@ -260,7 +272,7 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
     // ---- the order, the range ----
     int err_h = 0;
     if (n > 0) {
-        k_bix_check<<<BGRID(n), BT, 0, st>>>(n, n_ref, T, err_d);
+        k_bix_check<<<BGRID(n), BT, 0, st>>>(n, n_ref, T, err_d, csi ? 0 : 1);
         HIPCHK(hipGetLastError());
         SVXCHK(svx_d2h(&err_h, err_d, 4, st));
     }
@@ -282,16 +294,35 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
         for (int32_t t = 0; t < n_ref; t++) n_refs_with_rows += first_h[(size_t)t + 1] > first_h[(size_t)t];
     }
     uint32_t* chunk_rec = nullptr; uint64_t *key = nullptr, *key2 = nullptr; uint32_t *val = nullptr, *val2 = nullptr;
+    int64_t* rmax = nullptr;
+    BixRows rows{T, n, v_end, first, upos, nullptr, header_bytes, 0};
+    if (csi) {
+        // ---- the running maximum of the ends inside every reference; the file's largest end gives the depth ----
+        int64_t max_end = 0;
+        if (n_placed > 0) {
+            int64_t* gmax; long long* tile_v; int* tile_f;
+            const size_t tiles = (size_t)((n_placed + BINIDX_RMAX_TILE - 1) / BINIDX_RMAX_TILE);
+            SVXCHK(S->pool.get(&rmax, (size_t)n_placed)); SVXCHK(S->pool.get(&gmax, (size_t)n_ref)); SVXCHK(S->pool.get(&tile_v, tiles)); SVXCHK(S->pool.get(&tile_f, tiles));
+            SVXCHK(binidx_launch_run_max(st, rows, n_placed, n_ref, rmax, gmax, tile_v, tile_f));
+            HIPCHK(hipGetLastError());
+            std::vector<int64_t> gmax_h((size_t)n_ref, 0);
+            SVXCHK(svx_d2h(gmax_h.data(), gmax, (size_t)n_ref * 8, st));
+            for (int64_t v : gmax_h) max_end = std::max(max_end, v);
+        }
+        depth = binidx_depth_for(max_end); key_shift = binidx_csi_key_shift(depth);
+        if (max_end > (1ll << (BINIDX_CSI_MIN_SHIFT + 3 * depth))) return svx_fail(SVX_E_STATE, "BAM index: an end beyond every depth (internal error)", __FILE__, __LINE__, hipSuccess);
+        rows.csi_depth = depth;
+    }
     if (n_placed > 0) {
         SVXCHK(S->pool.get(&bhead, (size_t)n_placed + 1)); SVXCHK(S->pool.get(&umark, (size_t)n_placed + 1)); SVXCHK(S->pool.get(&bpos, (size_t)n_placed + 1)); SVXCHK(S->pool.get(&upos, (size_t)n_placed + 1));
-        k_bix_heads<<<BGRID(n_placed + 1), BT, 0, st>>>(n_placed, T, bhead, umark);
+        k_bix_heads<<<BGRID(n_placed + 1), BT, 0, st>>>(n_placed, T, bhead, umark, depth);
         SVXCHK((svx_exclusive_scan<int32_t, int64_t>(bhead, bpos, n_placed + 1, st, S->scan_tmp)));
         SVXCHK((svx_exclusive_scan<int32_t, int64_t>(umark, upos, n_placed + 1, st, S->scan_tmp)));
         SVXCHK(svx_d2h(&n_chunks, bpos + n_placed, 8, st));
         if (n_chunks < 1 || n_chunks > n_placed) return svx_fail(SVX_E_STATE, "BAM index: the chunk count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
         SVXCHK(S->pool.get(&chunk_rec, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&key, (size_t)n_chunks)); SVXCHK(S->pool.get(&val, (size_t)n_chunks));
         SVXCHK(S->pool.get(&key2, (size_t)n_chunks)); SVXCHK(S->pool.get(&val2, (size_t)n_chunks));
-        k_bix_chunks<<<BGRID(n_placed + 1), BT, 0, st>>>(n_placed, n_chunks, T, bhead, bpos, chunk_rec, key, val);
+        k_bix_chunks<<<BGRID(n_placed + 1), BT, 0, st>>>(n_placed, n_chunks, T, bhead, bpos, chunk_rec, key, val, depth);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st)); S->t_mark[2] = bix_now();
@@ -299,21 +330,33 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
     int32_t *bh = nullptr, *tmax = nullptr; int64_t *binpos = nullptr, *tsz = nullptr, *nintv = nullptr, *toff = nullptr, *loff = nullptr; uint32_t *bin_first = nullptr, *ref_first_bin = nullptr;
     if (n_placed > 0) {
         SVXCHK(S->pool.get(&bh, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&binpos, (size_t)n_chunks + 1));
-        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, val2, n_chunks, 0, binidx_sort_end_bit(n_ref)));
+        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, val2, n_chunks, 0, binidx_sort_end_bit(n_ref, key_shift)));
         k_binidx_bin_heads<BixRows><<<BGRID(n_chunks + 1), BT, 0, st>>>(n_chunks, key2, bh);
         SVXCHK((svx_exclusive_scan<int32_t, int64_t>(bh, binpos, n_chunks + 1, st, S->scan_tmp)));
         SVXCHK(svx_d2h(&n_bins, binpos + n_chunks, 8, st));
         if (n_bins < 1 || n_bins > n_chunks) return svx_fail(SVX_E_STATE, "BAM index: the bin count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
         SVXCHK(S->pool.get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->pool.get(&ref_first_bin, (size_t)n_ref + 1));
-        binidx_launch_bins<BixRows>(st, n_chunks, n_bins, n_ref, key2, bh, binpos, bin_first, ref_first_bin);
+        binidx_launch_bins<BixRows>(st, n_chunks, n_bins, n_ref, key2, bh, binpos, bin_first, ref_first_bin, key_shift);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st)); S->t_mark[3] = bix_now();
     // ---- sizes; the linear index: the smallest vbeg per window ----
     unsigned long long* lin = nullptr;
-    int64_t body = (int64_t)BINIDX_EMPTY_PART_BYTES * n_ref;
-    BixRows rows{T, n, v_end, first, upos, nullptr};
-    if (n_placed > 0) {
+    uint64_t* bin_loff = nullptr;
+    const int64_t empty_part = csi ? BINIDX_CSI_EMPTY_PART_BYTES : BINIDX_EMPTY_PART_BYTES;
+    int64_t body = empty_part * n_ref;
+    rows.first_row = first; rows.upos = upos;
+    if (n_placed > 0 && csi) {
+        // (a .csi: the loffset of every bin by bisection of the running maximum; no largest end per reference, no slots)
+        SVXCHK(S->pool.get(&tsz, (size_t)n_ref + 1)); SVXCHK(S->pool.get(&toff, (size_t)n_ref + 2)); SVXCHK(S->pool.get(&bin_loff, (size_t)n_bins));
+        k_binidx_bin_loff<<<BGRID(n_chunks), BT, 0, st>>>(rows, n_chunks, n_bins, n_placed, key_shift, key2, bh, binpos, rmax, bin_loff, err_d, BIXF_LAYOUT);
+        k_binidx_sizes_csi<<<BGRID(n_ref + 1), BT, 0, st>>>(rows, n_ref, ref_first_bin, bin_first, tsz);
+        SVXCHK((svx_exclusive_scan<int64_t, int64_t>(tsz, toff, (long long)n_ref + 1, st, S->scan_tmp)));
+        HIPCHK(hipGetLastError());
+        SVXCHK(svx_d2h(&body, toff + n_ref, 8, st));
+        if (body < empty_part * n_ref) return svx_fail(SVX_E_STATE, "BAM index: the sizes are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+    }
+    if (n_placed > 0 && !csi) {
         SVXCHK(S->pool.get(&tmax, (size_t)n_ref + 1)); SVXCHK(S->pool.get(&tsz, (size_t)n_ref + 1)); SVXCHK(S->pool.get(&nintv, (size_t)n_ref + 1));
         SVXCHK(S->pool.get(&toff, (size_t)n_ref + 2)); SVXCHK(S->pool.get(&loff, (size_t)n_ref + 2));
         HIPCHK(hipMemsetAsync(tmax, 0, ((size_t)n_ref + 1) * 4, st));
@@ -336,23 +379,31 @@ int bamindex_finish(BamIndex* S, int32_t n_ref, uint64_t v_end, hipStream_t st) 
     }
     HIPCHK(hipStreamSynchronize(st)); S->t_mark[4] = bix_now();
     // ---- layout: header, the references' parts, trailer; every field at its offset ----
-    const int64_t n_blob = BIX_HEADER_BYTES + body + 8;
+    const int64_t n_blob = header_bytes + body + 8;
     SVXCHK(S->blob.reserve((size_t)n_blob + 64));
     uint8_t* blob = S->blob.as<uint8_t>();
     HIPCHK(hipMemsetAsync(blob, 0, (size_t)n_blob + 64, st));
     {
-        uint8_t head[BIX_HEADER_BYTES], trail[8];
-        memcpy(head, "BAI\1", 4); binidx_put32(head + 4, (uint32_t)n_ref);
+        uint8_t head[BIX_CSI_HEADER_BYTES], trail[8];
+        if (csi) {
+            memcpy(head, "CSI\1", 4);
+            binidx_put32(head + 4, BINIDX_CSI_MIN_SHIFT); binidx_put32(head + 8, (uint32_t)depth); binidx_put32(head + 12, 0u); binidx_put32(head + 16, (uint32_t)n_ref);
+        } else { memcpy(head, "BAI\1", 4); binidx_put32(head + 4, (uint32_t)n_ref); }
         binidx_put64(trail, (uint64_t)(n - n_placed));
         HostCopy hc(st);
-        SVXCHK(hc.h2d(blob, head, sizeof head)); SVXCHK(hc.h2d(blob + n_blob - 8, trail, sizeof trail));
+        SVXCHK(hc.h2d(blob, head, (size_t)header_bytes)); SVXCHK(hc.h2d(blob + n_blob - 8, trail, sizeof trail));
         SVXCHK(hc.finish());
     }
     if (n_placed > 0) {
         rows.toff = toff;
         const BinIdxOut o{blob, n_blob - 8, err_d, BIXF_LAYOUT};
-        k_binidx_ser_chunks<<<BGRID(n_chunks), BT, 0, st>>>(rows, n_chunks, key2, val2, bh, binpos, bin_first, ref_first_bin, chunk_rec, o);
-        k_binidx_ser_group<<<(unsigned)n_ref, 64, 0, st>>>(rows, n_ref, ref_first_bin, bin_first, loff, lin, o);
+        if (csi) {
+            k_binidx_ser_chunks_csi<<<BGRID(n_chunks), BT, 0, st>>>(rows, n_chunks, key_shift, key2, val2, bh, binpos, bin_first, ref_first_bin, chunk_rec, bin_loff, o);
+            k_binidx_ser_group_csi<<<BGRID(n_ref), BT, 0, st>>>(rows, n_ref, ref_first_bin, bin_first, o);
+        } else {
+            k_binidx_ser_chunks<<<BGRID(n_chunks), BT, 0, st>>>(rows, n_chunks, key2, val2, bh, binpos, bin_first, ref_first_bin, chunk_rec, o);
+            k_binidx_ser_group<<<(unsigned)n_ref, 64, 0, st>>>(rows, n_ref, ref_first_bin, bin_first, loff, lin, o);
+        }
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(st)); S->t_mark[5] = bix_now();

@@ -18,8 +18,9 @@ int  bamindex_append(BamIndex* ix, const BamIndexChunk& c, hipStream_t st);
 // perm, rec_soff (n entries) and coff (n_blk entries) are device arrays; whatever `ix` held is replaced
 int  bamindex_take_rows(BamIndex* ix, const BamIndex* src, const uint32_t* perm, const int64_t* rec_soff, const int64_t* coff, int64_t n_blk, int64_t block_bytes, hipStream_t st);
 int64_t bamindex_rows(const BamIndex* ix);
-// the bytes of the .bai from the table, which is dropped whatever the result: SVX_OK, SVX_E_ORDER, SVX_E_RANGE
-int  bamindex_finish(BamIndex* ix, int32_t n_ref, uint64_t v_end, hipStream_t st);
+// the bytes of the .bai (fmt SVX_INDEX_CLASSIC) or the uncompressed .csi (SVX_INDEX_CSI) from the table, which is dropped whatever the result: SVX_OK,
+// SVX_E_ORDER, SVX_E_RANGE (a .bai only)
+int  bamindex_finish(BamIndex* ix, int32_t n_ref, uint64_t v_end, hipStream_t st, int fmt);
 bool bamindex_bytes(const BamIndex* ix, int64_t* n_bytes);        // false: no finished index
 int  bamindex_fetch(BamIndex* ix, uint8_t* host_dst, hipStream_t st);
 void bamindex_stats(const BamIndex* ix, svx_bam_index_stats* out);

@@ -5,6 +5,7 @@
 #include "binidx_core.hpp"
 
 #define BIX_HEADER_BYTES 8                   /* magic + n_ref */
+#define BIX_CSI_HEADER_BYTES 20              /* a .csi: magic, min_shift, depth, l_aux = 0, n_ref */
 
 // the interval the index takes for a placed row: a negative pos is read as 0, an end that is not beyond beg as beg + 1
 BINIDX_HD BinIdxInterval bix_interval(int32_t pos, int64_t end) {

@@ -1140,14 +1140,17 @@ extern "C" int svx_bam_index_begin(svx_bam* h) {
     h->dev_data_end = 0; h->dev_eof_seen = false;
     return SVX_OK;
 }
-extern "C" int svx_bam_index_finish(svx_bam* h) {
+static bool index_fmt_ok(int fmt) { return fmt == SVX_INDEX_CLASSIC || fmt == SVX_INDEX_CSI; }
+extern "C" int svx_bam_index_finish_fmt(svx_bam* h, int fmt) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
+    if (!index_fmt_ok(fmt)) return bam_fail(SVX_E_ARG, "svx_bam_index_finish_fmt: unknown index format (SVX_INDEX_CLASSIC or SVX_INDEX_CSI)");
     if (!h->dev || !devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_index_finish without svx_bam_index_begin");
     if (!h->dev_eof_seen || h->dev_prefetching) return bam_fail(SVX_E_STATE, "svx_bam_index_finish before svx_bam_read_batch has returned 0 records at the end of the file");
-    const int rc = devdec_index_finish(h->dev, (uint64_t)h->dev_data_end << 16);
+    const int rc = devdec_index_finish(h->dev, (uint64_t)h->dev_data_end << 16, fmt);
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
     return SVX_OK;
 }
+extern "C" int svx_bam_index_finish(svx_bam* h) { return svx_bam_index_finish_fmt(h, SVX_INDEX_CLASSIC); }
 extern "C" int svx_bam_index_abort(svx_bam* h) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
     if (!h->dev || !devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_index_abort without svx_bam_index_begin");
@@ -1265,12 +1268,14 @@ extern "C" int svx_bam_sort_fetch(svx_bam* h, uint8_t* compressed_dst, uint8_t* 
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
     return SVX_OK;
 }
-extern "C" int svx_bam_sort_index(svx_bam* h) {
+extern "C" int svx_bam_sort_index_fmt(svx_bam* h, int fmt) {
     SORT_NEEDS_FINISHED("svx_bam_sort_index");
-    const int rc = devdec_sort_index(h->dev);
+    if (!index_fmt_ok(fmt)) return bam_fail(SVX_E_ARG, "svx_bam_sort_index_fmt: unknown index format (SVX_INDEX_CLASSIC or SVX_INDEX_CSI)");
+    const int rc = devdec_sort_index(h->dev, fmt);
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
     return SVX_OK;
 }
+extern "C" int svx_bam_sort_index(svx_bam* h) { return svx_bam_sort_index_fmt(h, SVX_INDEX_CLASSIC); }
 extern "C" int svx_bam_sort_permutation(svx_bam* h, uint32_t* perm) {
     SORT_NEEDS_FINISHED("svx_bam_sort_permutation");
     const int rc = devdec_sort_permutation(h->dev, perm);

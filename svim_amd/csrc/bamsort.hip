@@ -665,7 +665,7 @@ int bamsort_fetch(BamSort* S, uint8_t* compressed_dst, uint8_t* stream_dst, hipS
     return SVX_OK;
 }
 
-int bamsort_index(BamSort* S, BamIndex* ix, hipStream_t st) {
+int bamsort_index(BamSort* S, BamIndex* ix, hipStream_t st, int fmt) {
     if (!S || !S->finished || !ix) return svx_fail(SVX_E_STATE, "svx_bam_sort_index before svx_bam_sort_finish", __FILE__, __LINE__, hipSuccess);
     if (S->broken || S->next_block != S->n_blocks)
         return svx_fail(SVX_E_STATE, "svx_bam_sort_index: the file's blocks have not all been encoded in ascending, gap-free ranges", __FILE__, __LINE__, hipSuccess);
@@ -677,7 +677,7 @@ int bamsort_index(BamSort* S, BamIndex* ix, hipStream_t st) {
     SVXCHK(svx_h2d(S->coff_all.p, h_coff.data(), (size_t)(nb + 1) * 8, st));
     SVXCHK(bamindex_take_rows(ix, S->rows, S->perm.as<uint32_t>(), S->soff.as<int64_t>() + 1, S->coff_all.as<int64_t>(), nb, BSORT_BLOCK, st));
     // the data ends where the end-of-file block starts
-    SVXCHK(bamindex_finish(ix, S->n_ref, (uint64_t)h_coff[(size_t)nb - 1] << 16, st));
+    SVXCHK(bamindex_finish(ix, S->n_ref, (uint64_t)h_coff[(size_t)nb - 1] << 16, st, fmt));
     S->stats.t_index_ms = (bs_now() - t0) * 1e3;
     return SVX_OK;
 }

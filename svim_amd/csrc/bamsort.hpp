@@ -24,7 +24,7 @@ void bamsort_count(const BamSort* s, int64_t* n_records, int64_t* stream_bytes, 
 int  bamsort_encode(BamSort* s, int64_t first_block, int64_t n_blocks, int64_t* n_bytes, hipStream_t st);
 int  bamsort_fetch(BamSort* s, uint8_t* compressed_dst, uint8_t* stream_dst, hipStream_t st);
 // the .bai of the encoded file into `ix` (SVX_E_STATE unless every block was encoded, in ascending gap-free ranges); SVX_E_RANGE as bamindex_finish
-int  bamsort_index(BamSort* s, BamIndex* ix, hipStream_t st);
+int  bamsort_index(BamSort* s, BamIndex* ix, hipStream_t st, int fmt);
 int  bamsort_permutation(BamSort* s, uint32_t* host_perm, hipStream_t st);
 void bamsort_stats(const BamSort* s, svx_bam_sort_stats* out);
 void bamsort_spill_stats(const BamSort* s, svx_bam_sort_spill_stats* out);

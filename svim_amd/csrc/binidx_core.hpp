@@ -34,3 +34,35 @@ BINIDX_HD void binidx_put32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = 
 BINIDX_HD void binidx_put64(uint8_t* p, uint64_t v) { binidx_put32(p, (uint32_t)v); binidx_put32(p + 4, (uint32_t)(v >> 32)); }
 // the bytes of the part of a group with rows: n_bin, its bins with their chunks, the pseudo-bin, n_intv, the linear index
 BINIDX_HD int64_t binidx_part_bytes(int64_t n_bins, int64_t n_chunks, int64_t n_intv) { return 4 + 8 * n_bins + 16 * n_chunks + 40 + 4 + 8 * n_intv; }
+
+// ---- the CSI form: the same bins at a depth chosen per file, a loffset per bin in place of the linear index (the definition in words: svim_amd/csi.py) ----
+#define BINIDX_CSI_MIN_SHIFT 14              /* 16 kb leaves, as the five-level scheme has them */
+#define BINIDX_CSI_MIN_DEPTH 5
+#define BINIDX_CSI_MAX_DEPTH 9               /* 2^41: beyond the text parser's cap of 2^40 plus a line's REF; a BAM never needs more than 7 */
+#define BINIDX_CSI_EMPTY_PART_BYTES 4        /* a group without rows: n_bin = 0 */
+
+// the smallest depth >= 5 whose root bin covers [0, max_end)
+BINIDX_HD int binidx_depth_for(int64_t max_end) {
+    int d = BINIDX_CSI_MIN_DEPTH;
+    while (d < BINIDX_CSI_MAX_DEPTH && max_end > (1ll << (BINIDX_CSI_MIN_SHIFT + 3 * d))) d++;
+    return d;
+}
+// the CSI specification's reg2bin at min_shift 14 (depth 5: binidx_reg2bin)
+BINIDX_HD uint32_t binidx_reg2bin_csi(int64_t beg, int64_t end, int depth) {
+    int l = depth, s = BINIDX_CSI_MIN_SHIFT;
+    int64_t t = ((1ll << (3 * depth)) - 1) / 7;
+    for (--end; l > 0; --l, s += 3, t -= 1ll << (3 * l)) if (beg >> s == end >> s) return (uint32_t)(t + (beg >> s));
+    return 0u;
+}
+// the first coordinate a bin covers
+BINIDX_HD int64_t binidx_bin_start(uint32_t bin, int depth) {
+    int l = 0; int64_t first = 0;                 // the level of the bin, and the first bin of that level
+    while (l < depth && (int64_t)bin >= first + (1ll << (3 * l))) { first += 1ll << (3 * l); l++; }
+    return ((int64_t)bin - first) << (BINIDX_CSI_MIN_SHIFT + 3 * (depth - l));
+}
+BINIDX_HD uint32_t binidx_csi_pseudo_bin(int depth) { return (uint32_t)(((1ll << (3 * depth + 3)) - 1) / 7 + 1); }
+// sort key of a chunk in the CSI form: the bin in the low 3 * (depth + 1) bits (it is below 8^(depth + 1) / 7), the group above
+BINIDX_HD int binidx_csi_key_shift(int depth) { return 3 * (depth + 1); }
+BINIDX_HD uint64_t binidx_csi_key(uint64_t group, uint32_t bin, int depth) { return (group << binidx_csi_key_shift(depth)) | bin; }
+// the bytes of the part of a group with rows: n_bin, its bins (bin, loffset, n_chunk) with their chunks, the pseudo-bin with its two pairs
+BINIDX_HD int64_t binidx_csi_part_bytes(int64_t n_bins, int64_t n_chunks) { return 4 + 16 * n_bins + 16 * n_chunks + 48; }

@@ -41,3 +41,32 @@ inline void binidx_append_part(std::vector<uint8_t>& blob, const BinIdxRow* rows
     for (int64_t w = n_intv - 2; w >= 0; w--) if (lin[(size_t)w] == BINIDX_NO_SLOT) lin[(size_t)w] = lin[(size_t)w + 1];
     for (int64_t w = 0; w < n_intv; w++) binidx_put64(p + 8 * w, lin[(size_t)w]);
 }
+
+// the CSI form of the same part (binidx_core.hpp; svim_amd/csi.py): the bins at `depth`, each with the loffset that the filled linear index would hold at
+// the bin's first window - the vbeg of the first row whose running maximum of ends lies beyond the bin's start - and no linear index
+inline void binidx_append_part_csi(std::vector<uint8_t>& blob, const BinIdxRow* rows, size_t n, uint64_t n_mapped, uint64_t n_unmapped, int depth) {
+    struct Chunk { uint32_t bin; uint64_t beg, end; };
+    std::vector<Chunk> chunks;
+    std::vector<int64_t> run_max(n);
+    for (size_t j = 0; j < n; j++) {
+        const uint32_t bin = binidx_reg2bin_csi(rows[j].beg, rows[j].end, depth);
+        if (j > 0 && bin == chunks.back().bin) chunks.back().end = rows[j].vend; else chunks.push_back(Chunk{bin, rows[j].vbeg, rows[j].vend});
+        run_max[j] = j > 0 ? std::max(run_max[j - 1], rows[j].end) : rows[j].end;
+    }
+    std::stable_sort(chunks.begin(), chunks.end(), [](const Chunk& a, const Chunk& b) { return a.bin < b.bin; });
+    int64_t n_bins = 0;
+    for (size_t k = 0; k < chunks.size(); k++) n_bins += k == 0 || chunks[k].bin != chunks[k - 1].bin;
+    const size_t at = blob.size();
+    blob.resize(at + (size_t)binidx_csi_part_bytes(n_bins, (int64_t)chunks.size()));
+    uint8_t* p = blob.data() + at;
+    binidx_put32(p, (uint32_t)(n_bins + 1)); p += 4;
+    for (size_t k = 0; k < chunks.size();) {
+        size_t m = k;
+        while (m < chunks.size() && chunks[m].bin == chunks[k].bin) m++;
+        const size_t j = (size_t)(std::upper_bound(run_max.begin(), run_max.end(), binidx_bin_start(chunks[k].bin, depth)) - run_max.begin());
+        binidx_put32(p, chunks[k].bin); binidx_put64(p + 4, j < n ? rows[j].vbeg : 0ull); binidx_put32(p + 12, (uint32_t)(m - k)); p += 16;
+        for (; k < m; k++) { binidx_put64(p, chunks[k].beg); binidx_put64(p + 8, chunks[k].end); p += 16; }
+    }
+    binidx_put32(p, binidx_csi_pseudo_bin(depth)); binidx_put64(p + 4, 0ull); binidx_put32(p + 12, 2u);
+    binidx_put64(p + 16, rows[0].vbeg); binidx_put64(p + 24, rows[n - 1].vend); binidx_put64(p + 32, n_mapped); binidx_put64(p + 40, n_unmapped);
+}

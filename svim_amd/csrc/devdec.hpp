@@ -42,7 +42,7 @@ void devdec_reset_names(svx_devdec* d);
 int  devdec_index_begin(svx_devdec* d);
 void devdec_index_drop(svx_devdec* d);
 bool devdec_index_on(const svx_devdec* d);
-int  devdec_index_finish(svx_devdec* d, uint64_t v_end);
+int  devdec_index_finish(svx_devdec* d, uint64_t v_end, int fmt);
 bool devdec_index_bytes(const svx_devdec* d, int64_t* n_bytes);
 int  devdec_index_fetch(svx_devdec* d, uint8_t* host_dst);
 void devdec_index_stats(const svx_devdec* d, svx_bam_index_stats* out);
@@ -58,7 +58,7 @@ int  devdec_sort_finish(svx_devdec* d, const uint8_t* header, int64_t header_byt
 void devdec_sort_count(const svx_devdec* d, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
 int  devdec_sort_encode(svx_devdec* d, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
 int  devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_dst);
-int  devdec_sort_index(svx_devdec* d);
+int  devdec_sort_index(svx_devdec* d, int fmt);
 int  devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm);
 void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out);
 void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out);

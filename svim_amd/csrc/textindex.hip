@@ -15,6 +15,8 @@
 //              offset; the wave's backward fill of the empty slots is a reverse scan in tiles of 64.
 // A file whose status is not 0 gets no bytes; its records still pass through the kernels (their sizes count as 0).  Every store into the index is checked
 // against the index's size: a layout that disagrees with its sizes is SVX_E_STATE, not a write somewhere else.
+// svx_text_index_fmt with SVX_INDEX_CSI builds the uncompressed .csi of every file instead (svim_amd/csi.py): a depth per file from the running maximum of the
+// ends inside every contig run, chunk heads and keys at those depths, a loffset per bin by bisection in place of the linear phase, no SVX_E_RANGE.
 #include "common.hpp"
 #include "hostcopy.hpp"
 #include "textindex_core.hpp"
@@ -83,9 +85,12 @@ __global__ void k_tix_compact_records(long long n_lines, const int32_t* isrec, c
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_lines && isrec[i] && rpos[i] < n_rec) r_line[rpos[i]] = (uint32_t)i;
 }
-__device__ __forceinline__ uint32_t tix_bin_of(const TixLines& L, long long i) { return binidx_bin(BinIdxInterval{L.beg[i], L.end[i]}); }
+// fdepth: null for the five-level bins of a .tbi, the depth of every file for a .csi
+__device__ __forceinline__ uint32_t tix_bin_of(const TixLines& L, long long i, const int32_t* fdepth) {
+    return fdepth ? binidx_reg2bin_csi(L.beg[i], L.end[i], fdepth[L.file[i]]) : binidx_bin(BinIdxInterval{L.beg[i], L.end[i]});
+}
 // contig run heads, chunk heads, the order check
-__global__ void k_tix_heads(TixIn in, long long n_rec, const uint32_t* r_line, const int64_t* line, TixLines L, int32_t* chead, int32_t* bhead) {
+__global__ void k_tix_heads(TixIn in, long long n_rec, const uint32_t* r_line, const int64_t* line, TixLines L, int32_t* chead, int32_t* bhead, const int32_t* fdepth) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j > n_rec) return;
     if (j == n_rec) { chead[j] = 0; bhead[j] = 0; return; }
@@ -102,11 +107,11 @@ __global__ void k_tix_heads(TixIn in, long long n_rec, const uint32_t* r_line, c
         if (!ch && L.beg[i] < L.beg[ip]) atomicOr(in.fflag + L.file[i], TIXF_ORDER);
     }
     chead[j] = ch ? 1 : 0;
-    bhead[j] = (ch || tix_bin_of(L, i) != tix_bin_of(L, ip)) ? 1 : 0;
+    bhead[j] = (ch || tix_bin_of(L, i, fdepth) != tix_bin_of(L, ip, fdepth)) ? 1 : 0;
 }
 struct TixRuns { uint32_t* run_rec; int32_t *run_file, *run_nlen; uint32_t* chunk_rec; uint64_t* chunk_key; uint32_t* chunk_val; };
 __global__ void k_tix_runs(long long n_rec, long long n_runs, long long n_chunks, const uint32_t* r_line, TixLines L, const int32_t* chead, const int32_t* bhead, const int64_t* cpos,
-                           const int64_t* bpos, TixRuns o) {
+                           const int64_t* bpos, TixRuns o, const int32_t* fdepth, int key_shift) {
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j > n_rec) return;
     if (j == n_rec) { o.run_rec[n_runs] = (uint32_t)n_rec; o.run_nlen[n_runs] = 0; o.run_file[n_runs] = 0; o.chunk_rec[n_chunks] = (uint32_t)n_rec; return; }
@@ -114,7 +119,12 @@ __global__ void k_tix_runs(long long n_rec, long long n_runs, long long n_chunks
     const long long t = cpos[j] + chead[j] - 1;                 // the run j lies in
     if (chead[j] && t < n_runs) { o.run_rec[t] = (uint32_t)j; o.run_file[t] = L.file[i]; o.run_nlen[t] = L.name_len[i] + 1; }
     const long long q = bpos[j];
-    if (bhead[j] && q < n_chunks) { o.chunk_rec[q] = (uint32_t)j; o.chunk_key[q] = binidx_key((uint64_t)t, tix_bin_of(L, i)); o.chunk_val[q] = (uint32_t)q; }
+    if (bhead[j] && q < n_chunks) { o.chunk_rec[q] = (uint32_t)j; o.chunk_key[q] = ((uint64_t)t << key_shift) | tix_bin_of(L, i, fdepth); o.chunk_val[q] = (uint32_t)q; }
+}
+// the file of every contig run, before the run table exists (a .csi needs the files' depths before it can tell the chunks apart)
+__global__ void k_tix_run_files(long long n_rec, long long n_runs, const uint32_t* r_line, TixLines L, const int32_t* chead, const int64_t* cpos, int32_t* gfile) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n_rec && chead[j] && cpos[j] < n_runs) gfile[cpos[j]] = L.file[r_line[j]];
 }
 __global__ void k_tix_names(long long n_runs, const uint8_t* text, const int64_t* line, const uint32_t* r_line, const uint32_t* run_rec, const int32_t* run_nlen, const int64_t* nm_off,
                             long long n_names, uint8_t* names) {
@@ -129,7 +139,8 @@ __global__ void k_tix_names(long long n_runs, const uint8_t* text, const int64_t
 // the row table as binidx_kernels.hpp reads it: row j is record j of the stream, a group is a contig run
 struct TixRows {
     const uint32_t* r_line; TixLines L; long long n_lines; const int32_t* chead; const int64_t* cpos; const int32_t* fstat; const uint64_t* eofv;
-    const uint32_t* run_rec; const int32_t* run_file; const int64_t *toff, *shift;
+    const uint32_t* run_rec; const int32_t* run_file; const int64_t *toff, *shift; const int32_t* fdepth;
+    __device__ int depth(long long t) const { return fdepth ? fdepth[run_file[t]] : BINIDX_CSI_MIN_DEPTH; }
     __device__ long long group(long long j) const { return cpos[j] + chead[j] - 1; }
     __device__ bool live(long long j) const { return fstat[L.file[r_line[j]]] == 0; }
     __device__ BinIdxInterval interval(long long j) const { const long long i = r_line[j]; return BinIdxInterval{L.beg[i], L.end[i]}; }
@@ -167,7 +178,9 @@ static bool tix_valid(svx_ctx* c, TextGzView* v) {
     return c && c->textindex && c->textindex->have && svx_textgz_view(c, v) && v->gen == c->textindex->gz_gen;
 }
 
-extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base) {
+extern "C" int svx_text_index_fmt(svx_ctx* c, int preset, const int64_t* stream_base, int fmt) {
+    if (fmt != SVX_INDEX_CLASSIC && fmt != SVX_INDEX_CSI) return svx_fail(SVX_E_ARG, "svx_text_index_fmt: unknown index format (SVX_INDEX_CLASSIC or SVX_INDEX_CSI)", __FILE__, __LINE__, hipSuccess);
+    const bool csi = fmt == SVX_INDEX_CSI;
     if (!c || (preset != SVX_INDEX_VCF && preset != SVX_INDEX_BED)) return svx_fail(SVX_E_ARG, "svx_text_index: bad argument (preset SVX_INDEX_VCF or SVX_INDEX_BED)", __FILE__, __LINE__, hipSuccess);
     HIPCHK(hipSetDevice(c->device));
     TextGzView V;
@@ -240,10 +253,44 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     std::vector<int64_t> nm_off_h; std::vector<uint8_t> names_h;
     int32_t *chead = nullptr, *bhead = nullptr; int64_t *cpos = nullptr, *bpos = nullptr, *nm_off = nullptr; uint8_t* names = nullptr;
     TixRuns R; memset(&R, 0, sizeof R);
+    std::vector<int32_t> fdepth_h((size_t)nf, BINIDX_CSI_MIN_DEPTH);
+    int32_t* fdepth = nullptr; int64_t* rmax = nullptr; int key_shift = BINIDX_KEY_SHIFT;
+    TixRows rows; memset(&rows, 0, sizeof rows);
     if (n_rec > 0) {
         SVXCHK(S->pool.get(&chead, (size_t)n_rec + 1)); SVXCHK(S->pool.get(&bhead, (size_t)n_rec + 1)); SVXCHK(S->pool.get(&cpos, (size_t)n_rec + 1)); SVXCHK(S->pool.get(&bpos, (size_t)n_rec + 1));
-        k_tix_heads<<<XGRID(n_rec + 1), XT, 0, st>>>(in, n_rec, r_line, line, L, chead, bhead);
+        k_tix_heads<<<XGRID(n_rec + 1), XT, 0, st>>>(in, n_rec, r_line, line, L, chead, bhead, nullptr);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, chead, cpos, n_rec + 1));
+        if (csi) {
+            // a .csi: the running maximum of the ends inside every contig run; the largest end of a file gives its depth, and only then can the chunk heads
+            // be told (k_tix_heads once more, now with the depths)
+            SVXCHK(svx_d2h(&n_runs, cpos + n_rec, 8, st));
+            if (n_runs < 1 || n_runs > n_rec) return svx_fail(SVX_E_STATE, "svx_text_index: the run counts are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+            int64_t* gmax; int32_t* gfile; long long* tile_v; int* tile_f;
+            const size_t tiles = (size_t)((n_rec + BINIDX_RMAX_TILE - 1) / BINIDX_RMAX_TILE);
+            SVXCHK(S->pool.get(&rmax, (size_t)n_rec)); SVXCHK(S->pool.get(&gmax, (size_t)n_runs)); SVXCHK(S->pool.get(&gfile, (size_t)n_runs)); SVXCHK(S->pool.get(&tile_v, tiles)); SVXCHK(S->pool.get(&tile_f, tiles));
+            SVXCHK(S->pool.get(&fdepth, (size_t)nf));
+            rows.r_line = r_line; rows.L = L; rows.n_lines = n_lines; rows.chead = chead; rows.cpos = cpos;
+            SVXCHK(binidx_launch_run_max(st, rows, n_rec, n_runs, rmax, gmax, tile_v, tile_f));
+            k_tix_run_files<<<XGRID(n_rec), XT, 0, st>>>(n_rec, n_runs, r_line, L, chead, cpos, gfile);
+            HIPCHK(hipGetLastError());
+            std::vector<int64_t> gmax_h((size_t)n_runs, 0); std::vector<int32_t> gfile_h((size_t)n_runs, 0);
+            {
+                HostCopy hc(st);
+                SVXCHK(hc.d2h(gmax_h.data(), gmax, (size_t)n_runs * 8)); SVXCHK(hc.d2h(gfile_h.data(), gfile, (size_t)n_runs * 4));
+                SVXCHK(hc.finish());
+            }
+            std::vector<int64_t> fmax((size_t)nf, 0);
+            for (int64_t t = 0; t < n_runs; t++) {
+                const int f = gfile_h[(size_t)t];
+                if (f < 0 || f >= nf) return svx_fail(SVX_E_STATE, "svx_text_index: a run names no file (internal error)", __FILE__, __LINE__, hipSuccess);
+                fmax[(size_t)f] = std::max(fmax[(size_t)f], gmax_h[(size_t)t]);
+            }
+            int dmax = BINIDX_CSI_MIN_DEPTH;
+            for (int k = 0; k < nf; k++) { fdepth_h[(size_t)k] = binidx_depth_for(fmax[(size_t)k]); dmax = std::max(dmax, (int)fdepth_h[(size_t)k]); }
+            key_shift = binidx_csi_key_shift(dmax);
+            SVXCHK(svx_h2d(fdepth, fdepth_h.data(), (size_t)nf * 4, st));
+            k_tix_heads<<<XGRID(n_rec + 1), XT, 0, st>>>(in, n_rec, r_line, line, L, chead, bhead, fdepth);
+        }
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, bhead, bpos, n_rec + 1));
         {
             HostCopy hc(st);
@@ -254,7 +301,7 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
         SVXCHK(S->pool.get(&R.run_rec, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&R.run_file, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&R.run_nlen, (size_t)n_runs + 1));
         SVXCHK(S->pool.get(&R.chunk_rec, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&R.chunk_key, (size_t)n_chunks)); SVXCHK(S->pool.get(&R.chunk_val, (size_t)n_chunks));
         SVXCHK(S->pool.get(&nm_off, (size_t)n_runs + 1));
-        k_tix_runs<<<XGRID(n_rec + 1), XT, 0, st>>>(n_rec, n_runs, n_chunks, r_line, L, chead, bhead, cpos, bpos, R);
+        k_tix_runs<<<XGRID(n_rec + 1), XT, 0, st>>>(n_rec, n_runs, n_chunks, r_line, L, chead, bhead, cpos, bpos, R, fdepth, key_shift);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, R.run_nlen, nm_off, n_runs + 1));
         run_file_h.assign((size_t)n_runs + 1, 0); nm_off_h.assign((size_t)n_runs + 1, 0);
         {
@@ -281,34 +328,44 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
             if (f != cur) { for (int k = cur + 1; k <= f; k++) first_run[(size_t)k] = t; cur = f; seen.clear(); }
             if (!seen.insert(std::string((const char*)names_h.data() + nm_off_h[(size_t)t], (size_t)(nm_off_h[(size_t)t + 1] - nm_off_h[(size_t)t] - 1))).second) fflag[(size_t)f] |= TIXF_ORDER;
         }
-        for (int k = 0; k < nf; k++) status[(size_t)k] = (fflag[(size_t)k] & TIXF_ORDER) ? SVX_E_ORDER : (fflag[(size_t)k] & TIXF_RANGE) ? SVX_E_RANGE : 0;
+        for (int k = 0; k < nf; k++) status[(size_t)k] = (fflag[(size_t)k] & TIXF_ORDER) ? SVX_E_ORDER : (!csi && (fflag[(size_t)k] & TIXF_RANGE)) ? SVX_E_RANGE : 0;
     }
     SVXCHK(svx_h2d(fstat_d, status.data(), (size_t)nf * 4, st));
     HIPCHK(hipEventRecord(S->ev[3], st));
     // ---- chunks sorted by (contig, bin); bins ----
     int64_t n_bins = 0, n_slots = 0;
-    TixRows rows; memset(&rows, 0, sizeof rows);
+    rows.fdepth = fdepth;
     rows.r_line = r_line; rows.L = L; rows.n_lines = n_lines; rows.chead = chead; rows.cpos = cpos; rows.fstat = fstat_d; rows.eofv = in.eofv; rows.run_rec = R.run_rec; rows.run_file = R.run_file;
     uint64_t* key2 = nullptr; uint32_t *val2 = nullptr, *bin_first = nullptr, *tid_first_bin = nullptr; int32_t *bh = nullptr, *tmax = nullptr; int64_t *binpos = nullptr, *tsz = nullptr, *nintv = nullptr,
               *toff = nullptr, *loff = nullptr;
     std::vector<int64_t> toff_h((size_t)n_runs + 1, 0);
+    uint64_t* bin_loff = nullptr;
     if (n_rec > 0) {
         SVXCHK(S->pool.get(&key2, (size_t)n_chunks)); SVXCHK(S->pool.get(&val2, (size_t)n_chunks)); SVXCHK(S->pool.get(&bh, (size_t)n_chunks + 1)); SVXCHK(S->pool.get(&binpos, (size_t)n_chunks + 1));
-        SVXCHK(svx_sort_pairs_u64(c, R.chunk_key, key2, R.chunk_val, val2, n_chunks, 0, binidx_sort_end_bit(n_runs)));
+        SVXCHK(svx_sort_pairs_u64(c, R.chunk_key, key2, R.chunk_val, val2, n_chunks, 0, binidx_sort_end_bit(n_runs, key_shift)));
         k_binidx_bin_heads<TixRows><<<XGRID(n_chunks + 1), XT, 0, st>>>(n_chunks, key2, bh);
         SVXCHK(svx_exclusive_scan_i32_to_i64(c, bh, binpos, n_chunks + 1));
         SVXCHK(svx_d2h(&n_bins, binpos + n_chunks, 8, st));
         if (n_bins < n_runs || n_bins > n_chunks) return svx_fail(SVX_E_STATE, "svx_text_index: the bin count is out of range (internal error)", __FILE__, __LINE__, hipSuccess);
-        SVXCHK(S->pool.get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->pool.get(&tid_first_bin, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&tmax, (size_t)n_runs + 1));
-        SVXCHK(S->pool.get(&tsz, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&nintv, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&toff, (size_t)n_runs + 2)); SVXCHK(S->pool.get(&loff, (size_t)n_runs + 2));
-        binidx_launch_bins<TixRows>(st, n_chunks, n_bins, n_runs, key2, bh, binpos, bin_first, tid_first_bin);
-        HIPCHK(hipMemsetAsync(tmax, 0, ((size_t)n_runs + 1) * 4, st));
-        k_binidx_max_end<<<XGRID(n_rec), XT, 0, st>>>(rows, n_rec, tmax);
-        k_binidx_sizes<<<XGRID(n_runs + 1), XT, 0, st>>>(rows, n_runs, tmax, tid_first_bin, bin_first, tsz, nintv);
-        SVXCHK(svx_exclusive_scan_i64(c, tsz, toff, n_runs + 1));
-        SVXCHK(svx_exclusive_scan_i64(c, nintv, loff, n_runs + 1));
-        HIPCHK(hipGetLastError());
-        {
+        SVXCHK(S->pool.get(&bin_first, (size_t)n_bins + 1)); SVXCHK(S->pool.get(&tid_first_bin, (size_t)n_runs + 1));
+        SVXCHK(S->pool.get(&tsz, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&toff, (size_t)n_runs + 2));
+        binidx_launch_bins<TixRows>(st, n_chunks, n_bins, n_runs, key2, bh, binpos, bin_first, tid_first_bin, key_shift);
+        if (csi) {
+            // (a .csi: the loffset of every bin by bisection of the running maximum; no largest end per contig, no slots)
+            SVXCHK(S->pool.get(&bin_loff, (size_t)n_bins));
+            k_binidx_bin_loff<<<XGRID(n_chunks), XT, 0, st>>>(rows, n_chunks, n_bins, n_rec, key_shift, key2, bh, binpos, rmax, bin_loff, err_d, 1);
+            k_binidx_sizes_csi<<<XGRID(n_runs + 1), XT, 0, st>>>(rows, n_runs, tid_first_bin, bin_first, tsz);
+            SVXCHK(svx_exclusive_scan_i64(c, tsz, toff, n_runs + 1));
+            HIPCHK(hipGetLastError());
+            SVXCHK(svx_d2h(toff_h.data(), toff, ((size_t)n_runs + 1) * 8, st));
+        } else {
+            SVXCHK(S->pool.get(&tmax, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&nintv, (size_t)n_runs + 1)); SVXCHK(S->pool.get(&loff, (size_t)n_runs + 2));
+            HIPCHK(hipMemsetAsync(tmax, 0, ((size_t)n_runs + 1) * 4, st));
+            k_binidx_max_end<<<XGRID(n_rec), XT, 0, st>>>(rows, n_rec, tmax);
+            k_binidx_sizes<<<XGRID(n_runs + 1), XT, 0, st>>>(rows, n_runs, tmax, tid_first_bin, bin_first, tsz, nintv);
+            SVXCHK(svx_exclusive_scan_i64(c, tsz, toff, n_runs + 1));
+            SVXCHK(svx_exclusive_scan_i64(c, nintv, loff, n_runs + 1));
+            HIPCHK(hipGetLastError());
             HostCopy hc(st);
             SVXCHK(hc.d2h(toff_h.data(), toff, ((size_t)n_runs + 1) * 8)); SVXCHK(hc.d2h(&n_slots, loff + n_runs, 8));
             SVXCHK(hc.finish());
@@ -318,7 +375,7 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     HIPCHK(hipEventRecord(S->ev[4], st));
     // ---- linear index: the smallest vbeg per window ----
     unsigned long long* lin = nullptr;
-    if (n_rec > 0) {
+    if (n_rec > 0 && !csi) {
         SVXCHK(S->pool.get(&lin, (size_t)n_slots));
         if (n_slots) HIPCHK(hipMemsetAsync(lin, 0xff, (size_t)n_slots * 8, st));
         k_binidx_linear<<<XGRID(n_rec), XT, 0, st>>>(rows, n_rec, loff, n_slots, lin);
@@ -338,13 +395,22 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
         const int64_t t0 = first_run[(size_t)k], t1 = first_run[(size_t)k + 1];
         const int64_t l_nm = n_runs ? nm_off_h[(size_t)t1] - nm_off_h[(size_t)t0] : 0, body = n_runs ? toff_h[(size_t)t1] - toff_h[(size_t)t0] : 0;
         std::vector<uint8_t>& h = heads[(size_t)k];
-        h.assign((size_t)(TIX_HEADER_BYTES + l_nm), 0);
-        memcpy(h.data(), "TBI\1", 4);
+        const int64_t head_bytes = csi ? TIX_CSI_HEADER_BYTES : TIX_HEADER_BYTES;
+        h.assign((size_t)(head_bytes + l_nm), 0);
         const uint32_t w[8] = {(uint32_t)(t1 - t0), preset == SVX_INDEX_BED ? 0x10000u : 2u, 1u, 2u, preset == SVX_INDEX_BED ? 3u : 0u, (uint32_t)'#', 0u, (uint32_t)l_nm};
-        for (int q = 0; q < 8; q++) binidx_put32(h.data() + 4 + 4 * q, w[q]);
-        if (l_nm) memcpy(h.data() + TIX_HEADER_BYTES, names_h.data() + nm_off_h[(size_t)t0], (size_t)l_nm);
-        shift[(size_t)k] = foff[(size_t)k] + TIX_HEADER_BYTES + l_nm - (n_runs ? toff_h[(size_t)t0] : 0);
-        foff[(size_t)k + 1] = foff[(size_t)k] + TIX_HEADER_BYTES + l_nm + body + 8;
+        if (csi) {                                              // magic, min_shift, depth, l_aux; aux: the seven int32 of a .tbi header and the names; n_ref
+            memcpy(h.data(), "CSI\1", 4);
+            binidx_put32(h.data() + 4, BINIDX_CSI_MIN_SHIFT); binidx_put32(h.data() + 8, (uint32_t)fdepth_h[(size_t)k]); binidx_put32(h.data() + 12, (uint32_t)(28 + l_nm));
+            for (int q = 1; q < 8; q++) binidx_put32(h.data() + 12 + 4 * q, w[q]);
+            if (l_nm) memcpy(h.data() + 44, names_h.data() + nm_off_h[(size_t)t0], (size_t)l_nm);
+            binidx_put32(h.data() + 44 + l_nm, w[0]);
+        } else {
+            memcpy(h.data(), "TBI\1", 4);
+            for (int q = 0; q < 8; q++) binidx_put32(h.data() + 4 + 4 * q, w[q]);
+            if (l_nm) memcpy(h.data() + TIX_HEADER_BYTES, names_h.data() + nm_off_h[(size_t)t0], (size_t)l_nm);
+        }
+        shift[(size_t)k] = foff[(size_t)k] + head_bytes + l_nm - (n_runs ? toff_h[(size_t)t0] : 0);
+        foff[(size_t)k + 1] = foff[(size_t)k] + head_bytes + l_nm + body + 8;
     }
     const int64_t n_blob = foff[(size_t)nf];
     SVXCHK(S->blob.reserve((size_t)n_blob + 64));
@@ -359,8 +425,13 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
         if (n_rec > 0) {
             rows.toff = toff; rows.shift = shift_d;
             const BinIdxOut o{blob, n_blob, err_d, 1};
-            k_binidx_ser_chunks<<<XGRID(n_chunks), XT, 0, st>>>(rows, n_chunks, key2, val2, bh, binpos, bin_first, tid_first_bin, R.chunk_rec, o);
-            k_binidx_ser_group<<<(unsigned)n_runs, 64, 0, st>>>(rows, n_runs, tid_first_bin, bin_first, loff, lin, o);
+            if (csi) {
+                k_binidx_ser_chunks_csi<<<XGRID(n_chunks), XT, 0, st>>>(rows, n_chunks, key_shift, key2, val2, bh, binpos, bin_first, tid_first_bin, R.chunk_rec, bin_loff, o);
+                k_binidx_ser_group_csi<<<XGRID(n_runs), XT, 0, st>>>(rows, n_runs, tid_first_bin, bin_first, o);
+            } else {
+                k_binidx_ser_chunks<<<XGRID(n_chunks), XT, 0, st>>>(rows, n_chunks, key2, val2, bh, binpos, bin_first, tid_first_bin, R.chunk_rec, o);
+                k_binidx_ser_group<<<(unsigned)n_runs, 64, 0, st>>>(rows, n_runs, tid_first_bin, bin_first, loff, lin, o);
+            }
             HIPCHK(hipGetLastError());
         }
     }
@@ -378,6 +449,8 @@ extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base
     S->gz_gen = V.gen; S->have = true;
     return SVX_OK;
 }
+
+extern "C" int svx_text_index(svx_ctx* c, int preset, const int64_t* stream_base) { return svx_text_index_fmt(c, preset, stream_base, SVX_INDEX_CLASSIC); }
 
 extern "C" int svx_text_index_count(svx_ctx* c, int32_t* n_files, int64_t* n_bytes) {
     TextGzView V;

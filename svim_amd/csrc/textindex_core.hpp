@@ -7,6 +7,7 @@
 #define TIX_HEAD 65280                       /* bytes of a line that are parsed (one BGZF block of text) */
 #define TIX_NUM_CAP (1ll << 40)
 #define TIX_HEADER_BYTES 36                  /* magic + eight int32, in front of the names */
+#define TIX_CSI_HEADER_BYTES 48              /* a .csi: magic, min_shift, depth, l_aux, then aux = seven int32 of the .tbi header and the names, then n_ref */
 
 struct TixLine { int32_t skip, name_len; int64_t beg, end; };
 

@@ -13,8 +13,9 @@ namespace {
 struct Rec { int64_t at, beg, end; int32_t name_len; uint64_t vbeg, vend; };
 }
 
-extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
-                                   uint8_t* out, int64_t cap, int64_t* n_out) {
+// csi: the .csi of the same text (svim_amd/csi.py) - a depth from the largest end, no range to refuse
+static int text_index_host(bool csi, const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
+                           uint8_t* out, int64_t cap, int64_t* n_out) {
     if (n < 0 || cap < 0 || (n && !text) || (cap && !out) || !n_out || !block_coff || !block_uoff || n_blocks < 1 || (preset != SVX_INDEX_VCF && preset != SVX_INDEX_BED) ||
         stream_base < 0 || block_uoff[0] != 0 || block_uoff[n_blocks - 1] != n)
         return SVX_E_ARG;
@@ -42,6 +43,7 @@ extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t
     std::vector<size_t> run_first;
     std::unordered_set<std::string> seen;
     bool bad_order = false, bad_range = false;
+    int64_t max_end = 0;
     for (size_t j = 0; j < recs.size(); j++) {
         const Rec& r = recs[j];
         const bool head = j == 0 || r.name_len != recs[j - 1].name_len || memcmp(text + r.at, text + recs[j - 1].at, (size_t)r.name_len) != 0;
@@ -49,31 +51,51 @@ extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t
             if (!seen.insert(std::string((const char*)text + r.at, (size_t)r.name_len)).second) bad_order = true;
             run_first.push_back(j);
         } else if (r.beg < recs[j - 1].beg) bad_order = true;
-        if (r.end > BINIDX_MAX_END) bad_range = true;
+        max_end = std::max(max_end, r.end);
     }
     if (bad_order) return SVX_E_ORDER;
+    bad_range = !csi && max_end > BINIDX_MAX_END;
     if (bad_range) return SVX_E_RANGE;
+    const int depth = binidx_depth_for(max_end);
     const size_t n_ref = run_first.size();
     run_first.push_back(recs.size());
-    std::vector<uint8_t> blob((size_t)TIX_HEADER_BYTES);
+    std::vector<uint8_t> blob((size_t)(csi ? TIX_CSI_HEADER_BYTES - 4 : TIX_HEADER_BYTES));     // (a .csi has n_ref behind the names)
     int64_t l_nm = 0;
     for (size_t t = 0; t < n_ref; t++) {
         const Rec& r = recs[run_first[t]];
         blob.insert(blob.end(), text + r.at, text + r.at + r.name_len); blob.push_back(0);
         l_nm += r.name_len + 1;
     }
-    memcpy(blob.data(), "TBI\1", 4);
     const uint32_t head[8] = {(uint32_t)n_ref, preset == SVX_INDEX_BED ? 0x10000u : 2u, 1u, 2u, preset == SVX_INDEX_BED ? 3u : 0u, (uint32_t)'#', 0u, (uint32_t)l_nm};
-    for (int k = 0; k < 8; k++) binidx_put32(blob.data() + 4 + 4 * k, head[k]);
+    if (csi) {
+        memcpy(blob.data(), "CSI\1", 4);
+        binidx_put32(blob.data() + 4, BINIDX_CSI_MIN_SHIFT); binidx_put32(blob.data() + 8, (uint32_t)depth); binidx_put32(blob.data() + 12, (uint32_t)(28 + l_nm));
+        for (int k = 1; k < 8; k++) binidx_put32(blob.data() + 12 + 4 * k, head[k]);
+        blob.resize(blob.size() + 4);
+        binidx_put32(blob.data() + blob.size() - 4, (uint32_t)n_ref);
+    } else {
+        memcpy(blob.data(), "TBI\1", 4);
+        for (int k = 0; k < 8; k++) binidx_put32(blob.data() + 4 + 4 * k, head[k]);
+    }
     for (size_t t = 0; t < n_ref; t++) {
         const size_t lo = run_first[t], hi = run_first[t + 1];
         std::vector<BinIdxRow> rows;
         for (size_t j = lo; j < hi; j++) rows.push_back(BinIdxRow{recs[j].beg, recs[j].end, recs[j].vbeg, recs[j].vend});
-        binidx_append_part(blob, rows.data(), rows.size(), (uint64_t)(hi - lo), 0ull);
+        if (csi) binidx_append_part_csi(blob, rows.data(), rows.size(), (uint64_t)(hi - lo), 0ull, depth);
+        else binidx_append_part(blob, rows.data(), rows.size(), (uint64_t)(hi - lo), 0ull);
     }
     blob.resize(blob.size() + 8, 0);
     *n_out = (int64_t)blob.size();
     if ((int64_t)blob.size() > cap) return SVX_E_CAPACITY;
     memcpy(out, blob.data(), blob.size());
     return SVX_OK;
+}
+
+extern "C" int svx_text_index_host(const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
+                                   uint8_t* out, int64_t cap, int64_t* n_out) {
+    return text_index_host(false, text, n, block_coff, block_uoff, n_blocks, preset, stream_base, out, cap, n_out);
+}
+extern "C" int svx_text_index_csi_host(const uint8_t* text, int64_t n, const int64_t* block_coff, const int64_t* block_uoff, int64_t n_blocks, int preset, int64_t stream_base,
+                                       uint8_t* out, int64_t cap, int64_t* n_out) {
+    return text_index_host(true, text, n, block_coff, block_uoff, n_blocks, preset, stream_base, out, cap, n_out);
 }

@@ -40,8 +40,10 @@ class BamPipeline(object):
     """reader thread || GPU thread over one BAM file; results stay resident in the engine (accumulated lists)."""
 
     def __init__(self, path, options, engine, threads=0, batch_records=200_000, mode="coordinate", sparse_seq=True, regions=None, gpu_inflate=None,
-                 device_decode=None, keep_alignments=False, build_index=False):
+                 device_decode=None, keep_alignments=False, build_index=False, index_format="bai"):
         from .bamio import NativeBam
+        if index_format not in ("bai", "csi", "auto"):
+            raise ValueError("index_format: bai, csi or auto")
         if build_index and regions is not None:
             raise ValueError("build_index needs the pass over the whole file (no regions): an index describes every record")
         if keep_alignments and (regions is not None or mode != "coordinate"):
@@ -60,6 +62,7 @@ class BamPipeline(object):
             self.bam.close()
             raise ValueError("build_index needs device decode: the index is built from the device reader's record stream")
         self.build_index, self.index_bytes = bool(build_index), None      # the .bai of the file, a by-product of run() (write_bai)
+        self.index_format = index_format                                  # "csi": the uncompressed .csi instead (write_csi); "auto": by the header's lengths
         self.options, self.eng, self.mode, self.batch_records = options, engine, mode, batch_records
         self.params = _abi.Params.from_options(options)
         if self.device_decode:
@@ -182,7 +185,9 @@ class BamPipeline(object):
         if self.build_index and at_end:
             # the reader has seen the end of the file: the row table its chunks appended becomes the .bai - no second read of the file
             t0 = time.perf_counter()
-            self.index_bytes = bam.index_finish()
+            if self.index_format == "auto":
+                self.index_format = _abi.auto_index_format(bam.lengths, "bai")
+            self.index_bytes = bam.index_finish(self.index_format)
             self.stats["t_index_finish_wall"] = time.perf_counter() - t0
             self.stats["index"] = bam.index_stats()
         try:
@@ -193,12 +198,33 @@ class BamPipeline(object):
 
     def write_bai(self, path=None):
         """the BAM index run() built beside COLLECT (build_index=True) -> path, default <bam>.bai"""
-        if self.index_bytes is None:
-            raise ValueError("BamPipeline.write_bai needs build_index=True and a completed run()")
+        if self.index_bytes is None or self.index_format != "bai":
+            raise ValueError("BamPipeline.write_bai needs build_index=True, a completed run() and an index in the .bai format")
         path = path or self.bam.filename + ".bai"
         with open(path, "wb") as fh:
             fh.write(self.index_bytes)
         return path
+
+    def write_csi(self, path=None):
+        """the CSI index run() built beside COLLECT (build_index=True, index_format="csi" or "auto" on a long contig) -> path, default <bam>.csi"""
+        if self.index_bytes is None or self.index_format != "csi":
+            raise ValueError("BamPipeline.write_csi needs build_index=True, index_format='csi' and a completed run()")
+        from . import SVIM_COMBINE as K
+        path = path or self.bam.filename + ".csi"
+        K._write_tbi(path, self.index_bytes)
+        return path
+
+    def _text_index_format(self, index):
+        """index of write_vcf and the file writers: False / True (.tbi) / "tbi" / "csi" / "auto" (a .csi when a reference is longer than 2^29) -> None or the format"""
+        if not index:
+            return None
+        if index is True:
+            return "tbi"
+        if index == "auto":
+            return _abi.auto_index_format(self.bam.lengths, "tbi")
+        if index not in ("tbi", "csi"):
+            raise ValueError("index: True, 'tbi', 'csi' or 'auto'")
+        return index
 
     def cluster(self, genome=None):
         """CLUSTER from the accumulated lists.  genome: (off, codes[, on_device]) or None when already set"""
@@ -230,7 +256,9 @@ class BamPipeline(object):
     def write_vcf(self, path, version="svim_amd", types_to_output=None, index=False):
         """header + the lines svx_vcf makes of the resident candidates, with the resident genotype columns when genotype() ran -> bytes written.
         index (the path must end in .gz): the lines in position order (svx_vcf_position_order) and path + ".tbi" beside the file, built on the device from
-        the text and the block table of the stream (svx_text_index); SvxError when the text cannot be indexed (a record beyond 2^29)"""
+        the text and the block table of the stream (svx_text_index); SvxError when the text cannot be indexed (a record beyond 2^29).  index "csi": path +
+        ".csi" instead, which has no such limit; "auto": a .csi when a reference of the file is longer than 2^29, else the .tbi; True stays the .tbi"""
+        index = self._text_index_format(index)
         from . import SVIM_COMBINE as K
         o = self.options
         types = types_to_output if types_to_output is not None else [t.strip() for t in str(getattr(o, "types", "DEL,INS,INV,DUP:TANDEM,DUP:INT,BND")).split(",")]
@@ -251,12 +279,12 @@ class BamPipeline(object):
                 out.write(head)
                 write_text_gz(self.eng, out)
                 if index:
-                    self.eng.text_index(_abi.INDEX_VCF, len(head))
+                    self.eng.text_index(_abi.INDEX_VCF, len(head), fmt=index)
                     blobs, status = self.eng.text_index_fetch()
                     if status[0] != 0:
                         from ._lib import SvxError
                         raise SvxError("%s cannot be indexed: %s" % (path, _abi.ERRORS.get(int(status[0]), int(status[0]))))
-                    K._write_tbi(str(path) + ".tbi", blobs[0])
+                    K._write_tbi(str(path) + "." + index, blobs[0])
             else:
                 out.write(head)
                 for at in range(0, n_bytes, K._VCF_PIECE):
@@ -266,28 +294,32 @@ class BamPipeline(object):
 
     # file -> the sixteen BED / signature-VCF files of the working directory without a Python object: run(), cluster(), write_signature_files(dir, version),
     # combine(), write_candidate_files(dir)
-    def _bed_files(self, product, directory, names, heads=None, compress=False, index=None):
+    def _bed_files(self, product, directory, names, heads=None, compress=False, index=None, index_format="tbi"):
         from . import bed
         if getattr(self, "_bed_read_names", None) is None:
             self._bed_read_names = self.bam.read_names()             # uploaded once: the engine knows the list by identity
         os.makedirs(directory, exist_ok=True)
         t0 = time.perf_counter()
         _, _, n_bytes = self.eng.bed(product, self.bam.references, read_names=self._bed_read_names)
-        self._not_indexed += bed.write_files(self.eng, directory, names, heads=heads, compress=compress, index=index)
+        self._not_indexed += bed.write_files(self.eng, directory, names, heads=heads, compress=compress, index=index, index_format=index_format)
         self.stats["t_bed_wall"] = self.stats.get("t_bed_wall", 0.0) + time.perf_counter() - t0
         return n_bytes
 
     def write_signature_files(self, working_dir, version="svim_amd", compress=False, index=False):
         """<working_dir>/signatures/*.bed and all.vcf of the resident clusters (after cluster()), made by svx_bed -> bytes of text behind the header.
         compress: the same names with .gz appended, BGZF made on the device (svx_text_gz).  index (with compress): a .tbi beside every file whose lines are
-        in an order tabix takes (svx_text_index; the reference's order is not changed) -> (bytes, names of the files that got none, each logged once)"""
+        in an order tabix takes (svx_text_index; the reference's order is not changed) -> (bytes, names of the files that got none, each logged once).
+        index "csi" / "auto": as write_vcf has them (a .gz.csi beside every file)"""
         from . import SVIM_CLUSTER as K
+        fmt = self._text_index_format(index) or "tbi"
         if index and not compress:
             raise ValueError("index=True needs compress=True (a tabix index belongs to a BGZF file)")
         d = os.path.join(working_dir, "signatures")
         self._not_indexed = []
-        n = self._bed_files(_abi.BED_SIGNATURE_BEDS, d, [name for name, _, _ in K._BED_FILES], compress=compress, index=_abi.INDEX_BED if index else None)
-        n += self._bed_files(_abi.BED_SIGNATURE_VCF, d, ["all.vcf"], heads=[K.vcf_header_text(version).encode("utf-8")], compress=compress, index=_abi.INDEX_VCF if index else None)
+        n = self._bed_files(_abi.BED_SIGNATURE_BEDS, d, [name for name, _, _ in K._BED_FILES], compress=compress, index=_abi.INDEX_BED if index else None,
+                            index_format=fmt)
+        n += self._bed_files(_abi.BED_SIGNATURE_VCF, d, ["all.vcf"], heads=[K.vcf_header_text(version).encode("utf-8")], compress=compress, index=_abi.INDEX_VCF if index else None,
+                             index_format=fmt)
         return (n, list(self._not_indexed)) if index else n
 
     def write_candidate_files(self, working_dir, compress=False, index=False):
@@ -295,11 +327,12 @@ class BamPipeline(object):
         compress: the same names with .gz appended, BGZF made on the device (svx_text_gz).  index (with compress): as write_signature_files has it
         -> (bytes, names of the files that got no .tbi)"""
         from . import SVIM_COMBINE as K
+        fmt = self._text_index_format(index) or "tbi"
         if index and not compress:
             raise ValueError("index=True needs compress=True (a tabix index belongs to a BGZF file)")
         self._not_indexed = []
         n = self._bed_files(_abi.BED_CANDIDATE_BEDS, os.path.join(working_dir, "candidates"), [name for name, _, _ in K._CANDIDATE_BED_FILES], compress=compress,
-                            index=_abi.INDEX_BED if index else None)
+                            index=_abi.INDEX_BED if index else None, index_format=fmt)
         return (n, list(self._not_indexed)) if index else n
 
     def rewind(self):
@@ -740,32 +773,51 @@ def end_to_end_sample(batch, g_off, genome, opts, device=0, resident_reads_per_s
     return out
 
 
-def index_bam(path, device=0, out=None, threads=0, batch_records=200_000):
+def _bam_index_format(fmt, lengths):
+    if fmt not in ("bai", "csi", "auto"):
+        raise ValueError("index format: bai, csi or auto")
+    return _abi.auto_index_format(lengths, "bai") if fmt == "auto" else fmt
+
+
+def index_bam(path, device=0, out=None, threads=0, batch_records=200_000, fmt="bai"):
     """The BAM index of a coordinate-sorted file one only wants indexed: one pass of the device reader whose batches are read and discarded, the index built
     on the device from the reader's record stream (NativeBam.index_begin / index_finish; svim_amd/bai.py says what it holds) -> the bytes, written to `out` when
-    given.  svim_amd.bai.BaiError for a file that has none (not in coordinate order, a record beyond 2^29)."""
+    given.  svim_amd.bai.BaiError for a file that has none (not in coordinate order, a record beyond 2^29).
+    fmt="csi": the .csi instead (svim_amd/csi.py; no limit at 2^29) -> its uncompressed bytes, `out` gets them BGZF-framed; "auto": a .csi exactly when a
+    reference length of the header exceeds 2^29."""
     from .bamio import NativeBam
     bam = NativeBam(path, threads=threads)
     try:
+        fmt = _bam_index_format(fmt, bam.lengths)
         bam.set_device_decode(int(device))
         bam.index_begin()
         while bam.read_batch(batch_records, 0, "coordinate")[1]:
             pass
-        data = bam.index_finish()
+        data = bam.index_finish(fmt)
     finally:
         bam.close()
     if out is not None:
-        with open(out, "wb") as fh:
-            fh.write(data)
+        _write_bam_index(out, data, fmt)
     return data
 
 
-def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None):
+def _write_bam_index(path, data, fmt):
+    """a .bai is its bytes; a .csi is BGZF-framed, by the route a .tbi takes"""
+    if fmt == "csi":
+        from . import SVIM_COMBINE as K
+        K._write_tbi(path, data)
+    else:
+        with open(path, "wb") as fh:
+            fh.write(data)
+
+
+def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None, index_format="bai"):
     """The BAM file (or the SAM text: NativeBam tells them apart) at `path`, in any order, written to `out` in coordinate order (svim_amd/bamsort.py says what the sorted file is), and its index to
     out + ".bai" when `index`: one pass of the device reader whose batches are read and discarded while every record stays on the device, a sort there, then
     the file encoded and written in pieces of piece_blocks BGZF blocks - the whole file is never held in host memory (NativeBam.sort_*).  max_bytes: the most
     the records may take on the device (0: what is free).  spill_dir: a directory for the spill file of a file whose records pass that limit (runs are
     written there and merged: the same bytes; the file is unlinked while it is open, nothing is left behind) - None: such a file raises with SVX_E_CAPACITY.
+    index_format="csi": out + ".csi" instead (svim_amd/csi.py), "auto": that when a reference length of the header exceeds 2^29.
     -> the sort's stats, the spill's under "spill".  On failure the partial output is removed and the sort given up;
     svim_amd.bamsort.BamSortError carries the library's status in .code."""
     from .bamio import NativeBam
@@ -774,6 +826,7 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
     bam = NativeBam(path, threads=threads)
     written = []
     try:
+        index_format = _bam_index_format(index_format, bam.lengths)
         bam.set_device_decode(int(device))
         bam.sort_begin(max_bytes, spill_dir)
         try:
@@ -785,10 +838,9 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
                 for first in range(0, n_blocks, piece_blocks):
                     fh.write(bam.sort_encode(first, min(piece_blocks, n_blocks - first)))
             if index:
-                data = bam.sort_index()
-                written.append(out + ".bai")
-                with open(out + ".bai", "wb") as fh:
-                    fh.write(data)
+                data = bam.sort_index(index_format)
+                written.append(out + "." + index_format)
+                _write_bam_index(out + "." + index_format, data, index_format)
             stats = bam.sort_stats()
             stats["spill"] = bam.sort_spill_stats()
             if bam.is_sam:
@@ -808,7 +860,7 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
     return stats
 
 
-def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None):
+def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None, index_format="bai"):
     """SAM text at `sam` -> a BAM file at `out_bam`: the reference's `samtools view -b | samtools sort` and `samtools index` (src/svim/SVIM_alignment.py).
     sort=True: one pass of the device reader, coordinate order and, with `index`, out_bam + ".bai" (sort_bam does it: svim_amd/sam.py says what the records are,
     svim_amd/bamsort.py what the sorted file is; spill_dir as there) -> the sort's stats with the front end's under "sam".
@@ -820,7 +872,8 @@ def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096,
     if not is_sam_text(sam):
         raise ValueError("sam_to_bam: %r is not SAM text" % sam)
     if sort:
-        return sort_bam(sam, out_bam, device=device, index=index, piece_blocks=piece_blocks, max_bytes=max_bytes, threads=threads, batch_records=batch_records, spill_dir=spill_dir)
+        return sort_bam(sam, out_bam, device=device, index=index, piece_blocks=piece_blocks, max_bytes=max_bytes, threads=threads, batch_records=batch_records, spill_dir=spill_dir,
+                        index_format=index_format)
     if index:
         raise ValueError("sam_to_bam: index=True needs sort=True (records in file order have no index)")
     with open(sam, "rb") as fh:
@@ -866,7 +919,9 @@ def collect_cluster_bam_sharded(bam_path, opts, engine, adapter, rank, world, th
     probe = NativeBam(bam_path, threads=1)
     refs, lens = probe.references, probe.lengths
     probe.close()
-    bai = records.read_bai(bai_path or bam_path + ".bai")
+    if bai_path is None:                                     # (either kind of index: a .csi when the file has no .bai)
+        bai_path = bam_path + ".bai" if os.path.exists(bam_path + ".bai") or not os.path.exists(bam_path + ".csi") else bam_path + ".csi"
+    bai = records.read_index(bai_path)
     owner, runs = shard_plan(refs, lens, bai, rank, world)
     pipe = BamPipeline(bam_path, opts, engine, threads=threads, batch_records=batch_records, regions=[(v, last) for v, last, _ in runs])
     n_rec = pipe.run()

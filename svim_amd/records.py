@@ -551,6 +551,24 @@ def write_bai(path, n_ref, rec_at, raw_len, block_at, block_payload):
             fh.write(struct.pack("<i", 0))                  # n_intv
 
 
+def read_index(path):
+    """the index of a BAM file, a .bai or a .csi, told apart by its first bytes (a .csi is BGZF-framed: it starts with the gzip magic) -> what read_bai gives:
+    per reference the (first, last) virtual offsets of its records, None for a reference without records"""
+    with open(path, "rb") as fh:
+        magic = fh.read(2)
+    if magic != b"\x1f\x8b":
+        return read_bai(path)
+    from . import csi
+    ix = csi.parse_index(csi.read_file(path))
+    if ix["aux"]:
+        raise ValueError("not the index of a BAM file: %s" % path)
+    out = []
+    for d in ix["bins"]:
+        chunks = [c for cs in d.values() for c in cs]
+        out.append((min(c[0] for c in chunks), max(c[1] for c in chunks)) if chunks else None)
+    return out
+
+
 def read_bai(path):
     """BAM index -> list of (first, last) virtual offsets per reference (None for a reference without records): the smallest chunk
     begin and largest chunk end over all bins (the metadata pseudo-bin 37450 aside)."""

@@ -264,6 +264,12 @@ def query(index, bgzf, contig, beg, end, stats=None):
             merged[-1][1] = max(merged[-1][1], c[1])
         else:
             merged.append(list(c))
+    return read_chunks(merged, bgzf, preset, name, beg, end, stats)
+
+
+def read_chunks(merged, bgzf, preset, name, beg, end, stats=None):
+    """the lines of the records of contig `name` (bytes) that overlap [beg, end) inside the chunks `merged` (ascending, disjoint), in file order: the walk
+    query() makes, also csi.query_text's"""
     cache, out = {}, []
 
     def block(coff):

@@ -115,7 +115,7 @@ void devdec_reset_names(svx_devdec* d) { d->names.clear(); }
 int devdec_index_begin(svx_devdec*) { return SVX_E_STATE; }
 void devdec_index_drop(svx_devdec*) {}
 bool devdec_index_on(const svx_devdec*) { return false; }
-int devdec_index_finish(svx_devdec*, uint64_t) { return SVX_E_STATE; }
+int devdec_index_finish(svx_devdec*, uint64_t, int) { return SVX_E_STATE; }
 bool devdec_index_bytes(const svx_devdec*, int64_t*) { return false; }
 int devdec_index_fetch(svx_devdec*, uint8_t*) { return SVX_E_STATE; }
 void devdec_index_stats(const svx_devdec*, svx_bam_index_stats* out) { memset(out, 0, sizeof *out); }
@@ -128,7 +128,7 @@ int devdec_sort_finish(svx_devdec*, const uint8_t*, int64_t) { return SVX_E_STAT
 void devdec_sort_count(const svx_devdec*, int64_t*, int64_t*, int64_t*) {}
 int devdec_sort_encode(svx_devdec*, int64_t, int64_t, int64_t*) { return SVX_E_STATE; }
 int devdec_sort_fetch(svx_devdec*, uint8_t*, uint8_t*) { return SVX_E_STATE; }
-int devdec_sort_index(svx_devdec*) { return SVX_E_STATE; }
+int devdec_sort_index(svx_devdec*, int) { return SVX_E_STATE; }
 int devdec_sort_permutation(svx_devdec*, uint32_t*) { return SVX_E_STATE; }
 void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
 void devdec_sort_spill_stats(const svx_devdec*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
