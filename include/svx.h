@@ -342,6 +342,12 @@ int  svx_combine_get_stats(svx_ctx* ctx, svx_combine_stats* out);
 /* host-only (no GPU needed; tests): random.seed(1524) followed by random.sample(range(sizes[k]), 100) for k = 0 .. n - 1, as partition_and_cluster_candidates
  * consumes the stream; out[100 * n] */
 int  svx_py_sample100(int64_t n, const int64_t* sizes, int32_t* out);
+/* host-only (no GPU needed; tests): one window of CLUSTER's consumption table by the host build of csrc/sample_core.hpp.  out[s], s = 0 .. width - 1: the words
+ * of stream[0 .. cap) a pool-method random.sample(range(n), 100), 101 <= n <= 1045, consumes from position lo + s; 0xffff for a walk that leaves the stream.
+ * method 0: the walk from every start; method 1: the backward sweep in chunks of `chunk` starts, begun `margin` words behind each chunk (0, 0: the kernel's
+ * constants), what it leaves open walked - the same table. */
+int  svx_sample_used_host(const uint32_t* stream, int64_t cap, int32_t n, int64_t lo, int32_t width, int32_t method, int32_t chunk, int32_t margin,
+                          uint16_t* out);
 
 /* ---- VCF text: replaces the body of write_final_vcf (src/svim/SVIM_COMBINE.py:139-184: entries, sorted_nicely :61-68, the svim.<label>.<k> ids) and the nine
  * get_vcf_entry* methods of src/svim/SVCandidate.py (:79, :149, :222, :323, :376, :476, :528, :640, :690) ---------------------------------------------------

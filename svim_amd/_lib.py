@@ -28,7 +28,7 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_inflater_create", "svx_inflater_destroy", "svx_inflater_staging", "svx_inflater_enqueue", "svx_inflater_wait",
            "svx_inflater_run",
            "svx_genome_load_fasta", "svx_genome_fetch", "svx_fasta_probe", "svx_fasta_plan",
-           "svx_combine", "svx_combine_count", "svx_combine_fetch", "svx_combine_stages_fetch", "svx_combine_get_stats", "svx_py_sample100",
+           "svx_combine", "svx_combine_count", "svx_combine_fetch", "svx_combine_stages_fetch", "svx_combine_get_stats", "svx_py_sample100", "svx_sample_used_host",
            "svx_vcf", "svx_vcf_count", "svx_vcf_fetch", "svx_vcf_get_stats", "svx_vcf_format_std",
            "svx_format_repr", "svx_format_repr_many", "svx_format_repr_device",
            "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats",
@@ -102,6 +102,18 @@ def py_sample100(sizes):
     out = np.zeros((max(1, sizes.size), 100), dtype=np.int32)
     _check(lib().svx_py_sample100(C.c_int64(sizes.size), ptr(sizes if sizes.size else np.zeros(1, np.int64)), ptr(out)), "svx_py_sample100")
     return out[:sizes.size]
+
+
+def sample_used_host(stream, n, lo, width, method="sweep", chunk=0, margin=0):
+    """svx_sample_used_host (host-only, no GPU needed): the window [lo, lo + width) of CLUSTER's consumption table for a partition of n members by the host build
+    of csrc/sample_core.hpp -> uint16 array; stream: the uint32 words of random.Random(1524).  method "walk": one walk per start (k_sample_tables); "sweep": the
+    backward sweep (k_sample_sweep) in chunks of `chunk` starts with a margin of `margin` words (0, 0: the kernel's constants)."""
+    stream = np.ascontiguousarray(stream, dtype=np.uint32)
+    out = np.zeros(max(1, int(width)), dtype=np.uint16)
+    _check(lib().svx_sample_used_host(ptr(stream if stream.size else np.zeros(1, np.uint32)), C.c_int64(stream.size), C.c_int32(int(n)), C.c_int64(int(lo)),
+                                      C.c_int32(int(width)), C.c_int32({"walk": 0, "sweep": 1}[method]), C.c_int32(int(chunk)), C.c_int32(int(margin)), ptr(out)),
+           "svx_sample_used_host")
+    return out[:int(width)]
 
 
 def vcf_format_std(x):

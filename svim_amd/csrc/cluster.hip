@@ -17,6 +17,7 @@
 // FP64 throughout with the reference's operation order (-ffp-contract=off), so labels are bit-exact.
 #include "common.hpp"
 #include "hostcopy.hpp"
+#include "sample_core.hpp"
 #include <cstdlib>
 
 int svx_launch_edit_pairs(svx_ctx* c, int64_t n_work, const void* work_dev, const ClusterIn& in, int32_t* ed_dev,
@@ -286,9 +287,13 @@ __global__ __launch_bounds__(64) void k_sample_scan(const int32_t* large_list, l
 // ---- Phase A without the serial walk -----------------------------------------------------------------------------------
 // How many words a pool-method partition consumes depends only on its size and on where in the stream it starts.  The host
 // brackets every partition's start (window = expected start -+ 6 sigma, from the exact mean / variance of the rejection
-// sampling), k_sample_tables simulates EVERY (partition, candidate start) with one lane each - ~10^6 independent ~150-word
-// walks, ideal GPU work - and following the chain is one table lookup per partition (k_chase_*).  Any surprise (a start outside its
-// window, a set-method partition, the stream running out) raises `err` and the caller falls back to k_sample_scan.
+// sampling), the consumption table holds the answer for EVERY (partition, candidate start), and following the chain is one table
+// lookup per partition (k_chase_*).  Any surprise (a start outside its window, a set-method partition, the stream running out)
+// raises `err` and the caller falls back to k_sample_scan.
+// The table is made by k_sample_sweep: one wave per 512 starts of a window carries the 101 states of the recurrence of sample_core.hpp
+// backwards over the words, one compare and one select per state and word, and every start it passes reads its count off state 0.
+// k_sample_tables (SVX_SAMPLE_TABLES=walk, read per call: the A/B) walks the ~130-250 words of every start on a lane of its own: the same
+// table from ~200 word tests per start instead of one sweep step.
 struct SampleMeta { long long lo; int width; int n; long long off; };      // window [lo, lo + width), partition size, first table slot
 
 __global__ void k_large_info(const int32_t* large_list, long long n_large, const int64_t* part_start, const uint32_t* sidx, const uint8_t* type,
@@ -313,23 +318,55 @@ __global__ __launch_bounds__(256) void k_sample_tables(const SampleMeta* meta, c
     __syncthreads();
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= m.width) return;
-    long long pos = m.lo + s;
-    const long long start = pos;
-    uint32_t bound = (uint32_t)m.n;
-    bool ok = true;
-    for (int i = 0; i < 100; i++, bound--) {
-        const int k = 32 - __clz((int)bound);           // Random._randbelow_with_getrandbits: k = bound.bit_length()
-        for (;;) {
-            if (pos >= cap) { ok = false; break; }
-            const long long o = pos - base;
-            const uint32_t word = o < SAMPLE_WIN ? win[o] : stream[pos];
-            pos++;
-            if ((word >> (32 - k)) < bound) break;
+    table[m.off + s] = sample_walk(m.n, m.lo + s, cap, [&](long long pos) { const long long o = pos - base; return o < SAMPLE_WIN ? win[o] : stream[pos]; });
+}
+
+// gfx9 DPP wave shifts (as dpp_wave_shr1 of edit.hip), one v_mov_b32_dpp each
+__device__ __forceinline__ uint32_t wave_shl1_zero(uint32_t v) {                 // lane l receives lane l+1's value, lane 63 receives 0 (wave_shl:1)
+    return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x130, 0xf, 0xf, true);
+}
+__device__ __forceinline__ uint32_t wave_shl1(uint32_t v, uint32_t edge) {       // ... lane 63 keeps `edge`
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)edge, (int)v, 0x130, 0xf, 0xf, false);
+}
+__device__ __forceinline__ uint32_t wave_shr1(uint32_t v, uint32_t edge) {       // lane l receives lane l-1's value, lane 0 keeps `edge` (wave_shr:1)
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)edge, (int)v, 0x138, 0xf, 0xf, false);
+}
+
+// The same table from one backward sweep per C starts (sample_core.hpp): one wave per chunk, grid (chunks of the widest window, large partitions).
+// Lane l holds the states l (a) and 36 + l (b): state i + 1 sits one lane above state i and arrives by a wave shift.  b ends with state 99, whose
+// neighbour is T[.][100] = 0 - the zero the shift fills in; a's lane 63 takes state 64 from b's lane 28 by a readlane (the states 36..63 are carried
+// twice: every lane of both registers is a state below 100, no lane needs a mask).  The words come 64 at a time, one per lane, and are handed round by
+// readlane.  The count of a start is state 0 after its step: `res` takes it in at lane 0 and moves on by one lane per step, so the start of lane j's
+// word ends in lane j and the 64 counts of a block leave in one store.  No atomics, no other workgroup is waited for, the trip count is the chunk's
+// length plus the margin; a start the sweep leaves open (its walk is longer than the margin, or runs into cap) takes the walk of k_sample_tables.
+template <int C, int M>
+__global__ __launch_bounds__(64) void k_sample_sweep(const SampleMeta* meta, const uint32_t* stream, long long cap, uint16_t* table) {
+    constexpr int B0 = SAMPLE_DRAWS - 64;                            // first state of b
+    const SampleMeta m = meta[blockIdx.y];
+    const int b = (int)blockIdx.x * C;
+    if (b >= m.width) return;
+    const int lane = lane_id();
+    const long long base = m.lo + b, end = m.lo + (b + C < m.width ? b + C : m.width);
+    const long long top = sample_sweep_top(end, M, cap);            // words at and beyond top are not read: no state accepts there
+    const long long hi = top > end ? top : end;
+    const uint32_t thr_a = sample_threshold(m.n, lane), thr_b = sample_threshold(m.n, B0 + lane);
+    uint32_t ta = SAMPLE_INVALID, tb = SAMPLE_INVALID;
+    for (long long p0 = base + ((hi - base - 1) >> 6) * 64; p0 >= base; p0 -= 64) {
+        const long long q = p0 + lane;
+        const uint32_t w = q < top ? stream[q] : SAMPLE_NO_WORD;
+        uint32_t res = SAMPLE_INVALID;
+#pragma unroll
+        for (int j = 63; j >= 0; j--) {
+            const uint32_t word = (uint32_t)__builtin_amdgcn_readlane((int)w, j);
+            const uint32_t na = wave_shl1(ta, (uint32_t)__builtin_amdgcn_readlane((int)tb, 64 - B0));
+            const uint32_t nb = wave_shl1_zero(tb);
+            ta = sample_sweep_step(ta, na, word, thr_a, 1u);
+            tb = sample_sweep_step(tb, nb, word, thr_b, 1u);
+            res = wave_shr1(res, ta);
         }
-        if (!ok) break;
+        if (q < end)
+            table[m.off + (q - m.lo)] = res < SAMPLE_INVALID ? (uint16_t)res : sample_walk(m.n, q, cap, [&](long long pos) { return stream[pos]; });
     }
-    const long long used = pos - start;
-    table[m.off + s] = (ok && used < 0xffff) ? (uint16_t)used : (uint16_t)0xffff;
 }
 
 // Following the tables is one dependent lookup per partition (0.55 us each for a lone lane).  The chain is therefore cut into runs of
@@ -1274,13 +1311,21 @@ static int svx_cluster_body(svx_ctx* c, const ClusterIn& in, int32_t n_contig, c
     }
     hi_sorted = c->k_hi.as<uint64_t>();
     sidx = c->k_idx.as<uint32_t>();
+    // The haplotype store needs nothing of the partition phase: it is packed as soon as the host has enqueued the sort, when the side stream's word counts
+    // have long arrived (the synchronise in there returns at once), and runs beside the radix passes and the partition scans.
+    // -DSVX_PACK_BEHIND_PARTITIONS: behind the n_part mailbox read, where it was (an A/B build of tools/build_variants.sh, no run-time switch).
+#ifndef SVX_PACK_BEHIND_PARTITIONS
+    SVXCHK(svx_edit_prepack_pack(c, in));
+#endif
     // ---- partitions ------------------------------------------------------------------------------------------------
     SVXCHK(c->part_flag.reserve((size_t)(n + 1) * 8)); SVXCHK(c->part_id.reserve((size_t)(n + 1) * 8));
     k_part_flags<<<GRID(n + 1, T), T, 0, st>>>(in, hi_sorted, hi_shift, sidx, p.partition_max_distance, c->part_flag.as<int64_t>());
     SVXCHK(svx_exclusive_scan_i64(c, c->part_flag.as<int64_t>(), c->part_id.as<int64_t>(), n + 1));
     int64_t n_part = 0;
     SVXCHK(svx_mail_read(c, st, c->part_id.as<int64_t>() + n, 1, &n_part));
+#ifdef SVX_PACK_BEHIND_PARTITIONS
     SVXCHK(svx_edit_prepack_pack(c, in));
+#endif
     SVXCHK(c->part_start.reserve((size_t)(n_part + 1) * 8));
     k_part_starts<<<GRID(n + 1, T), T, 0, st>>>(c->part_flag.as<int64_t>(), c->part_id.as<int64_t>(), n, c->part_start.as<int64_t>(), n_part);
     // per-partition sizes -> sample base, large-partition slots, INS pair slots (5 arrays of n_part+1 int64 in part_meta)
@@ -1352,8 +1397,13 @@ static int svx_cluster_body(svx_ctx* c, const ClusterIn& in, int32_t n_contig, c
         SVXCHK(svx_h2d(plan.meta_dev, plan.meta.data(), (size_t)n_large * sizeof(SampleMeta), st));
         SVXCHK(svx_h2d(plan.runs_dev, plan.runs.data(), (size_t)plan.n_runs * sizeof(ChaseRun), st));
         HIPCHK(hipMemcpyAsync(plan.trb_dev, plan.type_run_begin, sizeof plan.type_run_begin, hipMemcpyHostToDevice, st));
-        k_sample_tables<<<dim3((unsigned)((plan.max_width + 255) / 256), (unsigned)n_large), 256, 0, st>>>(plan.meta_dev, c->mt_words.as<uint32_t>(), c->mt_have,
-                                                                                                         c->samp_table.as<uint16_t>());
+        const char* how = getenv("SVX_SAMPLE_TABLES");                    // =walk: one walk per candidate start (the A/B of the sweep), read per call
+        if (how && !strcmp(how, "walk"))
+            k_sample_tables<<<dim3((unsigned)((plan.max_width + 255) / 256), (unsigned)n_large), 256, 0, st>>>(plan.meta_dev, c->mt_words.as<uint32_t>(), c->mt_have,
+                                                                                                             c->samp_table.as<uint16_t>());
+        else
+            k_sample_sweep<SAMPLE_SWEEP_C, SAMPLE_SWEEP_M><<<dim3((unsigned)((plan.max_width + SAMPLE_SWEEP_C - 1) / SAMPLE_SWEEP_C), (unsigned)n_large), 64, 0, st>>>(
+                plan.meta_dev, c->mt_words.as<uint32_t>(), c->mt_have, c->samp_table.as<uint16_t>());
         k_chase_runs<<<dim3((unsigned)((plan.max_width + 255) / 256), (unsigned)plan.n_runs), 256, 0, st>>>(plan.meta_dev, plan.runs_dev, c->samp_table.as<uint16_t>(), plan.ends_dev);
         HIPCHK(hipGetLastError());
         return SVX_OK;

@@ -2212,13 +2212,14 @@ int svx_edit_distance_pairs(svx_ctx* c, int64_t n_pairs, const uint8_t* codes_de
 // The packed store of a CLUSTER call does not depend on the pair list except through the flank radius, and every pair that needs an edit
 // distance has |start_a - start_b| <= 2 * cluster_max_distance * position_distance_normalizer (ins_needs_edit in cluster.hip): with that bound as
 // radius the store is built on a side stream while the main stream sorts, partitions and samples.  begin: word counts + offsets (enqueue only);
-// pack: called after the caller's next host synchronisation - reads the total, reserves, packs, records ev[18].
-// The store is built on the high-priority stream of the full-matrix rounds (idle at that time): on the HiFi-like stand-in k_edit_prep waits for it, and at the
-// main stream's priority or below it arrives 0.6-0.9 ms later (profiles/r06_prepack_priority_ab.txt).  What the high priority cost configs[1] - the main stream's
-// one-workgroup scans of the partition sizes waited 0.04-0.4 ms each for a CU with sixteen free wave slots while the store's blocks were being dispatched - is
-// taken care of in scan.hpp (256-thread workgroups for small scans).  SVX_PREPACK_PRIO=normal / low: A/B.
+// pack: called once the caller has enqueued its ordering sort (the word counts have arrived by then) - reads the total, reserves, packs, records ev[18].
+// Priority: packed from behind the partition count, as it was until the sampling tables came from one sweep, the store had to be on the high-priority stream of the
+// full-matrix rounds - on the HiFi-like stand-in k_edit_prep waits for it, and at the main stream's priority it arrived 0.6-0.9 ms later
+// (profiles/r06_prepack_priority_ab.txt; still +0.9 ms per step with the pack at that place, profiles/sample_sweep_ab_c2.txt).  Started behind the sort it has
+// the whole partition phase to itself and runs at the main stream's priority: at high priority its blocks take the CUs from the latency-bound kernels of that phase
+// (configs[1]: cluster_partition_sample_ms 0.82 against 0.73 ms).  SVX_PREPACK_PRIO=high / low: A/B.
 static hipStream_t prepack_stream(svx_ctx* c) {
-    static const int which = []() { const char* e = getenv("SVX_PREPACK_PRIO"); return e && !strcmp(e, "normal") ? 6 : (e && !strcmp(e, "low") ? 0 : 2); }();
+    static const int which = []() { const char* e = getenv("SVX_PREPACK_PRIO"); return e && !strcmp(e, "high") ? 2 : (e && !strcmp(e, "low") ? 0 : 6); }();
     return c->aux[which];
 }
 
