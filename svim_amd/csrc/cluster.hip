@@ -1313,19 +1313,14 @@ static int svx_cluster_body(svx_ctx* c, const ClusterIn& in, int32_t n_contig, c
     sidx = c->k_idx.as<uint32_t>();
     // The haplotype store needs nothing of the partition phase: it is packed as soon as the host has enqueued the sort, when the side stream's word counts
     // have long arrived (the synchronise in there returns at once), and runs beside the radix passes and the partition scans.
-    // -DSVX_PACK_BEHIND_PARTITIONS: behind the n_part mailbox read, where it was (an A/B build of tools/build_variants.sh, no run-time switch).
-#ifndef SVX_PACK_BEHIND_PARTITIONS
+    // (Until then it was packed behind the n_part mailbox read: DESIGN section 30.)
     SVXCHK(svx_edit_prepack_pack(c, in));
-#endif
     // ---- partitions ------------------------------------------------------------------------------------------------
     SVXCHK(c->part_flag.reserve((size_t)(n + 1) * 8)); SVXCHK(c->part_id.reserve((size_t)(n + 1) * 8));
     k_part_flags<<<GRID(n + 1, T), T, 0, st>>>(in, hi_sorted, hi_shift, sidx, p.partition_max_distance, c->part_flag.as<int64_t>());
     SVXCHK(svx_exclusive_scan_i64(c, c->part_flag.as<int64_t>(), c->part_id.as<int64_t>(), n + 1));
     int64_t n_part = 0;
     SVXCHK(svx_mail_read(c, st, c->part_id.as<int64_t>() + n, 1, &n_part));
-#ifdef SVX_PACK_BEHIND_PARTITIONS
-    SVXCHK(svx_edit_prepack_pack(c, in));
-#endif
     SVXCHK(c->part_start.reserve((size_t)(n_part + 1) * 8));
     k_part_starts<<<GRID(n + 1, T), T, 0, st>>>(c->part_flag.as<int64_t>(), c->part_id.as<int64_t>(), n, c->part_start.as<int64_t>(), n_part);
     // per-partition sizes -> sample base, large-partition slots, INS pair slots (5 arrays of n_part+1 int64 in part_meta)

@@ -260,13 +260,9 @@ __device__ __forceinline__ int full_class_for(int m) {
     if (m <= 512) return CLS_LANE0 + lane_class_for(m);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-#ifndef SVX_NO_WIDE1014
         if (m <= (640 << k)) return CLS_WIDE10 + k;
-#endif
         if (m <= (768 << k)) return CLS_WIDE12 + k;
-#ifndef SVX_NO_WIDE1014
         if (m <= (896 << k)) return CLS_WIDE14 + k;
-#endif
         if (m <= (1024 << k)) return CLS_WIDE0 + k;
     }
     return CLS_FULL;
@@ -504,17 +500,8 @@ __global__ __launch_bounds__(256) void k_edit_prep(long long n_work, PairSource 
 }
 
 // first class of every pair + its sort key (one thread per pair)
-// classes whose round-0 pairs run in row blocks (SVX_EDIT_BLOCKED): the 2- and 4-lane families (<= 4 blocks: the blocks of a pair are serial launches); words per block
-__host__ __device__ __forceinline__ int blocked_words(int cls, int kmax) {
-    if (cls >= CLS_WIDE0 && cls <= CLS_WIDE0 + kmax) return 16;
-    if (cls >= CLS_WIDE12 && cls <= CLS_WIDE12 + kmax) return 12;
-    if (cls >= CLS_WIDE14 && cls <= CLS_WIDE14 + kmax) return 14;
-    if (cls >= CLS_WIDE10 && cls <= CLS_WIDE10 + kmax) return 10;
-    return 0;
-}
-__global__ void k_edit_classify(long long n_work, PairDesc* desc, uint64_t* sort_key, uint32_t* sort_val, int force_full, unsigned long long* guess_word, int few_pairs_flags) {
+__global__ void k_edit_classify(long long n_work, PairDesc* desc, uint64_t* sort_key, uint32_t* sort_val, int force_full, unsigned long long* guess_word, int few_pairs) {
     const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int few_pairs = few_pairs_flags & 1, blocked_kmax = (few_pairs_flags >> 1) - 1;          // -1: no blocked route
     if (w >= n_work) return;
     const PairDesc pd = desc[w];
     if (pd.cls == -1) return;                               // empty core: answered by k_edit_prep, key already written
@@ -547,17 +534,7 @@ __global__ void k_edit_classify(long long n_work, PairDesc* desc, uint64_t* sort
         cls = pd.m <= 4096 ? CLS_WIDE0 + 2 : (pd.m <= 6144 ? CLS_WIDE12 + 3 : (pd.m <= 8192 ? CLS_WIDE0 + 3 : CLS_FULL));
     const int flagged = cls | (pd.cls & ~0xff);
     desc[w].cls = flagged;
-    int cost_n = pd.n;
-    const int bq = blocked_kmax >= 0 ? blocked_words(cls, blocked_kmax) : 0;
-    if (bq) {
-        // a row block walks 32 Q + (length gap) + 2 x columns (d_edit_blocked): pairs that share a wave should agree on THAT; and the longest text of the
-        // blocked pairs sizes their boundary words (guess_word[1], read by the host with the class bounds)
-        int ub = pd.ub; if (ub > pd.m + pd.n) ub = pd.m + pd.n; if (ub < pd.n - pd.m) ub = pd.n - pd.m;
-        const long long walk = 32ll * bq + (pd.n - pd.m) + 2ll * ((ub - (pd.n - pd.m)) / 2 + 1);
-        cost_n = walk < pd.n ? (int)walk : pd.n;
-        if ((unsigned long long)pd.n > __hip_atomic_load(guess_word + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(guess_word + 1, (unsigned long long)pd.n);
-    }
-    sort_key[w] = sort_key_of(sort_class(flagged), work_key(cls, pd.m, cost_n));
+    sort_key[w] = sort_key_of(sort_class(flagged), work_key(cls, pd.m, pd.n));
     sort_val[w] = (uint32_t)w;
 }
 
@@ -1152,103 +1129,6 @@ __device__ __forceinline__ void d_edit_lane(long long blk, long long count, cons
     if (live) ed[slot_of ? slot_of[widx] : (long long)widx] = score;
 }
 
-// ---- 3d. full matrix in ROW BLOCKS: one lane per (pair, block of 32 Q rows), the blocks of a pair in successive launches (round 6, SVX_EDIT_BLOCKED=1) --------
-// The multi-lane forms below sweep the text in lock step: a lane whose rows lie outside the band the pair's upper bound allows - the two corner triangles of a
-// pair whose length gap exceeds every band - idles while its wave still pays for the column.  Here block r of a pair (rows r * 32 Q - pad + 1 .. of the
-// bottom-aligned pattern, pad in block 0) is a task of its own: it walks only the columns jlo .. jhi its rows can meet on diagonals -x .. delta + x
-// (x = floor((ub - delta) / 2) + 1: a path of cost <= ub leaves the corridor 0 .. delta by no more), 64 pairs per wave like d_edit_lane, no hand-off between
-// lanes.  What it needs from the block above - the horizontal delta of that block's last row, two bits per column - comes through memory (written by the launch
-// of rank r - 1; columns behind that block's range step +1), together with the value of its last row in front of this block's first column; the column in
-// front of the block's range steps +1 per row.  Both assumptions are upper bounds of cells no path of cost <= ub visits (the cut-off argument of the staircase
-// window), so the last block's last row ends at the distance.  Deltas stay in {-1, 0, +1}: the boundaries are.
-struct BlkArgs { int rank; uint32_t* bnd_in; uint32_t* bnd_out; int* e_in; int* e_out; long long wmax; };
-__device__ __forceinline__ long long blk_word_at(long long slot, long long wmax, int wi, int plane) { return (((slot >> 6) * wmax + wi) * 2 + plane) * 64 + (slot & 63); }
-
-template <int Q, int P>
-__device__ __forceinline__ void d_edit_blocked(const BlkArgs& A, long long slot_base, long long blk, long long count, const uint32_t* list, const uint32_t* scratch,
-                                               const PairDesc* desc, const long long* slot_of, int32_t* ed, unsigned long long* wc) {
-    constexpr int RL = 32 * Q;
-    const long long t = blk * 256 + threadIdx.x;
-    bool live = t < count;
-    uint32_t widx = 0;
-    PairDesc pd; pd.m = 1; pd.n = 1; pd.pat = 0; pd.txt = 0; pd.ub = 2; pd.cls = 0;
-    if (live) { widx = list[t]; pd = desc[widx]; }
-    const long long slot = slot_base + t;
-    const int m = pd.m, n = pd.n, r = A.rank;
-    const int B = (m + RL - 1) / RL;
-    if (r >= B) live = false;
-    const int pad = B * RL - m, delta = n - m;
-    int ub = pd.ub; if (ub > m + n) ub = m + n; if (ub < delta) ub = delta;
-    const int x = (ub - delta) / 2 + 1;
-    const int ihi = (r + 1) * RL - pad, ilo = r * RL - pad + 1 > 1 ? r * RL - pad + 1 : 1;
-    const int jlo = ilo - x > 1 ? ilo - x : 1;
-    const long long jhi_l = (long long)ihi + delta + x;
-    const int jhi = jhi_l > n ? n : (int)jhi_l;
-    const long long jhp_l = (long long)(r * RL - pad) + delta + x;                       // last column of the block above
-    const int jhi_prev = jhp_l > n ? n : (int)jhp_l;
-    const int jlo_next = ihi + 1 - x > 1 ? ihi + 1 - x : 1;                              // first column of the block below
-    const int len = live && jhi >= jlo ? jhi - jlo + 1 : 0;
-    const Packed pat{scratch + pd.pat, CLS_PAT_SH(pd.cls)};
-    const int ts = (CLS_TXT_SH(pd.cls) >> 2) + jlo - 1;                                 // text symbol of column jlo, counted from the record word pd.txt
-    const Packed txt{scratch + pd.txt + (ts >> 3), (ts & 7) << 2};
-    uint32_t pv[Q], mv[Q], pl[P][Q];
-#pragma unroll
-    for (int q = 0; q < Q; q++) {
-        const int nvirt = r == 0 ? pad - 32 * q : 0;                                    // virtual rows above row 1 (block 0 only): vertical delta -1
-        const uint32_t mlow = nvirt >= 32 ? 0xffffffffu : (nvirt <= 0 ? 0u : ((1u << nvirt) - 1u));
-        mv[q] = mlow; pv[q] = ~mlow;
-        uint32_t e[P];
-        planes32_at<P>(pat, r * RL + 32 * q - pad, live, e);
-#pragma unroll
-        for (int b = 0; b < P; b++) pl[b][q] = e[b];
-    }
-    // value of the block's last row in front of its first column: column 0 (D[i][0] = i), or what the block above handed over + one per row
-    int cur = jlo == 1 ? ihi : (live ? A.e_in[slot] : 0) + RL;
-    int lenmax = len;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const int v = __shfl_xor(lenmax, o, 64); lenmax = v > lenmax ? v : lenmax; }
-    const int txt_words = (len + 7) >> 3;
-    uint32_t tw_next = txt_words > 0 ? txt.word(0) : 0u;
-    uint32_t in_p = 0u, in_m = 0u, out_p = 0u, out_m = 0u;
-    const bool has_above = r > 0, has_below = r + 1 < B;
-    for (int cb = 0; cb * 8 < lenmax; cb++) {
-        const uint32_t tw = tw_next;
-        tw_next = (cb + 1 < txt_words) ? txt.word(cb + 1) : 0u;
-        uint32_t tp[P];
-        planes8<P>(tw, tp);
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const int c = cb * 8 + k;
-            if (c < len) {
-                const int a = jlo - 1 + c, sh = a & 31;                                 // column j = a + 1; its bit in the boundary words
-                unsigned cyp = 1, cym = 0;
-                if (has_above) {
-                    if (c == 0 || sh == 0) { in_p = A.bnd_in[blk_word_at(slot, A.wmax, a >> 5, 0)]; in_m = A.bnd_in[blk_word_at(slot, A.wmax, a >> 5, 1)]; }
-                    if (a < jhi_prev) { cyp = (in_p >> sh) & 1u; cym = (in_m >> sh) & 1u; }
-                }
-                uint32_t nk[P];
-#pragma unroll
-                for (int b = 0; b < P; b++) nk[b] = ((tp[b] >> k) & 1u) - 1u;
-                unsigned carry = 0;
-                const uint32_t hin_m = cym;
-                uint32_t ph_last, mh_last;
-                MYERS_COLUMN_B(Q, P, pl, pv, mv, nk, hin_m, carry, cyp, cym, ph_last, mh_last)
-                cur += (int)cyp - (int)cym;                                             // the bits pushed out of the last word: the horizontal delta of the block's last row
-                if (has_below) {
-                    out_p |= cyp << sh; out_m |= cym << sh;
-                    if (sh == 31 || c == len - 1) {
-                        A.bnd_out[blk_word_at(slot, A.wmax, a >> 5, 0)] = out_p; A.bnd_out[blk_word_at(slot, A.wmax, a >> 5, 1)] = out_m;
-                        out_p = 0u; out_m = 0u;
-                    }
-                    if (a + 1 == jlo_next - 1) A.e_out[slot] = cur;
-                }
-            }
-        }
-    }
-    wc_account(wc, (long long)lenmax * Q * 64, (long long)len * Q);
-    if (live && !has_below) ed[slot_of ? slot_of[widx] : (long long)widx] = cur;
-}
-
 // ---- 3c. full matrix, G lanes per pair, 32 Q rows (Q = 16 or 12 words) per lane ------------------------------------------------
 // The column is ONE wide bit-vector spread over the first L = ceil(m / (32 Q)) lanes of a group, bottom-aligned like above (row m is
 // bit 31 of lane L-1's last word); lane g of a group works on text column t-g at step t and hands (symbol, adder carry,
@@ -1581,25 +1461,6 @@ __global__ __launch_bounds__(256) void k_edit_fulls(FusedTab tab, const uint32_t
     }
 }
 
-// the row-block launches of the classes below (SVX_EDIT_BLOCKED): one launch per block rank, segments as in k_edit_fulls; slot_base[s] = position of the
-// segment's first pair among the blocked pairs of the round (the index of its boundary words)
-struct BlkTab { long long slot_base[SEG_MAX]; };
-template <int P>
-__global__ __launch_bounds__(256) void k_edit_blocked(FusedTab tab, BlkTab bt, BlkArgs A, const uint32_t* list, const uint32_t* scratch, const PairDesc* desc,
-                                                      const long long* slot_of, int32_t* ed, unsigned long long* wc) {
-    int s = 0;
-    while (s + 1 < tab.n && blockIdx.x >= tab.first_block[s + 1]) s++;
-    const long long blk = (long long)(blockIdx.x - tab.first_block[s]);
-    const uint32_t* l = list + tab.lo[s];
-    switch (tab.kind[s]) {
-        case 10: d_edit_blocked<10, P>(A, bt.slot_base[s], blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case 12: d_edit_blocked<12, P>(A, bt.slot_base[s], blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case 14: d_edit_blocked<14, P>(A, bt.slot_base[s], blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        default: d_edit_blocked<16, P>(A, bt.slot_base[s], blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-    }
-}
-
-
 __global__ __launch_bounds__(64) void k_edit_full_big(long long count, const uint32_t* big_list, const long long* state_off, const uint32_t* scratch,
                                                       const PairDesc* desc, const long long* slot_of, int32_t* ed, uint32_t* state) {
     const long long q = blockIdx.x;
@@ -1617,16 +1478,8 @@ __global__ void k_slots(long long n_work, PairSource src, long long* slot_of) {
 }
 
 // class boundaries in the sorted key array: first index whose sort class >= c, for c = 0..N_SORT_CLASSES
-// threads 128 .. 191 (row-block route): split[c] = first index of class c whose cost order is at most `limit` (the pairs of a class are sorted by descending cost)
-__global__ void k_class_bounds(const uint64_t* keys, long long n, long long* bounds, long long* split, long long limit) {
+__global__ void k_class_bounds(const uint64_t* keys, long long n, long long* bounds) {
     const int c = threadIdx.x;
-    if (c >= 128 && c < 128 + N_SORT_CLASSES && split) {
-        const unsigned long long top = (1ull << SORT_COST_BITS) - 1, want = sort_key_of((unsigned long long)(c - 128), top - (unsigned long long)(limit < 0 ? 0 : ((unsigned long long)limit > top ? top : limit)));
-        long long lo = 0, hi = n;
-        while (lo < hi) { const long long mid = (lo + hi) >> 1; if (keys[mid] < want) lo = mid + 1; else hi = mid; }
-        split[c - 128] = lo;
-        return;
-    }
     if (c > N_SORT_CLASSES) return;
     long long lo = 0, hi = n;
     while (lo < hi) { const long long mid = (lo + hi) >> 1; if ((long long)(keys[mid] >> SORT_COST_BITS) < c) lo = mid + 1; else hi = mid; }
@@ -1710,20 +1563,306 @@ static float guess_from_histogram(const unsigned long long* h, float fallback) {
     return (float)((best + 2) / 256.0);
 }
 
-static int run_edit_pipeline(svx_ctx* c, long long n_work, const PairSource& src_in, int32_t* ed_dev, unsigned long long* cells_dev) {
-    if (n_work <= 0) return SVX_OK;
-    if (n_work >= (1ll << 32)) return svx_fail(SVX_E_ARG, "more than 2^32 edit-distance pairs in one call", __FILE__, __LINE__, hipSuccess);
-    hipStream_t st = c->stream;
-    const int T = 256;
-    PairSource src = src_in;
-    src.n_pairs = n_work;
-    const size_t WC_OFF = 128 + MAX_ROUNDS * N_SORT_CLASSES, WC_PER_LAUNCH = 2 * WC_SHARDS, EARLY_OFF = WC_OFF + MAX_ROUNDS * 2 * WC_PER_LAUNCH, CNT_WORDS = EARLY_OFF + 2 * N_SORT_CLASSES;
-    SVXCHK(c->e_fail.reserve(CNT_WORDS * 8));
-    unsigned long long* cnt = c->e_fail.as<unsigned long long>();        // [1] big pairs, [8..40] class bounds of round 0 (first [16..31] the span shards), [128 + 64 r ..] retry counters written by round r, [WC_OFF ..] word-column counters per (round, kind)
-    HIPCHK(hipMemsetAsync(cnt, 0, CNT_WORDS * 8, st));
-    // cnt[2]: the speculation fraction k_edit_classify reads (float bits) - the fallback here, overwritten by k_edit_guess when the call is sampled
-    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(cnt + 2), (int)__builtin_bit_cast(uint32_t, c->edit_guess), 1, st));
-    // 1. packed store: one record per string / signature
+// The switches of one call, read once at its top (a process may change them between two calls); what each means and its default stands here and nowhere else.
+// None of them changes a distance.  SVX_EDIT_GUESS, SVX_EDIT_FORCE_FULL and SVX_MAILBOX belong to the context (svx_ctx_create, api.hip), SVX_EDIT_NO_PREPACK to
+// svx_edit_prepack_begin below.
+struct EditSwitches {
+    int shift_bounds = 1;             // SVX_EDIT_SHIFT_BOUNDS=0: upper bounds from the left-justified alignment only (A/B switch)
+    int prep_depth = PREP_DEPTH;      // SVX_EDIT_PREP_DEPTH=1|2|4|8: chunks per lane in the later trips of a bound pass (1 = rounds 1-6; A/B switch)
+    int narrow_windows = 1;           // SVX_EDIT_NARROW=0: static staircase windows (A/B switch; results are the same either way)
+    long long few_pairs = 2048;       // SVX_EDIT_FEW_PAIRS: calls with at most this many pairs take the low-latency route (0 = never)
+    // A retry round with only a few band pairs is bound by the LATENCY of its slowest pair: a band retry walks its columns in one lane with 6-16 state words
+    // (configs[1], round 1: 196 pairs, one wave of 16-word windows = 0.31 ms at the very end of the window), a full matrix spread over the 64 lanes of a wave
+    // (KIND_RETRY) finishes the same pair in a fifth of that and never fails, so the round is also the last.  Up to this many band pairs of a retry round go there
+    // (SVX_EDIT_RETRY_FULL, 0 = never; the distances are exact either way).
+    long long retry_full = 4096;
+    bool no_early = false;            // SVX_EDIT_NO_EARLY: round 0 launches its band classes in one part (no early retries of the widest classes' failures)
+    bool no_ll = false;               // SVX_EDIT_NO_LL: no low-latency forms of the long full-matrix classes
+    bool profile = false;             // SVX_EDIT_PROFILE: per-class work, band fit, corner analysis and the exact histogram on stderr (reads the device back: not for timing)
+    bool serial = false;              // SVX_EDIT_SERIAL: every launch of the rounds alone on the device and timed (edit_launch lines on stderr); no early part
+};
+static EditSwitches read_edit_switches() {
+    EditSwitches sw;
+    if (const char* e = getenv("SVX_EDIT_SHIFT_BOUNDS")) sw.shift_bounds = atoi(e) == 0 ? 0 : 1;
+    if (const char* e = getenv("SVX_EDIT_PREP_DEPTH")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) sw.prep_depth = v; }
+    if (const char* e = getenv("SVX_EDIT_NARROW")) sw.narrow_windows = atoi(e) == 0 ? 0 : 1;
+    if (const char* e = getenv("SVX_EDIT_FEW_PAIRS")) sw.few_pairs = atoll(e);
+    if (const char* e = getenv("SVX_EDIT_RETRY_FULL")) sw.retry_full = atoll(e);
+    sw.no_early = getenv("SVX_EDIT_NO_EARLY") != nullptr;
+    sw.no_ll = getenv("SVX_EDIT_NO_LL") != nullptr;
+    sw.profile = getenv("SVX_EDIT_PROFILE") != nullptr;
+    sw.serial = getenv("SVX_EDIT_SERIAL") != nullptr;
+    return sw;
+}
+
+// counter words of a call (svx_ctx::e_fail): [1] big pairs, [2] the speculation fraction k_edit_classify reads, [8..72] class bounds of round 0 (first [16..31] the span
+// shards), [128 + 64 r ..] retry counters written by round r, [WC_OFF ..] word-column counters per (round, kind), [EARLY_OFF ..] retry counters of round 0's two early launches
+static const size_t WC_OFF = 128 + MAX_ROUNDS * N_SORT_CLASSES, WC_PER_LAUNCH = 2 * WC_SHARDS, EARLY_OFF = WC_OFF + MAX_ROUNDS * 2 * WC_PER_LAUNCH, CNT_WORDS = EARLY_OFF + 2 * N_SORT_CLASSES;
+static const int EDIT_T = 256;        // threads per block of the launches below
+
+// what the stages of one call share
+struct EditCall {
+    svx_ctx* c; hipStream_t st;
+    long long n_work; PairSource src; int32_t* ed_dev; unsigned long long* cells_dev;
+    EditSwitches sw;
+    unsigned long long* cnt;                                  // the counter words (layout above)
+    hipStream_t band_st[2], full_st[2], early_st[2];          // A/C/G/T-only pairs, generic pairs | even / odd rounds | the early parts of the two alphabets in round 0
+    uint64_t* key_a; uint64_t* key_b; uint32_t* val_a; uint32_t* val_b;
+    long long* slot_of; PairDesc* desc; uint32_t* scratch;
+    long long bounds[N_SORT_CLASSES + 1];                     // class bounds in the sorted list val_b
+    std::vector<PairDesc> first_desc;                         // SVX_EDIT_PROFILE: the descriptors as round 0 saw them (first class of every pair)
+};
+
+// what the launches of one round share
+struct EarlyPost { unsigned long long ticket; int generic, set; };
+struct EditRound {
+    int round;
+    long long pending;                                        // pairs of the round = slots of every retry list it appends to
+    const uint32_t* list; const long long* seg_lo; const long long* seg_cn;      // the round's pairs: one segment of `list` per sort class
+    unsigned long long* fail_cnt; uint32_t* fail_list;        // retry counters and lists the band launches append to
+    unsigned long long* fail_cnt_early[2]; uint32_t* fail_list_early[2];         // the same of the two early launches of round 0
+    unsigned long long* wc_band; unsigned long long* wc_full;
+    int split_cls;                                            // first band class of round 0's early part
+    bool band_used[2], split_used[2];
+    std::vector<EarlyPost> early_posts;
+};
+
+// ---- SVX_EDIT_PROFILE: everything below runs only under that switch ----------------------------------------------------
+static int profile_pilot_guess(const EditCall& ec, long long n_samp) {
+    unsigned long long gw = 0;
+    SVXCHK(svx_mail_read(ec.c, ec.st, ec.cnt + 2, 1, &gw));
+    fprintf(stderr, "{\"edit_guess_pilot\": %.4f, \"sampled_pairs\": %lld}\n", __builtin_bit_cast(float, (uint32_t)gw), n_samp);
+    return SVX_OK;
+}
+
+static int profile_round_start(EditCall& ec, const EditRound& r) {
+    profile_round(ec.c, r.round, r.seg_lo, r.seg_cn, r.list, ec.desc, ec.n_work);
+    if (r.round == 0) {
+        ec.first_desc.resize((size_t)ec.n_work);
+        SVXCHK(svx_d2h(ec.first_desc.data(), ec.desc, (size_t)ec.n_work * sizeof(PairDesc), ec.st));
+    }
+    return SVX_OK;
+}
+
+// how much wider than necessary was the first band of every pair?  (needed = narrowest band class that certifies the distance found in the end) - and the corners of
+// round 0's full matrices
+static int profile_band_fit_and_corners(const EditCall& ec) {
+    const long long n_work = ec.n_work;
+    const long long* slot_of = ec.slot_of;
+    const std::vector<PairDesc>& first_desc = ec.first_desc;
+    std::vector<long long> slot((size_t)n_work);
+    long long n_slot = n_work;
+    if (slot_of) {
+        SVXCHK(svx_d2h(slot.data(), slot_of, (size_t)n_work * 8, ec.st));
+        for (long long w = 0; w < n_work; w++) if (slot[(size_t)w] + 1 > n_slot) n_slot = slot[(size_t)w] + 1;
+    }
+    std::vector<int32_t> ed((size_t)n_slot);
+    SVXCHK(svx_d2h(ed.data(), ec.ed_dev, (size_t)n_slot * 4, ec.st));
+    double used[N_CLASSES] = {0}, need[N_CLASSES] = {0}, failed[N_CLASSES] = {0}; long long cnt_c[N_CLASSES] = {0};
+    double ratio_hist[8] = {0};
+    auto h_need_class = [](int m, int n, int d) { int x = (d - (n - m)) / 2; if (x < 0) x = 0; const int nw = (n - m) + 2 * x + 1;
+        for (int b = 0; b < NBAND; b++) if (nw + (b < FIRST_STAIR_CLS ? 14 : 46) <= 32 * band_words(b)) return b; return (int)CLS_FULL; };
+    for (long long w = 0; w < n_work; w++) {
+        const PairDesc& pd = first_desc[(size_t)w];
+        if (pd.cls == -1) continue;
+        const int cls = pd.cls & 0xff;
+        if (cls >= NBAND) continue;
+        const int d = ed[(size_t)(slot_of ? slot[(size_t)w] : w)];
+        const int nc = h_need_class(pd.m, pd.n, d);
+        const double u = (double)pd.n * band_words(cls), nd = (double)pd.n * (nc < NBAND ? band_words(nc) : (pd.m + 31) / 32);
+        cnt_c[cls]++; used[cls] += u;
+        if (nc <= cls) { need[cls] += nd; int r = band_words(cls) * 4 / band_words(nc) - 4; if (r > 7) r = 7; ratio_hist[r] += u; }
+        else failed[cls] += u;
+    }
+    // The full matrices of round 0 (pairs whose length gap exceeds every band): how many of their word-columns (32 rows x 1 column) lie outside the diagonals
+    // [-x, (n - m) + x] a tile decomposition could skip?  x from the upper bound the pair came with (what such a kernel would know beforehand) and from the
+    // distance found in the end (perfect foresight).  A word of rows [32 w, 32 w + 31] is needed in the columns 32 w - x .. 32 w + 31 + (n - m) + x
+    for (int grp = 0; grp < 2; grp++) {                                          // 0: whole pattern in one lane (<= 512 rows), 1: the multi-lane forms
+        double all = 0, by_ub = 0, by_d = 0; long long pairs = 0;
+        for (long long w = 0; w < n_work; w++) {
+            const PairDesc& pd = first_desc[(size_t)w];
+            if (pd.cls == -1) continue;
+            const int cls = pd.cls & 0xff;
+            if (cls < NBAND || (cls >= (int)CLS_LANE0 && cls < (int)CLS_WIDE0) != (grp == 0)) continue;
+            const int d = ed[(size_t)(slot_of ? slot[(size_t)w] : w)], m = pd.m, n = pd.n, gap = n - m;
+            if (gap < 0) continue;
+            pairs++;
+            for (int which = 0; which < 2; which++) {
+                const int bound = which == 0 ? (pd.ub < m + n ? pd.ub : m + n) : d;
+                const int x = bound > gap ? (bound - gap + 1) / 2 : 0;
+                double cols = 0;
+                for (int r0 = 0; r0 < m; r0 += 32) {
+                    int lo = r0 - x, hi = r0 + 31 + gap + x;
+                    if (lo < 0) lo = 0;
+                    if (hi > n - 1) hi = n - 1;
+                    cols += hi >= lo ? hi - lo + 1 : 0;
+                }
+                (which == 0 ? by_ub : by_d) += cols;
+            }
+            all += (double)n * ((m + 31) / 32);
+        }
+        fprintf(stderr, "{\"edit_full_matrix_corners\": {\"form\": \"%s\", \"pairs\": %lld, \"word_cols\": %.4g, \"inside_band_of_upper_bound\": %.4g, \"inside_band_of_final_distance\": %.4g, "
+                        "\"skippable_fraction_known_beforehand\": %.4f, \"skippable_fraction_perfect_foresight\": %.4f}}\n",
+                grp == 0 ? "one lane per pair" : "multi-lane", pairs, all, by_ub, by_d, all > 0 ? 1.0 - by_ub / all : 0.0, all > 0 ? 1.0 - by_d / all : 0.0);
+    }
+    for (int b = 0; b < NBAND; b++) if (cnt_c[b])
+        fprintf(stderr, "{\"edit_band_fit\": {\"first_cls\": %d, \"words\": %d, \"pairs\": %lld, \"word_cols_first_band\": %.4g, \"of_which_failed\": %.4g, \"word_cols_narrowest_sufficient\": %.4g}}\n",
+                b, band_words(b), cnt_c[b], used[b], failed[b], need[b]);
+    fprintf(stderr, "{\"edit_band_fit_ratio_hist\": {\"bins\": \"first band / narrowest sufficient band in [1, 1.25), [1.25, 1.5) ... >= 2.75, weighted by word-columns\", \"h\": [%.4g, %.4g, %.4g, %.4g, %.4g, %.4g, %.4g, %.4g]}}\n",
+            ratio_hist[0], ratio_hist[1], ratio_hist[2], ratio_hist[3], ratio_hist[4], ratio_hist[5], ratio_hist[6], ratio_hist[7]);
+    return SVX_OK;
+}
+
+// the divergence histogram of the exact distances, next to what the pilot guessed from its sample
+static int profile_exact_histogram(const EditCall& ec, float guess) {
+    svx_ctx* c = ec.c;
+    SVXCHK(c->e_hist.reserve(256 * 8));
+    HIPCHK(hipMemsetAsync(c->e_hist.p, 0, 256 * 8, ec.st));
+    k_edit_hist<<<(unsigned)(c->n_cu * 2), 256, 0, ec.st>>>(ec.n_work, ec.desc, ec.slot_of, ec.ed_dev, c->e_hist.as<unsigned long long>());
+    unsigned long long h[256];
+    HIPCHK(hipMemcpyAsync(h, c->e_hist.p, sizeof h, hipMemcpyDeviceToHost, ec.st));
+    HIPCHK(hipStreamSynchronize(ec.st));
+    double total = 0, acc = 0;
+    for (int b = 0; b < 256; b++) total += (double)h[b];
+    fprintf(stderr, "{\"edit_guess_used\": %.4f, \"edit_guess_exact_histogram\": %.4f, \"cum_weight_by_bin\": [", guess, guess_from_histogram(h, guess));
+    for (int b = 0; b < 256; b++) { acc += (double)h[b]; if (b % 8 == 7) fprintf(stderr, "%.3f%s", total > 0 ? acc / total : 0.0, b == 255 ? "" : ", "); }
+    fprintf(stderr, "]}\n");
+    return SVX_OK;
+}
+
+// ---- the three launches of the rounds ------------------------------------------------------------------------------------
+// full-matrix launch of one alphabet from per-class segments (lo / cn_of indexed by sort class) of `lst`
+static int launch_fulls(const EditCall& ec, int generic, const long long* lo, const long long* cn_of, const uint32_t* lst, hipStream_t fs, unsigned long long* wc, int label) {
+    svx_ctx* c = ec.c;
+    static const int order[SEG_MAX] = {CLS_FULL, CLS_WIDE0 + 3, CLS_WIDE14 + 3, CLS_WIDE12 + 3, CLS_WIDE10 + 3, CLS_WIDE0 + 2, CLS_WIDE14 + 2, CLS_WIDE12 + 2, CLS_WIDE10 + 2,
+                                       CLS_WIDE0 + 1, CLS_WIDE14 + 1, CLS_WIDE12 + 1, CLS_WIDE10 + 1, CLS_WIDE0, CLS_WIDE14, CLS_WIDE12, CLS_WIDE10,
+                                       CLS_LANE0 + 4, CLS_LANE0 + 3, CLS_LANE0 + 2, CLS_LANE0 + 1, CLS_LANE0};     // longest serial chains first
+    const int base = GENERIC_BASE * generic;
+    FusedTab tf; memset(&tf, 0, sizeof tf);
+    unsigned nblk = 0;
+    auto class_threads = [&](int cls, long long cn) -> long long {
+        if (cls == CLS_FULL) return cn * 64;
+        if (cls >= CLS_WIDE0) return cn * (2 << ((cls - CLS_WIDE0) & 3));        // the four wide families: 2 / 4 / 8 / 16 lanes per pair
+        return cn;
+    };
+    // low-latency form of a long class: KIND_LL + words per lane (64 lanes), 0 = none
+    auto ll_kind = [](int cls) -> int {
+        if (cls == CLS_WIDE0 + 2 || cls == CLS_WIDE12 + 2 || cls == CLS_WIDE14 + 2 || cls == CLS_WIDE10 + 2) return KIND_LL + 2;       // <= 4096 rows
+        if (cls == CLS_WIDE12 + 3 || cls == CLS_WIDE10 + 3) return KIND_LL + 3;     // <= 6144
+        if (cls == CLS_WIDE0 + 3 || cls == CLS_WIDE14 + 3) return KIND_LL + 4;      // <= 8192
+        return 0;
+    };
+    long long waves_normal = 0, waves_ll = 0;
+    for (int k = 0; k < SEG_MAX; k++) {
+        const long long cn = cn_of[base + order[k]];
+        if (cn <= 0) continue;
+        waves_normal += (class_threads(order[k], cn) + 63) / 64;
+        waves_ll += ll_kind(order[k]) ? cn : (class_threads(order[k], cn) + 63) / 64;
+    }
+    const long long ll_waves = 2;                                        // waves per SIMD below which the launch counts as latency-bound
+    const bool low_latency = !ec.sw.no_ll && waves_normal <= ll_waves * 4 * (long long)c->n_cu && waves_ll <= 8 * 4 * (long long)c->n_cu;
+    for (int k = 0; k < SEG_MAX; k++) {
+        const int cls = order[k];
+        const long long cn = cn_of[base + cls];
+        if (cn <= 0) continue;
+        const int ll = low_latency ? ll_kind(cls) : 0;
+        const long long threads = ll ? cn * 64 : class_threads(cls, cn);
+        tf.kind[tf.n] = ll ? ll : cls; tf.lo[tf.n] = lo[base + cls]; tf.cn[tf.n] = cn; tf.first_block[tf.n] = nblk;
+        nblk += (unsigned)((threads + EDIT_T - 1) / EDIT_T); tf.n++;
+    }
+    tf.first_block[tf.n] = nblk;
+    if (!tf.n) return SVX_OK;
+    if (ec.sw.serial) HIPCHK(hipEventRecord(c->ev[6], fs));
+    if (generic) k_edit_fulls<4><<<nblk, EDIT_T, 0, fs>>>(tf, lst, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, ec.cnt + 1, c->e_big_list.as<uint32_t>(), wc);
+    else k_edit_fulls<2><<<nblk, EDIT_T, 0, fs>>>(tf, lst, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, ec.cnt + 1, c->e_big_list.as<uint32_t>(), wc);
+    HIPCHK(hipGetLastError());
+    if (ec.sw.serial) {
+        HIPCHK(hipEventRecord(c->ev[7], fs));
+        HIPCHK(hipStreamSynchronize(fs));
+        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+        fprintf(stderr, "{\"edit_launch\": {\"round\": %d, \"kind\": \"fulls\", \"generic\": %d, \"blocks\": %u, \"ms\": %.4f}}\n", label, generic, nblk, ms);
+    }
+    return SVX_OK;
+}
+
+// the band lists (lo / cn_of by sort class) of one alphabet as full matrices, one wave per pair (KIND_RETRY)
+static int launch_bands_as_fulls(const EditCall& ec, int generic, const long long* lo, const long long* cn_of, const uint32_t* lst, hipStream_t fs, unsigned long long* wc) {
+    svx_ctx* c = ec.c;
+    const int base = GENERIC_BASE * generic;
+    FusedTab tf; memset(&tf, 0, sizeof tf);
+    unsigned nblk = 0;
+    for (int cls = NBAND - 1; cls >= 0; cls--) {
+        const long long cn = cn_of[base + cls];
+        if (cn <= 0) continue;
+        tf.kind[tf.n] = KIND_RETRY; tf.lo[tf.n] = lo[base + cls]; tf.cn[tf.n] = cn; tf.first_block[tf.n] = nblk;
+        nblk += (unsigned)((cn * 64 + EDIT_T - 1) / EDIT_T); tf.n++;
+    }
+    tf.first_block[tf.n] = nblk;
+    if (!tf.n) return SVX_OK;
+    if (generic) k_edit_fulls<4><<<nblk, EDIT_T, 0, fs>>>(tf, lst, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, ec.cnt + 1, c->e_big_list.as<uint32_t>(), wc);
+    else k_edit_fulls<2><<<nblk, EDIT_T, 0, fs>>>(tf, lst, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, ec.cnt + 1, c->e_big_list.as<uint32_t>(), wc);
+    HIPCHK(hipGetLastError());
+    return SVX_OK;
+}
+
+// the band launch of one alphabet and part.  Not split: part3 = 0, every band class.  Split (round 0): part3 0 = classes 7, 8; 1 = split_cls .. 6 - both the early
+// part, on a stream of its own with retry lists of its own, and posted when it ends; 2 = the rest
+static int launch_bands(const EditCall& ec, EditRound& r, int generic, bool split, int part3) {
+    svx_ctx* c = ec.c;
+    const int base = GENERIC_BASE * generic;
+    const bool early = split && part3 < 2;
+    FusedTab tb; memset(&tb, 0, sizeof tb);
+    tb.narrow = ec.sw.narrow_windows;
+    unsigned nblk = 0;
+    for (int cls = NBAND - 1; cls >= 0; cls--) {                          // widest band first
+        const long long cn = r.seg_cn[base + cls];
+        if (cn <= 0) continue;
+        if (split && (part3 == 0 ? cls < 7 : (part3 == 1 ? (cls >= 7 || cls < r.split_cls) : cls >= r.split_cls))) continue;
+        tb.kind[tb.n] = cls; tb.lo[tb.n] = r.seg_lo[base + cls]; tb.cn[tb.n] = cn; tb.first_block[tb.n] = nblk;
+        nblk += (unsigned)((cn + EDIT_T - 1) / EDIT_T); tb.n++;
+    }
+    tb.first_block[tb.n] = nblk;
+    if (!tb.n) return SVX_OK;
+    r.band_used[generic] = true;
+    if (ec.sw.serial) HIPCHK(hipEventRecord(c->ev[6], ec.band_st[generic]));
+    // the first part (few, long pairs: latency) on a stream of its own, so that the second does not wait for it
+    hipStream_t bs = early ? ec.early_st[generic] : ec.band_st[generic];
+    // the kernel built for 12 state words keeps more waves per SIMD: every launch without the two widest classes takes it
+    bool wide16 = false;
+    for (int k = 0; k < tb.n; k++) if (band_words(tb.kind[k]) > 12) wide16 = true;
+    // (each launch of the early part has lists of its own: everything it failed is launched when IT has ended)
+    unsigned long long* const fc = early ? r.fail_cnt_early[part3] : r.fail_cnt;
+    uint32_t* const fl = early ? r.fail_list_early[part3] : r.fail_list;
+    if (generic) {
+        if (wide16) k_edit_bands<4, 16><<<nblk, EDIT_T, 0, bs>>>(tb, r.list, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, fc, fl, r.pending, r.wc_band);
+        else k_edit_bands<4, 12><<<nblk, EDIT_T, 0, bs>>>(tb, r.list, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, fc, fl, r.pending, r.wc_band);
+    } else {
+        if (wide16) k_edit_bands<2, 16><<<nblk, EDIT_T, 0, bs>>>(tb, r.list, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, fc, fl, r.pending, r.wc_band);
+        else k_edit_bands<2, 12><<<nblk, EDIT_T, 0, bs>>>(tb, r.list, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, fc, fl, r.pending, r.wc_band);
+    }
+    HIPCHK(hipGetLastError());
+    if (early) {
+        r.split_used[generic] = true;
+        MailSrc ms; memset(&ms, 0, sizeof ms); ms.k = 1; ms.p[0] = r.fail_cnt_early[part3] + base; ms.n[0] = GENERIC_BASE;
+        EarlyPost ep; ep.generic = generic; ep.set = part3;
+        SVXCHK(svx_mail_post(c, bs, ms, &ep.ticket));                     // behind this launch on its stream
+        r.early_posts.push_back(ep);
+    }
+    if (ec.sw.serial) {                                                  // SVX_EDIT_SERIAL=1: stand-alone kernel durations for profiling
+        HIPCHK(hipEventRecord(c->ev[7], ec.band_st[generic]));
+        HIPCHK(hipStreamSynchronize(ec.band_st[generic]));
+        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
+        fprintf(stderr, "{\"edit_launch\": {\"round\": %d, \"kind\": \"bands\", \"generic\": %d, \"blocks\": %u, \"ms\": %.4f}}\n", r.round, generic, nblk, ms);
+    }
+    return SVX_OK;
+}
+
+// ---- the stages of a call ------------------------------------------------------------------------------------------------
+// 1. packed store: one record per string / signature - prepacked (svx_edit_prepack_*) or built here - and the buffers of the later stages
+static int edit_packed_store(EditCall& ec) {
+    svx_ctx* c = ec.c; hipStream_t st = ec.st;
+    PairSource& src = ec.src;
+    const long long n_work = ec.n_work;
     src.radius = 0;
     const bool prepacked = !src.plain && c->prepack_state == 2 && c->prepack_n == src.in.n;
     c->prepack_state = 0;
@@ -1731,9 +1870,9 @@ static int run_edit_pipeline(svx_ctx* c, long long n_work, const PairSource& src
         src.radius = c->prepack_radius;
         HIPCHK(hipStreamWaitEvent(st, c->ev[18], 0));
     } else if (!src.plain) {
-        k_pair_span<<<(unsigned)(c->n_cu * 4), T, 0, st>>>(n_work, src, cnt);
+        k_pair_span<<<(unsigned)(c->n_cu * 4), EDIT_T, 0, st>>>(n_work, src, ec.cnt);
         unsigned long long shard[16], span = 0;
-        SVXCHK(svx_mail_read(c, st, cnt + 16, 16, shard));
+        SVXCHK(svx_mail_read(c, st, ec.cnt + 16, 16, shard));
         for (unsigned long long v : shard) span = v > span ? v : span;
         src.radius = (long long)span + 100;
     }
@@ -1747,7 +1886,7 @@ static int run_edit_pipeline(svx_ctx* c, long long n_work, const PairSource& src
         SVXCHK(c->e_off.reserve((size_t)(n_rec + 1) * 8));
         SVXCHK(c->e_rec.reserve((size_t)n_rec * sizeof(HapRec) + 64));
         src.rec = c->e_rec.as<HapRec>();
-        k_hap_words<<<(unsigned)((n_rec + 1 + T - 1) / T), T, 0, st>>>(n_rec, src, c->e_words.as<int64_t>());
+        k_hap_words<<<(unsigned)((n_rec + 1 + EDIT_T - 1) / EDIT_T), EDIT_T, 0, st>>>(n_rec, src, c->e_words.as<int64_t>());
         SVXCHK(svx_exclusive_scan_i64(c, c->e_words.as<int64_t>(), c->e_off.as<int64_t>(), n_rec + 1));
         SVXCHK(svx_mail_read(c, st, c->e_off.as<int64_t>() + n_rec, 1, &total_words));
         SVXCHK(c->e_scratch.reserve((size_t)(total_words + 64) * 4));
@@ -1759,447 +1898,208 @@ static int run_edit_pipeline(svx_ctx* c, long long n_work, const PairSource& src
     SVXCHK(c->e_key.reserve((size_t)n_work * 8 * 2)); SVXCHK(c->e_val.reserve((size_t)n_work * 4 * 2));
     SVXCHK(c->e_slot.reserve((size_t)n_work * 8));
     SVXCHK(c->e_big_list.reserve((size_t)n_work * 4 + 64));
-    uint64_t* key_a = c->e_key.as<uint64_t>(); uint64_t* key_b = key_a + n_work;
-    uint32_t* val_a = c->e_val.as<uint32_t>(); uint32_t* val_b = val_a + n_work;
-    long long* slot_of = c->e_slot.as<long long>();
-    PairDesc* desc = c->e_desc.as<PairDesc>();
-    uint32_t* scratch = c->e_scratch.as<uint32_t>();
+    ec.key_a = c->e_key.as<uint64_t>(); ec.key_b = ec.key_a + n_work;
+    ec.val_a = c->e_val.as<uint32_t>(); ec.val_b = ec.val_a + n_work;
+    ec.slot_of = c->e_slot.as<long long>();
+    ec.desc = c->e_desc.as<PairDesc>();
+    ec.scratch = c->e_scratch.as<uint32_t>();
     c->stats.n_hap_bytes += total_words * 4;
-    // 2. trim + classify
-    int shift_bounds = 1;                                   // SVX_EDIT_SHIFT_BOUNDS=0: upper bounds from the left-justified alignment only (A/B switch)
-    if (const char* e = getenv("SVX_EDIT_SHIFT_BOUNDS")) shift_bounds = atoi(e) == 0 ? 0 : 1;
-    k_slots<<<(unsigned)((n_work + T - 1) / T), T, 0, st>>>(n_work, src, slot_of);
-    int prep_depth = PREP_DEPTH;                            // SVX_EDIT_PREP_DEPTH=1|2|4|8: chunks per lane in the later trips of a bound pass (1 = rounds 1-6; A/B switch)
-    if (const char* e = getenv("SVX_EDIT_PREP_DEPTH")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) prep_depth = v; }
+    return SVX_OK;
+}
+
+// 2. trim + bounds (k_edit_prep), the call's band speculation (pilot), first class of every pair, the list grouped by class, the class bounds on the host
+static int edit_classify_and_sort(EditCall& ec) {
+    svx_ctx* c = ec.c; hipStream_t st = ec.st;
+    const long long n_work = ec.n_work;
+    k_slots<<<(unsigned)((n_work + EDIT_T - 1) / EDIT_T), EDIT_T, 0, st>>>(n_work, ec.src, ec.slot_of);
     {
+        const int prep_depth = ec.sw.prep_depth;
         const unsigned prep_grid = (unsigned)((n_work + 4 * (64 / PREP_LANES) - 1) / (4 * (64 / PREP_LANES)));
         auto* prep = prep_depth == 1 ? &k_edit_prep<PREP_LANES, 1> : (prep_depth == 2 ? &k_edit_prep<PREP_LANES, 2> : (prep_depth == 8 ? &k_edit_prep<PREP_LANES, 8> : &k_edit_prep<PREP_LANES, 4>));
-        prep<<<prep_grid, 256, 0, st>>>(n_work, src, scratch, desc, key_a, val_a, ed_dev, cells_dev, shift_bounds);
+        prep<<<prep_grid, 256, 0, st>>>(n_work, ec.src, ec.scratch, ec.desc, ec.key_a, ec.val_a, ec.ed_dev, ec.cells_dev, ec.sw.shift_bounds);
     }
     HIPCHK(hipGetLastError());
-    const bool profile = getenv("SVX_EDIT_PROFILE") != nullptr, serial = getenv("SVX_EDIT_SERIAL") != nullptr;
-    std::vector<PairDesc> first_desc;                       // SVX_EDIT_PROFILE: the descriptors as round 0 saw them (first class of every pair)
-    // 2a. band speculation of THIS call from a strided sample of its own pairs (k_edit_pilot); SVX_EDIT_GUESS pins it instead
-    float guess = c->edit_guess;
+    // band speculation of THIS call from a strided sample of its own pairs (k_edit_pilot); SVX_EDIT_GUESS pins it instead
     if (!c->edit_guess_pinned && !c->edit_force_full && n_work >= 4096) {
         SVXCHK(c->e_hist.reserve(256 * 8));
         HIPCHK(hipMemsetAsync(c->e_hist.p, 0, 256 * 8, st));
         const long long stride = (n_work + PILOT_MAX - 1) / PILOT_MAX, n_samp = (n_work + stride - 1) / stride;
-        k_edit_pilot<<<(unsigned)((n_samp + 255) / 256), 256, 0, st>>>(n_work, stride, desc, scratch, c->e_hist.as<unsigned long long>());
-        k_edit_guess<<<1, 128, 0, st>>>(c->e_hist.as<unsigned long long>(), cnt + 2);        // the host learns the value with the last post of the call (k_edit_tail)
+        k_edit_pilot<<<(unsigned)((n_samp + 255) / 256), 256, 0, st>>>(n_work, stride, ec.desc, ec.scratch, c->e_hist.as<unsigned long long>());
+        k_edit_guess<<<1, 128, 0, st>>>(c->e_hist.as<unsigned long long>(), ec.cnt + 2);        // the host learns the value with the last post of the call (k_edit_tail)
         HIPCHK(hipGetLastError());
-        if (profile) {
-            unsigned long long gw = 0;
-            SVXCHK(svx_mail_read(c, st, cnt + 2, 1, &gw));
-            guess = __builtin_bit_cast(float, (uint32_t)gw);
-            fprintf(stderr, "{\"edit_guess_pilot\": %.4f, \"sampled_pairs\": %lld}\n", guess, n_samp);
-        }
+        if (ec.sw.profile) SVXCHK(profile_pilot_guess(ec, n_samp));
     }
-    int narrow_windows = 1;                                 // SVX_EDIT_NARROW=0: static staircase windows (A/B switch; results are the same either way)
-    if (const char* e = getenv("SVX_EDIT_NARROW")) narrow_windows = atoi(e) == 0 ? 0 : 1;
-    long long few_pairs = 2048;                             // SVX_EDIT_FEW_PAIRS: calls with at most this many pairs take the low-latency route (0 = never)
-    if (const char* e = getenv("SVX_EDIT_FEW_PAIRS")) few_pairs = atoll(e);
-    // SVX_EDIT_BLOCKED=1 (round 6, opt-in): the round-0 pairs of the 2- and 4-lane full-matrix families run in row blocks that skip the corners outside the band of
-    // the pair's upper bound (d_edit_blocked); SVX_EDIT_BLOCKED_K: up to which family (0: 2 lanes, 1: 4 lanes [default], 2: 8 lanes)
-    int blocked_kmax = -1;
-    if (const char* e = getenv("SVX_EDIT_BLOCKED")) if (e[0] == '1' && !c->edit_force_full && n_work > few_pairs) { blocked_kmax = 1; if (const char* k = getenv("SVX_EDIT_BLOCKED_K")) blocked_kmax = atoi(k) < 0 ? 0 : (atoi(k) > 2 ? 2 : atoi(k)); }
-    k_edit_classify<<<(unsigned)((n_work + T - 1) / T), T, 0, st>>>(n_work, desc, key_a, val_a, c->edit_force_full ? 1 : 0, cnt + 2, (n_work <= few_pairs ? 1 : 0) | ((blocked_kmax + 1) << 1));
+    k_edit_classify<<<(unsigned)((n_work + EDIT_T - 1) / EDIT_T), EDIT_T, 0, st>>>(n_work, ec.desc, ec.key_a, ec.val_a, c->edit_force_full ? 1 : 0, ec.cnt + 2, n_work <= ec.sw.few_pairs ? 1 : 0);
     HIPCHK(hipGetLastError());
-    // 3. group by class (and by descending text length inside a class, so that the 64 pairs of a wave finish together)
-    SVXCHK(svx_sort_pairs_u64(c, key_a, key_b, val_a, val_b, n_work, 0, SORT_COST_BITS + 7));      // 17 bits of cost order + 7 bits of class: three passes
-    // the row-block route takes the pairs of its classes that walk at most this many columns per block (the blocks of a pair are serial launches: the longest
-    // texts would make the chain of launches the tail of the window) - the others stay in the multi-lane forms (SVX_EDIT_BLOCKED_WALK)
-    long long blocked_walk = 2500;
-    if (const char* e = getenv("SVX_EDIT_BLOCKED_WALK")) blocked_walk = atoll(e);
-    SVXCHK(c->e_hist.reserve(256 * 8));
-    k_class_bounds<<<1, 256, 0, st>>>(key_b, n_work, reinterpret_cast<long long*>(cnt + 8), blocked_kmax >= 0 ? c->e_hist.as<long long>() : nullptr, blocked_walk);
-    long long bounds[N_SORT_CLASSES + 1], blocked_split[N_SORT_CLASSES];
-    unsigned long long blocked_nmax = 0;
-    if (blocked_kmax >= 0) SVXCHK(svx_mail_read3(c, st, cnt + 8, N_SORT_CLASSES + 1, bounds, cnt + 3, 1, &blocked_nmax, c->e_hist.p, N_SORT_CLASSES, blocked_split));
-    else SVXCHK(svx_mail_read(c, st, cnt + 8, N_SORT_CLASSES + 1, bounds));
-    // A retry round with only a few band pairs is bound by the LATENCY of its slowest pair: a band retry walks its columns in one lane with 6-16 state words
-    // (configs[1], round 1: 196 pairs, one wave of 16-word windows = 0.31 ms at the very end of the window), a full matrix spread over the 64 lanes of a wave
-    // (KIND_RETRY) finishes the same pair in a fifth of that and never fails, so the round is also the last.  Up to this many band pairs of a retry round go there
-    // (SVX_EDIT_RETRY_FULL, 0 = never; the distances are exact either way).
-    long long retry_full = 4096;
-    if (const char* e = getenv("SVX_EDIT_RETRY_FULL")) retry_full = atoll(e);
+    // group by class (and by descending text length inside a class, so that the 64 pairs of a wave finish together)
+    SVXCHK(svx_sort_pairs_u64(c, ec.key_a, ec.key_b, ec.val_a, ec.val_b, n_work, 0, SORT_COST_BITS + 7));      // 17 bits of cost order + 7 bits of class: three passes
+    k_class_bounds<<<1, 256, 0, st>>>(ec.key_b, n_work, reinterpret_cast<long long*>(ec.cnt + 8));
+    SVXCHK(svx_mail_read(c, st, ec.cnt + 8, N_SORT_CLASSES + 1, ec.bounds));
+    return SVX_OK;
+}
 
-    // 4. rounds.  Full-matrix classes (never fail, most of the work and the longest serial chains) run on high-priority streams, band classes (may fail)
-    // on low-priority ones (api.hip, SVX_EDIT_PRIO), each kind as ONE fused launch per round.  A failing pair is appended to the retry list of its next
-    // class; a round only waits for its band launch, reads 64 counters and launches the next round straight from those lists - no sort, no small kernels
-    // that would queue behind the long-running waves - so the retry rounds overlap the full-matrix work of the earlier ones.
-    // (Measured and taken out again, profiles/r04_edit_early_fulls_ab.txt: the pairs whose length gap alone exceeds every band - known before
-    // k_edit_prep has read a symbol, most of the full-matrix work - launched while bounds, pilot and sort of the other pairs are still computed.  The
-    // full-matrix waves leave k_edit_prep one or two waves per SIMD: it takes 6.4 ms instead of 1.6, the band launches start 5 ms later and the window
-    // ends where it ended before.)
-    hipStream_t band_st[2] = {c->aux[0], c->aux[1]};     // A/C/G/T-only pairs, generic pairs
-    hipStream_t full_st[2] = {c->aux[2], c->aux[3]};     // even / odd rounds
+// 3. rounds.  Full-matrix classes (never fail, most of the work and the longest serial chains) run on high-priority streams, band classes (may fail)
+// on low-priority ones (api.hip), each kind as ONE fused launch per round.  A failing pair is appended to the retry list of its next
+// class; a round only waits for its band launch, reads 64 counters and launches the next round straight from those lists - no sort, no small kernels
+// that would queue behind the long-running waves - so the retry rounds overlap the full-matrix work of the earlier ones.
+// (Measured and taken out again, profiles/r04_edit_early_fulls_ab.txt: the pairs whose length gap alone exceeds every band - known before
+// k_edit_prep has read a symbol, most of the full-matrix work - launched while bounds, pilot and sort of the other pairs are still computed.  The
+// full-matrix waves leave k_edit_prep one or two waves per SIMD: it takes 6.4 ms instead of 1.6, the band launches start 5 ms later and the window
+// ends where it ended before.)
+static int edit_rounds(EditCall& ec) {
+    svx_ctx* c = ec.c; hipStream_t st = ec.st;
+    unsigned long long* cnt = ec.cnt;
     long long seg_lo[N_SORT_CLASSES], seg_cn[N_SORT_CLASSES];
     long long pending = 0;
-    for (int sc = 0; sc < N_SORT_CLASSES; sc++) { seg_lo[sc] = bounds[sc]; seg_cn[sc] = bounds[sc + 1] - bounds[sc]; pending += seg_cn[sc]; }
-    const uint32_t* list = val_b;
-    bool blocked_used = false;
+    for (int sc = 0; sc < N_SORT_CLASSES; sc++) { seg_lo[sc] = ec.bounds[sc]; seg_cn[sc] = ec.bounds[sc + 1] - ec.bounds[sc]; pending += seg_cn[sc]; }
+    const uint32_t* list = ec.val_b;
     for (int round = 0; pending > 0; round++) {
         if (round >= MAX_ROUNDS) return svx_fail(SVX_E_STATE, "edit-distance retry loop did not converge", __FILE__, __LINE__, hipSuccess);
-        if (profile) profile_round(c, round, seg_lo, seg_cn, list, desc, n_work);
-        if (profile && round == 0) {
-            first_desc.resize((size_t)n_work);
-            SVXCHK(svx_d2h(first_desc.data(), desc, (size_t)n_work * sizeof(PairDesc), st));
-        }
+        EditRound r;
+        r.round = round; r.pending = pending; r.list = list; r.seg_lo = seg_lo; r.seg_cn = seg_cn;
+        if (ec.sw.profile) SVXCHK(profile_round_start(ec, r));
         // retry lists this round's band launch appends to: one list of `pending` slots per sort class.  Three buffers rotate; the one reused now was
         // last read by round-2's launches
         DevBuf& fb = c->e_retry[round % 3];
-        if (round >= 2) HIPCHK(hipStreamSynchronize(full_st[round & 1]));
+        if (round >= 2) HIPCHK(hipStreamSynchronize(ec.full_st[round & 1]));
         // (two sets of lists: the second one and the counters at EARLY_OFF belong to the FIRST PART of round 0 alone.  Its failures are launched as soon as that
         // part's kernels have ended - their list entries are then visible - while the second part is still appending to the round's own lists: a counter of those
         // says how many entries have been CLAIMED, not how many have been written, and a store of a running kernel need not have left its XCD's L2.  Until round 6
         // both parts shared lists and the early launch took "what the counters say now": entries of the second part in flight among them.)
         SVXCHK(fb.reserve((size_t)3 * N_SORT_CLASSES * (size_t)pending * 4 + 64));
-        uint32_t* const fb_early[2] = {fb.as<uint32_t>() + (size_t)N_SORT_CLASSES * (size_t)pending, fb.as<uint32_t>() + (size_t)2 * N_SORT_CLASSES * (size_t)pending};
-        unsigned long long* const fail_cnt_early[2] = {cnt + EARLY_OFF, cnt + EARLY_OFF + N_SORT_CLASSES};
-        hipStream_t const early_st[2] = {c->aux[5], c->aux[7]};          // the early parts of the two alphabets, each a chain of its own (both high priority)
-        struct EarlyPost { unsigned long long ticket; int generic, set; };
-        std::vector<EarlyPost> early_posts;
-        unsigned long long* fail_cnt = cnt + 128 + (size_t)round * N_SORT_CLASSES;
-        unsigned long long* wc_band = cnt + WC_OFF + (size_t)(round * 2) * WC_PER_LAUNCH;
-        unsigned long long* wc_full = wc_band + WC_PER_LAUNCH;
-        bool band_used[2] = {false, false};
-        // full-matrix launch of one alphabet from per-class segments (lo / cn indexed by sort class) of `lst`
-        static const int order[SEG_MAX] = {CLS_FULL, CLS_WIDE0 + 3, CLS_WIDE14 + 3, CLS_WIDE12 + 3, CLS_WIDE10 + 3, CLS_WIDE0 + 2, CLS_WIDE14 + 2, CLS_WIDE12 + 2, CLS_WIDE10 + 2,
-                                           CLS_WIDE0 + 1, CLS_WIDE14 + 1, CLS_WIDE12 + 1, CLS_WIDE10 + 1, CLS_WIDE0, CLS_WIDE14, CLS_WIDE12, CLS_WIDE10,
-                                           CLS_LANE0 + 4, CLS_LANE0 + 3, CLS_LANE0 + 2, CLS_LANE0 + 1, CLS_LANE0};     // longest serial chains first
-        auto launch_fulls = [&](int generic, const long long* lo, const long long* cn_of_in, const uint32_t* lst, hipStream_t fs, unsigned long long* wc, int label, bool skip_blocked = false) -> int {
-            const int base = GENERIC_BASE * generic;
-            long long cn_local[N_SORT_CLASSES];
-            for (int sc = 0; sc < N_SORT_CLASSES; sc++) cn_local[sc] = cn_of_in[sc];
-            if (skip_blocked) for (int cls = CLS_WIDE0; cls < N_CLASSES; cls++) if (blocked_words(cls, blocked_kmax)) {      // the pairs behind the split run in row blocks
-                long long sp = blocked_split[base + cls]; if (sp < lo[base + cls]) sp = lo[base + cls]; if (sp > lo[base + cls] + cn_local[base + cls]) sp = lo[base + cls] + cn_local[base + cls];
-                cn_local[base + cls] = sp - lo[base + cls];
-            }
-            const long long* cn_of = cn_local;
-            FusedTab tf; memset(&tf, 0, sizeof tf);
-            unsigned nblk = 0;
-            auto class_threads = [&](int cls, long long cn) -> long long {
-                if (cls == CLS_FULL) return cn * 64;
-                if (cls >= CLS_WIDE0) return cn * (2 << ((cls - CLS_WIDE0) & 3));        // the four wide families: 2 / 4 / 8 / 16 lanes per pair
-                return cn;
-            };
-            // low-latency form of a long class: KIND_LL + words per lane (64 lanes), 0 = none
-            auto ll_kind = [](int cls) -> int {
-                if (cls == CLS_WIDE0 + 2 || cls == CLS_WIDE12 + 2 || cls == CLS_WIDE14 + 2 || cls == CLS_WIDE10 + 2) return KIND_LL + 2;       // <= 4096 rows
-                if (cls == CLS_WIDE12 + 3 || cls == CLS_WIDE10 + 3) return KIND_LL + 3;     // <= 6144
-                if (cls == CLS_WIDE0 + 3 || cls == CLS_WIDE14 + 3) return KIND_LL + 4;      // <= 8192
-                return 0;
-            };
-            long long waves_normal = 0, waves_ll = 0;
-            for (int k = 0; k < SEG_MAX; k++) {
-                const long long cn = cn_of[base + order[k]];
-                if (cn <= 0) continue;
-                waves_normal += (class_threads(order[k], cn) + 63) / 64;
-                waves_ll += ll_kind(order[k]) ? cn : (class_threads(order[k], cn) + 63) / 64;
-            }
-            static long long ll_waves = 0;                                       // waves per SIMD below which the launch counts as latency-bound
-            if (!ll_waves) { const char* e = getenv("SVX_EDIT_LL_WAVES"); ll_waves = e && atoi(e) > 0 ? atoi(e) : 2; }
-            const bool low_latency = !getenv("SVX_EDIT_NO_LL") && waves_normal <= ll_waves * 4 * (long long)c->n_cu && waves_ll <= 8 * 4 * (long long)c->n_cu;
-            for (int k = 0; k < SEG_MAX; k++) {
-                const int cls = order[k];
-                const long long cn = cn_of[base + cls];
-                if (cn <= 0) continue;
-                const int ll = low_latency ? ll_kind(cls) : 0;
-                const long long threads = ll ? cn * 64 : class_threads(cls, cn);
-                tf.kind[tf.n] = ll ? ll : cls; tf.lo[tf.n] = lo[base + cls]; tf.cn[tf.n] = cn; tf.first_block[tf.n] = nblk;
-                nblk += (unsigned)((threads + T - 1) / T); tf.n++;
-            }
-            tf.first_block[tf.n] = nblk;
-            if (!tf.n) return SVX_OK;
-            if (serial) HIPCHK(hipEventRecord(c->ev[6], fs));
-            if (generic) k_edit_fulls<4><<<nblk, T, 0, fs>>>(tf, lst, scratch, desc, slot_of, ed_dev, cnt + 1, c->e_big_list.as<uint32_t>(), wc);
-            else k_edit_fulls<2><<<nblk, T, 0, fs>>>(tf, lst, scratch, desc, slot_of, ed_dev, cnt + 1, c->e_big_list.as<uint32_t>(), wc);
-            HIPCHK(hipGetLastError());
-            if (serial) {
-                HIPCHK(hipEventRecord(c->ev[7], fs));
-                HIPCHK(hipStreamSynchronize(fs));
-                float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
-                fprintf(stderr, "{\"edit_launch\": {\"round\": %d, \"kind\": \"fulls\", \"generic\": %d, \"blocks\": %u, \"ms\": %.4f}}\n", label, generic, nblk, ms);
-            }
-            return SVX_OK;
-        };
+        r.fail_list = fb.as<uint32_t>();
+        r.fail_list_early[0] = fb.as<uint32_t>() + (size_t)N_SORT_CLASSES * (size_t)pending; r.fail_list_early[1] = fb.as<uint32_t>() + (size_t)2 * N_SORT_CLASSES * (size_t)pending;
+        r.fail_cnt_early[0] = cnt + EARLY_OFF; r.fail_cnt_early[1] = cnt + EARLY_OFF + N_SORT_CLASSES;
+        r.fail_cnt = cnt + 128 + (size_t)round * N_SORT_CLASSES;
+        r.wc_band = cnt + WC_OFF + (size_t)(round * 2) * WC_PER_LAUNCH;
+        r.wc_full = r.wc_band + WC_PER_LAUNCH;
+        r.band_used[0] = r.band_used[1] = false;
+        r.split_used[0] = r.split_used[1] = false;
         // Round 0 launches its band classes in two parts, widest first: the pairs that fail the WIDEST bands are the long ones whose full matrices are
         // the serial tail of the next round, and they are known as soon as the first part is through - their full-matrix retries start right then,
-        // beside the rest of the round (early_cn: what of every retry list has been launched already).
-        // the band lists (lo / cn by sort class) of one alphabet as full matrices, one wave per pair (KIND_RETRY)
-        auto launch_retry_as_fulls = [&](int generic, const long long* lo, const long long* cn_of, const uint32_t* lst, hipStream_t fs, unsigned long long* wc) -> int {
-            const int base = GENERIC_BASE * generic;
-            FusedTab tf; memset(&tf, 0, sizeof tf);
-            unsigned nblk = 0;
-            for (int cls = NBAND - 1; cls >= 0; cls--) {
-                const long long cn = cn_of[base + cls];
-                if (cn <= 0) continue;
-                tf.kind[tf.n] = KIND_RETRY; tf.lo[tf.n] = lo[base + cls]; tf.cn[tf.n] = cn; tf.first_block[tf.n] = nblk;
-                nblk += (unsigned)((cn * 64 + T - 1) / T); tf.n++;
-            }
-            tf.first_block[tf.n] = nblk;
-            if (!tf.n) return SVX_OK;
-            if (generic) k_edit_fulls<4><<<nblk, T, 0, fs>>>(tf, lst, scratch, desc, slot_of, ed_dev, cnt + 1, c->e_big_list.as<uint32_t>(), wc);
-            else k_edit_fulls<2><<<nblk, T, 0, fs>>>(tf, lst, scratch, desc, slot_of, ed_dev, cnt + 1, c->e_big_list.as<uint32_t>(), wc);
-            HIPCHK(hipGetLastError());
-            return SVX_OK;
-        };
+        // beside the rest of the round.
         // First class of the early part.  Classes 7, 8 (14 / 16 words) are always in it (the longest pairs; the only ones that need the 16-word kernel).  When classes
         // 5 and 6 hold a real share of the band work (configs[1]: 27 %, the long related pairs; >= 8 % by the proxy pairs x words^2) they join it as a second launch
         // on the early stream (12-word kernel): their failures - full matrices of 3000-5000 rows - then start in the middle of the round instead of at its end
         // (12.7 -> 12.4 ms on configs[1]).  Where they hold next to nothing (the HiFi-like stand-in: 2 %) the extra launch only delays that stream (5.0 -> 6.2 ms there):
-        // profiles/r06_edit_split_class_ab.txt.  SVX_EDIT_SPLIT_CLS pins it (7 = classes 7, 8 alone).
-        int SPLIT_CLS = 7;
+        // profiles/r06_edit_split_class_ab.txt.
+        r.split_cls = 7;
         if (round == 0) {
             double early56 = 0, all = 0;
             for (int generic = 0; generic <= 1; generic++) for (int cls = 0; cls < NBAND; cls++) {
                 const double wgt = (double)seg_cn[GENERIC_BASE * generic + cls] * band_words(cls) * band_words(cls);
                 all += wgt; if (cls == 5 || cls == 6) early56 += wgt;
             }
-            if (all > 0 && early56 >= 0.08 * all) SPLIT_CLS = 5;
-            if (const char* e = getenv("SVX_EDIT_SPLIT_CLS")) { const int v = atoi(e); if (v >= 1 && v <= 7) SPLIT_CLS = v; }
+            if (all > 0 && early56 >= 0.08 * all) r.split_cls = 5;
         }
-        bool split_used[2] = {false, false};
         long long band_pending = 0;
         for (int generic = 0; generic <= 1; generic++) for (int cls = 0; cls < NBAND; cls++) band_pending += seg_cn[GENERIC_BASE * generic + cls];
-        const bool bands_as_fulls = round >= 1 && band_pending > 0 && band_pending <= retry_full && !c->edit_force_full;
+        const bool bands_as_fulls = round >= 1 && band_pending > 0 && band_pending <= ec.sw.retry_full && !c->edit_force_full;
         for (int generic = 0; generic <= 1; generic++) {
             const int base = GENERIC_BASE * generic;
             if (bands_as_fulls) {
                 // the band lists of this alphabet as full matrices, beside the round's full-matrix launch (not behind it)
-                SVXCHK(launch_retry_as_fulls(generic, seg_lo, seg_cn, list, full_st[(round + 1) & 1], wc_full));
-                SVXCHK(launch_fulls(generic, seg_lo, seg_cn, list, full_st[round & 1], wc_full, round));
+                SVXCHK(launch_bands_as_fulls(ec, generic, seg_lo, seg_cn, list, ec.full_st[(round + 1) & 1], r.wc_full));
+                SVXCHK(launch_fulls(ec, generic, seg_lo, seg_cn, list, ec.full_st[round & 1], r.wc_full, round));
                 continue;
             }
             bool any_wide = false, any_narrow = false;
-            for (int cls = 0; cls < NBAND; cls++) if (seg_cn[base + cls] > 0) { if (cls >= SPLIT_CLS) any_wide = true; else any_narrow = true; }
-            const bool split = round == 0 && !serial && any_wide && any_narrow && !getenv("SVX_EDIT_NO_EARLY");
-            for (int part3 = 0; part3 < (split ? 3 : 1); part3++) {
-                // (split: part3 0 = classes 7, 8; 1 = SPLIT_CLS .. 6, both "part 0" = the early part on its own stream; 2 = the rest)
-                const int part = split ? (part3 < 2 ? 0 : 1) : 0;
-                FusedTab tb; memset(&tb, 0, sizeof tb);
-                tb.narrow = narrow_windows;
-                unsigned nblk = 0;
-                for (int cls = NBAND - 1; cls >= 0; cls--) {                          // widest band first
-                    const long long cn = seg_cn[base + cls];
-                    if (cn <= 0) continue;
-                    if (split && (part3 == 0 ? cls < 7 : (part3 == 1 ? (cls >= 7 || cls < SPLIT_CLS) : cls >= SPLIT_CLS))) continue;
-                    tb.kind[tb.n] = cls; tb.lo[tb.n] = seg_lo[base + cls]; tb.cn[tb.n] = cn; tb.first_block[tb.n] = nblk;
-                    nblk += (unsigned)((cn + T - 1) / T); tb.n++;
-                }
-                tb.first_block[tb.n] = nblk;
-                if (!tb.n) continue;
-                band_used[generic] = true;
-                if (serial) HIPCHK(hipEventRecord(c->ev[6], band_st[generic]));
-                // the first part (few, long pairs: latency) on a stream of its own, so that the second does not wait for it
-                hipStream_t bs = (split && part == 0) ? early_st[generic] : band_st[generic];
-                // the kernel built for 12 state words keeps more waves per SIMD: every launch without the two widest classes takes it
-                bool wide16 = false;
-                for (int k = 0; k < tb.n; k++) if (band_words(tb.kind[k]) > 12) wide16 = true;
-                // (each launch of the early part has lists of its own: everything it failed is launched when IT has ended)
-                unsigned long long* const fc = (split && part == 0) ? fail_cnt_early[part3] : fail_cnt;
-                uint32_t* const fl = (split && part == 0) ? fb_early[part3] : fb.as<uint32_t>();
-                if (generic) {
-                    if (wide16) k_edit_bands<4, 16><<<nblk, T, 0, bs>>>(tb, list, scratch, desc, slot_of, ed_dev, fc, fl, pending, wc_band);
-                    else k_edit_bands<4, 12><<<nblk, T, 0, bs>>>(tb, list, scratch, desc, slot_of, ed_dev, fc, fl, pending, wc_band);
-                } else {
-                    if (wide16) k_edit_bands<2, 16><<<nblk, T, 0, bs>>>(tb, list, scratch, desc, slot_of, ed_dev, fc, fl, pending, wc_band);
-                    else k_edit_bands<2, 12><<<nblk, T, 0, bs>>>(tb, list, scratch, desc, slot_of, ed_dev, fc, fl, pending, wc_band);
-                }
-                HIPCHK(hipGetLastError());
-                if (split && part == 0) {
-                    split_used[generic] = true;
-                    MailSrc ms; memset(&ms, 0, sizeof ms); ms.k = 1; ms.p[0] = fail_cnt_early[part3] + base; ms.n[0] = GENERIC_BASE;
-                    EarlyPost ep; ep.generic = generic; ep.set = part3;
-                    SVXCHK(svx_mail_post(c, bs, ms, &ep.ticket));                     // behind this launch on its stream
-                    early_posts.push_back(ep);
-                }
-                if (serial) {                                                        // SVX_EDIT_SERIAL=1: stand-alone kernel durations for profiling
-                    HIPCHK(hipEventRecord(c->ev[7], band_st[generic]));
-                    HIPCHK(hipStreamSynchronize(band_st[generic]));
-                    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, c->ev[6], c->ev[7]));
-                    fprintf(stderr, "{\"edit_launch\": {\"round\": %d, \"kind\": \"bands\", \"generic\": %d, \"blocks\": %u, \"ms\": %.4f}}\n", round, generic, nblk, ms);
-                }
-            }
-            SVXCHK(launch_fulls(generic, seg_lo, seg_cn, list, full_st[round & 1], wc_full, round, round == 0 && blocked_kmax >= 0));
-            if (round == 0 && blocked_kmax >= 0) {
-                // the row-block route: one launch per block rank on a high-priority stream of its own; boundary words and hand-over values ping-pong between ranks
-                FusedTab tb; memset(&tb, 0, sizeof tb);
-                BlkTab bt; memset(&bt, 0, sizeof bt);
-                unsigned nblk = 0;
-                long long slots = 0;
-                for (int cls = N_CLASSES - 1; cls >= (int)CLS_WIDE0; cls--) {
-                    const int bq = blocked_words(cls, blocked_kmax);
-                    if (!bq || seg_cn[base + cls] <= 0) continue;
-                    long long sp = blocked_split[base + cls]; if (sp < seg_lo[base + cls]) sp = seg_lo[base + cls]; if (sp > seg_lo[base + cls] + seg_cn[base + cls]) sp = seg_lo[base + cls] + seg_cn[base + cls];
-                    const long long cn = seg_lo[base + cls] + seg_cn[base + cls] - sp;
-                    if (cn <= 0) continue;
-                    tb.kind[tb.n] = bq; tb.lo[tb.n] = sp; tb.cn[tb.n] = cn; tb.first_block[tb.n] = nblk; bt.slot_base[tb.n] = slots;
-                    nblk += (unsigned)((cn + T - 1) / T); slots += (cn + 63) / 64 * 64; tb.n++;
-                }
-                tb.first_block[tb.n] = nblk;
-                if (tb.n) {
-                    const long long wmax = (long long)((blocked_nmax + 31) / 32) + 1;
-                    const size_t bnd_words = (size_t)(slots / 64) * (size_t)wmax * 2 * 64;
-                    DevBuf& bb = generic ? c->e_blk[1] : c->e_blk[0];
-                    SVXCHK(bb.reserve((bnd_words * 2 + (size_t)slots * 2) * 4 + 256));
-                    uint32_t* bnd0 = bb.as<uint32_t>(); uint32_t* bnd1 = bnd0 + bnd_words;
-                    int* e0 = reinterpret_cast<int*>(bnd1 + bnd_words); int* e1 = e0 + slots;
-                    hipStream_t bs = c->aux[7];
-                    const int ranks = 2 << blocked_kmax;
-                    for (int r = 0; r < ranks; r++) {
-                        BlkArgs A; A.rank = r; A.wmax = wmax;
-                        A.bnd_in = (r & 1) ? bnd0 : bnd1; A.bnd_out = (r & 1) ? bnd1 : bnd0; A.e_in = (r & 1) ? e0 : e1; A.e_out = (r & 1) ? e1 : e0;
-                        if (generic) k_edit_blocked<4><<<nblk, T, 0, bs>>>(tb, bt, A, list, scratch, desc, slot_of, ed_dev, wc_full);
-                        else k_edit_blocked<2><<<nblk, T, 0, bs>>>(tb, bt, A, list, scratch, desc, slot_of, ed_dev, wc_full);
-                    }
-                    HIPCHK(hipGetLastError());
-                    blocked_used = true;
-                }
-            }
+            for (int cls = 0; cls < NBAND; cls++) if (seg_cn[base + cls] > 0) { if (cls >= r.split_cls) any_wide = true; else any_narrow = true; }
+            const bool split = round == 0 && !ec.sw.serial && any_wide && any_narrow && !ec.sw.no_early;
+            for (int part3 = 0; part3 < (split ? 3 : 1); part3++) SVXCHK(launch_bands(ec, r, generic, split, part3));
+            SVXCHK(launch_fulls(ec, generic, seg_lo, seg_cn, list, ec.full_st[round & 1], r.wc_full, round));
         }
         // the early parts, in the order they end: everything such a launch failed - full-matrix classes in their forms, band classes (class 4..6 can fail into class 8)
         // as one-wave-per-pair full matrices - starts now, beside the rest of the round
-        for (int set = 0; set < 2; set++) for (const EarlyPost& ep : early_posts) {
+        for (int set = 0; set < 2; set++) for (const EarlyPost& ep : r.early_posts) {
             if (ep.set != set) continue;
             const unsigned long long* w = nullptr;
-            SVXCHK(svx_mail_wait(c, early_st[ep.generic], ep.ticket, &w));
+            SVXCHK(svx_mail_wait(c, ec.early_st[ep.generic], ep.ticket, &w));
             long long e_lo[N_SORT_CLASSES], e_cn[N_SORT_CLASSES];
             for (int sc = 0; sc < N_SORT_CLASSES; sc++) { e_lo[sc] = (long long)sc * pending; e_cn[sc] = 0; }
             for (int k = 0; k < GENERIC_BASE; k++) e_cn[GENERIC_BASE * ep.generic + k] = (long long)w[k];
-            hipStream_t fs = full_st[(round + 1) & 1];
+            hipStream_t fs = ec.full_st[(round + 1) & 1];
             unsigned long long* wc_next = cnt + WC_OFF + (size_t)((round + 1) * 2 + 1) * WC_PER_LAUNCH;
-            SVXCHK(launch_fulls(ep.generic, e_lo, e_cn, fb_early[ep.set], fs, wc_next, round + 1));
-            SVXCHK(launch_retry_as_fulls(ep.generic, e_lo, e_cn, fb_early[ep.set], fs, wc_next));
+            SVXCHK(launch_fulls(ec, ep.generic, e_lo, e_cn, r.fail_list_early[ep.set], fs, wc_next, round + 1));
+            SVXCHK(launch_bands_as_fulls(ec, ep.generic, e_lo, e_cn, r.fail_list_early[ep.set], fs, wc_next));
         }
         // only the band launches can hand pairs to the next round
         const long long cap = pending;
         pending = 0;
         for (int sc = 0; sc < N_SORT_CLASSES; sc++) { seg_lo[sc] = (long long)sc * cap; seg_cn[sc] = 0; }
-        if (band_used[0] || band_used[1]) {
+        if (r.band_used[0] || r.band_used[1]) {
             // one post for the round: the main stream (idle during the rounds, not a low-priority one) waits for every band stream and sends the counters
-            for (int g = 0; g <= 1; g++) if (band_used[g]) { HIPCHK(hipEventRecord(c->ev[22 + g], band_st[g])); HIPCHK(hipStreamWaitEvent(st, c->ev[22 + g], 0)); }
-            for (int g = 0; g <= 1; g++) if (split_used[g]) { HIPCHK(hipEventRecord(c->ev[20 + g], early_st[g])); HIPCHK(hipStreamWaitEvent(st, c->ev[20 + g], 0)); }
+            for (int g = 0; g <= 1; g++) if (r.band_used[g]) { HIPCHK(hipEventRecord(c->ev[22 + g], ec.band_st[g])); HIPCHK(hipStreamWaitEvent(st, c->ev[22 + g], 0)); }
+            for (int g = 0; g <= 1; g++) if (r.split_used[g]) { HIPCHK(hipEventRecord(c->ev[20 + g], ec.early_st[g])); HIPCHK(hipStreamWaitEvent(st, c->ev[20 + g], 0)); }
             unsigned long long h[N_SORT_CLASSES];
-            SVXCHK(svx_mail_read(c, st, fail_cnt, N_SORT_CLASSES, h));
+            SVXCHK(svx_mail_read(c, st, r.fail_cnt, N_SORT_CLASSES, h));
             for (int sc = 0; sc < N_SORT_CLASSES; sc++) {
                 seg_cn[sc] = (long long)h[sc];                                    // (the first part's failures have lists of their own and are running already)
                 pending += seg_cn[sc];
             }
         }
-        list = fb.as<uint32_t>();
+        list = r.fail_list;
     }
-    // the end of the rounds: the main stream waits for both full-matrix streams, sums the counters (k_edit_tail) and posts them - one wait for the host
+    return SVX_OK;
+}
+
+// 4. the end of the rounds: the main stream waits for both full-matrix streams, sums the counters (k_edit_tail) and posts them - one wait for the host; statistics;
+// the rare big pairs
+static int edit_tail(EditCall& ec) {
+    svx_ctx* c = ec.c; hipStream_t st = ec.st;
+    unsigned long long* cnt = ec.cnt;
     unsigned long long tail[6];
-    for (int k = 0; k < 2; k++) { HIPCHK(hipEventRecord(c->ev[22 + k], full_st[k])); HIPCHK(hipStreamWaitEvent(st, c->ev[22 + k], 0)); }
-    if (blocked_used) { HIPCHK(hipEventRecord(c->ev[19], c->aux[7])); HIPCHK(hipStreamWaitEvent(st, c->ev[19], 0)); }
+    for (int k = 0; k < 2; k++) { HIPCHK(hipEventRecord(c->ev[22 + k], ec.full_st[k])); HIPCHK(hipStreamWaitEvent(st, c->ev[22 + k], 0)); }
     k_edit_tail<<<1, 256, 0, st>>>(cnt, cnt + WC_OFF, MAX_ROUNDS, cnt + 8);             // (the class bounds at cnt[8..] are history by now)
     HIPCHK(hipGetLastError());
     SVXCHK(svx_mail_read(c, st, cnt + 8, 6, tail));
-    guess = __builtin_bit_cast(float, (uint32_t)tail[1]);
+    const float guess = __builtin_bit_cast(float, (uint32_t)tail[1]);
     c->edit_guess_last = guess;
-    if (profile && !first_desc.empty()) {
-        // how much wider than necessary was the first band of every pair?  (needed = narrowest band class that certifies the distance found in the end)
-        std::vector<long long> slot((size_t)n_work);
-        long long n_slot = n_work;
-        if (slot_of) {
-            SVXCHK(svx_d2h(slot.data(), slot_of, (size_t)n_work * 8, st));
-            for (long long w = 0; w < n_work; w++) if (slot[(size_t)w] + 1 > n_slot) n_slot = slot[(size_t)w] + 1;
-        }
-        std::vector<int32_t> ed((size_t)n_slot);
-        SVXCHK(svx_d2h(ed.data(), ed_dev, (size_t)n_slot * 4, st));
-        double used[N_CLASSES] = {0}, need[N_CLASSES] = {0}, failed[N_CLASSES] = {0}; long long cnt_c[N_CLASSES] = {0};
-        double ratio_hist[8] = {0};
-        auto h_need_class = [](int m, int n, int d) { int x = (d - (n - m)) / 2; if (x < 0) x = 0; const int nw = (n - m) + 2 * x + 1;
-            for (int b = 0; b < NBAND; b++) if (nw + (b < FIRST_STAIR_CLS ? 14 : 46) <= 32 * band_words(b)) return b; return (int)CLS_FULL; };
-        for (long long w = 0; w < n_work; w++) {
-            const PairDesc& pd = first_desc[(size_t)w];
-            if (pd.cls == -1) continue;
-            const int cls = pd.cls & 0xff;
-            if (cls >= NBAND) continue;
-            const int d = ed[(size_t)(slot_of ? slot[(size_t)w] : w)];
-            const int nc = h_need_class(pd.m, pd.n, d);
-            const double u = (double)pd.n * band_words(cls), nd = (double)pd.n * (nc < NBAND ? band_words(nc) : (pd.m + 31) / 32);
-            cnt_c[cls]++; used[cls] += u;
-            if (nc <= cls) { need[cls] += nd; int r = band_words(cls) * 4 / band_words(nc) - 4; if (r > 7) r = 7; ratio_hist[r] += u; }
-            else failed[cls] += u;
-        }
-        // The full matrices of round 0 (pairs whose length gap exceeds every band): how many of their word-columns (32 rows x 1 column) lie outside the diagonals
-        // [-x, (n - m) + x] a tile decomposition could skip?  x from the upper bound the pair came with (what such a kernel would know beforehand) and from the
-        // distance found in the end (perfect foresight).  A word of rows [32 w, 32 w + 31] is needed in the columns 32 w - x .. 32 w + 31 + (n - m) + x
-        for (int grp = 0; grp < 2; grp++) {                                          // 0: whole pattern in one lane (<= 512 rows), 1: the multi-lane forms
-            double all = 0, by_ub = 0, by_d = 0; long long pairs = 0;
-            for (long long w = 0; w < n_work; w++) {
-                const PairDesc& pd = first_desc[(size_t)w];
-                if (pd.cls == -1) continue;
-                const int cls = pd.cls & 0xff;
-                if (cls < NBAND || (cls >= (int)CLS_LANE0 && cls < (int)CLS_WIDE0) != (grp == 0)) continue;
-                const int d = ed[(size_t)(slot_of ? slot[(size_t)w] : w)], m = pd.m, n = pd.n, gap = n - m;
-                if (gap < 0) continue;
-                pairs++;
-                for (int which = 0; which < 2; which++) {
-                    const int bound = which == 0 ? (pd.ub < m + n ? pd.ub : m + n) : d;
-                    const int x = bound > gap ? (bound - gap + 1) / 2 : 0;
-                    double cols = 0;
-                    for (int r0 = 0; r0 < m; r0 += 32) {
-                        int lo = r0 - x, hi = r0 + 31 + gap + x;
-                        if (lo < 0) lo = 0;
-                        if (hi > n - 1) hi = n - 1;
-                        cols += hi >= lo ? hi - lo + 1 : 0;
-                    }
-                    (which == 0 ? by_ub : by_d) += cols;
-                }
-                all += (double)n * ((m + 31) / 32);
-            }
-            fprintf(stderr, "{\"edit_full_matrix_corners\": {\"form\": \"%s\", \"pairs\": %lld, \"word_cols\": %.4g, \"inside_band_of_upper_bound\": %.4g, \"inside_band_of_final_distance\": %.4g, "
-                            "\"skippable_fraction_known_beforehand\": %.4f, \"skippable_fraction_perfect_foresight\": %.4f}}\n",
-                    grp == 0 ? "one lane per pair" : "multi-lane", pairs, all, by_ub, by_d, all > 0 ? 1.0 - by_ub / all : 0.0, all > 0 ? 1.0 - by_d / all : 0.0);
-        }
-        for (int b = 0; b < NBAND; b++) if (cnt_c[b])
-            fprintf(stderr, "{\"edit_band_fit\": {\"first_cls\": %d, \"words\": %d, \"pairs\": %lld, \"word_cols_first_band\": %.4g, \"of_which_failed\": %.4g, \"word_cols_narrowest_sufficient\": %.4g}}\n",
-                    b, band_words(b), cnt_c[b], used[b], failed[b], need[b]);
-        fprintf(stderr, "{\"edit_band_fit_ratio_hist\": {\"bins\": \"first band / narrowest sufficient band in [1, 1.25), [1.25, 1.5) ... >= 2.75, weighted by word-columns\", \"h\": [%.4g, %.4g, %.4g, %.4g, %.4g, %.4g, %.4g, %.4g]}}\n",
-                ratio_hist[0], ratio_hist[1], ratio_hist[2], ratio_hist[3], ratio_hist[4], ratio_hist[5], ratio_hist[6], ratio_hist[7]);
-    }
-    {
-        const unsigned long long nb = tail[0];
-        c->stats.n_edit_wordcols_issued += (int64_t)tail[2]; c->stats.n_edit_wordcols_useful += (int64_t)tail[3];
-        c->stats.n_edit_wordcols_retry += (int64_t)tail[4]; c->stats.n_edit_wordcols_band += (int64_t)tail[5];
-        c->stats.edit_guess = guess;
-        if (nb) {
-            // rare: shorter core > 16384 symbols.  Size the block-state scratch exactly from the core lengths.
-            const long long nbig = (long long)nb;
-            std::vector<uint32_t> items((size_t)nbig);
-            SVXCHK(svx_d2h(items.data(), c->e_big_list.p, (size_t)nbig * 4, st));
-            std::vector<PairDesc> pd((size_t)nbig);
-            { HostCopy hc(st); for (long long i = 0; i < nbig; i++) SVXCHK(hc.d2h(&pd[(size_t)i], desc + items[(size_t)i], sizeof(PairDesc))); SVXCHK(hc.finish()); }
-            std::vector<long long> off((size_t)nbig + 1, 0);
-            for (long long i = 0; i < nbig; i++) off[(size_t)i + 1] = off[(size_t)i] + (((long long)pd[(size_t)i].m + 31) / 32) * 7;
-            SVXCHK(c->e_big_state.reserve((size_t)off[(size_t)nbig] * 4 + 16));
-            SVXCHK(c->e_big_off.reserve((size_t)(nbig + 1) * 8));
-            SVXCHK(svx_h2d(c->e_big_off.p, off.data(), (size_t)(nbig + 1) * 8, st));
-            k_edit_full_big<<<(unsigned)nbig, 64, 0, st>>>(nbig, c->e_big_list.as<uint32_t>(), c->e_big_off.as<long long>(), scratch, desc, slot_of, ed_dev,
-                                                          c->e_big_state.as<uint32_t>());
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(st));
-        }
-    }
-    if (profile && n_work >= 4096) {
-        // the divergence histogram of the exact distances, next to what the pilot guessed from its sample
-        SVXCHK(c->e_hist.reserve(256 * 8));
-        HIPCHK(hipMemsetAsync(c->e_hist.p, 0, 256 * 8, st));
-        k_edit_hist<<<(unsigned)(c->n_cu * 2), 256, 0, st>>>(n_work, desc, slot_of, ed_dev, c->e_hist.as<unsigned long long>());
-        unsigned long long h[256];
-        HIPCHK(hipMemcpyAsync(h, c->e_hist.p, sizeof h, hipMemcpyDeviceToHost, st));
+    if (ec.sw.profile && !ec.first_desc.empty()) SVXCHK(profile_band_fit_and_corners(ec));
+    const unsigned long long nb = tail[0];
+    c->stats.n_edit_wordcols_issued += (int64_t)tail[2]; c->stats.n_edit_wordcols_useful += (int64_t)tail[3];
+    c->stats.n_edit_wordcols_retry += (int64_t)tail[4]; c->stats.n_edit_wordcols_band += (int64_t)tail[5];
+    c->stats.edit_guess = guess;
+    if (nb) {
+        // rare: shorter core > 16384 symbols.  Size the block-state scratch exactly from the core lengths.
+        const long long nbig = (long long)nb;
+        std::vector<uint32_t> items((size_t)nbig);
+        SVXCHK(svx_d2h(items.data(), c->e_big_list.p, (size_t)nbig * 4, st));
+        std::vector<PairDesc> pd((size_t)nbig);
+        { HostCopy hc(st); for (long long i = 0; i < nbig; i++) SVXCHK(hc.d2h(&pd[(size_t)i], ec.desc + items[(size_t)i], sizeof(PairDesc))); SVXCHK(hc.finish()); }
+        std::vector<long long> off((size_t)nbig + 1, 0);
+        for (long long i = 0; i < nbig; i++) off[(size_t)i + 1] = off[(size_t)i] + (((long long)pd[(size_t)i].m + 31) / 32) * 7;
+        SVXCHK(c->e_big_state.reserve((size_t)off[(size_t)nbig] * 4 + 16));
+        SVXCHK(c->e_big_off.reserve((size_t)(nbig + 1) * 8));
+        SVXCHK(svx_h2d(c->e_big_off.p, off.data(), (size_t)(nbig + 1) * 8, st));
+        k_edit_full_big<<<(unsigned)nbig, 64, 0, st>>>(nbig, c->e_big_list.as<uint32_t>(), c->e_big_off.as<long long>(), ec.scratch, ec.desc, ec.slot_of, ec.ed_dev,
+                                                      c->e_big_state.as<uint32_t>());
+        HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(st));
-        double total = 0, acc = 0;
-        for (int b = 0; b < 256; b++) total += (double)h[b];
-        fprintf(stderr, "{\"edit_guess_used\": %.4f, \"edit_guess_exact_histogram\": %.4f, \"cum_weight_by_bin\": [", guess, guess_from_histogram(h, guess));
-        for (int b = 0; b < 256; b++) { acc += (double)h[b]; if (b % 8 == 7) fprintf(stderr, "%.3f%s", total > 0 ? acc / total : 0.0, b == 255 ? "" : ", "); }
-        fprintf(stderr, "]}\n");
     }
+    if (ec.sw.profile && ec.n_work >= 4096) SVXCHK(profile_exact_histogram(ec, guess));
     return SVX_OK;
+}
+
+static int run_edit_pipeline(svx_ctx* c, long long n_work, const PairSource& src_in, int32_t* ed_dev, unsigned long long* cells_dev) {
+    if (n_work <= 0) return SVX_OK;
+    if (n_work >= (1ll << 32)) return svx_fail(SVX_E_ARG, "more than 2^32 edit-distance pairs in one call", __FILE__, __LINE__, hipSuccess);
+    EditCall ec;
+    ec.c = c; ec.st = c->stream;
+    ec.n_work = n_work; ec.src = src_in; ec.src.n_pairs = n_work; ec.ed_dev = ed_dev; ec.cells_dev = cells_dev;
+    ec.sw = read_edit_switches();
+    ec.band_st[0] = c->aux[0]; ec.band_st[1] = c->aux[1];
+    ec.full_st[0] = c->aux[2]; ec.full_st[1] = c->aux[3];
+    ec.early_st[0] = c->aux[5]; ec.early_st[1] = c->aux[7];          // each a chain of its own
+    SVXCHK(c->e_fail.reserve(CNT_WORDS * 8));
+    ec.cnt = c->e_fail.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(ec.cnt, 0, CNT_WORDS * 8, ec.st));
+    // cnt[2]: the speculation fraction k_edit_classify reads (float bits) - the fallback here, overwritten by k_edit_guess when the call is sampled
+    HIPCHK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ec.cnt + 2), (int)__builtin_bit_cast(uint32_t, c->edit_guess), 1, ec.st));
+    SVXCHK(edit_packed_store(ec));
+    SVXCHK(edit_classify_and_sort(ec));
+    SVXCHK(edit_rounds(ec));
+    return edit_tail(ec);
 }
 
 int svx_edit_distance_pairs(svx_ctx* c, int64_t n_pairs, const uint8_t* codes_dev, const int64_t* a_off_dev, const int64_t* b_off_dev,
@@ -2217,12 +2117,7 @@ int svx_edit_distance_pairs(svx_ctx* c, int64_t n_pairs, const uint8_t* codes_de
 // full-matrix rounds - on the HiFi-like stand-in k_edit_prep waits for it, and at the main stream's priority it arrived 0.6-0.9 ms later
 // (profiles/r06_prepack_priority_ab.txt; still +0.9 ms per step with the pack at that place, profiles/sample_sweep_ab_c2.txt).  Started behind the sort it has
 // the whole partition phase to itself and runs at the main stream's priority: at high priority its blocks take the CUs from the latency-bound kernels of that phase
-// (configs[1]: cluster_partition_sample_ms 0.82 against 0.73 ms).  SVX_PREPACK_PRIO=high / low: A/B.
-static hipStream_t prepack_stream(svx_ctx* c) {
-    static const int which = []() { const char* e = getenv("SVX_PREPACK_PRIO"); return e && !strcmp(e, "high") ? 2 : (e && !strcmp(e, "low") ? 0 : 6); }();
-    return c->aux[which];
-}
-
+// (configs[1]: cluster_partition_sample_ms 0.82 against 0.73 ms): the pack runs on aux[6].
 static PairSource prepack_source(svx_ctx* c, const ClusterIn& in) {
     PairSource src; memset(&src, 0, sizeof src);
     src.plain = 0; src.in = in; src.g_off = c->g_off_p; src.g_codes = c->g_codes_p; src.radius = c->prepack_radius; src.rec = c->e_rec.as<HapRec>();
@@ -2236,7 +2131,7 @@ int svx_edit_prepack_begin(svx_ctx* c, const ClusterIn& in, const svx_params& p,
     if (!(bound >= 0) || !(bound < 16000.0)) return SVX_OK;                       // unusual parameters: the exact radius is found from the pair list
     c->prepack_radius = (long long)(bound * (1.0 + 1e-9)) + 2 + 100;
     c->prepack_n = in.n;
-    hipStream_t ps = prepack_stream(c);
+    hipStream_t ps = c->aux[6];
     const long long n_rec = in.n;
     SVXCHK(c->e_words.reserve((size_t)(n_rec + 1) * 8));
     SVXCHK(c->e_off.reserve((size_t)(n_rec + 1) * 8));
@@ -2252,7 +2147,7 @@ int svx_edit_prepack_begin(svx_ctx* c, const ClusterIn& in, const svx_params& p,
 
 int svx_edit_prepack_pack(svx_ctx* c, const ClusterIn& in) {
     if (c->prepack_state != 1) return SVX_OK;
-    hipStream_t ps = prepack_stream(c);
+    hipStream_t ps = c->aux[6];
     HIPCHK(hipStreamSynchronize(ps));
     const int64_t total_words = c->pinned[0];
     SVXCHK(c->e_scratch.reserve((size_t)(total_words + 64) * 4));

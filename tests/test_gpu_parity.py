@@ -657,13 +657,11 @@ def test_partition_and_cluster_candidates_matches_reference(eng):
         assert H.close(a[7], b[7]) and H.close(a[8], b[8])
 
 
-@pytest.mark.parametrize("kmax", ["0", "1", "2"])
-def test_edit_distance_row_blocks_vs_oracle(oracle, monkeypatch, kmax):
-    """SVX_EDIT_BLOCKED=1 (round 6): the round-0 pairs of the 2-, 4- (and 8-) lane full-matrix families run as row blocks that only walk the columns inside the
-    band of the pair's own upper bound, the blocks of a pair in successive launches with their boundary rows handed over through memory.  Pairs at every block-count
-    boundary of the four word widths, with a large length gap (what sends a pair to a full matrix in the first place): related ones (one long deletion + a few edits:
-    tight upper bound, narrow band, big corners), loosely related and unrelated ones (upper bound = the trivial one: nothing is spared).  Equal to the default route
-    on every pair and to the oracle on a sample."""
+def test_edit_distance_large_gap_full_matrix_pairs_vs_oracle(oracle):
+    """846 pairs with a large length gap (what sends a pair to a full matrix in the first place), the shorter string at every lane-count boundary of the 10-, 12-,
+    14- and 16-word full-matrix families: related ones (one long deletion + none / a few / many point edits: tight upper bound, narrow band, big corners outside
+    it), unrelated ones (upper bound = the trivial one), and the shorter string as the longer one's head or tail with a few substitutions.  2 100 short filler
+    pairs make the call a large one, so the pairs take the classes of a large call and not the low-latency route.  Equal to the oracle on a sample of 120."""
     from svim_amd._lib import Engine
     rng = random.Random(29)
     pairs = []
@@ -693,22 +691,13 @@ def test_edit_distance_row_blocks_vs_oracle(oracle, monkeypatch, kmax):
     filler = [(synth.random_seq(rng, 40), synth.random_seq(rng, 44)) for _ in range(2100)]
     idx = rng.sample(range(len(pairs)), 120)
     exp = {i: oracle.edit_distance(*pairs[i]) for i in idx}
-    results = []
-    # (SVX_EDIT_BLOCKED_WALK: pairs that walk more columns per block stay in the multi-lane forms - the default split in one variant, everything in row blocks in the others)
-    walk = {} if kmax == "2" else {"SVX_EDIT_BLOCKED_WALK": "1000000"}
-    for env in ({}, dict({"SVX_EDIT_BLOCKED": "1", "SVX_EDIT_BLOCKED_K": kmax}, **walk)):
-        for k in ("SVX_EDIT_BLOCKED", "SVX_EDIT_BLOCKED_K", "SVX_EDIT_BLOCKED_WALK"):
-            monkeypatch.delenv(k, raising=False)
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
-        e = Engine()
-        try:
-            results.append(e.edit_distances(pairs + filler))
-        finally:
-            e.close()
-    assert results[0] == results[1]
+    e = Engine()
+    try:
+        got = e.edit_distances(pairs + filler)
+    finally:
+        e.close()
     for i in idx:
-        assert results[1][i] == exp[i], (i, len(pairs[i][0]), len(pairs[i][1]))
+        assert got[i] == exp[i], (i, len(pairs[i][0]), len(pairs[i][1]))
 
 
 @pytest.mark.parametrize("few_pairs", [None, "0"])
