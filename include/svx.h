@@ -483,6 +483,20 @@ int  svx_text_gz_fetch(svx_ctx* ctx, int64_t byte_offset, int64_t bytes, uint8_t
 int  svx_text_gz_get_stats(svx_ctx* ctx, svx_text_gz_stats* out);
 /* host-only, no GPU: the same encoder built for the host, one file.  SVX_E_CAPACITY: cap is too small (n + 64 * (n / 65280 + 2) always suffices). */
 int  svx_text_gz_host(const uint8_t* text, int64_t n, uint8_t* out, int64_t cap, int64_t* n_out);
+/* Test infrastructure (as svx_selftest_prims): ONE phase of the encoder over a batch of 1 .. 2048 blocks, one wave per block, by the kernels svx_text_gz launches;
+ * the context's stream of the last svx_text_gz is left alone.  All arrays are host memory with one fixed stride per block b:
+ *   text[text_off[b] .. + n[b])  the block's text (text_off: n_blocks + 1 entries from 0, the last one the size of `text`; its alignment is that of text_off[b])
+ *   tok[b * 65280 ..), nt[b]     the token list (literal byte, or 0x80000000 | (distance - 1) << 9 | (length - 3)) and its length
+ *   hist[b * 320 ..)             counts of the 288 literal/length and 32 distance symbols, the end-of-block symbol counted once
+ *   codes[b * 692 ..)            the words of DefBlockCodes (csrc/deflate_core.hpp): codes, header items, trailer items, n_pre, n_suf, size, kind; unused words 0
+ *   slots[b * 65536 ..)          the block as it is written; the first `size` bytes count
+ * phase 0 (match): text, n -> tok, nt, hist.  phase 1 (codes): hist, n, crc -> codes (n 0: the end-of-file block).  phase 2 (bits): text, n, tok, nt, codes -> slots;
+ * the codes may be synthetic (any lengths up to 15, any items up to 48 bits) as long as the block fits its slot.  SVX_E_ARG for anything a phase would index
+ * out of range with.  svx_text_gz_phase_host: the host build of the same header, no GPU. */
+int  svx_text_gz_phase(svx_ctx* ctx, int phase, int64_t n_blocks, const uint8_t* text, const int64_t* text_off, const uint32_t* n, const uint32_t* crc, uint32_t* tok,
+                       uint32_t* nt, uint32_t* hist, uint32_t* codes, uint8_t* slots);
+int  svx_text_gz_phase_host(int phase, int64_t n_blocks, const uint8_t* text, const int64_t* text_off, const uint32_t* n, const uint32_t* crc, uint32_t* tok, uint32_t* nt,
+                            uint32_t* hist, uint32_t* codes, uint8_t* slots);
 
 /* ---- tabix index of the BGZF stream (textindex.hip, textindex_core.hpp; bins and layout: binidx_core.hpp; the definition in words: svim_amd/tabix.py) ----
  * svx_text_index builds, for every file of the last svx_text_gz, the uncompressed bytes of its .tbi from the text AND the block table of that call, both where

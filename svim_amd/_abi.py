@@ -208,6 +208,7 @@ class BedStats(C.Structure):
 
 # BGZF output (include/svx.h: svx_text_gz*): text bytes per block, the end-of-file block every file ends with, the sources of Engine.text_gz
 TEXT_GZ_BLOCK = 65280
+TEXT_GZ_NHIST, TEXT_GZ_CODES_WORDS = 320, 692                 # DEF_NHIST; sizeof(DefBlockCodes) / 4 (csrc/deflate_core.hpp): svx_text_gz_phase
 TEXT_GZ_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
 TEXT_GZ_VCF, TEXT_GZ_BED, TEXT_GZ_HOST = 0, 1, 2
 

@@ -32,7 +32,7 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_vcf", "svx_vcf_count", "svx_vcf_fetch", "svx_vcf_get_stats", "svx_vcf_format_std",
            "svx_format_repr", "svx_format_repr_many", "svx_format_repr_device",
            "svx_bed", "svx_bed_set_read_names", "svx_bed_count", "svx_bed_fetch", "svx_bed_get_stats",
-           "svx_text_gz", "svx_text_gz_count", "svx_text_gz_fetch", "svx_text_gz_get_stats", "svx_text_gz_host",
+           "svx_text_gz", "svx_text_gz_count", "svx_text_gz_fetch", "svx_text_gz_get_stats", "svx_text_gz_host", "svx_text_gz_phase", "svx_text_gz_phase_host",
            "svx_vcf_position_order", "svx_text_index", "svx_text_index_count", "svx_text_index_fetch", "svx_text_index_get_stats", "svx_text_index_host",
            "svx_text_index_fmt", "svx_text_index_csi_host", "svx_bam_index_finish_fmt", "svx_bam_sort_index_fmt", "svx_bam_index_csi_host",
            "svx_bam_index_begin", "svx_bam_index_finish", "svx_bam_index_abort", "svx_bam_index_count", "svx_bam_index_fetch", "svx_bam_index_get_stats", "svx_bam_index_host",
@@ -149,6 +149,31 @@ def text_gz_host(data):
     src = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, np.uint8)
     _check(lib().svx_text_gz_host(ptr(src), C.c_int64(len(data)), ptr(out), C.c_int64(cap), C.byref(n)), "svx_text_gz_host")
     return out[:n.value].tobytes()
+
+
+def text_gz_phase(phase, n, text=b"", text_off=None, crc=None, tok=None, nt=None, hist=None, codes=None, engine=None):
+    """svx_text_gz_phase (engine: an Engine) / svx_text_gz_phase_host (engine None; no GPU needed): one phase of the encoder of csrc/deflate_core.hpp over a
+    batch of blocks - test infrastructure.  phase "match": text, text_off, n -> (tok uint32[nb, 65280], nt uint32[nb], hist uint32[nb, 320]); "codes": hist, n,
+    crc -> codes uint32[nb, 692] (the words of DefBlockCodes); "bits": text, text_off, n, tok, nt, codes -> slots uint8[nb, 65536].  Layouts: include/svx.h."""
+    ph = {"match": 0, "codes": 1, "bits": 2}[phase]
+    n = np.ascontiguousarray(n, dtype=np.uint32)
+    nb = int(n.size)
+    text = bytes(text)
+    src = np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, np.uint8)
+    off = np.ascontiguousarray(text_off if text_off is not None else np.zeros(nb + 1), dtype=np.int64)
+    if off.size != nb + 1 or (ph != 1 and int(off[-1]) != len(text)):
+        raise ValueError("text_gz_phase: text_off must hold one offset per block and len(text)")
+    want = lambda a, shape: np.ascontiguousarray(a, dtype=np.uint32).reshape(shape) if a is not None else np.zeros(shape, dtype=np.uint32)       # noqa: E731
+    crc, nt = want(crc, (nb,)), want(nt, (nb,)).copy()
+    hist, codes = want(hist, (nb, _abi.TEXT_GZ_NHIST)).copy(), want(codes, (nb, _abi.TEXT_GZ_CODES_WORDS)).copy()
+    tok = want(tok, (nb, _abi.TEXT_GZ_BLOCK)) if ph == 2 else np.zeros((nb, _abi.TEXT_GZ_BLOCK) if ph == 0 else (1, 1), dtype=np.uint32)
+    slots = np.zeros((nb, 65536) if ph == 2 else (1, 1), dtype=np.uint8)
+    args = (C.c_int(ph), C.c_int64(nb), ptr(src), ptr(off), ptr(n), ptr(crc), ptr(tok), ptr(nt), ptr(hist), ptr(codes), ptr(slots))
+    if engine is None:
+        _check(lib().svx_text_gz_phase_host(*args), "svx_text_gz_phase_host")
+    else:
+        _check(engine.L.svx_text_gz_phase(engine.ctx, *args), "svx_text_gz_phase")
+    return {0: (tok, nt, hist), 1: codes, 2: slots}[ph]
 
 
 def text_index_host(text, block_coff, block_uoff, preset, stream_base=0, fmt="tbi"):

@@ -876,7 +876,10 @@ INF_FN int inflate_raw(const uint8_t* payload, uint32_t in_bytes, uint8_t* out, 
                     }
                 }
                 s.pos += n;
-                inf_flush(s, s.pos - ((s.pos + s.mis) & 15u));
+                // up to the last 16-byte boundary of the destination - if the output has reached one: a stored block of fewer bytes than lie in front of the
+                // first boundary (out not aligned, pos + mis < 16) has nothing to flush yet, and pos - tail would wrap to a flush of four gigabytes
+                const uint32_t tail = (s.pos + s.mis) & 15u;
+                if (s.pos > tail) inf_flush(s, s.pos - tail);
             }
             s.bp += 8u * len;
         } else if (type == 1 || type == 2) {

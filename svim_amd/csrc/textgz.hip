@@ -11,6 +11,7 @@
 #include "common.hpp"
 #include "hostcopy.hpp"
 #include "textgz_kernels.hpp"
+#include "textgz_phase.hpp"
 #include <algorithm>
 
 struct TextGzState {
@@ -181,6 +182,64 @@ extern "C" int svx_text_gz_fetch(svx_ctx* c, int64_t byte_offset, int64_t bytes,
         SVXCHK(hc.finish());
         HIPCHK(hipStreamSynchronize(c->stream));
     }
+    return SVX_OK;
+}
+
+// Test infrastructure (include/svx.h): one phase of the encoder over a batch of blocks, its inputs and results in host memory.  The kernels are the ones
+// svx_text_gz launches, one wave per block, one launch; the buffers live for the call only and the context's stream of the last svx_text_gz is left alone.
+extern "C" int svx_text_gz_phase(svx_ctx* c, int phase, int64_t nb, const uint8_t* text, const int64_t* text_off, const uint32_t* n, const uint32_t* crc, uint32_t* tok,
+                                 uint32_t* nt, uint32_t* hist, uint32_t* codes, uint8_t* slots) {
+    if (!c) return svx_fail(SVX_E_ARG, "svx_text_gz_phase: no context", __FILE__, __LINE__, hipSuccess);
+    if (const char* bad = tgz_phase_check(phase, nb, text, text_off, n, crc, tok, nt, hist, codes, slots)) {
+        char msg[200]; snprintf(msg, sizeof msg, "svx_text_gz_phase: %s", bad);
+        return svx_fail(SVX_E_ARG, msg, __FILE__, __LINE__, hipSuccess);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    struct Bufs { DevBuf text, blocks, crc, tok, hist, nt, codes, bsize, kinds, slots; ~Bufs() { for (DevBuf* b : {&text, &blocks, &crc, &tok, &hist, &nt, &codes, &bsize, &kinds, &slots}) b->release(); } } B;
+    std::vector<TgzBlock> hb((size_t)nb);
+    for (int64_t b = 0; b < nb; b++) hb[(size_t)b] = TgzBlock{(unsigned long long)(phase == TGZ_PHASE_CODES ? 0 : text_off[b]), n[b], 0u};
+    const int64_t n_text = phase == TGZ_PHASE_CODES ? 0 : text_off[nb];
+    const size_t tok_b = (size_t)nb * DEF_BLOCK * 4, hist_b = (size_t)nb * DEF_NHIST * 4, codes_b = (size_t)nb * sizeof(DefBlockCodes), slots_b = (size_t)nb * DEF_SLOT;
+    SVXCHK(B.blocks.reserve((size_t)nb * sizeof(TgzBlock))); SVXCHK(B.text.reserve((size_t)n_text + 64)); SVXCHK(B.nt.reserve((size_t)nb * 4));
+    {
+        HostCopy hc(st);
+        SVXCHK(hc.h2d(B.blocks.p, hb.data(), (size_t)nb * sizeof(TgzBlock)));
+        if (n_text) SVXCHK(hc.h2d(B.text.p, text, (size_t)n_text));
+        if (phase == TGZ_PHASE_CODES) {
+            SVXCHK(B.hist.reserve(hist_b)); SVXCHK(B.crc.reserve((size_t)nb * 4));
+            SVXCHK(hc.h2d(B.hist.p, hist, hist_b)); SVXCHK(hc.h2d(B.crc.p, crc, (size_t)nb * 4));
+        }
+        if (phase == TGZ_PHASE_BITS) {
+            SVXCHK(B.tok.reserve(tok_b)); SVXCHK(B.codes.reserve(codes_b));
+            SVXCHK(hc.h2d(B.tok.p, tok, tok_b)); SVXCHK(hc.h2d(B.nt.p, nt, (size_t)nb * 4)); SVXCHK(hc.h2d(B.codes.p, codes, codes_b));
+        }
+        SVXCHK(hc.finish());
+    }
+    if (phase == TGZ_PHASE_MATCH) {
+        SVXCHK(B.tok.reserve(tok_b)); SVXCHK(B.hist.reserve(hist_b));
+        HIPCHK(hipMemsetAsync(B.tok.p, 0, tok_b, st));
+        k_tgz_match<<<(unsigned)nb, 64, 0, st>>>(B.text.as<uint8_t>(), B.blocks.as<TgzBlock>(), 0, B.tok.as<uint32_t>(), B.hist.as<uint32_t>(), B.nt.as<uint32_t>());
+    } else if (phase == TGZ_PHASE_CODES) {
+        SVXCHK(B.codes.reserve(codes_b)); SVXCHK(B.bsize.reserve((size_t)nb * 8)); SVXCHK(B.kinds.reserve(64));
+        HIPCHK(hipMemsetAsync(B.codes.p, 0, codes_b, st));
+        HIPCHK(hipMemsetAsync(B.kinds.p, 0, 64, st));
+        k_tgz_codes<<<(unsigned)nb, 64, 0, st>>>(B.blocks.as<TgzBlock>(), 0, B.hist.as<uint32_t>(), B.crc.as<uint32_t>(), B.codes.as<DefBlockCodes>(), B.bsize.as<int64_t>(),
+                                                 B.kinds.as<unsigned long long>());
+    } else {
+        SVXCHK(B.slots.reserve(slots_b));
+        HIPCHK(hipMemsetAsync(B.slots.p, 0, slots_b, st));
+        k_tgz_bits<<<(unsigned)nb, 64, 0, st>>>(B.text.as<uint8_t>(), B.blocks.as<TgzBlock>(), 0, B.tok.as<uint32_t>(), B.nt.as<uint32_t>(), B.codes.as<DefBlockCodes>(), B.slots.as<uint32_t>());
+    }
+    HIPCHK(hipGetLastError());
+    {
+        HostCopy hc(st);
+        if (phase == TGZ_PHASE_MATCH) { SVXCHK(hc.d2h(tok, B.tok.p, tok_b)); SVXCHK(hc.d2h(nt, B.nt.p, (size_t)nb * 4)); SVXCHK(hc.d2h(hist, B.hist.p, hist_b)); }
+        else if (phase == TGZ_PHASE_CODES) SVXCHK(hc.d2h(codes, B.codes.p, codes_b));
+        else SVXCHK(hc.d2h(slots, B.slots.p, slots_b));
+        SVXCHK(hc.finish());
+    }
+    HIPCHK(hipStreamSynchronize(st));
     return SVX_OK;
 }
 

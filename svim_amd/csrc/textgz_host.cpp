@@ -2,6 +2,7 @@
 // the kernels of textgz.hip write for the same text: sizes are measured, and zlib and the host builds of both decoders judge the stream, on a CPU.
 #define DEF_HOST 1
 #include "deflate_core.hpp"
+#include "textgz_phase.hpp"
 #include "../../include/svx.h"
 #include <zlib.h>
 
@@ -13,4 +14,9 @@ extern "C" int svx_text_gz_host(const uint8_t* text, int64_t n, uint8_t* out, in
     if (got < 0) return SVX_E_CAPACITY;
     *n_out = got;
     return SVX_OK;
+}
+
+extern "C" int svx_text_gz_phase_host(int phase, int64_t n_blocks, const uint8_t* text, const int64_t* text_off, const uint32_t* n, const uint32_t* crc, uint32_t* tok, uint32_t* nt,
+                                      uint32_t* hist, uint32_t* codes, uint8_t* slots) {
+    return tgz_phase_host(phase, n_blocks, text, text_off, n, crc, tok, nt, hist, codes, slots) ? SVX_E_ARG : SVX_OK;
 }

@@ -627,6 +627,9 @@ def _valid_cases(add):
     s = Stream().stored(R(46, 3000)).fixed(list(R(47, 2000)) + [(258, 4000), (10, 5000)]).dynamic(list(R(48, 2500)) + [(258, 7000), (100, 2600), (50, 7800)])
     s.stored(R(49, 10)).fixed([(258, 8000), (200, 9), (258, 4200)]).dynamic([(258, 8600), (258, 300), (3, 9000)], True)
     add("block/matches-back-into-stored-fixed-dynamic-predecessors", "block structure", s)
+    for k in (1, 2, 5, 14, 15):                                                # fewer bytes than lie in front of the destination's first 16-byte boundary: nothing to flush yet
+        add("block/stored-%d-bytes-alone" % k, "block structure", Stream().stored(R(50 + k, k), True))
+    add("block/stored-3-bytes-then-fixed", "block structure", Stream().stored(R(66, 3)).fixed([7, 8, 9, (3, 6)], True))
     add("block/output-0-bytes.stored", "block structure", Stream().stored(b"", True))
     add("block/output-0-bytes.fixed", "block structure", Stream().fixed([], True))
     add("block/output-0-bytes.dynamic", "block structure", Stream().dynamic([], True))

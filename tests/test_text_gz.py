@@ -59,7 +59,9 @@ def test_the_projects_decoders_read_it(tmp_path):
 
 def test_encoder_under_the_sanitizers(tmp_path):
     """tools/text_gz_host_test.cpp (the header with -DDEF_HOST) under AddressSanitizer + UndefinedBehaviorSanitizer over a seeded fuzz of the kinds of text above:
-    every stream inflates back under zlib, no report (the LDS scratch members are plain arrays here: their bounds are checked)"""
+    every stream inflates back under zlib, no report (the LDS scratch members are plain arrays here: their bounds are checked); and over the phase-level cases
+    of tests/deflate_encode_cases.py (`cases FILE`): every block equals the model's, with the staging window of the 64 x 48-bit batches, every token buffer
+    and every slot a heap block of its own size"""
     out = str(tmp_path / "text_gz_host_asan")
     build = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-DDEF_HOST", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
                             "-I", CSRC, os.path.join(REPO, "tools", "text_gz_host_test.cpp"), "-lz", "-o", out], capture_output=True, text=True)
@@ -70,6 +72,12 @@ def test_encoder_under_the_sanitizers(tmp_path):
     assert run.returncode == 0 and "3000 buffers, 0 mismatches" in run.stdout, (run.stdout[-500:], run.stderr[-3000:])
     stored, dynamic = (int(run.stdout.split(w)[0].split()[-1]) for w in (" stored", " dynamic"))
     assert stored > 300 and dynamic > 1000, run.stdout[-300:]
+    import deflate_encode_cases as DC
+    cases = str(tmp_path / "cases.bin")
+    n_blocks = DC.write_case_file(cases)
+    assert sum(1 for c in DC.bits_cases() if c["name"].startswith("items_64x48_at_")) == 32
+    run = subprocess.run([out, "cases", cases], capture_output=True, text=True, timeout=1200)
+    assert run.returncode == 0 and "cases: %d blocks, 0 mismatches" % n_blocks in run.stdout, (run.stdout[-500:], run.stderr[-3000:])
 
 
 def test_size_against_zlib_level_1():

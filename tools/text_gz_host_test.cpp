@@ -2,8 +2,11 @@
 // zlib: every stream must inflate back to its text.  Meant for -fsanitize=address,undefined (tests/test_text_gz.py builds it so).
 //   text_gz_host_test fuzz SEED COUNT     COUNT seeded buffers of the kinds the writers meet and the corners of the format -> "COUNT buffers, 0 mismatches"
 //   text_gz_host_test file IN OUT         the BGZF stream of file IN written to OUT; prints bytes in / out and blocks by kind
+//   text_gz_host_test cases FILE          the phase-level cases of tests/deflate_encode_cases.py (write_case_file: inputs and what tests/deflate_model.py answers)
+//                                         through the host phases (textgz_phase.hpp) -> "cases: N blocks, 0 mismatches"; exit status 3 when a block differs
 // build: g++ -O1 -g -std=c++17 -DDEF_HOST -fsanitize=address,undefined -I svim_amd/csrc tools/text_gz_host_test.cpp -lz
 #include "deflate_core.hpp"
+#include "textgz_phase.hpp"
 #include <zlib.h>
 #include <cstdio>
 #include <cstdlib>
@@ -66,6 +69,55 @@ static void make_buffer(std::vector<uint8_t>& t) {
     } else { for (uint32_t i = 0; i < n; i++) t[i] = (uint8_t)(rnd() % (1 + i % 7) + 'a'); }           // skewed small alphabet
 }
 
+// ---- cases FILE: sections of (phase, nb, text, text_off, n, crc, inputs, expected results), little-endian, as write_case_file lays them out ----
+template <class T> static bool rd(FILE* f, std::vector<T>& v, size_t count) { v.resize(count); return count == 0 || fread(v.data(), sizeof(T), count, f) == count; }
+static int run_cases(const char* path) {
+    FILE* f = fopen(path, "rb");
+    if (!f) { perror(path); return 2; }
+    std::vector<int64_t> head;
+    long blocks = 0, bad = 0;
+    if (!rd(f, head, 1) || head[0] != 0x3143464544585653ll) { fprintf(stderr, "%s: not a case file\n", path); return 2; }
+    while (rd(f, head, 3)) {
+        const int phase = (int)head[0]; const int64_t nb = head[1], n_text = head[2];
+        if (phase < 0 || phase > 2 || nb < 1 || nb > TGZ_PHASE_MAXBLOCKS || n_text < 0) { fprintf(stderr, "%s: bad section\n", path); return 2; }
+        std::vector<uint8_t> text, want_bytes, slots;
+        std::vector<int64_t> off;
+        std::vector<uint32_t> n, crc, nt, want_nt, hist, want_hist, dense, codes, want_codes, want_size, tok((size_t)(phase == 1 ? 1 : nb * (int64_t)DEF_BLOCK), 0u);
+        bool ok = rd(f, text, (size_t)n_text) && rd(f, off, (size_t)nb + 1) && rd(f, n, (size_t)nb) && rd(f, crc, (size_t)nb);
+        auto dense_sum = [&](const std::vector<uint32_t>& c) { size_t t = 0; for (uint32_t x : c) t += x; return t; };
+        if (ok && phase == TGZ_PHASE_MATCH) ok = rd(f, want_nt, (size_t)nb) && rd(f, want_hist, (size_t)nb * DEF_NHIST) && rd(f, dense, dense_sum(want_nt));
+        if (ok && phase == TGZ_PHASE_CODES) ok = rd(f, hist, (size_t)nb * DEF_NHIST) && rd(f, want_codes, (size_t)nb * TGZ_CODES_WORDS);
+        if (ok && phase == TGZ_PHASE_BITS) ok = rd(f, nt, (size_t)nb) && rd(f, dense, dense_sum(nt)) && rd(f, codes, (size_t)nb * TGZ_CODES_WORDS) && rd(f, want_size, (size_t)nb) && rd(f, want_bytes, dense_sum(want_size));
+        if (!ok) { fprintf(stderr, "%s: truncated\n", path); return 2; }
+        text.resize(text.size() + 1);                   // (data() of an empty vector may be null)
+        if (phase == TGZ_PHASE_MATCH) { nt.assign((size_t)nb, 0u); hist.assign((size_t)nb * DEF_NHIST, 0u); }
+        if (phase == TGZ_PHASE_CODES) codes.assign((size_t)nb * TGZ_CODES_WORDS, 0xffffffffu);
+        if (phase == TGZ_PHASE_BITS) {
+            slots.assign((size_t)nb * DEF_SLOT, 0);
+            size_t at = 0;
+            for (int64_t b = 0; b < nb; b++) { if (nt[b] > DEF_BLOCK) return 2; memcpy(tok.data() + b * (int64_t)DEF_BLOCK, dense.data() + at, (size_t)nt[b] * 4); at += nt[b]; }
+        }
+        if (const char* why = tgz_phase_host(phase, nb, text.data(), off.data(), n.data(), crc.data(), tok.data(), nt.data(), hist.data(), codes.data(), slots.data())) {
+            printf("phase %d: refused: %s\n", phase, why);
+            return 2;
+        }
+        size_t at = 0;
+        for (int64_t b = 0; b < nb; b++) {
+            bool same = true;
+            if (phase == TGZ_PHASE_MATCH) {
+                same = nt[b] == want_nt[b] && !memcmp(&hist[b * DEF_NHIST], &want_hist[b * DEF_NHIST], DEF_NHIST * 4) && !memcmp(&tok[b * (int64_t)DEF_BLOCK], dense.data() + at, (size_t)want_nt[b] * 4);
+                at += want_nt[b];
+            } else if (phase == TGZ_PHASE_CODES) same = !memcmp(&codes[b * TGZ_CODES_WORDS], &want_codes[b * TGZ_CODES_WORDS], TGZ_CODES_WORDS * 4);
+            else { same = !memcmp(&slots[b * (int64_t)DEF_SLOT], want_bytes.data() + at, want_size[b]); at += want_size[b]; }
+            if (!same) { if (bad < 10) printf("phase %d, block %lld differs\n", phase, (long long)b); bad++; }
+        }
+        blocks += nb;
+    }
+    fclose(f);
+    printf("cases: %ld blocks, %ld mismatches\n", blocks, bad);
+    return bad ? 3 : 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 4 && std::string(argv[1]) == "fuzz") {
         g_state = 0x9E3779B97F4A7C15ull ^ (uint64_t)atoll(argv[2]);
@@ -99,6 +151,7 @@ int main(int argc, char** argv) {
         printf("%zu bytes -> %lld bytes (blocks: %lld end-of-file, %lld stored, %lld dynamic)\n", t.size(), (long long)got, (long long)kinds[0], (long long)kinds[1], (long long)kinds[2]);
         return 0;
     }
-    fprintf(stderr, "usage: %s fuzz SEED COUNT | file IN OUT\n", argv[0]);
+    if (argc == 3 && std::string(argv[1]) == "cases") return run_cases(argv[2]);
+    fprintf(stderr, "usage: %s fuzz SEED COUNT | file IN OUT | cases FILE\n", argv[0]);
     return 2;
 }
