@@ -663,6 +663,27 @@ int  svx_bam_rewind(svx_bam* h);
 /* contig-sharded ranks: continue at BGZF virtual offset `voff` (the .bai gives the first record of every contig) and report end-of-file at
  * the first record whose reference id exceeds last_tid or that is unplaced (-2: no limit) */
 int  svx_bam_seek(svx_bam* h, uint64_t voff, int32_t last_tid);
+/* Region reads (coordinate mode only; the definition in words: svim_amd/regions.py, the tests in one place: csrc/region_core.hpp).  Reading continues at
+ * virtual offset `voff` (from the .bai / .csi: regions.plan) and reports end-of-file at the first record that is unplaced, lies on a reference behind `tid`,
+ * or lies on `tid` with pos >= end.  Records of an earlier reference are not kept and do not stop the read.  What is handed out is ONE contiguous run of the
+ * file: from the first kept record to the last record in front of the stop; inside it a record the rule does not keep carries SVX_FLAG_SKIP (COLLECT, the
+ * alignment table and the oracle pass over it), and n_out of svx_bam_read_batch counts the run, marked records included.  A region without a kept record
+ * hands out nothing.  SVX_REGION_OVERLAP keeps a record whose interval - the index's own: pos .. pos + reference span of the effective CIGAR (CG rule), a
+ * record without a span occupies [pos, pos + 1) - overlaps [beg, end): what `samtools view file region` prints.  SVX_REGION_START keeps beg <= pos < end:
+ * a record belongs to exactly one of a set of abutting regions.
+ * SVX_E_STATE: SAM text, an index build or a sort pass in progress; a svx_bam_read_batch in query-name mode while a region is set.  SVX_E_ARG: end <= beg,
+ * beg < 0, a tid outside the header, an unknown rule, an offset beyond the file.  svx_bam_rewind and svx_bam_seek lift the bound; while it is set
+ * svx_bam_index_begin and svx_bam_sort_begin answer SVX_E_STATE (their pass runs over the whole file).
+ * Device decode: chunks in front of the first kept record are decoded and dropped without being handed out; they are loaded into the slot that was loaded
+ * last, so the lifetime of earlier batches is what it is without regions. */
+#define SVX_REGION_OVERLAP 0
+#define SVX_REGION_START   1
+int  svx_bam_seek_region(svx_bam* h, uint64_t voff, int32_t tid, int32_t beg, int32_t end, int rule);
+/* since the last svx_bam_seek_region: records examined in front of the stop, records kept, records handed out with SVX_FLAG_SKIP by the rule, bytes of the
+ * BGZF blocks loaded (in the file / inflated; a reader that loads ahead counts what it has loaded).  Kept and marked records are those of the run: in a
+ * file that is not sorted a record behind the first stop is neither, whatever the rule says of it */
+struct svx_bam_region_stats { int64_t n_seen, n_kept, n_marked, bytes_compressed, bytes_inflated; };      /* (a tag, no typedef: the function has the name) */
+int  svx_bam_region_stats(svx_bam* h, struct svx_bam_region_stats* out);
 /* BGZF inflate shared between the GPU (svx_inflater on `device`; < 0: off) and the host's cores: of every chunk of blocks the GPU takes sub-batches
  * from the front while the worker threads take blocks from the back - whoever is faster inflates more.  stats: blocks inflated by either so far. */
 int  svx_bam_set_gpu_inflate(svx_bam* h, int device);

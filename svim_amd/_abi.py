@@ -260,6 +260,16 @@ class BamIndexStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+REGION_RULES = {"overlap": 0, "start": 1}      # SVX_REGION_OVERLAP, SVX_REGION_START (svim_amd/regions.py)
+
+
+class BamRegionStats(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_seen", "n_kept", "n_marked", "bytes_compressed", "bytes_inflated")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class GenotypeParams(C.Structure):
     _fields_ = [("minimum_score", C.c_double), ("min_mapq", C.c_int32), ("minimum_depth", C.c_int32), ("homozygous_threshold", C.c_double),
                 ("heterozygous_threshold", C.c_double)]

@@ -24,7 +24,7 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_collect_keep_alignments", "svx_alignments_count", "svx_alignments_fetch", "svx_alignments_get_stats",
            "svx_genotype_resident", "svx_genotype_count", "svx_genotype_fetch", "svx_genotype_get_stats", "svx_vcf_use_resident_genotypes",
            "svx_cigar_indel", "svx_edit_distance", "svx_linkage_fcluster", "svx_pair_distances",
-           "svx_bam_open", "svx_bam_close", "svx_bam_header", "svx_bam_read_batch", "svx_bam_read_names", "svx_bam_set_seq_filter", "svx_bam_rewind", "svx_bam_seek", "svx_bam_set_gpu_inflate", "svx_bam_gpu_inflate_stats",
+           "svx_bam_open", "svx_bam_close", "svx_bam_header", "svx_bam_read_batch", "svx_bam_read_names", "svx_bam_set_seq_filter", "svx_bam_rewind", "svx_bam_seek", "svx_bam_seek_region", "svx_bam_region_stats", "svx_bam_set_gpu_inflate", "svx_bam_gpu_inflate_stats",
            "svx_inflater_create", "svx_inflater_destroy", "svx_inflater_staging", "svx_inflater_enqueue", "svx_inflater_wait",
            "svx_inflater_run",
            "svx_genome_load_fasta", "svx_genome_fetch", "svx_fasta_probe", "svx_fasta_plan",

@@ -91,6 +91,24 @@ class NativeBam(object):
         if rc != 0:
             raise self._error(rc, "svx_bam_seek")
 
+    def seek_region(self, voff, tid, beg, end, rule="overlap"):
+        """region read (svx_bam_seek_region; svim_amd/regions.py says what it hands out): continue at virtual offset `voff` (regions.plan) and hand out the run
+        of records from the first one the rule keeps on reference `tid` in [beg, end) to the last one in front of the stop; records of the run that the
+        rule does not keep carry SVX_FLAG_SKIP.  rule: "overlap" (samtools view) or "start" (beg <= pos < end).  rewind() and seek() lift the bound"""
+        from . import regions
+        if rule not in (regions.RULE_OVERLAP, regions.RULE_START):
+            raise ValueError("seek_region: rule is %r or %r" % (regions.RULE_OVERLAP, regions.RULE_START))
+        rc = self.L.svx_bam_seek_region(self.h, C.c_uint64(int(voff)), C.c_int32(int(tid)), C.c_int32(int(beg)), C.c_int32(int(end)),
+                                        C.c_int(_abi.REGION_RULES[rule]))
+        if rc != 0:
+            raise self._error(rc, "svx_bam_seek_region")
+
+    def region_stats(self):
+        """since the last seek_region: records examined in front of the stop, kept, handed out marked; bytes of the BGZF blocks loaded (svx_bam_region_stats)"""
+        s = _abi.BamRegionStats()
+        self.L.svx_bam_region_stats(self.h, C.byref(s))
+        return s.as_dict()
+
     def rewind(self):
         """back to the first record; buffers, threads and interned names are kept (svx_bam_rewind)"""
         rc = self.L.svx_bam_rewind(self.h)

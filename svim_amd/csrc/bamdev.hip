@@ -15,6 +15,8 @@
 #include "bamsort.hpp"
 #include "sam.hpp"
 #include "contig_core.hpp"
+#include "cigar_span.hpp"
+#include "region_core.hpp"
 #include <zlib.h>
 #include <chrono>
 #include <mutex>
@@ -357,6 +359,88 @@ __global__ void k_first_beyond(long long n, const int32_t* tid, int32_t limit, u
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && (tid[i] < 0 || tid[i] > limit)) atomicMin(first, (unsigned long long)i);
 }
+// ---- region reads (include/svx.h svx_bam_seek_region; the tests themselves: region_core.hpp) ----------------------------------------------------------------
+// counters: [0] long records listed, [1] giant records listed, [2] first kept record, [3] first stopping record, [4] kept records.
+// k_region_span: a DPP row of 16 lanes per record.  Only a record of the region's reference that starts in front of the region needs a reference span, and only
+// under SVX_REGION_OVERLAP; records beyond RG_LONG_OPS operations go to a list (long from its front, giant - the CG records - from its back), as in k_bix_rows
+#define RG_LONG_OPS 4096
+#define RG_GIANT_OPS 65536
+#define RG_TILE 1024
+#define RG_LONG_BLOCKS 256
+__global__ __launch_bounds__(256) void k_region_span(long long n, RegionBound g, const int32_t* tid, const int32_t* pos, const uint64_t* cigar_off, const uint32_t* cigar, uint32_t* span,
+                                                     uint32_t* long_list, unsigned long long* counters) {
+    const long long r = ((long long)blockIdx.x * 256 + threadIdx.x) >> 4;
+    const int l = (int)(threadIdx.x & 15);
+    const bool in = r < n;
+    uint32_t s = 0; bool is_long = false, is_giant = false;
+    if (in && region_needs_span(g, tid[r], pos[r]) && !region_stops(g, tid[r], pos[r])) {
+        const unsigned long long lo = cigar_off[r], hi = cigar_off[r + 1];
+        if (hi > lo) { if (hi - lo > RG_LONG_OPS) { is_long = true; is_giant = hi - lo > RG_GIANT_OPS; } else s = span_partial(cigar, lo, hi, l, 16); }
+    }
+    s = (uint32_t)row_sum_i32((int)s);
+    if (in && l == 15) {
+        span[r] = s;
+        if (is_giant) long_list[n - 1 - (long long)atomicAdd(&counters[1], 1ull)] = (uint32_t)r;
+        else if (is_long) long_list[atomicAdd(&counters[0], 1ull)] = (uint32_t)r;
+    }
+}
+// the listed records: a wave per long record, the waves of the grid over the tiles of a giant one
+__global__ __launch_bounds__(256) void k_region_span_long(long long n, const unsigned long long* counters, const uint32_t* long_list, const uint64_t* cigar_off, const uint32_t* cigar,
+                                                          uint32_t* span) {
+    const unsigned long long n_mid = counters[0], n_giant = counters[1];
+    const int lane = lane_id();
+    const unsigned long long wave = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (unsigned long long)gridDim.x * 4;
+    for (unsigned long long k = wave; k < n_mid; k += n_waves) {
+        const uint32_t r = long_list[k];
+        const int s = wave_sum_i32((int)span_partial(cigar, cigar_off[r], cigar_off[r + 1], lane, 64));
+        if (lane == 0) atomicAdd(&span[r], (uint32_t)s);
+    }
+    for (unsigned long long k = 0; k < n_giant; k++) {
+        const uint32_t r = long_list[n - 1 - (long long)k];
+        const unsigned long long lo = cigar_off[r], hi = cigar_off[r + 1];
+        const unsigned long long tiles = (hi - lo + RG_TILE - 1) / RG_TILE;
+        for (unsigned long long t = wave; t < tiles; t += n_waves) {
+            const unsigned long long a = lo + t * RG_TILE, b = a + RG_TILE < hi ? a + RG_TILE : hi;
+            const int s = wave_sum_i32((int)span_partial(cigar, a, b, lane, 64));
+            if (lane == 0 && s) atomicAdd(&span[r], (uint32_t)s);
+        }
+    }
+}
+// per record: the stop and keep tests; the first of each by a 64-bit atomicMin (as k_first_beyond) - one per wave, from its first such lane: records behind a narrow
+// region's stop are nearly all of a chunk, and a million atomics on one address cost more than the chunk's decode.  span is read only where region_needs_span
+// holds (under SVX_REGION_START nowhere: the array is not even reserved then)
+__global__ __launch_bounds__(256) void k_region_decide(long long n, RegionBound g, const int32_t* tid, const int32_t* pos, const uint16_t* flag, const uint32_t* span,
+                                                       unsigned long long* counters) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    bool stop = false, keep = false;
+    if (i < n) {
+        const int32_t t = tid[i], p = pos[i];
+        stop = region_stops(g, t, p);
+        keep = !stop && region_keeps(g, t, p, region_needs_span(g, t, p) ? span[i] : 0u, flag[i]);
+    }
+    const unsigned long long m_stop = __ballot(stop), m_keep = __ballot(keep);
+    const int lane = lane_id();
+    if (m_stop && lane == __ffsll((long long)m_stop) - 1) atomicMin(&counters[3], (unsigned long long)i);
+    if (m_keep && lane == __ffsll((long long)m_keep) - 1) atomicMin(&counters[2], (unsigned long long)i);
+}
+// the run [first kept record (0 when the region has begun in an earlier chunk), first stopping record): a record the rule does not keep gets SVX_FLAG_SKIP, the kept
+// ones are counted through a wave reduction.  Only the run counts, as in the host reader, which ends at the first stop: in a file that is not sorted a record
+// behind the stop may pass the keep test
+__global__ __launch_bounds__(256) void k_region_flags(long long n, RegionBound g, int started, const int32_t* tid, const int32_t* pos, const uint32_t* span, unsigned long long* counters,
+                                                      uint16_t* flag) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long first = started ? 0ull : counters[2], stop = counters[3];
+    bool keep = false;
+    if (i < n && (unsigned long long)i >= first && (unsigned long long)i < stop) {
+        const int32_t t = tid[i], p = pos[i];
+        const uint16_t f = flag[i];
+        keep = region_keeps(g, t, p, region_needs_span(g, t, p) ? span[i] : 0u, f);
+        if (!keep) flag[i] = (uint16_t)(f | SVX_FLAG_SKIP);
+    }
+    const unsigned long long m_keep = __ballot(keep);
+    if (m_keep && lane_id() == 0) atomicAdd(&counters[4], (unsigned long long)__popcll(m_keep));
+}
+
 __global__ void k_order_iota(long long n, uint32_t* order, uint32_t* seg_order) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { order[i] = (uint32_t)(2 * i); seg_order[i] = (uint32_t)(2 * i + 1); }
@@ -457,6 +541,7 @@ struct DevChunk {
     std::vector<uint64_t> ix_start, ix_vbase;      // while a BAM index is being built: the chunk's block table (bamindex.hpp), the blocks under its carry-over included
     DevBuf flag, tid, pos, mapq, lseq, read_id, cigar_off, cigar, seq_off, seg_off, segop_off, seg_tid, seg_pos, seg_rev, seg_mapq, seg_lseq, seg_cigar_off, seg_cigar;
     DevBuf slot_of, new_rec, name_len, name_at, name_blob;
+    DevBuf rg_span, rg_long;                // region reads (devdec_region): reference span per record, the records with a long CIGAR
     DevBuf order[2], seg_order[2]; int order_flip = 0;
     // query-name mode: per handed-out batch (two alternating sets like order[]) the flags with SVX_FLAG_SKIP, the segment table made of the good supplementary records
     DevBuf q_flag[2], q_seg_off[2], q_seg_tid[2], q_seg_pos[2], q_seg_rev[2], q_seg_mapq[2], q_seg_lseq[2], q_seg_cigar_off[2], q_seg_cigar[2];
@@ -466,7 +551,7 @@ struct DevChunk {
     void release() {
         DevBuf* all[] = {&stream, &blk_off, &anchor, &cnt, &exit_at, &base, &rec_off, &desc, &n_cig, &n_seg, &n_segop, &scan_tmp, &crc_jobs, &flag, &tid, &pos, &mapq, &lseq, &read_id,
                          &cigar_off, &cigar, &seq_off, &seg_off, &segop_off, &seg_tid, &seg_pos, &seg_rev, &seg_mapq, &seg_lseq, &seg_cigar_off, &seg_cigar, &slot_of,
-                         &new_rec, &name_len, &name_at, &name_blob, &order[0], &order[1], &seg_order[0], &seg_order[1],
+                         &new_rec, &name_len, &name_at, &name_blob, &rg_span, &rg_long, &order[0], &order[1], &seg_order[0], &seg_order[1],
                          &q_flag[0], &q_flag[1], &q_seg_off[0], &q_seg_off[1], &q_seg_tid[0], &q_seg_tid[1], &q_seg_pos[0], &q_seg_pos[1], &q_seg_rev[0], &q_seg_rev[1],
                          &q_seg_mapq[0], &q_seg_mapq[1], &q_seg_lseq[0], &q_seg_lseq[1], &q_seg_cigar_off[0], &q_seg_cigar_off[1], &q_seg_cigar[0], &q_seg_cigar[1],
                          &q_head, &q_good, &q_gidx, &q_good_ex, &q_gs, &q_nprim, &q_pidx, &q_slots, &q_rows, &q_slot_ex, &q_row_ex, &q_row_rec, &q_row_ops};
@@ -480,7 +565,7 @@ struct svx_devdec {
     hipStream_t batch_stream = nullptr;        // the consumer's (devdec_batch): a chunk it hands out is complete, nothing of it waits behind the NEXT chunk's inflate
     svx_inflater* inf = nullptr;
     int32_t n_ref = 0;
-    DevBuf ref_len, contig_rank, ct_key, ct_tid, ct_names, ct_name_off, err, counters, crc_shift, batch_cnt;
+    DevBuf ref_len, contig_rank, ct_key, ct_tid, ct_names, ct_name_off, err, counters, crc_shift, batch_cnt, rg_cnt;
     uint32_t ct_mask = 0;
     DevBuf nt_key, nt_check, nt_id; uint32_t nt_cap = 0;
     std::vector<std::string> names;
@@ -496,7 +581,7 @@ struct svx_devdec {
 
 // slots of svx_devdec::h_cnt (pinned read-backs).  The loader thread (devdec_load / devdec_count) and the consumer (devdec_batch) use disjoint slots.
 enum { DD_H_OPS = 0, DD_H_WALK_TAIL = 1, DD_H_SEGOPS = 2, DD_H_SEG = 4, DD_H_SA_BAD = 6, DD_H_NEW = 8, DD_H_BLOB = 10, DD_H_FIRST_BEYOND = 12, DD_H_TAIL_BS = 13,
-       DD_H_LAST_GROUP = 16, DD_H_LAST_OFF = 17, DD_H_NEXT_BOUNDARY = 18, DD_H_GROUPS = 20, DD_H_ROWS = 21, DD_H_ROW_OPS = 22, DD_H_SLOTS = 24 };
+       DD_H_LAST_GROUP = 16, DD_H_LAST_OFF = 17, DD_H_NEXT_BOUNDARY = 18, DD_H_GROUPS = 20, DD_H_ROWS = 21, DD_H_ROW_OPS = 22, DD_H_REGION = 24 /* 3 values, the loader's */, DD_H_SLOTS = 28 };
 #define DD_PINNED_BYTES 320
 static_assert(64 + DD_H_SLOTS * sizeof(unsigned long long) <= DD_PINNED_BYTES, "the pinned block of svx_devdec holds h_err (64 bytes) and DD_H_SLOTS values of h_cnt");
 
@@ -553,7 +638,7 @@ void devdec_destroy(svx_devdec* d) {
     samdev_destroy(d->sam); d->sam = nullptr;
     bamindex_destroy(d->index); d->index = nullptr;
     for (auto& c : d->chunk) c.release();
-    DevBuf* all[] = {&d->ref_len, &d->contig_rank, &d->ct_key, &d->ct_tid, &d->ct_names, &d->ct_name_off, &d->err, &d->counters, &d->crc_shift, &d->batch_cnt, &d->nt_key, &d->nt_check, &d->nt_id};
+    DevBuf* all[] = {&d->ref_len, &d->contig_rank, &d->ct_key, &d->ct_tid, &d->ct_names, &d->ct_name_off, &d->err, &d->counters, &d->crc_shift, &d->batch_cnt, &d->rg_cnt, &d->nt_key, &d->nt_check, &d->nt_id};
     for (auto* b : all) b->release();
     if (d->h_err) (void)hipHostFree(d->h_err);
     if (d->hbuf) (void)hipHostFree(d->hbuf);
@@ -1049,6 +1134,40 @@ int devdec_count(svx_devdec* d, int slot, int32_t tid_limit, int64_t* n_rec, int
     *n_valid = (int64_t)d->h_cnt[DD_H_FIRST_BEYOND];
     return SVX_OK;
 }
+
+// region reads: marks, the first kept and the first stopping record, the count of kept records - one pinned read-back of three numbers per chunk
+int devdec_region(svx_devdec* d, int slot, int32_t tid, int32_t beg, int32_t end, int rule, bool started, int64_t* first_kept, int64_t* stop, int64_t* n_kept) {
+    DevChunk& c = d->chunk[slot];
+    *first_kept = c.n_rec; *stop = c.n_rec; *n_kept = 0;
+    if (c.n_rec == 0) return SVX_OK;
+    HIPCHK(hipSetDevice(d->device));
+    const long long n = c.n_rec;
+    const RegionBound g{tid, beg, end, rule};
+    hipStream_t st = d->stream;
+    const bool spans = rule == SVX_REGION_OVERLAP;             // (SVX_REGION_START decides by pos alone: no span array, no list, no span kernel)
+    SVXCHK(d->rg_cnt.reserve(64));
+    if (spans) { SVXCHK(c.rg_span.reserve((size_t)n * 4)); SVXCHK(c.rg_long.reserve((size_t)n * 4)); }
+    unsigned long long* cn = d->rg_cnt.as<unsigned long long>();
+    unsigned long long* hv = &d->h_cnt[DD_H_REGION];            // (pinned: the source and the target of asynchronous copies)
+    hv[0] = hv[1] = (unsigned long long)n; hv[2] = 0;
+    HIPCHK(hipMemsetAsync(cn, 0, 16, st));
+    HIPCHK(hipMemcpyAsync(cn + 2, hv, 24, hipMemcpyHostToDevice, st));
+    const uint32_t* span = spans ? c.rg_span.as<uint32_t>() : nullptr;
+    if (spans) {
+        k_region_span<<<GRIDB(n * 16, 256), 256, 0, st>>>(n, g, c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>(), c.rg_span.as<uint32_t>(),
+                                                         c.rg_long.as<uint32_t>(), cn);
+        k_region_span_long<<<RG_LONG_BLOCKS, 256, 0, st>>>(n, cn, c.rg_long.as<uint32_t>(), c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>(), c.rg_span.as<uint32_t>());
+    }
+    k_region_decide<<<GRIDB(n, 256), 256, 0, st>>>(n, g, c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(), span, cn);
+    k_region_flags<<<GRIDB(n, 256), 256, 0, st>>>(n, g, started ? 1 : 0, c.tid.as<int32_t>(), c.pos.as<int32_t>(), span, cn, c.flag.as<uint16_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hv, cn + 2, 24, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *first_kept = (int64_t)hv[0]; *stop = (int64_t)hv[1]; *n_kept = (int64_t)hv[2];
+    return SVX_OK;
+}
+// bytes of the slot's stream behind its last complete record (what the next chunk would carry over)
+uint64_t devdec_tail_bytes(const svx_devdec* d, int slot) { const DevChunk& c = d->chunk[slot]; return c.data_end > c.tail_start ? (uint64_t)(c.data_end - c.tail_start) : 0; }
 
 int devdec_batch(svx_devdec* d, int slot, int64_t first, int64_t* count_io, int mode, int min_mapq, svx_batch* out) {
     DevChunk& c = d->chunk[slot];

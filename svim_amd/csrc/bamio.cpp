@@ -30,6 +30,7 @@
 #include "../../include/svx.h"
 #include "devdec.hpp"
 #include "sam_host.hpp"
+#include "region_core.hpp"
 
 extern thread_local std::string g_svx_err;
 static int bam_fail(int code, const std::string& what) { g_svx_err = what; return code; }
@@ -189,12 +190,14 @@ struct svx_bam {
     Pool* pool = nullptr; Pool* pool_inflate = nullptr;
     bool region_done = false;
     int32_t tid_limit = -2;         // svx_bam_seek: reading stops (like EOF) at the first record whose reference id exceeds this (-2 = none)
+    // svx_bam_seek_region: the bound, whether a kept record has been seen since (what lies in front of it is not handed out), and the counts since the seek
+    bool rg_on = false, rg_started = false, rg_progress = false; bool rg_pending = false; RegionBound rg{-1, 0, 0, 0}, rg_next{-1, 0, 0, 0}; struct svx_bam_region_stats rg_stats{0, 0, 0, 0, 0};
     int seq_min_ins = 0;            // > 0: sparse SEQ (coordinate mode): only insertions of at least this length + whole split-read primaries
     struct KeptRange { uint32_t rec; int32_t q0, len; };
     std::vector<std::vector<KeptRange>> t_ranges;          // per decode task
     std::vector<uint32_t> t_rng_cnt; std::vector<uint64_t> t_seq_bytes;
     std::vector<uint32_t> name_id_tmp;
-    struct RecRef { const uint8_t* r; const uint8_t* end; const uint8_t* cig; uint32_t n_cig; };
+    struct RecRef { const uint8_t* r; const uint8_t* end; const uint8_t* cig; uint32_t n_cig; bool marked; };
     std::vector<RecRef> refs; std::vector<const char*> t_name, t_sa; std::vector<uint32_t> t_name_len, t_sa_len; std::vector<uint64_t> t_name_hash;
     int64_t total_records = 0;
     // svx_bam_set_gpu_inflate: the GPU inflates sub-batches of blocks from the front of every chunk while the host's cores take blocks from its back
@@ -209,7 +212,8 @@ struct svx_bam {
     size_t dev_chunk_bytes = (size_t)8192 << 20, dev_chunk_blocks = (size_t)1 << 30;      // test hooks: SVX_BAM_DEV_CHUNK_MB, SVX_BAM_DEV_CHUNK_BLOCKS
     std::string dev_names_blob;
     struct DevLoad { int slot = 0, carry_slot = -1, rc = SVX_OK; std::string err; int64_t n_rec = 0, n_valid = 0; bool file_done = false, empty = false;
-                     size_t fpos_start = 0; uint64_t skip = 0; };
+                     size_t fpos_start = 0; uint64_t skip = 0;
+                     int64_t first_kept = 0, n_kept = 0, n_seen = 0, bytes_compressed = 0, bytes_inflated = 0; };      // region reads
     // Chunk slots rotate 0 -> 1 -> 2 -> 0 over the whole life of the reader - ALSO across svx_bam_seek / svx_bam_rewind: the batch handed out last (and the
     // one before it) may still be read by the consumer's stream when the next region's first chunk is loaded (include/svx.h: arrays stay valid until the
     // third next chunk is loaded).  dev_last_slot = the slot that was loaded last.
@@ -289,8 +293,10 @@ static void inflate_next_chunk(svx_bam* h) {
         const size_t max_bytes = h->chunk_bytes;
         while (blocks.size() < h->chunk_blocks && total < max_bytes) {
             RawBlock b;
+            const size_t at = h->fpos;
             if (!read_block(h, b)) { h->next_eof = true; break; }
             b.out_at = total; total += b.isize;
+            if (h->rg_on) { h->rg_stats.bytes_compressed += (int64_t)(h->fpos - at); h->rg_stats.bytes_inflated += b.isize; }
             blocks.push_back(b);
         }
         h->next.resize_uninit(WIN_HEAD + total);
@@ -665,17 +671,41 @@ extern "C" int svx_bam_seek(svx_bam* h, uint64_t voff, int32_t last_tid) {
     if (coff > h->map_len) return bam_fail(SVX_E_ARG, "virtual offset beyond the end of the file");
     h->fpos = coff; h->file_eof = false; h->buf.clear(); h->pos = 0; h->next_len = 0; h->next_eof = false;
     h->tid_limit = last_tid; h->region_done = false;
+    // (the inflating thread is idle here: it reads the bound and counts into rg_stats)
+    h->rg_on = h->rg_pending; h->rg_pending = false;
+    if (h->rg_on) { h->rg = h->rg_next; h->rg_started = false; h->rg_progress = false; h->rg_stats = {0, 0, 0, 0, 0}; }
     if (h->dev) {                                          // device decode: the next chunk starts at that block, `uoff` bytes into its data
         dev_drop_prefetch(h);
         h->dev_eof_seen = false;
         h->dev_fpos = coff; h->dev_skip = uoff; h->dev_file_done = false; h->dev_region_done = false; h->dev_cur = -1; h->dev_first = h->dev_valid = 0; h->dev_have_carry = false;
-        h->dev_grow = 0; h->dev_region_bytes = last_tid != -2 ? (size_t)256 << 20 : 0;
+        h->dev_grow = 0; h->dev_region_bytes = last_tid != -2 || h->rg_on ? (size_t)256 << 20 : 0;
         return SVX_OK;
     }
     try {
         if (uoff && !ensure(h, uoff)) throw std::string("virtual offset beyond its block");
         h->pos += uoff;
     } catch (const std::string& e) { return bam_fail(SVX_E_ARG, e); }
+    return SVX_OK;
+}
+
+// Region reads (include/svx.h; the tests themselves: region_core.hpp): svx_bam_seek to `voff` without a contig limit, then the bound
+extern "C" int svx_bam_seek_region(svx_bam* h, uint64_t voff, int32_t tid, int32_t beg, int32_t end, int rule) {
+    if (!h) return bam_fail(SVX_E_ARG, "null reader");
+    if (h->is_sam) return bam_fail(SVX_E_STATE, "svx_bam_seek_region: SAM text has no virtual offsets");
+    if (h->dev && devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_seek_region while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
+    if (h->dev && devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_seek_region during a sort pass (svx_bam_sort_finish or svx_bam_sort_abort first)");
+    if (rule != SVX_REGION_OVERLAP && rule != SVX_REGION_START) return bam_fail(SVX_E_ARG, "svx_bam_seek_region: unknown rule (SVX_REGION_OVERLAP or SVX_REGION_START)");
+    if (tid < 0 || (size_t)tid >= h->ref_names.size()) return bam_fail(SVX_E_ARG, "svx_bam_seek_region: the header has no reference of that id");
+    if (beg < 0 || end <= beg) return bam_fail(SVX_E_ARG, "svx_bam_seek_region: an empty region (0 <= beg < end)");
+    h->rg_next = RegionBound{tid, beg, end, rule}; h->rg_pending = true;      // (svx_bam_seek takes the bound once the inflating thread is idle)
+    const int rc = svx_bam_seek(h, voff, -2);
+    h->rg_pending = false;
+    return rc;
+}
+extern "C" int svx_bam_region_stats(svx_bam* h, struct svx_bam_region_stats* out) {
+    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
+    if (h->prefetch_active) h->prefetch.wait();             // (the inflating thread counts the blocks it loads)
+    *out = h->rg_stats;
     return SVX_OK;
 }
 
@@ -687,6 +717,7 @@ extern "C" int svx_bam_rewind(svx_bam* h) {
     if (h->dev && devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_rewind during a sort pass (svx_bam_sort_finish or svx_bam_sort_abort first)");
     if (h->prefetch_active) { h->prefetch.wait(); h->prefetch_active = false; }
     h->prefetch_err.clear();
+    h->rg_on = false;                                    // (here, while the inflating thread is idle: it reads the flag)
     if (getenv("SVX_BAM_TIMING")) {                      // per pass: the stages of the pass that just ended
         fprintf(stderr, "bamio pass: wait for inflate %.3f s, window copy %.3f, record walk %.3f, decode %.3f, names + SA %.3f\n", h->t_wait, h->t_copy, h->t_walk, h->t_decode, h->t_intern);
         h->t_wait = h->t_copy = h->t_walk = h->t_decode = h->t_intern = 0;
@@ -696,10 +727,10 @@ extern "C" int svx_bam_rewind(svx_bam* h) {
         h->dev_eof_seen = false;
         h->dev_fpos = 0; h->dev_skip = h->header_bytes; h->dev_file_done = false; h->dev_region_done = false; h->dev_cur = -1; h->dev_first = h->dev_valid = 0; h->dev_have_carry = false;
         h->dev_grow = 0; h->dev_region_bytes = 0;
-        h->total_records = 0; h->tid_limit = -2; h->region_done = false;
+        h->total_records = 0; h->tid_limit = -2; h->region_done = false; h->rg_on = false;
         return SVX_OK;
     }
-    if (h->is_sam) { h->total_records = 0; h->tid_limit = -2; h->region_done = false; return SVX_OK; }      // (device decode is its only reading route)
+    if (h->is_sam) { h->total_records = 0; h->tid_limit = -2; h->region_done = false; h->rg_on = false; return SVX_OK; }      // (device decode is its only reading route)
     h->fpos = 0; h->file_eof = false; h->buf.clear(); h->pos = 0; h->next_len = 0; h->next_eof = false;
     try {
         if (!ensure(h, 12)) throw std::string("not a BAM file");
@@ -714,7 +745,7 @@ extern "C" int svx_bam_rewind(svx_bam* h) {
             h->pos += l_name + 4;
         }
     } catch (const std::string& e) { return bam_fail(SVX_E_ARG, e); }
-    h->total_records = 0; h->tid_limit = -2; h->region_done = false;
+    h->total_records = 0; h->tid_limit = -2; h->region_done = false; h->rg_on = false;
     return SVX_OK;
 }
 
@@ -850,6 +881,18 @@ static int64_t decode_run(svx_bam* h, int64_t max_count, bool sparse) {
             // (bam_tag2cigar: only a CG array at least as long as the placeholder replaces it - "don't move if the real CIGAR length is shorter than the fake")
             if (cg && cg_n >= rr.n_cig && cg_n < (1u << 29)) { if (cg + 4 * (size_t)cg_n > rr.end) throw std::string("corrupt CG tag"); rr.cig = cg; rr.n_cig = cg_n; }
         }
+        rr.marked = false;
+        if (h->rg_on) {                                    // region read (region_core.hpp): stop, keep or mark; nothing in front of the first kept record is handed out
+            const int32_t t = (int32_t)rd32(rr.r), ps = (int32_t)rd32(rr.r + 4);
+            if (region_stops(h->rg, t, ps)) { h->region_done = true; break; }
+            uint32_t span = 0;
+            if (region_needs_span(h->rg, t, ps)) for (uint32_t c = 0; c < rr.n_cig; c++) { const uint32_t w = rd32(rr.cig + 4 * (size_t)c); if ((0x18Du >> (w & 15u)) & 1u) span += w >> 4; }
+            const bool keep = region_keeps(h->rg, t, ps, span, rd16(rr.r + 14));
+            h->rg_stats.n_seen++;
+            if (keep) { h->rg_stats.n_kept++; h->rg_started = true; }
+            else if (!h->rg_started) { p += 4 + (size_t)bs; h->pos = p; h->rg_progress = true; continue; }
+            else { h->rg_stats.n_marked++; rr.marked = true; }
+        }
         cig_total += rr.n_cig;
         B.cigar_off.push_back(cig_total);
         refs.push_back(rr);
@@ -880,7 +923,7 @@ static int64_t decode_run(svx_bam* h, int64_t max_count, bool sparse) {
                 const unsigned l_name = r[8];
                 const uint32_t l_seq = rd32(r + 16);
                 B.tid[k] = (int32_t)rd32(r); B.bpos[k] = (int32_t)rd32(r + 4); B.mapq[k] = r[9];
-                B.flag[k] = (uint16_t)(rd16(r + 14) & 0x0fff); B.lseq[k] = (int32_t)l_seq;
+                B.flag[k] = (uint16_t)((rd16(r + 14) & 0x0fff) | (rr.marked ? SVX_FLAG_SKIP : 0u)); B.lseq[k] = (int32_t)l_seq;
                 h->t_name[i] = (const char*)r + 32; h->t_name_len[i] = l_name ? l_name - 1 : 0;
                 h->t_name_hash[i] = name_hash(h->t_name[i], h->t_name_len[i]);
                 const uint8_t* q = r + 32 + l_name + 4 * (size_t)rd16(r + 12);       // the record's own CIGAR field, CG or not
@@ -1028,30 +1071,59 @@ static svx_bam::DevLoad dev_load_chunk(svx_bam* h, int slot, int carry_slot, uin
         } catch (const std::exception& e) { r.rc = SVX_E_ARG; r.err = e.what(); }
         return r;
     }
-    std::vector<DevDecBlock> blocks;
-    size_t total = 0;
-    try {
-        size_t fp = h->dev_fpos;
-        std::swap(fp, h->fpos);                                   // (read_block walks h->fpos; the host reader is idle in device mode)
-        while (total < budget_bytes && blocks.size() < budget_blocks) {
-            RawBlock b;
-            const size_t coff = h->fpos;
-            if (!read_block(h, b)) { r.file_done = true; break; }
-            blocks.push_back(DevDecBlock{b.comp, (uint32_t)b.clen, b.isize, b.crc, (uint64_t)coff});
-            if (b.isize) h->dev_data_end = h->fpos;              // (the block behind the last data byte starts here: where a BAM index lets the last record end)
-            total += b.isize;
-        }
-        std::swap(fp, h->fpos);
-        h->dev_fpos = fp;
-    } catch (const std::string& e) { r.rc = SVX_E_ARG; r.err = e; return r; }
-    catch (const std::exception& e) { r.rc = SVX_E_ARG; r.err = e.what(); return r; }      // (this runs on a std::async thread: nothing may escape into future::get of a C entry point)
-    if (blocks.empty() && carry_slot < 0) { r.file_done = true; r.empty = true; return r; }
-    try {
-        r.rc = devdec_load(h->dev, slot, blocks.data(), blocks.size(), carry_slot, skip, r.file_done, min_mapq, mode);
-        if (r.rc == SVX_OK) r.rc = devdec_count(h->dev, slot, h->tid_limit, &r.n_rec, &r.n_valid);
-        if (r.rc != SVX_OK) r.err = svx_last_error();
-    } catch (const std::exception& e) { r.rc = SVX_E_ARG; r.err = e.what(); }
-    return r;
+    // (a loop only for region reads: a chunk in front of the region's first kept record is dropped and the same slot loaded again)
+    for (;;) {
+        std::vector<DevDecBlock> blocks;
+        size_t total = 0;
+        try {
+            size_t fp = h->dev_fpos;
+            std::swap(fp, h->fpos);                                   // (read_block walks h->fpos; the host reader is idle in device mode)
+            while (total < budget_bytes && blocks.size() < budget_blocks) {
+                RawBlock b;
+                const size_t coff = h->fpos;
+                if (!read_block(h, b)) { r.file_done = true; break; }
+                blocks.push_back(DevDecBlock{b.comp, (uint32_t)b.clen, b.isize, b.crc, (uint64_t)coff});
+                if (b.isize) h->dev_data_end = h->fpos;              // (the block behind the last data byte starts here: where a BAM index lets the last record end)
+                total += b.isize;
+            }
+            std::swap(fp, h->fpos);
+            h->dev_fpos = fp;
+        } catch (const std::string& e) { r.rc = SVX_E_ARG; r.err = e; return r; }
+        catch (const std::exception& e) { r.rc = SVX_E_ARG; r.err = e.what(); return r; }      // (this runs on a std::async thread: nothing may escape into future::get of a C entry point)
+        if (blocks.empty() && carry_slot < 0) { r.file_done = true; r.empty = true; return r; }
+        try {
+            r.rc = devdec_load(h->dev, slot, blocks.data(), blocks.size(), carry_slot, skip, r.file_done, min_mapq, mode);
+            if (r.rc == SVX_OK) r.rc = devdec_count(h->dev, slot, h->tid_limit, &r.n_rec, &r.n_valid);
+            if (r.rc == SVX_OK && h->rg_on) {
+                r.bytes_inflated += (int64_t)total; r.bytes_compressed += (int64_t)(h->dev_fpos - r.fpos_start);
+                int64_t stop = 0;
+                r.rc = devdec_region(h->dev, slot, h->rg.tid, h->rg.beg, h->rg.end, h->rg.rule, h->rg_started, &r.first_kept, &stop, &r.n_kept);
+                if (r.rc == SVX_OK) {
+                    r.n_valid = stop; r.n_seen += stop;
+                    if (h->rg_started) r.first_kept = 0;
+                    else if (r.first_kept > stop) r.first_kept = stop;
+                    // Nothing kept and no stop, in front of the region's first kept record: the chunk is dropped and the SAME slot is loaded again from where its
+                    // last complete record ends (the block that holds that byte, the bytes in front of it skipped): the rotation must not advance for a chunk
+                    // nothing is handed out from.  Such a chunk has no carry-over: the loads since the seek have all started inside a block of their own
+                    if (!h->rg_started && r.n_rec > 0 && r.n_kept == 0 && stop == r.n_rec && !r.file_done && carry_slot < 0) {
+                        const uint64_t tail = devdec_tail_bytes(h->dev, slot);
+                        uint64_t back = 0;
+                        size_t b = blocks.size();
+                        while (b > 0 && back < tail) { b--; back += blocks[b].isize; }
+                        if (back >= tail) {
+                            if (tail) h->dev_fpos = (size_t)blocks[b].coff;
+                            skip = tail ? back - tail : 0;
+                            r.skip = skip; r.fpos_start = h->dev_fpos;
+                            budget_bytes = std::min(budget_bytes * 4, std::max(budget_bytes, h->dev_chunk_bytes));
+                            continue;
+                        }
+                    }
+                }
+            }
+            if (r.rc != SVX_OK) r.err = svx_last_error();
+        } catch (const std::exception& e) { r.rc = SVX_E_ARG; r.err = e.what(); }
+        return r;
+    }
 }
 static void dev_start_prefetch(svx_bam* h, int slot, int carry_slot, uint64_t skip, int min_mapq) {
     // budgets are fixed here, on the caller's thread (the loader runs beside the consumer)
@@ -1091,6 +1163,9 @@ static int read_batch_device(svx_bam* h, int64_t max_records, int mode, int min_
         h->dev_prefetching = false;
         h->dev_skip = 0;
         if (r.rc != SVX_OK) return bam_fail(r.rc, r.err);
+        if (h->rg_on) {                                                     // region read: what this load examined and loaded, the chunks it dropped included
+            h->rg_stats.n_seen += r.n_seen; h->rg_stats.bytes_compressed += r.bytes_compressed; h->rg_stats.bytes_inflated += r.bytes_inflated;
+        }
         if (r.empty) { h->dev_file_done = true; h->dev_eof_seen = true; return SVX_OK; }
         if (r.n_rec == 0 && !r.file_done) {
             // not one complete record in the chunk (a header or a record longer than the chunk: only with the small chunks of the test hooks).  The rotation
@@ -1103,6 +1178,11 @@ static int read_batch_device(svx_bam* h, int64_t max_records, int mode, int min_
         }
         h->dev_grow = 0;
         h->dev_cur = r.slot; h->dev_first = 0; h->dev_valid = r.n_valid; h->dev_have_carry = true;
+        if (h->rg_on) {                                                     // region read: nothing in front of the first kept record; the counts of the chunks taken so far
+            h->dev_first = r.first_kept;
+            h->rg_stats.n_kept += r.n_kept; h->rg_stats.n_marked += (r.n_valid - r.first_kept) - r.n_kept;
+            if (r.n_kept > 0) h->rg_started = true;
+        }
         h->dev_file_done = r.file_done;                                     // (the records of this last chunk are still to be handed out: checked after them)
         if (r.n_valid < r.n_rec) h->dev_region_done = true;                 // contig-range reading: the range ends where the next contig (or the unplaced tail) begins
         // (a chunk without one complete record is carried over whole into the next load; devdec_load refuses when a record outgrows its carry-over room)
@@ -1132,6 +1212,7 @@ extern "C" int svx_bam_index_begin(svx_bam* h) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
     if (h->is_sam) return bam_fail(SVX_E_STATE, "svx_bam_index_begin: SAM text has no virtual offsets (sort it: svx_bam_sort_index gives the sorted file's index)");
     if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_index_begin: the index is built from the device reader's record stream (svx_bam_set_device_decode first)");
+    if (h->rg_on) return bam_fail(SVX_E_STATE, "svx_bam_index_begin on a region read (svx_bam_seek_region): the pass runs over the whole file (rewind first)");
     if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
         return bam_fail(SVX_E_STATE, "svx_bam_index_begin: the handle is not at its first record (begin before the first read, or rewind first)");
     if (devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_index_begin during a sort pass (the sorted file's index comes from svx_bam_sort_index)");
@@ -1214,6 +1295,7 @@ static int sort_begin(svx_bam* h, int64_t max_bytes, const char* spill_dir) {
     if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the sort is fed by the device reader's record stream (svx_bam_set_device_decode first)");
     if (devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
     if (devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin during a sort pass");
+    if (h->rg_on) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin on a region read (svx_bam_seek_region): the pass runs over the whole file (rewind first)");
     if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
         return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the handle is not at its first record (begin before the first read, or rewind first)");
     const int rc = devdec_sort_begin(h->dev, max_bytes, spill_dir);
@@ -1295,6 +1377,7 @@ extern "C" int svx_bam_sort_get_spill_stats(svx_bam* h, svx_bam_sort_spill_stats
 }
 
 extern "C" int svx_bam_read_batch(svx_bam* h, int64_t max_records, int mode, int min_mapq, svx_batch* out, int64_t* n_out) {
+    if (h->rg_on && mode == 1) return bam_fail(SVX_E_STATE, "svx_bam_read_batch: a region read (svx_bam_seek_region) has coordinate mode only");
     if (h->dev) return read_batch_device(h, max_records, mode == 1 ? 1 : 0, min_mapq, out, n_out);
     if (h->is_sam) return bam_fail(SVX_E_STATE, "svx_bam_read_batch: SAM text is read by the device reader only (svx_bam_set_device_decode first)");
     BatchArrays* const handed_out = h->b;                                                 // the set the previous call handed out: the caller may still upload from it
@@ -1307,8 +1390,9 @@ extern "C" int svx_bam_read_batch(svx_bam* h, int64_t max_records, int mode, int
             if (!ensure(h, 4)) break;                                                   // end of file
             const uint32_t bs = rd32(h->buf.data() + h->pos);
             if (!ensure(h, 4 + (size_t)bs)) throw std::string("truncated BAM record");
-            const int64_t got = decode_run(h, max_records - n, sparse);                  // at least the record just made available
-            if (got == 0 && !h->region_done) throw std::string("BAM record larger than the inflate window");
+            h->rg_progress = false;
+            const int64_t got = decode_run(h, max_records - n, sparse);                  // at least the record just made available (a region read may have passed over it)
+            if (got == 0 && !h->region_done && !h->rg_progress) throw std::string("BAM record larger than the inflate window");
             n += got;
         }
         if (mode == 1 && n == max_records) {

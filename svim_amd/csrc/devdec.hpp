@@ -26,6 +26,12 @@ int  devdec_load_text(svx_devdec* d, int slot, const uint8_t* text, size_t n, bo
 void devdec_sam_stats(const svx_devdec* d, svx_sam_stats* out);
 // records decoded in the slot; n_valid: those before the first record whose reference id is negative or above tid_limit (tid_limit -2: all)
 int  devdec_count(svx_devdec* d, int slot, int32_t tid_limit, int64_t* n_rec, int64_t* n_valid);
+// Region reads (svx_bam_seek_region; region_core.hpp): over the records of the slot, *stop = the first stopping record (n_rec: none), *first_kept = the first
+// record the rule keeps (n_rec: none), *n_kept = the records it keeps; SVX_FLAG_SKIP is or-ed into the flags of the records of [first_kept - or 0 when the
+// region has `started` in an earlier chunk - , stop) that the rule does not keep
+int  devdec_region(svx_devdec* d, int slot, int32_t tid, int32_t beg, int32_t end, int rule, bool started, int64_t* first_kept, int64_t* stop, int64_t* n_kept);
+// bytes of the slot's inflated stream behind its last complete record (what the next load would carry over)
+uint64_t devdec_tail_bytes(const svx_devdec* d, int slot);
 // device-resident svx_batch over records [first, first + count) of the slot (arrays stay valid until the slot is loaded again)
 // mode 1: *count grows to the end of the read group it ends in; flags carry SVX_FLAG_SKIP, the segment table holds the good supplementary records of every analysed
 // read and the emission slots follow the reference's per-read order (bamio.cpp svx_bam_read_batch does the same on the host)

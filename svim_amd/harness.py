@@ -40,13 +40,25 @@ class BamPipeline(object):
     """reader thread || GPU thread over one BAM file; results stay resident in the engine (accumulated lists)."""
 
     def __init__(self, path, options, engine, threads=0, batch_records=200_000, mode="coordinate", sparse_seq=True, regions=None, gpu_inflate=None,
-                 device_decode=None, keep_alignments=False, build_index=False, index_format="bai"):
+                 device_decode=None, keep_alignments=False, build_index=False, index_format="bai", index=None, region_rule="overlap"):
+        """regions: None (the whole file); [(virtual offset, last reference id)]: contig runs (svx_bam_seek); or coordinate regions (svim_amd/regions.py): region
+        strings ("chr1:10,000,000-12,000,000"), (contig, beg, end) tuples (0-based, half-open) - parsed, normalised and planned from the file's index, read in
+        file order - or planned reads (virtual offset, tid, beg, end) as regions.plan and harness.window_plan give them.  index: the .bai / .csi the plan comes
+        from - a path, its bytes, or None: <bam>.bai if present, else <bam>.csi.  region_rule: "overlap" (samtools view) or "start" (ownership by start)"""
         from .bamio import NativeBam
+        from . import regions as _regions
+        coordinate_regions = regions is not None and any(isinstance(r, str) or len(r) != 2 for r in regions)
+        if coordinate_regions and any(not isinstance(r, str) and len(r) == 2 for r in regions):
+            raise ValueError("regions: either (virtual offset, last reference id) pairs or coordinate regions, not both")
+        if coordinate_regions and mode != "coordinate":
+            raise ValueError("coordinate regions need a coordinate-sorted file (mode='coordinate')")
+        if region_rule not in _regions.RULES:
+            raise ValueError("region_rule: %s or %s" % _regions.RULES)
         if index_format not in ("bai", "csi", "auto"):
             raise ValueError("index_format: bai, csi or auto")
         if build_index and regions is not None:
             raise ValueError("build_index needs the pass over the whole file (no regions): an index describes every record")
-        if keep_alignments and (regions is not None or mode != "coordinate"):
+        if keep_alignments and ((regions is not None and not coordinate_regions) or mode != "coordinate"):
             raise ValueError("keep_alignments needs the whole coordinate-sorted file on one rank (contig shards and query-name order genotype through "
                              "SVIM_genotyping.genotype)")
         self.keep_alignments = bool(keep_alignments)
@@ -75,13 +87,45 @@ class BamPipeline(object):
                 self.bam.set_gpu_inflate(int(gpu_inflate))          # BGZF inflate shared between that GPU and the host's cores
             if sparse_seq and mode == "coordinate":
                 self.bam.set_seq_filter(int(getattr(options, "min_sv_size", 40)))
-        self.regions = regions            # [(virtual offset, last reference id)]: the contig runs this rank reads (None: the whole file)
-        self.region_slots = []            # per region: (first local emission slot, records)
+        self.region_rule = region_rule
+        if coordinate_regions:
+            try:
+                regions = self._plan_regions(path, regions, index, region_rule)
+            except Exception:
+                self.bam.close()
+                raise
+        self.regions = regions            # [(virtual offset, last reference id)]: the contig runs this rank reads; [(virtual offset, tid, beg, end)]: region reads (None: the whole file)
+        self.region_slots = []            # per region that handed out records: (first local emission slot, records)
+        self.region_slot_regions = []     # ... and the region itself (a region read may hand out nothing: it has no entry)
         self.stats = {}
         self.interrupted = False          # run() was ended by Ctrl-C (KeyboardInterrupt): the results are those of the batches collected until then
 
+    def _plan_regions(self, path, items, index, rule):
+        """coordinate regions -> [(virtual offset, tid, beg, end)] in file order; planned reads pass through (checked against the header)"""
+        from . import regions as _regions
+        refs, lens = self.bam.references, self.bam.lengths
+        planned = [r for r in items if not isinstance(r, str) and len(r) == 4]
+        if planned:
+            if len(planned) != len(items):
+                raise ValueError("regions: planned reads (virtual offset, tid, beg, end) are not mixed with regions still to be planned")
+            for _v, tid, beg, end in planned:
+                _regions.as_region((int(tid), beg, end), refs, lens)
+            return [(int(v), int(t), int(b), int(e)) for v, t, b, e in planned]
+        parsed = [_regions.as_region(r, refs, lens) for r in items]
+        if index is None:
+            index = next((path + ext for ext in (".bai", ".csi") if os.path.exists(path + ext)), None)
+            if index is None:
+                raise ValueError("regions need the file's index: %s.bai or %s.csi not found (harness.index_bam(path) writes one)" % (path, path))
+        if isinstance(index, (str, os.PathLike)):
+            if not os.path.exists(index):
+                raise ValueError("regions need the file's index: %s not found (harness.index_bam(path) writes one)" % (index,))
+            with open(index, "rb") as fh:
+                index = fh.read()
+        return _regions.plan(index, parsed, rule)
+
     def run(self):
         bam, eng, p = self.bam, self.eng, self.params
+        region_counts = dict(region_records_kept=0, region_records_marked=0, region_bytes_inflated=0)
         self._bed_read_names = None                   # (write_signature_files / write_candidate_files: the names of THIS pass)
         min_mapq = int(getattr(self.options, "min_mapq", 20))
         free = threading.Semaphore(2)                # the reader owns two array sets: at most one batch ahead of the GPU thread
@@ -94,7 +138,9 @@ class BamPipeline(object):
                 for region in (self.regions if self.regions is not None else [None]):
                     if stop.is_set():
                         break
-                    if region is not None:
+                    if region is not None and len(region) == 4:
+                        bam.seek_region(region[0], region[1], region[2], region[3], self.region_rule)
+                    elif region is not None:
                         bam.seek(region[0], region[1])
                     while True:
                         free.acquire()
@@ -105,6 +151,11 @@ class BamPipeline(object):
                         t_read[0] += time.perf_counter() - t0
                         if n == 0:
                             free.release()
+                            if region is not None and len(region) == 4:
+                                st = bam.region_stats()
+                                region_counts["region_records_kept"] += st["n_kept"]
+                                region_counts["region_records_marked"] += st["n_marked"]
+                                region_counts["region_bytes_inflated"] += st["bytes_inflated"]
                             break
                         box.append((b, n, region))
                         ready.release()
@@ -128,7 +179,7 @@ class BamPipeline(object):
         th.start()
         n_rec, slot_base, t_gpu, t_wait, n_batches = 0, 0, 0.0, 0.0, 0
         k = 0
-        self.region_slots = []
+        self.region_slots, self.region_slot_regions = [], []
         cur_region = object()
         at_end = False                                # the reader has returned 0 records at the end of the file
         try:
@@ -146,6 +197,7 @@ class BamPipeline(object):
                 if region is not cur_region:
                     cur_region = region
                     self.region_slots.append([slot_base, 0])
+                    self.region_slot_regions.append(region)
                 t0 = time.perf_counter()
                 eng.set_slot_base(slot_base)
                 # A KeyboardInterrupt that arrives while the call is inside libsvx is raised when the call RETURNS (ctypes): the batch's signatures are in the
@@ -182,6 +234,8 @@ class BamPipeline(object):
         t_collect_done = time.perf_counter()
         self.stats = dict(records=n_rec, batches=n_batches, t_collect_wall=t_collect_done - t_start, t_reader_busy=t_read[0], t_gpu_collect=t_gpu,
                           t_gpu_waits_for_reader=t_wait)
+        if self.regions is not None and any(len(r) == 4 for r in self.regions):
+            self.stats.update(region_counts)
         if self.build_index and at_end:
             # the reader has seen the end of the file: the row table its chunks appended becomes the .bai - no second read of the file
             t0 = time.perf_counter()
@@ -908,10 +962,28 @@ def shard_plan(references, lengths, bai, rank, world):
     return owner, runs
 
 
-def collect_cluster_bam_sharded(bam_path, opts, engine, adapter, rank, world, threads=0, batch_records=200_000, bai_path=None, gather_names=True):
-    """One rank of a contig-sharded run over an indexed, coordinate-sorted BAM: read this rank's contig runs (svx_bam_seek), COLLECT
-    them batch by batch (accumulating), exchange the region sizes so that emission slots are global, then multigpu.cluster_step.
+def window_plan(windows, rank, references, lengths, index):
+    """The reads of one rank under coordinate-window ownership: the part of every contig whose keys the rank owns (Windows.rank_intervals), planned from the
+    file's index (bytes or a parsed dict, .bai or .csi) under regions.RULE_START - a record belongs to the rank that owns its start -> [(virtual offset, tid,
+    beg, end)] in file order.  Global contig ids are the header's reference ids here, so `windows` must have been cut for this header: its contig ranks are those
+    of `references` (ValueError otherwise - windows of another header would deal the records out by another order of the contigs)"""
+    from . import regions as _regions
+    from .batch import contig_ranks
+    if len(references) != len(lengths) or not np.array_equal(np.asarray(windows.crank), contig_ranks(references)[:len(references)]):
+        raise ValueError("window_plan: the windows were not cut for this header's references")
+    return _regions.plan(index, windows.rank_intervals(rank, lengths), _regions.RULE_START)
+
+
+def collect_cluster_bam_sharded(bam_path, opts, engine, adapter, rank, world, threads=0, batch_records=200_000, bai_path=None, gather_names=True,
+                                ownership="contigs", windows=None):
+    """One rank of a sharded run over an indexed, coordinate-sorted BAM: read this rank's share of the file, COLLECT it batch by batch (accumulating), exchange
+    the region sizes so that emission slots are global, then multigpu.cluster_step.
+    ownership "contigs": whole contigs (multigpu.assign_contigs), read as contig runs (svx_bam_seek).  "windows": coordinate windows with cuts inside contigs -
+    `windows`, or multigpu.assign_windows(references, lengths, world) - read as window_plan gives them (svx_bam_seek_region, ownership by start).  The windows
+    only deal out the records here: cluster_step refines the cuts and sends every signature to its window's owner, whoever collected it.
     Returns (StepResult or None, pipeline, read-name list of this rank)."""
+    if ownership not in ("contigs", "windows"):
+        raise ValueError("ownership: contigs or windows")
     import torch.distributed as dist
     from . import multigpu, records
     from .batch import contig_ranks
@@ -921,21 +993,29 @@ def collect_cluster_bam_sharded(bam_path, opts, engine, adapter, rank, world, th
     probe.close()
     if bai_path is None:                                     # (either kind of index: a .csi when the file has no .bai)
         bai_path = bam_path + ".bai" if os.path.exists(bam_path + ".bai") or not os.path.exists(bam_path + ".csi") else bam_path + ".csi"
-    bai = records.read_index(bai_path)
-    owner, runs = shard_plan(refs, lens, bai, rank, world)
-    pipe = BamPipeline(bam_path, opts, engine, threads=threads, batch_records=batch_records, regions=[(v, last) for v, last, _ in runs])
+    if ownership == "windows":
+        owner = windows if windows is not None else multigpu.assign_windows(refs, lens, world)
+        with open(bai_path, "rb") as fh:
+            plan = window_plan(owner, rank, refs, lens, fh.read())
+        pipe = BamPipeline(bam_path, opts, engine, threads=threads, batch_records=batch_records, regions=plan, region_rule="start")
+    else:
+        bai = records.read_index(bai_path)
+        owner, runs = shard_plan(refs, lens, bai, rank, world)
+        pipe = BamPipeline(bam_path, opts, engine, threads=threads, batch_records=batch_records, regions=[(v, last) for v, last, _ in runs])
     n_rec = pipe.run()
     # emission slots in file order: every region's local slot range moves to the sum of the spans of the regions before it in the file
     ends = [s for s, _ in pipe.region_slots[1:]] + [pipe.region_slots[-1][0] + 2 * pipe.region_slots[-1][1] + 2 * pipe.stats["batches"] + 2] if pipe.region_slots else []
-    local = [(runs[k][2], pipe.region_slots[k][0], ends[k] - pipe.region_slots[k][0]) for k in range(len(pipe.region_slots))]   # (first tid, local start, span)
+    # (first tid, beg, local start, span) of every region that handed out records.  With cuts inside a contig two ranks' regions share a first tid: beg orders them
+    first_of = {tuple(g): ((g[1], g[2]) if len(g) == 4 else (runs[k][2], 0)) for k, g in enumerate(pipe.regions)}
+    local = [first_of[tuple(g)] + (pipe.region_slots[k][0], ends[k] - pipe.region_slots[k][0]) for k, g in enumerate(pipe.region_slot_regions)]
     everyone = [None] * world
     dist.all_gather_object(everyone, local)
-    order = sorted((first_tid, r, k, span) for r, regs in enumerate(everyone) for k, (first_tid, _, span) in enumerate(regs))
+    order = sorted((first_tid, beg, r, k, span) for r, regs in enumerate(everyone) for k, (first_tid, beg, _, span) in enumerate(regs))
     base, acc = {}, 0
-    for first_tid, r, k, span in order:
+    for first_tid, _beg, r, k, span in order:
         base[(r, k)] = acc
         acc += span
-    key_runs = ([st for _, st, _ in local], [base[(rank, k)] for k in range(len(local))]) if local else ([0], [0])
+    key_runs = ([st for _, _, st, _ in local], [base[(rank, k)] for k in range(len(local))]) if local else ([0], [0])
     names = pipe.bam.read_names()
     index = None
 

@@ -127,6 +127,21 @@ class Windows(object):
         key = (cr[contig_gid.long()] << 33) | (pos.long() + 1).clamp_min(0)
         return self._rank_of_keys(key)
 
+    def rank_intervals(self, rank, lengths):
+        """the part of every contig whose keys lie in the rank's [cut[rank - 1], cut[rank]) -> [(global contig id, beg, end)], 0-based half-open, in reference-id
+        order: the positions p of the contig with owner_of_positions(contig, p) == rank.  A cut with cut_pos = -1 gives the whole contig to the rank above"""
+        cuts = self._cut_keys()
+        lo = int(cuts[rank - 1]) if rank > 0 else None
+        hi = int(cuts[rank]) if rank < self.world - 1 else None
+        out = []
+        for c in range(len(lengths)):
+            base = int(self.crank[c]) << 33                              # key of position p: base | (p + 1)
+            beg = 0 if lo is None else max(0, lo - base - 1)
+            end = int(lengths[c]) if hi is None else min(int(lengths[c]), hi - base - 1)
+            if beg < end:
+                out.append((c, beg, end))
+        return out
+
     def owner_of_signatures(self, typ, contig_gid, contig2_gid, start, end, pos2):
         """owner of signature rows (columns of a signature table with GLOBAL contig ids): the coordinate is the one the partition key uses
         (csrc/cluster.hip k_make_keys); DUP_INT rows go with the first base of their destination contig"""

@@ -14,6 +14,7 @@
 #include <vector>
 #include "../include/svx.h"
 #include "../svim_amd/csrc/devdec.hpp"
+#include "../svim_amd/csrc/region_core.hpp"
 
 thread_local std::string g_svx_err;
 extern "C" const char* svx_last_error(void) { return g_svx_err.c_str(); }
@@ -108,6 +109,23 @@ int devdec_batch(svx_devdec* d, int slot, int64_t first, int64_t* count, int mod
     out->seg_off = S.seg_off + first; out->seg_cigar_off = S.seg_cigar_off; out->n_contig = (int32_t)d->rank.size(); out->contig_rank = d->rank.data();
     return SVX_OK;
 }
+// region reads (bamdev.hip k_region_*): the same tests of region_core.hpp, record by record
+int devdec_region(svx_devdec* d, int slot, int32_t tid, int32_t beg, int32_t end, int rule, bool started, int64_t* first_kept, int64_t* stop, int64_t* n_kept) {
+    MockSlot& S = d->slot[slot];
+    const RegionBound g{tid, beg, end, rule};
+    *first_kept = S.n_rec; *stop = S.n_rec; *n_kept = 0;
+    std::vector<uint8_t> keep((size_t)S.n_rec, 0);
+    for (int64_t i = 0; i < S.n_rec; i++) {
+        if (region_stops(g, S.tid[i], S.pos[i])) { if (i < *stop) *stop = i; continue; }
+        uint32_t span = 0;
+        for (uint64_t c = S.cigar_off[i]; c < S.cigar_off[i + 1]; c++) if ((0x18Du >> (S.cigar[c] & 15u)) & 1u) span += S.cigar[c] >> 4;
+        if (region_keeps(g, S.tid[i], S.pos[i], span, S.flag[i])) { keep[(size_t)i] = 1; if (i < *first_kept) *first_kept = i; }
+    }
+    // (only the run [first kept, stop) is marked and counted: in a file that is not sorted a record behind the stop may pass the keep test)
+    for (int64_t i = started ? 0 : *first_kept; i < *stop; i++) { if (keep[(size_t)i]) (*n_kept)++; else S.flag[i] |= (uint16_t)SVX_FLAG_SKIP; }
+    return SVX_OK;
+}
+uint64_t devdec_tail_bytes(const svx_devdec* d, int slot) { const MockSlot& S = d->slot[slot]; return S.stream ? (uint64_t)S.stream->size() - S.tail_start : 0; }
 const std::vector<std::string>& devdec_names(svx_devdec* d) { return d->names; }
 void devdec_stats(svx_devdec*, DevDecStats*) {}
 void devdec_reset_names(svx_devdec* d) { d->names.clear(); }
@@ -204,6 +222,7 @@ static long long read_to_end(const char* path, int mode, int seq_filter, int thr
     return total;
 }
 
+#ifndef BAMIO_FUZZ_NO_MAIN          /* (tools/region_host_test.cpp takes the stand-in and the helpers above and has a main of its own) */
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: bamio_fuzz <seed.bam> <iterations>\n"); return 2; }
     const std::vector<uint8_t> file = read_file(argv[1]);
@@ -359,3 +378,4 @@ int main(int argc, char** argv) {
     printf("damaged files: %d, read to the end %lld, refused %lld\n", iters, ok, failed);
     return 0;
 }
+#endif
