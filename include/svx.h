@@ -810,6 +810,21 @@ int  svx_bam_sort_spill_host(const uint8_t* records, int64_t n_bytes, int32_t n_
 /* host-only: the header of the sorted file from a file's header (magic .. reference dictionary).  *n_out is the size also when cap is too small (SVX_E_CAPACITY) */
 int  svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out);
 
+/* ---- several files merged into one sorted file: the definition's host build (the definition in words: svim_amd/bammerge.py) ----
+ * The merged dictionary is the first file's references, then file by file the names not yet present; tid_map[f][i] is the merged id of file f's reference i.
+ * A record of a file whose map is the identity is copied verbatim; any other record gets refID and next_refID replaced by their mapped values (-1 stays -1),
+ * and there a next_refID outside [-1, n_ref of that file) is SVX_E_ARG, as a refID outside it always is.  The order is that of svx_bam_sort_host over the
+ * translated records, stable over the record numbers of the concatenation of the files.  The device does not merge yet: see DESIGN section 35. */
+/* host-only: the merged header (magic .. merged reference dictionary) of k headers, in the order given, by the rule of svim_amd/bammerge.py.  tid_maps_out (may
+ * be NULL): the maps back to back, the sum of the files' n_ref entries.  *n_out is the size also when cap is too small (SVX_E_CAPACITY).  SVX_E_ARG: a header
+ * that cannot be walked, a name twice in one dictionary, one name with two lengths, two @RG lines with one ID and different bytes. */
+int  svx_bam_merge_header_host(const uint8_t* const* headers, const int64_t* sizes, int64_t k, uint8_t* out, int64_t cap, int64_t* n_out, int32_t* tid_maps_out);
+/* host-only: the merged record stream of k record streams (file order; n_ref[f] references each, tid_maps: the maps back to back) and the permutation over the
+ * record numbers of their concatenation.  out (may be NULL) takes the sum of the sizes; perm, perm_cap, *n_records and the refusals as svx_bam_sort_host, and
+ * SVX_E_ARG for a mate id outside a translated file's dictionary or a map entry outside [0, n_ref_merged). */
+int  svx_bam_merge_host(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, uint8_t* out,
+                        uint32_t* perm, int64_t perm_cap, int64_t* n_records);
+
 /* ---- SAM text through the device reader (sam.hip, sam_core.hpp; the definition in words: svim_amd/sam.py) ----
  * svx_sam_open gives the handle type of svx_bam_open for a file of uncompressed SAM text (what an aligner writes): the header is parsed on the host
  * (svx_bam_header answers as for a BAM, sort_order from @HD), the alignment lines are turned into the BAM record stream on the device, slice by slice, and

@@ -39,6 +39,7 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_bam_sort_begin", "svx_bam_sort_finish", "svx_bam_sort_abort", "svx_bam_sort_count", "svx_bam_sort_encode", "svx_bam_sort_fetch", "svx_bam_sort_index",
            "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host", "svx_bam_sort_begin_spill", "svx_bam_sort_get_spill_stats",
            "svx_bam_sort_spill_host",
+           "svx_bam_merge_header_host", "svx_bam_merge_host",
            "svx_sam_open", "svx_sam_get_stats", "svx_sam_convert_host", "svx_sam_header_host"]
 
 
@@ -294,6 +295,66 @@ def bam_sort_header_host(header):
     if rc != 0:
         raise SvxError("svx_bam_sort_header_host failed: %s" % _abi.ERRORS.get(rc, rc))
     return out[:n.value].tobytes()
+
+
+def bam_merge_header_host(headers):
+    """svx_bam_merge_header_host (host-only): the header of the merged file of the files whose headers (magic .. dictionary) are given, in that order, and the
+    maps of their reference ids into the merged dictionary -> (header bytes, [map per file]), as svim_amd.bammerge.merged_header and tid_maps define them.
+    svim_amd.bammerge.BamMergeError (code E_ARG) for what the definition refuses."""
+    from . import bammerge
+    headers = [bytes(h) for h in headers]
+    k = len(headers)
+    if k < 1:
+        raise bammerge.BamMergeError(_abi.SVX_E_ARG, "bam_merge_header_host: no input")
+    bufs = [np.frombuffer(h, dtype=np.uint8) if h else np.zeros(1, np.uint8) for h in headers]
+    ptrs = (C.c_void_p * k)(*[b.ctypes.data for b in bufs])
+    sizes = np.array([len(h) for h in headers], dtype=np.int64)
+    n_refs = []
+    for h in headers:       # (the count sits behind the text; a header too short to hold one is the library's to refuse)
+        l_text = int.from_bytes(h[4:8], "little", signed=True) if len(h) >= 12 else -1
+        n_refs.append(min(len(h) // 8, int.from_bytes(h[8 + l_text:12 + l_text], "little", signed=True)) if 0 <= l_text <= len(h) - 12 else 0)
+    maps = np.zeros(max(1, sum(max(0, n) for n in n_refs)), dtype=np.int32)
+    n, cap = C.c_int64(), 0
+    for _ in range(2):
+        out = np.zeros(max(1, cap), dtype=np.uint8)
+        rc = lib().svx_bam_merge_header_host(ptrs, ptr(sizes), C.c_int64(k), ptr(out), C.c_int64(cap), C.byref(n), ptr(maps))
+        if rc != _abi.SVX_E_CAPACITY:
+            break
+        cap = n.value
+    if rc == _abi.SVX_E_ARG:
+        raise bammerge.BamMergeError(rc, "bam_merge_header_host: " + _abi.ERRORS[rc])
+    if rc != 0:
+        raise SvxError("svx_bam_merge_header_host failed: %s" % _abi.ERRORS.get(rc, rc))
+    out_maps, at = [], 0
+    for nr in n_refs:
+        out_maps.append([int(x) for x in maps[at:at + nr]])
+        at += nr
+    return out[:n.value].tobytes(), out_maps
+
+
+def bam_merge_host(files, n_ref_merged):
+    """svx_bam_merge_host (host-only): files: per input (record stream in file order, n_ref, tid_map) -> (the merged record stream, the permutation over global
+    record numbers as a uint32 array), what svim_amd.bammerge.merge gives.  svim_amd.bammerge.BamMergeError (code E_ARG / E_RANGE) for what it refuses."""
+    from . import bammerge
+    files = [(bytes(s), int(nr), [int(t) for t in m]) for s, nr, m in files]
+    k = len(files)
+    if k < 1 or any(len(m) != nr for _, nr, m in files):
+        raise bammerge.BamMergeError(_abi.SVX_E_ARG, "bam_merge_host: no input, or a map that has not one entry per reference of its file")
+    bufs = [np.frombuffer(s, dtype=np.uint8) if s else np.zeros(1, np.uint8) for s, _, _ in files]
+    ptrs = (C.c_void_p * k)(*[b.ctypes.data for b in bufs])
+    sizes = np.array([len(s) for s, _, _ in files], dtype=np.int64)
+    n_refs = np.array([nr for _, nr, _ in files], dtype=np.int32)
+    maps = np.array([t for _, _, m in files for t in m] or [0], dtype=np.int32)
+    total = int(sizes.sum())
+    out = np.zeros(max(1, total), dtype=np.uint8)
+    cap = total // 36 + 1
+    perm, n = np.zeros(cap, dtype=np.uint32), C.c_int64()
+    rc = lib().svx_bam_merge_host(ptrs, ptr(sizes), ptr(n_refs), C.c_int64(k), C.c_int32(int(n_ref_merged)), ptr(maps), ptr(out), ptr(perm), C.c_int64(cap), C.byref(n))
+    if rc in (_abi.SVX_E_ARG, _abi.SVX_E_RANGE):
+        raise bammerge.BamMergeError(rc, "bam_merge_host: " + _abi.ERRORS[rc])
+    if rc != 0:
+        raise SvxError("svx_bam_merge_host failed: %s" % _abi.ERRORS.get(rc, rc))
+    return out[:total].tobytes(), perm[:n.value].copy()
 
 
 def sam_convert_host(text, references, cap=None):

@@ -11,7 +11,9 @@
 
 #define BSORT_BLOCK 65280                    /* stream bytes per BGZF block of the output (deflate_core.hpp: DEF_BLOCK) */
 #define BSORT_MIN_BLOCK_SIZE 32u             /* the fixed fields of a record behind its block_size field */
-enum { BSORT_BAD_SIZE = 1, BSORT_BAD_TID = 2, BSORT_BAD_POS = 4 };
+enum { BSORT_BAD_SIZE = 1, BSORT_BAD_TID = 2, BSORT_BAD_POS = 4, BSORT_BAD_MATE = 8 };
+#define BSORT_REFID_AT 4u                    /* refID and next_refID of a record, counted from its block_size field (body offsets 0 and 20) */
+#define BSORT_MATE_AT 24u
 
 // what is wrong with a record (0: nothing)
 BSORT_FN int bsort_check(int32_t tid, int32_t pos, uint32_t block_size, int32_t n_ref) {
@@ -48,5 +50,15 @@ BSORT_FN int64_t bsort_run_of(const int64_t* run_base, int64_t n_runs, int64_t q
     while (b - a > 1) { const int64_t m = a + ((b - a) >> 1); if (run_base[m] <= q) a = m; else b = m; }
     return a;
 }
-// the status of a stream whose records showed the union `bad` of bsort_check: SVX_E_ARG (-3) before SVX_E_RANGE (-10)
-BSORT_FN int bsort_status(int bad) { return (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID)) ? -3 : (bad & BSORT_BAD_POS) ? -10 : 0; }
+// the status of a stream whose records showed the union `bad` of bsort_check and bsort_translate: SVX_E_ARG (-3) before SVX_E_RANGE (-10)
+BSORT_FN int bsort_status(int bad) { return (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID | BSORT_BAD_MATE)) ? -3 : (bad & BSORT_BAD_POS) ? -10 : 0; }
+// ---- the merge of several files (svim_amd/bammerge.py): the ids of a record of a file whose dictionary is not the merged one ----
+// (used by svx_bam_merge_host today; written for host and device alike, as everything in this file is)
+// map[i]: the merged id of the file's reference i (n_ref_file entries).  -1 stays -1.  A refID outside [-1, n_ref_file) is BSORT_BAD_TID, a next_refID outside
+// it BSORT_BAD_MATE; such an id is handed on as -1, so that nothing behind this function indexes with it.  Returns the union of what is wrong (0: nothing)
+BSORT_FN int bsort_translate(int32_t tid, int32_t mate, const int32_t* map, int32_t n_ref_file, int32_t* tid_out, int32_t* mate_out) {
+    const bool bad_tid = tid < -1 || tid >= n_ref_file, bad_mate = mate < -1 || mate >= n_ref_file;
+    *tid_out = bad_tid || tid < 0 ? -1 : map[tid];
+    *mate_out = bad_mate || mate < 0 ? -1 : map[mate];
+    return (bad_tid ? BSORT_BAD_TID : 0) | (bad_mate ? BSORT_BAD_MATE : 0);
+}

@@ -1,6 +1,7 @@
 // bamsort_host.cpp - svx_bam_sort_host and svx_bam_sort_header_host: the coordinate sort of a record stream and the header of the sorted file by the rule of
 // bamsort_core.hpp and svim_amd/bamsort.py, built for the host; no GPU involved.  The kernels of bamsort.hip write the same bytes and the same permutation:
 // there the keys go through the radix sort and the records through a gather, here through std::stable_sort and memcpy.
+// svx_bam_merge_header_host and svx_bam_merge_host: the same for several files merged into one (svim_amd/bammerge.py; bsort_translate).
 #include "bamsort_core.hpp"
 #include "../../include/svx.h"
 #include <algorithm>
@@ -178,5 +179,215 @@ extern "C" int svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, 
     wr32(out + 4, (uint32_t)text.size());
     memcpy(out + 8, text.data(), text.size());
     memcpy(out + 8 + text.size(), header + 8 + l_text, (size_t)rest);
+    return SVX_OK;
+}
+
+// ---- the merge of several files (svim_amd/bammerge.py) ------------------------------------------------------------------------------------------------------
+namespace {
+struct MergeHeader { std::string text; std::vector<std::string> names; std::vector<int32_t> lens; };
+// header bytes (magic .. dictionary) -> the text up to its first NUL and the dictionary; false: it cannot be walked
+bool merge_parse(const uint8_t* h, int64_t n, MergeHeader* o) {
+    if (!h || n < 12 || memcmp(h, "BAM\1", 4) != 0) return false;
+    const int64_t l_text = (int32_t)rd32(h + 4);
+    if (l_text < 0 || l_text > n - 12) return false;
+    o->text.assign((const char*)h + 8, (size_t)l_text);
+    const size_t nul = o->text.find('\0');
+    if (nul != std::string::npos) o->text.resize(nul);
+    int64_t p = 8 + l_text;
+    const int64_t n_ref = (int32_t)rd32(h + p);
+    p += 4;
+    if (n_ref < 0) return false;
+    for (int64_t i = 0; i < n_ref; i++) {
+        if (n - p < 8) return false;
+        const int64_t l_name = (int32_t)rd32(h + p);
+        if (l_name < 0 || l_name > n - p - 8) return false;
+        std::string name((const char*)h + p + 4, (size_t)l_name);
+        const size_t z = name.find('\0');
+        if (z != std::string::npos) name.resize(z);
+        o->names.push_back(name); o->lens.push_back((int32_t)rd32(h + p + 4 + l_name));
+        p += 8 + l_name;
+    }
+    return true;
+}
+std::vector<std::string> merge_split(const std::string& s, char sep, bool keep_empty) {
+    std::vector<std::string> out;
+    for (size_t a = 0; a <= s.size();) {
+        size_t b = s.find(sep, a);
+        if (b == std::string::npos) b = s.size();
+        if (keep_empty || b > a) out.push_back(s.substr(a, b - a));
+        a = b + 1;
+    }
+    return out;
+}
+bool merge_starts(const std::string& s, const char* t) { return s.compare(0, strlen(t), t) == 0; }
+// the value of the first field behind the record type that starts with tag; false: none
+bool merge_field(const std::string& line, const char* tag, std::string* v) {
+    const std::vector<std::string> f = merge_split(line, '\t', true);
+    for (size_t i = 1; i < f.size(); i++) if (merge_starts(f[i], tag)) { *v = f[i].substr(strlen(tag)); return true; }
+    return false;
+}
+std::string merge_join(const std::vector<std::string>& f) {
+    std::string s;
+    for (size_t i = 0; i < f.size(); i++) { if (i) s += '\t'; s += f[i]; }
+    return s;
+}
+bool merge_has(const std::vector<std::string>& v, const std::string& s) { return std::find(v.begin(), v.end(), s) != v.end(); }
+}  // namespace
+
+extern "C" int svx_bam_merge_header_host(const uint8_t* const* headers, const int64_t* sizes, int64_t k, uint8_t* out, int64_t cap, int64_t* n_out, int32_t* tid_maps_out) {
+    if (!headers || !sizes || k < 1 || cap < 0 || (cap && !out) || !n_out) return SVX_E_ARG;
+    *n_out = 0;
+    std::vector<MergeHeader> H((size_t)k);
+    for (int64_t f = 0; f < k; f++) if (!merge_parse(headers[f], sizes[f], &H[(size_t)f])) return SVX_E_ARG;
+    if (k == 1) {                                                                // the merge of one file is the sort of that file
+        if (tid_maps_out) for (size_t i = 0; i < H[0].names.size(); i++) tid_maps_out[i] = (int32_t)i;
+        return svx_bam_sort_header_host(headers[0], sizes[0], out, cap, n_out);
+    }
+    // the dictionary: the first file's, then the names not yet present; the maps
+    std::vector<std::string> names; std::vector<int32_t> lens;
+    size_t at = 0;
+    for (int64_t f = 0; f < k; f++) {
+        const MergeHeader& h = H[(size_t)f];
+        for (size_t i = 0; i < h.names.size(); i++) {
+            for (size_t j = 0; j < i; j++) if (h.names[j] == h.names[i]) return SVX_E_ARG;              // a name twice in one dictionary
+            const size_t m = (size_t)(std::find(names.begin(), names.end(), h.names[i]) - names.begin());
+            if (m == names.size()) { names.push_back(h.names[i]); lens.push_back(h.lens[i]); }
+            else if (lens[m] != h.lens[i]) return SVX_E_ARG;                                            // one name, two lengths
+            if (tid_maps_out) tid_maps_out[at] = (int32_t)m;
+            at++;
+        }
+    }
+    // the text: rule 1 to 5 of svim_amd/bammerge.py
+    std::vector<std::vector<std::string>> lines((size_t)k);
+    for (int64_t f = 0; f < k; f++) lines[(size_t)f] = merge_split(H[(size_t)f].text, '\n', false);
+    std::vector<std::string> made;
+    {
+        std::vector<uint8_t> fake(12 + H[0].text.size(), 0), sorted(12 + H[0].text.size() + 64, 0);
+        memcpy(fake.data(), "BAM\1", 4); wr32(fake.data() + 4, (uint32_t)H[0].text.size());
+        if (!H[0].text.empty()) memcpy(fake.data() + 8, H[0].text.data(), H[0].text.size());
+        int64_t n = 0;
+        if (svx_bam_sort_header_host(fake.data(), (int64_t)fake.size(), sorted.data(), (int64_t)sorted.size(), &n) != SVX_OK) return SVX_E_ARG;
+        const std::string text((const char*)sorted.data() + 8, (size_t)rd32(sorted.data() + 4));
+        made.push_back(text.substr(0, text.find('\n')));
+    }
+    bool any_sq = false;
+    for (const auto& ls : lines) for (const auto& ln : ls) any_sq = any_sq || merge_starts(ln, "@SQ\t");
+    if (any_sq)
+        for (size_t r = 0; r < names.size(); r++) {
+            const std::string want = "SN:" + names[r];
+            const std::string* hit = nullptr;
+            for (size_t f = 0; f < lines.size() && !hit; f++)
+                for (const auto& ln : lines[f]) {
+                    if (!merge_starts(ln, "@SQ\t")) continue;
+                    const std::vector<std::string> fl = merge_split(ln, '\t', true);
+                    if (std::find(fl.begin() + 1, fl.end(), want) != fl.end()) { hit = &ln; break; }
+                }
+            made.push_back(hit ? *hit : "@SQ\tSN:" + names[r] + "\tLN:" + std::to_string(lens[r]));
+        }
+    std::vector<std::string> rg_ids, pg_ids;
+    for (int64_t f = 0; f < k; f++) {
+        std::vector<std::pair<std::string, std::string>> renamed;
+        const std::string suffix = "-" + std::to_string(f);
+        for (size_t j = 0; j < lines[(size_t)f].size(); j++) {
+            std::string ln = lines[(size_t)f][j];
+            if ((j == 0 && merge_starts(H[(size_t)f].text, "@HD\t")) || merge_starts(ln, "@SQ\t")) continue;
+            const bool pg = merge_starts(ln, "@PG\t");
+            if (pg && !renamed.empty()) {                                        // PP: follows the renames of this file so far
+                std::vector<std::string> fl = merge_split(ln, '\t', true);
+                for (auto& x : fl)
+                    if (merge_starts(x, "PP:")) for (const auto& rn : renamed) if (x.compare(3, std::string::npos, rn.first) == 0) { x = "PP:" + rn.second; break; }
+                ln = merge_join(fl);
+            }
+            if (merge_has(made, ln)) continue;
+            std::string id;
+            if (merge_starts(ln, "@RG\t")) {
+                if (merge_field(ln, "ID:", &id)) { if (merge_has(rg_ids, id)) return SVX_E_ARG; rg_ids.push_back(id); }      // read groups are not renamed (RG:Z tags: out of scope)
+            } else if (pg && merge_field(ln, "ID:", &id)) {
+                if (f >= 1 && merge_has(pg_ids, id)) {
+                    std::string nid = id + suffix;
+                    while (merge_has(pg_ids, nid)) nid += suffix;
+                    bool found = false;
+                    for (auto& rn : renamed) if (rn.first == id) { rn.second = nid; found = true; }
+                    if (!found) renamed.push_back({id, nid});
+                    std::vector<std::string> fl = merge_split(ln, '\t', true);
+                    for (size_t i = 1; i < fl.size(); i++) if (merge_starts(fl[i], "ID:")) { fl[i] = "ID:" + nid; break; }
+                    ln = merge_join(fl); id = nid;
+                }
+                pg_ids.push_back(id);
+            }
+            made.push_back(ln);
+        }
+    }
+    std::string text;
+    for (const auto& ln : made) { text += ln; text += '\n'; }
+    int64_t total = 12 + (int64_t)text.size();
+    for (const auto& nm : names) total += 9 + (int64_t)nm.size();
+    *n_out = total;
+    if (total > cap) return SVX_E_CAPACITY;
+    uint8_t* p = out;
+    memcpy(p, "BAM\1", 4); wr32(p + 4, (uint32_t)text.size()); memcpy(p + 8, text.data(), text.size());
+    p += 8 + text.size();
+    wr32(p, (uint32_t)names.size()); p += 4;
+    for (size_t r = 0; r < names.size(); r++) {
+        wr32(p, (uint32_t)names[r].size() + 1); memcpy(p + 4, names[r].c_str(), names[r].size() + 1);
+        wr32(p + 5 + names[r].size(), (uint32_t)lens[r]);
+        p += 9 + names[r].size();
+    }
+    return SVX_OK;
+}
+
+extern "C" int svx_bam_merge_host(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, uint8_t* out,
+                                  uint32_t* perm, int64_t perm_cap, int64_t* n_records) {
+    if (!streams || !sizes || !n_ref || k < 1 || n_ref_merged < 0 || perm_cap < 0 || !n_records) return SVX_E_ARG;
+    *n_records = 0;
+    struct Row { uint64_t key; int64_t at; uint32_t len; };
+    std::vector<Row> rows;
+    std::vector<uint8_t> all;                                                    // the concatenation of the inputs, translated
+    int bad = 0;
+    const int32_t* map = tid_maps;
+    for (int64_t f = 0; f < k; f++) {
+        const int64_t n_bytes = sizes[f];
+        const uint8_t* records = streams[f];
+        if (n_bytes < 0 || n_ref[f] < 0 || (n_bytes && !records) || (n_ref[f] && !map)) return SVX_E_ARG;
+        bool identity = true;
+        for (int32_t i = 0; i < n_ref[f]; i++) {
+            if (map[i] < 0 || map[i] >= n_ref_merged) return SVX_E_ARG;
+            identity = identity && map[i] == i;
+        }
+        const int64_t base = (int64_t)all.size();
+        if (n_bytes) all.insert(all.end(), records, records + n_bytes);
+        for (int64_t p = 0; p < n_bytes;) {
+            if (n_bytes - p < 4) return SVX_E_ARG;
+            const uint32_t bs = rd32(records + p);
+            if (bs < BSORT_MIN_BLOCK_SIZE || (int64_t)bs > n_bytes - p - 4) return SVX_E_ARG;
+            int32_t tid = (int32_t)rd32(records + p + BSORT_REFID_AT);
+            const int32_t pos = (int32_t)rd32(records + p + 8);
+            const uint32_t flag = rd32(records + p + 16) >> 16;
+            if (!identity) {                                                     // the ids of this file's records go through its map, in the copy
+                int32_t t, m;
+                bad |= bsort_translate(tid, (int32_t)rd32(records + p + BSORT_MATE_AT), map, n_ref[f], &t, &m);
+                wr32(all.data() + base + p + BSORT_REFID_AT, (uint32_t)t); wr32(all.data() + base + p + BSORT_MATE_AT, (uint32_t)m);
+                tid = t;
+            }
+            bad |= bsort_check(tid, pos, bs, identity ? n_ref[f] : n_ref_merged);
+            rows.push_back(Row{bsort_key(tid, pos, flag, n_ref_merged), base + p, 4u + bs});
+            p += 4 + (int64_t)bs;
+        }
+        map += n_ref[f];
+    }
+    if (bad) return bsort_status(bad);
+    if (rows.size() > 0xffffffffull) return SVX_E_CAPACITY;
+    *n_records = (int64_t)rows.size();
+    if (perm && (int64_t)rows.size() > perm_cap) return SVX_E_CAPACITY;
+    std::vector<uint32_t> order(rows.size());
+    for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].key < rows[b].key; });
+    int64_t at = 0;
+    for (size_t i = 0; i < order.size(); i++) {
+        const Row& r = rows[order[i]];
+        if (out) memcpy(out + at, all.data() + r.at, r.len);
+        if (perm) perm[i] = order[i];
+        at += r.len;
+    }
     return SVX_OK;
 }
