@@ -1129,6 +1129,8 @@ __device__ __forceinline__ void d_edit_lane(long long blk, long long count, cons
     if (live) ed[slot_of ? slot_of[widx] : (long long)widx] = score;
 }
 
+// option of a full-matrix launch (FusedTab::opt): d_edit_wide runs a trip whose eight columns lie inside the text of every pair of the wave without the per-column range test
+#define FULLS_WIDE_PLAIN 1
 // ---- 3c. full matrix, G lanes per pair, 32 Q rows (Q = 16 or 12 words) per lane ------------------------------------------------
 // The column is ONE wide bit-vector spread over the first L = ceil(m / (32 Q)) lanes of a group, bottom-aligned like above (row m is
 // bit 31 of lane L-1's last word); lane g of a group works on text column t-g at step t and hands (symbol, adder carry,
@@ -1136,7 +1138,7 @@ __device__ __forceinline__ void d_edit_lane(long long blk, long long count, cons
 // state, so the per-step overhead is amortised over 512 cells (the 1-block-per-lane systolic kernel pays it per 32 cells).
 template <int G, int Q, int P>
 __device__ __forceinline__ void d_edit_wide(long long blk, long long count, const uint32_t* list, const uint32_t* scratch, const PairDesc* desc,
-                                            const long long* slot_of, int32_t* ed, unsigned long long* wc) {
+                                            const long long* slot_of, int32_t* ed, unsigned long long* wc, const int opt) {
     constexpr int RL = 32 * Q;                               // rows per lane
     const int lane = lane_id();
     const int gl = lane & (G - 1);
@@ -1166,6 +1168,8 @@ __device__ __forceinline__ void d_edit_wide(long long blk, long long count, cons
     int steps = live ? n + lanes_used - 1 : 0, smax = steps;
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { const int v = __shfl_xor(smax, o, 64); smax = v > smax ? v : smax; }
+    smax = __builtin_amdgcn_readfirstlane(smax);             // a scalar: the hand-off masks live across the trip loops, and behind a loop whose exit the compiler takes
+                                                             // for lane-dependent they would be kept per lane, in VGPR pairs
     const int txt_words = (n + 7) >> 3;
     const bool mine = live && gl < lanes_used;               // this lane holds pattern rows
     const unsigned n_on = mine ? (unsigned)n : 0u;           // columns this lane works on (none: a lane beyond the pattern)
@@ -1183,12 +1187,34 @@ __device__ __forceinline__ void d_edit_wide(long long blk, long long count, cons
     uint32_t o_ph = 0u, o_mh = 0u;                           // a lane's last ph / mh words (bit 31 = the bits it hands down)
     unsigned o_cy = 0u;
     int col = -gl;                                           // text column of this lane at the current step
-    for (int jb = 0; jb * 8 < smax; jb++) {
-        uint32_t tpb[P], tp[P];
+    // the (inverted) plane bits of trip jb: bit k = the symbol of sub-step k
+    auto trip_text = [&](const int jb, uint32_t (&tp)[P]) {
+        uint32_t tpb[P];
         planes8<P>(tw_next, tpb);
         tw_next = text_word(jb + 2 - wo);
 #pragma unroll
         for (int b = 0; b < P; b++) { tp[b] = ~((tpa[b] | (tpb[b] << 8)) >> r8); tpa[b] = tpb[b]; }
+    };
+    // A trip is PLAIN when every lane that holds pattern rows has all eight of its columns inside its text: no range test per column and no divergent branch, so
+    // the update's results need not leave it through VGPR copies - the score takes the lane's own pushed-out bits as the carries the chains end on, and the masks
+    // are balloted from the update's own last words.  A lane without pattern rows (beyond the pattern, or in a group beyond `count`) runs the update on its dummy
+    // state there: its masks reach only lanes of its own kind or a FIRST lane, which overrides them, and nothing reads its score.  The pairs of a class are sorted by
+    // descending text length, so the predicated form serves the first ceil(G / 8) trips of a wave (a lane starts at column -gl) and the trips behind its shortest text.
+    // Which trips those are is known before the first one (a lane's column at the start of trip jb is 8 jb - gl): trips [t_lo, t_hi) of a lane, the latest t_lo and
+    // the earliest t_hi of the wave's lanes with pattern rows.  Scalars, so that the three loops below are counted loops with nothing to decide per trip.
+    int t_lo = mine ? (gl + 7) >> 3 : 0, t_hi = mine ? (n + gl >= 8 ? ((n + gl - 8) >> 3) + 1 : 0) : 0x7fffffff;
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        const int lo = __shfl_xor(t_lo, o, 64), hi = __shfl_xor(t_hi, o, 64);
+        t_lo = lo > t_lo ? lo : t_lo; t_hi = hi < t_hi ? hi : t_hi;
+    }
+    const int trips = (smax + 7) >> 3;
+    t_lo = __builtin_amdgcn_readfirstlane(t_lo); t_hi = __builtin_amdgcn_readfirstlane(t_hi);
+    const int plain_from = t_lo < trips ? t_lo : trips;
+    const int plain_to = ((opt & FULLS_WIDE_PLAIN) && t_hi > plain_from) ? (t_hi < trips ? t_hi : trips) : plain_from;
+    auto pred_trip = [&](const int jb) {
+        uint32_t tp[P];
+        trip_text(jb, tp);
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             uint32_t nk[P];
@@ -1206,7 +1232,32 @@ __device__ __forceinline__ void d_edit_wide(long long blk, long long count, cons
             m_ph = __builtin_amdgcn_ballot_w64((int)o_ph < 0); m_mh = __builtin_amdgcn_ballot_w64((int)o_mh < 0); m_cy = __builtin_amdgcn_ballot_w64(o_cy != 0u);
             col += 1;
         }
+    };
+    // one loop per form, one behind the other (not a branch inside one loop: DESIGN section 3, round 4): the predicated prologue, the plain trips, the predicated rest
+    int jb = 0;
+    for (; jb < plain_from; jb++) pred_trip(jb);
+    for (; jb < plain_to; jb++) {
+        uint32_t tp[P];
+        trip_text(jb, tp);
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            uint32_t nk[P];
+#pragma unroll
+            for (int b = 0; b < P; b++) nk[b] = (uint32_t)__builtin_amdgcn_sbfe((int)tp[b], k, 1);
+            unsigned cyp = __builtin_amdgcn_inverse_ballot_w64((m_ph << 1) | FIRST), cym = __builtin_amdgcn_inverse_ballot_w64((m_mh << 1) & ~FIRST);
+            unsigned carry = __builtin_amdgcn_inverse_ballot_w64((m_cy << 1) & ~FIRST);
+            uint32_t ph_last, mh_last;
+            MYERS_COLUMN_C(Q, P, 0, pl, pv, mv, nk, carry, cyp, cym, ph_last, mh_last)
+            score += (int)cyp - (int)cym;                     // the lane's own pushed-out bits, as carries: v_addc_co + v_subbrev_co
+            // (a ballot of a carry is lowered through a VGPR - v_cndmask + v_cmp; bit 31 of the last ph / mh word is the same bit for one v_cmp)
+            m_ph = __builtin_amdgcn_ballot_w64((int)ph_last < 0); m_mh = __builtin_amdgcn_ballot_w64((int)mh_last < 0); m_cy = __builtin_amdgcn_ballot_w64(carry != 0u);
+        }
+        col += 8;
     }
+    // back to the predicated form: a lane's last outputs stand in its own words again (the same bits when no trip ran plain)
+    o_ph = __builtin_amdgcn_inverse_ballot_w64(m_ph) ? 0x80000000u : 0u; o_mh = __builtin_amdgcn_inverse_ballot_w64(m_mh) ? 0x80000000u : 0u;
+    o_cy = __builtin_amdgcn_inverse_ballot_w64(m_cy) ? 1u : 0u;
+    for (; jb < trips; jb++) pred_trip(jb);
     wc_account(wc, (long long)smax * Q * 64, (live && gl == 0) ? (long long)n * ((m + 31) >> 5) : 0);
     if (live && is_last) ed[slot_of ? slot_of[widx] : (long long)widx] = score;
 }
@@ -1398,7 +1449,7 @@ __device__ __forceinline__ void d_edit_full(long long blk, long long count, cons
 #define KIND_RETRY 40
 struct FusedTab {
     int n;
-    int narrow;                            // band launches: the staircase windows narrow as they run (d_edit_stair)
+    int opt;                               // band launches: 1 = the staircase windows narrow as they run (d_edit_stair); full-matrix launches: FULLS_WIDE_PLAIN or 0
     int kind[SEG_MAX];                     // class id, or KIND_LL + words for a low-latency form
     unsigned first_block[SEG_MAX + 1];
     long long lo[SEG_MAX], cn[SEG_MAX];    // range of the class in the sorted list
@@ -1414,7 +1465,7 @@ __global__ __launch_bounds__(256) void k_edit_bands(FusedTab tab, const uint32_t
     const uint32_t* l = list + tab.lo[s];
     switch (tab.kind[s]) {
         case 0: d_edit_band<1, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, fail_cnt, fail_lists, fail_cap, wc); break;
-                                                default: d_edit_stair<P, QM>(band_words(tab.kind[s]), tab.narrow != 0, blk, tab.cn[s], l, scratch, desc, slot_of, ed, fail_cnt, fail_lists, fail_cap, wc); break;
+                                                default: d_edit_stair<P, QM>(band_words(tab.kind[s]), tab.opt != 0, blk, tab.cn[s], l, scratch, desc, slot_of, ed, fail_cnt, fail_lists, fail_cap, wc); break;
     }
 }
 
@@ -1438,26 +1489,26 @@ __global__ __launch_bounds__(256) void k_edit_fulls(FusedTab tab, const uint32_t
         case CLS_LANE0 + 2: d_edit_lane<4, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
         case CLS_LANE0 + 3: d_edit_lane<8, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
         case CLS_LANE0 + 4: d_edit_lane<16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE0: d_edit_wide<2, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE0 + 1: d_edit_wide<4, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE0 + 2: d_edit_wide<8, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE0 + 3: d_edit_wide<16, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE12: d_edit_wide<2, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE12 + 1: d_edit_wide<4, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE12 + 2: d_edit_wide<8, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE12 + 3: d_edit_wide<16, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE14: d_edit_wide<2, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE14 + 1: d_edit_wide<4, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE14 + 2: d_edit_wide<8, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE14 + 3: d_edit_wide<16, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE10: d_edit_wide<2, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE10 + 1: d_edit_wide<4, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE10 + 2: d_edit_wide<8, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case CLS_WIDE10 + 3: d_edit_wide<16, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
+        case CLS_WIDE0: d_edit_wide<2, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE0 + 1: d_edit_wide<4, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE0 + 2: d_edit_wide<8, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE0 + 3: d_edit_wide<16, 16, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE12: d_edit_wide<2, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE12 + 1: d_edit_wide<4, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE12 + 2: d_edit_wide<8, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE12 + 3: d_edit_wide<16, 12, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE14: d_edit_wide<2, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE14 + 1: d_edit_wide<4, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE14 + 2: d_edit_wide<8, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE14 + 3: d_edit_wide<16, 14, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE10: d_edit_wide<2, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE10 + 1: d_edit_wide<4, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE10 + 2: d_edit_wide<8, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case CLS_WIDE10 + 3: d_edit_wide<16, 10, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
         // low-latency forms of the long classes (KIND_LL + words per lane): one pair per wave, 64 lanes x 2 / 3 / 4 words
-        case KIND_LL + 2: d_edit_wide<64, 2, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        case KIND_LL + 3: d_edit_wide<64, 3, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
-        default: d_edit_wide<64, 4, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc); break;
+        case KIND_LL + 2: d_edit_wide<64, 2, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        case KIND_LL + 3: d_edit_wide<64, 3, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
+        default: d_edit_wide<64, 4, P>(blk, tab.cn[s], l, scratch, desc, slot_of, ed, wc, tab.opt); break;
     }
 }
 
@@ -1570,6 +1621,7 @@ struct EditSwitches {
     int shift_bounds = 1;             // SVX_EDIT_SHIFT_BOUNDS=0: upper bounds from the left-justified alignment only (A/B switch)
     int prep_depth = PREP_DEPTH;      // SVX_EDIT_PREP_DEPTH=1|2|4|8: chunks per lane in the later trips of a bound pass (1 = rounds 1-6; A/B switch)
     int narrow_windows = 1;           // SVX_EDIT_NARROW=0: static staircase windows (A/B switch; results are the same either way)
+    int wide_plain = 1;               // SVX_EDIT_WIDE_PLAIN=0: every trip of the multi-lane full matrices tests the range of each column (A/B switch)
     long long few_pairs = 2048;       // SVX_EDIT_FEW_PAIRS: calls with at most this many pairs take the low-latency route (0 = never)
     // A retry round with only a few band pairs is bound by the LATENCY of its slowest pair: a band retry walks its columns in one lane with 6-16 state words
     // (configs[1], round 1: 196 pairs, one wave of 16-word windows = 0.31 ms at the very end of the window), a full matrix spread over the 64 lanes of a wave
@@ -1586,6 +1638,7 @@ static EditSwitches read_edit_switches() {
     if (const char* e = getenv("SVX_EDIT_SHIFT_BOUNDS")) sw.shift_bounds = atoi(e) == 0 ? 0 : 1;
     if (const char* e = getenv("SVX_EDIT_PREP_DEPTH")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) sw.prep_depth = v; }
     if (const char* e = getenv("SVX_EDIT_NARROW")) sw.narrow_windows = atoi(e) == 0 ? 0 : 1;
+    if (const char* e = getenv("SVX_EDIT_WIDE_PLAIN")) sw.wide_plain = atoi(e) == 0 ? 0 : 1;
     if (const char* e = getenv("SVX_EDIT_FEW_PAIRS")) sw.few_pairs = atoll(e);
     if (const char* e = getenv("SVX_EDIT_RETRY_FULL")) sw.retry_full = atoll(e);
     sw.no_early = getenv("SVX_EDIT_NO_EARLY") != nullptr;
@@ -1771,6 +1824,7 @@ static int launch_fulls(const EditCall& ec, int generic, const long long* lo, co
         nblk += (unsigned)((threads + EDIT_T - 1) / EDIT_T); tf.n++;
     }
     tf.first_block[tf.n] = nblk;
+    tf.opt = ec.sw.wide_plain ? FULLS_WIDE_PLAIN : 0;
     if (!tf.n) return SVX_OK;
     if (ec.sw.serial) HIPCHK(hipEventRecord(c->ev[6], fs));
     if (generic) k_edit_fulls<4><<<nblk, EDIT_T, 0, fs>>>(tf, lst, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, ec.cnt + 1, c->e_big_list.as<uint32_t>(), wc);
@@ -1798,6 +1852,7 @@ static int launch_bands_as_fulls(const EditCall& ec, int generic, const long lon
         nblk += (unsigned)((cn * 64 + EDIT_T - 1) / EDIT_T); tf.n++;
     }
     tf.first_block[tf.n] = nblk;
+    tf.opt = ec.sw.wide_plain ? FULLS_WIDE_PLAIN : 0;
     if (!tf.n) return SVX_OK;
     if (generic) k_edit_fulls<4><<<nblk, EDIT_T, 0, fs>>>(tf, lst, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, ec.cnt + 1, c->e_big_list.as<uint32_t>(), wc);
     else k_edit_fulls<2><<<nblk, EDIT_T, 0, fs>>>(tf, lst, ec.scratch, ec.desc, ec.slot_of, ec.ed_dev, ec.cnt + 1, c->e_big_list.as<uint32_t>(), wc);
@@ -1812,7 +1867,7 @@ static int launch_bands(const EditCall& ec, EditRound& r, int generic, bool spli
     const int base = GENERIC_BASE * generic;
     const bool early = split && part3 < 2;
     FusedTab tb; memset(&tb, 0, sizeof tb);
-    tb.narrow = ec.sw.narrow_windows;
+    tb.opt = ec.sw.narrow_windows;
     unsigned nblk = 0;
     for (int cls = NBAND - 1; cls >= 0; cls--) {                          // widest band first
         const long long cn = r.seg_cn[base + cls];
