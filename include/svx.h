@@ -814,7 +814,7 @@ int  svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* o
  * The merged dictionary is the first file's references, then file by file the names not yet present; tid_map[f][i] is the merged id of file f's reference i.
  * A record of a file whose map is the identity is copied verbatim; any other record gets refID and next_refID replaced by their mapped values (-1 stays -1),
  * and there a next_refID outside [-1, n_ref of that file) is SVX_E_ARG, as a refID outside it always is.  The order is that of svx_bam_sort_host over the
- * translated records, stable over the record numbers of the concatenation of the files.  The device does not merge yet: see DESIGN section 35. */
+ * translated records, stable over the record numbers of the concatenation of the files.  The device build is the session below. */
 /* host-only: the merged header (magic .. merged reference dictionary) of k headers, in the order given, by the rule of svim_amd/bammerge.py.  tid_maps_out (may
  * be NULL): the maps back to back, the sum of the files' n_ref entries.  *n_out is the size also when cap is too small (SVX_E_CAPACITY).  SVX_E_ARG: a header
  * that cannot be walked, a name twice in one dictionary, one name with two lengths, two @RG lines with one ID and different bytes. */
@@ -824,6 +824,46 @@ int  svx_bam_merge_header_host(const uint8_t* const* headers, const int64_t* siz
  * SVX_E_ARG for a mate id outside a translated file's dictionary or a map entry outside [0, n_ref_merged). */
 int  svx_bam_merge_host(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, uint8_t* out,
                         uint32_t* perm, int64_t perm_cap, int64_t* n_records);
+/* ---- the merge on the device: a session that readers only feed (bammerge.hip, bamsort.hip: k_bs_translate) ----
+ * A session is an object of its own.  It owns its sort, its HIP stream and its output index; a reader never owns any of it, and a reader's own sort
+ * (svx_bam_sort_*) and index are not touched by a merge.
+ * svx_bam_merge_open: readers are k >= 1 open handles (BAM, or SAM text) in file order.  They are used ONLY inside this call, to read their headers and
+ * dictionaries: the session keeps no pointer to any of them, and they may be closed as soon as it returns.  The merged header and the id maps are those of
+ * svx_bam_merge_header_host, and its refusals (one name with two lengths, a name twice in one file, @RG lines that clash) leave here with SVX_E_ARG before
+ * any device work.  max_bytes and spill_dir (may be NULL) mean what they mean to svx_bam_sort_begin and svx_bam_sort_begin_spill, over all files together.
+ * svx_bam_merge_add, k times, file i as the i-th call: h must satisfy the preconditions of svx_bam_sort_begin (device decode on, at its first record, no
+ * index pass, no sort pass, no region read and no contig limit of svx_bam_seek: SVX_E_STATE), decode on the session's device, and have the dictionary file i had at open (SVX_E_ARG).  The call
+ * drives the whole pass itself: it reads the file to its end, discards the batches, waits until the reader's loader is idle and only then returns; the appends
+ * run in the reader's loader thread but on the session's stream, so that no command on a reader's stream ever touches the session's memory.  A reader
+ * is attached for the length of this one call; afterwards it stands at the end of its file, rewinds, sorts on its own or is closed exactly as before.
+ * A file whose map is the identity is copied verbatim (a refID beyond its OWN dictionary is still refused); any other file's records get refID and
+ * next_refID translated in the session's copy.  SVX_E_CAPACITY / SVX_E_IO from the arena or the spill file, and any failed read: the session's sort is
+ * dropped and the session is broken - every later call but close is SVX_E_STATE - while the reader is usable after svx_bam_rewind.
+ * svx_bam_merge_finish after k adds (SVX_E_STATE before): the sort and the layout under the merged header; SVX_E_ARG / SVX_E_RANGE as svx_bam_sort_finish,
+ * and SVX_E_ARG for a next_refID outside the dictionary of a translated file.  count, encode, fetch, permutation, get_stats and get_spill_stats mean what
+ * they mean for svx_bam_sort_*; record numbers are places in the concatenation of the files.  svx_bam_merge_index_fmt builds the merged file's .bai or .csi
+ * into the session's own index, read by svx_bam_merge_index_count / svx_bam_merge_index_fetch.  svx_bam_merge_close at any point frees what the session
+ * owns and nothing else. */
+typedef struct svx_bam_merge svx_bam_merge;
+typedef struct svx_bam_merge_stats {
+    int64_t n_files, n_added, n_ref_merged, header_bytes, n_translated_files /* of those added */, n_translated_chunks, n_translated_records,
+            translate_bytes /* read and written by k_bs_translate */;
+    double  t_open_ms, t_add_ms /* the reading passes, over all files */, t_translate_ms /* k_bs_translate between events on the session's stream */;
+} svx_bam_merge_stats;
+int  svx_bam_merge_open(svx_bam* const* readers, int64_t k, int device, int64_t max_bytes, const char* spill_dir_or_null, svx_bam_merge** out);
+int  svx_bam_merge_add(svx_bam_merge* m, svx_bam* h);
+int  svx_bam_merge_finish(svx_bam_merge* m);
+int  svx_bam_merge_count(svx_bam_merge* m, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
+int  svx_bam_merge_encode(svx_bam_merge* m, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
+int  svx_bam_merge_fetch(svx_bam_merge* m, uint8_t* compressed_dst, uint8_t* stream_dst_or_null);
+int  svx_bam_merge_index_fmt(svx_bam_merge* m, int fmt);
+int  svx_bam_merge_index_count(svx_bam_merge* m, int64_t* n_bytes);
+int  svx_bam_merge_index_fetch(svx_bam_merge* m, uint8_t* host_dst);
+int  svx_bam_merge_permutation(svx_bam_merge* m, uint32_t* perm);
+int  svx_bam_merge_get_stats(svx_bam_merge* m, svx_bam_sort_stats* out);
+int  svx_bam_merge_get_spill_stats(svx_bam_merge* m, svx_bam_sort_spill_stats* out);
+int  svx_bam_merge_get_merge_stats(svx_bam_merge* m, svx_bam_merge_stats* out);
+void svx_bam_merge_close(svx_bam_merge* m);
 
 /* ---- SAM text through the device reader (sam.hip, sam_core.hpp; the definition in words: svim_amd/sam.py) ----
  * svx_sam_open gives the handle type of svx_bam_open for a file of uncompressed SAM text (what an aligner writes): the header is parsed on the host

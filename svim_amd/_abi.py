@@ -298,6 +298,16 @@ class BamSortSpillStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BamMergeStats(C.Structure):
+    """svx_bam_merge_stats: a merge session (svx_bam_merge_*): its files, the merged dictionary, what k_bs_translate did"""
+    _fields_ = [(n, C.c_int64) for n in ("n_files", "n_added", "n_ref_merged", "header_bytes", "n_translated_files", "n_translated_chunks", "n_translated_records",
+                                         "translate_bytes")] + \
+               [(n, C.c_double) for n in ("t_open_ms", "t_add_ms", "t_translate_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 SPILL_WRITE_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_uint8), C.c_int64)
 SPILL_READ_FN = C.CFUNCTYPE(C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_uint8), C.c_int64)
 

@@ -40,6 +40,9 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host", "svx_bam_sort_begin_spill", "svx_bam_sort_get_spill_stats",
            "svx_bam_sort_spill_host",
            "svx_bam_merge_header_host", "svx_bam_merge_host",
+           "svx_bam_merge_open", "svx_bam_merge_add", "svx_bam_merge_finish", "svx_bam_merge_count", "svx_bam_merge_encode", "svx_bam_merge_fetch", "svx_bam_merge_index_fmt",
+           "svx_bam_merge_index_count", "svx_bam_merge_index_fetch", "svx_bam_merge_permutation", "svx_bam_merge_get_stats", "svx_bam_merge_get_spill_stats",
+           "svx_bam_merge_get_merge_stats", "svx_bam_merge_close",
            "svx_sam_open", "svx_sam_get_stats", "svx_sam_convert_host", "svx_sam_header_host"]
 
 

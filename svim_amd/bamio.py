@@ -363,3 +363,111 @@ class NativeBam(object):
             self.close()
         except Exception:
             pass
+
+
+class BamMerge(object):
+    """A merge session on the device (svx_bam_merge_*; svim_amd/bammerge.py says what the merged file is): several files, in the order given, into one file in
+    coordinate order.  The session owns its sort, its stream and its index; readers only feed it.
+        m = BamMerge.open(readers, device=0)     # reads headers and dictionaries; keeps nothing of the readers, which may be closed at once
+        for r in readers: m.add(r)               # file by file, in the order of open: the call reads the whole file and returns when the reader is idle again
+        n_records, n_bytes, n_blocks = m.finish()
+        m.encode(first_block, n_blocks) ...; m.index("bai"); m.permutation(); m.stats(); m.close()
+    What the definition refuses - header clashes at open, records at finish - and the state rules are svim_amd.bammerge.BamMergeError with the library's status
+    in .code; an add that fails (SVX_E_CAPACITY, SVX_E_IO) breaks the session: close() is all that is left, the reader works again after rewind()."""
+
+    def __init__(self, handle, L):
+        self.h, self.L = handle, L
+
+    @classmethod
+    def open(cls, readers, device=0, max_bytes=0, spill_dir=None):
+        L = lib()
+        readers = list(readers)
+        if not readers:
+            raise ValueError("BamMerge.open: no reader")
+        arr = (C.c_void_p * len(readers))(*[r.h for r in readers])
+        h = C.c_void_p()
+        rc = L.svx_bam_merge_open(arr, C.c_int64(len(readers)), C.c_int(int(device)), C.c_int64(int(max_bytes)), None if spill_dir is None else os.fsencode(spill_dir), C.byref(h))
+        if rc != 0:
+            raise cls._error_of(L, rc, "svx_bam_merge_open")
+        return cls(h, L)
+
+    @staticmethod
+    def _error_of(L, rc, what):
+        from . import bammerge
+        return bammerge.BamMergeError(rc, "%s failed: %s (%s)" % (what, _abi.ERRORS.get(rc, rc), L.svx_last_error().decode("utf-8", "replace")))
+
+    def _call(self, what, *args):
+        if not self.h:
+            raise self._error_of(self.L, _abi.SVX_E_STATE, what + " on a closed session")
+        rc = getattr(self.L, what)(self.h, *args)
+        if rc != 0:
+            if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE) and what == "svx_bam_merge_index_fmt":
+                from . import bai
+                raise bai.BaiError(rc, "%s failed: %s (%s)" % (what, _abi.ERRORS.get(rc, rc), self.L.svx_last_error().decode("utf-8", "replace")))
+            raise self._error_of(self.L, rc, what)
+
+    def add(self, reader):
+        """the next file of the session: `reader` (a NativeBam with device decode on, at its first record) is read to its end inside this call"""
+        self._call("svx_bam_merge_add", reader.h)
+
+    def finish(self):
+        """-> (records, bytes of the merged stream, BGZF blocks of the merged file), once every file has been added"""
+        self._call("svx_bam_merge_finish")
+        return self.count()
+
+    def count(self):
+        n, nbytes, nb = C.c_int64(), C.c_int64(), C.c_int64()
+        self._call("svx_bam_merge_count", C.byref(n), C.byref(nbytes), C.byref(nb))
+        return n.value, nbytes.value, nb.value
+
+    def encode(self, first_block, n_blocks, stream=False):
+        """blocks [first_block, first_block + n_blocks) of the merged file -> their compressed bytes, or (compressed bytes, stream bytes) with stream=True;
+        ascending ranges without gaps when index() is to follow"""
+        n = C.c_int64()
+        self._call("svx_bam_merge_encode", C.c_int64(int(first_block)), C.c_int64(int(n_blocks)), C.byref(n))
+        out = np.zeros(max(1, n.value), dtype=np.uint8)
+        raw, nraw = None, 0
+        if stream:
+            total = self.count()[1]
+            nraw = min(total, (int(first_block) + int(n_blocks)) * _abi.TEXT_GZ_BLOCK) - min(total, int(first_block) * _abi.TEXT_GZ_BLOCK)
+            raw = np.zeros(max(1, nraw), dtype=np.uint8)
+        self._call("svx_bam_merge_fetch", out.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p) if stream else None)
+        return (out[:n.value].tobytes(), raw[:nraw].tobytes()) if stream else out[:n.value].tobytes()
+
+    def index(self, fmt="bai"):
+        """-> the bytes of the merged file's .bai, or with fmt="csi" the uncompressed bytes of its .csi, after every block has been encoded; svim_amd.bai.BaiError
+        (E_RANGE) when a record ends beyond 2^29 of a .bai"""
+        self._call("svx_bam_merge_index_fmt", C.c_int(_abi.index_format(fmt, "bai")))
+        n = C.c_int64()
+        self._call("svx_bam_merge_index_count", C.byref(n))
+        out = np.zeros(max(1, n.value), dtype=np.uint8)
+        self._call("svx_bam_merge_index_fetch", out.ctypes.data_as(C.c_void_p))
+        return out[:n.value].tobytes()
+
+    def permutation(self):
+        """uint32 array: for every record of the merged order its place in the concatenation of the files"""
+        n = self.count()[0]
+        perm = np.zeros(max(1, n), dtype=np.uint32)
+        self._call("svx_bam_merge_permutation", perm.ctypes.data_as(C.c_void_p))
+        return perm[:n]
+
+    def stats(self):
+        """the sort's stats (svx_bam_sort_stats), the spill's under "spill", the session's own under "merge" """
+        a, b, c = _abi.BamSortStats(), _abi.BamSortSpillStats(), _abi.BamMergeStats()
+        self._call("svx_bam_merge_get_stats", C.byref(a))
+        self._call("svx_bam_merge_get_spill_stats", C.byref(b))
+        self._call("svx_bam_merge_get_merge_stats", C.byref(c))
+        d = a.as_dict()
+        d["spill"], d["merge"] = b.as_dict(), c.as_dict()
+        return d
+
+    def close(self):
+        if self.h:
+            self.L.svx_bam_merge_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

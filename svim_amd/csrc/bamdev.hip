@@ -577,6 +577,9 @@ struct svx_devdec {
     BamIndex* index = nullptr; bool index_on = false;      // svx_bam_index_begin: the row table every load appends to (bamindex.hip)
     BamSort* sort = nullptr; bool sort_on = false;         // svx_bam_sort_begin: the arena and the rows every load appends to (bamsort.hip)
     SamDev* sam = nullptr;                                 // devdec_load_text: the scratch of the SAM text front end (sam.hip)
+    // svx_bam_merge_add: a merge session's sort, BORROWED for the length of that one call - never dropped, finished or destroyed from here - with the session's
+    // stream, on which the appends run, and the file's map into the merged dictionary (device memory of the session).  Null unless an add is running: the loads then test this pointer and nothing else
+    BamSort* feed = nullptr; hipStream_t feed_stream = nullptr; const int32_t* feed_map = nullptr; int32_t feed_n_ref = 0; bool feed_identity = true;
 };
 
 // slots of svx_devdec::h_cnt (pinned read-backs).  The loader thread (devdec_load / devdec_count) and the consumer (devdec_batch) use disjoint slots.
@@ -781,6 +784,14 @@ static int dd_decode(svx_devdec* d, DevChunk& c, uint64_t n_rec, bool final_chun
                               c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>()};
         const int rc = bamsort_append(d->sort, sc, st);
         if (rc != SVX_OK) { d->sort_on = false; bamsort_drop(d->sort); return rc; }      // (SVX_E_CAPACITY: the arena is full - the sort is given up, the handle rewinds)
+    }
+    if (d->feed && c.n_rec > 0) {
+        BamSortChunk sc{(long long)c.n_rec, sp, (uint64_t)c.data_begin, (uint64_t)c.tail_start, c.rec_off.as<uint64_t>(), c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(),
+                        c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>()};
+        sc.tid_map = d->feed_map; sc.n_ref_file = d->feed_n_ref; sc.identity = d->feed_identity;
+        HIPCHK(hipStreamSynchronize(st));                   // the chunk is complete: the session's stream reads it from here on, this decoder's no longer
+        const int rc = bamsort_append(d->feed, sc, d->feed_stream);      // (drains the session's stream before it returns: the chunk's arrays are free again)
+        if (rc != SVX_OK) { d->feed = nullptr; return rc; }      // (nothing more is appended; the session drops its sort once this loader is idle)
     }
     d->stats.records += c.n_rec;
     c.loaded = true;
@@ -1047,6 +1058,13 @@ int devdec_load_text(svx_devdec* d, int slot, const uint8_t* text, size_t n, boo
     return samdev_line_start(d->sam, c.n_rec, consumed, st);
 }
 void devdec_sam_stats(const svx_devdec* d, svx_sam_stats* out) { samdev_stats(d->sam, out); }
+
+void devdec_feed_set(svx_devdec* d, BamSort* sort, void* session_stream, const int32_t* dev_map, int32_t n_ref_file, bool identity) {
+    d->feed_stream = (hipStream_t)session_stream; d->feed_map = dev_map; d->feed_n_ref = n_ref_file; d->feed_identity = identity; d->feed = sort;
+}
+void devdec_feed_clear(svx_devdec* d) { d->feed = nullptr; d->feed_map = nullptr; }
+bool devdec_feed_on(const svx_devdec* d) { return d->feed != nullptr; }
+int devdec_device(const svx_devdec* d) { return d->device; }
 
 int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir) {
     HIPCHK(hipSetDevice(d->device));

@@ -669,6 +669,7 @@ extern "C" int svx_bam_seek(svx_bam* h, uint64_t voff, int32_t last_tid) {
     h->prefetch_err.clear();
     const size_t coff = (size_t)(voff >> 16), uoff = (size_t)(voff & 0xffff);
     if (coff > h->map_len) return bam_fail(SVX_E_ARG, "virtual offset beyond the end of the file");
+    if (h->dev) dev_drop_prefetch(h);                      // (the device reader's loader reads tid_limit, rg_on and rg: a chunk it is still loading is waited for before they change)
     h->fpos = coff; h->file_eof = false; h->buf.clear(); h->pos = 0; h->next_len = 0; h->next_eof = false;
     h->tid_limit = last_tid; h->region_done = false;
     // (the inflating thread is idle here: it reads the bound and counts into rg_stats)
@@ -717,7 +718,8 @@ extern "C" int svx_bam_rewind(svx_bam* h) {
     if (h->dev && devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_rewind during a sort pass (svx_bam_sort_finish or svx_bam_sort_abort first)");
     if (h->prefetch_active) { h->prefetch.wait(); h->prefetch_active = false; }
     h->prefetch_err.clear();
-    h->rg_on = false;                                    // (here, while the inflating thread is idle: it reads the flag)
+    if (h->dev) dev_drop_prefetch(h);                    // (the device reader's loader reads rg_on too: a chunk it is still loading is waited for first)
+    h->rg_on = false;                                    // (here, while the inflating thread and the loader are idle: they read the flag)
     if (getenv("SVX_BAM_TIMING")) {                      // per pass: the stages of the pass that just ended
         fprintf(stderr, "bamio pass: wait for inflate %.3f s, window copy %.3f, record walk %.3f, decode %.3f, names + SA %.3f\n", h->t_wait, h->t_copy, h->t_walk, h->t_decode, h->t_intern);
         h->t_wait = h->t_copy = h->t_walk = h->t_decode = h->t_intern = 0;
@@ -1259,13 +1261,13 @@ extern "C" int svx_bam_index_get_stats(svx_bam* h, svx_bam_index_stats* out) {
 
 // ---- coordinate sort from the device reader's record stream (include/svx.h; bamdev.hip appends bytes and rows, bamsort.hip sorts, lays out and encodes) -----
 // the header as the file holds it (magic .. reference dictionary), inflated from the first blocks of the mapped file
-static int raw_header(svx_bam* h, std::vector<uint8_t>& out) {
+static int raw_header(svx_bam* h, std::vector<uint8_t>& out, const char* who = "svx_bam_sort_finish") {
     out.clear();
     if (h->is_sam) {                                             // the BAM header of the text's header lines (sam_host.cpp)
         int64_t n = 0;
         int rc = svx_sam_header_host((const char*)h->map, (int64_t)h->header_bytes, nullptr, 0, &n);
         if (rc == SVX_E_CAPACITY) { out.resize((size_t)n); rc = svx_sam_header_host((const char*)h->map, (int64_t)h->header_bytes, out.data(), n, &n); }
-        return rc == SVX_OK ? SVX_OK : bam_fail(rc, "svx_bam_sort_finish: the SAM header cannot be turned into a BAM header");
+        return rc == SVX_OK ? SVX_OK : bam_fail(rc, std::string(who) + ": the SAM header cannot be turned into a BAM header");
     }
     size_t fp = 0;
     std::swap(fp, h->fpos);                                      // (read_block walks h->fpos; the host reader is idle in device mode)
@@ -1286,7 +1288,7 @@ static int raw_header(svx_bam* h, std::vector<uint8_t>& out) {
     } catch (const std::string& e) { err = e; }
     inflateEnd(&zs);
     std::swap(fp, h->fpos);
-    if (!err.empty()) return bam_fail(SVX_E_ARG, "svx_bam_sort_finish: " + err);
+    if (!err.empty()) return bam_fail(SVX_E_ARG, std::string(who) + ": " + err);
     out.resize(h->header_bytes);
     return SVX_OK;
 }
@@ -1373,6 +1375,193 @@ extern "C" int svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out) {
 extern "C" int svx_bam_sort_get_spill_stats(svx_bam* h, svx_bam_sort_spill_stats* out) {
     if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
     if (h->dev) devdec_sort_spill_stats(h->dev, out); else memset(out, 0, sizeof *out);
+    return SVX_OK;
+}
+
+// ---- several files merged on the device: the session (include/svx.h; its device side: bammerge.hip; what the merged file is: svim_amd/bammerge.py) -----------
+// The session owns its sort, stream and index (MergeDev) and copies of what it read from the readers at open: the merged header, every file's dictionary and
+// map.  It holds NO pointer to a reader.  A reader's decoder borrows the session's sort for the length of one svx_bam_merge_add and for no longer: the feed is set
+// and cleared inside that call, with the reader's loader idle at both points, so no state a caller can see has a handle pointing into a session.
+struct svx_bam_merge {
+    int64_t k = 0, added = 0; int device = 0;
+    MergeDev* dev = nullptr;
+    std::vector<uint8_t> header; int32_t n_ref_merged = 0;
+    struct File { std::vector<std::string> names; std::vector<int32_t> lens; int64_t map_at = 0; bool identity = true; };
+    std::vector<File> files;
+    bool broken = false, finished = false;
+    int64_t n_translated_files = 0; double t_open = 0, t_add = 0;
+};
+
+extern "C" void svx_bam_merge_close(svx_bam_merge* m) {
+    if (!m) return;
+    mergedev_destroy(m->dev); m->dev = nullptr;
+    delete m;
+}
+extern "C" int svx_bam_merge_open(svx_bam* const* readers, int64_t k, int device, int64_t max_bytes, const char* spill_dir, svx_bam_merge** out) {
+    if (!readers || k < 1 || max_bytes < 0 || !out) return bam_fail(SVX_E_ARG, "svx_bam_merge_open: bad argument");
+    for (int64_t f = 0; f < k; f++) if (!readers[f]) return bam_fail(SVX_E_ARG, "svx_bam_merge_open: null reader");
+    const double t0 = now_s();
+    svx_bam_merge* m = new svx_bam_merge();
+    m->k = k; m->device = device; m->files.resize((size_t)k);
+    std::vector<std::vector<uint8_t>> raw((size_t)k);
+    std::vector<const uint8_t*> ptrs((size_t)k); std::vector<int64_t> sizes((size_t)k);
+    int64_t n_maps = 0;
+    for (int64_t f = 0; f < k; f++) {
+        svx_bam* h = readers[f];
+        if (h->prefetch_active) h->prefetch.wait();         // (raw_header walks the mapped file through h->fpos, which the inflating thread advances; the chunk it made stays)
+        const int rc = raw_header(h, raw[(size_t)f], "svx_bam_merge_open");
+        if (rc != SVX_OK) { svx_bam_merge_close(m); return rc; }
+        ptrs[(size_t)f] = raw[(size_t)f].data(); sizes[(size_t)f] = (int64_t)raw[(size_t)f].size();
+        svx_bam_merge::File& F = m->files[(size_t)f];
+        F.names = h->ref_names; F.lens = h->ref_len; F.map_at = n_maps;
+        n_maps += (int64_t)F.names.size();
+    }
+    // the header rule and its refusals, before any device work
+    std::vector<int32_t> maps((size_t)std::max<int64_t>(n_maps, 1), 0);
+    int64_t n = 0;
+    int rc = svx_bam_merge_header_host(ptrs.data(), sizes.data(), k, nullptr, 0, &n, maps.data());
+    if (rc == SVX_E_CAPACITY) { m->header.resize((size_t)n); rc = svx_bam_merge_header_host(ptrs.data(), sizes.data(), k, m->header.data(), n, &n, maps.data()); }
+    if (rc != SVX_OK) { svx_bam_merge_close(m); return bam_fail(rc, "svx_bam_merge_open: the headers cannot be merged (a reference name with two lengths or twice in one file, @RG lines with one ID and different bytes, or a header that cannot be walked)"); }
+    {   // n_ref of the merged dictionary: behind the text of the header just made
+        const uint8_t* p = m->header.data();
+        const size_t l_text = m->header.size() >= 12 ? rd32(p + 4) : 0;
+        if (m->header.size() < 12 + l_text) { svx_bam_merge_close(m); return bam_fail(SVX_E_STATE, "svx_bam_merge_open: the merged header is cut short (internal error)"); }
+        m->n_ref_merged = (int32_t)rd32(p + 8 + l_text);
+    }
+    for (int64_t f = 0; f < k; f++) {
+        svx_bam_merge::File& F = m->files[(size_t)f];
+        for (size_t i = 0; i < F.names.size(); i++) {
+            const int32_t t = maps[(size_t)F.map_at + i];
+            if (t < 0 || t >= m->n_ref_merged) { svx_bam_merge_close(m); return bam_fail(SVX_E_STATE, "svx_bam_merge_open: a map entry outside the merged dictionary (internal error)"); }
+            if (t != (int32_t)i) F.identity = false;
+        }
+    }
+    rc = mergedev_create(device, max_bytes, m->n_ref_merged, spill_dir, maps.data(), n_maps, &m->dev);
+    if (rc != SVX_OK) { m->dev = nullptr; const std::string e = svx_last_error(); svx_bam_merge_close(m); return bam_fail(rc, e); }
+    m->t_open = now_s() - t0;
+    *out = m;
+    return SVX_OK;
+}
+#define MERGE_USABLE(what) \
+    if (!m) return bam_fail(SVX_E_ARG, what ": null session"); \
+    if (m->broken) return bam_fail(SVX_E_STATE, what ": the session is broken (an add or the finish failed): svx_bam_merge_close is all that is left")
+extern "C" int svx_bam_merge_add(svx_bam_merge* m, svx_bam* h) {
+    MERGE_USABLE("svx_bam_merge_add");
+    if (!h) return bam_fail(SVX_E_ARG, "svx_bam_merge_add: null reader");
+    if (m->finished || m->added >= m->k) return bam_fail(SVX_E_STATE, "svx_bam_merge_add: every file of the session has been added");
+    if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_merge_add: the session is fed by the device reader's record stream (svx_bam_set_device_decode first)");
+    if (devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_merge_add while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
+    if (devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_merge_add during a sort pass of the reader (svx_bam_sort_finish or svx_bam_sort_abort first)");
+    if (h->rg_on) return bam_fail(SVX_E_STATE, "svx_bam_merge_add on a region read (svx_bam_seek_region): the pass runs over the whole file (rewind first)");
+    if (h->tid_limit != -2) return bam_fail(SVX_E_STATE, "svx_bam_merge_add on a contig range (svx_bam_seek with a last reference id): the pass runs over the whole file (rewind first)");
+    if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
+        return bam_fail(SVX_E_STATE, "svx_bam_merge_add: the handle is not at its first record (add before the first read, or rewind first)");
+    if (devdec_feed_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_merge_add: the reader is feeding a session (internal error)");
+    if (devdec_device(h->dev) != mergedev_device(m->dev)) return bam_fail(SVX_E_ARG, "svx_bam_merge_add: the reader decodes on another device than the session's");
+    const svx_bam_merge::File& F = m->files[(size_t)m->added];
+    if (h->ref_names != F.names || h->ref_len != F.lens)
+        return bam_fail(SVX_E_ARG, "svx_bam_merge_add: the reader's dictionary is not the one file " + std::to_string(m->added) + " had at svx_bam_merge_open (files are added in the order they were opened in)");
+    const double t0 = now_s();
+    mergedev_feed(m->dev, h->dev, F.map_at, (int32_t)F.names.size(), F.identity);
+    h->dev_eof_seen = false;
+    // the whole pass, here: batches are read and discarded, every chunk the loader decodes is appended to the session's sort on the session's stream
+    int rc = SVX_OK; std::string err;
+    for (;;) {
+        svx_batch b; int64_t n = 0;
+        rc = read_batch_device(h, 200000, 0, 0, &b, &n);
+        if (rc != SVX_OK) { err = g_svx_err; break; }
+        if (n == 0) break;
+    }
+    if (rc == SVX_OK && !h->dev_eof_seen) { rc = SVX_E_STATE; err = "the pass ended in front of the end of the file (internal error)"; }      // (what svx_bam_sort_finish asks, too)
+    dev_drop_prefetch(h);                                   // (a failed pass may have left a chunk being loaded: the loader is idle from here on)
+    // Appends ran in the reader's loader thread, on the SESSION's stream (the reader's own was drained in front of each); bamsort_append drains that stream
+    // before it returns and the loader is idle here, so what svx_bam_merge_finish does on the same stream needs no event.  From here on the reader holds
+    // nothing of the session, and nothing of the session was ever touched by a command on the reader's streams.
+    devdec_feed_clear(h->dev);
+    m->t_add += now_s() - t0;
+    if (rc != SVX_OK) {
+        mergedev_drop(m->dev); m->broken = true;            // (the reader is usable after svx_bam_rewind, as after a failed sort pass)
+        return bam_fail(rc, "svx_bam_merge_add: " + err);
+    }
+    if (!F.identity) m->n_translated_files++;
+    m->added++;
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_finish(svx_bam_merge* m) {
+    MERGE_USABLE("svx_bam_merge_finish");
+    if (m->finished) return bam_fail(SVX_E_STATE, "svx_bam_merge_finish twice");
+    if (m->added != m->k) return bam_fail(SVX_E_STATE, "svx_bam_merge_finish before every file has been added");
+    const int rc = mergedev_finish(m->dev, m->header.data(), (int64_t)m->header.size());
+    if (rc != SVX_OK) { m->broken = true; return bam_fail(rc, svx_last_error()); }
+    m->finished = true;
+    return SVX_OK;
+}
+#define MERGE_NEEDS_FINISHED(what) \
+    MERGE_USABLE(what); \
+    if (!m->finished) return bam_fail(SVX_E_STATE, what ": no merged records (k adds, then svx_bam_merge_finish)")
+extern "C" int svx_bam_merge_count(svx_bam_merge* m, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) {
+    MERGE_NEEDS_FINISHED("svx_bam_merge_count");
+    mergedev_count(m->dev, n_records, stream_bytes, n_blocks);
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_encode(svx_bam_merge* m, int64_t first_block, int64_t n_blocks, int64_t* n_bytes) {
+    MERGE_NEEDS_FINISHED("svx_bam_merge_encode");
+    const int rc = mergedev_encode(m->dev, first_block, n_blocks, n_bytes);
+    if (rc == SVX_E_IO) { mergedev_drop(m->dev); m->broken = true; }      // (the spill file cannot be read: nothing of the sort is of use)
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_fetch(svx_bam_merge* m, uint8_t* compressed_dst, uint8_t* stream_dst) {
+    MERGE_NEEDS_FINISHED("svx_bam_merge_fetch");
+    const int rc = mergedev_fetch(m->dev, compressed_dst, stream_dst);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_index_fmt(svx_bam_merge* m, int fmt) {
+    MERGE_NEEDS_FINISHED("svx_bam_merge_index_fmt");
+    if (!index_fmt_ok(fmt)) return bam_fail(SVX_E_ARG, "svx_bam_merge_index_fmt: unknown index format (SVX_INDEX_CLASSIC or SVX_INDEX_CSI)");
+    const int rc = mergedev_index(m->dev, fmt);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_index_count(svx_bam_merge* m, int64_t* n_bytes) {
+    MERGE_USABLE("svx_bam_merge_index_count");
+    if (!mergedev_index_bytes(m->dev, n_bytes)) return bam_fail(SVX_E_STATE, "no index of the merged file: svx_bam_merge_finish, every block encoded, svx_bam_merge_index_fmt");
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_index_fetch(svx_bam_merge* m, uint8_t* host_dst) {
+    MERGE_USABLE("svx_bam_merge_index_fetch");
+    if (!mergedev_index_bytes(m->dev, nullptr)) return bam_fail(SVX_E_STATE, "no index of the merged file: svx_bam_merge_finish, every block encoded, svx_bam_merge_index_fmt");
+    const int rc = mergedev_index_fetch(m->dev, host_dst);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_permutation(svx_bam_merge* m, uint32_t* perm) {
+    MERGE_NEEDS_FINISHED("svx_bam_merge_permutation");
+    const int rc = mergedev_permutation(m->dev, perm);
+    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
+    return SVX_OK;
+}
+static void merge_stats(svx_bam_merge* m, svx_bam_sort_stats* st, svx_bam_sort_spill_stats* sp, svx_bam_merge_stats* ms) {
+    svx_bam_sort_stats a; svx_bam_sort_spill_stats b; int64_t c = 0, r = 0, by = 0; double t = 0;
+    mergedev_stats(m->dev, &a, &b, &c, &r, &by, &t);
+    if (st) *st = a;
+    if (sp) *sp = b;
+    if (ms) *ms = svx_bam_merge_stats{m->k, m->added, m->n_ref_merged, (int64_t)m->header.size(), m->n_translated_files, c, r, by, m->t_open * 1e3, m->t_add * 1e3, t};
+}
+extern "C" int svx_bam_merge_get_stats(svx_bam_merge* m, svx_bam_sort_stats* out) {
+    if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
+    merge_stats(m, out, nullptr, nullptr);
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_get_spill_stats(svx_bam_merge* m, svx_bam_sort_spill_stats* out) {
+    if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
+    merge_stats(m, nullptr, out, nullptr);
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_get_merge_stats(svx_bam_merge* m, svx_bam_merge_stats* out) {
+    if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
+    merge_stats(m, nullptr, nullptr, out);
     return SVX_OK;
 }
 

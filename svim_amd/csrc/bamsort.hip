@@ -5,7 +5,8 @@
 // src/svim/SVIM_alignment.py:48-50): single-threaded zlib both ways and a merge on the host, for records this reader has already found.
 //   append   while sorting is on, every chunk the reader loads leaves its records' bytes - they lie back to back in the inflated stream - in a slab of their own
 //            (one device-to-device copy; slabs are never moved or regrown) and one row per record: k_bs_rows the key, the length, the address in the slab, the
-//            checks; the index rows (tid, pos, end, flag) by bamindex.hip's own append
+//            checks; the index rows (tid, pos, end, flag) by bamindex.hip's own append.  A chunk of a file of a merge session (bammerge.hip) whose dictionary is
+//            not the merged one passes k_bs_translate first: refID and next_refID mapped, patched in the slab by byte stores, the merged id in a column of its own
 //   finish   the keys sorted stably (svx_sort_pairs_u64_on over the key's used bits) with the record number as payload = the permutation; k_bs_layout the
 //            segments of the output stream (the header, then the records in order) with their lengths and addresses; a scan gives every segment's offset
 //   encode   a range of 65 280-byte blocks: k_bs_gather lays the stream bytes of the range out in the piece buffer, then the encoder's phases over the piece
@@ -52,18 +53,40 @@ static_assert(BSORT_BLOCK % 16 == 0 && BS_TILE % 16 == 0, "a piece and its tiles
 typedef unsigned int bs_u32x4 __attribute__((ext_vector_type(4)));
 
 // ---- append ---------------------------------------------------------------------------------------------------------------------------------------------
+// n_ref_check: the dictionary the record's id must lie in (of a file of a merge: that file's own); n_ref: the dictionary the key is built over
 __global__ void k_bs_rows(long long n, const uint8_t* st, const uint64_t* rec_off, uint64_t first_byte, uint64_t end_byte, uint64_t slab, const int32_t* tid, const int32_t* pos,
-                          const uint16_t* flag, int32_t n_ref, uint64_t* key, uint32_t* len, uint64_t* addr, int* bad) {
+                          const uint16_t* flag, int32_t n_ref_check, int32_t n_ref, uint64_t* key, uint32_t* len, uint64_t* addr, int* bad) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint64_t p = rec_off[i];
     const uint32_t bs = (uint32_t)st[p] | ((uint32_t)st[p + 1] << 8) | ((uint32_t)st[p + 2] << 16) | ((uint32_t)st[p + 3] << 24);
-    int b = bsort_check(tid[i], pos[i], bs, n_ref);
+    int b = bsort_check(tid[i], pos[i], bs, n_ref_check);
     if (p < first_byte || p + 4ull + bs > end_byte) b |= BSORT_BAD_SIZE;            // (cannot happen: the reader walked these records)
     if (b) atomicOr(bad, b);
     key[i] = bsort_key(tid[i], pos[i], flag[i], n_ref);
     len[i] = 4u + bs;
     addr[i] = slab + (p - first_byte);
+}
+// a chunk of a file of a merge whose dictionary is not the merged one (svim_amd/bammerge.py), in front of k_bs_rows: a thread per record.  refID is the decoded
+// column, next_refID the record's bytes - records are 4-byte aligned only by accident, so bytes are loaded - and bsort_translate maps both.  The merged refID goes
+// to tid_out (the key's and the index row's column), and the two fields are patched in the SLAB's copy by byte stores: two 36-byte neighbours may share an
+// aligned word, which a read-modify-write of it by both their threads would tear.  A record shorter than its fixed fields is left alone (k_bs_rows refuses it)
+__global__ void k_bs_translate(long long n, const uint64_t* rec_off, uint64_t first_byte, uint64_t end_byte, uint8_t* slab, const int32_t* tid, const int32_t* map, int32_t n_ref_file,
+                               int32_t* tid_out, int* bad) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t p = rec_off[i];
+    if (p < first_byte || p + 4ull + BSORT_MIN_BLOCK_SIZE > end_byte) { tid_out[i] = -1; return; }
+    uint8_t* r = slab + (p - first_byte);
+    const uint32_t bs = (uint32_t)r[0] | ((uint32_t)r[1] << 8) | ((uint32_t)r[2] << 16) | ((uint32_t)r[3] << 24);
+    if (bs < BSORT_MIN_BLOCK_SIZE) { tid_out[i] = -1; return; }
+    const uint8_t* m = r + BSORT_MATE_AT;
+    const int32_t mate = (int32_t)((uint32_t)m[0] | ((uint32_t)m[1] << 8) | ((uint32_t)m[2] << 16) | ((uint32_t)m[3] << 24));
+    int32_t t, mt;
+    const int b = bsort_translate(tid[i], mate, map, n_ref_file, &t, &mt);
+    tid_out[i] = t;
+    for (int k = 0; k < 4; k++) { r[BSORT_REFID_AT + k] = (uint8_t)((uint32_t)t >> (8 * k)); r[BSORT_MATE_AT + k] = (uint8_t)((uint32_t)mt >> (8 * k)); }
+    if (b) atomicOr(bad, b);
 }
 
 // ---- finish ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -242,6 +265,8 @@ struct BamSort {
     std::vector<uint8_t> h_io;                               // the host's side of the file's traffic
     std::vector<int64_t> h_cuts;                             // of the piece being encoded: 2 n_runs byte offsets, j0, j1
     svx_bam_sort_spill_stats sp;
+    // chunks of a merge (BamSortChunk::tid_map): the merged refID column of the chunk being appended, and what k_bs_translate has done since begin
+    DevBuf xtid; hipEvent_t tr_ev[2] = {nullptr, nullptr}; int64_t tr_chunks = 0, tr_records = 0, tr_bytes = 0; double tr_ms = 0;
 };
 static inline double bs_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -280,12 +305,14 @@ void bamsort_drop(BamSort* S) {
     S->n = S->cap = 0; S->finished = false; S->have_piece = false; S->stream_bytes = S->n_blocks = S->next_block = 0; S->broken = false; S->t_append = 0;
     S->piece_bytes = S->out_bytes = 0;
     S->h_csize.clear(); S->h_csize.shrink_to_fit();
+    S->xtid.release(); S->tr_chunks = S->tr_records = S->tr_bytes = 0; S->tr_ms = 0;
 }
 void bamsort_destroy(BamSort* S) {
     if (!S) return;
     bamsort_drop(S);
     bamindex_destroy(S->rows);
     S->bad.release(); S->crc_shift.release();
+    for (auto& e : S->tr_ev) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     delete S;
 }
 
@@ -354,6 +381,8 @@ static int bs_close_run(BamSort* S, hipStream_t st) {
 
 int bamsort_append(BamSort* S, const BamSortChunk& c, hipStream_t st) {
     if (!S || S->finished || c.n < 0 || c.end_byte < c.first_byte) return svx_fail(SVX_E_ARG, "BAM sort: bad chunk", __FILE__, __LINE__, hipSuccess);
+    const bool translated = c.n_ref_file >= 0 && !c.identity;
+    if (c.n_ref_file > S->n_ref || (translated && c.n_ref_file > 0 && !c.tid_map)) return svx_fail(SVX_E_ARG, "BAM sort: a chunk of a file whose dictionary is not part of the sort's", __FILE__, __LINE__, hipSuccess);
     if (c.n == 0) return SVX_OK;
     const double t0 = bs_now();
     if (S->n + c.n > 0xffffffffll) return svx_fail(SVX_E_CAPACITY, "BAM sort: more than 2^32 - 1 records", __FILE__, __LINE__, hipSuccess);
@@ -385,13 +414,30 @@ int bamsort_append(BamSort* S, const BamSortChunk& c, hipStream_t st) {
     S->sp.max_chunk_bytes = std::max<int64_t>(S->sp.max_chunk_bytes, (int64_t)need);
     HIPCHK(hipMemcpyAsync(slab, c.stream + c.first_byte, need, hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemsetAsync((uint8_t*)slab + need, 0, BS_PAD, st));
-    k_bs_rows<<<BS_GRID(c.n), BS_T, 0, st>>>(c.n, c.stream, c.rec_off, c.first_byte, c.end_byte, (uint64_t)(uintptr_t)slab, c.tid, c.pos, c.flag, S->n_ref, S->key.as<uint64_t>() + n_run,
-                                             S->len.as<uint32_t>() + n_run, S->addr.as<uint64_t>() + n_run, S->bad.as<int>());
+    const int32_t* tid = c.tid;                              // the column the key and the index row are made of
+    int32_t n_ref_check = c.n_ref_file >= 0 ? c.n_ref_file : S->n_ref;
+    if (translated) {
+        // the ids of this file are not the merged ones: mapped for the rows, patched in the slab (an identity file takes no launch and keeps its bytes)
+        SVXCHK(S->xtid.reserve((size_t)c.n * 4));
+        for (auto& e : S->tr_ev) if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventRecord(S->tr_ev[0], st));
+        k_bs_translate<<<BS_GRID(c.n), BS_T, 0, st>>>(c.n, c.rec_off, c.first_byte, c.end_byte, (uint8_t*)slab, c.tid, c.tid_map, c.n_ref_file, S->xtid.as<int32_t>(), S->bad.as<int>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(S->tr_ev[1], st));
+        tid = S->xtid.as<int32_t>(); n_ref_check = S->n_ref;  // (the mapped ids lie in the merged dictionary; what the file's own did not hold is flagged)
+    }
+    k_bs_rows<<<BS_GRID(c.n), BS_T, 0, st>>>(c.n, c.stream, c.rec_off, c.first_byte, c.end_byte, (uint64_t)(uintptr_t)slab, tid, c.pos, c.flag, n_ref_check, S->n_ref,
+                                             S->key.as<uint64_t>() + n_run, S->len.as<uint32_t>() + n_run, S->addr.as<uint64_t>() + n_run, S->bad.as<int>());
     HIPCHK(hipGetLastError());
     // the index rows: end from the CIGAR (CG included) by bamindex.hip's append; its virtual offsets are replaced when the sorted file's are known
     const uint64_t blk_start = 0, blk_vbase = 0;
-    const BamIndexChunk ic{c.n, c.tid, c.pos, c.flag, c.cigar_off, c.cigar, c.rec_off, &blk_start, &blk_vbase, 1};
-    SVXCHK(bamindex_append(S->rows, ic, st));               // (drains the stream: the chunk's arrays and its stream are no longer read)
+    const BamIndexChunk ic{c.n, tid, c.pos, c.flag, c.cigar_off, c.cigar, c.rec_off, &blk_start, &blk_vbase, 1};
+    SVXCHK(bamindex_append(S->rows, ic, st));               // (drains the stream: the chunk's arrays, its stream and xtid are no longer read)
+    if (translated) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, S->tr_ev[0], S->tr_ev[1]) == hipSuccess) S->tr_ms += ms;
+        S->tr_chunks++; S->tr_records += c.n; S->tr_bytes += c.n * 32;      // per record: 8 of rec_off, 4 + 4 + 4 read (size, refID column, mate), 4 written, 8 patched
+    }
     S->n += c.n;
     S->t_append += bs_now() - t0 - t_closing;
     return SVX_OK;
@@ -447,6 +493,7 @@ int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipS
     const double t0 = bs_now();
     int bad = 0;
     SVXCHK(svx_d2h(&bad, S->bad.p, 4, st));
+    if (bad & BSORT_BAD_MATE) return svx_fail(SVX_E_ARG, "BAM merge: a record of a file whose ids are translated names a mate reference its header does not have", __FILE__, __LINE__, hipSuccess);
     if (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID)) return svx_fail(SVX_E_ARG, "BAM sort: a record names a reference the header does not have, or is shorter than its fixed fields", __FILE__, __LINE__, hipSuccess);
     if (bad & BSORT_BAD_POS) return svx_fail(SVX_E_RANGE, "BAM sort: a record has a position below -1", __FILE__, __LINE__, hipSuccess);
     SVXCHK(S->hdr.reserve((size_t)header_bytes + BS_PAD));
@@ -692,4 +739,7 @@ void bamsort_spill_stats(const BamSort* S, svx_bam_sort_spill_stats* out) {
 }
 void bamsort_stats(const BamSort* S, svx_bam_sort_stats* out) {
     if (S) *out = S->stats; else memset(out, 0, sizeof *out);
+}
+void bamsort_translate_stats(const BamSort* S, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms) {
+    *n_chunks = S ? S->tr_chunks : 0; *n_records = S ? S->tr_records : 0; *n_bytes = S ? S->tr_bytes : 0; *ms = S ? S->tr_ms : 0;
 }

@@ -5,10 +5,14 @@
 
 struct BamSort;
 // what one loaded chunk hands over: its n records lie back to back in stream[first_byte, end_byte), record i at rec_off[i]; the decoded columns are those the
-// index takes (device arrays)
+// index takes (device arrays).  A merge session (bammerge.hip) says which file of several the chunk is of: n_ref_file >= 0 is that file's dictionary size - the
+// range checks run over it, the key over the sort's n_ref (the merged dictionary) - and, unless `identity`, tid_map (device, n_ref_file entries) the merged id
+// of every reference of the file: the chunk's records then get refID and next_refID translated in the sort's copy (k_bs_translate).  n_ref_file < 0: one file
+// sorted alone, nothing of this applies
 struct BamSortChunk {
     long long n; const uint8_t* stream; uint64_t first_byte, end_byte; const uint64_t* rec_off;
     const int32_t *tid, *pos; const uint16_t* flag; const uint64_t* cigar_off; const uint32_t* cigar;
+    const int32_t* tid_map = nullptr; int32_t n_ref_file = -1; bool identity = true;
 };
 // an empty arena (the state is made on first use); max_bytes 0: what the device has free.  spill_dir (may be null): the directory of the spill file - a chunk
 // that would pass the limit then closes a run (sorted, laid out, written to the file, slabs freed) instead of failing; SVX_E_ARG: not a writable directory
@@ -28,3 +32,5 @@ int  bamsort_index(BamSort* s, BamIndex* ix, hipStream_t st, int fmt);
 int  bamsort_permutation(BamSort* s, uint32_t* host_perm, hipStream_t st);
 void bamsort_stats(const BamSort* s, svx_bam_sort_stats* out);
 void bamsort_spill_stats(const BamSort* s, svx_bam_sort_spill_stats* out);
+// what k_bs_translate has done for the sort since begin: chunks and records it ran over, the bytes it read and wrote, its time between events on the stream
+void bamsort_translate_stats(const BamSort* s, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms);

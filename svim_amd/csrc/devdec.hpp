@@ -68,3 +68,30 @@ int  devdec_sort_index(svx_devdec* d, int fmt);
 int  devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm);
 void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out);
 void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out);
+// A merge session's feed (svx_bam_merge_add; bammerge.hip): while set, every devdec_load appends the records it hands to devdec_count to the SESSION's sort -
+// in this decoder's loader thread but on the SESSION's stream (session_stream: a hipStream_t), once the decoder's own stream has been drained - as records of a
+// file with n_ref_file references whose ids dev_map (device memory of the session; unused when `identity`) takes into the merged dictionary.  Every command that
+// touches the session's memory thus runs on the one stream that lives as long as that memory does, whichever readers come and go.  The decoder borrows the sort
+// and never owns it: a failed append clears the feed and fails the load, nothing else.  Set and cleared only while no loader runs.
+struct BamSort;
+void devdec_feed_set(svx_devdec* d, BamSort* sort, void* session_stream, const int32_t* dev_map, int32_t n_ref_file, bool identity);
+void devdec_feed_clear(svx_devdec* d);
+bool devdec_feed_on(const svx_devdec* d);
+int  devdec_device(const svx_devdec* d);
+// ---- the device side of a merge session (bammerge.hip): a sort, a stream and an output index of its OWN; thin wrappers over bamsort_* / bamindex_* ----
+struct MergeDev;
+// maps: the files' maps back to back (n_maps entries, uploaded once); spill_dir may be null
+int  mergedev_create(int device, int64_t max_bytes, int32_t n_ref_merged, const char* spill_dir, const int32_t* maps, int64_t n_maps, MergeDev** out);
+void mergedev_destroy(MergeDev* m);
+int  mergedev_device(const MergeDev* m);
+void mergedev_feed(MergeDev* m, svx_devdec* d, int64_t map_at, int32_t n_ref_file, bool identity);      // devdec_feed_set with the session's sort and map
+void mergedev_drop(MergeDev* m);                         // the sort's memory goes back (a failed append, a failed finish)
+int  mergedev_finish(MergeDev* m, const uint8_t* header, int64_t header_bytes);
+void mergedev_count(const MergeDev* m, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
+int  mergedev_encode(MergeDev* m, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
+int  mergedev_fetch(MergeDev* m, uint8_t* compressed_dst, uint8_t* stream_dst);
+int  mergedev_index(MergeDev* m, int fmt);
+bool mergedev_index_bytes(const MergeDev* m, int64_t* n_bytes);
+int  mergedev_index_fetch(MergeDev* m, uint8_t* host_dst);
+int  mergedev_permutation(MergeDev* m, uint32_t* host_perm);
+void mergedev_stats(const MergeDev* m, svx_bam_sort_stats* out, svx_bam_sort_spill_stats* spill, int64_t* tr_chunks, int64_t* tr_records, int64_t* tr_bytes, double* tr_ms);

@@ -40,13 +40,16 @@ class BamPipeline(object):
     """reader thread || GPU thread over one BAM file; results stay resident in the engine (accumulated lists)."""
 
     def __init__(self, path, options, engine, threads=0, batch_records=200_000, mode="coordinate", sparse_seq=True, regions=None, gpu_inflate=None,
-                 device_decode=None, keep_alignments=False, build_index=False, index_format="bai", index=None, region_rule="overlap"):
-        """regions: None (the whole file); [(virtual offset, last reference id)]: contig runs (svx_bam_seek); or coordinate regions (svim_amd/regions.py): region
+                 device_decode=None, keep_alignments=False, build_index=False, index_format="bai", index=None, region_rule="overlap", merged_out=None):
+        """path: one BAM file (or SAM text), or a list of them with merged_out=PATH: the files are merged into that file first (merge_bam) and read from it.
+        regions: None (the whole file); [(virtual offset, last reference id)]: contig runs (svx_bam_seek); or coordinate regions (svim_amd/regions.py): region
         strings ("chr1:10,000,000-12,000,000"), (contig, beg, end) tuples (0-based, half-open) - parsed, normalised and planned from the file's index, read in
         file order - or planned reads (virtual offset, tid, beg, end) as regions.plan and harness.window_plan give them.  index: the .bai / .csi the plan comes
         from - a path, its bytes, or None: <bam>.bai if present, else <bam>.csi.  region_rule: "overlap" (samtools view) or "start" (ownership by start)"""
         from .bamio import NativeBam
         from . import regions as _regions
+        if isinstance(path, (list, tuple)):                         # several files: merged on the device into merged_out first, the pipeline runs over that file
+            path = _merged_input(path, merged_out, getattr(engine, "device", None) or 0, threads)
         coordinate_regions = regions is not None and any(isinstance(r, str) or len(r) != 2 for r in regions)
         if coordinate_regions and any(not isinstance(r, str) and len(r) == 2 for r in regions):
             raise ValueError("regions: either (virtual offset, last reference id) pairs or coordinate regions, not both")
@@ -914,6 +917,64 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
     return stats
 
 
+def merge_bam(paths, out, device=0, index=True, index_format="bai", piece_blocks=4096, max_bytes=0, spill_dir=None, threads=0, batch_records=200_000):
+    """Several BAM files (or SAM texts: NativeBam tells them apart), each in any order, written to `out` as ONE file in coordinate order (svim_amd/bammerge.py
+    says what the merged file is: the merged dictionary and header, reference ids translated, ties in file order), and its index to out + ".bai" or ".csi" when
+    `index`: `samtools merge` of the reference's front end, on the device (bamio.BamMerge).  The readers are opened, the session reads their headers, then every
+    file is added in turn - one pass of the device reader each - and its reader closed; the merged file is encoded and written in pieces of piece_blocks BGZF
+    blocks.  max_bytes, spill_dir: as sort_bam, over all files together.  batch_records: unused (a session reads the files itself).
+    -> the sort's stats with the spill's under "spill" and the session's under "merge".  On failure what was written is removed and the session closed;
+    svim_amd.bammerge.BamMergeError carries the library's status in .code."""
+    from .bamio import BamMerge, NativeBam
+    paths = [os.fspath(p) for p in paths]
+    if not paths:
+        raise ValueError("merge_bam: no input")
+    if piece_blocks < 1:
+        raise ValueError("merge_bam: piece_blocks must be at least 1")
+    readers, session, written = [], None, []
+    try:
+        for p in paths:
+            readers.append(NativeBam(p, threads=threads))
+        lengths = {}
+        for r in readers:
+            lengths.update(zip(r.references, r.lengths))
+        index_format = _bam_index_format(index_format, list(lengths.values()))
+        for r in readers:
+            r.set_device_decode(int(device))
+        session = BamMerge.open(readers, device=device, max_bytes=max_bytes, spill_dir=spill_dir)
+        for r in readers:
+            session.add(r)
+            r.close()
+        _, _, n_blocks = session.finish()
+        written.append(out)
+        with open(out, "wb") as fh:
+            for first in range(0, n_blocks, piece_blocks):
+                fh.write(session.encode(first, min(piece_blocks, n_blocks - first)))
+        if index:
+            data = session.index(index_format)
+            written.append(out + "." + index_format)
+            _write_bam_index(out + "." + index_format, data, index_format)
+        return session.stats()
+    except BaseException:
+        for f in written:
+            if os.path.exists(f):
+                os.remove(f)
+        raise
+    finally:
+        if session is not None:
+            session.close()
+        for r in readers:
+            r.close()
+
+
+def _merged_input(paths, merged_out, device, threads=0):
+    """a list of inputs for an entry point that takes one file: merged to `merged_out` first (merge_bam, with its .bai) -> that path"""
+    if not merged_out:
+        raise ValueError("several BAM files need merged_out=PATH: they are merged into that file first (harness.merge_bam), and the run is over it")
+    merge_bam(list(paths), merged_out, device=device, threads=threads)
+    return merged_out
+
+
 def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None, index_format="bai"):
     """SAM text at `sam` -> a BAM file at `out_bam`: the reference's `samtools view -b | samtools sort` and `samtools index` (src/svim/SVIM_alignment.py).
     sort=True: one pass of the device reader, coordinate order and, with `index`, out_bam + ".bai" (sort_bam does it: svim_amd/sam.py says what the records are,
@@ -1052,11 +1113,15 @@ def collect_cluster_bam_sharded(bam_path, opts, engine, adapter, rank, world, th
     return res, pipe, names
 
 
-def run_bam(bam_path, fasta_path, opts, rank=0, world=1, device=0, steps=1, warmup=0, threads=0):
+def run_bam(bam_path, fasta_path, opts, rank=0, world=1, device=0, steps=1, warmup=0, threads=0, merged_out=None):
     """bench.py --bam PATH --fasta PATH: read / op / signature / cluster counts and the end-to-end rates of a real
     coordinate-sorted BAM on ONE GPU (contig-sharded multi-GPU reading needs the .bai route)."""
     if not fasta_path:
         raise SystemExit("bench.py --bam needs --fasta (the reference genome the insertion haplotypes are built from)")
+    if isinstance(bam_path, (list, tuple)):                        # one BAM per flow cell: merged on the device into merged_out first (rank 0 writes it)
+        if world > 1:
+            raise SystemExit("run_bam: a list of BAM files is merged and read on one GPU (merge first with harness.merge_bam, then run the ranks on that file)")
+        bam_path = _merged_input(bam_path, merged_out, device, threads)
     eng = _lib.Engine(device)
     from .bamio import NativeBam
     nb = NativeBam(bam_path, threads=1)

@@ -36,12 +36,29 @@ struct MockSlot {
                      delete[] cigar; delete[] seq_off; delete[] seg_off; delete[] seg_cigar_off;
                      flag = nullptr; tid = pos = lseq = read_id = nullptr; mapq = nullptr; order = seg_off = cigar = nullptr; cigar_off = seq_off = seg_cigar_off = nullptr; n_rec = 0; tail_start = 0; }
 };
-struct svx_devdec { MockSlot slot[3]; std::vector<std::string> names; std::vector<int32_t> rank; long long loads = 0; };
+#ifdef BAMIO_FUZZ_SORT_MODEL       /* (tools/bam_merge_session_test.cpp: the decoder's own sort and a merge session's feed over a CPU model of the sort) */
+struct BamSort;
+struct svx_devdec;
+static int model_after_load(svx_devdec* d, const MockSlot& S, const uint64_t* rec, size_t n_rec);
+static void model_destroy_decoder(svx_devdec* d);
+#endif
+struct svx_devdec { MockSlot slot[3]; std::vector<std::string> names; std::vector<int32_t> rank; long long loads = 0;
+#ifdef BAMIO_FUZZ_SORT_MODEL
+                    BamSort* sort = nullptr; bool sort_on = false; BamSort* feed = nullptr; const int32_t* feed_map = nullptr; int32_t feed_n_ref = 0; bool feed_identity = true;
+#endif
+};
 static uint32_t m32(const uint8_t* p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 int devdec_create(int, int, int32_t n_ref, const int32_t*, const char*, const int32_t* contig_rank, svx_devdec** out) {
     svx_devdec* d = new svx_devdec(); d->rank.assign(contig_rank, contig_rank + n_ref); *out = d; return SVX_OK;
 }
-void devdec_destroy(svx_devdec* d) { if (!d) return; for (auto& s : d->slot) s.release(); delete d; }
+void devdec_destroy(svx_devdec* d) {
+    if (!d) return;
+#ifdef BAMIO_FUZZ_SORT_MODEL
+    model_destroy_decoder(d);
+#endif
+    for (auto& s : d->slot) s.release();
+    delete d;
+}
 int devdec_load(svx_devdec* d, int slot, const DevDecBlock* blocks, size_t n, int carry_slot, uint64_t skip, bool final_chunk, int, int mode) {
     std::vector<uint8_t>* st = new std::vector<uint8_t>();
     if (carry_slot >= 0) { const MockSlot& c = d->slot[carry_slot]; if (!c.stream) { delete st; g_svx_err = "mock: carry from an empty slot"; return SVX_E_STATE; }
@@ -89,7 +106,11 @@ int devdec_load(svx_devdec* d, int slot, const DevDecBlock* blocks, size_t n, in
         S.read_id[i] = id;
     }
     S.cigar_off[m] = c; S.seq_off[m] = 0;
+#ifdef BAMIO_FUZZ_SORT_MODEL
+    return model_after_load(d, S, rec.data(), keep);
+#else
     return SVX_OK;
+#endif
 }
 int devdec_count(svx_devdec* d, int slot, int32_t tid_limit, int64_t* n_rec, int64_t* n_valid) {
     const MockSlot& S = d->slot[slot];
@@ -137,6 +158,7 @@ int devdec_index_finish(svx_devdec*, uint64_t, int) { return SVX_E_STATE; }
 bool devdec_index_bytes(const svx_devdec*, int64_t*) { return false; }
 int devdec_index_fetch(svx_devdec*, uint8_t*) { return SVX_E_STATE; }
 void devdec_index_stats(const svx_devdec*, svx_bam_index_stats* out) { memset(out, 0, sizeof *out); }
+#ifndef BAMIO_FUZZ_SORT_MODEL       /* (a program that defines it brings these itself, over a model of the sort, and links bamsort_host.cpp) */
 // (so is the coordinate sort; the header rewrite it asks the host for lives in bamsort_host.cpp, which this program does not link)
 int devdec_sort_begin(svx_devdec*, int64_t, const char*) { return SVX_E_STATE; }
 void devdec_sort_drop(svx_devdec*) {}
@@ -151,6 +173,27 @@ int devdec_sort_permutation(svx_devdec*, uint32_t*) { return SVX_E_STATE; }
 void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
 void devdec_sort_spill_stats(const svx_devdec*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
 extern "C" int svx_bam_sort_header_host(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
+// (and the merge session of several files, which is fed by that sort's appends)
+void devdec_feed_set(svx_devdec*, BamSort*, void*, const int32_t*, int32_t, bool) {}
+void devdec_feed_clear(svx_devdec*) {}
+bool devdec_feed_on(const svx_devdec*) { return false; }
+int devdec_device(const svx_devdec*) { return 0; }
+int mergedev_create(int, int64_t, int32_t, const char*, const int32_t*, int64_t, MergeDev**) { return SVX_E_NODEVICE; }
+void mergedev_destroy(MergeDev*) {}
+int mergedev_device(const MergeDev*) { return 0; }
+void mergedev_feed(MergeDev*, svx_devdec*, int64_t, int32_t, bool) {}
+void mergedev_drop(MergeDev*) {}
+int mergedev_finish(MergeDev*, const uint8_t*, int64_t) { return SVX_E_STATE; }
+void mergedev_count(const MergeDev*, int64_t*, int64_t*, int64_t*) {}
+int mergedev_encode(MergeDev*, int64_t, int64_t, int64_t*) { return SVX_E_STATE; }
+int mergedev_fetch(MergeDev*, uint8_t*, uint8_t*) { return SVX_E_STATE; }
+int mergedev_index(MergeDev*, int) { return SVX_E_STATE; }
+bool mergedev_index_bytes(const MergeDev*, int64_t*) { return false; }
+int mergedev_index_fetch(MergeDev*, uint8_t*) { return SVX_E_STATE; }
+int mergedev_permutation(MergeDev*, uint32_t*) { return SVX_E_STATE; }
+void mergedev_stats(const MergeDev*, svx_bam_sort_stats* a, svx_bam_sort_spill_stats* b, int64_t* c, int64_t* r, int64_t* by, double* t) { memset(a, 0, sizeof *a); memset(b, 0, sizeof *b); *c = *r = *by = 0; *t = 0; }
+extern "C" int svx_bam_merge_header_host(const uint8_t* const*, const int64_t*, int64_t, uint8_t*, int64_t, int64_t*, int32_t*) { return SVX_E_STATE; }
+#endif
 // SAM text (svx_sam_open): the front end is the device's (sam.hip) and the header parser sam_host.cpp's; neither is part of this program
 int devdec_load_text(svx_devdec*, int, const uint8_t*, size_t, bool, int, int, int64_t, uint64_t*, int64_t*) { return SVX_E_STATE; }
 void devdec_sam_stats(const svx_devdec*, svx_sam_stats* out) { memset(out, 0, sizeof *out); }
