@@ -810,6 +810,33 @@ int  svx_bam_sort_spill_host(const uint8_t* records, int64_t n_bytes, int32_t n_
 /* host-only: the header of the sorted file from a file's header (magic .. reference dictionary).  *n_out is the size also when cap is too small (SVX_E_CAPACITY) */
 int  svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out);
 
+/* ---- query-name order for the sort above: `samtools sort -N` (bamsort.hip: the k_ns_* kernels; the definition in words: svim_amd/bamsort.py) ----
+ * The order: records compare by (name, name_rank).  The name is the l_read_name bytes at body offset 32 cut at their first NUL (the whole field when it holds
+ * none); names compare as unsigned bytes, a proper prefix first.  name_rank = ((flag >> 6) & 3) << 2 | ((flag >> 11) & 1) << 1 | ((flag >> 8) & 1): READ1 /
+ * READ2 first, then primary < secondary < supplementary.  Equal keys keep file order.  The header gets SO:queryname and SS:queryname:lexicographical behind it
+ * (GO: and every other SS: field go).  This is the input of the query-name front end (svx_bam_read_batch mode 1): the records of a read lie next to each other.
+ * svx_bam_sort_begin_order(h, max_bytes, order): svx_bam_sort_begin is this call with SVX_SORT_COORDINATE; any other order than the two: SVX_E_ARG.  The pass,
+ * finish, count, encode, fetch, permutation, get_stats and abort are those above.  svx_bam_sort_finish refuses, besides what it refuses above, a record with
+ * l_read_name = 0 or 32 + l_read_name > block_size (SVX_E_ARG, which goes before SVX_E_RANGE).  The permutation comes from one stable 4-bit radix pass by
+ * name_rank and then most-significant-first rounds of 4 name bytes over the rows whose order is still open, at most 64 of them; a round costs the host one
+ * 8-byte read-back.  A query-name-sorted file has no index: svx_bam_sort_index and svx_bam_sort_index_fmt answer SVX_E_STATE after such a sort.
+ * Not built, and refused: a spilled query-name sort (svx_bam_sort_begin_spill is coordinate order; a query-name sort that passes max_bytes ends with
+ * SVX_E_CAPACITY as an in-memory coordinate sort does), a merge session in query-name order (svx_bam_merge_*), samtools' natural order (-n).
+ * svx_bam_sort_get_name_stats: valid after the finish of a query-name sort (zeros otherwise): rounds run, rows that took part in round r (active_rows[r],
+ * r < 64), their sum and maximum, and the host-clock times of the phases of finish with the stream drained at each edge. */
+#define SVX_SORT_COORDINATE 0
+#define SVX_SORT_QUERYNAME  1
+typedef struct svx_bam_name_sort_stats {
+    double  t_names_ms /* name extents, ranks and checks */, t_rank_ms /* the radix pass by name_rank */, t_rounds_ms, t_layout_ms;
+    int64_t n_records, word_bytes /* 4 */, rounds, active_total, active_max, active_rows[64];
+} svx_bam_name_sort_stats;
+int  svx_bam_sort_begin_order(svx_bam* h, int64_t max_bytes, int order);
+int  svx_bam_sort_get_name_stats(svx_bam* h, svx_bam_name_sort_stats* out);
+/* host-only, no GPU: svx_bam_sort_host and svx_bam_sort_header_host in the order asked for (they are these calls with SVX_SORT_COORDINATE); any other order
+ * than the two: SVX_E_ARG.  Query-name order adds the two refusals above to those of svx_bam_sort_host. */
+int  svx_bam_sort_host_order(const uint8_t* records, int64_t n_bytes, int32_t n_ref, int order, uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records);
+int  svx_bam_sort_header_host_order(const uint8_t* header, int64_t n_bytes, int order, uint8_t* out, int64_t cap, int64_t* n_out);
+
 /* ---- several files merged into one sorted file: the definition's host build (the definition in words: svim_amd/bammerge.py) ----
  * The merged dictionary is the first file's references, then file by file the names not yet present; tid_map[f][i] is the merged id of file f's reference i.
  * A record of a file whose map is the identity is copied verbatim; any other record gets refID and next_refID replaced by their mapped values (-1 stays -1),

@@ -298,6 +298,26 @@ class BamSortSpillStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+SORT_ORDERS = {"coordinate": 0, "queryname": 1}      # SVX_SORT_COORDINATE, SVX_SORT_QUERYNAME (svim_amd/bamsort.py)
+
+
+def sort_order(order):
+    if order not in SORT_ORDERS:
+        raise ValueError("order is 'coordinate' or 'queryname', not %r" % (order,))
+    return SORT_ORDERS[order]
+
+
+class BamNameSortStats(C.Structure):
+    """svx_bam_name_sort_stats: the permutation of a query-name sort (svx_bam_sort_begin_order); zeros after any other sort"""
+    _fields_ = [(n, C.c_double) for n in ("t_names_ms", "t_rank_ms", "t_rounds_ms", "t_layout_ms")] + \
+               [(n, C.c_int64) for n in ("n_records", "word_bytes", "rounds", "active_total", "active_max")] + [("active_rows", C.c_int64 * 64)]
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n != "active_rows"}
+        d["active_rows"] = list(self.active_rows)[:self.rounds]
+        return d
+
+
 class BamMergeStats(C.Structure):
     """svx_bam_merge_stats: a merge session (svx_bam_merge_*): its files, the merged dictionary, what k_bs_translate did"""
     _fields_ = [(n, C.c_int64) for n in ("n_files", "n_added", "n_ref_merged", "header_bytes", "n_translated_files", "n_translated_chunks", "n_translated_records",

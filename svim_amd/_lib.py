@@ -39,6 +39,7 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_bam_sort_begin", "svx_bam_sort_finish", "svx_bam_sort_abort", "svx_bam_sort_count", "svx_bam_sort_encode", "svx_bam_sort_fetch", "svx_bam_sort_index",
            "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host", "svx_bam_sort_begin_spill", "svx_bam_sort_get_spill_stats",
            "svx_bam_sort_spill_host",
+           "svx_bam_sort_begin_order", "svx_bam_sort_get_name_stats", "svx_bam_sort_host_order", "svx_bam_sort_header_host_order",
            "svx_bam_merge_header_host", "svx_bam_merge_host",
            "svx_bam_merge_open", "svx_bam_merge_add", "svx_bam_merge_finish", "svx_bam_merge_count", "svx_bam_merge_encode", "svx_bam_merge_fetch", "svx_bam_merge_index_fmt",
            "svx_bam_merge_index_count", "svx_bam_merge_index_fetch", "svx_bam_merge_permutation", "svx_bam_merge_get_stats", "svx_bam_merge_get_spill_stats",
@@ -236,17 +237,18 @@ def bam_index_host(n_ref, rows, v_end, fmt="bai"):
     return out[:n.value].tobytes()
 
 
-def bam_sort_host(records, n_ref):
-    """svx_bam_sort_host (host-only, no GPU needed): records in file order (bytes: block_size + body each) -> (the sorted record stream, the permutation as a
-    uint32 array) by the host build of csrc/bamsort_core.hpp - what NativeBam.sort_finish leaves on the device, and svim_amd.bamsort.sort_records by the
-    definition.  svim_amd.bamsort.BamSortError (code E_ARG / E_RANGE) for a stream the definition refuses."""
+def bam_sort_host(records, n_ref, order="coordinate"):
+    """svx_bam_sort_host_order (host-only, no GPU needed): records in file order (bytes: block_size + body each) -> (the sorted record stream, the permutation
+    as a uint32 array) by the host build of csrc/bamsort_core.hpp - what NativeBam.sort_finish leaves on the device, and svim_amd.bamsort.sort_records by the
+    definition.  order: "coordinate" or "queryname".  svim_amd.bamsort.BamSortError (code E_ARG / E_RANGE) for a stream the definition refuses."""
     from . import bamsort
+    which = _abi.sort_order(order)
     records = bytes(records)
     src = np.frombuffer(records, dtype=np.uint8) if records else np.zeros(1, np.uint8)
     out = np.zeros(max(1, len(records)), dtype=np.uint8)
     cap = len(records) // 36 + 1
     perm, n = np.zeros(cap, dtype=np.uint32), C.c_int64()
-    rc = lib().svx_bam_sort_host(ptr(src), C.c_int64(len(records)), C.c_int32(int(n_ref)), ptr(out), ptr(perm), C.c_int64(cap), C.byref(n))
+    rc = lib().svx_bam_sort_host_order(ptr(src), C.c_int64(len(records)), C.c_int32(int(n_ref)), C.c_int(which), ptr(out), ptr(perm), C.c_int64(cap), C.byref(n))
     if rc in (_abi.SVX_E_ARG, _abi.SVX_E_RANGE):
         raise bamsort.BamSortError(rc, "bam_sort_host: " + _abi.ERRORS[rc])
     if rc != 0:
@@ -288,13 +290,14 @@ def bam_sort_spill_host(records, n_ref, run_ends, piece_blocks=4096, write=None,
     return out[:len(records)].tobytes(), perm[:n.value].copy()
 
 
-def bam_sort_header_host(header):
-    """svx_bam_sort_header_host (host-only): the header of the sorted file, as svim_amd.bamsort.sorted_header defines it"""
+def bam_sort_header_host(header, order="coordinate"):
+    """svx_bam_sort_header_host_order (host-only): the header of the sorted file in that order, as svim_amd.bamsort.sorted_header defines it"""
+    which = _abi.sort_order(order)
     header = bytes(header)
     src = np.frombuffer(header, dtype=np.uint8) if header else np.zeros(1, np.uint8)
     cap = len(header) + 64
     out, n = np.zeros(cap, dtype=np.uint8), C.c_int64()
-    rc = lib().svx_bam_sort_header_host(ptr(src), C.c_int64(len(header)), ptr(out), C.c_int64(cap), C.byref(n))
+    rc = lib().svx_bam_sort_header_host_order(ptr(src), C.c_int64(len(header)), C.c_int(which), ptr(out), C.c_int64(cap), C.byref(n))
     if rc != 0:
         raise SvxError("svx_bam_sort_header_host failed: %s" % _abi.ERRORS.get(rc, rc))
     return out[:n.value].tobytes()

@@ -159,15 +159,23 @@ class NativeBam(object):
         self.L.svx_bam_index_get_stats(self.h, C.byref(s))
         return s.as_dict()
 
-    def sort_begin(self, max_bytes=0, spill_dir=None):
+    def sort_begin(self, max_bytes=0, spill_dir=None, order="coordinate"):
         """the pass that follows keeps every record on the device to put the file into coordinate order (svx_bam_sort_begin; svim_amd/bamsort.py says what the
         sorted file is): device decode must be on, nothing read yet since open / rewind and no index pass on.  max_bytes: the most the records may take on the
         device (0: what is free); the read that would pass it raises with .code SVX_E_CAPACITY, the sort is dropped and the handle rewinds.  seek() and
         rewind() raise until sort_finish() or sort_abort().
         spill_dir: a directory the process can write to (svx_bam_sort_begin_spill).  The read that would pass max_bytes (0: what is free) then closes a run -
         sorted, written to one spill file there that is unlinked as soon as it is open - and goes on; only a chunk that alone passes the limit raises.
-        sort_finish() merges the runs; the file, its index and the permutation are those of the in-memory sort.  None: no spill file, the limit raises"""
-        if spill_dir is None:
+        sort_finish() merges the runs; the file, its index and the permutation are those of the in-memory sort.  None: no spill file, the limit raises.
+        order="queryname" (svx_bam_sort_begin_order): the sorted file is in query-name order, `samtools sort -N` - the input of the query-name front end.  It
+        sorts in memory only (with a spill_dir: ValueError) and has no index (sort_index() raises with .code SVX_E_STATE); sort_name_stats() says what the
+        rounds did"""
+        which = _abi.sort_order(order)
+        if which and spill_dir is not None:
+            raise ValueError("sort_begin: a spilled sort is in coordinate order (order='queryname' sorts in memory only)")
+        if which:
+            rc = self.L.svx_bam_sort_begin_order(self.h, C.c_int64(int(max_bytes)), C.c_int(which))
+        elif spill_dir is None:
             rc = self.L.svx_bam_sort_begin(self.h, C.c_int64(int(max_bytes)))
         else:
             rc = self.L.svx_bam_sort_begin_spill(self.h, C.c_int64(int(max_bytes)), os.fsencode(spill_dir))
@@ -242,6 +250,13 @@ class NativeBam(object):
         (svx_bam_sort_get_spill_stats); after a sort that spilled nothing: n_runs 1 (0 without records), spilled_bytes 0"""
         s = _abi.BamSortSpillStats()
         self.L.svx_bam_sort_get_spill_stats(self.h, C.byref(s))
+        return s.as_dict()
+
+    def sort_name_stats(self):
+        """the permutation of a query-name sort (svx_bam_sort_get_name_stats): rounds, the rows that took part in each ("active_rows"), their sum and maximum,
+        the times of the name pass, the rank pass, the rounds and the layout; zeros after a coordinate sort"""
+        s = _abi.BamNameSortStats()
+        self.L.svx_bam_sort_get_name_stats(self.h, C.byref(s))
         return s.as_dict()
 
     def sam_stats(self):

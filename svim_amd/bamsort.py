@@ -18,12 +18,25 @@ What the sorted file is:
   index       bai.build_index(*bai.rows_of_bam(file)): a record that starts at stream offset u has vbeg = (coff[u // 65280] << 16) | (u % 65280).
   spilled     a file whose records do not fit on the device is sorted in runs (svx_bam_sort_begin_spill): runs_of cuts the file into consecutive ranges and
               sorts each, merge_runs merges them with ties to the lower run - the same stream and permutation, whatever the cuts - and piece_cuts says which
-              contiguous range of every run a piece of the output needs.  The device and the host build (svx_bam_sort_spill_host) are held to these."""
+              contiguous range of every run a piece of the output needs.  The device and the host build (svx_bam_sort_spill_host) are held to these.
+
+Query-name order (order="queryname"; csrc/bamsort.hip: the k_ns_* kernels, csrc/bamsort_host.cpp: svx_bam_sort_host_order) - the input of SVIM's query-name
+front end, which needs the records of a read next to each other:
+  order       records are compared by name_key = (name_of(body), name_rank(flag)).  name_of is body[32 : 32 + l_read_name] cut at its first NUL (the whole
+              range when it holds none); names compare as unsigned bytes and a proper prefix sorts first.  name_rank puts the READ1 / READ2 bits first, then
+              primary < secondary < supplementary.  Equal keys keep their file order.  This is the lexicographic order samtools calls `-N` (its `-n` is a
+              natural order that compares runs of digits as numbers: not this one); samtools is not at hand here and byte identity with its output is not claimed.
+  refusals    those above, and E_ARG for l_read_name = 0 and for a name field that runs past the record (32 + l_read_name > block_size).  E_ARG before E_RANGE.
+  header      the same rule with SO:queryname; GO: and every SS: field are removed and SS:queryname:lexicographical is put behind the (first) SO: field.  A
+              text without an @HD line gets "@HD\tVN:1.6\tSO:queryname\tSS:queryname:lexicographical\n" in front.
+  stream, file  as above.  A query-name-sorted file has no index, and spilled sorts and merges stay in coordinate order."""
 import struct
 
 E_ARG, E_RANGE = -3, -10
 BLOCK = 65280
 _NEW_HD = b"@HD\tVN:1.6\tSO:coordinate\n"
+ORDERS = ("coordinate", "queryname")
+_SS_NAME = b"SS:queryname:lexicographical"
 
 
 class BamSortError(ValueError):
@@ -41,6 +54,29 @@ def sort_key(body):
     return (ref_id & 0xffffffff, (pos + 1) & 0xffffffff, flag & 16)
 
 
+def name_of(body):
+    """the read name of a record: the bytes of its name field in front of the first NUL"""
+    field = bytes(body[32:32 + body[8]])
+    nul = field.find(b"\0")
+    return field if nul < 0 else field[:nul]
+
+
+def name_rank(flag):
+    """READ1 / READ2 first, then primary < secondary < supplementary"""
+    return ((flag >> 6) & 3) << 2 | ((flag >> 11) & 1) << 1 | ((flag >> 8) & 1)
+
+
+def name_key(body):
+    """body: the bytes of one record behind its block_size field -> its place in query-name order (bytes compare as unsigned, a proper prefix first)"""
+    return (name_of(body), name_rank(struct.unpack_from("<H", body, 14)[0]))
+
+
+def _order(order):
+    if order not in ORDERS:
+        raise ValueError("order is %r or %r" % ORDERS)
+    return order == "queryname"
+
+
 def split_header(raw):
     """raw: the inflated bytes of a BAM file -> (header bytes, n_ref, offset of the first record)"""
     if raw[:4] != b"BAM\1":
@@ -53,8 +89,10 @@ def split_header(raw):
     return raw[:p], n_ref, p
 
 
-def sorted_header(header):
+def sorted_header(header, order="coordinate"):
     """the header of the sorted file (see above)"""
+    by_name = _order(order)
+    so = b"SO:queryname" if by_name else b"SO:coordinate"
     header = bytes(header)
     if header[:4] != b"BAM\1":
         raise ValueError("not a BAM header")
@@ -71,18 +109,24 @@ def sorted_header(header):
             if f.startswith(b"GO:") or f.startswith(b"SS:"):
                 continue
             if f.startswith(b"SO:"):
-                f, seen = b"SO:coordinate", True
+                fields.append(so)
+                if by_name and not seen:
+                    fields.append(_SS_NAME)
+                seen = True
+                continue
             fields.append(f)
         if not seen:
-            fields.append(b"SO:coordinate")
+            fields += [so, _SS_NAME] if by_name else [so]
         text = b"\t".join([b"@HD"] + fields) + tail
     else:
-        text = _NEW_HD + text
+        text = (b"@HD\tVN:1.6\t" + so + b"\t" + _SS_NAME + b"\n" if by_name else _NEW_HD) + text
     return b"BAM\1" + struct.pack("<i", len(text)) + text + rest
 
 
-def split_records(stream, n_ref):
-    """stream: records in file order (block_size + body each) -> list of their byte strings; BamSortError for what the definition refuses"""
+def split_records(stream, n_ref, order="coordinate"):
+    """stream: records in file order (block_size + body each) -> list of their byte strings; BamSortError for what the definition refuses (query-name order
+    refuses a record without a name field or with one that runs past the record as well)"""
+    by_name = _order(order)
     stream = bytes(stream)
     out, p, bad_arg, bad_range = [], 0, False, False
     while p < len(stream):
@@ -95,25 +139,27 @@ def split_records(stream, n_ref):
             raise BamSortError(E_ARG, "the stream ends inside a record")
         ref_id, pos = struct.unpack_from("<ii", stream, p + 4)
         bad_arg |= ref_id < -1 or ref_id >= n_ref
+        bad_arg |= by_name and (stream[p + 12] == 0 or 32 + stream[p + 12] > size)
         bad_range |= pos < -1
         out.append(stream[p:p + 4 + size])
         p += 4 + size
     if bad_arg:
-        raise BamSortError(E_ARG, "a record names a reference the header does not have")
+        raise BamSortError(E_ARG, "a record names a reference the header does not have" + (", has no name field or one that runs past its end" if by_name else ""))
     if bad_range:
         raise BamSortError(E_RANGE, "a record has a position below -1")
     return out
 
 
-def permutation(recs):
+def permutation(recs, order="coordinate"):
     """the file index of every record of the sorted order (stable)"""
-    return sorted(range(len(recs)), key=lambda k: sort_key(recs[k][4:]))
+    key = name_key if _order(order) else sort_key
+    return sorted(range(len(recs)), key=lambda k: key(recs[k][4:]))
 
 
-def sort_records(stream, n_ref):
+def sort_records(stream, n_ref, order="coordinate"):
     """-> (the sorted record stream, the permutation)"""
-    recs = split_records(stream, n_ref)
-    perm = permutation(recs)
+    recs = split_records(stream, n_ref, order)
+    perm = permutation(recs, order)
     return b"".join(recs[k] for k in perm), perm
 
 
@@ -183,11 +229,11 @@ def inflate(path):
         return b"".join(b[2] for b in bgzf_blocks(fh.read()))
 
 
-def sorted_stream(path):
+def sorted_stream(path, order="coordinate"):
     """the inflated bytes of the sorted file of the BAM file at `path`"""
     raw = inflate(path)
     header, n_ref, at = split_header(raw)
-    return sorted_header(header) + sort_records(raw[at:], n_ref)[0]
+    return sorted_header(header, order) + sort_records(raw[at:], n_ref, order)[0]
 
 
 def n_blocks(stream_bytes):
@@ -195,7 +241,7 @@ def n_blocks(stream_bytes):
     return (stream_bytes + BLOCK - 1) // BLOCK + 1
 
 
-def file(path):
+def file(path, order="coordinate"):
     """the bytes of the sorted file (the library's host build of the encoder compresses the stream: no GPU)"""
     from ._lib import text_gz_host
-    return text_gz_host(sorted_stream(path))
+    return text_gz_host(sorted_stream(path, order))

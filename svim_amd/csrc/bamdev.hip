@@ -1066,9 +1066,9 @@ void devdec_feed_clear(svx_devdec* d) { d->feed = nullptr; d->feed_map = nullptr
 bool devdec_feed_on(const svx_devdec* d) { return d->feed != nullptr; }
 int devdec_device(const svx_devdec* d) { return d->device; }
 
-int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir) {
+int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir, int order) {
     HIPCHK(hipSetDevice(d->device));
-    SVXCHK(bamsort_begin(&d->sort, max_bytes, d->n_ref, spill_dir));
+    SVXCHK(bamsort_begin(&d->sort, max_bytes, d->n_ref, spill_dir, order));
     d->sort_on = true;
     return SVX_OK;
 }
@@ -1111,6 +1111,7 @@ int devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm) {
 }
 void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out) { bamsort_stats(d->sort, out); }
 void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out) { bamsort_spill_stats(d->sort, out); }
+void devdec_sort_name_stats(const svx_devdec* d, svx_bam_name_sort_stats* out) { bamsort_name_stats(d->sort, out); }
 
 int devdec_index_begin(svx_devdec* d) {
     HIPCHK(hipSetDevice(d->device));

@@ -209,6 +209,7 @@ struct svx_bam {
     size_t dev_fpos = 0; uint64_t dev_skip = 0; bool dev_file_done = false, dev_region_done = false;
     int dev_cur = -1; int64_t dev_first = 0, dev_valid = 0; bool dev_have_carry = false;
     size_t dev_data_end = 0; bool dev_eof_seen = false;      // file offset behind the last block with data the loader has walked; a read has returned 0 records at the end of the file
+    int sort_pass_order = 0;                                 // SVX_SORT_*: the order of the sort pass begun last (svx_bam_sort_begin_order), which picks the header svx_bam_sort_finish writes
     size_t dev_chunk_bytes = (size_t)8192 << 20, dev_chunk_blocks = (size_t)1 << 30;      // test hooks: SVX_BAM_DEV_CHUNK_MB, SVX_BAM_DEV_CHUNK_BLOCKS
     std::string dev_names_blob;
     struct DevLoad { int slot = 0, carry_slot = -1, rc = SVX_OK; std::string err; int64_t n_rec = 0, n_valid = 0; bool file_done = false, empty = false;
@@ -1292,20 +1293,22 @@ static int raw_header(svx_bam* h, std::vector<uint8_t>& out, const char* who = "
     out.resize(h->header_bytes);
     return SVX_OK;
 }
-static int sort_begin(svx_bam* h, int64_t max_bytes, const char* spill_dir) {
-    if (!h || max_bytes < 0) return bam_fail(SVX_E_ARG, "svx_bam_sort_begin: bad argument");
+static int sort_begin(svx_bam* h, int64_t max_bytes, const char* spill_dir, int order = SVX_SORT_COORDINATE) {
+    if (!h || max_bytes < 0 || (order != SVX_SORT_COORDINATE && order != SVX_SORT_QUERYNAME)) return bam_fail(SVX_E_ARG, "svx_bam_sort_begin: bad argument");
     if (!h->dev) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the sort is fed by the device reader's record stream (svx_bam_set_device_decode first)");
     if (devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin while a BAM index is being built (svx_bam_index_finish or svx_bam_index_abort first)");
     if (devdec_sort_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin during a sort pass");
     if (h->rg_on) return bam_fail(SVX_E_STATE, "svx_bam_sort_begin on a region read (svx_bam_seek_region): the pass runs over the whole file (rewind first)");
     if (h->dev_cur >= 0 || h->dev_prefetching || h->dev_file_done || h->dev_fpos != 0 || h->dev_skip != h->header_bytes)
         return bam_fail(SVX_E_STATE, "svx_bam_sort_begin: the handle is not at its first record (begin before the first read, or rewind first)");
-    const int rc = devdec_sort_begin(h->dev, max_bytes, spill_dir);
+    const int rc = devdec_sort_begin(h->dev, max_bytes, spill_dir, order);
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
     h->dev_eof_seen = false;
+    h->sort_pass_order = order;
     return SVX_OK;
 }
 extern "C" int svx_bam_sort_begin(svx_bam* h, int64_t max_bytes) { return sort_begin(h, max_bytes, nullptr); }
+extern "C" int svx_bam_sort_begin_order(svx_bam* h, int64_t max_bytes, int order) { return sort_begin(h, max_bytes, nullptr, order); }
 extern "C" int svx_bam_sort_begin_spill(svx_bam* h, int64_t max_bytes, const char* spill_dir) {
     if (!spill_dir) return bam_fail(SVX_E_ARG, "svx_bam_sort_begin_spill: no spill directory");
     return sort_begin(h, max_bytes, spill_dir);
@@ -1318,8 +1321,8 @@ extern "C" int svx_bam_sort_finish(svx_bam* h) {
     int rc = raw_header(h, raw);
     if (rc != SVX_OK) { devdec_sort_drop(h->dev); return rc; }
     int64_t n = 0;
-    rc = svx_bam_sort_header_host(raw.data(), (int64_t)raw.size(), nullptr, 0, &n);
-    if (rc == SVX_E_CAPACITY) { made.resize((size_t)n); rc = svx_bam_sort_header_host(raw.data(), (int64_t)raw.size(), made.data(), n, &n); }
+    rc = svx_bam_sort_header_host_order(raw.data(), (int64_t)raw.size(), h->sort_pass_order, nullptr, 0, &n);
+    if (rc == SVX_E_CAPACITY) { made.resize((size_t)n); rc = svx_bam_sort_header_host_order(raw.data(), (int64_t)raw.size(), h->sort_pass_order, made.data(), n, &n); }
     if (rc != SVX_OK) { devdec_sort_drop(h->dev); return bam_fail(rc, "svx_bam_sort_finish: the file's header cannot be rewritten"); }
     rc = devdec_sort_finish(h->dev, made.data(), (int64_t)made.size());
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
@@ -1372,6 +1375,11 @@ extern "C" int svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out) {
     return SVX_OK;
 }
 
+extern "C" int svx_bam_sort_get_name_stats(svx_bam* h, svx_bam_name_sort_stats* out) {
+    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
+    if (h->dev) devdec_sort_name_stats(h->dev, out); else memset(out, 0, sizeof *out);
+    return SVX_OK;
+}
 extern "C" int svx_bam_sort_get_spill_stats(svx_bam* h, svx_bam_sort_spill_stats* out) {
     if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
     if (h->dev) devdec_sort_spill_stats(h->dev, out); else memset(out, 0, sizeof *out);

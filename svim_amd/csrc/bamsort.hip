@@ -9,6 +9,7 @@
 //            not the merged one passes k_bs_translate first: refID and next_refID mapped, patched in the slab by byte stores, the merged id in a column of its own
 //   finish   the keys sorted stably (svx_sort_pairs_u64_on over the key's used bits) with the record number as payload = the permutation; k_bs_layout the
 //            segments of the output stream (the header, then the records in order) with their lengths and addresses; a scan gives every segment's offset
+//            In query-name order (svx_bam_sort_begin_order; in memory only) the permutation comes from the names instead: the k_ns_* kernels below
 //   encode   a range of 65 280-byte blocks: k_bs_gather lays the stream bytes of the range out in the piece buffer, then the encoder's phases over the piece
 //            (textgz_kernels.hpp: CRC, matches, codes, bits, compaction), every block's compressed size kept on the host
 //   index    the sorted rows with the virtual offsets the block sizes give, through bamindex.hip's phases (bamindex_take_rows, bamindex_finish)
@@ -48,6 +49,7 @@
 #define BS_SPILL_PIECE (32ll << 20)   /* bytes of a run's stream gathered and written at a time (a multiple of 16) */
 #define BS_PAD 64                     /* bytes behind a slab, the header and the piece: the aligned loads around a record's last bytes stay inside the allocation */
 static_assert(BSORT_BLOCK == DEF_BLOCK, "the output's blocks are the encoder's");
+static_assert(BSORT_NAME_MAX_ROUNDS <= 64, "svx_bam_name_sort_stats.active_rows holds every round");
 static_assert(BSORT_BLOCK % 16 == 0 && BS_TILE % 16 == 0, "a piece and its tiles start at aligned words of the destination");
 
 typedef unsigned int bs_u32x4 __attribute__((ext_vector_type(4)));
@@ -127,6 +129,67 @@ __global__ void k_bs_spill_layout(long long n, const uint32_t* gp, const uint32_
     perm[j - 1] = rfile[q];
     slen[j] = (int64_t)rlen[q]; srun[j] = (uint32_t)bsort_run_of(run_base, n_runs, (int64_t)q); sroff[j] = roff[q];
     gpos[q] = (uint32_t)(j - 1);
+}
+
+// ---- query-name order: the permutation ------------------------------------------------------------------------------------------------------------------
+// The key is (name, name_rank) (bamsort_core.hpp): a string of up to 255 bytes at any byte alignment in a slab, which no 64-bit radix key holds.  The order is
+// made least significant part first, then most significant word first:
+//   k_ns_names   a thread per record: l_read_name and the name's extent through addr[i] by byte loads (records are 4-byte aligned only by accident), the checks
+//                (BSORT_BAD_NAME), the name's length and name_rank as the key of the rank pass
+//   rank pass    one stable radix pass over the 4 bits of name_rank, payload the record number: perm = the records in (rank, file) order.  Every later sort is
+//                stable, so records whose names are equal stay in that order
+//   round r      over the ACTIVE rows only - the places of perm whose order is still open, in ascending place, each with the label of its segment (a maximal run
+//                of places whose names agree in every byte in front of 4 r; labels ascend with the place).  k_ns_keys: (label << 32) | the big-endian word of
+//                name bytes [4 r, 4 r + 4), zero-filled behind the name's end; one stable radix sort over 32 + ceil(log2(labels)) bits; the k-th sorted row
+//                goes to the k-th active place (a segment's rows are a contiguous range of the active list before and after the sort).  k_ns_heads: a row
+//                starts a new segment where its key differs from its neighbour's, and it stays active unless its segment has one member or its word's last
+//                byte is 0 - a name holds no NUL, so that name ended inside the word and every name of the segment is the same name; both flags go through ONE
+//                scan as the two halves of a 64-bit word.  k_ns_apply: perm written, the rows that stay compacted with their new labels
+//   end          the host reads the scan's last entry (8 bytes: rows that stay, segments) once per round; no rows left ends the rounds - after at most
+//                BSORT_NAME_MAX_ROUNDS = 64, the round in which a name of 255 bytes ends inside its word
+// A name that ends exactly at a word's edge stays active for one more round, where its word is 0 and sorts in front of every longer name: a proper prefix first.
+__global__ void k_ns_names(long long n, const uint64_t* addr, const uint32_t* len, uint8_t* name_len, uint64_t* rank, int* bad) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t* r = reinterpret_cast<const uint8_t*>(addr[i]);                 // (the whole record lies in its slab and holds its fixed fields: k_bs_rows saw to it)
+    const uint32_t l_name = r[BSORT_LNAME_AT];
+    const int b = bsort_name_check(l_name, len[i] - 4u);
+    if (b) atomicOr(bad, b);
+    name_len[i] = b ? (uint8_t)0 : (uint8_t)bsort_name_len(r + BSORT_NAME_AT, l_name);
+    rank[i] = bsort_name_rank((uint32_t)r[BSORT_FLAG_AT] | ((uint32_t)r[BSORT_FLAG_AT + 1] << 8));
+}
+// the m active rows of round r; place and seg null: round 0, every place active in one segment
+__global__ void k_ns_keys(long long m, uint32_t r, const uint32_t* perm, const uint32_t* place, const uint32_t* seg, const uint64_t* addr, const uint8_t* name_len, uint64_t* key,
+                          uint32_t* val) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const uint32_t rec = perm[place ? place[k] : (uint32_t)k];
+    const uint32_t w = bsort_name_word(reinterpret_cast<const uint8_t*>(addr[rec]) + BSORT_NAME_AT, name_len[rec], r);      // (reads nothing behind the name's end)
+    key[k] = ((uint64_t)(seg ? seg[k] : 0u) << 32) | w;
+    val[k] = rec;
+}
+// flags has m + 1 entries (the last one 0, so that the scan ends with the totals): bit 32 a segment starts here, bit 0 the row stays active
+__global__ void k_ns_heads(long long m, const uint64_t* key, int64_t* flags) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > m) return;
+    if (k == m) { flags[k] = 0; return; }
+    const uint64_t x = key[k];
+    const bool head = k == 0 || key[k - 1] != x, last = k == m - 1 || key[k + 1] != x;
+    const bool stays = !(head && last) && (x & 0xffull) != 0;
+    flags[k] = ((int64_t)head << 32) | (int64_t)stays;
+}
+// ex: the exclusive scan of flags.  The k-th sorted row goes to the k-th active place; the rows that stay are compacted, with the number of their segment
+__global__ void k_ns_apply(long long m, const uint32_t* val, const int64_t* flags, const int64_t* ex, const uint32_t* place, uint32_t* perm, uint32_t* place_out, uint32_t* seg_out) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const uint32_t at = place ? place[k] : (uint32_t)k;
+    perm[at] = val[k];
+    const uint64_t f = (uint64_t)flags[k], e = (uint64_t)ex[k];
+    if (f & 1ull) {
+        const uint32_t j = (uint32_t)e;                                           // (j <= k: rows that stay in front of this one)
+        place_out[j] = at;
+        seg_out[j] = (uint32_t)((e >> 32) + (f >> 32) - 1ull);                    // (segments started up to and including this row, less one)
+    }
 }
 
 // ---- the gather -----------------------------------------------------------------------------------------------------------------------------------------
@@ -267,11 +330,17 @@ struct BamSort {
     svx_bam_sort_spill_stats sp;
     // chunks of a merge (BamSortChunk::tid_map): the merged refID column of the chunk being appended, and what k_bs_translate has done since begin
     DevBuf xtid; hipEvent_t tr_ev[2] = {nullptr, nullptr}; int64_t tr_chunks = 0, tr_records = 0, tr_bytes = 0; double tr_ms = 0;
+    // query-name order (bamsort_begin with BSORT_QUERYNAME): the name lengths, the sorted payload, the active places and their segments (two of each: a round
+    // reads one and writes the other), the flags of a round and their scan; all of it goes back at the end of finish
+    int order = BSORT_COORDINATE;
+    DevBuf ns_len, ns_val, ns_place[2], ns_seg[2], ns_flags, ns_ex;
+    svx_bam_name_sort_stats ns;
 };
 static inline double bs_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir) {
-    if (max_bytes < 0 || n_ref < 0) return svx_fail(SVX_E_ARG, "BAM sort: bad argument", __FILE__, __LINE__, hipSuccess);
+int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir, int order) {
+    if (max_bytes < 0 || n_ref < 0 || (order != BSORT_COORDINATE && order != BSORT_QUERYNAME)) return svx_fail(SVX_E_ARG, "BAM sort: bad argument", __FILE__, __LINE__, hipSuccess);
+    if (order == BSORT_QUERYNAME && spill_dir) return svx_fail(SVX_E_ARG, "BAM sort: a spilled sort is in coordinate order (query-name order sorts in memory only)", __FILE__, __LINE__, hipSuccess);
     if (spill_dir) {
         struct stat sb;
         if (!*spill_dir || stat(spill_dir, &sb) != 0 || !S_ISDIR(sb.st_mode) || access(spill_dir, W_OK | X_OK) != 0)
@@ -280,11 +349,11 @@ int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spi
     if (!*s) *s = new BamSort();
     BamSort* S = *s;
     bamsort_drop(S);
-    S->n_ref = n_ref; S->max_bytes = max_bytes;
+    S->n_ref = n_ref; S->max_bytes = max_bytes; S->order = order;
     S->spill = spill_dir != nullptr; S->spill_dir = spill_dir ? spill_dir : "";
     S->spill_piece = BS_SPILL_PIECE;                         // test hook: SVX_BAM_SORT_SPILL_PIECE_KB, so that small runs leave in several pieces
     { const char* e = getenv("SVX_BAM_SORT_SPILL_PIECE_KB"); if (e && atoll(e) > 0 && atoll(e) <= (BS_SPILL_PIECE >> 10)) S->spill_piece = atoll(e) << 10; }
-    memset(&S->stats, 0, sizeof S->stats); memset(&S->sp, 0, sizeof S->sp);
+    memset(&S->stats, 0, sizeof S->stats); memset(&S->sp, 0, sizeof S->sp); memset(&S->ns, 0, sizeof S->ns);
     SVXCHK(bamindex_begin(&S->rows));
     SVXCHK(S->bad.reserve(64));
     HIPCHK(hipMemset(S->bad.p, 0, 64));
@@ -296,7 +365,8 @@ void bamsort_drop(BamSort* S) {
     S->slabs.clear(); S->arena_bytes = 0;
     DevBuf* all[] = {&S->key, &S->len, &S->addr, &S->key2, &S->val, &S->perm, &S->sort_tmp, &S->scan_tmp, &S->slen, &S->soff, &S->saddr, &S->hdr, &S->piece, &S->blocks, &S->crc, &S->tok,
                      &S->hist, &S->nt, &S->codes, &S->bsize, &S->coff, &S->kinds, &S->slots, &S->out, &S->coff_all,
-                     &S->rkey, &S->rlen, &S->rfile, &S->roff, &S->gp, &S->srun, &S->sroff, &S->gpos, &S->run_base, &S->run_bytes, &S->cuts, &S->stage_at, &S->stage};
+                     &S->rkey, &S->rlen, &S->rfile, &S->roff, &S->gp, &S->srun, &S->sroff, &S->gpos, &S->run_base, &S->run_bytes, &S->cuts, &S->stage_at, &S->stage,
+                     &S->ns_len, &S->ns_val, &S->ns_place[0], &S->ns_place[1], &S->ns_seg[0], &S->ns_seg[1], &S->ns_flags, &S->ns_ex};
     for (auto* b : all) b->release();
     if (S->fd >= 0) { (void)close(S->fd); S->fd = -1; }      // (unlinked when it was opened: its blocks go back now)
     S->runs.clear(); S->file_bytes = S->total_bytes = S->run_first = S->n_slabs_all = 0; S->rcap = 0;
@@ -485,6 +555,58 @@ static int bs_finish_spilled(BamSort* S, int64_t header_bytes, double t0, hipStr
     return SVX_OK;
 }
 
+// query-name order, in front of the sort: the names' extents, ranks and checks (k_ns_names); *bad gets BSORT_BAD_NAME.  The caller has refused BSORT_BAD_SIZE:
+// every record lies inside its slab and holds its fixed fields
+static int bs_name_extents(BamSort* S, int* bad, hipStream_t st) {
+    const int64_t n = S->n;
+    if (n == 0) return SVX_OK;
+    SVXCHK(S->ns_len.reserve((size_t)n));
+    k_ns_names<<<BS_GRID(n), BS_T, 0, st>>>(n, S->addr.as<uint64_t>(), S->len.as<uint32_t>(), S->ns_len.as<uint8_t>(), S->key.as<uint64_t>(), S->bad.as<int>());
+    HIPCHK(hipGetLastError());
+    SVXCHK(svx_d2h(bad, S->bad.p, 4, st));
+    return SVX_OK;
+}
+// the permutation of query-name order into S->perm (the kernels and the rounds: above); S->key holds the ranks
+static int bs_name_order(BamSort* S, double t0, hipStream_t st) {
+    const int64_t n = S->n;
+    svx_bam_name_sort_stats& X = S->ns;
+    if (n == 0) return SVX_OK;
+    SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4)); SVXCHK(S->ns_val.reserve((size_t)n * 4));
+    for (int k = 0; k < 2; k++) { SVXCHK(S->ns_place[k].reserve((size_t)n * 4)); SVXCHK(S->ns_seg[k].reserve((size_t)n * 4)); }
+    SVXCHK(S->ns_flags.reserve((size_t)(n + 1) * 8)); SVXCHK(S->ns_ex.reserve((size_t)(n + 1) * 8));
+    uint64_t *key = S->key.as<uint64_t>(), *key2 = S->key2.as<uint64_t>();
+    uint32_t *val = S->val.as<uint32_t>(), *val2 = S->ns_val.as<uint32_t>(), *perm = S->perm.as<uint32_t>();
+    k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, val);
+    SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, perm, n, 0, 4));
+    HIPCHK(hipStreamSynchronize(st));
+    const double t1 = bs_now();
+    X.t_rank_ms = (t1 - t0) * 1e3;
+    int64_t m = n > 1 ? n : 0, n_seg = 1;                    // the active rows and their segments; one record is in order
+    int cur = 0;
+    for (uint32_t r = 0; m > 0; r++, cur ^= 1) {
+        if (r >= BSORT_NAME_MAX_ROUNDS) return svx_fail(SVX_E_STATE, "BAM sort: names still open behind their last possible byte (internal error)", __FILE__, __LINE__, hipSuccess);
+        const uint32_t *place = r ? S->ns_place[cur].as<uint32_t>() : nullptr, *seg = r ? S->ns_seg[cur].as<uint32_t>() : nullptr;
+        k_ns_keys<<<BS_GRID(m), BS_T, 0, st>>>(m, r, perm, place, seg, S->addr.as<uint64_t>(), S->ns_len.as<uint8_t>(), key, val);
+        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, val2, m, 0, 32 + (n_seg > 1 ? svx_ceil_log2(n_seg) : 0)));
+        k_ns_heads<<<BS_GRID(m + 1), BS_T, 0, st>>>(m, key2, S->ns_flags.as<int64_t>());
+        SVXCHK((svx_exclusive_scan<int64_t, int64_t>(S->ns_flags.as<int64_t>(), S->ns_ex.as<int64_t>(), m + 1, st, S->scan_tmp)));
+        k_ns_apply<<<BS_GRID(m), BS_T, 0, st>>>(m, val2, S->ns_flags.as<int64_t>(), S->ns_ex.as<int64_t>(), place, perm, S->ns_place[cur ^ 1].as<uint32_t>(), S->ns_seg[cur ^ 1].as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        uint64_t totals = 0;                                 // the round's one read-back: rows that stay (low half), segments of this round (high half)
+        SVXCHK(svx_d2h(&totals, S->ns_ex.as<int64_t>() + m, 8, st));
+        X.active_rows[r] = m; X.active_total += m; X.active_max = std::max<int64_t>(X.active_max, m); X.rounds = (int64_t)r + 1;
+        const int64_t stay = (int64_t)(totals & 0xffffffffull);
+        n_seg = (int64_t)(totals >> 32);
+        if (stay > m || n_seg < 1 || n_seg > m) return svx_fail(SVX_E_STATE, "BAM sort: a round's totals are out of range (internal error)", __FILE__, __LINE__, hipSuccess);
+        m = stay;
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    X.t_rounds_ms = (bs_now() - t1) * 1e3;
+    DevBuf* done[] = {&S->ns_len, &S->ns_val, &S->ns_place[0], &S->ns_place[1], &S->ns_seg[0], &S->ns_seg[1], &S->ns_flags, &S->ns_ex};
+    for (auto* b : done) b->release();
+    return SVX_OK;
+}
+
 int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipStream_t st) {
     if (!S || S->finished || !header || header_bytes < 12) return svx_fail(SVX_E_ARG, "BAM sort: bad argument", __FILE__, __LINE__, hipSuccess);
     const int64_t n = S->n;
@@ -495,13 +617,21 @@ int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipS
     SVXCHK(svx_d2h(&bad, S->bad.p, 4, st));
     if (bad & BSORT_BAD_MATE) return svx_fail(SVX_E_ARG, "BAM merge: a record of a file whose ids are translated names a mate reference its header does not have", __FILE__, __LINE__, hipSuccess);
     if (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID)) return svx_fail(SVX_E_ARG, "BAM sort: a record names a reference the header does not have, or is shorter than its fixed fields", __FILE__, __LINE__, hipSuccess);
+    const bool by_name = S->order == BSORT_QUERYNAME;
+    double t_names = t0;
+    if (by_name) {                                           // (the names' checks are SVX_E_ARG, which goes before SVX_E_RANGE)
+        SVXCHK(bs_name_extents(S, &bad, st));
+        t_names = bs_now();
+        if (bad & BSORT_BAD_NAME) return svx_fail(SVX_E_ARG, "BAM sort: a record has no name field, or one that runs past the record's end (query-name order)", __FILE__, __LINE__, hipSuccess);
+    }
     if (bad & BSORT_BAD_POS) return svx_fail(SVX_E_RANGE, "BAM sort: a record has a position below -1", __FILE__, __LINE__, hipSuccess);
     SVXCHK(S->hdr.reserve((size_t)header_bytes + BS_PAD));
     HIPCHK(hipMemsetAsync((uint8_t*)S->hdr.p + header_bytes, 0, BS_PAD, st));
     SVXCHK(svx_h2d(S->hdr.p, header, (size_t)header_bytes, st));
     SVXCHK(S->perm.reserve((size_t)(n + 1) * 4));
     if (!S->runs.empty()) return bs_finish_spilled(S, header_bytes, t0, st);      // (no run was closed: exactly the in-memory path, no file)
-    if (n > 0) {
+    if (by_name) SVXCHK(bs_name_order(S, t_names, st));
+    else if (n > 0) {
         SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4));
         k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, S->val.as<uint32_t>());
         SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->key.as<uint64_t>(), S->key2.as<uint64_t>(), S->val.as<uint32_t>(), S->perm.as<uint32_t>(), n, 0, bsort_key_bits(S->n_ref)));
@@ -520,12 +650,13 @@ int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipS
     S->key.release(); S->key2.release(); S->val.release(); S->len.release(); S->addr.release(); S->slen.release(); S->sort_tmp.release();
     S->cap = 0;
     const double t2 = bs_now();
+    if (by_name) { S->ns.t_names_ms = (t_names - t0) * 1e3; S->ns.t_layout_ms = (t2 - t1) * 1e3; S->ns.n_records = n; S->ns.word_bytes = BSORT_NAME_WORD; }
     S->stream_bytes = total; S->n_blocks = (total + BSORT_BLOCK - 1) / BSORT_BLOCK + 1; S->next_block = 0; S->broken = false;
     S->h_csize.assign((size_t)S->n_blocks, 0);
     S->finished = true;
     S->stats.t_append_ms = S->t_append * 1e3; S->stats.t_sort_ms = (t1 - t0) * 1e3; S->stats.t_layout_ms = (t2 - t1) * 1e3; S->stats.t_finish_ms = (t2 - t0) * 1e3;
     S->stats.n_records = n; S->stats.n_slabs = (int64_t)S->slabs.size(); S->stats.arena_bytes = S->arena_bytes; S->stats.stream_bytes = total; S->stats.n_blocks = S->n_blocks;
-    S->stats.key_bits = bsort_key_bits(S->n_ref);
+    S->stats.key_bits = by_name ? 0 : bsort_key_bits(S->n_ref);
     S->sp.n_runs = n > 0 ? 1 : 0; S->sp.max_run_bytes = S->arena_bytes;      // one run, resident
     return SVX_OK;
 }
@@ -714,6 +845,7 @@ int bamsort_fetch(BamSort* S, uint8_t* compressed_dst, uint8_t* stream_dst, hipS
 
 int bamsort_index(BamSort* S, BamIndex* ix, hipStream_t st, int fmt) {
     if (!S || !S->finished || !ix) return svx_fail(SVX_E_STATE, "svx_bam_sort_index before svx_bam_sort_finish", __FILE__, __LINE__, hipSuccess);
+    if (S->order == BSORT_QUERYNAME) return svx_fail(SVX_E_STATE, "svx_bam_sort_index: a query-name-sorted file has no index", __FILE__, __LINE__, hipSuccess);
     if (S->broken || S->next_block != S->n_blocks)
         return svx_fail(SVX_E_STATE, "svx_bam_sort_index: the file's blocks have not all been encoded in ascending, gap-free ranges", __FILE__, __LINE__, hipSuccess);
     const double t0 = bs_now();
@@ -739,6 +871,9 @@ void bamsort_spill_stats(const BamSort* S, svx_bam_sort_spill_stats* out) {
 }
 void bamsort_stats(const BamSort* S, svx_bam_sort_stats* out) {
     if (S) *out = S->stats; else memset(out, 0, sizeof *out);
+}
+void bamsort_name_stats(const BamSort* S, svx_bam_name_sort_stats* out) {
+    if (S) *out = S->ns; else memset(out, 0, sizeof *out);
 }
 void bamsort_translate_stats(const BamSort* S, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms) {
     *n_chunks = S ? S->tr_chunks : 0; *n_records = S ? S->tr_records : 0; *n_bytes = S ? S->tr_bytes : 0; *ms = S ? S->tr_ms : 0;

@@ -1,4 +1,4 @@
-// bamsort.hpp - internal interface between the device reader (bamdev.hip) and the coordinate sort it can feed from its record stream (bamsort.hip).
+// bamsort.hpp - internal interface between the device reader (bamdev.hip) and the sort (coordinate or query-name order) it can feed from its record stream (bamsort.hip).
 #pragma once
 #include "common.hpp"
 #include "bamindex.hpp"
@@ -16,7 +16,8 @@ struct BamSortChunk {
 };
 // an empty arena (the state is made on first use); max_bytes 0: what the device has free.  spill_dir (may be null): the directory of the spill file - a chunk
 // that would pass the limit then closes a run (sorted, laid out, written to the file, slabs freed) instead of failing; SVX_E_ARG: not a writable directory
-int  bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir = nullptr);
+// order: BSORT_COORDINATE or BSORT_QUERYNAME (bamsort_core.hpp); query-name order with a spill directory is SVX_E_ARG, and bamsort_index after it SVX_E_STATE
+int  bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir = nullptr, int order = 0);
 void bamsort_drop(BamSort* s);                                         // arena, rows and the encoder's buffers go back
 void bamsort_destroy(BamSort* s);
 // SVX_E_CAPACITY: the arena would pass max_bytes (nothing of the chunk is kept); with a spill directory only for a chunk that alone passes it.  SVX_E_IO: the spill file
@@ -32,5 +33,6 @@ int  bamsort_index(BamSort* s, BamIndex* ix, hipStream_t st, int fmt);
 int  bamsort_permutation(BamSort* s, uint32_t* host_perm, hipStream_t st);
 void bamsort_stats(const BamSort* s, svx_bam_sort_stats* out);
 void bamsort_spill_stats(const BamSort* s, svx_bam_sort_spill_stats* out);
+void bamsort_name_stats(const BamSort* s, svx_bam_name_sort_stats* out);      // zeros unless the last finish was in query-name order
 // what k_bs_translate has done for the sort since begin: chunks and records it ran over, the bytes it read and wrote, its time between events on the stream
 void bamsort_translate_stats(const BamSort* s, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms);

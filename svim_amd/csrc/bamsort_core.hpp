@@ -1,4 +1,4 @@
-// bamsort_core.hpp - the coordinate order of BAM records and the checks a record must pass before it is sorted: one source for the host build
+// bamsort_core.hpp - the coordinate order and the query-name order of BAM records and the checks a record must pass before it is sorted: one source for the host build
 // (bamsort_host.cpp: svx_bam_sort_host) and the kernels (bamsort.hip).  The rule in words: svim_amd/bamsort.py.
 #pragma once
 #include <stdint.h>
@@ -11,9 +11,15 @@
 
 #define BSORT_BLOCK 65280                    /* stream bytes per BGZF block of the output (deflate_core.hpp: DEF_BLOCK) */
 #define BSORT_MIN_BLOCK_SIZE 32u             /* the fixed fields of a record behind its block_size field */
-enum { BSORT_BAD_SIZE = 1, BSORT_BAD_TID = 2, BSORT_BAD_POS = 4, BSORT_BAD_MATE = 8 };
+enum { BSORT_BAD_SIZE = 1, BSORT_BAD_TID = 2, BSORT_BAD_POS = 4, BSORT_BAD_MATE = 8, BSORT_BAD_NAME = 16 };
 #define BSORT_REFID_AT 4u                    /* refID and next_refID of a record, counted from its block_size field (body offsets 0 and 20) */
 #define BSORT_MATE_AT 24u
+#define BSORT_LNAME_AT 12u                   /* l_read_name (one byte), the flag (two bytes) and the name field, counted the same way (body offsets 8, 14 and 32) */
+#define BSORT_FLAG_AT 18u
+#define BSORT_NAME_AT 36u
+#define BSORT_NAME_WORD 4u                   /* name bytes per round of the query-name sort */
+#define BSORT_COORDINATE 0                   /* the orders (include/svx.h: SVX_SORT_COORDINATE, SVX_SORT_QUERYNAME) */
+#define BSORT_QUERYNAME 1
 
 // what is wrong with a record (0: nothing)
 BSORT_FN int bsort_check(int32_t tid, int32_t pos, uint32_t block_size, int32_t n_ref) {
@@ -51,7 +57,33 @@ BSORT_FN int64_t bsort_run_of(const int64_t* run_base, int64_t n_runs, int64_t q
     return a;
 }
 // the status of a stream whose records showed the union `bad` of bsort_check and bsort_translate: SVX_E_ARG (-3) before SVX_E_RANGE (-10)
-BSORT_FN int bsort_status(int bad) { return (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID | BSORT_BAD_MATE)) ? -3 : (bad & BSORT_BAD_POS) ? -10 : 0; }
+BSORT_FN int bsort_status(int bad) { return (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID | BSORT_BAD_MATE | BSORT_BAD_NAME)) ? -3 : (bad & BSORT_BAD_POS) ? -10 : 0; }
+// ---- query-name order (svim_amd/bamsort.py: name_key) ----
+// The key is (name, name_rank); names compare as unsigned bytes, a proper prefix first; equal keys keep file order.
+// READ1 / READ2 first, then primary < secondary < supplementary: 4 bits
+BSORT_FN uint32_t bsort_name_rank(uint32_t flag) { return (((flag >> 6) & 3u) << 2) | (((flag >> 11) & 1u) << 1) | ((flag >> 8) & 1u); }
+// the name field: l_read_name bytes at BSORT_NAME_AT, counted from the block_size field; a record without one, or whose field runs past its end, is refused
+BSORT_FN int bsort_name_check(uint32_t l_read_name, uint32_t block_size) {
+    return l_read_name == 0u || BSORT_MIN_BLOCK_SIZE + l_read_name > block_size ? BSORT_BAD_NAME : 0;
+}
+// the name's length: the field cut at its first NUL (the whole field when it holds none) - at most 255
+BSORT_FN uint32_t bsort_name_len(const uint8_t* field, uint32_t l_read_name) {
+    uint32_t k = 0;
+    while (k < l_read_name && field[k] != 0) k++;
+    return k;
+}
+// name bytes [BSORT_NAME_WORD * r, BSORT_NAME_WORD * (r + 1)) as one big-endian word, zero-filled behind the name's end: words compare as the bytes do, and
+// since a name holds no NUL, a word whose LAST byte is 0 says that the name ended inside it - two names with that same word are the same name
+BSORT_FN uint32_t bsort_name_word(const uint8_t* field, uint32_t name_len, uint32_t r) {
+    uint32_t w = 0;
+    for (uint32_t k = 0; k < BSORT_NAME_WORD; k++) {
+        const uint32_t at = BSORT_NAME_WORD * r + k;
+        w = (w << 8) | (at < name_len ? (uint32_t)field[at] : 0u);
+    }
+    return w;
+}
+// rounds after which every name has ended inside a word: a name of 255 bytes ends inside word 63
+#define BSORT_NAME_MAX_ROUNDS ((255 + BSORT_NAME_WORD) / BSORT_NAME_WORD)
 // ---- the merge of several files (svim_amd/bammerge.py): the ids of a record of a file whose dictionary is not the merged one ----
 // (used by svx_bam_merge_host today; written for host and device alike, as everything in this file is)
 // map[i]: the merged id of the file's reference i (n_ref_file entries).  -1 stays -1.  A refID outside [-1, n_ref_file) is BSORT_BAD_TID, a next_refID outside

@@ -1,5 +1,6 @@
-// bamsort_host.cpp - svx_bam_sort_host and svx_bam_sort_header_host: the coordinate sort of a record stream and the header of the sorted file by the rule of
-// bamsort_core.hpp and svim_amd/bamsort.py, built for the host; no GPU involved.  The kernels of bamsort.hip write the same bytes and the same permutation:
+// bamsort_host.cpp - svx_bam_sort_host_order and svx_bam_sort_header_host_order (svx_bam_sort_host and svx_bam_sort_header_host are their coordinate case): the
+// sort of a record stream in coordinate or query-name order and the header of the sorted file by the rule of bamsort_core.hpp and svim_amd/bamsort.py, built
+// for the host; no GPU involved.  The kernels of bamsort.hip write the same bytes and the same permutation:
 // there the keys go through the radix sort and the records through a gather, here through std::stable_sort and memcpy.
 // svx_bam_merge_header_host and svx_bam_merge_host: the same for several files merged into one (svim_amd/bammerge.py; bsort_translate).
 #include "bamsort_core.hpp"
@@ -12,10 +13,13 @@
 static inline uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 static inline void wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
 
-extern "C" int svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_t n_ref, uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records) {
-    if (n_bytes < 0 || n_ref < 0 || perm_cap < 0 || (n_bytes && !records) || !n_records) return SVX_E_ARG;
+// order SVX_SORT_QUERYNAME: a row's key is the name's rank, and the name lies at records + at + BSORT_NAME_AT, name_len bytes long (bamsort_core.hpp); names
+// compare as unsigned bytes (memcmp), a proper prefix first, then the rank; equal keys keep file order (the sort is stable)
+extern "C" int svx_bam_sort_host_order(const uint8_t* records, int64_t n_bytes, int32_t n_ref, int which, uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records) {
+    if (n_bytes < 0 || n_ref < 0 || perm_cap < 0 || (n_bytes && !records) || !n_records || (which != SVX_SORT_COORDINATE && which != SVX_SORT_QUERYNAME)) return SVX_E_ARG;
     *n_records = 0;
-    struct Row { uint64_t key; int64_t at; uint32_t len; };
+    const bool by_name = which == SVX_SORT_QUERYNAME;
+    struct Row { uint64_t key; int64_t at; uint32_t len, name_len; };
     std::vector<Row> rows;
     int bad = 0;
     for (int64_t p = 0; p < n_bytes;) {
@@ -25,7 +29,12 @@ extern "C" int svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_
         const int32_t tid = (int32_t)rd32(records + p + 4), pos = (int32_t)rd32(records + p + 8);
         const uint32_t flag = rd32(records + p + 16) >> 16;
         bad |= bsort_check(tid, pos, bs, n_ref);
-        rows.push_back(Row{bsort_key(tid, pos, flag, n_ref), p, 4u + bs});
+        if (by_name) {
+            const uint32_t l_name = records[p + BSORT_LNAME_AT];
+            const int b = bsort_name_check(l_name, bs);
+            bad |= b;
+            rows.push_back(Row{bsort_name_rank(flag), p, 4u + bs, b ? 0u : bsort_name_len(records + p + BSORT_NAME_AT, l_name)});
+        } else rows.push_back(Row{bsort_key(tid, pos, flag, n_ref), p, 4u + bs, 0u});
         p += 4 + (int64_t)bs;
     }
     if (bad) return bsort_status(bad);
@@ -34,7 +43,15 @@ extern "C" int svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_
     if (perm && (int64_t)rows.size() > perm_cap) return SVX_E_CAPACITY;
     std::vector<uint32_t> order(rows.size());
     for (size_t k = 0; k < order.size(); k++) order[k] = (uint32_t)k;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].key < rows[b].key; });
+    if (by_name)
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+            const Row &x = rows[a], &y = rows[b];
+            const int c = memcmp(records + x.at + BSORT_NAME_AT, records + y.at + BSORT_NAME_AT, std::min(x.name_len, y.name_len));
+            if (c != 0) return c < 0;
+            if (x.name_len != y.name_len) return x.name_len < y.name_len;
+            return x.key < y.key;
+        });
+    else std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].key < rows[b].key; });
     int64_t at = 0;
     for (size_t k = 0; k < order.size(); k++) {
         const Row& r = rows[order[k]];
@@ -43,6 +60,9 @@ extern "C" int svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_
         at += r.len;
     }
     return SVX_OK;
+}
+extern "C" int svx_bam_sort_host(const uint8_t* records, int64_t n_bytes, int32_t n_ref, uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records) {
+    return svx_bam_sort_host_order(records, n_bytes, n_ref, SVX_SORT_COORDINATE, out, perm, perm_cap, n_records);
 }
 
 // The spilled sort as bamsort.hip does it, on the host: every run sorted stably and written to a run file, one stable sort over the run-sorted keys (ties: run,
@@ -146,8 +166,11 @@ extern "C" int svx_bam_sort_spill_host(const uint8_t* records, int64_t n_bytes, 
 }
 
 // header: magic, l_text, text, n_ref, the reference dictionary (the inflated file up to its first record)
-extern "C" int svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out) {
-    if (!header || n_bytes < 12 || cap < 0 || (cap && !out) || !n_out || memcmp(header, "BAM\1", 4) != 0) return SVX_E_ARG;
+// order SVX_SORT_QUERYNAME: SO:queryname, and SS:queryname:lexicographical behind the first SO: field (every other SS: field goes, as in coordinate order)
+extern "C" int svx_bam_sort_header_host_order(const uint8_t* header, int64_t n_bytes, int order, uint8_t* out, int64_t cap, int64_t* n_out) {
+    if (!header || n_bytes < 12 || cap < 0 || (cap && !out) || !n_out || memcmp(header, "BAM\1", 4) != 0 || (order != SVX_SORT_COORDINATE && order != SVX_SORT_QUERYNAME)) return SVX_E_ARG;
+    const bool by_name = order == SVX_SORT_QUERYNAME;
+    const std::string so = by_name ? "SO:queryname" : "SO:coordinate", ss = by_name ? "\tSS:queryname:lexicographical" : "";
     *n_out = 0;
     const uint32_t l_text = rd32(header + 4);
     if ((int64_t)l_text > n_bytes - 12) return SVX_E_ARG;
@@ -165,13 +188,13 @@ extern "C" int svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, 
             const std::string f = line.substr(a, b - a);
             if (f.compare(0, 3, "GO:") != 0 && f.compare(0, 3, "SS:") != 0) {
                 made += '\t';
-                if (f.compare(0, 3, "SO:") == 0) { made += "SO:coordinate"; seen = true; } else made += f;
+                if (f.compare(0, 3, "SO:") == 0) { made += so; if (!seen) made += ss; seen = true; } else made += f;
             }
             a = b + 1;
         }
-        if (!seen) made += "\tSO:coordinate";
+        if (!seen) made += "\t" + so + ss;
         text = made + tail;
-    } else text = "@HD\tVN:1.6\tSO:coordinate\n" + text;
+    } else text = "@HD\tVN:1.6\t" + so + ss + "\n" + text;
     const int64_t rest = n_bytes - 8 - (int64_t)l_text, total = 8 + (int64_t)text.size() + rest;
     *n_out = total;
     if (total > cap) return SVX_E_CAPACITY;
@@ -180,6 +203,9 @@ extern "C" int svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, 
     memcpy(out + 8, text.data(), text.size());
     memcpy(out + 8 + text.size(), header + 8 + l_text, (size_t)rest);
     return SVX_OK;
+}
+extern "C" int svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* out, int64_t cap, int64_t* n_out) {
+    return svx_bam_sort_header_host_order(header, n_bytes, SVX_SORT_COORDINATE, out, cap, n_out);
 }
 
 // ---- the merge of several files (svim_amd/bammerge.py) ------------------------------------------------------------------------------------------------------

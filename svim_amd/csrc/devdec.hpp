@@ -56,7 +56,7 @@ void devdec_index_stats(const svx_devdec* d, svx_bam_index_stats* out);
 // rows of the records it hands to devdec_count (once per chunk, on the loader's stream); a load whose records pass max_bytes fails with SVX_E_CAPACITY and drops
 // the sort.  finish (header: the rewritten header): appending is over, the sorted order and the stream layout stay until drop or the next begin.  encode / fetch /
 // index / permutation need a finished sort; index leaves its bytes where devdec_index_bytes / devdec_index_fetch read them.
-int  devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir /* null: no spill file, SVX_E_CAPACITY at the limit */);
+int  devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir /* null: no spill file, SVX_E_CAPACITY at the limit */, int order = 0 /* SVX_SORT_* */);
 void devdec_sort_drop(svx_devdec* d);
 bool devdec_sort_on(const svx_devdec* d);               // appending
 bool devdec_sort_finished(const svx_devdec* d);
@@ -68,6 +68,7 @@ int  devdec_sort_index(svx_devdec* d, int fmt);
 int  devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm);
 void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out);
 void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out);
+void devdec_sort_name_stats(const svx_devdec* d, svx_bam_name_sort_stats* out);
 // A merge session's feed (svx_bam_merge_add; bammerge.hip): while set, every devdec_load appends the records it hands to devdec_count to the SESSION's sort -
 // in this decoder's loader thread but on the SESSION's stream (session_stream: a hipStream_t), once the decoder's own stream has been drained - as records of a
 // file with n_ref_file references whose ids dev_map (device memory of the session; unused when `identity`) takes into the merged dictionary.  Every command that

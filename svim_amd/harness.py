@@ -868,24 +868,42 @@ def _write_bam_index(path, data, fmt):
             fh.write(data)
 
 
-def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None, index_format="bai"):
+_DEFAULT = object()      # sort_bam / sam_to_bam: an argument the caller did not give (index=True and index_format="bai" are then what they always were)
+
+
+def sort_bam(path, out, device=0, index=_DEFAULT, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None, index_format=_DEFAULT, order="coordinate"):
     """The BAM file (or the SAM text: NativeBam tells them apart) at `path`, in any order, written to `out` in coordinate order (svim_amd/bamsort.py says what the sorted file is), and its index to
     out + ".bai" when `index`: one pass of the device reader whose batches are read and discarded while every record stays on the device, a sort there, then
     the file encoded and written in pieces of piece_blocks BGZF blocks - the whole file is never held in host memory (NativeBam.sort_*).  max_bytes: the most
     the records may take on the device (0: what is free).  spill_dir: a directory for the spill file of a file whose records pass that limit (runs are
     written there and merged: the same bytes; the file is unlinked while it is open, nothing is left behind) - None: such a file raises with SVX_E_CAPACITY.
     index_format="csi": out + ".csi" instead (svim_amd/csi.py), "auto": that when a reference length of the header exceeds 2^29.
+    order="queryname": the file in query-name order (`samtools sort -N`; svim_amd/bamsort.py), the input of the query-name front end.  Such a file has no
+    index: none is written when `index` is left at its default, index=True or an index_format given by the caller is a ValueError, and so is a spill_dir
+    (query-name order sorts in memory only).  The stats then carry the rounds under "name".
     -> the sort's stats, the spill's under "spill".  On failure the partial output is removed and the sort given up;
     svim_amd.bamsort.BamSortError carries the library's status in .code."""
     from .bamio import NativeBam
+    from . import _abi
     if piece_blocks < 1:
         raise ValueError("sort_bam: piece_blocks must be at least 1")
+    by_name = bool(_abi.sort_order(order))
+    if by_name:
+        if index_format is not _DEFAULT:
+            raise ValueError("sort_bam: a query-name-sorted file has no index (index_format with order='queryname')")
+        if index is not _DEFAULT and index:
+            raise ValueError("sort_bam: a query-name-sorted file has no index (index=True with order='queryname')")
+        if spill_dir is not None:
+            raise ValueError("sort_bam: a spilled sort is in coordinate order (spill_dir with order='queryname')")
+        index = False
+    index = True if index is _DEFAULT else index
+    index_format = "bai" if index_format is _DEFAULT else index_format
     bam = NativeBam(path, threads=threads)
     written = []
     try:
         index_format = _bam_index_format(index_format, bam.lengths)
         bam.set_device_decode(int(device))
-        bam.sort_begin(max_bytes, spill_dir)
+        bam.sort_begin(max_bytes, spill_dir, order)
         try:
             while bam.read_batch(batch_records, 0, "coordinate")[1]:
                 pass
@@ -900,6 +918,8 @@ def sort_bam(path, out, device=0, index=True, piece_blocks=4096, max_bytes=0, th
                 _write_bam_index(out + "." + index_format, data, index_format)
             stats = bam.sort_stats()
             stats["spill"] = bam.sort_spill_stats()
+            if by_name:
+                stats["name"] = bam.sort_name_stats()
             if bam.is_sam:
                 stats["sam"] = bam.sam_stats()
         except BaseException:
@@ -975,21 +995,22 @@ def _merged_input(paths, merged_out, device, threads=0):
     return merged_out
 
 
-def sam_to_bam(sam, out_bam, sort=True, index=True, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None, index_format="bai"):
+def sam_to_bam(sam, out_bam, sort=True, index=_DEFAULT, device=0, piece_blocks=4096, max_bytes=0, threads=0, batch_records=200_000, spill_dir=None, index_format=_DEFAULT):
     """SAM text at `sam` -> a BAM file at `out_bam`: the reference's `samtools view -b | samtools sort` and `samtools index` (src/svim/SVIM_alignment.py).
     sort=True: one pass of the device reader, coordinate order and, with `index`, out_bam + ".bai" (sort_bam does it: svim_amd/sam.py says what the records are,
     svim_amd/bamsort.py what the sorted file is; spill_dir as there) -> the sort's stats with the front end's under "sam".
     sort=False: the records in file order under the header the text has; no index - a file in file order has none.  This route is the HOST's: the host build
     of the converter (svx_sam_convert_host) and of the encoder (svx_text_gz_host) write the bytes the device builds write, the file is held in host memory
-    once, and `device` and the sort's limits play no part -> {"n_records", "text_bytes", "stream_bytes"}."""
+    once, and `device` and the sort's limits play no part -> {"n_records", "text_bytes", "stream_bytes"}.
+    sort="queryname": the device route in query-name order (sort_bam(order="queryname"): no index; index=True or an index_format is a ValueError)."""
     from .bamio import is_sam_text
     from . import _lib, sam as samdef
     if not is_sam_text(sam):
         raise ValueError("sam_to_bam: %r is not SAM text" % sam)
     if sort:
         return sort_bam(sam, out_bam, device=device, index=index, piece_blocks=piece_blocks, max_bytes=max_bytes, threads=threads, batch_records=batch_records, spill_dir=spill_dir,
-                        index_format=index_format)
-    if index:
+                        index_format=index_format, order="queryname" if sort == "queryname" else "coordinate")
+    if index is _DEFAULT or index:
         raise ValueError("sam_to_bam: index=True needs sort=True (records in file order have no index)")
     with open(sam, "rb") as fh:
         text = fh.read()

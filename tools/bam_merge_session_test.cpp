@@ -160,7 +160,7 @@ void devdec_feed_set(svx_devdec* d, BamSort* sort, void*, const int32_t* map, in
 void devdec_feed_clear(svx_devdec* d) { if (d->feed) { model_alive(d->feed, "feed_clear"); d->feed->borrowers--; } d->feed = nullptr; d->feed_map = nullptr; }
 bool devdec_feed_on(const svx_devdec* d) { return d->feed != nullptr; }
 int devdec_device(const svx_devdec*) { return 0; }
-int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char*) { model_begin(&d->sort, max_bytes, (int32_t)d->rank.size()); d->sort_on = true; return SVX_OK; }
+int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char*, int) { model_begin(&d->sort, max_bytes, (int32_t)d->rank.size()); d->sort_on = true; return SVX_OK; }
 void devdec_sort_drop(svx_devdec* d) { d->sort_on = false; model_drop(d->sort); }
 bool devdec_sort_on(const svx_devdec* d) { return d->sort_on; }
 bool devdec_sort_finished(const svx_devdec* d) { return d->sort && model_alive(d->sort, "finished")->finished; }
@@ -172,6 +172,7 @@ int devdec_sort_index(svx_devdec*, int) { return SVX_E_STATE; }
 int devdec_sort_permutation(svx_devdec* d, uint32_t* perm) { return model_permutation(d->sort, perm); }
 void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
 void devdec_sort_spill_stats(const svx_devdec*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
+void devdec_sort_name_stats(const svx_devdec*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
 
 // ---- the session's device side (devdec.hpp: mergedev_*) ------------------------------------------------------------------------------------------------------
 struct MergeDev { uint32_t magic = MODEL_ALIVE; BamSort* sort = nullptr; std::vector<int32_t>* maps = nullptr; std::vector<uint8_t> index; bool have_index = false; };

@@ -160,7 +160,7 @@ int devdec_index_fetch(svx_devdec*, uint8_t*) { return SVX_E_STATE; }
 void devdec_index_stats(const svx_devdec*, svx_bam_index_stats* out) { memset(out, 0, sizeof *out); }
 #ifndef BAMIO_FUZZ_SORT_MODEL       /* (a program that defines it brings these itself, over a model of the sort, and links bamsort_host.cpp) */
 // (so is the coordinate sort; the header rewrite it asks the host for lives in bamsort_host.cpp, which this program does not link)
-int devdec_sort_begin(svx_devdec*, int64_t, const char*) { return SVX_E_STATE; }
+int devdec_sort_begin(svx_devdec*, int64_t, const char*, int) { return SVX_E_STATE; }
 void devdec_sort_drop(svx_devdec*) {}
 bool devdec_sort_on(const svx_devdec*) { return false; }
 bool devdec_sort_finished(const svx_devdec*) { return false; }
@@ -172,7 +172,9 @@ int devdec_sort_index(svx_devdec*, int) { return SVX_E_STATE; }
 int devdec_sort_permutation(svx_devdec*, uint32_t*) { return SVX_E_STATE; }
 void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
 void devdec_sort_spill_stats(const svx_devdec*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
+void devdec_sort_name_stats(const svx_devdec*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
 extern "C" int svx_bam_sort_header_host(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
+extern "C" int svx_bam_sort_header_host_order(const uint8_t*, int64_t, int, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
 // (and the merge session of several files, which is fed by that sort's appends)
 void devdec_feed_set(svx_devdec*, BamSort*, void*, const int32_t*, int32_t, bool) {}
 void devdec_feed_clear(svx_devdec*) {}
