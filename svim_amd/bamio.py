@@ -21,9 +21,73 @@ def is_sam_text(path):
     return head[:1] == b"@" or (len(head) > 0 and head != b"\x1f\x8b" and 0x21 <= head[0] <= 0x7e)
 
 
-class NativeBam(object):
+class _SortedOutput(object):
+    """What a finished sort on the device gives, written once for its two owners: a reader's own sort (NativeBam.sort_*: svx_bam_sort_*) and a merge session
+    (BamMerge: svx_bam_merge_*).  The owner brings L, h, _out_prefix - what the names of its C functions start with - and _out_error(rc, what), its error
+    factory; an owner whose handle may be gone overrides _out_open(what), and one that keeps its index elsewhere _out_index_bytes()."""
+    _out_prefix = None
+
+    def _out_open(self, what):
+        pass
+
+    def _out_call(self, name, *args):
+        what = self._out_prefix + name
+        self._out_open(what)
+        rc = getattr(self.L, what)(self.h, *args)
+        if rc != 0:
+            if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE) and name == "index_fmt":
+                from . import bai
+                raise bai.BaiError(rc, "%s failed: %s (%s)" % (what, _abi.ERRORS.get(rc, rc), self.L.svx_last_error().decode("utf-8", "replace")))
+            raise self._out_error(rc, what)
+
+    def _out_count(self):
+        n, nbytes, nb = C.c_int64(), C.c_int64(), C.c_int64()
+        self._out_call("count", C.byref(n), C.byref(nbytes), C.byref(nb))
+        return n.value, nbytes.value, nb.value
+
+    def _out_encode(self, first_block, n_blocks, stream=False):
+        n = C.c_int64()
+        self._out_call("encode", C.c_int64(int(first_block)), C.c_int64(int(n_blocks)), C.byref(n))
+        out = np.zeros(max(1, n.value), dtype=np.uint8)
+        raw, nraw = None, 0
+        if stream:
+            total = self._out_count()[1]
+            nraw = min(total, (int(first_block) + int(n_blocks)) * _abi.TEXT_GZ_BLOCK) - min(total, int(first_block) * _abi.TEXT_GZ_BLOCK)
+            raw = np.zeros(max(1, nraw), dtype=np.uint8)
+        self._out_call("fetch", out.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p) if stream else None)
+        return (out[:n.value].tobytes(), raw[:nraw].tobytes()) if stream else out[:n.value].tobytes()
+
+    def _out_index(self, fmt):
+        self._out_call("index_fmt", C.c_int(_abi.index_format(fmt, "bai")))
+        return self._out_index_bytes()
+
+    def _out_index_bytes(self):
+        n = C.c_int64()
+        self._out_call("index_count", C.byref(n))
+        out = np.zeros(max(1, n.value), dtype=np.uint8)
+        self._out_call("index_fetch", out.ctypes.data_as(C.c_void_p))
+        return out[:n.value].tobytes()
+
+    def _out_permutation(self):
+        n = self._out_count()[0]
+        perm = np.zeros(max(1, n), dtype=np.uint32)
+        self._out_call("permutation", perm.ctypes.data_as(C.c_void_p))
+        return perm[:n]
+
+    def _out_stats(self, name, struct, checked=True):
+        """checked=False: a reader's stats have never raised (zeros from a handle that is closed)"""
+        s = struct()
+        if checked:
+            self._out_call(name, C.byref(s))
+        else:
+            getattr(self.L, self._out_prefix + name)(self.h, C.byref(s))
+        return s.as_dict()
+
+
+class NativeBam(_SortedOutput):
     """BAM reader with the handful of pysam.AlignmentFile members SVIM's COLLECT driver uses (references, lengths,
     get_tid/getrname, header['HD']['SO']) plus read_batch(), which yields ready-made svx_batch structs."""
+    _out_prefix = "svx_bam_sort_"
 
     def __init__(self, path, threads=0):
         self.L = lib()
@@ -174,90 +238,54 @@ class NativeBam(object):
         if which and spill_dir is not None:
             raise ValueError("sort_begin: a spilled sort is in coordinate order (order='queryname' sorts in memory only)")
         if which:
-            rc = self.L.svx_bam_sort_begin_order(self.h, C.c_int64(int(max_bytes)), C.c_int(which))
+            self._out_call("begin_order", C.c_int64(int(max_bytes)), C.c_int(which))
         elif spill_dir is None:
-            rc = self.L.svx_bam_sort_begin(self.h, C.c_int64(int(max_bytes)))
+            self._out_call("begin", C.c_int64(int(max_bytes)))
         else:
-            rc = self.L.svx_bam_sort_begin_spill(self.h, C.c_int64(int(max_bytes)), os.fsencode(spill_dir))
-        if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_begin" if spill_dir is None else "svx_bam_sort_begin_spill")
+            self._out_call("begin_spill", C.c_int64(int(max_bytes)), os.fsencode(spill_dir))
 
     def sort_finish(self):
         """-> (records, bytes of the sorted stream, BGZF blocks of the sorted file), once read_batch has returned 0 records at the end of the file
         (svx_bam_sort_finish): the records are sorted and laid out; sort_encode() makes the file, piece by piece"""
-        rc = self.L.svx_bam_sort_finish(self.h)
-        if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_finish")
+        self._out_call("finish")
         return self.sort_count()
 
     def sort_count(self):
-        n, nbytes, nb = C.c_int64(), C.c_int64(), C.c_int64()
-        rc = self.L.svx_bam_sort_count(self.h, C.byref(n), C.byref(nbytes), C.byref(nb))
-        if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_count")
-        return n.value, nbytes.value, nb.value
+        return self._out_count()
 
     def sort_abort(self):
         """give the sort up at any point (svx_bam_sort_abort): the records on the device are dropped, seek() / rewind() work again"""
-        rc = self.L.svx_bam_sort_abort(self.h)
-        if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_abort")
+        self._out_call("abort")
 
     def sort_encode(self, first_block, n_blocks, stream=False):
         """blocks [first_block, first_block + n_blocks) of the sorted file (svx_bam_sort_encode / svx_bam_sort_fetch) -> their compressed bytes, or
         (compressed bytes, their stream bytes) with stream=True.  Ranges go in ascending order without gaps when sort_index() is to follow"""
-        n = C.c_int64()
-        rc = self.L.svx_bam_sort_encode(self.h, C.c_int64(int(first_block)), C.c_int64(int(n_blocks)), C.byref(n))
-        if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_encode")
-        out = np.zeros(max(1, n.value), dtype=np.uint8)
-        if stream:
-            total = self.sort_count()[1]
-            nraw = min(total, (int(first_block) + int(n_blocks)) * _abi.TEXT_GZ_BLOCK) - min(total, int(first_block) * _abi.TEXT_GZ_BLOCK)
-            raw = np.zeros(max(1, nraw), dtype=np.uint8)
-        rc = self.L.svx_bam_sort_fetch(self.h, out.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p) if stream else None)
-        if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_fetch")
-        return (out[:n.value].tobytes(), raw[:nraw].tobytes()) if stream else out[:n.value].tobytes()
+        return self._out_encode(first_block, n_blocks, stream)
 
     def sort_index(self, fmt="bai"):
-        """-> the bytes of the sorted file's .bai, after every block has been encoded (svx_bam_sort_index); svim_amd.bai.BaiError (E_RANGE) when a record
-        ends beyond 2^29.  fmt="csi": the uncompressed bytes of its .csi (svx_bam_sort_index_fmt), which has no such limit"""
-        if fmt == "bai":
-            rc = self.L.svx_bam_sort_index(self.h)
-        else:
-            rc = self.L.svx_bam_sort_index_fmt(self.h, C.c_int(_abi.index_format(fmt, "bai")))
-        if rc != 0:
-            raise (self._index_error if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE) else self._sort_error)(rc, "svx_bam_sort_index")
-        return self.index_bytes()
+        """-> the bytes of the sorted file's .bai, after every block has been encoded (svx_bam_sort_index_fmt); svim_amd.bai.BaiError (E_RANGE) when a record
+        ends beyond 2^29.  fmt="csi": the uncompressed bytes of its .csi, which has no such limit"""
+        return self._out_index(fmt)
+
+    def _out_index_bytes(self):
+        return self.index_bytes()                           # (the sorted file's index lies where an index pass of the reader leaves its own)
 
     def sort_permutation(self):
         """uint32 array: the file index of every record of the sorted order (svx_bam_sort_permutation)"""
-        n = self.sort_count()[0]
-        perm = np.zeros(max(1, n), dtype=np.uint32)
-        rc = self.L.svx_bam_sort_permutation(self.h, perm.ctypes.data_as(C.c_void_p))
-        if rc != 0:
-            raise self._sort_error(rc, "svx_bam_sort_permutation")
-        return perm[:n]
+        return self._out_permutation()
 
     def sort_stats(self):
-        s = _abi.BamSortStats()
-        self.L.svx_bam_sort_get_stats(self.h, C.byref(s))
-        return s.as_dict()
+        return self._out_stats("get_stats", _abi.BamSortStats, checked=False)
 
     def sort_spill_stats(self):
         """runs, bytes written to and read from the spill file, the largest chunk, run and staging buffer, the time spent spilling, reading back and merging
         (svx_bam_sort_get_spill_stats); after a sort that spilled nothing: n_runs 1 (0 without records), spilled_bytes 0"""
-        s = _abi.BamSortSpillStats()
-        self.L.svx_bam_sort_get_spill_stats(self.h, C.byref(s))
-        return s.as_dict()
+        return self._out_stats("get_spill_stats", _abi.BamSortSpillStats, checked=False)
 
     def sort_name_stats(self):
         """the permutation of a query-name sort (svx_bam_sort_get_name_stats): rounds, the rows that took part in each ("active_rows"), their sum and maximum,
         the times of the name pass, the rank pass, the rounds and the layout; zeros after a coordinate sort"""
-        s = _abi.BamNameSortStats()
-        self.L.svx_bam_sort_get_name_stats(self.h, C.byref(s))
-        return s.as_dict()
+        return self._out_stats("get_name_stats", _abi.BamNameSortStats, checked=False)
 
     def sam_stats(self):
         """what the SAM text front end has done for this handle (svx_sam_get_stats); zeros for a BAM file"""
@@ -265,7 +293,7 @@ class NativeBam(object):
         self.L.svx_sam_get_stats(self.h, C.byref(s))
         return s.as_dict()
 
-    def _sort_error(self, rc, what):
+    def _out_error(self, rc, what):
         from . import bamsort
         return bamsort.BamSortError(rc, "%s failed: %s (%s)" % (what, _abi.ERRORS.get(rc, rc), self.L.svx_last_error().decode("utf-8", "replace")))
 
@@ -380,7 +408,7 @@ class NativeBam(object):
             pass
 
 
-class BamMerge(object):
+class BamMerge(_SortedOutput):
     """A merge session on the device (svx_bam_merge_*; svim_amd/bammerge.py says what the merged file is): several files, in the order given, into one file in
     coordinate order.  The session owns its sort, its stream and its index; readers only feed it.
         m = BamMerge.open(readers, device=0)     # reads headers and dictionaries; keeps nothing of the readers, which may be closed at once
@@ -389,6 +417,7 @@ class BamMerge(object):
         m.encode(first_block, n_blocks) ...; m.index("bai"); m.permutation(); m.stats(); m.close()
     What the definition refuses - header clashes at open, records at finish - and the state rules are svim_amd.bammerge.BamMergeError with the library's status
     in .code; an add that fails (SVX_E_CAPACITY, SVX_E_IO) breaks the session: close() is all that is left, the reader works again after rewind()."""
+    _out_prefix = "svx_bam_merge_"
 
     def __init__(self, handle, L):
         self.h, self.L = handle, L
@@ -411,69 +440,43 @@ class BamMerge(object):
         from . import bammerge
         return bammerge.BamMergeError(rc, "%s failed: %s (%s)" % (what, _abi.ERRORS.get(rc, rc), L.svx_last_error().decode("utf-8", "replace")))
 
-    def _call(self, what, *args):
+    def _out_error(self, rc, what):
+        return self._error_of(self.L, rc, what)
+
+    def _out_open(self, what):
         if not self.h:
             raise self._error_of(self.L, _abi.SVX_E_STATE, what + " on a closed session")
-        rc = getattr(self.L, what)(self.h, *args)
-        if rc != 0:
-            if rc in (_abi.SVX_E_ORDER, _abi.SVX_E_RANGE) and what == "svx_bam_merge_index_fmt":
-                from . import bai
-                raise bai.BaiError(rc, "%s failed: %s (%s)" % (what, _abi.ERRORS.get(rc, rc), self.L.svx_last_error().decode("utf-8", "replace")))
-            raise self._error_of(self.L, rc, what)
 
     def add(self, reader):
         """the next file of the session: `reader` (a NativeBam with device decode on, at its first record) is read to its end inside this call"""
-        self._call("svx_bam_merge_add", reader.h)
+        self._out_call("add", reader.h)
 
     def finish(self):
         """-> (records, bytes of the merged stream, BGZF blocks of the merged file), once every file has been added"""
-        self._call("svx_bam_merge_finish")
+        self._out_call("finish")
         return self.count()
 
     def count(self):
-        n, nbytes, nb = C.c_int64(), C.c_int64(), C.c_int64()
-        self._call("svx_bam_merge_count", C.byref(n), C.byref(nbytes), C.byref(nb))
-        return n.value, nbytes.value, nb.value
+        return self._out_count()
 
     def encode(self, first_block, n_blocks, stream=False):
         """blocks [first_block, first_block + n_blocks) of the merged file -> their compressed bytes, or (compressed bytes, stream bytes) with stream=True;
         ascending ranges without gaps when index() is to follow"""
-        n = C.c_int64()
-        self._call("svx_bam_merge_encode", C.c_int64(int(first_block)), C.c_int64(int(n_blocks)), C.byref(n))
-        out = np.zeros(max(1, n.value), dtype=np.uint8)
-        raw, nraw = None, 0
-        if stream:
-            total = self.count()[1]
-            nraw = min(total, (int(first_block) + int(n_blocks)) * _abi.TEXT_GZ_BLOCK) - min(total, int(first_block) * _abi.TEXT_GZ_BLOCK)
-            raw = np.zeros(max(1, nraw), dtype=np.uint8)
-        self._call("svx_bam_merge_fetch", out.ctypes.data_as(C.c_void_p), raw.ctypes.data_as(C.c_void_p) if stream else None)
-        return (out[:n.value].tobytes(), raw[:nraw].tobytes()) if stream else out[:n.value].tobytes()
+        return self._out_encode(first_block, n_blocks, stream)
 
     def index(self, fmt="bai"):
         """-> the bytes of the merged file's .bai, or with fmt="csi" the uncompressed bytes of its .csi, after every block has been encoded; svim_amd.bai.BaiError
         (E_RANGE) when a record ends beyond 2^29 of a .bai"""
-        self._call("svx_bam_merge_index_fmt", C.c_int(_abi.index_format(fmt, "bai")))
-        n = C.c_int64()
-        self._call("svx_bam_merge_index_count", C.byref(n))
-        out = np.zeros(max(1, n.value), dtype=np.uint8)
-        self._call("svx_bam_merge_index_fetch", out.ctypes.data_as(C.c_void_p))
-        return out[:n.value].tobytes()
+        return self._out_index(fmt)
 
     def permutation(self):
         """uint32 array: for every record of the merged order its place in the concatenation of the files"""
-        n = self.count()[0]
-        perm = np.zeros(max(1, n), dtype=np.uint32)
-        self._call("svx_bam_merge_permutation", perm.ctypes.data_as(C.c_void_p))
-        return perm[:n]
+        return self._out_permutation()
 
     def stats(self):
         """the sort's stats (svx_bam_sort_stats), the spill's under "spill", the session's own under "merge" """
-        a, b, c = _abi.BamSortStats(), _abi.BamSortSpillStats(), _abi.BamMergeStats()
-        self._call("svx_bam_merge_get_stats", C.byref(a))
-        self._call("svx_bam_merge_get_spill_stats", C.byref(b))
-        self._call("svx_bam_merge_get_merge_stats", C.byref(c))
-        d = a.as_dict()
-        d["spill"], d["merge"] = b.as_dict(), c.as_dict()
+        d = self._out_stats("get_stats", _abi.BamSortStats)
+        d["spill"], d["merge"] = self._out_stats("get_spill_stats", _abi.BamSortSpillStats), self._out_stats("get_merge_stats", _abi.BamMergeStats)
         return d
 
     def close(self):

@@ -1,7 +1,7 @@
 """Several BAM files merged into one file in coordinate order: the definition the host build (csrc/bamsort_host.cpp: svx_bam_merge_header_host,
-svx_bam_merge_host, the id rule in csrc/bamsort_core.hpp: bsort_translate) is held against, and the one a device build will be held against (DESIGN section 35
-says why there is none yet).  Pure Python, no GPU, no library (only file() asks the library for the compressed bytes).  It stands on svim_amd/bamsort.py: the
-merge of one file IS the sort of that file.
+svx_bam_merge_host, the id rule in csrc/bamsort_core.hpp: bsort_translate) and the device build (a merge session: svx_bam_merge_*, bamio.BamMerge,
+csrc/bammerge.hip; DESIGN sections 35 and 38) are both held against.  Pure Python, no GPU, no library (only file() asks the library for the compressed bytes).
+It stands on svim_amd/bamsort.py: the merge of one file IS the sort of that file.
 
 What the merged file is:
   inputs      k >= 1 files in the order given, each the inflated bytes of a BAM file (SAM text: through the BAM header and records svim_amd/sam.py defines).

@@ -575,11 +575,11 @@ struct svx_devdec {
     int* h_err = nullptr;                      // pinned (DD_PINNED_BYTES: 64 bytes for h_err, then the DD_H_* values of h_cnt)
     unsigned long long* h_cnt = nullptr;       // pinned: indexed by the DD_H_* slots below, each written by one copy and read after the synchronise that follows it
     BamIndex* index = nullptr; bool index_on = false;      // svx_bam_index_begin: the row table every load appends to (bamindex.hip)
-    BamSort* sort = nullptr; bool sort_on = false;         // svx_bam_sort_begin: the arena and the rows every load appends to (bamsort.hip)
+    SortOut out;                                           // svx_bam_sort_begin: the arena and the rows every load appends to while out.on (bamsort.hip), on `stream`; its index goes to `index`
     SamDev* sam = nullptr;                                 // devdec_load_text: the scratch of the SAM text front end (sam.hip)
     // svx_bam_merge_add: a merge session's sort, BORROWED for the length of that one call - never dropped, finished or destroyed from here - with the session's
     // stream, on which the appends run, and the file's map into the merged dictionary (device memory of the session).  Null unless an add is running: the loads then test this pointer and nothing else
-    BamSort* feed = nullptr; hipStream_t feed_stream = nullptr; const int32_t* feed_map = nullptr; int32_t feed_n_ref = 0; bool feed_identity = true;
+    SortOut* feed = nullptr; const int32_t* feed_map = nullptr; int32_t feed_n_ref = 0; bool feed_identity = true;
 };
 
 // slots of svx_devdec::h_cnt (pinned read-backs).  The loader thread (devdec_load / devdec_count) and the consumer (devdec_batch) use disjoint slots.
@@ -603,6 +603,7 @@ int devdec_create(int device, int n_threads, int32_t n_ref, const int32_t* ref_l
     d->device = device; d->n_ref = n_ref;
     d->n_threads = n_threads > 0 ? n_threads : 1;
     HIPCHK(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    d->out.device = device; d->out.stream = d->stream; d->out.index = &d->index;
     HIPCHK(hipStreamCreateWithFlags(&d->batch_stream, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
     SVXCHK(svx_inflater_create(device, &d->inf));
@@ -637,7 +638,7 @@ void devdec_destroy(svx_devdec* d) {
     (void)hipStreamSynchronize(d->stream);
     (void)hipStreamSynchronize(d->batch_stream);
     if (d->inf) svx_inflater_destroy(d->inf);
-    bamsort_destroy(d->sort); d->sort = nullptr;
+    bamsort_destroy(d->out.sort); d->out.sort = nullptr;     // (in front of the stream it ran on)
     samdev_destroy(d->sam); d->sam = nullptr;
     bamindex_destroy(d->index); d->index = nullptr;
     for (auto& c : d->chunk) c.release();
@@ -672,6 +673,16 @@ static int dd_check(svx_devdec* d, const char* where) {
 }
 
 #define GRIDB(n, t) (unsigned)(((n) + (t) - 1) / (t))
+
+// where a decoded chunk's records are appended: a sort, the stream the append runs on and, for a file of a merge session, its place in the merged dictionary
+// (BamSortChunk: n_ref_file -1 for one file sorted alone)
+struct SortSink { BamSort* sort; hipStream_t stream; const int32_t* tid_map; int32_t n_ref_file; bool identity; };
+// the chunk's records lie back to back from its first byte to where its tail (a partial record, in query-name mode the last read's group) begins
+static int dd_sort_append(const DevChunk& c, const uint8_t* sp, const SortSink& k) {
+    const BamSortChunk sc{(long long)c.n_rec, sp, (uint64_t)c.data_begin, (uint64_t)c.tail_start, c.rec_off.as<uint64_t>(), c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(),
+                          c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>(), k.tid_map, k.n_ref_file, k.identity};
+    return bamsort_append(k.sort, sc, k.stream);
+}
 
 // the records of a chunk whose stream and rec_off are in place (c.data_begin, c.data_end, c.tail_start set; d->err cleared on the stream): the batch arrays, the
 // read names, the index and sort rows.  Shared by the BGZF route (devdec_load) and the SAM text route (devdec_load_text)
@@ -778,20 +789,16 @@ static int dd_decode(svx_devdec* d, DevChunk& c, uint64_t n_rec, bool final_chun
                                c.ix_start.data(), c.ix_vbase.data(), (long long)c.ix_start.size()};
         SVXCHK(bamindex_append(d->index, ic, st));
     }
-    if (d->sort_on && c.n_rec > 0) {
-        // the chunk's records lie back to back from its first byte to where its tail (a partial record, in query-name mode the last read's group) begins
-        const BamSortChunk sc{(long long)c.n_rec, sp, (uint64_t)c.data_begin, (uint64_t)c.tail_start, c.rec_off.as<uint64_t>(), c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(),
-                              c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>()};
-        const int rc = bamsort_append(d->sort, sc, st);
-        if (rc != SVX_OK) { d->sort_on = false; bamsort_drop(d->sort); return rc; }      // (SVX_E_CAPACITY: the arena is full - the sort is given up, the handle rewinds)
+    if (d->out.on && c.n_rec > 0) {
+        // the decoder's OWN sort: on the loader's stream, behind the kernels that made the chunk, with no synchronise of its own
+        const int rc = dd_sort_append(c, sp, SortSink{d->out.sort, st, nullptr, -1, true});
+        if (rc != SVX_OK) { sortout_drop(&d->out); return rc; }      // (SVX_E_CAPACITY: the arena is full - the sort is given up, the handle rewinds)
     }
     if (d->feed && c.n_rec > 0) {
-        BamSortChunk sc{(long long)c.n_rec, sp, (uint64_t)c.data_begin, (uint64_t)c.tail_start, c.rec_off.as<uint64_t>(), c.tid.as<int32_t>(), c.pos.as<int32_t>(), c.flag.as<uint16_t>(),
-                        c.cigar_off.as<uint64_t>(), c.cigar.as<uint32_t>()};
-        sc.tid_map = d->feed_map; sc.n_ref_file = d->feed_n_ref; sc.identity = d->feed_identity;
-        HIPCHK(hipStreamSynchronize(st));                   // the chunk is complete: the session's stream reads it from here on, this decoder's no longer
-        const int rc = bamsort_append(d->feed, sc, d->feed_stream);      // (drains the session's stream before it returns: the chunk's arrays are free again)
-        if (rc != SVX_OK) { d->feed = nullptr; return rc; }      // (nothing more is appended; the session drops its sort once this loader is idle)
+        // a session's sort, BORROWED: the append runs on the session's stream, which knows nothing of this decoder's - so the chunk is complete first
+        HIPCHK(hipStreamSynchronize(st));
+        const int rc = dd_sort_append(c, sp, SortSink{d->feed->sort, d->feed->stream, d->feed_map, d->feed_n_ref, d->feed_identity});      // (drains the session's stream before it returns: the chunk's arrays are free again)
+        if (rc != SVX_OK) { d->feed = nullptr; return rc; }      // (nothing more is appended and nothing is dropped here: the session drops its sort once this loader is idle)
     }
     d->stats.records += c.n_rec;
     c.loaded = true;
@@ -1059,8 +1066,8 @@ int devdec_load_text(svx_devdec* d, int slot, const uint8_t* text, size_t n, boo
 }
 void devdec_sam_stats(const svx_devdec* d, svx_sam_stats* out) { samdev_stats(d->sam, out); }
 
-void devdec_feed_set(svx_devdec* d, BamSort* sort, void* session_stream, const int32_t* dev_map, int32_t n_ref_file, bool identity) {
-    d->feed_stream = (hipStream_t)session_stream; d->feed_map = dev_map; d->feed_n_ref = n_ref_file; d->feed_identity = identity; d->feed = sort;
+void devdec_feed_set(svx_devdec* d, SortOut* session, const int32_t* dev_map, int32_t n_ref_file, bool identity) {
+    d->feed_map = dev_map; d->feed_n_ref = n_ref_file; d->feed_identity = identity; d->feed = session;
 }
 void devdec_feed_clear(svx_devdec* d) { d->feed = nullptr; d->feed_map = nullptr; }
 bool devdec_feed_on(const svx_devdec* d) { return d->feed != nullptr; }
@@ -1068,50 +1075,12 @@ int devdec_device(const svx_devdec* d) { return d->device; }
 
 int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir, int order) {
     HIPCHK(hipSetDevice(d->device));
-    SVXCHK(bamsort_begin(&d->sort, max_bytes, d->n_ref, spill_dir, order));
-    d->sort_on = true;
+    SVXCHK(bamsort_begin(&d->out.sort, max_bytes, d->n_ref, spill_dir, order));
+    d->out.on = true;
     return SVX_OK;
 }
-void devdec_sort_drop(svx_devdec* d) {
-    (void)hipSetDevice(d->device);
-    d->sort_on = false;
-    bamsort_drop(d->sort);
-}
-bool devdec_sort_on(const svx_devdec* d) { return d->sort_on; }
-bool devdec_sort_finished(const svx_devdec* d) { return bamsort_finished(d->sort); }
-int devdec_sort_finish(svx_devdec* d, const uint8_t* header, int64_t header_bytes) {
-    HIPCHK(hipSetDevice(d->device));
-    d->sort_on = false;
-    const int rc = bamsort_finish(d->sort, header, header_bytes, d->stream);
-    if (rc != SVX_OK) bamsort_drop(d->sort);
-    return rc;
-}
-void devdec_sort_count(const svx_devdec* d, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) { bamsort_count(d->sort, n_records, stream_bytes, n_blocks); }
-int devdec_sort_encode(svx_devdec* d, int64_t first_block, int64_t n_blocks, int64_t* n_bytes) {
-    HIPCHK(hipSetDevice(d->device));
-    const int rc = bamsort_encode(d->sort, first_block, n_blocks, n_bytes, d->stream);
-    if (rc == SVX_E_IO) bamsort_drop(d->sort);              // (the spill file cannot be read: nothing of the sort is of use)
-    return rc;
-}
-int devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_dst) {
-    HIPCHK(hipSetDevice(d->device));
-    return bamsort_fetch(d->sort, compressed_dst, stream_dst, d->stream);
-}
-int devdec_sort_index(svx_devdec* d, int fmt) {
-    HIPCHK(hipSetDevice(d->device));
-    if (d->index_on) return svx_fail(SVX_E_STATE, "svx_bam_sort_index while a BAM index pass is on", __FILE__, __LINE__, hipSuccess);
-    SVXCHK(bamindex_begin(&d->index));
-    const int rc = bamsort_index(d->sort, d->index, d->stream, fmt);
-    bamindex_drop(d->index);                                // (the table's memory goes back; the bytes of a finished index stay)
-    return rc;
-}
-int devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm) {
-    HIPCHK(hipSetDevice(d->device));
-    return bamsort_permutation(d->sort, host_perm, d->stream);
-}
-void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out) { bamsort_stats(d->sort, out); }
-void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out) { bamsort_spill_stats(d->sort, out); }
-void devdec_sort_name_stats(const svx_devdec* d, svx_bam_name_sort_stats* out) { bamsort_name_stats(d->sort, out); }
+bool devdec_sort_on(const svx_devdec* d) { return d->out.on; }
+SortOut* devdec_sort_out(svx_devdec* d) { return &d->out; }
 
 int devdec_index_begin(svx_devdec* d) {
     HIPCHK(hipSetDevice(d->device));

@@ -1319,72 +1319,62 @@ extern "C" int svx_bam_sort_finish(svx_bam* h) {
     if (!h->dev_eof_seen || h->dev_prefetching) return bam_fail(SVX_E_STATE, "svx_bam_sort_finish before svx_bam_read_batch has returned 0 records at the end of the file");
     std::vector<uint8_t> raw, made;
     int rc = raw_header(h, raw);
-    if (rc != SVX_OK) { devdec_sort_drop(h->dev); return rc; }
+    if (rc != SVX_OK) { sortout_drop(devdec_sort_out(h->dev)); return rc; }
     int64_t n = 0;
     rc = svx_bam_sort_header_host_order(raw.data(), (int64_t)raw.size(), h->sort_pass_order, nullptr, 0, &n);
     if (rc == SVX_E_CAPACITY) { made.resize((size_t)n); rc = svx_bam_sort_header_host_order(raw.data(), (int64_t)raw.size(), h->sort_pass_order, made.data(), n, &n); }
-    if (rc != SVX_OK) { devdec_sort_drop(h->dev); return bam_fail(rc, "svx_bam_sort_finish: the file's header cannot be rewritten"); }
-    rc = devdec_sort_finish(h->dev, made.data(), (int64_t)made.size());
+    if (rc != SVX_OK) { sortout_drop(devdec_sort_out(h->dev)); return bam_fail(rc, "svx_bam_sort_finish: the file's header cannot be rewritten"); }
+    rc = sortout_finish(devdec_sort_out(h->dev), made.data(), (int64_t)made.size());
     if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
     return SVX_OK;
 }
 extern "C" int svx_bam_sort_abort(svx_bam* h) {
     if (!h) return bam_fail(SVX_E_ARG, "null reader");
-    if (!h->dev || !(devdec_sort_on(h->dev) || devdec_sort_finished(h->dev))) return bam_fail(SVX_E_STATE, "svx_bam_sort_abort without a sort");
+    if (!h->dev || !(devdec_sort_on(h->dev) || sortout_finished(devdec_sort_out(h->dev)))) return bam_fail(SVX_E_STATE, "svx_bam_sort_abort without a sort");
     if (h->dev_prefetching) h->dev_future.wait();           // the chunk being loaded appends its records: it is kept for the next read, the arena goes after it
-    devdec_sort_drop(h->dev);
+    sortout_drop(devdec_sort_out(h->dev));
     return SVX_OK;
 }
+// ---- a finished sort, whoever owns it: a reader (svx_bam_sort_*) or a merge session (svx_bam_merge_*).  Each exported accessor checks its own family's
+// state, under its own name, and then is one sortout_* call (devdec.hpp) ----
+static int out_status(int rc) { return rc == SVX_OK ? SVX_OK : bam_fail(rc, svx_last_error()); }
 #define SORT_NEEDS_FINISHED(what) \
     if (!h) return bam_fail(SVX_E_ARG, "null reader"); \
-    if (!h->dev || !devdec_sort_finished(h->dev)) return bam_fail(SVX_E_STATE, what ": no sorted records (svx_bam_sort_begin, a pass over the file, svx_bam_sort_finish)")
+    if (!h->dev || !sortout_finished(devdec_sort_out(h->dev))) return bam_fail(SVX_E_STATE, what ": no sorted records (svx_bam_sort_begin, a pass over the file, svx_bam_sort_finish)"); \
+    SortOut* const o = devdec_sort_out(h->dev)
 extern "C" int svx_bam_sort_count(svx_bam* h, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) {
     SORT_NEEDS_FINISHED("svx_bam_sort_count");
-    devdec_sort_count(h->dev, n_records, stream_bytes, n_blocks);
+    sortout_count(o, n_records, stream_bytes, n_blocks);
     return SVX_OK;
 }
 extern "C" int svx_bam_sort_encode(svx_bam* h, int64_t first_block, int64_t n_blocks, int64_t* n_bytes) {
     SORT_NEEDS_FINISHED("svx_bam_sort_encode");
-    const int rc = devdec_sort_encode(h->dev, first_block, n_blocks, n_bytes);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    return out_status(sortout_encode(o, first_block, n_blocks, n_bytes));
 }
 extern "C" int svx_bam_sort_fetch(svx_bam* h, uint8_t* compressed_dst, uint8_t* stream_dst) {
     SORT_NEEDS_FINISHED("svx_bam_sort_fetch");
-    const int rc = devdec_sort_fetch(h->dev, compressed_dst, stream_dst);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    return out_status(sortout_fetch(o, compressed_dst, stream_dst));
 }
 extern "C" int svx_bam_sort_index_fmt(svx_bam* h, int fmt) {
     SORT_NEEDS_FINISHED("svx_bam_sort_index");
     if (!index_fmt_ok(fmt)) return bam_fail(SVX_E_ARG, "svx_bam_sort_index_fmt: unknown index format (SVX_INDEX_CLASSIC or SVX_INDEX_CSI)");
-    const int rc = devdec_sort_index(h->dev, fmt);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    // (the reader's alone: its sort indexes into the slot an index pass of the reader fills)
+    if (devdec_index_on(h->dev)) return bam_fail(SVX_E_STATE, "svx_bam_sort_index while a BAM index pass is on");
+    return out_status(sortout_index(o, fmt));
 }
 extern "C" int svx_bam_sort_index(svx_bam* h) { return svx_bam_sort_index_fmt(h, SVX_INDEX_CLASSIC); }
 extern "C" int svx_bam_sort_permutation(svx_bam* h, uint32_t* perm) {
     SORT_NEEDS_FINISHED("svx_bam_sort_permutation");
-    const int rc = devdec_sort_permutation(h->dev, perm);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    return out_status(sortout_permutation(o, perm));
 }
-extern "C" int svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out) {
-    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
-    if (h->dev) devdec_sort_stats(h->dev, out); else memset(out, 0, sizeof *out);
-    return SVX_OK;
-}
-
-extern "C" int svx_bam_sort_get_name_stats(svx_bam* h, svx_bam_name_sort_stats* out) {
-    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
-    if (h->dev) devdec_sort_name_stats(h->dev, out); else memset(out, 0, sizeof *out);
-    return SVX_OK;
-}
-extern "C" int svx_bam_sort_get_spill_stats(svx_bam* h, svx_bam_sort_spill_stats* out) {
-    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument");
-    if (h->dev) devdec_sort_spill_stats(h->dev, out); else memset(out, 0, sizeof *out);
-    return SVX_OK;
-}
+// (the stats of a reader that never decoded on the device are zeros)
+#define SORT_STATS(getter) \
+    if (!h || !out) return bam_fail(SVX_E_ARG, "null argument"); \
+    if (h->dev) getter(devdec_sort_out(h->dev), out); else memset(out, 0, sizeof *out); \
+    return SVX_OK
+extern "C" int svx_bam_sort_get_stats(svx_bam* h, svx_bam_sort_stats* out) { SORT_STATS(sortout_stats); }
+extern "C" int svx_bam_sort_get_name_stats(svx_bam* h, svx_bam_name_sort_stats* out) { SORT_STATS(sortout_name_stats); }
+extern "C" int svx_bam_sort_get_spill_stats(svx_bam* h, svx_bam_sort_spill_stats* out) { SORT_STATS(sortout_spill_stats); }
 
 // ---- several files merged on the device: the session (include/svx.h; its device side: bammerge.hip; what the merged file is: svim_amd/bammerge.py) -----------
 // The session owns its sort, stream and index (MergeDev) and copies of what it read from the readers at open: the merged header, every file's dictionary and
@@ -1488,7 +1478,7 @@ extern "C" int svx_bam_merge_add(svx_bam_merge* m, svx_bam* h) {
     devdec_feed_clear(h->dev);
     m->t_add += now_s() - t0;
     if (rc != SVX_OK) {
-        mergedev_drop(m->dev); m->broken = true;            // (the reader is usable after svx_bam_rewind, as after a failed sort pass)
+        sortout_drop(mergedev_sort_out(m->dev)); m->broken = true;            // (the reader is usable after svx_bam_rewind, as after a failed sort pass)
         return bam_fail(rc, "svx_bam_merge_add: " + err);
     }
     if (!F.identity) m->n_translated_files++;
@@ -1499,77 +1489,64 @@ extern "C" int svx_bam_merge_finish(svx_bam_merge* m) {
     MERGE_USABLE("svx_bam_merge_finish");
     if (m->finished) return bam_fail(SVX_E_STATE, "svx_bam_merge_finish twice");
     if (m->added != m->k) return bam_fail(SVX_E_STATE, "svx_bam_merge_finish before every file has been added");
-    const int rc = mergedev_finish(m->dev, m->header.data(), (int64_t)m->header.size());
+    const int rc = sortout_finish(mergedev_sort_out(m->dev), m->header.data(), (int64_t)m->header.size());
     if (rc != SVX_OK) { m->broken = true; return bam_fail(rc, svx_last_error()); }
     m->finished = true;
     return SVX_OK;
 }
 #define MERGE_NEEDS_FINISHED(what) \
     MERGE_USABLE(what); \
-    if (!m->finished) return bam_fail(SVX_E_STATE, what ": no merged records (k adds, then svx_bam_merge_finish)")
+    if (!m->finished) return bam_fail(SVX_E_STATE, what ": no merged records (k adds, then svx_bam_merge_finish)"); \
+    SortOut* const o = mergedev_sort_out(m->dev)
 extern "C" int svx_bam_merge_count(svx_bam_merge* m, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks) {
     MERGE_NEEDS_FINISHED("svx_bam_merge_count");
-    mergedev_count(m->dev, n_records, stream_bytes, n_blocks);
+    sortout_count(o, n_records, stream_bytes, n_blocks);
     return SVX_OK;
 }
 extern "C" int svx_bam_merge_encode(svx_bam_merge* m, int64_t first_block, int64_t n_blocks, int64_t* n_bytes) {
     MERGE_NEEDS_FINISHED("svx_bam_merge_encode");
-    const int rc = mergedev_encode(m->dev, first_block, n_blocks, n_bytes);
-    if (rc == SVX_E_IO) { mergedev_drop(m->dev); m->broken = true; }      // (the spill file cannot be read: nothing of the sort is of use)
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    const int rc = sortout_encode(o, first_block, n_blocks, n_bytes);
+    if (rc == SVX_E_IO) m->broken = true;                   // (the session's alone: the sort was dropped, svx_bam_merge_close is all that is left)
+    return out_status(rc);
 }
 extern "C" int svx_bam_merge_fetch(svx_bam_merge* m, uint8_t* compressed_dst, uint8_t* stream_dst) {
     MERGE_NEEDS_FINISHED("svx_bam_merge_fetch");
-    const int rc = mergedev_fetch(m->dev, compressed_dst, stream_dst);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    return out_status(sortout_fetch(o, compressed_dst, stream_dst));
 }
 extern "C" int svx_bam_merge_index_fmt(svx_bam_merge* m, int fmt) {
     MERGE_NEEDS_FINISHED("svx_bam_merge_index_fmt");
     if (!index_fmt_ok(fmt)) return bam_fail(SVX_E_ARG, "svx_bam_merge_index_fmt: unknown index format (SVX_INDEX_CLASSIC or SVX_INDEX_CSI)");
-    const int rc = mergedev_index(m->dev, fmt);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    return out_status(sortout_index(o, fmt));
 }
 extern "C" int svx_bam_merge_index_count(svx_bam_merge* m, int64_t* n_bytes) {
     MERGE_USABLE("svx_bam_merge_index_count");
-    if (!mergedev_index_bytes(m->dev, n_bytes)) return bam_fail(SVX_E_STATE, "no index of the merged file: svx_bam_merge_finish, every block encoded, svx_bam_merge_index_fmt");
+    if (!sortout_index_bytes(mergedev_sort_out(m->dev), n_bytes)) return bam_fail(SVX_E_STATE, "no index of the merged file: svx_bam_merge_finish, every block encoded, svx_bam_merge_index_fmt");
     return SVX_OK;
 }
 extern "C" int svx_bam_merge_index_fetch(svx_bam_merge* m, uint8_t* host_dst) {
     MERGE_USABLE("svx_bam_merge_index_fetch");
-    if (!mergedev_index_bytes(m->dev, nullptr)) return bam_fail(SVX_E_STATE, "no index of the merged file: svx_bam_merge_finish, every block encoded, svx_bam_merge_index_fmt");
-    const int rc = mergedev_index_fetch(m->dev, host_dst);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
+    if (!sortout_index_bytes(mergedev_sort_out(m->dev), nullptr)) return bam_fail(SVX_E_STATE, "no index of the merged file: svx_bam_merge_finish, every block encoded, svx_bam_merge_index_fmt");
+    return out_status(sortout_index_fetch(mergedev_sort_out(m->dev), host_dst));
 }
 extern "C" int svx_bam_merge_permutation(svx_bam_merge* m, uint32_t* perm) {
     MERGE_NEEDS_FINISHED("svx_bam_merge_permutation");
-    const int rc = mergedev_permutation(m->dev, perm);
-    if (rc != SVX_OK) return bam_fail(rc, svx_last_error());
-    return SVX_OK;
-}
-static void merge_stats(svx_bam_merge* m, svx_bam_sort_stats* st, svx_bam_sort_spill_stats* sp, svx_bam_merge_stats* ms) {
-    svx_bam_sort_stats a; svx_bam_sort_spill_stats b; int64_t c = 0, r = 0, by = 0; double t = 0;
-    mergedev_stats(m->dev, &a, &b, &c, &r, &by, &t);
-    if (st) *st = a;
-    if (sp) *sp = b;
-    if (ms) *ms = svx_bam_merge_stats{m->k, m->added, m->n_ref_merged, (int64_t)m->header.size(), m->n_translated_files, c, r, by, m->t_open * 1e3, m->t_add * 1e3, t};
+    return out_status(sortout_permutation(o, perm));
 }
 extern "C" int svx_bam_merge_get_stats(svx_bam_merge* m, svx_bam_sort_stats* out) {
     if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
-    merge_stats(m, out, nullptr, nullptr);
+    sortout_stats(mergedev_sort_out(m->dev), out);
     return SVX_OK;
 }
 extern "C" int svx_bam_merge_get_spill_stats(svx_bam_merge* m, svx_bam_sort_spill_stats* out) {
     if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
-    merge_stats(m, nullptr, out, nullptr);
+    sortout_spill_stats(mergedev_sort_out(m->dev), out);
     return SVX_OK;
 }
 extern "C" int svx_bam_merge_get_merge_stats(svx_bam_merge* m, svx_bam_merge_stats* out) {
     if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
-    merge_stats(m, nullptr, nullptr, out);
+    int64_t c = 0, r = 0, by = 0; double t = 0;
+    sortout_translate_stats(mergedev_sort_out(m->dev), &c, &r, &by, &t);
+    *out = svx_bam_merge_stats{m->k, m->added, m->n_ref_merged, (int64_t)m->header.size(), m->n_translated_files, c, r, by, m->t_open * 1e3, m->t_add * 1e3, t};
     return SVX_OK;
 }
 

@@ -36,3 +36,6 @@ void bamsort_spill_stats(const BamSort* s, svx_bam_sort_spill_stats* out);
 void bamsort_name_stats(const BamSort* s, svx_bam_name_sort_stats* out);      // zeros unless the last finish was in query-name order
 // what k_bs_translate has done for the sort since begin: chunks and records it ran over, the bytes it read and wrote, its time between events on the stream
 void bamsort_translate_stats(const BamSort* s, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms);
+// A sort with the stream it runs on and the slot its index goes to (devdec.hpp: sortout_*; sortout.hip).  The owner - a reader's decoder, a merge session -
+// fills it in and outlives it; stream and *index are the owner's and are only borrowed here.  on: appending (the owner's begin sets it, finish and drop clear it)
+struct SortOut { int device = 0; hipStream_t stream = nullptr; BamSort* sort = nullptr; BamIndex** index = nullptr; bool on = false; };

@@ -52,47 +52,47 @@ int  devdec_index_finish(svx_devdec* d, uint64_t v_end, int fmt);
 bool devdec_index_bytes(const svx_devdec* d, int64_t* n_bytes);
 int  devdec_index_fetch(svx_devdec* d, uint8_t* host_dst);
 void devdec_index_stats(const svx_devdec* d, svx_bam_index_stats* out);
-// Coordinate sort from the record stream (bamsort.hip; include/svx.h: svx_bam_sort*).  begin: an empty arena, every later devdec_load appends the bytes and the
-// rows of the records it hands to devdec_count (once per chunk, on the loader's stream); a load whose records pass max_bytes fails with SVX_E_CAPACITY and drops
-// the sort.  finish (header: the rewritten header): appending is over, the sorted order and the stream layout stay until drop or the next begin.  encode / fetch /
-// index / permutation need a finished sort; index leaves its bytes where devdec_index_bytes / devdec_index_fetch read them.
+// Sort from the record stream (bamsort.hip; include/svx.h: svx_bam_sort*).  begin: an empty arena, every later devdec_load appends the bytes and the rows of the
+// records it hands to devdec_count (once per chunk, on the loader's stream, with no synchronise of its own); a load whose records pass max_bytes fails with
+// SVX_E_CAPACITY and drops the sort.  on: appending, from begin to the finish or drop of devdec_sort_out (below), which holds everything else.
 int  devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char* spill_dir /* null: no spill file, SVX_E_CAPACITY at the limit */, int order = 0 /* SVX_SORT_* */);
-void devdec_sort_drop(svx_devdec* d);
-bool devdec_sort_on(const svx_devdec* d);               // appending
-bool devdec_sort_finished(const svx_devdec* d);
-int  devdec_sort_finish(svx_devdec* d, const uint8_t* header, int64_t header_bytes);
-void devdec_sort_count(const svx_devdec* d, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
-int  devdec_sort_encode(svx_devdec* d, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
-int  devdec_sort_fetch(svx_devdec* d, uint8_t* compressed_dst, uint8_t* stream_dst);
-int  devdec_sort_index(svx_devdec* d, int fmt);
-int  devdec_sort_permutation(svx_devdec* d, uint32_t* host_perm);
-void devdec_sort_stats(const svx_devdec* d, svx_bam_sort_stats* out);
-void devdec_sort_spill_stats(const svx_devdec* d, svx_bam_sort_spill_stats* out);
-void devdec_sort_name_stats(const svx_devdec* d, svx_bam_name_sort_stats* out);
+bool devdec_sort_on(const svx_devdec* d);
 // A merge session's feed (svx_bam_merge_add; bammerge.hip): while set, every devdec_load appends the records it hands to devdec_count to the SESSION's sort -
-// in this decoder's loader thread but on the SESSION's stream (session_stream: a hipStream_t), once the decoder's own stream has been drained - as records of a
+// in this decoder's loader thread but on the SESSION's stream (both are `session`'s), once the decoder's own stream has been drained - as records of a
 // file with n_ref_file references whose ids dev_map (device memory of the session; unused when `identity`) takes into the merged dictionary.  Every command that
 // touches the session's memory thus runs on the one stream that lives as long as that memory does, whichever readers come and go.  The decoder borrows the sort
 // and never owns it: a failed append clears the feed and fails the load, nothing else.  Set and cleared only while no loader runs.
-struct BamSort;
-void devdec_feed_set(svx_devdec* d, BamSort* sort, void* session_stream, const int32_t* dev_map, int32_t n_ref_file, bool identity);
+struct SortOut;
+void devdec_feed_set(svx_devdec* d, SortOut* session, const int32_t* dev_map, int32_t n_ref_file, bool identity);
 void devdec_feed_clear(svx_devdec* d);
 bool devdec_feed_on(const svx_devdec* d);
 int  devdec_device(const svx_devdec* d);
-// ---- the device side of a merge session (bammerge.hip): a sort, a stream and an output index of its OWN; thin wrappers over bamsort_* / bamindex_* ----
+// ---- the device side of a merge session (bammerge.hip): a sort, a stream and an output index of its OWN, and the files' id maps ----
 struct MergeDev;
 // maps: the files' maps back to back (n_maps entries, uploaded once); spill_dir may be null
 int  mergedev_create(int device, int64_t max_bytes, int32_t n_ref_merged, const char* spill_dir, const int32_t* maps, int64_t n_maps, MergeDev** out);
 void mergedev_destroy(MergeDev* m);
 int  mergedev_device(const MergeDev* m);
-void mergedev_feed(MergeDev* m, svx_devdec* d, int64_t map_at, int32_t n_ref_file, bool identity);      // devdec_feed_set with the session's sort and map
-void mergedev_drop(MergeDev* m);                         // the sort's memory goes back (a failed append, a failed finish)
-int  mergedev_finish(MergeDev* m, const uint8_t* header, int64_t header_bytes);
-void mergedev_count(const MergeDev* m, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
-int  mergedev_encode(MergeDev* m, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
-int  mergedev_fetch(MergeDev* m, uint8_t* compressed_dst, uint8_t* stream_dst);
-int  mergedev_index(MergeDev* m, int fmt);
-bool mergedev_index_bytes(const MergeDev* m, int64_t* n_bytes);
-int  mergedev_index_fetch(MergeDev* m, uint8_t* host_dst);
-int  mergedev_permutation(MergeDev* m, uint32_t* host_perm);
-void mergedev_stats(const MergeDev* m, svx_bam_sort_stats* out, svx_bam_sort_spill_stats* spill, int64_t* tr_chunks, int64_t* tr_records, int64_t* tr_bytes, double* tr_ms);
+void mergedev_feed(MergeDev* m, svx_devdec* d, int64_t map_at, int32_t n_ref_file, bool identity);      // devdec_feed_set with the session's sort, stream and map
+// ---- a sort with the stream it runs on and the slot its index goes to (sortout.hip): what a reader's own sort and a merge session both end as ----
+// The owner makes the sort (devdec_sort_begin, mergedev_create) and appends to it; everything from finish on is written once, here.  finish (header: the
+// rewritten header): appending is over, the sorted order and the stream layout stay until drop or the owner's next begin; a failed finish drops the sort.
+// drop: the sort's memory goes back (an abort, a failed append).  count / encode / fetch / index / permutation need a finished sort.  encode: SVX_E_IO is a
+// spill file that cannot be read - nothing of the sort is of use and it is dropped.  index leaves its bytes where index_bytes / index_fetch read them: for a
+// reader that is the decoder's own index slot (devdec_index_bytes / devdec_index_fetch see the same bytes), for a session its own.
+SortOut* devdec_sort_out(svx_devdec* d);
+SortOut* mergedev_sort_out(MergeDev* m);
+int  sortout_finish(SortOut* o, const uint8_t* header, int64_t header_bytes);
+void sortout_drop(SortOut* o);
+bool sortout_finished(const SortOut* o);
+void sortout_count(const SortOut* o, int64_t* n_records, int64_t* stream_bytes, int64_t* n_blocks);
+int  sortout_encode(SortOut* o, int64_t first_block, int64_t n_blocks, int64_t* n_bytes);
+int  sortout_fetch(SortOut* o, uint8_t* compressed_dst, uint8_t* stream_dst);
+int  sortout_index(SortOut* o, int fmt);
+bool sortout_index_bytes(const SortOut* o, int64_t* n_bytes);
+int  sortout_index_fetch(SortOut* o, uint8_t* host_dst);
+int  sortout_permutation(SortOut* o, uint32_t* host_perm);
+void sortout_stats(const SortOut* o, svx_bam_sort_stats* out);
+void sortout_spill_stats(const SortOut* o, svx_bam_sort_spill_stats* out);
+void sortout_name_stats(const SortOut* o, svx_bam_name_sort_stats* out);      // zeros unless the last finish was in query-name order
+void sortout_translate_stats(const SortOut* o, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms);

@@ -868,6 +868,20 @@ def _write_bam_index(path, data, fmt):
             fh.write(data)
 
 
+def _write_sorted_bam(out, n_blocks, encode, index, piece_blocks, index_format, written):
+    """A finished sort on the device - a reader's own (sort_bam), a merge session's (merge_bam) - written to `out`: encode(first_block, n_blocks) -> bytes, in
+    pieces of piece_blocks BGZF blocks, then index(index_format) -> bytes to out + "." + index_format unless `index` is None.  `written` takes every file as
+    it is begun: what the caller removes when anything fails"""
+    written.append(out)
+    with open(out, "wb") as fh:
+        for first in range(0, n_blocks, piece_blocks):
+            fh.write(encode(first, min(piece_blocks, n_blocks - first)))
+    if index is not None:
+        data = index(index_format)
+        written.append(out + "." + index_format)
+        _write_bam_index(out + "." + index_format, data, index_format)
+
+
 _DEFAULT = object()      # sort_bam / sam_to_bam: an argument the caller did not give (index=True and index_format="bai" are then what they always were)
 
 
@@ -908,14 +922,7 @@ def sort_bam(path, out, device=0, index=_DEFAULT, piece_blocks=4096, max_bytes=0
             while bam.read_batch(batch_records, 0, "coordinate")[1]:
                 pass
             _, _, n_blocks = bam.sort_finish()
-            written.append(out)
-            with open(out, "wb") as fh:
-                for first in range(0, n_blocks, piece_blocks):
-                    fh.write(bam.sort_encode(first, min(piece_blocks, n_blocks - first)))
-            if index:
-                data = bam.sort_index(index_format)
-                written.append(out + "." + index_format)
-                _write_bam_index(out + "." + index_format, data, index_format)
+            _write_sorted_bam(out, n_blocks, bam.sort_encode, bam.sort_index if index else None, piece_blocks, index_format, written)
             stats = bam.sort_stats()
             stats["spill"] = bam.sort_spill_stats()
             if by_name:
@@ -966,14 +973,7 @@ def merge_bam(paths, out, device=0, index=True, index_format="bai", piece_blocks
             session.add(r)
             r.close()
         _, _, n_blocks = session.finish()
-        written.append(out)
-        with open(out, "wb") as fh:
-            for first in range(0, n_blocks, piece_blocks):
-                fh.write(session.encode(first, min(piece_blocks, n_blocks - first)))
-        if index:
-            data = session.index(index_format)
-            written.append(out + "." + index_format)
-            _write_bam_index(out + "." + index_format, data, index_format)
+        _write_sorted_bam(out, n_blocks, session.encode, session.index if index else None, piece_blocks, index_format, written)
         return session.stats()
     except BaseException:
         for f in written:

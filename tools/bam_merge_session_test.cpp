@@ -1,7 +1,7 @@
 // bam_merge_session_test.cpp - the life cycle of a merge session (svx_bam_merge_*: the host logic in svim_amd/csrc/bamio.cpp) and of the readers that feed it,
 // walked in every order on the CPU.  bamio.cpp and bamsort_host.cpp are the library's; the device side is a stand-in: the decoder of tools/bamio_fuzz.cpp (chunk
-// slots, a loader thread per chunk) and, below, a model of the sort (BamSort) and of the session's device side (MergeDev) that keeps appended records in host
-// memory and sorts with std::stable_sort.  The model POISONS what it frees and COUNTS owners and borrowers: a sort destroyed twice, used after its destruction,
+// slots, a loader thread per chunk) and, below, a model of the sort (BamSort), of what it ends as for either owner (SortOut) and of the session's device side
+// (MergeDev) that keeps appended records in host memory and sorts with std::stable_sort.  The model POISONS what it frees and COUNTS owners and borrowers: a sort destroyed twice, used after its destruction,
 // dropped or destroyed while a decoder still borrows it, or appended to by a decoder that does not hold it, ends the program with a message even where the
 // allocator would forgive it.  Meant for -fsanitize=address,undefined (with LeakSanitizer) and, in a second build, -fsanitize=thread: appends run on the loader
 // threads bamio.cpp starts, the feed is set and cleared on the caller's.  tests/test_bam_merge_session.py builds both and runs them as stand-alone programs.
@@ -134,53 +134,68 @@ static int model_permutation(BamSort* S, uint32_t* perm) {
     return SVX_OK;
 }
 
+// ---- what a sort ends as, whoever owns it (devdec.hpp: sortout_*): the model, directly ------------------------------------------------------------------------
+struct SortOut { BamSort* sort = nullptr; bool on = false; std::vector<uint8_t> index; bool have_index = false; };
+void sortout_drop(SortOut* o) { o->on = false; model_drop(o->sort); }
+int sortout_finish(SortOut* o, const uint8_t* header, int64_t n) { o->on = false; const int rc = model_finish(o->sort, header, n); if (rc != SVX_OK) model_drop(o->sort); return rc; }
+bool sortout_finished(const SortOut* o) { return o->sort && model_alive(o->sort, "finished")->finished; }
+void sortout_count(const SortOut* o, int64_t* a, int64_t* b, int64_t* c) { model_count(o->sort, a, b, c); }
+int sortout_encode(SortOut* o, int64_t first, int64_t nb, int64_t* n_bytes) { return model_encode(o->sort, first, nb, n_bytes); }
+int sortout_fetch(SortOut* o, uint8_t* a, uint8_t* b) { return model_fetch(o->sort, a, b); }
+int sortout_index(SortOut* o, int fmt) {                    // (the index is the kernels' work: the model's holds the record count and the format)
+    if (!model_alive(o->sort, "index")->finished) return SVX_E_STATE;
+    const uint64_t n = o->sort->rows.size();
+    o->index.assign(12, 0); memcpy(o->index.data(), &n, 8); memcpy(o->index.data() + 8, &fmt, 4); o->have_index = true;
+    return SVX_OK;
+}
+bool sortout_index_bytes(const SortOut* o, int64_t* n) { if (o->have_index && n) *n = (int64_t)o->index.size(); return o->have_index; }
+int sortout_index_fetch(SortOut* o, uint8_t* dst) { memcpy(dst, o->index.data(), o->index.size()); return SVX_OK; }
+int sortout_permutation(SortOut* o, uint32_t* perm) { return model_permutation(o->sort, perm); }
+void sortout_stats(const SortOut*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_spill_stats(const SortOut*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_name_stats(const SortOut*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_translate_stats(const SortOut*, int64_t* c, int64_t* r, int64_t* by, double* t) { *c = *r = *by = 0; *t = 0; }
+
 // ---- the decoder's side (devdec.hpp): its own sort, and the feed it borrows --------------------------------------------------------------------------------
 static int model_after_load(svx_devdec* d, const MockSlot& S, const uint64_t* rec, size_t n_rec) {
-    if (d->sort_on && n_rec > 0) {
-        const int rc = model_append(d->sort, S, rec, n_rec, nullptr, -1, true, false);
-        if (rc != SVX_OK) { d->sort_on = false; model_drop(d->sort); return rc; }
+    if (d->out->on && n_rec > 0) {
+        const int rc = model_append(d->out->sort, S, rec, n_rec, nullptr, -1, true, false);
+        if (rc != SVX_OK) { sortout_drop(d->out); return rc; }
     }
     if (d->feed && n_rec > 0) {
-        if (d->feed->borrowers.load() < 1) model_die("a decoder appends to a sort it has not borrowed");
-        const int rc = model_append(d->feed, S, rec, n_rec, d->feed_map, d->feed_n_ref, d->feed_identity, true);
-        if (rc != SVX_OK) { d->feed->borrowers--; d->feed = nullptr; return rc; }
+        BamSort* const fed = d->feed->sort;
+        if (fed->borrowers.load() < 1) model_die("a decoder appends to a sort it has not borrowed");
+        const int rc = model_append(fed, S, rec, n_rec, d->feed_map, d->feed_n_ref, d->feed_identity, true);
+        if (rc != SVX_OK) { fed->borrowers--; d->feed = nullptr; return rc; }
     }
     return SVX_OK;
 }
+static void model_create_decoder(svx_devdec* d) { d->out = new SortOut(); }
 static void model_destroy_decoder(svx_devdec* d) {
     if (d->feed) model_die("a decoder was destroyed while it feeds a session");
-    model_destroy(d->sort); d->sort = nullptr;
+    model_destroy(d->out->sort);
+    delete d->out; d->out = nullptr;
 }
-void devdec_feed_set(svx_devdec* d, BamSort* sort, void*, const int32_t* map, int32_t n_ref_file, bool identity) {
-    model_alive(sort, "feed_set");
+void devdec_feed_set(svx_devdec* d, SortOut* session, const int32_t* map, int32_t n_ref_file, bool identity) {
+    model_alive(session->sort, "feed_set");
     if (d->feed) model_die("a decoder that feeds a session was given a second feed");
-    sort->borrowers++;
-    d->feed_map = map; d->feed_n_ref = n_ref_file; d->feed_identity = identity; d->feed = sort;
+    session->sort->borrowers++;
+    d->feed_map = map; d->feed_n_ref = n_ref_file; d->feed_identity = identity; d->feed = session;
 }
-void devdec_feed_clear(svx_devdec* d) { if (d->feed) { model_alive(d->feed, "feed_clear"); d->feed->borrowers--; } d->feed = nullptr; d->feed_map = nullptr; }
+void devdec_feed_clear(svx_devdec* d) { if (d->feed) { model_alive(d->feed->sort, "feed_clear"); d->feed->sort->borrowers--; } d->feed = nullptr; d->feed_map = nullptr; }
 bool devdec_feed_on(const svx_devdec* d) { return d->feed != nullptr; }
 int devdec_device(const svx_devdec*) { return 0; }
-int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char*, int) { model_begin(&d->sort, max_bytes, (int32_t)d->rank.size()); d->sort_on = true; return SVX_OK; }
-void devdec_sort_drop(svx_devdec* d) { d->sort_on = false; model_drop(d->sort); }
-bool devdec_sort_on(const svx_devdec* d) { return d->sort_on; }
-bool devdec_sort_finished(const svx_devdec* d) { return d->sort && model_alive(d->sort, "finished")->finished; }
-int devdec_sort_finish(svx_devdec* d, const uint8_t* header, int64_t n) { d->sort_on = false; const int rc = model_finish(d->sort, header, n); if (rc != SVX_OK) model_drop(d->sort); return rc; }
-void devdec_sort_count(const svx_devdec* d, int64_t* a, int64_t* b, int64_t* c) { model_count(d->sort, a, b, c); }
-int devdec_sort_encode(svx_devdec* d, int64_t first, int64_t nb, int64_t* n_bytes) { return model_encode(d->sort, first, nb, n_bytes); }
-int devdec_sort_fetch(svx_devdec* d, uint8_t* a, uint8_t* b) { return model_fetch(d->sort, a, b); }
-int devdec_sort_index(svx_devdec*, int) { return SVX_E_STATE; }
-int devdec_sort_permutation(svx_devdec* d, uint32_t* perm) { return model_permutation(d->sort, perm); }
-void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
-void devdec_sort_spill_stats(const svx_devdec*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
-void devdec_sort_name_stats(const svx_devdec*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
+int devdec_sort_begin(svx_devdec* d, int64_t max_bytes, const char*, int) { model_begin(&d->out->sort, max_bytes, (int32_t)d->rank.size()); d->out->on = true; return SVX_OK; }
+bool devdec_sort_on(const svx_devdec* d) { return d->out->on; }
+SortOut* devdec_sort_out(svx_devdec* d) { return d->out; }
 
 // ---- the session's device side (devdec.hpp: mergedev_*) ------------------------------------------------------------------------------------------------------
-struct MergeDev { uint32_t magic = MODEL_ALIVE; BamSort* sort = nullptr; std::vector<int32_t>* maps = nullptr; std::vector<uint8_t> index; bool have_index = false; };
+struct MergeDev { uint32_t magic = MODEL_ALIVE; SortOut out; std::vector<int32_t>* maps = nullptr; };
 static std::atomic<int> g_sessions_alive{0};
 static MergeDev* md_alive(const MergeDev* m, const char* where) { if (!m || m->magic != MODEL_ALIVE) { fprintf(stderr, "in %s: ", where); model_die("a session's device side was used after its destruction"); } return const_cast<MergeDev*>(m); }
 int mergedev_create(int, int64_t max_bytes, int32_t n_ref_merged, const char*, const int32_t* maps, int64_t n_maps, MergeDev** out) {
     MergeDev* m = new MergeDev();
-    model_begin(&m->sort, max_bytes, n_ref_merged);
+    model_begin(&m->out.sort, max_bytes, n_ref_merged); m->out.on = true;
     m->maps = new std::vector<int32_t>(maps, maps + n_maps);
     g_sessions_alive++;
     *out = m;
@@ -189,32 +204,15 @@ int mergedev_create(int, int64_t max_bytes, int32_t n_ref_merged, const char*, c
 void mergedev_destroy(MergeDev* m) {
     if (!m) return;
     md_alive(m, "destroy");
-    model_destroy(m->sort); m->sort = nullptr;
+    model_destroy(m->out.sort); m->out.sort = nullptr;
     if (m->maps) { std::fill(m->maps->begin(), m->maps->end(), 0x55555555); delete m->maps; m->maps = nullptr; }
     m->magic = MODEL_DEAD;
     g_sessions_alive--;
     delete m;
 }
 int mergedev_device(const MergeDev* m) { md_alive(m, "device"); return 0; }
-void mergedev_feed(MergeDev* m, svx_devdec* d, int64_t map_at, int32_t n_ref_file, bool identity) { md_alive(m, "feed"); devdec_feed_set(d, m->sort, nullptr, m->maps->data() + map_at, n_ref_file, identity); }
-void mergedev_drop(MergeDev* m) { md_alive(m, "drop"); model_drop(m->sort); }
-int mergedev_finish(MergeDev* m, const uint8_t* header, int64_t n) { md_alive(m, "finish"); const int rc = model_finish(m->sort, header, n); if (rc != SVX_OK) model_drop(m->sort); return rc; }
-void mergedev_count(const MergeDev* m, int64_t* a, int64_t* b, int64_t* c) { model_count(md_alive(m, "count")->sort, a, b, c); }
-int mergedev_encode(MergeDev* m, int64_t first, int64_t nb, int64_t* n_bytes) { return model_encode(md_alive(m, "encode")->sort, first, nb, n_bytes); }
-int mergedev_fetch(MergeDev* m, uint8_t* a, uint8_t* b) { return model_fetch(md_alive(m, "fetch")->sort, a, b); }
-int mergedev_index(MergeDev* m, int fmt) {                  // (the index is the kernels' work: the model's holds the record count and the format)
-    md_alive(m, "index");
-    if (!m->sort->finished) return SVX_E_STATE;
-    const uint64_t n = m->sort->rows.size();
-    m->index.assign(12, 0); memcpy(m->index.data(), &n, 8); memcpy(m->index.data() + 8, &fmt, 4); m->have_index = true;
-    return SVX_OK;
-}
-bool mergedev_index_bytes(const MergeDev* m, int64_t* n) { md_alive(m, "index_bytes"); if (m->have_index && n) *n = (int64_t)m->index.size(); return m->have_index; }
-int mergedev_index_fetch(MergeDev* m, uint8_t* dst) { md_alive(m, "index_fetch"); memcpy(dst, m->index.data(), m->index.size()); return SVX_OK; }
-int mergedev_permutation(MergeDev* m, uint32_t* perm) { return model_permutation(md_alive(m, "permutation")->sort, perm); }
-void mergedev_stats(const MergeDev* m, svx_bam_sort_stats* a, svx_bam_sort_spill_stats* b, int64_t* c, int64_t* r, int64_t* by, double* t) {
-    md_alive(m, "stats"); memset(a, 0, sizeof *a); memset(b, 0, sizeof *b); *c = *r = *by = 0; *t = 0;
-}
+void mergedev_feed(MergeDev* m, svx_devdec* d, int64_t map_at, int32_t n_ref_file, bool identity) { md_alive(m, "feed"); devdec_feed_set(d, &m->out, m->maps->data() + map_at, n_ref_file, identity); }
+SortOut* mergedev_sort_out(MergeDev* m) { return &md_alive(m, "sort_out")->out; }
 
 // ---- inputs and a plain reimplementation of the merge ---------------------------------------------------------------------------------------------------------
 static void put32(std::vector<uint8_t>& v, uint32_t x) { for (int k = 0; k < 4; k++) v.push_back((uint8_t)(x >> (8 * k))); }

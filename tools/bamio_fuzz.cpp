@@ -37,19 +37,23 @@ struct MockSlot {
                      flag = nullptr; tid = pos = lseq = read_id = nullptr; mapq = nullptr; order = seg_off = cigar = nullptr; cigar_off = seq_off = seg_cigar_off = nullptr; n_rec = 0; tail_start = 0; }
 };
 #ifdef BAMIO_FUZZ_SORT_MODEL       /* (tools/bam_merge_session_test.cpp: the decoder's own sort and a merge session's feed over a CPU model of the sort) */
-struct BamSort;
 struct svx_devdec;
 static int model_after_load(svx_devdec* d, const MockSlot& S, const uint64_t* rec, size_t n_rec);
+static void model_create_decoder(svx_devdec* d);
 static void model_destroy_decoder(svx_devdec* d);
 #endif
 struct svx_devdec { MockSlot slot[3]; std::vector<std::string> names; std::vector<int32_t> rank; long long loads = 0;
 #ifdef BAMIO_FUZZ_SORT_MODEL
-                    BamSort* sort = nullptr; bool sort_on = false; BamSort* feed = nullptr; const int32_t* feed_map = nullptr; int32_t feed_n_ref = 0; bool feed_identity = true;
+                    SortOut* out = nullptr; SortOut* feed = nullptr; const int32_t* feed_map = nullptr; int32_t feed_n_ref = 0; bool feed_identity = true;
 #endif
 };
 static uint32_t m32(const uint8_t* p) { return p[0] | (p[1] << 8) | (p[2] << 16) | ((uint32_t)p[3] << 24); }
 int devdec_create(int, int, int32_t n_ref, const int32_t*, const char*, const int32_t* contig_rank, svx_devdec** out) {
-    svx_devdec* d = new svx_devdec(); d->rank.assign(contig_rank, contig_rank + n_ref); *out = d; return SVX_OK;
+    svx_devdec* d = new svx_devdec(); d->rank.assign(contig_rank, contig_rank + n_ref);
+#ifdef BAMIO_FUZZ_SORT_MODEL
+    model_create_decoder(d);
+#endif
+    *out = d; return SVX_OK;
 }
 void devdec_destroy(svx_devdec* d) {
     if (!d) return;
@@ -161,22 +165,11 @@ void devdec_index_stats(const svx_devdec*, svx_bam_index_stats* out) { memset(ou
 #ifndef BAMIO_FUZZ_SORT_MODEL       /* (a program that defines it brings these itself, over a model of the sort, and links bamsort_host.cpp) */
 // (so is the coordinate sort; the header rewrite it asks the host for lives in bamsort_host.cpp, which this program does not link)
 int devdec_sort_begin(svx_devdec*, int64_t, const char*, int) { return SVX_E_STATE; }
-void devdec_sort_drop(svx_devdec*) {}
 bool devdec_sort_on(const svx_devdec*) { return false; }
-bool devdec_sort_finished(const svx_devdec*) { return false; }
-int devdec_sort_finish(svx_devdec*, const uint8_t*, int64_t) { return SVX_E_STATE; }
-void devdec_sort_count(const svx_devdec*, int64_t*, int64_t*, int64_t*) {}
-int devdec_sort_encode(svx_devdec*, int64_t, int64_t, int64_t*) { return SVX_E_STATE; }
-int devdec_sort_fetch(svx_devdec*, uint8_t*, uint8_t*) { return SVX_E_STATE; }
-int devdec_sort_index(svx_devdec*, int) { return SVX_E_STATE; }
-int devdec_sort_permutation(svx_devdec*, uint32_t*) { return SVX_E_STATE; }
-void devdec_sort_stats(const svx_devdec*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
-void devdec_sort_spill_stats(const svx_devdec*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
-void devdec_sort_name_stats(const svx_devdec*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
 extern "C" int svx_bam_sort_header_host(const uint8_t*, int64_t, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
 extern "C" int svx_bam_sort_header_host_order(const uint8_t*, int64_t, int, uint8_t*, int64_t, int64_t*) { return SVX_E_STATE; }
 // (and the merge session of several files, which is fed by that sort's appends)
-void devdec_feed_set(svx_devdec*, BamSort*, void*, const int32_t*, int32_t, bool) {}
+void devdec_feed_set(svx_devdec*, SortOut*, const int32_t*, int32_t, bool) {}
 void devdec_feed_clear(svx_devdec*) {}
 bool devdec_feed_on(const svx_devdec*) { return false; }
 int devdec_device(const svx_devdec*) { return 0; }
@@ -184,16 +177,23 @@ int mergedev_create(int, int64_t, int32_t, const char*, const int32_t*, int64_t,
 void mergedev_destroy(MergeDev*) {}
 int mergedev_device(const MergeDev*) { return 0; }
 void mergedev_feed(MergeDev*, svx_devdec*, int64_t, int32_t, bool) {}
-void mergedev_drop(MergeDev*) {}
-int mergedev_finish(MergeDev*, const uint8_t*, int64_t) { return SVX_E_STATE; }
-void mergedev_count(const MergeDev*, int64_t*, int64_t*, int64_t*) {}
-int mergedev_encode(MergeDev*, int64_t, int64_t, int64_t*) { return SVX_E_STATE; }
-int mergedev_fetch(MergeDev*, uint8_t*, uint8_t*) { return SVX_E_STATE; }
-int mergedev_index(MergeDev*, int) { return SVX_E_STATE; }
-bool mergedev_index_bytes(const MergeDev*, int64_t*) { return false; }
-int mergedev_index_fetch(MergeDev*, uint8_t*) { return SVX_E_STATE; }
-int mergedev_permutation(MergeDev*, uint32_t*) { return SVX_E_STATE; }
-void mergedev_stats(const MergeDev*, svx_bam_sort_stats* a, svx_bam_sort_spill_stats* b, int64_t* c, int64_t* r, int64_t* by, double* t) { memset(a, 0, sizeof *a); memset(b, 0, sizeof *b); *c = *r = *by = 0; *t = 0; }
+// (and what both end as: a sort that never begins is never finished, so only these are reached)
+SortOut* devdec_sort_out(svx_devdec*) { return nullptr; }
+SortOut* mergedev_sort_out(MergeDev*) { return nullptr; }
+bool sortout_finished(const SortOut*) { return false; }
+void sortout_drop(SortOut*) {}
+int sortout_finish(SortOut*, const uint8_t*, int64_t) { return SVX_E_STATE; }
+void sortout_count(const SortOut*, int64_t*, int64_t*, int64_t*) {}
+int sortout_encode(SortOut*, int64_t, int64_t, int64_t*) { return SVX_E_STATE; }
+int sortout_fetch(SortOut*, uint8_t*, uint8_t*) { return SVX_E_STATE; }
+int sortout_index(SortOut*, int) { return SVX_E_STATE; }
+bool sortout_index_bytes(const SortOut*, int64_t*) { return false; }
+int sortout_index_fetch(SortOut*, uint8_t*) { return SVX_E_STATE; }
+int sortout_permutation(SortOut*, uint32_t*) { return SVX_E_STATE; }
+void sortout_stats(const SortOut*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_spill_stats(const SortOut*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_name_stats(const SortOut*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_translate_stats(const SortOut*, int64_t* c, int64_t* r, int64_t* by, double* t) { *c = *r = *by = 0; *t = 0; }
 extern "C" int svx_bam_merge_header_host(const uint8_t* const*, const int64_t*, int64_t, uint8_t*, int64_t, int64_t*, int32_t*) { return SVX_E_STATE; }
 #endif
 // SAM text (svx_sam_open): the front end is the device's (sam.hip) and the header parser sam_host.cpp's; neither is part of this program
