@@ -820,8 +820,9 @@ int  svx_bam_sort_header_host(const uint8_t* header, int64_t n_bytes, uint8_t* o
  * l_read_name = 0 or 32 + l_read_name > block_size (SVX_E_ARG, which goes before SVX_E_RANGE).  The permutation comes from one stable 4-bit radix pass by
  * name_rank and then most-significant-first rounds of 4 name bytes over the rows whose order is still open, at most 64 of them; a round costs the host one
  * 8-byte read-back.  A query-name-sorted file has no index: svx_bam_sort_index and svx_bam_sort_index_fmt answer SVX_E_STATE after such a sort.
- * Not built, and refused: a spilled query-name sort (svx_bam_sort_begin_spill is coordinate order; a query-name sort that passes max_bytes ends with
- * SVX_E_CAPACITY as an in-memory coordinate sort does), a merge session in query-name order (svx_bam_merge_*), samtools' natural order (-n).
+ * Not built, and refused: a spilled query-name sort of the READER (svx_bam_sort_begin_spill is coordinate order; a query-name sort that passes max_bytes ends
+ * with SVX_E_CAPACITY as an in-memory coordinate sort does; a merge session over the one file with a spill directory, svx_bam_merge_open_order below, is that
+ * sort), samtools' natural order (-n).
  * svx_bam_sort_get_name_stats: valid after the finish of a query-name sort (zeros otherwise): rounds run, rows that took part in round r (active_rows[r],
  * r < 64), their sum and maximum, and the host-clock times of the phases of finish with the stream drained at each edge. */
 #define SVX_SORT_COORDINATE 0
@@ -851,6 +852,17 @@ int  svx_bam_merge_header_host(const uint8_t* const* headers, const int64_t* siz
  * SVX_E_ARG for a mate id outside a translated file's dictionary or a map entry outside [0, n_ref_merged). */
 int  svx_bam_merge_host(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, uint8_t* out,
                         uint32_t* perm, int64_t perm_cap, int64_t* n_records);
+/* host-only: the two calls above in the order asked for (they are these with SVX_SORT_COORDINATE; any other order than the two: SVX_E_ARG).  In
+ * SVX_SORT_QUERYNAME rule 1 of the header takes the first line of the first file's header as svx_bam_sort_header_host_order rewrites it (one file: that whole
+ * header), the records are translated exactly as above and compare by (name, name_rank), stable over the record numbers of the concatenation, and the two name
+ * refusals of svx_bam_sort_host_order hold per file (SVX_E_ARG in any file before SVX_E_RANGE in any file). */
+int  svx_bam_merge_header_host_order(const uint8_t* const* headers, const int64_t* sizes, int64_t k, int order, uint8_t* out, int64_t cap, int64_t* n_out, int32_t* tid_maps_out);
+int  svx_bam_merge_host_order(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, int order,
+                              uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records);
+/* host-only, for tests: one name (1..255 bytes, no NUL) packed at word word_off of a name table of tab_words 32-bit words (bamsort_core.hpp: bsort_name_tab_*)
+ * -> how many of the rounds 0..63 read another word from the table than from the name itself, plus the words written outside the name's own (0: none);
+ * SVX_E_ARG for a name that does not fit. */
+int  svx_bam_name_tab_check_host(const uint8_t* name, int32_t name_len, int64_t word_off, int64_t tab_words);
 /* ---- the merge on the device: a session that readers only feed (bammerge.hip, bamsort.hip: k_bs_translate) ----
  * A session is an object of its own.  It owns its sort, its HIP stream and its output index; a reader never owns any of it, and a reader's own sort
  * (svx_bam_sort_*) and index are not touched by a merge.
@@ -891,6 +903,24 @@ int  svx_bam_merge_get_stats(svx_bam_merge* m, svx_bam_sort_stats* out);
 int  svx_bam_merge_get_spill_stats(svx_bam_merge* m, svx_bam_sort_spill_stats* out);
 int  svx_bam_merge_get_merge_stats(svx_bam_merge* m, svx_bam_merge_stats* out);
 void svx_bam_merge_close(svx_bam_merge* m);
+/* ---- a merge session in query-name order, spilled runs too (bamsort.hip: k_ns_pack, k_ns_keys_tab) ----
+ * svx_bam_merge_open_order: svx_bam_merge_open is this call with SVX_SORT_COORDINATE; any other order than the two: SVX_E_ARG.  With SVX_SORT_QUERYNAME the
+ * merged header is svx_bam_merge_header_host_order's and the merged file svx_bam_merge_host_order's.  Without a spill directory, or when no run is closed,
+ * finish is the in-memory query-name sort over all files.  With one, a run that closes is sorted by name on the device and its names stay there in a table
+ * of aligned words while its records go to the spill file; a record finish would refuse with SVX_E_ARG (refID, mate id, record size, name field) fails the
+ * svx_bam_merge_add that closes its run, a position below -1 waits for finish (SVX_E_RANGE, behind every SVX_E_ARG).  Finish merges the runs by the same rank
+ * pass and rounds over the table.  A session over ONE file with a spill directory is the spilled query-name sort of that file.  No index:
+ * svx_bam_merge_index_fmt answers SVX_E_STATE after a query-name finish.
+ * svx_bam_merge_get_name_stats: svx_bam_sort_get_name_stats for the session; after a finish over closed runs it describes the merge's rounds.
+ * svx_bam_merge_get_name_spill_stats: the runs closed in query-name order - their number, the rounds and active rows summed over the runs' own sorts, the
+ * bytes of the name table at finish, the host-clock times of the runs' name sorts and of the table's packing (zeros when no run was closed). */
+typedef struct svx_bam_name_spill_stats {
+    int64_t n_runs, run_rounds, run_active_rows, table_bytes;
+    double  t_run_sort_ms, t_pack_ms;
+} svx_bam_name_spill_stats;
+int  svx_bam_merge_open_order(svx_bam* const* readers, int64_t k, int device, int64_t max_bytes, const char* spill_dir_or_null, int order, svx_bam_merge** out);
+int  svx_bam_merge_get_name_stats(svx_bam_merge* m, svx_bam_name_sort_stats* out);
+int  svx_bam_merge_get_name_spill_stats(svx_bam_merge* m, svx_bam_name_spill_stats* out);
 
 /* ---- SAM text through the device reader (sam.hip, sam_core.hpp; the definition in words: svim_amd/sam.py) ----
  * svx_sam_open gives the handle type of svx_bam_open for a file of uncompressed SAM text (what an aligner writes): the header is parsed on the host

@@ -318,6 +318,14 @@ class BamNameSortStats(C.Structure):
         return d
 
 
+class BamNameSpillStats(C.Structure):
+    """svx_bam_name_spill_stats: the runs a merge session closed in query-name order (svx_bam_merge_open_order with a spill directory); zeros without any"""
+    _fields_ = [(n, C.c_int64) for n in ("n_runs", "run_rounds", "run_active_rows", "table_bytes")] + [(n, C.c_double) for n in ("t_run_sort_ms", "t_pack_ms")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class BamMergeStats(C.Structure):
     """svx_bam_merge_stats: a merge session (svx_bam_merge_*): its files, the merged dictionary, what k_bs_translate did"""
     _fields_ = [(n, C.c_int64) for n in ("n_files", "n_added", "n_ref_merged", "header_bytes", "n_translated_files", "n_translated_chunks", "n_translated_records",

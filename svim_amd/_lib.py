@@ -40,7 +40,8 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_bam_sort_permutation", "svx_bam_sort_get_stats", "svx_bam_sort_host", "svx_bam_sort_header_host", "svx_bam_sort_begin_spill", "svx_bam_sort_get_spill_stats",
            "svx_bam_sort_spill_host",
            "svx_bam_sort_begin_order", "svx_bam_sort_get_name_stats", "svx_bam_sort_host_order", "svx_bam_sort_header_host_order",
-           "svx_bam_merge_header_host", "svx_bam_merge_host",
+           "svx_bam_merge_header_host", "svx_bam_merge_host", "svx_bam_merge_header_host_order", "svx_bam_merge_host_order", "svx_bam_name_tab_check_host",
+           "svx_bam_merge_open_order", "svx_bam_merge_get_name_stats", "svx_bam_merge_get_name_spill_stats",
            "svx_bam_merge_open", "svx_bam_merge_add", "svx_bam_merge_finish", "svx_bam_merge_count", "svx_bam_merge_encode", "svx_bam_merge_fetch", "svx_bam_merge_index_fmt",
            "svx_bam_merge_index_count", "svx_bam_merge_index_fetch", "svx_bam_merge_permutation", "svx_bam_merge_get_stats", "svx_bam_merge_get_spill_stats",
            "svx_bam_merge_get_merge_stats", "svx_bam_merge_close",
@@ -303,11 +304,12 @@ def bam_sort_header_host(header, order="coordinate"):
     return out[:n.value].tobytes()
 
 
-def bam_merge_header_host(headers):
-    """svx_bam_merge_header_host (host-only): the header of the merged file of the files whose headers (magic .. dictionary) are given, in that order, and the
+def bam_merge_header_host(headers, order="coordinate"):
+    """svx_bam_merge_header_host_order (host-only; order: "coordinate" or "queryname"): the header of the merged file of the files whose headers (magic .. dictionary) are given, in that order, and the
     maps of their reference ids into the merged dictionary -> (header bytes, [map per file]), as svim_amd.bammerge.merged_header and tid_maps define them.
     svim_amd.bammerge.BamMergeError (code E_ARG) for what the definition refuses."""
     from . import bammerge
+    which = _abi.sort_order(order)
     headers = [bytes(h) for h in headers]
     k = len(headers)
     if k < 1:
@@ -323,7 +325,7 @@ def bam_merge_header_host(headers):
     n, cap = C.c_int64(), 0
     for _ in range(2):
         out = np.zeros(max(1, cap), dtype=np.uint8)
-        rc = lib().svx_bam_merge_header_host(ptrs, ptr(sizes), C.c_int64(k), ptr(out), C.c_int64(cap), C.byref(n), ptr(maps))
+        rc = lib().svx_bam_merge_header_host_order(ptrs, ptr(sizes), C.c_int64(k), C.c_int(which), ptr(out), C.c_int64(cap), C.byref(n), ptr(maps))
         if rc != _abi.SVX_E_CAPACITY:
             break
         cap = n.value
@@ -338,10 +340,11 @@ def bam_merge_header_host(headers):
     return out[:n.value].tobytes(), out_maps
 
 
-def bam_merge_host(files, n_ref_merged):
-    """svx_bam_merge_host (host-only): files: per input (record stream in file order, n_ref, tid_map) -> (the merged record stream, the permutation over global
+def bam_merge_host(files, n_ref_merged, order="coordinate"):
+    """svx_bam_merge_host_order (host-only; order: "coordinate" or "queryname"): files: per input (record stream in file order, n_ref, tid_map) -> (the merged record stream, the permutation over global
     record numbers as a uint32 array), what svim_amd.bammerge.merge gives.  svim_amd.bammerge.BamMergeError (code E_ARG / E_RANGE) for what it refuses."""
     from . import bammerge
+    which = _abi.sort_order(order)
     files = [(bytes(s), int(nr), [int(t) for t in m]) for s, nr, m in files]
     k = len(files)
     if k < 1 or any(len(m) != nr for _, nr, m in files):
@@ -355,12 +358,24 @@ def bam_merge_host(files, n_ref_merged):
     out = np.zeros(max(1, total), dtype=np.uint8)
     cap = total // 36 + 1
     perm, n = np.zeros(cap, dtype=np.uint32), C.c_int64()
-    rc = lib().svx_bam_merge_host(ptrs, ptr(sizes), ptr(n_refs), C.c_int64(k), C.c_int32(int(n_ref_merged)), ptr(maps), ptr(out), ptr(perm), C.c_int64(cap), C.byref(n))
+    rc = lib().svx_bam_merge_host_order(ptrs, ptr(sizes), ptr(n_refs), C.c_int64(k), C.c_int32(int(n_ref_merged)), ptr(maps), C.c_int(which), ptr(out), ptr(perm), C.c_int64(cap),
+                                        C.byref(n))
     if rc in (_abi.SVX_E_ARG, _abi.SVX_E_RANGE):
         raise bammerge.BamMergeError(rc, "bam_merge_host: " + _abi.ERRORS[rc])
     if rc != 0:
         raise SvxError("svx_bam_merge_host failed: %s" % _abi.ERRORS.get(rc, rc))
     return out[:total].tobytes(), perm[:n.value].copy()
+
+
+def bam_name_tab_check_host(name, word_off, tab_words):
+    """svx_bam_name_tab_check_host (host-only): `name` (1..255 bytes) packed at word word_off of a name table of tab_words words (csrc/bamsort_core.hpp:
+    bsort_name_tab_pack) -> the rounds 0..63 at which bsort_name_tab_word differs from bsort_name_word, plus the words written outside the name's own"""
+    name = bytes(name)
+    buf = np.frombuffer(name, dtype=np.uint8) if name else np.zeros(1, np.uint8)
+    rc = lib().svx_bam_name_tab_check_host(ptr(buf), C.c_int32(len(name)), C.c_int64(int(word_off)), C.c_int64(int(tab_words)))
+    if rc < 0:
+        raise SvxError("svx_bam_name_tab_check_host failed: %s" % _abi.ERRORS.get(rc, rc))
+    return rc
 
 
 def sam_convert_host(text, references, cap=None):

@@ -410,7 +410,9 @@ class NativeBam(_SortedOutput):
 
 class BamMerge(_SortedOutput):
     """A merge session on the device (svx_bam_merge_*; svim_amd/bammerge.py says what the merged file is): several files, in the order given, into one file in
-    coordinate order.  The session owns its sort, its stream and its index; readers only feed it.
+    coordinate order, or with order="queryname" in query-name order (no index then; with a spill_dir the runs are sorted by name and merged from a table of
+    their names that stays on the device: a session over one file is the spilled query-name sort of that file).  The session owns its sort, its stream and
+    its index; readers only feed it.
         m = BamMerge.open(readers, device=0)     # reads headers and dictionaries; keeps nothing of the readers, which may be closed at once
         for r in readers: m.add(r)               # file by file, in the order of open: the call reads the whole file and returns when the reader is idle again
         n_records, n_bytes, n_blocks = m.finish()
@@ -423,14 +425,15 @@ class BamMerge(_SortedOutput):
         self.h, self.L = handle, L
 
     @classmethod
-    def open(cls, readers, device=0, max_bytes=0, spill_dir=None):
+    def open(cls, readers, device=0, max_bytes=0, spill_dir=None, order="coordinate"):
         L = lib()
         readers = list(readers)
         if not readers:
             raise ValueError("BamMerge.open: no reader")
         arr = (C.c_void_p * len(readers))(*[r.h for r in readers])
         h = C.c_void_p()
-        rc = L.svx_bam_merge_open(arr, C.c_int64(len(readers)), C.c_int(int(device)), C.c_int64(int(max_bytes)), None if spill_dir is None else os.fsencode(spill_dir), C.byref(h))
+        rc = L.svx_bam_merge_open_order(arr, C.c_int64(len(readers)), C.c_int(int(device)), C.c_int64(int(max_bytes)), None if spill_dir is None else os.fsencode(spill_dir),
+                                        C.c_int(_abi.sort_order(order)), C.byref(h))
         if rc != 0:
             raise cls._error_of(L, rc, "svx_bam_merge_open")
         return cls(h, L)
@@ -466,8 +469,16 @@ class BamMerge(_SortedOutput):
 
     def index(self, fmt="bai"):
         """-> the bytes of the merged file's .bai, or with fmt="csi" the uncompressed bytes of its .csi, after every block has been encoded; svim_amd.bai.BaiError
-        (E_RANGE) when a record ends beyond 2^29 of a .bai"""
+        (E_RANGE) when a record ends beyond 2^29 of a .bai.  A session in query-name order has no index: BamMergeError with .code SVX_E_STATE"""
         return self._out_index(fmt)
+
+    def name_stats(self):
+        """the permutation of a session in query-name order (svx_bam_merge_get_name_stats: NativeBam.sort_name_stats for the session; after a finish over
+        closed runs the merge's rounds), and under "spill" the runs closed in that order (svx_bam_merge_get_name_spill_stats): their number, rounds and
+        active rows summed over the runs' sorts, the name table's bytes, the times of the runs' name sorts and of the table's packing"""
+        d = self._out_stats("get_name_stats", _abi.BamNameSortStats)
+        d["spill"] = self._out_stats("get_name_spill_stats", _abi.BamNameSpillStats)
+        return d
 
     def permutation(self):
         """uint32 array: for every record of the merged order its place in the concatenation of the files"""

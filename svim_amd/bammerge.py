@@ -29,7 +29,19 @@ What the merged file is:
                    before the line is compared with what is written).  PG:Z tags inside records are NOT rewritten: a stated limitation.
               l_text is the new length (no NUL padding); the binary dictionary is the merged one.
   stream, file, index: as in bamsort.py - blocks of 65 280 stream bytes, the bytes svx_text_gz_host writes, the .bai / .csi of bai.py / csi.py over the merged
-              dictionary.  As there, byte identity with samtools merge is not claimed."""
+              dictionary.  As there, byte identity with samtools merge is not claimed.
+
+Query-name order (order="queryname" as the last keyword of merged_text, merged_header, merge, stream_of and file; the default leaves every byte as it is) - the
+input of the query-name front end when a run comes as one file per flow cell:
+  records     translated exactly as above, per file.  The two name refusals of bamsort.split_records(order="queryname") - l_read_name = 0, a name field that
+              runs past the record - are E_ARG like a bad refID or mate id; an E_ARG in ANY file goes before an E_RANGE in any file.
+  order       bamsort.name_key of the translated record (the key ignores the ids), stable over global record numbers: equal (name, rank) leave in file
+              order, then in in-file order.
+  header      one input: bamsort.sorted_header(header, "queryname") - the merge of one file is the name sort of that file byte for byte.  Several inputs:
+              rule 1 takes the first line of sorted_header(first file, "queryname") (SO:queryname followed by SS:queryname:lexicographical); rules 2 to 5
+              are unchanged.
+  index       none.
+  runs        bamsort.runs_of(..., order="queryname") keys the runs by name_key; merge_runs and piece_cuts stay as they are (tuples compare)."""
 import struct
 
 from . import bamsort
@@ -94,10 +106,11 @@ def _field(line, tag):
     return None
 
 
-def merged_text(texts, refs):
-    """the text of the merged header of several files (rule 1 to 5 above); texts: each cut at its first NUL already; refs: the merged dictionary"""
+def merged_text(texts, refs, order="coordinate"):
+    """the text of the merged header of several files (rule 1 to 5 above); texts: each cut at its first NUL already; refs: the merged dictionary;
+    order="queryname": rule 1 takes the first line of sorted_header(first file, "queryname")"""
     lines_of = [[ln for ln in t.split(b"\n") if ln] for t in texts]
-    first = parse_header(bamsort.sorted_header(b"BAM\1" + struct.pack("<i", len(texts[0])) + texts[0] + struct.pack("<i", 0)))[0]
+    first = parse_header(bamsort.sorted_header(b"BAM\1" + struct.pack("<i", len(texts[0])) + texts[0] + struct.pack("<i", 0), order))[0]
     out = [first.split(b"\n")[0]]
     written = set(out)
     if any(ln.startswith(b"@SQ\t") for lines in lines_of for ln in lines):
@@ -144,16 +157,17 @@ def merged_text(texts, refs):
     return b"".join(ln + b"\n" for ln in out)
 
 
-def merged_header(headers):
-    """headers: per file the bytes magic .. dictionary -> the header of the merged file"""
+def merged_header(headers, order="coordinate"):
+    """headers: per file the bytes magic .. dictionary -> the header of the merged file (order: "coordinate" or "queryname")"""
+    bamsort._order(order)
     headers = [bytes(h) for h in headers]
     if not headers:
         raise BamMergeError(E_ARG, "no input")
     if len(headers) == 1:
-        return bamsort.sorted_header(headers[0])
+        return bamsort.sorted_header(headers[0], order)
     parsed = [parse_header(h) for h in headers]
     refs = merged_dictionary([p[1] for p in parsed])
-    text = merged_text([p[0] for p in parsed], refs)
+    text = merged_text([p[0] for p in parsed], refs, order)
     out = [b"BAM\1", struct.pack("<i", len(text)), text, struct.pack("<i", len(refs))]
     for name, length in refs:
         out.append(struct.pack("<i", len(name) + 1) + name + b"\0" + struct.pack("<i", length))
@@ -173,8 +187,9 @@ def translate_record(rec, tid_map):
     return rec[:4] + struct.pack("<i", m(ref_id)) + rec[8:24] + struct.pack("<i", m(mate)) + rec[28:]
 
 
-def _split(stream, n_ref):
-    """bamsort.split_records, but what is wrong is handed back instead of raised: (records, a refID outside the dictionary, a position below -1)"""
+def _split(stream, n_ref, by_name=False):
+    """bamsort.split_records, but what is wrong is handed back instead of raised: (records, a refID outside the dictionary - by_name: or one of the two name
+    refusals of query-name order -, a position below -1)"""
     stream = bytes(stream)
     out, p, bad_arg, bad_range = [], 0, False, False
     while p < len(stream):
@@ -185,20 +200,23 @@ def _split(stream, n_ref):
             raise BamMergeError(E_ARG, "block_size %d at offset %d: below 32, or the stream ends inside the record" % (size, p))
         ref_id, pos = struct.unpack_from("<ii", stream, p + 4)
         bad_arg |= ref_id < -1 or ref_id >= n_ref
+        bad_arg |= by_name and (stream[p + 12] == 0 or 32 + stream[p + 12] > size)
         bad_range |= pos < -1
         out.append(stream[p:p + 4 + size])
         p += 4 + size
     return out, bad_arg, bad_range
 
 
-def merge(files):
-    """files: per input (record stream in file order, n_ref, tid_map) -> (the merged record stream, the permutation over global record numbers)"""
+def merge(files, order="coordinate"):
+    """files: per input (record stream in file order, n_ref, tid_map) -> (the merged record stream, the permutation over global record numbers);
+    order="queryname": the key is bamsort.name_key of the translated record, and the two name refusals are E_ARG"""
+    by_name = bamsort._order(order)
     recs, bad_arg, bad_range = [], False, False
     for stream, n_ref, tmap in files:
         tmap = [int(t) for t in tmap]
         if len(tmap) != n_ref:
             raise BamMergeError(E_ARG, "a map needs one entry per reference of its file")
-        rs, a, r = _split(stream, n_ref)
+        rs, a, r = _split(stream, n_ref, by_name)
         bad_arg, bad_range = bad_arg or a, bad_range or r
         if tmap != list(range(n_ref)):
             for i, rec in enumerate(rs):
@@ -208,14 +226,15 @@ def merge(files):
                     bad_arg = True
         recs += rs
     if bad_arg:
-        raise BamMergeError(E_ARG, "a record names a reference, or a translated record a mate reference, that its file's header does not have")
+        raise BamMergeError(E_ARG, "a record names a reference, or a translated record a mate reference, that its file's header does not have"
+                            + (", or has no name field or one that runs past its end" if by_name else ""))
     if bad_range:
         raise BamMergeError(E_RANGE, "a record has a position below -1")
-    perm = bamsort.permutation(recs)
+    perm = bamsort.permutation(recs, order)
     return b"".join(recs[k] for k in perm), perm
 
 
-def stream_of(raws):
+def stream_of(raws, order="coordinate"):
     """raws: the inflated bytes of every input file -> (the inflated bytes of the merged file, the permutation)"""
     parts = [bamsort.split_header(bytes(raw)) for raw in raws]
     headers = [h for h, _, _ in parts]
@@ -223,8 +242,8 @@ def stream_of(raws):
         maps = [list(range(parts[0][1]))]
     else:
         maps = tid_maps([parse_header(h)[1] for h in headers])
-    header = merged_header(headers)
-    stream, perm = merge([(raw[at:], n_ref, m) for raw, (_, n_ref, at), m in zip(raws, parts, maps)])
+    header = merged_header(headers, order)
+    stream, perm = merge([(raw[at:], n_ref, m) for raw, (_, n_ref, at), m in zip(raws, parts, maps)], order)
     return header + stream, perm
 
 
@@ -271,7 +290,7 @@ def header_of(path):
                 return raw[:size]
 
 
-def file(paths):
+def file(paths, order="coordinate"):
     """the bytes of the merged file of the BAM files at `paths` (the library's host build of the encoder compresses the stream: no GPU)"""
     from ._lib import text_gz_host
-    return text_gz_host(stream_of([bamsort.inflate(p) for p in paths])[0])
+    return text_gz_host(stream_of([bamsort.inflate(p) for p in paths], order)[0])

@@ -29,7 +29,8 @@ front end, which needs the records of a read next to each other:
   refusals    those above, and E_ARG for l_read_name = 0 and for a name field that runs past the record (32 + l_read_name > block_size).  E_ARG before E_RANGE.
   header      the same rule with SO:queryname; GO: and every SS: field are removed and SS:queryname:lexicographical is put behind the (first) SO: field.  A
               text without an @HD line gets "@HD\tVN:1.6\tSO:queryname\tSS:queryname:lexicographical\n" in front.
-  stream, file  as above.  A query-name-sorted file has no index, and spilled sorts and merges stay in coordinate order."""
+  stream, file  as above.  A query-name-sorted file has no index.  sort_begin / sort_bam sort in this order in memory only; beyond device memory and over several
+              files the order is a merge session's (svim_amd/bammerge.py, order="queryname"; runs_of(order="queryname") forms its runs)."""
 import struct
 
 E_ARG, E_RANGE = -3, -10
@@ -163,15 +164,17 @@ def sort_records(stream, n_ref, order="coordinate"):
     return b"".join(recs[k] for k in perm), perm
 
 
-def runs_of(stream, n_ref, run_ends):
+def runs_of(stream, n_ref, run_ends, order="coordinate"):
     """The spilled sort (svx_bam_sort_begin_spill) forms runs: consecutive ranges of the file, each sorted on its own.  stream: records in file order;
     run_ends: the number of records in front of the end of every run, non-decreasing (equal neighbours: an empty run), the last one the number of records
-    -> one list per run of (sort key, file index, record bytes), in the run's stable order.  The bytes of a run, joined, are its part of the spill file."""
-    recs = list(stream) if isinstance(stream, (list, tuple)) else split_records(stream, n_ref)      # (a list: records already split and checked)
+    -> one list per run of (sort key, file index, record bytes), in the run's stable order.  The bytes of a run, joined, are its part of the spill file.
+    order="queryname": the key is name_key (a merge session with a spill directory forms such runs); merge_runs and piece_cuts take them as they are."""
+    key = name_key if _order(order) else sort_key
+    recs = list(stream) if isinstance(stream, (list, tuple)) else split_records(stream, n_ref, order)      # (a list: records already split and checked)
     run_ends = [int(e) for e in run_ends]
     if any(b < a for a, b in zip([0] + run_ends, run_ends)) or (run_ends[-1] if run_ends else 0) != len(recs):
         raise ValueError("run_ends must be non-decreasing and end with the number of records")
-    return [[(sort_key(recs[k][4:]), k, recs[k]) for k in sorted(range(a, b), key=lambda k: sort_key(recs[k][4:]))] for a, b in zip([0] + run_ends, run_ends)]
+    return [[(key(recs[k][4:]), k, recs[k]) for k in sorted(range(a, b), key=lambda k: key(recs[k][4:]))] for a, b in zip([0] + run_ends, run_ends)]
 
 
 def merge_runs(runs):

@@ -61,7 +61,7 @@ void svx_guard_free(void* p) {
 }
 
 extern "C" const char* svx_last_error(void) { return g_svx_err.c_str(); }
-extern "C" int svx_version(void) { return 108; }
+extern "C" int svx_version(void) { return 109; }
 
 extern "C" int svx_ctx_create(int device_ordinal, svx_ctx** out) {
     int ndev = 0;

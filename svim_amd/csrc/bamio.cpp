@@ -1395,8 +1395,8 @@ extern "C" void svx_bam_merge_close(svx_bam_merge* m) {
     mergedev_destroy(m->dev); m->dev = nullptr;
     delete m;
 }
-extern "C" int svx_bam_merge_open(svx_bam* const* readers, int64_t k, int device, int64_t max_bytes, const char* spill_dir, svx_bam_merge** out) {
-    if (!readers || k < 1 || max_bytes < 0 || !out) return bam_fail(SVX_E_ARG, "svx_bam_merge_open: bad argument");
+extern "C" int svx_bam_merge_open_order(svx_bam* const* readers, int64_t k, int device, int64_t max_bytes, const char* spill_dir, int order, svx_bam_merge** out) {
+    if (!readers || k < 1 || max_bytes < 0 || !out || (order != SVX_SORT_COORDINATE && order != SVX_SORT_QUERYNAME)) return bam_fail(SVX_E_ARG, "svx_bam_merge_open: bad argument");
     for (int64_t f = 0; f < k; f++) if (!readers[f]) return bam_fail(SVX_E_ARG, "svx_bam_merge_open: null reader");
     const double t0 = now_s();
     svx_bam_merge* m = new svx_bam_merge();
@@ -1417,8 +1417,8 @@ extern "C" int svx_bam_merge_open(svx_bam* const* readers, int64_t k, int device
     // the header rule and its refusals, before any device work
     std::vector<int32_t> maps((size_t)std::max<int64_t>(n_maps, 1), 0);
     int64_t n = 0;
-    int rc = svx_bam_merge_header_host(ptrs.data(), sizes.data(), k, nullptr, 0, &n, maps.data());
-    if (rc == SVX_E_CAPACITY) { m->header.resize((size_t)n); rc = svx_bam_merge_header_host(ptrs.data(), sizes.data(), k, m->header.data(), n, &n, maps.data()); }
+    int rc = svx_bam_merge_header_host_order(ptrs.data(), sizes.data(), k, order, nullptr, 0, &n, maps.data());
+    if (rc == SVX_E_CAPACITY) { m->header.resize((size_t)n); rc = svx_bam_merge_header_host_order(ptrs.data(), sizes.data(), k, order, m->header.data(), n, &n, maps.data()); }
     if (rc != SVX_OK) { svx_bam_merge_close(m); return bam_fail(rc, "svx_bam_merge_open: the headers cannot be merged (a reference name with two lengths or twice in one file, @RG lines with one ID and different bytes, or a header that cannot be walked)"); }
     {   // n_ref of the merged dictionary: behind the text of the header just made
         const uint8_t* p = m->header.data();
@@ -1434,11 +1434,14 @@ extern "C" int svx_bam_merge_open(svx_bam* const* readers, int64_t k, int device
             if (t != (int32_t)i) F.identity = false;
         }
     }
-    rc = mergedev_create(device, max_bytes, m->n_ref_merged, spill_dir, maps.data(), n_maps, &m->dev);
+    rc = mergedev_create(device, max_bytes, m->n_ref_merged, spill_dir, order, maps.data(), n_maps, &m->dev);
     if (rc != SVX_OK) { m->dev = nullptr; const std::string e = svx_last_error(); svx_bam_merge_close(m); return bam_fail(rc, e); }
     m->t_open = now_s() - t0;
     *out = m;
     return SVX_OK;
+}
+extern "C" int svx_bam_merge_open(svx_bam* const* readers, int64_t k, int device, int64_t max_bytes, const char* spill_dir, svx_bam_merge** out) {
+    return svx_bam_merge_open_order(readers, k, device, max_bytes, spill_dir, SVX_SORT_COORDINATE, out);
 }
 #define MERGE_USABLE(what) \
     if (!m) return bam_fail(SVX_E_ARG, what ": null session"); \
@@ -1540,6 +1543,16 @@ extern "C" int svx_bam_merge_get_stats(svx_bam_merge* m, svx_bam_sort_stats* out
 extern "C" int svx_bam_merge_get_spill_stats(svx_bam_merge* m, svx_bam_sort_spill_stats* out) {
     if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
     sortout_spill_stats(mergedev_sort_out(m->dev), out);
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_get_name_stats(svx_bam_merge* m, svx_bam_name_sort_stats* out) {
+    if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
+    sortout_name_stats(mergedev_sort_out(m->dev), out);
+    return SVX_OK;
+}
+extern "C" int svx_bam_merge_get_name_spill_stats(svx_bam_merge* m, svx_bam_name_spill_stats* out) {
+    if (!m || !out) return bam_fail(SVX_E_ARG, "null argument");
+    sortout_name_spill_stats(mergedev_sort_out(m->dev), out);
     return SVX_OK;
 }
 extern "C" int svx_bam_merge_get_merge_stats(svx_bam_merge* m, svx_bam_merge_stats* out) {

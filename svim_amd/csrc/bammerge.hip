@@ -16,7 +16,7 @@ struct MergeDev {
     SortOut out;                               // the sort, on `stream`, its index into `index`
 };
 
-int mergedev_create(int device, int64_t max_bytes, int32_t n_ref_merged, const char* spill_dir, const int32_t* maps, int64_t n_maps, MergeDev** out) {
+int mergedev_create(int device, int64_t max_bytes, int32_t n_ref_merged, const char* spill_dir, int order, const int32_t* maps, int64_t n_maps, MergeDev** out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device || device < 0) return svx_fail(SVX_E_NODEVICE, "svx_bam_merge_open: no such GPU", __FILE__, __LINE__, hipSuccess);
     HIPCHK(hipSetDevice(device));
@@ -25,7 +25,7 @@ int mergedev_create(int device, int64_t max_bytes, int32_t n_ref_merged, const c
     int rc = SVX_OK;
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) { m->stream = nullptr; rc = svx_fail(SVX_E_HIP, "svx_bam_merge_open: no stream", __FILE__, __LINE__, hipSuccess); }
     m->out.stream = m->stream;
-    if (rc == SVX_OK) rc = bamsort_begin(&m->out.sort, max_bytes, n_ref_merged, spill_dir);
+    if (rc == SVX_OK) rc = bamsort_begin(&m->out.sort, max_bytes, n_ref_merged, spill_dir, order);
     m->out.on = rc == SVX_OK;
     if (rc == SVX_OK) rc = bamindex_begin(&m->index);
     if (rc == SVX_OK) rc = m->maps.reserve((size_t)(n_maps > 0 ? n_maps : 1) * 4);

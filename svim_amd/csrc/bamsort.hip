@@ -9,7 +9,8 @@
 //            not the merged one passes k_bs_translate first: refID and next_refID mapped, patched in the slab by byte stores, the merged id in a column of its own
 //   finish   the keys sorted stably (svx_sort_pairs_u64_on over the key's used bits) with the record number as payload = the permutation; k_bs_layout the
 //            segments of the output stream (the header, then the records in order) with their lengths and addresses; a scan gives every segment's offset
-//            In query-name order (svx_bam_sort_begin_order; in memory only) the permutation comes from the names instead: the k_ns_* kernels below
+//            In query-name order (svx_bam_sort_begin_order; a merge session: svx_bam_merge_open_order) the permutation comes from the names instead: the
+//            k_ns_* kernels below.  Runs in that order (a session with a spill directory): "query-name order beyond device memory" below
 //   encode   a range of 65 280-byte blocks: k_bs_gather lays the stream bytes of the range out in the piece buffer, then the encoder's phases over the piece
 //            (textgz_kernels.hpp: CRC, matches, codes, bits, compaction), every block's compressed size kept on the host
 //   index    the sorted rows with the virtual offsets the block sizes give, through bamindex.hip's phases (bamindex_take_rows, bamindex_finish)
@@ -47,6 +48,7 @@
 #define BS_SEGS 512                   /* segments of a tile kept in LDS: a record is at least 36 bytes, so a tile touches at most 16384 / 36 + 2 = 457 */
 #define BS_MAX_GRID 2048
 #define BS_SPILL_PIECE (32ll << 20)   /* bytes of a run's stream gathered and written at a time (a multiple of 16) */
+#define BSORT_NAME_ROW_BYTES (26 + 37)  /* per record of a spilling query-name sort, in the free-memory rule of bamsort_append */
 #define BS_PAD 64                     /* bytes behind a slab, the header and the piece: the aligned loads around a record's last bytes stay inside the allocation */
 static_assert(BSORT_BLOCK == DEF_BLOCK, "the output's blocks are the encoder's");
 static_assert(BSORT_NAME_MAX_ROUNDS <= 64, "svx_bam_name_sort_stats.active_rows holds every round");
@@ -192,6 +194,49 @@ __global__ void k_ns_apply(long long m, const uint32_t* val, const int64_t* flag
     }
 }
 
+// ---- query-name order beyond device memory: runs and their merge ----------------------------------------------------------------------------------------
+// A run that closes in query-name order (bs_close_run) gets its permutation from the rank pass and the rounds above, over the open run's rows.  Its records
+// leave the device, so the NAMES stay: one table of 32-bit words (bamsort_core.hpp: bsort_name_tab_*), every name at a word's edge, zero-filled to the next.
+//   k_ns_tab_words  a thread per place of the run's order: the words its name takes (one entry more, 0, so that the scan ends with the run's total)
+//   k_ns_pack       a thread per place j of the run's order: the name of record order[j] copied byte by byte from its slab to tab[base + woff[j] ..] (a name is
+//                   4-byte aligned in its slab only by accident; the stores are whole words), and what stays per record beside rlen / rfile / roff: the word
+//                   offset (64 bits, in rkey's place: this order has no radix key), the name's length and the rank (a byte each)
+// The merge at finish (bs_finish_spilled) is the same rank pass and the same rounds over all n places of the concatenation of the runs, with
+//   k_ns_rank_keys  the ranks widened to the rank pass's keys
+//   k_ns_keys_tab   k_ns_keys with the word read from the table: one aligned 32-bit load per row and round instead of four byte loads through addr
+// Every sort is stable, the initial order is (run, place in the run), a run's own order is stable over file order and runs are consecutive ranges of the
+// global numbering: equal (name, rank) leave in global record order, which is the definition's rule for ties (svim_amd/bammerge.py).
+__global__ void k_ns_tab_words(long long m, const uint32_t* order, const uint8_t* name_len, int64_t* words) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > m) return;
+    words[j] = j == m ? 0 : (int64_t)bsort_name_tab_words(name_len[order[j]]);
+}
+__global__ void k_ns_pack(long long m, const uint32_t* order, const uint64_t* addr, const uint8_t* name_len, const int64_t* woff, uint64_t base, uint32_t* tab, uint64_t* rwoff,
+                          uint8_t* rnlen, uint8_t* rrank) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint32_t i = order[j];
+    const uint8_t* r = reinterpret_cast<const uint8_t*>(addr[i]);                 // (the record lies in its slab with its fixed fields and its name field: k_bs_rows, k_ns_names)
+    const uint32_t nl = name_len[i];
+    const uint64_t at = base + (uint64_t)woff[j];
+    bsort_name_tab_pack(r + BSORT_NAME_AT, nl, tab + at);                         // (reads nl bytes, writes bsort_name_tab_words(nl) words: the range the scan gave this name)
+    rwoff[j] = at; rnlen[j] = (uint8_t)nl;
+    rrank[j] = (uint8_t)bsort_name_rank((uint32_t)r[BSORT_FLAG_AT] | ((uint32_t)r[BSORT_FLAG_AT + 1] << 8));
+}
+__global__ void k_ns_rank_keys(long long n, const uint8_t* rrank, uint64_t* key) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < n) key[q] = (uint64_t)rrank[q];
+}
+// the m active rows of round r over the places of the concatenation of the runs (perm holds places q; rwoff, rnlen: per place)
+__global__ void k_ns_keys_tab(long long m, uint32_t r, const uint32_t* perm, const uint32_t* place, const uint32_t* seg, const uint32_t* tab, const uint64_t* rwoff, const uint8_t* rnlen,
+                              uint64_t* key, uint32_t* val) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= m) return;
+    const uint32_t q = perm[place ? place[k] : (uint32_t)k];
+    key[k] = ((uint64_t)(seg ? seg[k] : 0u) << 32) | bsort_name_tab_word(tab, rwoff[q], rnlen[q], r);      // (reads no word behind the name's own)
+    val[k] = q;
+}
+
 // ---- the gather -----------------------------------------------------------------------------------------------------------------------------------------
 struct BsSegs { const int64_t* soff; const uint64_t* saddr; long long n_seg; };      // soff: n_seg + 1 entries, soff[0] = 0, soff[n_seg] = the stream's size
 
@@ -335,12 +380,15 @@ struct BamSort {
     int order = BSORT_COORDINATE;
     DevBuf ns_len, ns_val, ns_place[2], ns_seg[2], ns_flags, ns_ex;
     svx_bam_name_sort_stats ns;
+    // runs in query-name order: the name table (32-bit words, grows by doubling, kept), per record of a closed run its name length and rank (rkey holds the
+    // word offset of its name), the words per place of the run being closed and their scan; all of it goes back at the end of finish
+    DevBuf ntab, rnlen, rrank, ns_words, ns_woff; int64_t ntab_words = 0;
+    svx_bam_name_spill_stats nsp;
 };
 static inline double bs_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir, int order) {
     if (max_bytes < 0 || n_ref < 0 || (order != BSORT_COORDINATE && order != BSORT_QUERYNAME)) return svx_fail(SVX_E_ARG, "BAM sort: bad argument", __FILE__, __LINE__, hipSuccess);
-    if (order == BSORT_QUERYNAME && spill_dir) return svx_fail(SVX_E_ARG, "BAM sort: a spilled sort is in coordinate order (query-name order sorts in memory only)", __FILE__, __LINE__, hipSuccess);
     if (spill_dir) {
         struct stat sb;
         if (!*spill_dir || stat(spill_dir, &sb) != 0 || !S_ISDIR(sb.st_mode) || access(spill_dir, W_OK | X_OK) != 0)
@@ -353,7 +401,7 @@ int bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spi
     S->spill = spill_dir != nullptr; S->spill_dir = spill_dir ? spill_dir : "";
     S->spill_piece = BS_SPILL_PIECE;                         // test hook: SVX_BAM_SORT_SPILL_PIECE_KB, so that small runs leave in several pieces
     { const char* e = getenv("SVX_BAM_SORT_SPILL_PIECE_KB"); if (e && atoll(e) > 0 && atoll(e) <= (BS_SPILL_PIECE >> 10)) S->spill_piece = atoll(e) << 10; }
-    memset(&S->stats, 0, sizeof S->stats); memset(&S->sp, 0, sizeof S->sp); memset(&S->ns, 0, sizeof S->ns);
+    memset(&S->stats, 0, sizeof S->stats); memset(&S->sp, 0, sizeof S->sp); memset(&S->ns, 0, sizeof S->ns); memset(&S->nsp, 0, sizeof S->nsp);
     SVXCHK(bamindex_begin(&S->rows));
     SVXCHK(S->bad.reserve(64));
     HIPCHK(hipMemset(S->bad.p, 0, 64));
@@ -366,8 +414,10 @@ void bamsort_drop(BamSort* S) {
     DevBuf* all[] = {&S->key, &S->len, &S->addr, &S->key2, &S->val, &S->perm, &S->sort_tmp, &S->scan_tmp, &S->slen, &S->soff, &S->saddr, &S->hdr, &S->piece, &S->blocks, &S->crc, &S->tok,
                      &S->hist, &S->nt, &S->codes, &S->bsize, &S->coff, &S->kinds, &S->slots, &S->out, &S->coff_all,
                      &S->rkey, &S->rlen, &S->rfile, &S->roff, &S->gp, &S->srun, &S->sroff, &S->gpos, &S->run_base, &S->run_bytes, &S->cuts, &S->stage_at, &S->stage,
-                     &S->ns_len, &S->ns_val, &S->ns_place[0], &S->ns_place[1], &S->ns_seg[0], &S->ns_seg[1], &S->ns_flags, &S->ns_ex};
+                     &S->ns_len, &S->ns_val, &S->ns_place[0], &S->ns_place[1], &S->ns_seg[0], &S->ns_seg[1], &S->ns_flags, &S->ns_ex,
+                     &S->ntab, &S->rnlen, &S->rrank, &S->ns_words, &S->ns_woff};
     for (auto* b : all) b->release();
+    S->ntab_words = 0;
     if (S->fd >= 0) { (void)close(S->fd); S->fd = -1; }      // (unlinked when it was opened: its blocks go back now)
     S->runs.clear(); S->file_bytes = S->total_bytes = S->run_first = S->n_slabs_all = 0; S->rcap = 0;
     S->h_io.clear(); S->h_io.shrink_to_fit(); S->h_cuts.clear();
@@ -399,21 +449,64 @@ static int bs_spill_open(BamSort* S) {
     S->file_bytes = 0;
     return SVX_OK;
 }
+static int bs_name_extents(BamSort* S, int64_t n, int* bad, hipStream_t st);
+static int bs_name_order(BamSort* S, int64_t n, uint32_t* perm, const uint32_t* tab, const uint64_t* rwoff, const uint8_t* rnlen, svx_bam_name_sort_stats& X, double t0, hipStream_t st);
+static void bs_name_release(BamSort* S);
+// a run closes in query-name order: the checks whose records are about to leave the device, the run's permutation into S->perm by the rank pass and the rounds
+// over the open run's m rows, and the run's names into the table, in the run's order, BEFORE the slabs go back.  rkey / rnlen / rrank hold first + m entries
+static int bs_close_run_names(BamSort* S, int64_t first, int64_t m, hipStream_t st) {
+    int bad = 0;
+    SVXCHK(svx_d2h(&bad, S->bad.p, 4, st));                  // (k_ns_names relies on every record holding its fixed fields)
+    if (bad & BSORT_BAD_MATE) return svx_fail(SVX_E_ARG, "BAM merge: a record of a file whose ids are translated names a mate reference its header does not have", __FILE__, __LINE__, hipSuccess);
+    if (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID)) return svx_fail(SVX_E_ARG, "BAM sort: a record names a reference the header does not have, or is shorter than its fixed fields", __FILE__, __LINE__, hipSuccess);
+    const double t0 = bs_now();
+    SVXCHK(bs_name_extents(S, m, &bad, st));
+    if (bad & BSORT_BAD_NAME) return svx_fail(SVX_E_ARG, "BAM sort: a record has no name field, or one that runs past the record's end (query-name order)", __FILE__, __LINE__, hipSuccess);
+    // (BSORT_BAD_POS waits for finish, behind every SVX_E_ARG of every run, as the definition orders them)
+    svx_bam_name_sort_stats X;
+    memset(&X, 0, sizeof X);
+    SVXCHK(bs_name_order(S, m, S->perm.as<uint32_t>(), nullptr, nullptr, nullptr, X, bs_now(), st));
+    const double t1 = bs_now();
+    SVXCHK(S->ns_words.reserve((size_t)(m + 1) * 8)); SVXCHK(S->ns_woff.reserve((size_t)(m + 1) * 8));
+    k_ns_tab_words<<<BS_GRID(m + 1), BS_T, 0, st>>>(m, S->perm.as<uint32_t>(), S->ns_len.as<uint8_t>(), S->ns_words.as<int64_t>());
+    HIPCHK(hipGetLastError());
+    SVXCHK((svx_exclusive_scan<int64_t, int64_t>(S->ns_words.as<int64_t>(), S->ns_woff.as<int64_t>(), m + 1, st, S->scan_tmp)));
+    int64_t words = 0;
+    SVXCHK(svx_d2h(&words, S->ns_woff.as<int64_t>() + m, 8, st));
+    if (words < m || words > m * 64) return svx_fail(SVX_E_STATE, "BAM sort: a run's names take less than a word or more than 64 words each (internal error)", __FILE__, __LINE__, hipSuccess);
+    const int64_t need = S->ntab_words + words;
+    if ((size_t)need * 4 > S->ntab.cap) SVXCHK(S->ntab.reserve((size_t)std::max<int64_t>(std::max<int64_t>(need, 2 * (int64_t)(S->ntab.cap / 4)), 1 << 16) * 4, true, st));
+    k_ns_pack<<<BS_GRID(m), BS_T, 0, st>>>(m, S->perm.as<uint32_t>(), S->addr.as<uint64_t>(), S->ns_len.as<uint8_t>(), S->ns_woff.as<int64_t>(), (uint64_t)S->ntab_words, S->ntab.as<uint32_t>(),
+                                           S->rkey.as<uint64_t>() + first, S->rnlen.as<uint8_t>() + first, S->rrank.as<uint8_t>() + first);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    S->ntab_words = need;
+    bs_name_release(S);
+    svx_bam_name_spill_stats& P = S->nsp;
+    P.n_runs++; P.run_rounds += X.rounds; P.run_active_rows += X.active_total; P.table_bytes = S->ntab_words * 4;
+    P.t_run_sort_ms += (t1 - t0) * 1e3; P.t_pack_ms += (bs_now() - t1) * 1e3;
+    return SVX_OK;
+}
 // the open run - records [run_first, n), their bytes in the slabs - sorted, laid out, written behind the runs before it; the slabs go back
 static int bs_close_run(BamSort* S, hipStream_t st) {
     const int64_t first = S->run_first, m = S->n - first;
     if (m <= 0) return SVX_OK;
     const double t0 = bs_now();
+    const bool by_name = S->order == BSORT_QUERYNAME;
     if (S->fd < 0) SVXCHK(bs_spill_open(S));
     if (S->n + 1 > S->rcap) {                                // (roff takes one entry more: the scan ends with the run's size)
         const int64_t ncap = std::max<int64_t>(std::max<int64_t>(S->n + 1, 2 * S->rcap), 1 << 16);
         SVXCHK(S->rkey.reserve((size_t)ncap * 8, true, st)); SVXCHK(S->rlen.reserve((size_t)ncap * 4, true, st)); SVXCHK(S->rfile.reserve((size_t)ncap * 4, true, st));
         SVXCHK(S->roff.reserve((size_t)ncap * 8, true, st));
+        if (by_name) { SVXCHK(S->rnlen.reserve((size_t)ncap, true, st)); SVXCHK(S->rrank.reserve((size_t)ncap, true, st)); }
         S->rcap = ncap;
     }
     SVXCHK(S->val.reserve((size_t)m * 4)); SVXCHK(S->perm.reserve((size_t)(m + 1) * 4)); SVXCHK(S->slen.reserve((size_t)(m + 1) * 8)); SVXCHK(S->saddr.reserve((size_t)(m + 1) * 8));
-    k_bs_iota<<<BS_GRID(m), BS_T, 0, st>>>(m, S->val.as<uint32_t>());
-    SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->key.as<uint64_t>(), S->rkey.as<uint64_t>() + first, S->val.as<uint32_t>(), S->perm.as<uint32_t>(), m, 0, bsort_key_bits(S->n_ref)));
+    if (by_name) SVXCHK(bs_close_run_names(S, first, m, st));
+    else {
+        k_bs_iota<<<BS_GRID(m), BS_T, 0, st>>>(m, S->val.as<uint32_t>());
+        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->key.as<uint64_t>(), S->rkey.as<uint64_t>() + first, S->val.as<uint32_t>(), S->perm.as<uint32_t>(), m, 0, bsort_key_bits(S->n_ref)));
+    }
     k_bs_run_layout<<<BS_GRID(m + 1), BS_T, 0, st>>>(m, S->perm.as<uint32_t>(), S->len.as<uint32_t>(), S->addr.as<uint64_t>(), (uint32_t)first, S->slen.as<int64_t>(), S->saddr.as<uint64_t>(),
                                                      S->rlen.as<uint32_t>() + first, S->rfile.as<uint32_t>() + first);
     HIPCHK(hipGetLastError());
@@ -458,12 +551,15 @@ int bamsort_append(BamSort* S, const BamSortChunk& c, hipStream_t st) {
     if (S->n + c.n > 0xffffffffll) return svx_fail(SVX_E_CAPACITY, "BAM sort: more than 2^32 - 1 records", __FILE__, __LINE__, hipSuccess);
     const size_t need = (size_t)(c.end_byte - c.first_byte);
     double t_closing = 0;
+    // runs in query-name order take more than the chunk and its rows when they close: the table (it doubles: as much again as it holds), per record so far
+    // and coming the rows that stay of this order (26 bytes: word offset, length, file index, offset in the run, name length, rank) and the 37 bytes the rounds take
+    const size_t name_extra = S->spill && S->order == BSORT_QUERYNAME ? S->ntab.cap + (size_t)(S->n + c.n) * BSORT_NAME_ROW_BYTES : 0;
     for (int attempt = 0;; attempt++) {
         char msg[200]; msg[0] = 0;
         size_t free_b = 0, total_b = 0;
         if (S->max_bytes > 0 && S->arena_bytes + (int64_t)need > S->max_bytes)
             snprintf(msg, sizeof msg, "BAM sort: the records do not fit into the arena (%lld bytes held, %zu more, limit %lld)", (long long)S->arena_bytes, need, (long long)S->max_bytes);
-        else if (S->max_bytes == 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + (size_t)c.n * 64 + ((size_t)64 << 20) > free_b)
+        else if (S->max_bytes == 0 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need + name_extra + (size_t)c.n * 64 + ((size_t)64 << 20) > free_b)
             snprintf(msg, sizeof msg, "BAM sort: the records do not fit into device memory (%lld bytes held, %zu more, %zu free)", (long long)S->arena_bytes, need, free_b);
         if (!msg[0]) break;
         // with a spill directory the open run is closed and the chunk starts the next one; a chunk that alone passes the limit has nowhere to go
@@ -524,9 +620,19 @@ static int bs_finish_spilled(BamSort* S, int64_t header_bytes, double t0, hipStr
     SVXCHK(S->run_base.reserve((size_t)(n_runs + 1) * 8)); SVXCHK(S->run_bytes.reserve((size_t)n_runs * 8));
     SVXCHK(svx_h2d(S->run_base.p, h_base.data(), (size_t)(n_runs + 1) * 8, st)); SVXCHK(svx_h2d(S->run_bytes.p, h_bytes.data(), (size_t)n_runs * 8, st));
     // the run-sorted keys lie back to back in rkey: one stable sort, the place in the concatenation as payload.  Equal keys keep the order run, place in the run
+    const bool by_name = S->order == BSORT_QUERYNAME;
     SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4)); SVXCHK(S->gp.reserve((size_t)n * 4));
-    k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, S->val.as<uint32_t>());
-    SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->rkey.as<uint64_t>(), S->key2.as<uint64_t>(), S->val.as<uint32_t>(), S->gp.as<uint32_t>(), n, 0, bsort_key_bits(S->n_ref)));
+    if (by_name) {
+        // query-name order: the rank pass and the rounds over all n places, the words from the name table; gp = the places in (name, rank, run, place in the run) order
+        SVXCHK(S->key.reserve((size_t)n * 8));
+        k_ns_rank_keys<<<BS_GRID(n), BS_T, 0, st>>>(n, S->rrank.as<uint8_t>(), S->key.as<uint64_t>());
+        HIPCHK(hipGetLastError());
+        SVXCHK(bs_name_order(S, n, S->gp.as<uint32_t>(), S->ntab.as<uint32_t>(), S->rkey.as<uint64_t>(), S->rnlen.as<uint8_t>(), S->ns, t1, st));
+        bs_name_release(S);
+    } else {
+        k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, S->val.as<uint32_t>());
+        SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, S->rkey.as<uint64_t>(), S->key2.as<uint64_t>(), S->val.as<uint32_t>(), S->gp.as<uint32_t>(), n, 0, bsort_key_bits(S->n_ref)));
+    }
     HIPCHK(hipStreamSynchronize(st));
     const double t2 = bs_now();
     SVXCHK(S->slen.reserve((size_t)(n + 2) * 8)); SVXCHK(S->soff.reserve((size_t)(n + 2) * 8)); SVXCHK(S->saddr.reserve((size_t)(n + 2) * 8));
@@ -543,22 +649,23 @@ static int bs_finish_spilled(BamSort* S, int64_t header_bytes, double t0, hipStr
     // resident from here on: the permutation, the segment table (offset, run, offset in the run), gpos, the runs' record offsets and the index rows
     S->key.release(); S->key2.release(); S->val.release(); S->len.release(); S->addr.release(); S->slen.release(); S->sort_tmp.release();
     S->rkey.release(); S->rlen.release(); S->rfile.release(); S->gp.release();
+    S->ntab.release(); S->rnlen.release(); S->rrank.release();             // (the table's size stays in the stats)
     S->cap = 0;
     const double t3 = bs_now();
+    if (by_name) { S->ns.t_layout_ms = (t3 - t2) * 1e3; S->ns.n_records = n; S->ns.word_bytes = BSORT_NAME_WORD; }
     S->stream_bytes = total; S->n_blocks = (total + BSORT_BLOCK - 1) / BSORT_BLOCK + 1; S->next_block = 0; S->broken = false;
     S->h_csize.assign((size_t)S->n_blocks, 0);
     S->finished = true;
     S->stats.t_append_ms = S->t_append * 1e3; S->stats.t_sort_ms = (t2 - t1) * 1e3; S->stats.t_layout_ms = (t3 - t2) * 1e3; S->stats.t_finish_ms = (t3 - t0) * 1e3;
     S->stats.n_records = n; S->stats.n_slabs = S->n_slabs_all; S->stats.arena_bytes = S->total_bytes; S->stats.stream_bytes = total; S->stats.n_blocks = S->n_blocks;
-    S->stats.key_bits = bsort_key_bits(S->n_ref);
+    S->stats.key_bits = by_name ? 0 : bsort_key_bits(S->n_ref);
     S->sp.t_merge_ms += (t3 - t1) * 1e3;
     return SVX_OK;
 }
 
 // query-name order, in front of the sort: the names' extents, ranks and checks (k_ns_names); *bad gets BSORT_BAD_NAME.  The caller has refused BSORT_BAD_SIZE:
 // every record lies inside its slab and holds its fixed fields
-static int bs_name_extents(BamSort* S, int* bad, hipStream_t st) {
-    const int64_t n = S->n;
+static int bs_name_extents(BamSort* S, int64_t n, int* bad, hipStream_t st) {
     if (n == 0) return SVX_OK;
     SVXCHK(S->ns_len.reserve((size_t)n));
     k_ns_names<<<BS_GRID(n), BS_T, 0, st>>>(n, S->addr.as<uint64_t>(), S->len.as<uint32_t>(), S->ns_len.as<uint8_t>(), S->key.as<uint64_t>(), S->bad.as<int>());
@@ -566,16 +673,16 @@ static int bs_name_extents(BamSort* S, int* bad, hipStream_t st) {
     SVXCHK(svx_d2h(bad, S->bad.p, 4, st));
     return SVX_OK;
 }
-// the permutation of query-name order into S->perm (the kernels and the rounds: above); S->key holds the ranks
-static int bs_name_order(BamSort* S, double t0, hipStream_t st) {
-    const int64_t n = S->n;
-    svx_bam_name_sort_stats& X = S->ns;
+// the permutation of query-name order of n rows into perm (the kernels and the rounds: above); S->key holds their ranks.  The rows are records in their slabs
+// (S->addr, S->ns_len: the in-memory sort and a run being closed; tab null) or places of the concatenation of the closed runs, their names in the table
+// (rwoff, rnlen: the merge at finish).  X: what the rounds were.  The caller gives the round buffers back (bs_name_release)
+static int bs_name_order(BamSort* S, int64_t n, uint32_t* perm, const uint32_t* tab, const uint64_t* rwoff, const uint8_t* rnlen, svx_bam_name_sort_stats& X, double t0, hipStream_t st) {
     if (n == 0) return SVX_OK;
     SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4)); SVXCHK(S->ns_val.reserve((size_t)n * 4));
     for (int k = 0; k < 2; k++) { SVXCHK(S->ns_place[k].reserve((size_t)n * 4)); SVXCHK(S->ns_seg[k].reserve((size_t)n * 4)); }
     SVXCHK(S->ns_flags.reserve((size_t)(n + 1) * 8)); SVXCHK(S->ns_ex.reserve((size_t)(n + 1) * 8));
     uint64_t *key = S->key.as<uint64_t>(), *key2 = S->key2.as<uint64_t>();
-    uint32_t *val = S->val.as<uint32_t>(), *val2 = S->ns_val.as<uint32_t>(), *perm = S->perm.as<uint32_t>();
+    uint32_t *val = S->val.as<uint32_t>(), *val2 = S->ns_val.as<uint32_t>();
     k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, val);
     SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, perm, n, 0, 4));
     HIPCHK(hipStreamSynchronize(st));
@@ -586,7 +693,8 @@ static int bs_name_order(BamSort* S, double t0, hipStream_t st) {
     for (uint32_t r = 0; m > 0; r++, cur ^= 1) {
         if (r >= BSORT_NAME_MAX_ROUNDS) return svx_fail(SVX_E_STATE, "BAM sort: names still open behind their last possible byte (internal error)", __FILE__, __LINE__, hipSuccess);
         const uint32_t *place = r ? S->ns_place[cur].as<uint32_t>() : nullptr, *seg = r ? S->ns_seg[cur].as<uint32_t>() : nullptr;
-        k_ns_keys<<<BS_GRID(m), BS_T, 0, st>>>(m, r, perm, place, seg, S->addr.as<uint64_t>(), S->ns_len.as<uint8_t>(), key, val);
+        if (tab) k_ns_keys_tab<<<BS_GRID(m), BS_T, 0, st>>>(m, r, perm, place, seg, tab, rwoff, rnlen, key, val);
+        else k_ns_keys<<<BS_GRID(m), BS_T, 0, st>>>(m, r, perm, place, seg, S->addr.as<uint64_t>(), S->ns_len.as<uint8_t>(), key, val);
         SVXCHK(svx_sort_pairs_u64_on(st, S->sort_tmp, key, key2, val, val2, m, 0, 32 + (n_seg > 1 ? svx_ceil_log2(n_seg) : 0)));
         k_ns_heads<<<BS_GRID(m + 1), BS_T, 0, st>>>(m, key2, S->ns_flags.as<int64_t>());
         SVXCHK((svx_exclusive_scan<int64_t, int64_t>(S->ns_flags.as<int64_t>(), S->ns_ex.as<int64_t>(), m + 1, st, S->scan_tmp)));
@@ -602,9 +710,11 @@ static int bs_name_order(BamSort* S, double t0, hipStream_t st) {
     }
     HIPCHK(hipStreamSynchronize(st));
     X.t_rounds_ms = (bs_now() - t1) * 1e3;
-    DevBuf* done[] = {&S->ns_len, &S->ns_val, &S->ns_place[0], &S->ns_place[1], &S->ns_seg[0], &S->ns_seg[1], &S->ns_flags, &S->ns_ex};
-    for (auto* b : done) b->release();
     return SVX_OK;
+}
+static void bs_name_release(BamSort* S) {
+    DevBuf* done[] = {&S->ns_len, &S->ns_val, &S->ns_place[0], &S->ns_place[1], &S->ns_seg[0], &S->ns_seg[1], &S->ns_flags, &S->ns_ex, &S->ns_words, &S->ns_woff};
+    for (auto* b : done) b->release();
 }
 
 int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipStream_t st) {
@@ -619,8 +729,9 @@ int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipS
     if (bad & (BSORT_BAD_SIZE | BSORT_BAD_TID)) return svx_fail(SVX_E_ARG, "BAM sort: a record names a reference the header does not have, or is shorter than its fixed fields", __FILE__, __LINE__, hipSuccess);
     const bool by_name = S->order == BSORT_QUERYNAME;
     double t_names = t0;
-    if (by_name) {                                           // (the names' checks are SVX_E_ARG, which goes before SVX_E_RANGE)
-        SVXCHK(bs_name_extents(S, &bad, st));
+    if (by_name && !S->runs.empty()) SVXCHK(bs_close_run(S, st));      // (runs in query-name order: the open run's names are checked where every run's were, SVX_E_ARG in front of SVX_E_RANGE)
+    else if (by_name) {                                      // (the names' checks are SVX_E_ARG, which goes before SVX_E_RANGE)
+        SVXCHK(bs_name_extents(S, n, &bad, st));
         t_names = bs_now();
         if (bad & BSORT_BAD_NAME) return svx_fail(SVX_E_ARG, "BAM sort: a record has no name field, or one that runs past the record's end (query-name order)", __FILE__, __LINE__, hipSuccess);
     }
@@ -630,7 +741,7 @@ int bamsort_finish(BamSort* S, const uint8_t* header, int64_t header_bytes, hipS
     SVXCHK(svx_h2d(S->hdr.p, header, (size_t)header_bytes, st));
     SVXCHK(S->perm.reserve((size_t)(n + 1) * 4));
     if (!S->runs.empty()) return bs_finish_spilled(S, header_bytes, t0, st);      // (no run was closed: exactly the in-memory path, no file)
-    if (by_name) SVXCHK(bs_name_order(S, t_names, st));
+    if (by_name) { SVXCHK(bs_name_order(S, n, S->perm.as<uint32_t>(), nullptr, nullptr, nullptr, S->ns, t_names, st)); bs_name_release(S); }
     else if (n > 0) {
         SVXCHK(S->key2.reserve((size_t)n * 8)); SVXCHK(S->val.reserve((size_t)n * 4));
         k_bs_iota<<<BS_GRID(n), BS_T, 0, st>>>(n, S->val.as<uint32_t>());
@@ -874,6 +985,9 @@ void bamsort_stats(const BamSort* S, svx_bam_sort_stats* out) {
 }
 void bamsort_name_stats(const BamSort* S, svx_bam_name_sort_stats* out) {
     if (S) *out = S->ns; else memset(out, 0, sizeof *out);
+}
+void bamsort_name_spill_stats(const BamSort* S, svx_bam_name_spill_stats* out) {
+    if (S) *out = S->nsp; else memset(out, 0, sizeof *out);
 }
 void bamsort_translate_stats(const BamSort* S, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms) {
     *n_chunks = S ? S->tr_chunks : 0; *n_records = S ? S->tr_records : 0; *n_bytes = S ? S->tr_bytes : 0; *ms = S ? S->tr_ms : 0;

@@ -16,7 +16,9 @@ struct BamSortChunk {
 };
 // an empty arena (the state is made on first use); max_bytes 0: what the device has free.  spill_dir (may be null): the directory of the spill file - a chunk
 // that would pass the limit then closes a run (sorted, laid out, written to the file, slabs freed) instead of failing; SVX_E_ARG: not a writable directory
-// order: BSORT_COORDINATE or BSORT_QUERYNAME (bamsort_core.hpp); query-name order with a spill directory is SVX_E_ARG, and bamsort_index after it SVX_E_STATE
+// order: BSORT_COORDINATE or BSORT_QUERYNAME (bamsort_core.hpp); bamsort_index after query-name order is SVX_E_STATE.  Query-name order with a spill directory
+// closes its runs in that order and keeps their names in a table (only a merge session begins such a sort; a run that closes refuses what finish refuses with
+// SVX_E_ARG at once, from bamsort_append)
 int  bamsort_begin(BamSort** s, int64_t max_bytes, int32_t n_ref, const char* spill_dir = nullptr, int order = 0);
 void bamsort_drop(BamSort* s);                                         // arena, rows and the encoder's buffers go back
 void bamsort_destroy(BamSort* s);
@@ -33,7 +35,8 @@ int  bamsort_index(BamSort* s, BamIndex* ix, hipStream_t st, int fmt);
 int  bamsort_permutation(BamSort* s, uint32_t* host_perm, hipStream_t st);
 void bamsort_stats(const BamSort* s, svx_bam_sort_stats* out);
 void bamsort_spill_stats(const BamSort* s, svx_bam_sort_spill_stats* out);
-void bamsort_name_stats(const BamSort* s, svx_bam_name_sort_stats* out);      // zeros unless the last finish was in query-name order
+void bamsort_name_stats(const BamSort* s, svx_bam_name_sort_stats* out);      // zeros unless the last finish was in query-name order (after runs: the merge's rounds)
+void bamsort_name_spill_stats(const BamSort* s, svx_bam_name_spill_stats* out);      // the runs closed in query-name order since begin
 // what k_bs_translate has done for the sort since begin: chunks and records it ran over, the bytes it read and wrote, its time between events on the stream
 void bamsort_translate_stats(const BamSort* s, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms);
 // A sort with the stream it runs on and the slot its index goes to (devdec.hpp: sortout_*; sortout.hip).  The owner - a reader's decoder, a merge session -

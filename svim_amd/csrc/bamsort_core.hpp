@@ -84,6 +84,28 @@ BSORT_FN uint32_t bsort_name_word(const uint8_t* field, uint32_t name_len, uint3
 }
 // rounds after which every name has ended inside a word: a name of 255 bytes ends inside word 63
 #define BSORT_NAME_MAX_ROUNDS ((255 + BSORT_NAME_WORD) / BSORT_NAME_WORD)
+// ---- the name table of a query-name sort that spills (bamsort.hip: k_ns_pack, k_ns_keys_tab) ----
+// The records of a closed run leave the device, their names stay: every name at a 4-byte aligned place of one table of 32-bit words, zero-filled to the word's
+// edge, so that a round of the merge reads its word with ONE aligned load.  A name takes ceil(len / 4) words, at least one
+BSORT_FN uint32_t bsort_name_tab_words(uint32_t name_len) { const uint32_t w = (name_len + BSORT_NAME_WORD - 1u) / BSORT_NAME_WORD; return w ? w : 1u; }
+// field: the name's bytes (nothing behind field[name_len - 1] is read) -> dst_words[0 .. bsort_name_tab_words): the bytes in memory order
+BSORT_FN void bsort_name_tab_pack(const uint8_t* field, uint32_t name_len, uint32_t* dst_words) {
+    const uint32_t nw = bsort_name_tab_words(name_len);
+    for (uint32_t w = 0; w < nw; w++) {
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < BSORT_NAME_WORD; k++) {
+            const uint32_t at = BSORT_NAME_WORD * w + k;
+            v |= (at < name_len ? (uint32_t)field[at] : 0u) << (8u * k);         // (byte k of a word is its k-th byte in memory: both builds are little-endian)
+        }
+        dst_words[w] = v;
+    }
+}
+// the word of round r of the name at tab[word_off ..]: one aligned load made big-endian, 0 behind the name's words.  Equals bsort_name_word(field, name_len, r)
+BSORT_FN uint32_t bsort_name_tab_word(const uint32_t* tab, uint64_t word_off, uint32_t name_len, uint32_t r) {
+    if (r >= bsort_name_tab_words(name_len)) return 0u;
+    const uint32_t v = tab[word_off + r];
+    return (v << 24) | ((v & 0xff00u) << 8) | ((v >> 8) & 0xff00u) | (v >> 24);
+}
 // ---- the merge of several files (svim_amd/bammerge.py): the ids of a record of a file whose dictionary is not the merged one ----
 // (used by svx_bam_merge_host today; written for host and device alike, as everything in this file is)
 // map[i]: the merged id of the file's reference i (n_ref_file entries).  -1 stays -1.  A refID outside [-1, n_ref_file) is BSORT_BAD_TID, a next_refID outside

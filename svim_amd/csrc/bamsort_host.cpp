@@ -2,7 +2,8 @@
 // sort of a record stream in coordinate or query-name order and the header of the sorted file by the rule of bamsort_core.hpp and svim_amd/bamsort.py, built
 // for the host; no GPU involved.  The kernels of bamsort.hip write the same bytes and the same permutation:
 // there the keys go through the radix sort and the records through a gather, here through std::stable_sort and memcpy.
-// svx_bam_merge_header_host and svx_bam_merge_host: the same for several files merged into one (svim_amd/bammerge.py; bsort_translate).
+// svx_bam_merge_header_host_order and svx_bam_merge_host_order (svx_bam_merge_header_host and svx_bam_merge_host are their coordinate case): the same for
+// several files merged into one (svim_amd/bammerge.py; bsort_translate).
 #include "bamsort_core.hpp"
 #include "../../include/svx.h"
 #include <algorithm>
@@ -260,14 +261,15 @@ std::string merge_join(const std::vector<std::string>& f) {
 bool merge_has(const std::vector<std::string>& v, const std::string& s) { return std::find(v.begin(), v.end(), s) != v.end(); }
 }  // namespace
 
-extern "C" int svx_bam_merge_header_host(const uint8_t* const* headers, const int64_t* sizes, int64_t k, uint8_t* out, int64_t cap, int64_t* n_out, int32_t* tid_maps_out) {
-    if (!headers || !sizes || k < 1 || cap < 0 || (cap && !out) || !n_out) return SVX_E_ARG;
+// order SVX_SORT_QUERYNAME: rule 1 takes the first line of the first file's header as query-name order rewrites it; every other rule is the same
+extern "C" int svx_bam_merge_header_host_order(const uint8_t* const* headers, const int64_t* sizes, int64_t k, int order, uint8_t* out, int64_t cap, int64_t* n_out, int32_t* tid_maps_out) {
+    if (!headers || !sizes || k < 1 || cap < 0 || (cap && !out) || !n_out || (order != SVX_SORT_COORDINATE && order != SVX_SORT_QUERYNAME)) return SVX_E_ARG;
     *n_out = 0;
     std::vector<MergeHeader> H((size_t)k);
     for (int64_t f = 0; f < k; f++) if (!merge_parse(headers[f], sizes[f], &H[(size_t)f])) return SVX_E_ARG;
     if (k == 1) {                                                                // the merge of one file is the sort of that file
         if (tid_maps_out) for (size_t i = 0; i < H[0].names.size(); i++) tid_maps_out[i] = (int32_t)i;
-        return svx_bam_sort_header_host(headers[0], sizes[0], out, cap, n_out);
+        return svx_bam_sort_header_host_order(headers[0], sizes[0], order, out, cap, n_out);
     }
     // the dictionary: the first file's, then the names not yet present; the maps
     std::vector<std::string> names; std::vector<int32_t> lens;
@@ -292,7 +294,7 @@ extern "C" int svx_bam_merge_header_host(const uint8_t* const* headers, const in
         memcpy(fake.data(), "BAM\1", 4); wr32(fake.data() + 4, (uint32_t)H[0].text.size());
         if (!H[0].text.empty()) memcpy(fake.data() + 8, H[0].text.data(), H[0].text.size());
         int64_t n = 0;
-        if (svx_bam_sort_header_host(fake.data(), (int64_t)fake.size(), sorted.data(), (int64_t)sorted.size(), &n) != SVX_OK) return SVX_E_ARG;
+        if (svx_bam_sort_header_host_order(fake.data(), (int64_t)fake.size(), order, sorted.data(), (int64_t)sorted.size(), &n) != SVX_OK) return SVX_E_ARG;
         const std::string text((const char*)sorted.data() + 8, (size_t)rd32(sorted.data() + 4));
         made.push_back(text.substr(0, text.find('\n')));
     }
@@ -362,11 +364,17 @@ extern "C" int svx_bam_merge_header_host(const uint8_t* const* headers, const in
     return SVX_OK;
 }
 
-extern "C" int svx_bam_merge_host(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, uint8_t* out,
-                                  uint32_t* perm, int64_t perm_cap, int64_t* n_records) {
-    if (!streams || !sizes || !n_ref || k < 1 || n_ref_merged < 0 || perm_cap < 0 || !n_records) return SVX_E_ARG;
+extern "C" int svx_bam_merge_header_host(const uint8_t* const* headers, const int64_t* sizes, int64_t k, uint8_t* out, int64_t cap, int64_t* n_out, int32_t* tid_maps_out) {
+    return svx_bam_merge_header_host_order(headers, sizes, k, SVX_SORT_COORDINATE, out, cap, n_out, tid_maps_out);
+}
+
+// order SVX_SORT_QUERYNAME: a row's key is the rank and the name lies in the translated copy (svx_bam_sort_host_order's comparison); the names' refusals are per file
+extern "C" int svx_bam_merge_host_order(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, int order,
+                                        uint8_t* out, uint32_t* perm, int64_t perm_cap, int64_t* n_records) {
+    if (!streams || !sizes || !n_ref || k < 1 || n_ref_merged < 0 || perm_cap < 0 || !n_records || (order != SVX_SORT_COORDINATE && order != SVX_SORT_QUERYNAME)) return SVX_E_ARG;
     *n_records = 0;
-    struct Row { uint64_t key; int64_t at; uint32_t len; };
+    const bool by_name = order == SVX_SORT_QUERYNAME;
+    struct Row { uint64_t key; int64_t at; uint32_t len, name_len; };
     std::vector<Row> rows;
     std::vector<uint8_t> all;                                                    // the concatenation of the inputs, translated
     int bad = 0;
@@ -396,7 +404,12 @@ extern "C" int svx_bam_merge_host(const uint8_t* const* streams, const int64_t* 
                 tid = t;
             }
             bad |= bsort_check(tid, pos, bs, identity ? n_ref[f] : n_ref_merged);
-            rows.push_back(Row{bsort_key(tid, pos, flag, n_ref_merged), base + p, 4u + bs});
+            if (by_name) {
+                const uint32_t l_name = records[p + BSORT_LNAME_AT];
+                const int b = bsort_name_check(l_name, bs);
+                bad |= b;
+                rows.push_back(Row{bsort_name_rank(flag), base + p, 4u + bs, b ? 0u : bsort_name_len(records + p + BSORT_NAME_AT, l_name)});
+            } else rows.push_back(Row{bsort_key(tid, pos, flag, n_ref_merged), base + p, 4u + bs, 0u});
             p += 4 + (int64_t)bs;
         }
         map += n_ref[f];
@@ -405,15 +418,40 @@ extern "C" int svx_bam_merge_host(const uint8_t* const* streams, const int64_t* 
     if (rows.size() > 0xffffffffull) return SVX_E_CAPACITY;
     *n_records = (int64_t)rows.size();
     if (perm && (int64_t)rows.size() > perm_cap) return SVX_E_CAPACITY;
-    std::vector<uint32_t> order(rows.size());
-    for (size_t i = 0; i < order.size(); i++) order[i] = (uint32_t)i;
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return rows[a].key < rows[b].key; });
+    std::vector<uint32_t> idx(rows.size());
+    for (size_t i = 0; i < idx.size(); i++) idx[i] = (uint32_t)i;
+    if (by_name)
+        std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) {
+            const Row &x = rows[a], &y = rows[b];
+            const int c = memcmp(all.data() + x.at + BSORT_NAME_AT, all.data() + y.at + BSORT_NAME_AT, std::min(x.name_len, y.name_len));
+            if (c != 0) return c < 0;
+            if (x.name_len != y.name_len) return x.name_len < y.name_len;
+            return x.key < y.key;
+        });
+    else std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return rows[a].key < rows[b].key; });
     int64_t at = 0;
-    for (size_t i = 0; i < order.size(); i++) {
-        const Row& r = rows[order[i]];
+    for (size_t i = 0; i < idx.size(); i++) {
+        const Row& r = rows[idx[i]];
         if (out) memcpy(out + at, all.data() + r.at, r.len);
-        if (perm) perm[i] = order[i];
+        if (perm) perm[i] = idx[i];
         at += r.len;
     }
     return SVX_OK;
+}
+extern "C" int svx_bam_merge_host(const uint8_t* const* streams, const int64_t* sizes, const int32_t* n_ref, int64_t k, int32_t n_ref_merged, const int32_t* tid_maps, uint8_t* out,
+                                  uint32_t* perm, int64_t perm_cap, int64_t* n_records) {
+    return svx_bam_merge_host_order(streams, sizes, n_ref, k, n_ref_merged, tid_maps, SVX_SORT_COORDINATE, out, perm, perm_cap, n_records);
+}
+// the name table's word against the name's own (bamsort_core.hpp), for one name packed at word_off of a table of tab_words words: what the tests hold
+// bsort_name_tab_word to.  -> the number of rounds r in [0, 64) at which the two differ (0: none), or SVX_E_ARG
+extern "C" int svx_bam_name_tab_check_host(const uint8_t* name, int32_t name_len, int64_t word_off, int64_t tab_words) {
+    if (!name || name_len < 1 || name_len > 255 || word_off < 0 || word_off + (int64_t)bsort_name_tab_words((uint32_t)name_len) > tab_words) return SVX_E_ARG;
+    std::vector<uint32_t> tab((size_t)tab_words, 0xa5a5a5a5u);
+    std::vector<uint8_t> field(name, name + name_len);                          // (exactly the name: a read behind its end is a read behind the allocation)
+    bsort_name_tab_pack(field.data(), (uint32_t)name_len, tab.data() + word_off);
+    int wrong = 0;
+    for (uint32_t r = 0; r < 64u; r++) wrong += bsort_name_tab_word(tab.data(), (uint64_t)word_off, (uint32_t)name_len, r) != bsort_name_word(field.data(), (uint32_t)name_len, r);
+    for (int64_t w = 0; w < tab_words; w++)                                      // nothing outside the name's words is written
+        if ((w < word_off || w >= word_off + (int64_t)bsort_name_tab_words((uint32_t)name_len)) && tab[(size_t)w] != 0xa5a5a5a5u) wrong++;
+    return wrong;
 }

@@ -70,7 +70,7 @@ int  devdec_device(const svx_devdec* d);
 // ---- the device side of a merge session (bammerge.hip): a sort, a stream and an output index of its OWN, and the files' id maps ----
 struct MergeDev;
 // maps: the files' maps back to back (n_maps entries, uploaded once); spill_dir may be null
-int  mergedev_create(int device, int64_t max_bytes, int32_t n_ref_merged, const char* spill_dir, const int32_t* maps, int64_t n_maps, MergeDev** out);
+int  mergedev_create(int device, int64_t max_bytes, int32_t n_ref_merged, const char* spill_dir, int order /* SVX_SORT_* */, const int32_t* maps, int64_t n_maps, MergeDev** out);
 void mergedev_destroy(MergeDev* m);
 int  mergedev_device(const MergeDev* m);
 void mergedev_feed(MergeDev* m, svx_devdec* d, int64_t map_at, int32_t n_ref_file, bool identity);      // devdec_feed_set with the session's sort, stream and map
@@ -95,4 +95,5 @@ int  sortout_permutation(SortOut* o, uint32_t* host_perm);
 void sortout_stats(const SortOut* o, svx_bam_sort_stats* out);
 void sortout_spill_stats(const SortOut* o, svx_bam_sort_spill_stats* out);
 void sortout_name_stats(const SortOut* o, svx_bam_name_sort_stats* out);      // zeros unless the last finish was in query-name order
+void sortout_name_spill_stats(const SortOut* o, svx_bam_name_spill_stats* out);      // zeros unless runs were closed in query-name order
 void sortout_translate_stats(const SortOut* o, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms);

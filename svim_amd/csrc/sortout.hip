@@ -48,4 +48,5 @@ int sortout_permutation(SortOut* o, uint32_t* host_perm) {
 void sortout_stats(const SortOut* o, svx_bam_sort_stats* out) { bamsort_stats(o->sort, out); }
 void sortout_spill_stats(const SortOut* o, svx_bam_sort_spill_stats* out) { bamsort_spill_stats(o->sort, out); }
 void sortout_name_stats(const SortOut* o, svx_bam_name_sort_stats* out) { bamsort_name_stats(o->sort, out); }
+void sortout_name_spill_stats(const SortOut* o, svx_bam_name_spill_stats* out) { bamsort_name_spill_stats(o->sort, out); }
 void sortout_translate_stats(const SortOut* o, int64_t* n_chunks, int64_t* n_records, int64_t* n_bytes, double* ms) { bamsort_translate_stats(o->sort, n_chunks, n_records, n_bytes, ms); }

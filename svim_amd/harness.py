@@ -41,7 +41,8 @@ class BamPipeline(object):
 
     def __init__(self, path, options, engine, threads=0, batch_records=200_000, mode="coordinate", sparse_seq=True, regions=None, gpu_inflate=None,
                  device_decode=None, keep_alignments=False, build_index=False, index_format="bai", index=None, region_rule="overlap", merged_out=None):
-        """path: one BAM file (or SAM text), or a list of them with merged_out=PATH: the files are merged into that file first (merge_bam) and read from it.
+        """path: one BAM file (or SAM text), or a list of them with merged_out=PATH: the files are merged into that file first (merge_bam; in query-name
+        order when mode="queryname", so that the records of a read lie next to each other across the files) and read from it.
         regions: None (the whole file); [(virtual offset, last reference id)]: contig runs (svx_bam_seek); or coordinate regions (svim_amd/regions.py): region
         strings ("chr1:10,000,000-12,000,000"), (contig, beg, end) tuples (0-based, half-open) - parsed, normalised and planned from the file's index, read in
         file order - or planned reads (virtual offset, tid, beg, end) as regions.plan and harness.window_plan give them.  index: the .bai / .csi the plan comes
@@ -49,7 +50,7 @@ class BamPipeline(object):
         from .bamio import NativeBam
         from . import regions as _regions
         if isinstance(path, (list, tuple)):                         # several files: merged on the device into merged_out first, the pipeline runs over that file
-            path = _merged_input(path, merged_out, getattr(engine, "device", None) or 0, threads)
+            path = _merged_input(path, merged_out, getattr(engine, "device", None) or 0, threads, order="queryname" if mode == "queryname" else "coordinate")
         coordinate_regions = regions is not None and any(isinstance(r, str) or len(r) != 2 for r in regions)
         if coordinate_regions and any(not isinstance(r, str) and len(r) == 2 for r in regions):
             raise ValueError("regions: either (virtual offset, last reference id) pairs or coordinate regions, not both")
@@ -894,7 +895,8 @@ def sort_bam(path, out, device=0, index=_DEFAULT, piece_blocks=4096, max_bytes=0
     index_format="csi": out + ".csi" instead (svim_amd/csi.py), "auto": that when a reference length of the header exceeds 2^29.
     order="queryname": the file in query-name order (`samtools sort -N`; svim_amd/bamsort.py), the input of the query-name front end.  Such a file has no
     index: none is written when `index` is left at its default, index=True or an index_format given by the caller is a ValueError, and so is a spill_dir
-    (query-name order sorts in memory only).  The stats then carry the rounds under "name".
+    (query-name order sorts in memory only here; beyond device memory it is merge_bam([path], out, order="queryname", spill_dir=...): a session over one file
+    with a spill directory is the spilled query-name sort of that file).  The stats then carry the rounds under "name".
     -> the sort's stats, the spill's under "spill".  On failure the partial output is removed and the sort given up;
     svim_amd.bamsort.BamSortError carries the library's status in .code."""
     from .bamio import NativeBam
@@ -944,12 +946,16 @@ def sort_bam(path, out, device=0, index=_DEFAULT, piece_blocks=4096, max_bytes=0
     return stats
 
 
-def merge_bam(paths, out, device=0, index=True, index_format="bai", piece_blocks=4096, max_bytes=0, spill_dir=None, threads=0, batch_records=200_000):
+def merge_bam(paths, out, device=0, index=_DEFAULT, index_format=_DEFAULT, piece_blocks=4096, max_bytes=0, spill_dir=None, threads=0, batch_records=200_000, order="coordinate"):
     """Several BAM files (or SAM texts: NativeBam tells them apart), each in any order, written to `out` as ONE file in coordinate order (svim_amd/bammerge.py
     says what the merged file is: the merged dictionary and header, reference ids translated, ties in file order), and its index to out + ".bai" or ".csi" when
     `index`: `samtools merge` of the reference's front end, on the device (bamio.BamMerge).  The readers are opened, the session reads their headers, then every
     file is added in turn - one pass of the device reader each - and its reader closed; the merged file is encoded and written in pieces of piece_blocks BGZF
     blocks.  max_bytes, spill_dir: as sort_bam, over all files together.  batch_records: unused (a session reads the files itself).
+    order="queryname": the merged file in query-name order (svim_amd/bammerge.py), the input of the query-name front end.  Such a file has no index: none is
+    written when `index` is left at its default, and index=True or an index_format given by the caller is a ValueError.  A spill_dir is taken in this order
+    too - one path with a spill_dir is the query-name sort of that file beyond device memory, which sort_bam refuses.  The stats then carry the rounds under
+    "name" and the runs' name sorts and name table under "name_spill".
     -> the sort's stats with the spill's under "spill" and the session's under "merge".  On failure what was written is removed and the session closed;
     svim_amd.bammerge.BamMergeError carries the library's status in .code."""
     from .bamio import BamMerge, NativeBam
@@ -958,6 +964,16 @@ def merge_bam(paths, out, device=0, index=True, index_format="bai", piece_blocks
         raise ValueError("merge_bam: no input")
     if piece_blocks < 1:
         raise ValueError("merge_bam: piece_blocks must be at least 1")
+    from . import _abi
+    by_name = bool(_abi.sort_order(order))
+    if by_name:
+        if index_format is not _DEFAULT:
+            raise ValueError("merge_bam: a query-name-sorted file has no index (index_format with order='queryname')")
+        if index is not _DEFAULT and index:
+            raise ValueError("merge_bam: a query-name-sorted file has no index (index=True with order='queryname')")
+        index = False
+    index = True if index is _DEFAULT else index
+    index_format = "bai" if index_format is _DEFAULT else index_format
     readers, session, written = [], None, []
     try:
         for p in paths:
@@ -968,13 +984,17 @@ def merge_bam(paths, out, device=0, index=True, index_format="bai", piece_blocks
         index_format = _bam_index_format(index_format, list(lengths.values()))
         for r in readers:
             r.set_device_decode(int(device))
-        session = BamMerge.open(readers, device=device, max_bytes=max_bytes, spill_dir=spill_dir)
+        session = BamMerge.open(readers, device=device, max_bytes=max_bytes, spill_dir=spill_dir, order=order)
         for r in readers:
             session.add(r)
             r.close()
         _, _, n_blocks = session.finish()
         _write_sorted_bam(out, n_blocks, session.encode, session.index if index else None, piece_blocks, index_format, written)
-        return session.stats()
+        stats = session.stats()
+        if by_name:
+            stats["name"] = session.name_stats()
+            stats["name_spill"] = stats["name"].pop("spill")
+        return stats
     except BaseException:
         for f in written:
             if os.path.exists(f):
@@ -987,11 +1007,12 @@ def merge_bam(paths, out, device=0, index=True, index_format="bai", piece_blocks
             r.close()
 
 
-def _merged_input(paths, merged_out, device, threads=0):
-    """a list of inputs for an entry point that takes one file: merged to `merged_out` first (merge_bam, with its .bai) -> that path"""
+def _merged_input(paths, merged_out, device, threads=0, order="coordinate"):
+    """a list of inputs for an entry point that takes one file: merged to `merged_out` first (merge_bam, with its .bai; order="queryname": in that order,
+    without an index) -> that path"""
     if not merged_out:
         raise ValueError("several BAM files need merged_out=PATH: they are merged into that file first (harness.merge_bam), and the run is over it")
-    merge_bam(list(paths), merged_out, device=device, threads=threads)
+    merge_bam(list(paths), merged_out, device=device, threads=threads, order=order)
     return merged_out
 
 

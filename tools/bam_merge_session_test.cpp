@@ -154,6 +154,7 @@ int sortout_permutation(SortOut* o, uint32_t* perm) { return model_permutation(o
 void sortout_stats(const SortOut*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
 void sortout_spill_stats(const SortOut*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
 void sortout_name_stats(const SortOut*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_name_spill_stats(const SortOut*, svx_bam_name_spill_stats* out) { memset(out, 0, sizeof *out); }
 void sortout_translate_stats(const SortOut*, int64_t* c, int64_t* r, int64_t* by, double* t) { *c = *r = *by = 0; *t = 0; }
 
 // ---- the decoder's side (devdec.hpp): its own sort, and the feed it borrows --------------------------------------------------------------------------------
@@ -193,7 +194,7 @@ SortOut* devdec_sort_out(svx_devdec* d) { return d->out; }
 struct MergeDev { uint32_t magic = MODEL_ALIVE; SortOut out; std::vector<int32_t>* maps = nullptr; };
 static std::atomic<int> g_sessions_alive{0};
 static MergeDev* md_alive(const MergeDev* m, const char* where) { if (!m || m->magic != MODEL_ALIVE) { fprintf(stderr, "in %s: ", where); model_die("a session's device side was used after its destruction"); } return const_cast<MergeDev*>(m); }
-int mergedev_create(int, int64_t max_bytes, int32_t n_ref_merged, const char*, const int32_t* maps, int64_t n_maps, MergeDev** out) {
+int mergedev_create(int, int64_t max_bytes, int32_t n_ref_merged, const char*, int /* the model sorts in coordinate order */, const int32_t* maps, int64_t n_maps, MergeDev** out) {
     MergeDev* m = new MergeDev();
     model_begin(&m->out.sort, max_bytes, n_ref_merged); m->out.on = true;
     m->maps = new std::vector<int32_t>(maps, maps + n_maps);

@@ -173,7 +173,7 @@ void devdec_feed_set(svx_devdec*, SortOut*, const int32_t*, int32_t, bool) {}
 void devdec_feed_clear(svx_devdec*) {}
 bool devdec_feed_on(const svx_devdec*) { return false; }
 int devdec_device(const svx_devdec*) { return 0; }
-int mergedev_create(int, int64_t, int32_t, const char*, const int32_t*, int64_t, MergeDev**) { return SVX_E_NODEVICE; }
+int mergedev_create(int, int64_t, int32_t, const char*, int, const int32_t*, int64_t, MergeDev**) { return SVX_E_NODEVICE; }
 void mergedev_destroy(MergeDev*) {}
 int mergedev_device(const MergeDev*) { return 0; }
 void mergedev_feed(MergeDev*, svx_devdec*, int64_t, int32_t, bool) {}
@@ -193,8 +193,10 @@ int sortout_permutation(SortOut*, uint32_t*) { return SVX_E_STATE; }
 void sortout_stats(const SortOut*, svx_bam_sort_stats* out) { memset(out, 0, sizeof *out); }
 void sortout_spill_stats(const SortOut*, svx_bam_sort_spill_stats* out) { memset(out, 0, sizeof *out); }
 void sortout_name_stats(const SortOut*, svx_bam_name_sort_stats* out) { memset(out, 0, sizeof *out); }
+void sortout_name_spill_stats(const SortOut*, svx_bam_name_spill_stats* out) { memset(out, 0, sizeof *out); }
 void sortout_translate_stats(const SortOut*, int64_t* c, int64_t* r, int64_t* by, double* t) { *c = *r = *by = 0; *t = 0; }
 extern "C" int svx_bam_merge_header_host(const uint8_t* const*, const int64_t*, int64_t, uint8_t*, int64_t, int64_t*, int32_t*) { return SVX_E_STATE; }
+extern "C" int svx_bam_merge_header_host_order(const uint8_t* const*, const int64_t*, int64_t, int, uint8_t*, int64_t, int64_t*, int32_t*) { return SVX_E_STATE; }
 #endif
 // SAM text (svx_sam_open): the front end is the device's (sam.hip) and the header parser sam_host.cpp's; neither is part of this program
 int devdec_load_text(svx_devdec*, int, const uint8_t*, size_t, bool, int, int, int64_t, uint64_t*, int64_t*) { return SVX_E_STATE; }
