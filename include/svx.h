@@ -569,6 +569,31 @@ typedef struct svx_alignments_stats {
     int64_t n_records, n_ops_read, n_long_records;
 } svx_alignments_stats;
 int  svx_alignments_get_stats(svx_ctx* ctx, svx_alignments_stats* out);
+/* Any record order.  svx_collect_keep_alignments_mode(ctx, on, flags) is svx_collect_keep_alignments with a mode for the rows appended from now on
+ * (svx_collect_keep_alignments(ctx, on) means flags 0: everything above, every error text and byte as it was).  The flags hold for a whole table: changing
+ * them while it holds rows is SVX_E_STATE at the next append.
+ *   SVX_ALN_SORT        the rows may arrive in any order.  The finalisation (at the first svx_genotype_resident after an append) checks the order on the
+ *                       full key of the coordinate sort (svim_amd/bamsort.py: (uint32(refID), uint32(pos + 1), flag & 16), refID -1 last) and, where a row
+ *                       is out of order, sorts the table stably by that key instead of refusing it: ties keep append order, so the table is that of the
+ *                       file svx_bam_sort would write.  Rows in order: nothing runs but the check.  Appending after a finalisation and finalising again
+ *                       sorts sorted old rows + new rows, which is the stable sort of the whole append order.  At most 2^32 - 1 rows (SVX_E_RANGE); a
+ *                       reference id outside [-1, n_contig) or a position below -1 is SVX_E_ARG.
+ *   SVX_ALN_FILE_FLAGS  SVX_FLAG_SKIP is the front end's mark, not the record's (query-name mode marks what COLLECT does not analyse, yet genotype() counts
+ *                       such records): the row keeps flag & 0x0fff and its end is computed from its CIGAR under the usual rule.  Not for region reads,
+ *                       where the mark means "outside the region".
+ * svx_alignments_fetch returns the table in its CURRENT order: append order until a finalisation has sorted it, coordinate order afterwards.
+ * svx_alignments_permutation: src_row[i] = the append position (0-based, over all appends since the table was emptied) of row i; SVX_E_STATE while the
+ * table has not been finalised since its last append.  Without a sort it is the identity. */
+enum { SVX_ALN_SORT = 1, SVX_ALN_FILE_FLAGS = 2 };
+typedef struct svx_alignments_sort_stats {
+    double  t_key_ms, t_sort_ms, t_gather_ms;   /* HIP events of the last finalisation: keys + row numbers, the radix sort, gather + copy back (0 when it did not sort) */
+    int64_t n_rows;
+    int32_t sorted;                             /* 1: the last finalisation sorted; 0: the rows were in order (or SVX_ALN_SORT was off) */
+    int32_t key_bits;                           /* 33 + tid bits: the key bits the sort ran over */
+} svx_alignments_sort_stats;
+int  svx_collect_keep_alignments_mode(svx_ctx* ctx, int on, uint32_t flags);
+int  svx_alignments_permutation(svx_ctx* ctx, uint32_t* src_row /* host, [n] */);
+int  svx_alignments_get_sort_stats(svx_ctx* ctx, svx_alignments_sort_stats* out);
 typedef struct svx_genotype_params {
     double  minimum_score;          /* 3   : candidates with score < minimum_score are not genotyped (:38-39) */
     int32_t min_mapq;               /* 20  */

@@ -17,14 +17,24 @@ from ._abi import ptr
 
 
 class AlignmentIndex(object):
-    """Structure-of-arrays view of every alignment record of a coordinate-sorted file, in file order."""
+    """Structure-of-arrays view of every alignment record of a coordinate-sorted file, in file order.
+    order="sort": the file may be in any order; the index is that of its records in the coordinate order of svim_amd/bamsort.py - key (uint32(refID),
+    uint32(pos + 1), flag & 16), stable, so ties keep file order - which is the index of sort_bam(file).  src_row[i] is then the place in the file of row i,
+    counted over all records (those without a position, which the index leaves out, sort last)."""
 
-    def __init__(self, bam):
+    def __init__(self, bam, order="file"):
+        if order not in ("file", "sort"):
+            raise ValueError("order: 'file' or 'sort'")
         self.references = list(bam.references)
         self.lengths = [int(x) for x in bam.lengths]
         tid, pos, end, flag, mapq, name = [], [], [], [], [], []
         self.name_ids = {}
-        for a in bam.fetch(until_eof=True):
+        recs = list(enumerate(bam.fetch(until_eof=True)))
+        if order == "sort":
+            from .bamsort import coordinate_key
+            recs.sort(key=lambda ka: coordinate_key(-1 if ka[1].reference_id is None else ka[1].reference_id, ka[1].reference_start, ka[1].flag))
+        self.src_row = np.asarray([k for k, a in recs if a.reference_id is not None and a.reference_id >= 0], dtype=np.uint32)
+        for _, a in recs:
             if a.reference_id is None or a.reference_id < 0:
                 continue                                    # records without a position are never returned by a region fetch
             tid.append(a.reference_id)
@@ -64,13 +74,14 @@ class AlignmentIndex(object):
 _INDEX_ATTR = "_svx_alignment_index"
 
 
-def alignment_index(bam):
-    """The index of `bam`, built on first use and kept on the object."""
-    ix = getattr(bam, _INDEX_ATTR, None)
+def alignment_index(bam, order="file"):
+    """The index of `bam` in that order, built on first use and kept on the object."""
+    attr = _INDEX_ATTR if order == "file" else _INDEX_ATTR + "_" + str(order)
+    ix = getattr(bam, attr, None)
     if ix is None:
-        ix = AlignmentIndex(bam)
+        ix = AlignmentIndex(bam, order=order)
         try:
-            setattr(bam, _INDEX_ATTR, ix)
+            setattr(bam, attr, ix)
         except AttributeError:
             pass
     return ix
@@ -96,10 +107,11 @@ def _engine(engine):
     return default_engine()
 
 
-def genotype(candidates, bam, type, options, engine=None):
-    """src/svim/SVIM_genotyping.py:34-93.  `type` is "DEL", "INV", "INS" or "DUP_INT" as at src/svim/svim:164-170."""
+def genotype(candidates, bam, type, options, engine=None, alignment_order="file"):
+    """src/svim/SVIM_genotyping.py:34-93.  `type` is "DEL", "INV", "INS" or "DUP_INT" as at src/svim/svim:164-170.
+    alignment_order="sort": `bam` may be in any record order (AlignmentIndex(order="sort")): the result is that of the coordinate-sorted file."""
     eng = _engine(engine)
-    index = alignment_index(bam)
+    index = alignment_index(bam, alignment_order)
     if getattr(eng, "_svx_index_id", None) != id(index):
         eng.set_alignment_index(index)
         eng._svx_index_id = id(index)

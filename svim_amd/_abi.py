@@ -364,7 +364,17 @@ class AlignmentsStats(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-GT_NAMES = ("./.", "0/0", "0/1", "1/1")      # codes of svx_vcf_inputs.gt / svx_genotype_fetch
+SVX_ALN_SORT, SVX_ALN_FILE_FLAGS = 1, 2      # svx_collect_keep_alignments_mode
+
+
+class AlignmentSortStats(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("t_key_ms", "t_sort_ms", "t_gather_ms")] + [("n_rows", C.c_int64), ("sorted", C.c_int32), ("key_bits", C.c_int32)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+GT_NAMES = ("./.", "0/0", "0/1", "1/1")     # codes of svx_vcf_inputs.gt / svx_genotype_fetch
 
 
 class AlnIndex(C.Structure):

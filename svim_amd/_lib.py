@@ -22,6 +22,7 @@ SYMBOLS = ["svx_ctx_create", "svx_ctx_destroy", "svx_last_error", "svx_version",
            "svx_cluster_count", "svx_cluster_fetch", "svx_cluster_set_ranks", "svx_cluster_abort_ranks", "svx_cluster_stream_positions",
            "svx_set_alignment_index", "svx_genotype",
            "svx_collect_keep_alignments", "svx_alignments_count", "svx_alignments_fetch", "svx_alignments_get_stats",
+           "svx_collect_keep_alignments_mode", "svx_alignments_permutation", "svx_alignments_get_sort_stats",
            "svx_genotype_resident", "svx_genotype_count", "svx_genotype_fetch", "svx_genotype_get_stats", "svx_vcf_use_resident_genotypes",
            "svx_cigar_indel", "svx_edit_distance", "svx_linkage_fcluster", "svx_pair_distances",
            "svx_bam_open", "svx_bam_close", "svx_bam_header", "svx_bam_read_batch", "svx_bam_read_names", "svx_bam_set_seq_filter", "svx_bam_rewind", "svx_bam_seek", "svx_bam_seek_region", "svx_bam_region_stats", "svx_bam_set_gpu_inflate", "svx_bam_gpu_inflate_stats",
@@ -914,13 +915,37 @@ class Engine(object):
         return out[:n]
 
     # ---- GENOTYPE from resident tables ----
-    def keep_alignments(self, on):
+    def keep_alignments(self, on, order="file", file_flags=False):
         """on: while accumulate() is on too, every collect() appends its batch's records to the alignment table resident in the context
-        (svx_collect_keep_alignments) - what genotype_resident() joins the candidates with"""
-        _check(self.L.svx_collect_keep_alignments(self.ctx, C.c_int(1 if on else 0)), "svx_collect_keep_alignments")
+        (svx_collect_keep_alignments) - what genotype_resident() joins the candidates with.
+        order="sort": the records may come in any order; the table is brought into coordinate order (svim_amd/bamsort.py, ties in append order) on the
+        device when it is first used, instead of being refused.  file_flags: a record marked SVX_FLAG_SKIP by the query-name front end keeps its own flag
+        and the end its CIGAR gives (svx_collect_keep_alignments_mode)"""
+        if order not in ("file", "sort"):
+            raise ValueError("order: 'file' or 'sort'")
+        flags = (_abi.SVX_ALN_SORT if order == "sort" else 0) | (_abi.SVX_ALN_FILE_FLAGS if file_flags else 0)
+        if flags == 0:
+            _check(self.L.svx_collect_keep_alignments(self.ctx, C.c_int(1 if on else 0)), "svx_collect_keep_alignments")
+        else:
+            _check(self.L.svx_collect_keep_alignments_mode(self.ctx, C.c_int(1 if on else 0), C.c_uint32(flags)), "svx_collect_keep_alignments_mode")
+
+    def alignments_permutation(self):
+        """the append position of every row of the resident alignment table (svx_alignments_permutation) -> uint32[n]; the identity when no finalisation
+        had to sort.  SvxError before the table has been finalised (the first genotype_resident() after an append does that)"""
+        n = C.c_int64()
+        _check(self.L.svx_alignments_count(self.ctx, C.byref(n)), "svx_alignments_count")
+        out = np.zeros(max(1, n.value), dtype=np.uint32)
+        _check(self.L.svx_alignments_permutation(self.ctx, ptr(out)), "svx_alignments_permutation")
+        return out[:n.value]
+
+    def alignment_sort_stats(self):
+        s = _abi.AlignmentSortStats()
+        _check(self.L.svx_alignments_get_sort_stats(self.ctx, C.byref(s)), "svx_alignments_get_sort_stats")
+        return s.as_dict()
 
     def alignments(self):
-        """the resident alignment table (svx_alignments_fetch) -> dict of numpy columns tid, pos, end, flag, mapq, read_id, in file order"""
+        """the resident alignment table (svx_alignments_fetch) -> dict of numpy columns tid, pos, end, flag, mapq, read_id, in the table's current order:
+        file (append) order, or coordinate order once a finalisation of keep_alignments(order="sort") has sorted it"""
         n = C.c_int64()
         _check(self.L.svx_alignments_count(self.ctx, C.byref(n)), "svx_alignments_count")
         cols = dict(tid=np.int32, pos=np.int32, end=np.int32, flag=np.uint16, mapq=np.uint8, read_id=np.int32)

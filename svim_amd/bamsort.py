@@ -48,11 +48,16 @@ class BamSortError(ValueError):
         self.code = code
 
 
+def coordinate_key(ref_id, pos, flag):
+    """the coordinate order's key from a record's fields (what SVIM_genotyping.AlignmentIndex(order="sort") and the resident alignment table sort by)"""
+    return (ref_id & 0xffffffff, (pos + 1) & 0xffffffff, flag & 16)
+
+
 def sort_key(body):
     """body: the bytes of one record behind its block_size field"""
     ref_id, pos = struct.unpack_from("<ii", body, 0)
     flag, = struct.unpack_from("<H", body, 14)
-    return (ref_id & 0xffffffff, (pos + 1) & 0xffffffff, flag & 16)
+    return coordinate_key(ref_id, pos, flag)
 
 
 def name_of(body):

@@ -180,7 +180,7 @@ struct svx_ctx {
     // GENOTYPE from resident tables: the alignment table svx_collect appends to while svx_collect_keep_alignments is on (alnindex.hip), the genotype columns
     // of the last svx_genotype_resident (genotype.hip), how many svx_combine calls the context has seen (the columns belong to one of them), and whether
     // svx_vcf source 0 reads the columns in place (svx_vcf_use_resident_genotypes)
-    struct AlnTable* aln = nullptr; bool keep_alignments = false;
+    struct AlnTable* aln = nullptr; bool keep_alignments = false; uint32_t aln_flags = 0;      // SVX_ALN_* of svx_collect_keep_alignments_mode
     struct GenoState* genores = nullptr; long long combine_calls = 0; bool vcf_resident_gt = false;
     DevBuf samp_meta, samp_table, samp_runs, samp_chain;    // consumption tables of the sampling walk; per-type stream positions
     int xr_rank = 0, xr_world = 1; svx_allgather_fn xr_fn = nullptr; void* xr_user = nullptr; bool xr_pending = false;   // svx_cluster_set_ranks

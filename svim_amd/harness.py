@@ -40,15 +40,21 @@ class BamPipeline(object):
     """reader thread || GPU thread over one BAM file; results stay resident in the engine (accumulated lists)."""
 
     def __init__(self, path, options, engine, threads=0, batch_records=200_000, mode="coordinate", sparse_seq=True, regions=None, gpu_inflate=None,
-                 device_decode=None, keep_alignments=False, build_index=False, index_format="bai", index=None, region_rule="overlap", merged_out=None):
+                 device_decode=None, keep_alignments=False, build_index=False, index_format="bai", index=None, region_rule="overlap", merged_out=None,
+                 alignment_order="file"):
         """path: one BAM file (or SAM text), or a list of them with merged_out=PATH: the files are merged into that file first (merge_bam; in query-name
         order when mode="queryname", so that the records of a read lie next to each other across the files) and read from it.
         regions: None (the whole file); [(virtual offset, last reference id)]: contig runs (svx_bam_seek); or coordinate regions (svim_amd/regions.py): region
         strings ("chr1:10,000,000-12,000,000"), (contig, beg, end) tuples (0-based, half-open) - parsed, normalised and planned from the file's index, read in
         file order - or planned reads (virtual offset, tid, beg, end) as regions.plan and harness.window_plan give them.  index: the .bai / .csi the plan comes
-        from - a path, its bytes, or None: <bam>.bai if present, else <bam>.csi.  region_rule: "overlap" (samtools view) or "start" (ownership by start)"""
+        from - a path, its bytes, or None: <bam>.bai if present, else <bam>.csi.  region_rule: "overlap" (samtools view) or "start" (ownership by start).
+        alignment_order (with keep_alignments): "file" - the records are in coordinate order, as genotyping has needed them so far; "sort" - they come in
+        any order (mode="queryname", SAM text from an aligner, an unsorted BAM in mode="coordinate") and the resident alignment table is brought into coordinate
+        order on the device when genotype() first uses it: the genotype columns are those of the coordinate pipeline over sort_bam(file)"""
         from .bamio import NativeBam
         from . import regions as _regions
+        if alignment_order not in ("file", "sort"):
+            raise ValueError("alignment_order: 'file' or 'sort'")
         if isinstance(path, (list, tuple)):                         # several files: merged on the device into merged_out first, the pipeline runs over that file
             path = _merged_input(path, merged_out, getattr(engine, "device", None) or 0, threads, order="queryname" if mode == "queryname" else "coordinate")
         coordinate_regions = regions is not None and any(isinstance(r, str) or len(r) != 2 for r in regions)
@@ -62,10 +68,12 @@ class BamPipeline(object):
             raise ValueError("index_format: bai, csi or auto")
         if build_index and regions is not None:
             raise ValueError("build_index needs the pass over the whole file (no regions): an index describes every record")
-        if keep_alignments and ((regions is not None and not coordinate_regions) or mode != "coordinate"):
+        if keep_alignments and ((regions is not None and not coordinate_regions) or (mode != "coordinate" and alignment_order != "sort")):
             raise ValueError("keep_alignments needs the whole coordinate-sorted file on one rank (contig shards and query-name order genotype through "
                              "SVIM_genotyping.genotype)")
         self.keep_alignments = bool(keep_alignments)
+        # (in query-name mode the front end marks what COLLECT does not analyse; GENOTYPE counts such records by their own flags)
+        self._keep_mode = dict(order=alignment_order, file_flags=alignment_order == "sort" and mode == "queryname")
         self.bam = NativeBam(path, threads=threads)
         dev = getattr(engine, "device", None)
         if device_decode is None:                                   # default on a GPU engine, either sort order (SVX_BAM_DEVICE_DECODE=0: host reader)
@@ -173,7 +181,7 @@ class BamPipeline(object):
                 ready.release()
 
         if self.keep_alignments:
-            eng.keep_alignments(True)                  # (before accumulate: a fresh accumulation empties the alignment table with the lists)
+            eng.keep_alignments(True, **self._keep_mode)     # (before accumulate: a fresh accumulation empties the alignment table with the lists)
         eng.accumulate(True)
         if self.build_index:
             self.index_bytes = None
@@ -232,7 +240,7 @@ class BamPipeline(object):
             free.release()
             th.join()
             if self.keep_alignments:
-                eng.keep_alignments(False)
+                eng.keep_alignments(False, **self._keep_mode)
             if self.build_index and not at_end:
                 bam.index_abort()                      # an interrupt, a failed read or collect: no index of a pass that did not end; the handle can rewind again
         t_collect_done = time.perf_counter()
